@@ -3,6 +3,7 @@
 the other BASELINE.json configurations as workloads of their own.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pointnet2|resgcn|tarnu|pointnet2_msg|randla]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one attack call over one batch of synthetic S3DIS-shaped input (pointnet2: NB_attack eps=0.05, alpha=2/255,
 40 PGD iterations on 8 rooms of 4096 points x 9 channels per GPU = BASELINE configs[1]), through the C ABI.  Inputs are
@@ -10,10 +11,15 @@ resident in HBM before the timed region.  Multi-GPU: one process per GPU; `pytho
 (torch.distributed.run children of a process that has not touched a GPU), or is started by torch.distributed.run; rooms
 are sharded by rank with NO data-path collective, one RCCL all-reduce of int64 counters after the timed region.
 
-Prints ONE JSON line (rank 0).  Every workload's line carries `roofline` (its dominant kernel, timed live with HIP events
-on the launch stream in one extra profiled attack after the timed region; `traffic` from the committed PMC passes of the
-same command) and, at N = 1, `cpu_baseline` (the CPU oracle on the host cores on a bounded sample; reported baseline
-only).  The default (pointnet2, N = 1) line also carries the other workloads, shortened, under `secondary`.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`metric`, `value`, `unit`, `ms_per_step`, ...).  With --full every workload's line also carries `roofline` (its dominant
+kernel, timed live with HIP events on the launch stream in one extra profiled attack after the timed region; `traffic`
+from the committed PMC passes of the same command), the checks and reference runs of its workload and, at N = 1,
+`cpu_baseline` (the CPU oracle on the host cores on a bounded sample; reported baseline only); the default (pointnet2,
+N = 1) full line also carries the other workloads, shortened, under `secondary`.
+
+--dump-outputs DIR writes what the timed path returned in its last step (the adversarial inputs of that step's rooms /
+cloud) as DIR/<name>.npy; the inputs are seeded, so the same arguments give the same inputs from run to run.
 """
 import argparse
 import json
@@ -364,7 +370,26 @@ def cpu_threads():
 
 
 def want_cpu(args, R):
-    return R.rank == 0 and R.world == 1 and not args.no_cpu_baseline      # reported baseline: rank 0 at N = 1 only
+    return args.full and R.rank == 0 and R.world == 1 and not args.no_cpu_baseline      # reported baseline: rank 0 at N = 1 only
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(args, R, **arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy (float64 stays, anything else becomes float32; rank r > 0 of a
+    multi-GPU run adds _rank<r>).  An array over its share of the 64 MB budget keeps a fixed, seeded sample of its rows."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BYTES // (len(arrays) * R.world)
+    for name, x in arrays.items():
+        a = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(args.dump_outputs, name + ("_rank%d" % R.rank if R.rank else "") + ".npy"), a)
 
 
 def main():
@@ -434,6 +459,13 @@ def main():
     ap.add_argument("--diag-build-ok", action="store_true",
                     help="tools/diag_*.sh only: run on a -DPSG_DIAG_BUILD library for its per-kernel times; the line then "
                          "carries value = null and invalid = 'diagnostic build'")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and extra measurements beside the headline figure: attack statistics, uncoalesced "
+                         "reference runs, the per-kernel roofline profile, API-level / whole-scene runs, the CPU-oracle baseline "
+                         "and, for the default workload at N = 1, the other workloads under `secondary` (--no-* trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -449,14 +481,15 @@ def main():
     runners = {"pointnet2": run_pointnet2, "resgcn": run_resgcn, "tarnu": run_tarnu, "pointnet2_msg": run_msg,
                "randla": run_randla}
     result = runners[args.workload](args, R)
-    if args.workload == "pointnet2" and R.world == 1 and not args.no_secondary:
-        # the other BASELINE configurations, shortened so that the default run stays within a few minutes: each a complete
+    if args.full and args.workload == "pointnet2" and R.world == 1 and not args.no_secondary:
+        # the other BASELINE configurations, shortened so that the full run stays within a few minutes: each a complete
         # line of its own (value, roofline, cpu_baseline) under "secondary"; `python bench.py --workload NAME` runs one alone
         import copy
         sec = {}
         for name, steps, warm in (("tarnu", 16, 8), ("resgcn", 24, 8), ("pointnet2_msg", 24, 8), ("randla", 48, 12)):
             a2 = copy.copy(args)
             a2.workload, a2.steps, a2.warmup, a2.cpu_seconds = name, steps, warm, min(args.cpu_seconds, 6.0)
+            a2.dump_outputs = None
             if name == "resgcn":
                 # behind the headline's and the NU line's streams a fourth ResGCN launch in flight costs more than it gives
                 # (14.2 against 14.7 - 14.8 rooms/s; alone: 14.9 with four, 14.75 with three): three here, four in the line of its own
@@ -552,25 +585,27 @@ def run_pointnet2(args, R):
     for i in range(n_warm):
         step(i)
     elapsed = R.timed(lambda: [step(i) for i in range(n_warm, n_all)])
+    dump_outputs(args, R, adv_images=d_adv[-1][-BATCH:])                           # the 8 rooms of the last timed step
 
-    # ---- attack statistics over the timed steps: clean vs adversarial accuracy / mIoU (RCCL all-reduce of counters)
-    clean = torch.zeros(3, 13, dtype=torch.int64, device="cuda")
-    adv = torch.zeros(3, 13, dtype=torch.int64, device="cuda")
-    evs = {}
-    for i in range(n_warm, min(n_all, n_warm + 2)):
-        ev = evs.setdefault(sizes[i], runtime.PN2Workspace(BATCH * sizes[i], NPOINT, 1))
-        ev_starts = d_starts[i][:1].contiguous()
-        for src, ctr in ((d_images[i], clean), (d_adv[i], adv)):
-            x0 = src.transpose(1, 2).contiguous()
-            ev.plan_build(x0, ev_starts, 1)
-            runtime.seg_stats(ev.forward(model, 0, x0), d_labels[i], counters=ctr)
-    if dist is not None:
-        dist.all_reduce(clean)
-        dist.all_reduce(adv)
-    clean, adv = clean.cpu().numpy().astype(np.float64), adv.cpu().numpy().astype(np.float64)
-    acc, adv_acc = clean[1].sum() / clean[0].sum(), adv[1].sum() / adv[0].sum()
-    miou = float(np.mean((clean[1] / (clean[2] + 1e-6))[clean[0] != 0]))
-    adv_miou = float(np.mean((adv[1] / (adv[2] + 1e-6))[adv[0] != 0]))
+    if args.full:
+        # ---- attack statistics over the timed steps: clean vs adversarial accuracy / mIoU (RCCL all-reduce of counters)
+        clean = torch.zeros(3, 13, dtype=torch.int64, device="cuda")
+        adv = torch.zeros(3, 13, dtype=torch.int64, device="cuda")
+        evs = {}
+        for i in range(n_warm, min(n_all, n_warm + 2)):
+            ev = evs.setdefault(sizes[i], runtime.PN2Workspace(BATCH * sizes[i], NPOINT, 1))
+            ev_starts = d_starts[i][:1].contiguous()
+            for src, ctr in ((d_images[i], clean), (d_adv[i], adv)):
+                x0 = src.transpose(1, 2).contiguous()
+                ev.plan_build(x0, ev_starts, 1)
+                runtime.seg_stats(ev.forward(model, 0, x0), d_labels[i], counters=ctr)
+        if dist is not None:
+            dist.all_reduce(clean)
+            dist.all_reduce(adv)
+        clean, adv = clean.cpu().numpy().astype(np.float64), adv.cpu().numpy().astype(np.float64)
+        acc, adv_acc = clean[1].sum() / clean[0].sum(), adv[1].sum() / adv[0].sum()
+        miou = float(np.mean((clean[1] / (clean[2] + 1e-6))[clean[0] != 0]))
+        adv_miou = float(np.mean((adv[1] / (adv[2] + 1e-6))[adv[0] != 0]))
 
     result = base_line("attacked rooms/sec (4096 pts, 40 PGD iters)", "rooms/s", BATCH * world * args.steps / elapsed, R, args,
                        elapsed, "NB non-targeted PGD (eps=0.05, alpha=2/255, 40 iters) on PointNet++ SSG sem_seg, batch=8 "
@@ -579,7 +614,7 @@ def run_pointnet2(args, R):
                         "device_batch_rooms": BATCH * max(sizes[n_warm:]),
                         "launch_sizes_in_steps": sizes[n_warm:], "launches_in_flight_per_gpu": conc,
                         "weights": "tests/golden/pn2_weights.npz (fitted fixture)"})
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- for reference: the same attack launched one 8-room step at a time (no coalescing), 2 in flight
         ref8 = None
         if G > 1 and not args.no_reference:
@@ -840,6 +875,7 @@ def run_resgcn(args, R):
     for i in range(n_warm):
         launch(i)
     elapsed = R.timed(lambda: [launch(i) for i in range(n_warm, n_all)])
+    dump_outputs(args, R, adv_images=d_adv[-1][-batch:])                          # the room(s) of the last timed step
     rooms_done = DB * n_launch * R.world
     # algorithmic FLOPs per PGD iteration per room (kNN distance GEMMs + split EdgeConv + fusion/prediction + transposes)
     n = NPOINT
@@ -855,7 +891,7 @@ def run_resgcn(args, R):
                         "knn": "matrix (round-1 path)" if os.environ.get("PSG_GCN_KNN") == "matrix" else "fused, matrix-free"})
     result["ms_per_step"] = elapsed / (DB * n_launch / batch) * 1e3
     result["tflops_effective"] = 2 * gmac * iters * rooms_done / elapsed / 1e3 if default_cfg else None
-    if R.rank == 0:
+    if R.rank == 0 and args.full:
         # ---- the same attack one step (batch rooms) per launch, for readers who want the number without coalescing
         if G > 1 and not args.no_reference:
             ws1 = [runtime.GCNWorkspace(batch, NPOINT, n_blocks, **cfg) for _ in range(conc)]
@@ -941,6 +977,7 @@ def run_msg(args, R):
     for i in range(n_warm):
         launch(i)
     elapsed = R.timed(lambda: [launch(i) for i in range(n_groups)])
+    dump_outputs(args, R, adv_images=pool[(n_groups - 1) % conc][3][-BATCH:])    # the 8 rooms of the last timed step
     rooms_done = DB * n_groups * R.world
     # algorithmic MACs per room per forward (the input-gradient pass has the same count)
     mac = 0
@@ -957,7 +994,7 @@ def run_msg(args, R):
     result["ms_per_step"] = elapsed / (DB * n_groups / BATCH) * 1e3
     result["tflops_effective"] = 2.0 * 2.0 * mac * ITERS * rooms_done / elapsed / 1e12
     result["gmac_per_room_forward"] = mac / 1e9
-    if R.rank == 0:
+    if R.rank == 0 and args.full:
         wss[0].prof_enable(True)
         launch(0)
         torch.cuda.synchronize()
@@ -1016,11 +1053,14 @@ def run_randla(args, R):
     def step(i, n_it=iters + 1, ws_list=wss, data=clouds, metric=metric):
         f, y = data[i % len(data)]
         with torch.cuda.stream(streams[i % conc]):
-            ws_list[i % conc].bim_attack(model, f, y, settings[metric][0], settings[metric][1], n_it, metric=metric)
+            return ws_list[i % conc].bim_attack(model, f, y, settings[metric][0], settings[metric][1], n_it, metric=metric)
 
     for i in range(n_warm):
         step(i)
-    elapsed = R.timed(lambda: [step(i) for i in range(n_warm, n_warm + n_launch)])
+    outs = []
+    elapsed = R.timed(lambda: outs.extend(step(i) for i in range(n_warm, n_warm + n_launch)))
+    dump_outputs(args, R, adv_cloud=outs[-1][-n_pts:])                             # the cloud of the last timed step
+    del outs
     clouds_done = G * n_launch * R.world
     # algorithmic MACs of one forward (the input-gradient pass has about the same count minus the xyz branch)
     mac = 0
@@ -1041,20 +1081,21 @@ def run_randla(args, R):
                        "tester_S3DIS.py:37,142-145) on RandLA-Net, 1 cloud x 40960 pts per step (BASELINE configs[4]); random-init "
                        "weights; network parity UNPINNED (TF1 reference)" % (metric, settings[metric][0], settings[metric][1], iters, iters + 1),
                        {"steps_coalesced_per_launch": G, "launches_in_flight_per_gpu": conc, "distance_metric": metric})
-    other = "l_inf" if metric == "l_2" else "l_2"
-    n_o = min(n_launch, conc)                                      # a few launches of the other metric, same shape
-    for i in range(n_o):
-        step(i, metric=other)                                      # (its hipGraph is captured here, outside the timing)
-    el_o = R.timed(lambda: [step(i, metric=other) for i in range(n_o)])
-    for i in range(min(n_launch, conc)):
-        step(i)                                                    # back to the headline metric's graph for what follows
-    result[other] = {"value": G * n_o * R.world / el_o, "unit": "clouds/s", "note": "magnitude=%g, alpha=%g, %d launches of %d clouds"
-                     % (settings[other][0], settings[other][1], n_o, G)}
+    if args.full:
+        other = "l_inf" if metric == "l_2" else "l_2"
+        n_o = min(n_launch, conc)                                  # a few launches of the other metric, same shape
+        for i in range(n_o):
+            step(i, metric=other)                                  # (its hipGraph is captured here, outside the timing)
+        el_o = R.timed(lambda: [step(i, metric=other) for i in range(n_o)])
+        for i in range(min(n_launch, conc)):
+            step(i)                                                # back to the headline metric's graph for what follows
+        result[other] = {"value": G * n_o * R.world / el_o, "unit": "clouds/s", "note": "magnitude=%g, alpha=%g, %d launches of %d "
+                         "clouds" % (settings[other][0], settings[other][1], n_o, G)}
     result["ms_per_step"] = elapsed / (G * n_launch) * 1e3
     result["ms_per_iteration"] = elapsed / (G * n_launch) / (iters + 1) * 1e3
     result["gmac_per_cloud_forward"] = mac / 1e9
     result["tflops_effective"] = 2.0 * 2.0 * mac * (iters + 1) * clouds_done / elapsed / 1e12
-    if R.rank == 0:
+    if R.rank == 0 and args.full:
         if G > 1 and not args.no_reference:
             # ---- the same attacks one cloud per launch (the reference's val_batch_size = 1)
             ws1 = [network.RandLAWorkspace(n_pts) for _ in range(conc)]
@@ -1162,16 +1203,16 @@ def run_tarnu(args, R):
     32 rows against ONE row's mask count (target.py:105-121), so it fires after the first optimiser step: that quirk is
     kept, and the line is reported for completeness (`batch32_quirk` of the default run)."""
     result = tarnu_measure(args, R, args.nu_mode)
-    if args.nu_mode == "per-room" and R.rank == 0 and R.world == 1 and not args.no_reference:
+    if args.full and args.nu_mode == "per-room" and R.rank == 0 and R.world == 1 and not args.no_reference:
         import copy
         a1 = copy.copy(args)
-        a1.steps, a1.warmup, a1.no_cpu_baseline = 3, 1, True
+        a1.steps, a1.warmup, a1.no_cpu_baseline, a1.dump_outputs = 3, 1, True, None
         q = tarnu_measure(a1, R, "per-room-calls", with_roofline=False)
         result["uncoalesced_reference"] = {"value": q["value"], "unit": "rooms/s",
                                            "note": "one call per room (batches of one), %d calls in flight" % q["config"]["attacks_in_flight"]}
         import copy
         a2 = copy.copy(args)
-        a2.steps, a2.warmup, a2.no_cpu_baseline = 3, 1, True
+        a2.steps, a2.warmup, a2.no_cpu_baseline, a2.dump_outputs = 3, 1, True, None
         q = tarnu_measure(a2, R, "batch32", with_roofline=False)
         result["batch32_quirk"] = {k: q[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "optimizer_steps_per_attack",
                                                      "room_steps_per_sec") if k in q}
@@ -1229,6 +1270,7 @@ def tarnu_measure(args, R, mode, with_roofline=True):
         net._packed()
     d_images = [torch.from_numpy(np.ascontiguousarray(r.transpose(0, 2, 1))).cuda() for r in rooms]
     opt_steps, exits, lock = [0], [0], threading.Lock()
+    last_outs = {}                                              # first room -> output, of the calls of the last group
 
     def attack(job, slot):
         step, b0, nb = job
@@ -1246,6 +1288,8 @@ def tarnu_measure(args, R, mode, with_roofline=True):
         with lock:
             opt_steps[0] += int(steps_run.sum())
             exits[0] += int((steps_run < cap).sum())
+            if step == len(g_sizes) - 1:
+                last_outs[b0] = out
         return out
 
     def run(lo, hi):
@@ -1266,6 +1310,9 @@ def tarnu_measure(args, R, mode, with_roofline=True):
     torch.cuda.synchronize()
     opt_steps[0], exits[0] = 0, 0
     elapsed = R.timed(lambda: run(n_warm_g, len(g_sizes)))
+    # the rooms of the last timed step (the last per_step rooms of the last group)
+    if args.dump_outputs:
+        dump_outputs(args, R, adv_images=torch.cat([last_outs[b] for b in sorted(last_outs)])[-per_step:])
     total_opt, total_exit = R.sum(opt_steps[0]), R.sum(exits[0])
     n_attacks = (per_step if per_room else 1) * args.steps * R.world
     rooms_per_attack = 1 if per_room else per_step
@@ -1283,7 +1330,7 @@ def tarnu_measure(args, R, mode, with_roofline=True):
     result.update({"optimizer_steps_per_sec": total_opt / elapsed, "optimizer_steps_run": int(total_opt),
                    "optimizer_steps_per_attack": total_opt / n_attacks, "attacks_that_reached_the_target": int(total_exit),
                    "attacks": int(n_attacks), "room_steps_per_sec": rooms_per_attack * total_opt / elapsed})
-    if R.rank == 0 and with_roofline:
+    if R.rank == 0 and with_roofline and args.full:
         # roofline: the network kernels of one more attack, HIP events on its launch stream
         ws = nets[0]._workspace(rooms_per_call, NPOINT, nu_mod.CHUNK + 1)
         ws.prof_enable(True)

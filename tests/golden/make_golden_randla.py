@@ -5,6 +5,7 @@
 
 Cases: a structured synthetic room cloud (4096 points: planes, so near-ties occur), uniform noise, the k = 1 up-sampling
 query of a sub-sampled cloud, and a cloud with duplicated points (exact ties).  Stored: inputs + the reference's indices.
+randla_knn_lib.npz: uniform clouds at k = 1, 3 and 16, the same from the same library.
 """
 import os
 import sys
@@ -37,6 +38,12 @@ def main():
     out["d_support"], out["d_idx"] = dup, randla.knn_ref(dup, dup, 16)
     np.savez_compressed(os.path.join(HERE, "randla_knn.npz"), **out)
     print({k: v.shape for k, v in out.items() if hasattr(v, "shape")})
+    # the inputs of tests/test_randla_knn.py::test_oracle_vs_reference_library and the library's answers at k = 1, 3, 16
+    rng = np.random.default_rng(17)
+    lib = {"support": rng.random((2, 2500, 3), dtype=np.float32), "query": rng.random((2, 600, 3), dtype=np.float32)}
+    for k in (1, 3, 16):
+        lib["idx_k%d" % k] = randla.knn_ref(lib["support"], lib["query"], k)
+    np.savez_compressed(os.path.join(HERE, "randla_knn_lib.npz"), **lib)
 
 
 if __name__ == "__main__":

@@ -1,8 +1,9 @@
 """RandLA-Net pipeline k-NN (first piece).
 
 CPU: the numpy oracle (oracle/randla.py: knn_brute) against tests/golden/randla_knn.npz, which holds the output of
-the reference's own nanoflann code (compiled from its sources into oracle/_ref by `make -C oracle ref`), and against
-that library directly when it is present.  GPU: psg_knn_points through the C ABI against the same fixtures, against the
+the reference's own nanoflann code (compiled from its sources into oracle/_ref by `make -C oracle ref`), against that
+library's stored answers on uniform clouds (tests/golden/randla_knn_lib.npz), and against the library directly when it
+is present.  GPU: psg_knn_points through the C ABI against the same fixtures, against the
 oracle, and at the reference's full size (40 960 points) through properties.
 
 Equality bar: the sorted squared distances of the returned neighbours are bit-equal and the index sets are equal;
@@ -15,6 +16,7 @@ import pytest
 from oracle import randla
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "randla_knn.npz")
+GOLD_LIB = os.path.join(os.path.dirname(__file__), "golden", "randla_knn_lib.npz")
 
 
 @pytest.fixture(scope="module")
@@ -60,13 +62,16 @@ def test_oracle_upsample_index_vs_reference_fixture(fx):
     assert_same_knn(randla.knn_brute(sub, room, 1), fx["c_idx"], sub, room)
 
 
-@pytest.mark.skipif(not randla.have_ref(), reason="oracle/_ref/libknn_ref.so not built (make -C oracle ref)")
 def test_oracle_vs_reference_library():
-    rng = np.random.default_rng(17)
-    s = rng.random((2, 2500, 3), dtype=np.float32)
-    q = rng.random((2, 600, 3), dtype=np.float32)
+    """Uniform clouds at k = 1, 3, 16 against the library's answers stored in tests/golden/randla_knn_lib.npz, and against
+    the library itself when oracle/_ref/libknn_ref.so is built."""
+    lib = dict(np.load(GOLD_LIB))
+    s, q = lib["support"], lib["query"]
     for k in (1, 3, 16):
-        assert_same_knn(randla.knn_brute(s, q, k), randla.knn_ref(s, q, k), s, q)
+        got = randla.knn_brute(s, q, k)
+        assert_same_knn(got, lib["idx_k%d" % k], s, q)
+        if randla.have_ref():
+            assert_same_knn(got, randla.knn_ref(s, q, k), s, q)
 
 
 def test_pyramid_shapes():

@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r03
 mkdir -p $O
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rs -o rs -- python3 bench.py --workload randla --steps 8 --warmup 0 --concurrency 1 --randla-iters ${ITERS:-20} --no-cpu-baseline --no-reference > $O/rla_stats.log 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rs -o rs -- python3 bench.py --full --workload randla --steps 8 --warmup 0 --concurrency 1 --randla-iters ${ITERS:-20} --no-cpu-baseline --no-reference > $O/rla_stats.log 2>&1 || exit 1
 cp $(find $O/rs -name '*kernel_stats.csv' | head -1) $O/rla_stats_kernel_stats.csv
 rm -rf $O/rs
 python3 - <<PY
