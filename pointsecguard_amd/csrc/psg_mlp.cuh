@@ -263,6 +263,124 @@ __device__ __forceinline__ f32x16 tile_mac4(const float4 *__restrict__ w, int k8
     return acc;
 }
 
+// Compile-time switch of the paired k-loop below (-DPSG_MLP_PAIRS=0: every layer deals single tiles, as before).
+#ifndef PSG_MLP_PAIRS
+#define PSG_MLP_PAIRS 1
+#endif
+
+// Two 32x32 output tiles that share the weight operand: point blocks pb and pb + 1 of one output block, i.e. activation
+// pointers bptr and bptr + 256 floats.  One weight stream feeds both accumulators: per 1 KiB weight chunk one
+// global_load_dwordx4, two ds_read_b128 and 8 MFMAs (tile_mac4: one load, one read, 4 MFMAs), so a pair pays one ring fill,
+// one weight stream and one loop overhead where two single tiles paid two.  Each accumulator sees exactly the k-chunk order
+// of tile_mac4: both results are bit-identical to two tile_mac4 calls.
+//
+// Same fixed ring v[64:87] as tile_mac4: the four weight slots v[64:79], and ONE activation buffer per point block instead
+// of tile_mac4's two for its one block (Xa = v[80:83], Xb = v[84:87]).  Per chunk: wait for Xa, 4 MFMAs on acc0, re-read Xa
+// for the next chunk (it lands under acc1's 4 MFMAs), wait for Xb, 4 MFMAs on acc1, weight re-load, re-read Xb.  Overwriting
+// an operand of an MFMA just issued is what tile_mac4 does with its weight slots and activation buffers already.  The ring
+// stays 24 registers; the pair adds only the second accumulator.
+template <int BLK, bool FLIP>
+__device__ __forceinline__ void tile_mac4x2(const float4 *__restrict__ w, int k8n, const float *__restrict__ bptr,
+                                            f32x16 &acc0, f32x16 &acc1)
+{
+    unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) const float *)bptr;
+    const float4 *wp = w;
+    int n_v = (k8n >> 2) - 1;             // (trip count: laundered and moved by the compiler's readfirstlane, see tile_mac4)
+    asm volatile("" : "+v"(n_v));
+    int n = __builtin_amdgcn_readfirstlane(n_v);
+    const unsigned long long step = 4096ull;
+    constexpr int S1 = BLK * 4, S2 = 2 * BLK * 4, S3 = 3 * BLK * 4, S4 = 4 * BLK * 4, PB1 = 32 * 8 * 4;
+#define PSG_X2_MFA(wa, xa) "v_mfma_f32_32x32x2_f32 %[a0], " wa ", " xa ", %[a0]\n\t"
+#define PSG_X2_MFB(wa, xa) "v_mfma_f32_32x32x2_f32 %[a1], " wa ", " xa ", %[a1]\n\t"
+    // four MFMAs of one accumulator; O0 / O1 pick the first / second MFMA source out of (weight, activation) register pairs
+#define PSG_X2_4(MF, w0, w1, w2, w3, x0, x1, x2, x3) MF(w0, x0) MF(w1, x1) MF(w2, x2) MF(w3, x3)
+#define PSG_X2_BODY(O0, O1)                                                                                                  \
+    "global_load_dwordx4 v[64:67], %[wp], off\n\t"                                                                          \
+    "global_load_dwordx4 v[68:71], %[wp], off offset:1024\n\t"                                                              \
+    "global_load_dwordx4 v[72:75], %[wp], off offset:2048\n\t"                                                              \
+    "global_load_dwordx4 v[76:79], %[wp], off offset:3072\n\t"                                                              \
+    "ds_read_b128 v[80:83], %[lds]\n\t"                                                                                     \
+    "ds_read_b128 v[84:87], %[lds] offset:%[p1]\n\t"                                                                        \
+    "s_cmp_eq_u32 %[n], 0\n\t"                                                                                              \
+    "s_cbranch_scc1 L_psg_x2_last_%=\n\t"                                                                                   \
+    "L_psg_x2_loop_%=:\n\t"                                                                                                 \
+    "v_lshl_add_u64 %[wp], %[wp], 0, %[step]\n\t"                                                                           \
+    "s_waitcnt vmcnt(3) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v64, v80), O0(v65, v81), O0(v66, v82), O0(v67, v83), O1(v64, v80), O1(v65, v81), O1(v66, v82), O1(v67, v83)) \
+    "ds_read_b128 v[80:83], %[lds] offset:%[s1]\n\t"                                                                        \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v64, v84), O0(v65, v85), O0(v66, v86), O0(v67, v87), O1(v64, v84), O1(v65, v85), O1(v66, v86), O1(v67, v87)) \
+    "global_load_dwordx4 v[64:67], %[wp], off\n\t"                                                                          \
+    "ds_read_b128 v[84:87], %[lds] offset:%[s1p]\n\t"                                                                       \
+    "s_waitcnt vmcnt(3) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v68, v80), O0(v69, v81), O0(v70, v82), O0(v71, v83), O1(v68, v80), O1(v69, v81), O1(v70, v82), O1(v71, v83)) \
+    "ds_read_b128 v[80:83], %[lds] offset:%[s2]\n\t"                                                                        \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v68, v84), O0(v69, v85), O0(v70, v86), O0(v71, v87), O1(v68, v84), O1(v69, v85), O1(v70, v86), O1(v71, v87)) \
+    "global_load_dwordx4 v[68:71], %[wp], off offset:1024\n\t"                                                              \
+    "ds_read_b128 v[84:87], %[lds] offset:%[s2p]\n\t"                                                                       \
+    "s_waitcnt vmcnt(3) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v72, v80), O0(v73, v81), O0(v74, v82), O0(v75, v83), O1(v72, v80), O1(v73, v81), O1(v74, v82), O1(v75, v83)) \
+    "ds_read_b128 v[80:83], %[lds] offset:%[s3]\n\t"                                                                        \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v72, v84), O0(v73, v85), O0(v74, v86), O0(v75, v87), O1(v72, v84), O1(v73, v85), O1(v74, v86), O1(v75, v87)) \
+    "global_load_dwordx4 v[72:75], %[wp], off offset:2048\n\t"                                                              \
+    "ds_read_b128 v[84:87], %[lds] offset:%[s3p]\n\t"                                                                       \
+    "s_waitcnt vmcnt(3) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v76, v80), O0(v77, v81), O0(v78, v82), O0(v79, v83), O1(v76, v80), O1(v77, v81), O1(v78, v82), O1(v79, v83)) \
+    "ds_read_b128 v[80:83], %[lds] offset:%[s4]\n\t"                                                                        \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v76, v84), O0(v77, v85), O0(v78, v86), O0(v79, v87), O1(v76, v84), O1(v77, v85), O1(v78, v86), O1(v79, v87)) \
+    "global_load_dwordx4 v[76:79], %[wp], off offset:3072\n\t"                                                              \
+    "ds_read_b128 v[84:87], %[lds] offset:%[s4p]\n\t"                                                                       \
+    "v_add_u32 %[lds], %[s4], %[lds]\n\t"                                                                                   \
+    "s_sub_u32 %[n], %[n], 1\n\t"                                                                                           \
+    "s_cmp_lg_u32 %[n], 0\n\t"                                                                                              \
+    "s_cbranch_scc1 L_psg_x2_loop_%=\n\t"                                                                                   \
+    "L_psg_x2_last_%=:\n\t"                                                                                                 \
+    "s_waitcnt vmcnt(3) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v64, v80), O0(v65, v81), O0(v66, v82), O0(v67, v83), O1(v64, v80), O1(v65, v81), O1(v66, v82), O1(v67, v83)) \
+    "ds_read_b128 v[80:83], %[lds] offset:%[s1]\n\t"                                                                        \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v64, v84), O0(v65, v85), O0(v66, v86), O0(v67, v87), O1(v64, v84), O1(v65, v85), O1(v66, v86), O1(v67, v87)) \
+    "ds_read_b128 v[84:87], %[lds] offset:%[s1p]\n\t"                                                                       \
+    "s_waitcnt vmcnt(2) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v68, v80), O0(v69, v81), O0(v70, v82), O0(v71, v83), O1(v68, v80), O1(v69, v81), O1(v70, v82), O1(v71, v83)) \
+    "ds_read_b128 v[80:83], %[lds] offset:%[s2]\n\t"                                                                        \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v68, v84), O0(v69, v85), O0(v70, v86), O0(v71, v87), O1(v68, v84), O1(v69, v85), O1(v70, v86), O1(v71, v87)) \
+    "ds_read_b128 v[84:87], %[lds] offset:%[s2p]\n\t"                                                                       \
+    "s_waitcnt vmcnt(1) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v72, v80), O0(v73, v81), O0(v74, v82), O0(v75, v83), O1(v72, v80), O1(v73, v81), O1(v74, v82), O1(v75, v83)) \
+    "ds_read_b128 v[80:83], %[lds] offset:%[s3]\n\t"                                                                        \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v72, v84), O0(v73, v85), O0(v74, v86), O0(v75, v87), O1(v72, v84), O1(v73, v85), O1(v74, v86), O1(v75, v87)) \
+    "ds_read_b128 v[84:87], %[lds] offset:%[s3p]\n\t"                                                                       \
+    "s_waitcnt vmcnt(0) lgkmcnt(1)\n\t"                                                                                     \
+    PSG_X2_4(PSG_X2_MFA, O0(v76, v80), O0(v77, v81), O0(v78, v82), O0(v79, v83), O1(v76, v80), O1(v77, v81), O1(v78, v82), O1(v79, v83)) \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                              \
+    PSG_X2_4(PSG_X2_MFB, O0(v76, v84), O0(v77, v85), O0(v78, v86), O0(v79, v87), O1(v76, v84), O1(v77, v85), O1(v78, v86), O1(v79, v87)) \
+    "s_nop 15\n\t"                                                                                                          \
+    "s_nop 3\n\t"
+#define PSG_X2_W(w, x) #w
+#define PSG_X2_X(w, x) #x
+#define PSG_X2_OPERANDS                                                                                                     \
+    : [a0] "+v"(acc0), [a1] "+v"(acc1), [wp] "+v"(wp), [lds] "+v"(lds), [n] "+s"(n)                                         \
+    : [step] "s"(step), [p1] "n"(PB1), [s1] "n"(S1), [s2] "n"(S2), [s3] "n"(S3), [s4] "n"(S4), [s1p] "n"(S1 + PB1),         \
+      [s2p] "n"(S2 + PB1), [s3p] "n"(S3 + PB1), [s4p] "n"(S4 + PB1)                                                         \
+    : "memory", "scc", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77",     \
+      "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87"
+    if (FLIP) asm volatile(PSG_X2_BODY(PSG_X2_X, PSG_X2_W) PSG_X2_OPERANDS);   // D[point][channel]: activation first
+    else asm volatile(PSG_X2_BODY(PSG_X2_W, PSG_X2_X) PSG_X2_OPERANDS);        // D[channel][point]: weight first
+#undef PSG_X2_OPERANDS
+#undef PSG_X2_X
+#undef PSG_X2_W
+#undef PSG_X2_BODY
+#undef PSG_X2_4
+#undef PSG_X2_MFB
+#undef PSG_X2_MFA
+}
+
 // The 18 wait states between a 16-pass MFMA and the first vector instruction that touches its result, spelled out for
 // the places where the COMPILER's MFMAs (the K tails below) are followed by a consumer inside inline assembly (relu_bits):
 // the hazard recognizer counts wait states only between instructions it can see, so it emitted v_mfma x 4, v_cmp_lt_f32 on
@@ -317,6 +435,24 @@ __device__ __forceinline__ f32x16 tile_mac(const float4 *__restrict__ w, int k8n
     return acc;
 }
 
+// tile_mac for the pair (pb, pb + 1) of tile_mac4x2: the same k-chunk order per accumulator, so each result equals its
+// tile_mac.  One fence behind the tail covers both accumulators (it reads both: no MFMA of the tail can sink below it).
+template <int BLK, bool FLIP>
+__device__ __forceinline__ void tile_mac_x2(const float4 *__restrict__ w, int k8n, const float *__restrict__ bptr,
+                                            f32x16 &acc0, f32x16 &acc1)
+{
+    const int k4 = k8n & ~3;
+    if (k4) tile_mac4x2<BLK, FLIP>(w, k4, bptr, acc0, acc1);
+    for (int k8 = k4; k8 < k8n; ++k8) {
+        const float4 a = w[(size_t)k8 * 64];
+        const float4 b0 = *(const float4 *)(bptr + (size_t)k8 * BLK);
+        const float4 b1 = *(const float4 *)(bptr + (size_t)k8 * BLK + 32 * 8);
+        acc0 = mfma4<FLIP>(a, b0, acc0);
+        acc1 = mfma4<FLIP>(a, b1, acc1);
+    }
+    if (k8n > k4) asm volatile("s_nop 15\n\ts_nop 1" : "+v"(acc0), "+v"(acc1));
+}
+
 // write a D[channel][point] accumulator tile back to LDS: 4 x ds_write_b128 per lane
 template <int P>
 __device__ __forceinline__ void store_tile(float *__restrict__ out, int mb, int pcol, int h, const f32x16 &v)
@@ -338,6 +474,34 @@ __device__ __forceinline__ void store_tile(float *__restrict__ out, int mb, int 
 // with fewer tiles than waves (the 13-class head: one tile) or a ragged count (10 tiles on 8 waves) would otherwise
 // always load the same SIMDs of the CU.
 
+// Pairs.  Where a workgroup has two or more point blocks, a wave can take the tiles (mb, pb) and (mb, pb + 1) as one pair
+// on one weight stream (tile_mac4x2).  A layer deals pairs instead of tiles when every wave gets the same number of them
+// and they fit its MAXT tiles; otherwise (fewer pairs than waves, a ragged count) it deals single tiles as before.  Either
+// way every tile's result and its mask slot (indexed by the tile, not by the wave) are the same, and a layer that deals
+// pairs has no partial round, so layer_bwd's K-split never applied to it.
+template <int P, int NW, int MAXT>
+__device__ __forceinline__ bool deal_pairs(int ntask)
+{
+    constexpr int PB = P / 32;
+    if constexpr (!PSG_MLP_PAIRS || PB < 2 || (PB & 1) || MAXT < 2) return false;
+    const int np = ntask >> 1;
+    return np >= NW && np % NW == 0 && (np / NW) * 2 <= MAXT;
+}
+
+// bias, ReLU and mask bits of one forward tile (the bias added behind the k-loop, in this order: see layer_fwd)
+__device__ __forceinline__ void fwd_epilogue(f32x16 &c, const float4 &bq0, const float4 &bq1, const float4 &bq2,
+                                             const float4 &bq3, const FwdLayer &L, size_t mask_slot)
+{
+    c[0] += bq0.x; c[1] += bq0.y; c[2] += bq0.z; c[3] += bq0.w;
+    c[4] += bq1.x; c[5] += bq1.y; c[6] += bq1.z; c[7] += bq1.w;
+    c[8] += bq2.x; c[9] += bq2.y; c[10] += bq2.z; c[11] += bq2.w;
+    c[12] += bq3.x; c[13] += bq3.y; c[14] += bq3.z; c[15] += bq3.w;
+    if (L.relu) {
+        const unsigned m = relu_bits(c);
+        if (L.mask) L.mask[mask_slot] = (uint16_t)m;
+    }
+}
+
 // Forward layer: buf[m][p] <- act(W buf[:, p] + b).
 template <int P, int NW, int MAXT>
 __device__ __forceinline__ void layer_fwd(const FwdLayer &L, float *__restrict__ buf, size_t wg_linear)
@@ -349,6 +513,41 @@ __device__ __forceinline__ void layer_fwd(const FwdLayer &L, float *__restrict__
     const int ntask = L.mb * PB;
     const int first = (wave + (int)(wg_linear & (NW - 1))) & (NW - 1);
     f32x16 acc[MAXT];
+    if (deal_pairs<P, NW, MAXT>(ntask)) {
+        constexpr int HP = PB / 2 > 0 ? PB / 2 : 1, NP = MAXT / 2;   // pairs per output block, pairs per wave at most
+        const int npair = ntask >> 1;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pr = first + i * NW;
+            if (pr < npair) {
+                const int mb = pr / HP, pb = 2 * (pr - mb * HP), task = mb * PB + pb;
+                const float4 *bp = (const float4 *)(L.bias + mb * 32 + 4 * h);
+                const float4 bq0 = bp[0], bq1 = bp[2], bq2 = bp[4], bq3 = bp[6];
+                f32x16 c0, c1;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; }
+                tile_mac_x2<BLK, false>(L.w + (size_t)mb * L.k8 * 64 + lane, L.k8, buf + (pb * 32 + j) * 8 + 4 * h, c0, c1);
+                // (32-bit slot arithmetic, as in layer_bwd's pair path: the masks hold far fewer than 2^32 entries, and 64-bit
+                // per-lane slot addresses for two tiles were what pushed fp_fwd_kernel<64> into scratch)
+                const unsigned slot = ((unsigned)wg_linear * (unsigned)ntask + (unsigned)task) * 64u + (unsigned)lane;
+                fwd_epilogue(c0, bq0, bq1, bq2, bq3, L, slot);
+                fwd_epilogue(c1, bq0, bq1, bq2, bq3, L, slot + 64u);
+                acc[2 * i] = c0;
+                acc[2 * i + 1] = c1;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pr = first + i * NW;
+            if (pr < npair) {
+                const int mb = pr / HP, pb = 2 * (pr - mb * HP);
+                store_tile<P>(buf, mb, pb * 32 + j, h, acc[2 * i]);
+                store_tile<P>(buf, mb, pb * 32 + 32 + j, h, acc[2 * i + 1]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < MAXT; ++i) {
         const int task = first + i * NW;
@@ -363,14 +562,7 @@ __device__ __forceinline__ void layer_fwd(const FwdLayer &L, float *__restrict__
 #pragma unroll
             for (int r = 0; r < 16; ++r) c[r] = 0.0f;
             c = tile_mac<BLK, false>(L.w + (size_t)mb * L.k8 * 64 + lane, L.k8, buf + (pb * 32 + j) * 8 + 4 * h, c);
-            c[0] += bq0.x; c[1] += bq0.y; c[2] += bq0.z; c[3] += bq0.w;
-            c[4] += bq1.x; c[5] += bq1.y; c[6] += bq1.z; c[7] += bq1.w;
-            c[8] += bq2.x; c[9] += bq2.y; c[10] += bq2.z; c[11] += bq2.w;
-            c[12] += bq3.x; c[13] += bq3.y; c[14] += bq3.z; c[15] += bq3.w;
-            if (L.relu) {
-                const unsigned m = relu_bits(c);
-                if (L.mask) L.mask[(wg_linear * ntask + task) * 64 + lane] = (uint16_t)m;
-            }
+            fwd_epilogue(c, bq0, bq1, bq2, bq3, L, (wg_linear * ntask + task) * 64 + lane);
             acc[i] = c;
         }
     }
@@ -413,6 +605,43 @@ __device__ __forceinline__ void layer_bwd(const BwdLayer &L, float *__restrict__
     const int j = lane & 31, h = lane >> 5;
     const int ntask = L.mb * PB;
     const int first = (wave + (int)(wg_linear & (NW - 1))) & (NW - 1);
+    if (deal_pairs<P, NW, MAXT>(ntask)) {
+        constexpr int HP = PB / 2 > 0 ? PB / 2 : 1, NP = MAXT / 2;
+        const int npair = ntask >> 1;
+        f32x16 acc[MAXT];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pr = first + i * NW;
+            if (pr < npair) {
+                const int mb = pr / HP, pb = 2 * (pr - mb * HP), task = mb * PB + pb;
+                unsigned m0 = 0xFFFFu, m1 = 0xFFFFu;
+                if (L.mask) {
+                    const unsigned slot = ((unsigned)wg_linear * (unsigned)ntask + (unsigned)task) * 64u + (unsigned)lane;
+                    m0 = L.mask[slot];
+                    m1 = L.mask[slot + 64u];
+                }
+                f32x16 c0, c1;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; }
+                tile_mac_x2<BLK, false>(L.w + (size_t)mb * L.k8 * 64 + lane, L.k8, buf + (pb * 32 + j) * 8 + 4 * h, c0, c1);
+                apply_bits(c0, m0);
+                apply_bits(c1, m1);
+                acc[2 * i] = c0;
+                acc[2 * i + 1] = c1;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pr = first + i * NW;
+            if (pr < npair) {
+                const int mb = pr / HP, pb = 2 * (pr - mb * HP);
+                store_tile<P>(buf, mb, pb * 32 + j, h, acc[2 * i]);
+                store_tile<P>(buf, mb, pb * 32 + 32 + j, h, acc[2 * i + 1]);
+            }
+        }
+        return;
+    }
     // split of the last, partial round
     const int full = ntask / NW, rem = ntask - full * NW;
     int per = 1, gsz = 1;                       // waves per left-over tile, K slices actually used

@@ -608,8 +608,12 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
 // (level 2), act[6] = fp2 out (level 1)
 inline int fp_out_slot(int lvl) { return 7 - lvl; }          // lvl 3 -> 4, 2 -> 5, 1 -> 6
 inline int fp_in2_slot(int lvl) { return lvl == 3 ? 3 : fp_out_slot(lvl + 1); }
-template <int LVL> struct FpCfg { static constexpr int P = 32, NW = 8; };
-template <> struct FpCfg<0> { static constexpr int P = 32, NW = 4; };
+// P = points per workgroup.  fp1 + head runs 64 points (two point blocks) where the level's point count allows it, so that
+// its 128-wide layers deal PAIRS of tiles on one weight stream (psg_mlp.cuh: tile_mac4x2, deal_pairs); fp2 - fp4 stay at 32
+// (their backward's staged gather, fp_bwd_gather_rows, is written for one point block).  Forward and backward must agree on
+// P: it decides the ReLU mask layout; both take it from the level's point count.
+template <int LVL> struct FpCfg { static constexpr int P = 32, P2 = 32, NW = 8; };
+template <> struct FpCfg<0> { static constexpr int P = 32, P2 = PSG_MLP_PAIRS ? 64 : 32, NW = 4; };
 
 // PSG_FP1_WAVE=1 selects the wave-private fp1 + head kernels (psg_chain.cuh) instead of the workgroup-cooperative
 // ones.  Measured on MI355X at a 32-room device batch: forward 193 vs 193 us, backward 211 vs 189 us, so the
@@ -708,10 +712,10 @@ int run_pw_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
     return PSG_OK;
 }
 
-template <int LVL>
-int run_fp_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStream_t st)
+template <int LVL, int P>
+int run_fp_fwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStream_t st)
 {
-    constexpr int P = FpCfg<LVL>::P, NW = FpCfg<LVL>::NW;
+    constexpr int NW = FpCfg<LVL>::NW;
     const ArchDesc &A = *m->arch;
     const int B = ws->B, N = ws->Nl[LVL], S = ws->Nl[LVL + 1];
     const size_t prob = (size_t)fwd * B;
@@ -783,13 +787,13 @@ int run_fp_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStream
         // a streamed first layer holds at most 64 blocks of its input at a time (fp_fwd_kernel<.., BIG>)
         const int k8 = (big && i == 0) ? std::min(a.layer[i].k8, 64) : a.layer[i].k8;
         blocks = std::max(blocks, layer_blocks(k8, a.layer[i].mb));
-        if (a.layer[i].mb * (P / 32) > NW) {
+        if (a.layer[i].mb > NW) {     // (P / 32 tiles per wave: fp_fwd_kernel)
             set_error("run_fp_fwd<%d>: more tiles than waves in layer %d", LVL, i);
             return PSG_ERR_STATE;
         }
     }
     if (a.out2) {
-        if (a.extra.mb * (P / 32) > NW || a.extra.k8 * 8 != a.Cout || a.Cout2 % 4) {
+        if (a.extra.mb > NW || a.extra.k8 * 8 != a.Cout || a.Cout2 % 4) {
             set_error("run_fp_fwd<%d>: unsupported shape of the finer module's split layer", LVL);
             return PSG_ERR_STATE;
         }
@@ -806,10 +810,10 @@ int run_fp_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStream
     return launch_lds(ws, TAG_FP_FWD + LVL, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
 }
 
-template <int LVL>
-int run_fp_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, const float *dlogp, hipStream_t st)
+template <int LVL, int P>
+int run_fp_bwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, const float *dlogp, hipStream_t st)
 {
-    constexpr int P = FpCfg<LVL>::P, NW = FpCfg<LVL>::NW;
+    constexpr int NW = FpCfg<LVL>::NW;
     const ArchDesc &A = *m->arch;
     const int B = ws->B, N = ws->Nl[LVL], S = ws->Nl[LVL + 1];
     const size_t prob = (size_t)fwd * B;
@@ -876,7 +880,7 @@ int run_fp_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, con
         if (a.Cd % 4 || a.C1 % 4) { set_error("run_fp_bwd<%d>: unsupported shape of the split first layer", LVL); return PSG_ERR_STATE; }
     }
     const bool big = LVL == 3 && A.fp4_big;
-    const int maxt = A.fp_maxt_b[LVL];
+    const int maxt = A.fp_maxt_b[LVL] * (P / 32);
     int blocks = std::max(a.mb_last * 4, a.Cg / 8);
     for (const BwdLayer *x : {&a.pre, &a.skipT}) {
         if (!x->w) continue;
@@ -897,14 +901,36 @@ int run_fp_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, con
     blocks += PSG_LDS_SPARE;
     const dim3 grid(N / P, B);
     if constexpr (LVL == 3) if (big) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 1, true>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
-    // (fp1 + head: 128-wide layers on 4 waves, one tile per wave; the 8-wave modules have ragged layers)
-    if (maxt == 1) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 1, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
-    if constexpr (LVL > 0) {
+    // (fp1 + head: 128-wide layers on 4 waves, one tile per wave at 32 points, one pair at 64; the 8-wave modules have
+    // ragged layers)
+    if constexpr (P == 64) {
+        // (fp1 + head at 64 points: two tiles = one pair per wave)
+        if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+    } else {
+        if (maxt == 1) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 1, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+    }
+    if constexpr (LVL > 0 && P == 32) {
         if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
         if (maxt == 3) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 3, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
     }
     set_error("run_fp_bwd<%d>: no kernel for MAXT=%d", LVL, maxt);
     return PSG_ERR_STATE;
+}
+
+template <int LVL>
+int run_fp_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStream_t st)
+{
+    if constexpr (FpCfg<LVL>::P2 != FpCfg<LVL>::P)
+        if (ws->Nl[LVL] % FpCfg<LVL>::P2 == 0) return run_fp_fwd_p<LVL, FpCfg<LVL>::P2>(m, ws, fwd, logp, st);
+    return run_fp_fwd_p<LVL, FpCfg<LVL>::P>(m, ws, fwd, logp, st);
+}
+
+template <int LVL>
+int run_fp_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, const float *dlogp, hipStream_t st)
+{
+    if constexpr (FpCfg<LVL>::P2 != FpCfg<LVL>::P)
+        if (ws->Nl[LVL] % FpCfg<LVL>::P2 == 0) return run_fp_bwd_p<LVL, FpCfg<LVL>::P2>(m, ws, fwd, logp, dlogp, st);
+    return run_fp_bwd_p<LVL, FpCfg<LVL>::P>(m, ws, fwd, logp, dlogp, st);
 }
 
 __global__ void extract_xyz_kernel(const float *__restrict__ x0, float *__restrict__ xyz, size_t rows)

@@ -248,10 +248,15 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
     // (an SSG level has nb3 * PB = 2 * NW last-layer tiles, i.e. two per wave; MSG scales have at most that)
     const int jj = lane & 31, h = lane >> 5;
     constexpr int T3 = 2;
+    // pairs (psg_mlp.cuh): with exactly two last-layer tiles per wave, a wave takes the point blocks g, g + 1 of ONE output block
+    // on one weight stream (tile_mac4x2) instead of one point block of two output blocks
+    constexpr int HP = PB / 2 > 0 ? PB / 2 : 1;
+    constexpr bool PAIR3 = PSG_MLP_PAIRS && PB >= 2 && (PB & 1) == 0;
+    const bool pair3 = PAIR3 && a.nb3 * PB == 2 * NW;
     float bias3[T3];
 #pragma unroll
     for (int i = 0; i < T3; ++i) {
-        const int task = wave + i * NW;
+        const int task = pair3 ? (wave / HP) * PB : wave + i * NW;
         bias3[i] = task < a.nb3 * PB ? a.b3[(task / PB) * 32 + jj] : 0.0f;
     }
     if (SPLIT) sa_layer1_split<P, NW, MAXT, KS>(a, b, s0, buf0, wg);
@@ -263,16 +268,7 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
 
     // last layer with the tile flipped (D[point][channel]) so the max over the 32 samples of a
     // group is an in-lane max over 16 accumulators + one exchange between lane halves.
-#pragma unroll
-    for (int i = 0; i < T3; ++i) {
-        const int task = wave + i * NW;
-        if (task >= a.nb3 * PB) break;
-        const int nb = task / PB, g = task - nb * PB;   // g = 32-point tile of the workgroup
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = bias3[i];
-        acc = tile_mac<L::BLK, true>(a.w3 + (size_t)nb * a.k8_3 * 64 + lane, a.k8_3, buf0 + (g * 32 + jj) * 8 + 4 * h,
-                                     acc);
+    auto pool = [&](const f32x16 &acc, int nb, int g) {   // g = 32-point tile of the workgroup
         if (KS == 32) {
             // max(relu(x)) = relu(max(x)): the raw maximum first (v_max3: 8 instructions for 16 values), then the lowest row
             // that holds it (descending scan: the last match written is the lowest), the ReLU once at the end - the values and
@@ -315,6 +311,28 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
             a.out[row * a.ld_out + a.c_out + nb * 32 + jj] = bv;
             a.arg[row * a.C3 + nb * 32 + jj] = bv > 0.0f ? (uint8_t)bi : (uint8_t)255;
         }
+    };
+    if (pair3) {
+        const int nb = wave / HP, g = 2 * (wave - nb * HP);
+        f32x16 c0, c1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { c0[r] = bias3[0]; c1[r] = bias3[0]; }
+        tile_mac_x2<L::BLK, true>(a.w3 + (size_t)nb * a.k8_3 * 64 + lane, a.k8_3, buf0 + (g * 32 + jj) * 8 + 4 * h, c0, c1);
+        pool(c0, nb, g);
+        pool(c1, nb, g + 1);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < T3; ++i) {
+        const int task = wave + i * NW;
+        if (task >= a.nb3 * PB) break;
+        const int nb = task / PB, g = task - nb * PB;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bias3[i];
+        acc = tile_mac<L::BLK, true>(a.w3 + (size_t)nb * a.k8_3 * 64 + lane, a.k8_3, buf0 + (g * 32 + jj) * 8 + 4 * h,
+                                     acc);
+        pool(acc, nb, g);
     }
 }
 
@@ -528,14 +546,19 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_kernel(SaBwdArgs a)
 template <int P, int NW>
 __device__ __forceinline__ void fp_layer1_split(const FpFwdArgs &a, int b, int n0, float *__restrict__ buf, size_t wg_linear)
 {
+    // up to PB tiles per wave (the layer has mb * PB tiles, at most PB * NW: run_fp_fwd checks mb <= NW), dealt like layer_fwd's
     constexpr int PB = P / 32, BLK = Lds<P>::BLK;
     const FwdLayer &L = a.layer[0];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int ntask = L.mb * PB;
-    const int task = (wave + (int)(wg_linear & (NW - 1))) & (NW - 1);
-    f32x16 c;
-    if (task < ntask) {
+    const int first = (wave + (int)(wg_linear & (NW - 1))) & (NW - 1);
+    f32x16 acc[PB];
+#pragma unroll
+    for (int i = 0; i < PB; ++i) {
+        const int task = first + i * NW;
+        if (task >= ntask) continue;
+        f32x16 c;
         const int mb = task / PB, pb = task - mb * PB;
         const size_t n3 = ((size_t)b * a.N + n0 + pb * 32 + j) * 3;
         const int i0 = a.nn_idx[n3], i1 = a.nn_idx[n3 + 1], i2 = a.nn_idx[n3 + 2];
@@ -567,12 +590,16 @@ __device__ __forceinline__ void fp_layer1_split(const FpFwdArgs &a, int b, int n
         c[8] += bq2.x; c[9] += bq2.y; c[10] += bq2.z; c[11] += bq2.w;
         c[12] += bq3.x; c[13] += bq3.y; c[14] += bq3.z; c[15] += bq3.w;
         const unsigned m = relu_bits(c);
-        if (L.mask) L.mask[(wg_linear * ntask + task) * 64 + lane] = (uint16_t)m;
+        if (L.mask) L.mask[((unsigned)wg_linear * (unsigned)ntask + (unsigned)task) * 64u + (unsigned)lane] = (uint16_t)m;
+        acc[i] = c;
     }
     __syncthreads();
-    if (task < ntask) {
+#pragma unroll
+    for (int i = 0; i < PB; ++i) {
+        const int task = first + i * NW;
+        if (task >= ntask) continue;
         const int mb = task / PB, pb = task - mb * PB;
-        store_tile<P>(buf, mb, pb * 32 + j, h, c);
+        store_tile<P>(buf, mb, pb * 32 + j, h, acc[i]);
     }
 }
 
@@ -581,7 +608,7 @@ __device__ __forceinline__ void fp_layer1_split(const FpFwdArgs &a, int b, int n
 template <int P, int NW, bool BIG = false>
 // (five waves per SIMD = at most 96 VGPRs: the split first layer and the extra layer took the allocator from 88 to 112 registers,
 // i.e. from five resident workgroups per CU to four; with fp_layer1_split's row pieces fenced into two halves it fits 96 unspilled)
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(5))) void fp_fwd_kernel(FpFwdArgs a)
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(P == 32 ? 5 : 4))) void fp_fwd_kernel(FpFwdArgs a)
 {
     using L = Lds<P>;
     constexpr int NT = NW * 64;
@@ -711,9 +738,21 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(5))) vo
     __syncthreads();
     float *in = buf0;
     if (PSG_DIAGBIT(a, 512) && (tid & 63) == 0) a.dbg[(wg * 8 + (tid >> 6)) * 16 + 0] = __builtin_amdgcn_s_memtime();
-    for (int l = BIG ? 1 : 0; l < a.n_layers; ++l) {
-        if (!BIG && l == 0 && a.tsrc) fp_layer1_split<P, NW>(a, b, n0, in, wg);
-        else if (!PSG_DIAGBIT(a, 8)) layer_fwd<P, NW, 1>(a.layer[l], in, wg);
+    int l0 = BIG ? 1 : 0;
+    if constexpr (P > 32) {
+        // (the split first layer peeled off the layer loop: with two tiles per wave, its addresses and the layer_fwd paths'
+        // hoisted together across the loop did not fit the registers and went to scratch)
+        if (a.tsrc) {
+            fp_layer1_split<P, NW>(a, b, n0, in, wg);
+            if (PSG_DIAGBIT(a, 512) && (tid & 63) == 0) a.dbg[(wg * 8 + (tid >> 6)) * 16 + 1] = __builtin_amdgcn_s_memtime();
+            if (!PSG_DIAGBIT(a, 16)) __syncthreads();
+            if (PSG_DIAGBIT(a, 512) && (tid & 63) == 0) a.dbg[(wg * 8 + (tid >> 6)) * 16 + 2] = __builtin_amdgcn_s_memtime();
+            l0 = 1;
+        }
+    }
+    for (int l = l0; l < a.n_layers; ++l) {
+        if (P == 32 && !BIG && l == 0 && a.tsrc) fp_layer1_split<P, NW>(a, b, n0, in, wg);
+        else if (!PSG_DIAGBIT(a, 8)) layer_fwd<P, NW, P / 32>(a.layer[l], in, wg);
         if (PSG_DIAGBIT(a, 512) && (tid & 63) == 0) a.dbg[(wg * 8 + (tid >> 6)) * 16 + 1 + 2 * l] = __builtin_amdgcn_s_memtime();
         if (!PSG_DIAGBIT(a, 16)) __syncthreads();
         if (PSG_DIAGBIT(a, 512) && (tid & 63) == 0) a.dbg[(wg * 8 + (tid >> 6)) * 16 + 2 + 2 * l] = __builtin_amdgcn_s_memtime();
@@ -738,7 +777,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(5))) vo
     if (a.out2) {
         // producer side of the finer module's split first layer (fp_layer1_split): T = out . W1b^T, in place over the output
         // (layer_fwd's barrier sits between the row reads above and its stores)
-        layer_fwd<P, NW, 1>(a.extra, in, wg);
+        layer_fwd<P, NW, P / 32>(a.extra, in, wg);
         __syncthreads();
         constexpr int RG = NT / 32;
         const int ql = tid & 31, rg = tid >> 5;
