@@ -274,6 +274,44 @@ int psg_pn2_nb_attack(psg_pn2_model *model, psg_pn2_ws *ws, const float *images,
                       const int32_t *starts, const uint8_t *mask, float eps, float alpha, int iters, int targeted,
                       int target, float *adv_out, psg_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Vanilla PointNet sem-seg network (get_model, PointNet/models/pointnet_sem_seg.py:8-38 with pointnet.py:10-130:
+ * STN3d, PointNetEncoder(global_feat=False, feature_transform=True, channel=6), STNkd), eval mode.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct psg_pointnet_model psg_pointnet_model;
+typedef struct psg_pointnet_ws psg_pointnet_ws;
+#define PSG_POINTNET_NUM_LAYERS 19
+#define PSG_POINTNET_NUM_CLASSES 13
+#define PSG_POINTNET_POINT_TILE 128  /* n_point must be a multiple of this */
+
+/* weights[l] [out][in] row-major and biases[l] [out] (HOST pointers, BatchNorm folded, runtime.fold_pointnet_state_dict),
+ * l in this order (out x in):
+ *   feat.stn  conv1 64x6, conv2 128x64, conv3 1024x128, fc1 512x1024, fc2 256x512, fc3 9x256 (bias + identity)
+ *   feat.conv1 64x6
+ *   feat.fstn conv1 64x64, conv2 128x64, conv3 1024x128, fc1 512x1024, fc2 256x512, fc3 4096x256 (bias + identity)
+ *   feat.conv2 128x64, feat.conv3 1024x128
+ *   conv1 512x1088 (columns: [global 1024 | pointfeat 64]), conv2 256x512, conv3 128x256, conv4 13x128 */
+int psg_pointnet_model_create(psg_ctx *ctx, const float *const *weights, const float *const *biases,
+                              psg_pointnet_model **out);
+int psg_pointnet_model_destroy(psg_pointnet_model *model);
+/* Activations and gradient buffers for `batch` rooms of n_point points (a multiple of PSG_POINTNET_POINT_TILE). */
+int psg_pointnet_ws_create(psg_ctx *ctx, int batch, int n_point, psg_pointnet_ws **out);
+int psg_pointnet_ws_destroy(psg_pointnet_ws *ws);
+/* x0 [B][N][9] point-major (channels 6:9 are not read: the reference uses x[:, :6]); logp_out [B][N][13] (nullable);
+ * trans_out [B][3][3], trans_feat_out [B][64][64], pool_out [B][3][1024] (the pooled vectors of STN3d, STNkd and the
+ * encoder; STN ones after their ReLU), arg_out [B][3][1024] (first arg-max point of each pooled channel): all nullable. */
+int psg_pointnet_forward(psg_pointnet_model *model, psg_pointnet_ws *ws, const float *x0, float *logp_out, float *trans_out,
+                         float *trans_feat_out, float *pool_out, int32_t *arg_out, psg_stream stream);
+/* Input gradient of the last forward: dlogp [B][N][13], dtrans_feat [B][64][64] (nullable: the upstream gradient of
+ * trans_feat, e.g. from get_loss's regulariser); dx0_out [B][N][9], channels 6:9 exactly zero. */
+int psg_pointnet_backward(psg_pointnet_model *model, psg_pointnet_ws *ws, const float *dlogp, const float *dtrans_feat,
+                          float *dx0_out, psg_stream stream);
+/* Fused NB_attack / tar_NB_attack for this network: iters x (forward, psg_ce_logp_grad, backward, psg_pgd_step),
+ * stream-ordered; arguments as psg_pn2_nb_attack without the FPS starts (the network draws no random numbers). */
+int psg_pointnet_nb_attack(psg_pointnet_model *model, psg_pointnet_ws *ws, const float *images, const int32_t *labels,
+                           const uint8_t *mask, float eps, float alpha, int iters, int targeted, int target, float *adv_out,
+                           psg_stream stream);
+
 /* ---- NU (Adam in tanh space) attack arithmetic: nontarget.py:52-135, target.py:62-175 -------------
  * w / m / v are [B][N][3] fp32 (the attack variable and its Adam moments); colours live in channels 3:6
  * of the point-major rooms x0 [B][N][9]; `mask` (nullable, [N] uint8) restricts every op to masked points. */

@@ -72,6 +72,13 @@ SIGNATURES = {
     "psg_ce_logp_grad": (ci, [vp, vp, ci, ci, ci, ci, cf, vp, vp, vp]),
     "psg_pgd_step": (ci, [vp, vp, vp, vp, ci, ci, cf, cf, cf, ci, vp]),
     "psg_pn2_nb_attack": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, ci, ci, ci, vp, vp]),
+    "psg_pointnet_model_create": (ci, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]),
+    "psg_pointnet_model_destroy": (ci, [vp]),
+    "psg_pointnet_ws_create": (ci, [vp, ci, ci, ctypes.POINTER(vp)]),
+    "psg_pointnet_ws_destroy": (ci, [vp]),
+    "psg_pointnet_forward": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "psg_pointnet_backward": (ci, [vp, vp, vp, vp, vp, vp]),
+    "psg_pointnet_nb_attack": (ci, [vp, vp, vp, vp, vp, cf, cf, ci, ci, ci, vp, vp]),
     "psg_nu_inverse_tanh": (ci, [vp, ci, ci, vp, vp]),
     "psg_nu_tanh_color": (ci, [vp, vp, ci, ci, vp, vp]),
     "psg_nu_f_loss_grad": (ci, [vp, vp, ci, ci, ci, cf, cf, vp, vp, vp, vp]),

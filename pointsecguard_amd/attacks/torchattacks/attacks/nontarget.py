@@ -6,6 +6,7 @@ from pointsecguard_amd.models.pointnet2_sem_seg import draw_fps_starts, upload
 
 from ..attack import Attack
 from ._common import labels_to_device, psg_model
+from .pointnet import is_pointnet, nb_attack as pointnet_nb_attack
 
 
 class NB_attack(Attack):
@@ -24,6 +25,8 @@ class NB_attack(Attack):
         self.iters = iters
 
     def forward(self, images, labels):
+        if is_pointnet(self.model):
+            return pointnet_nb_attack(self, images, labels)
         net = psg_model(self.model)
         images = images.detach().to(self.device).float().contiguous()
         B, C, N = images.shape
@@ -43,6 +46,9 @@ class NU_attack(Attack):
         self.lr = lr
 
     def forward(self, images, labels):
+        if is_pointnet(self.model):
+            from .pointnet import nu_attack as pointnet_nu_attack
+            return pointnet_nu_attack(self, images, labels, mask=None, target=None, neighbour=10)
         from .nu import nu_attack
         return nu_attack(self, images, labels, mask=None, target=None, neighbour=10)
 

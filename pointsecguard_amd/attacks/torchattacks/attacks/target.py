@@ -6,6 +6,7 @@ from pointsecguard_amd.models.pointnet2_sem_seg import draw_fps_starts, upload
 
 from ..attack import Attack
 from ._common import mask_to_device, psg_model
+from .pointnet import is_pointnet, nb_attack as pointnet_nb_attack
 
 
 class tar_NB_attack(Attack):
@@ -22,6 +23,10 @@ class tar_NB_attack(Attack):
         self.mask = mask
 
     def forward(self, images, labels):
+        if is_pointnet(self.model):
+            if self.target is None or self.mask is None:
+                raise ValueError("tar_NB_attack needs target and mask")
+            return pointnet_nb_attack(self, images, None, mask=self.mask, target=self.target)
         net = psg_model(self.model)
         if self.target is None or self.mask is None:
             raise ValueError("tar_NB_attack needs target and mask")
@@ -46,6 +51,10 @@ class tar_NU_attack(Attack):
         self.mask = mask
 
     def forward(self, images, labels):
+        if is_pointnet(self.model):
+            from .pointnet import nu_attack as pointnet_nu_attack
+            return pointnet_nu_attack(self, images, labels, mask=self.mask, target=self.target, neighbour=5,
+                                      targeted_variant=True)
         from .nu import nu_attack
         return nu_attack(self, images, labels, mask=self.mask, target=self.target, neighbour=5, targeted_variant=True)
 

@@ -248,6 +248,130 @@ class PN2Workspace:
         return out
 
 
+# ---- vanilla PointNet sem-seg (pointnet_sem_seg.py + pointnet.py of the reference) ----------------------------------
+POINTNET_POINT_TILE = 128   # PSG_POINTNET_POINT_TILE: n_point must be a multiple of it
+# (conv / linear, BatchNorm or None, identity size added to the bias) in the layer order of psg_pointnet_model_create
+POINTNET_LAYERS = (("feat.stn.conv1", "feat.stn.bn1", 0), ("feat.stn.conv2", "feat.stn.bn2", 0),
+                   ("feat.stn.conv3", "feat.stn.bn3", 0), ("feat.stn.fc1", "feat.stn.bn4", 0),
+                   ("feat.stn.fc2", "feat.stn.bn5", 0), ("feat.stn.fc3", None, 3),
+                   ("feat.conv1", "feat.bn1", 0),
+                   ("feat.fstn.conv1", "feat.fstn.bn1", 0), ("feat.fstn.conv2", "feat.fstn.bn2", 0),
+                   ("feat.fstn.conv3", "feat.fstn.bn3", 0), ("feat.fstn.fc1", "feat.fstn.bn4", 0),
+                   ("feat.fstn.fc2", "feat.fstn.bn5", 0), ("feat.fstn.fc3", None, 64),
+                   ("feat.conv2", "feat.bn2", 0), ("feat.conv3", "feat.bn3", 0),
+                   ("conv1", "bn1", 0), ("conv2", "bn2", 0), ("conv3", "bn3", 0), ("conv4", None, 0))
+
+
+def fold_pointnet_state_dict(sd, eps=1e-5, dtype=np.float32):
+    """Eval-mode BatchNorm folded into the preceding conv / linear layer of pointnet_sem_seg.get_model, and the STN
+    identities of pointnet.py:41-47 / 77-83 added to the fc3 biases, in the layer order of psg_pointnet_model_create.
+    sd: the reference's state_dict keys.  fp64 math, `dtype` result (fp32 for the device): [(w [out][in], b [out])] * 19."""
+    def arr(k):
+        v = sd[k]
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        return np.asarray(v, np.float64)
+
+    out = []
+    for layer, bn, iden in POINTNET_LAYERS:
+        w = arr(layer + ".weight")
+        w = w.reshape(w.shape[0], -1)
+        b = arr(layer + ".bias")
+        if bn is not None:
+            s = arr(bn + ".weight") / np.sqrt(arr(bn + ".running_var") + eps)
+            w = w * s[:, None]
+            b = (b - arr(bn + ".running_mean")) * s + arr(bn + ".bias")
+        if iden:
+            b = b + np.eye(iden).reshape(-1)
+        out.append((np.ascontiguousarray(w, dtype), np.ascontiguousarray(b, dtype)))
+    return out
+
+
+class PointNetModel:
+    """Device-resident BN-folded weights of pointnet_sem_seg.get_model (psg_pointnet_model)."""
+
+    def __init__(self, folded, device=None):
+        n = len(POINTNET_LAYERS)
+        if len(folded) != n:
+            raise _lib.PsgError("expected %d folded layers, got %d" % (n, len(folded)))
+        self.ctx = context(device)
+        folded = [(np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32)) for w, b in folded]
+        ws = (ctypes.c_void_p * n)(*[w.ctypes.data_as(ctypes.c_void_p) for w, _ in folded])
+        bs = (ctypes.c_void_p * n)(*[b.ctypes.data_as(ctypes.c_void_p) for _, b in folded])
+        self._keep = folded
+        self.handle = ctypes.c_void_p()
+        _lib.check(_lib.load().psg_pointnet_model_create(self.ctx, ws, bs, ctypes.byref(self.handle)), "psg_pointnet_model_create")
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _lib.load().psg_pointnet_model_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class PointNetWorkspace:
+    """Activations, ReLU bits, pooled arg-max sets and gradient buffers for (batch, n_point) (psg_pointnet_ws)."""
+
+    def __init__(self, batch, n_point, device=None):
+        if n_point % POINTNET_POINT_TILE:
+            raise _lib.PsgError("n_point=%d is not a multiple of the point tile %d" % (n_point, POINTNET_POINT_TILE))
+        self.ctx = context(device)
+        self.batch, self.n_point = batch, n_point
+        self.handle = ctypes.c_void_p()
+        _lib.check(_lib.load().psg_pointnet_ws_create(self.ctx, batch, n_point, ctypes.byref(self.handle)), "psg_pointnet_ws_create")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _lib.load().psg_pointnet_ws_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def forward(self, model, x0, logp=None, extras=False):
+        """x0 [B][N][9] point-major -> logp [B][N][13]; extras=True also returns (trans [B,3,3], trans_feat [B,64,64],
+        pooled [B,3,1024], arg-max [B,3,1024]) of STN3d, STNkd and the encoder."""
+        require_cuda(x0, "x0", torch.float32)
+        assert x0.shape == (self.batch, self.n_point, 9)
+        dev = x0.device
+        if logp is None:
+            logp = torch.empty(self.batch, self.n_point, NUM_CLASSES, device=dev, dtype=torch.float32)
+        trans = torch.empty(self.batch, 3, 3, device=dev, dtype=torch.float32)
+        tf = torch.empty(self.batch, 64, 64, device=dev, dtype=torch.float32)
+        pool = torch.empty(self.batch, 3, 1024, device=dev, dtype=torch.float32) if extras else None
+        arg = torch.empty(self.batch, 3, 1024, device=dev, dtype=torch.int32) if extras else None
+        _lib.call("psg_pointnet_forward", model.handle, self.handle, ptr(x0), ptr(logp), ptr(trans), ptr(tf), ptr(pool), ptr(arg),
+                  stream())
+        if extras:
+            return logp, trans, tf, pool, arg
+        return logp, tf
+
+    def backward(self, model, dlogp, dtrans_feat=None, dx0=None):
+        """dlogp [B][N][13] (+ optional d trans_feat [B][64][64]) -> dx0 [B][N][9] of the last forward."""
+        require_cuda(dlogp, "dlogp", torch.float32)
+        if dtrans_feat is not None:
+            require_cuda(dtrans_feat, "dtrans_feat", torch.float32)
+        if dx0 is None:
+            dx0 = torch.empty(self.batch, self.n_point, 9, device=dlogp.device, dtype=torch.float32)
+        _lib.call("psg_pointnet_backward", model.handle, self.handle, ptr(dlogp), ptr(dtrans_feat), ptr(dx0), stream())
+        return dx0
+
+    def nb_attack(self, model, images, labels, eps, alpha, iters, mask=None, target=None, out=None):
+        require_cuda(images, "images", torch.float32)
+        if labels is not None:
+            require_cuda(labels, "labels", torch.int32)
+        if mask is not None:
+            require_cuda(mask, "mask", torch.uint8)
+        if out is None:
+            out = torch.empty_like(images)
+        _lib.call("psg_pointnet_nb_attack", model.handle, self.handle, ptr(images), ptr(labels), ptr(mask), float(eps),
+                  float(alpha), int(iters), 0 if target is None else 1, 0 if target is None else int(target), ptr(out), stream())
+        return out
+
+
 # ---- unit ops -----------------------------------------------------------------------------------
 def square_distance(src, dst):
     require_cuda(src, "src", torch.float32)

@@ -124,6 +124,41 @@ def msg_state_dict(seed):
     return sd
 
 
+# (name, in, out, BatchNorm name or None) of pointnet_sem_seg.get_model(13) (PointNet/models/pointnet.py:10-100 and
+# pointnet_sem_seg.py:15-24 of the reference)
+POINTNET_LAYERS = (("feat.stn.conv1", 6, 64, "feat.stn.bn1"), ("feat.stn.conv2", 64, 128, "feat.stn.bn2"),
+                   ("feat.stn.conv3", 128, 1024, "feat.stn.bn3"), ("feat.stn.fc1", 1024, 512, "feat.stn.bn4"),
+                   ("feat.stn.fc2", 512, 256, "feat.stn.bn5"), ("feat.stn.fc3", 256, 9, None),
+                   ("feat.conv1", 6, 64, "feat.bn1"), ("feat.conv2", 64, 128, "feat.bn2"), ("feat.conv3", 128, 1024, "feat.bn3"),
+                   ("feat.fstn.conv1", 64, 64, "feat.fstn.bn1"), ("feat.fstn.conv2", 64, 128, "feat.fstn.bn2"),
+                   ("feat.fstn.conv3", 128, 1024, "feat.fstn.bn3"), ("feat.fstn.fc1", 1024, 512, "feat.fstn.bn4"),
+                   ("feat.fstn.fc2", 512, 256, "feat.fstn.bn5"), ("feat.fstn.fc3", 256, 4096, None),
+                   ("conv1", 1088, 512, "bn1"), ("conv2", 512, 256, "bn2"), ("conv3", 256, 128, "bn3"), ("conv4", 128, NUM_CLASSES, None))
+
+
+def pointnet_state_dict(seed):
+    """Seeded random weights for pointnet_sem_seg.get_model(13) with the reference's state_dict keys and shapes, in the
+    style of msg_state_dict.  The STN output layers (fc3) are kept small, so that both transforms stay within about 0.1
+    of the identity: a far-from-identity 64x64 transform amplifies, and the 1e-4 parity bars would lose their meaning."""
+    rng = np.random.RandomState(int(seed))
+    sd = {}
+    for name, cin, cout, bn in POINTNET_LAYERS:
+        conv = not (".fc" in name)
+        shape = (cout, cin, 1) if conv else (cout, cin)
+        scale = np.sqrt(2.0 / cin)
+        if name.endswith("fc3"):
+            scale = 0.05 / np.sqrt(cin) / (3.0 if cout == 9 else 8.0)
+        sd[name + ".weight"] = (rng.standard_normal(shape) * scale).astype(np.float32)
+        sd[name + ".bias"] = rng.uniform(-0.1, 0.1, cout).astype(np.float32) * (0.1 if name.endswith("fc3") else 1.0)
+        if bn is not None:
+            sd[bn + ".weight"] = rng.uniform(0.8, 1.2, cout).astype(np.float32)
+            sd[bn + ".bias"] = rng.uniform(-0.1, 0.1, cout).astype(np.float32)
+            sd[bn + ".running_mean"] = rng.uniform(-0.1, 0.1, cout).astype(np.float32)
+            sd[bn + ".running_var"] = rng.uniform(0.5, 1.5, cout).astype(np.float32)
+            sd[bn + ".num_batches_tracked"] = np.array(1, np.int64)
+    return sd
+
+
 def gcn_state_dict(seed, n_blocks, block="res", conv="edge"):
     """Seeded random weights for DenseDeepGCN(opt) (n_filters=64, k=16, in_channels=9, 13 classes) with the reference's
     state_dict keys and shapes for the given `block` / `conv` switches (ResGCN/sem_seg_dense/architecture.py:20-45):

@@ -1,0 +1,202 @@
+"""GPU tests of the vanilla PointNet sem-seg network (pointsecguard_amd.models.pointnet_sem_seg) and its NB colour attacks
+on the gfx950 kernels (psg_pointnet.hip), against the reference's recorded outputs (tests/golden/pointnet_*.npz, made by
+tests/golden/make_golden_pointnet.py) and the float64 restatement tests/pointnet_ref64.py."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import pointnet_ref64 as ref64  # noqa: E402
+
+PN_SEED, ROOM_SEED = 3, 5
+
+
+def _golden(name):
+    return np.load(os.path.join(HERE, "golden", name))
+
+
+@pytest.fixture(scope="module")
+def sd():
+    from pointsecguard_amd import synthetic
+    return synthetic.pointnet_state_dict(PN_SEED)
+
+
+def _net(sd):
+    from pointsecguard_amd.models.pointnet_sem_seg import get_model
+    m = get_model(13)
+    res = m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    assert not res.missing_keys and not res.unexpected_keys
+    return m.cuda().eval()
+
+
+@pytest.fixture(scope="module")
+def net(sd):
+    return _net(sd)
+
+
+@pytest.fixture(scope="module")
+def rooms():
+    from pointsecguard_amd import synthetic
+    r = synthetic.make_rooms(2, ROOM_SEED)
+    return r, synthetic.rule_labels(r)
+
+
+def _x(r):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(r).transpose(0, 2, 1))).cuda()
+
+
+def _close(a, b, tol=1e-4):
+    """within tol, relative where the magnitude is above 1"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.all(np.abs(a - b) <= tol * np.maximum(1.0, np.abs(b)))
+
+
+def test_forward_matches_reference(net, rooms):
+    g = _golden("pointnet_room.npz")
+    x = _x(rooms[0])
+    with torch.no_grad():
+        logp, tf = net(x)
+    assert logp.shape == (2, 4096, 13) and tf.shape == (2, 64, 64)
+    assert _close(logp.cpu().numpy(), g["logp"])
+    assert _close(tf.cpu().numpy(), g["trans_feat"])
+    ws = net._workspace(2, 4096)
+    x0 = x.permute(0, 2, 1).contiguous()
+    _, trans, tf2, pool, arg = ws.forward(net._packed(), x0, extras=True)
+    assert _close(trans.cpu().numpy(), g["trans"])
+    assert torch.equal(tf2, tf)
+    for k, name in enumerate(("stn", "fstn", "feat")):
+        assert _close(pool[:, k].cpu().numpy(), g["g_" + name])
+        a, ra = arg[:, k].cpu().numpy(), g["arg_" + name]
+        # a near-tie (top-2 gap within the fp32 parity bar) or a dead channel (ReLU'd max = 0) may pick another point
+        decided = (g["gap_" + name] > 1e-4 * np.maximum(1.0, np.abs(g["g_" + name]))) & (g["g_" + name] > 0 if name != "feat" else True)
+        assert decided.mean() > 0.5
+        assert np.array_equal(a[decided], ra[decided]), name
+
+
+def _sign_agree(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    big = np.abs(b) > 1e-6 * np.abs(b).max()
+    return (np.sign(a[big]) == np.sign(b[big])).mean()
+
+
+@pytest.mark.parametrize("with_reg", [False, True])
+def test_input_gradient_matches_reference(net, rooms, with_reg):
+    from pointsecguard_amd.models.pointnet_sem_seg import get_loss
+    g = _golden("pointnet_room.npz")
+    x = _x(rooms[0]).requires_grad_(True)
+    lab = torch.from_numpy(rooms[1]).cuda()
+    logp, tf = net(x)
+    if with_reg:
+        loss = get_loss()(logp.reshape(-1, 13), lab.reshape(-1), tf, None)
+    else:
+        loss = F.nll_loss(logp.reshape(-1, 13), lab.reshape(-1))
+    loss.backward()
+    got = x.grad.cpu().numpy()
+    want = g["dloss" if with_reg else "dnll"]
+    assert np.all(got[:, 6:9] == 0.0)
+    assert np.array_equal(got[:, :6] == 0.0, want == 0.0)
+    assert _sign_agree(got[:, :6], want) >= 0.999
+    assert np.abs(got[:, :6] - want).max() <= 1e-3 * np.abs(want).max()
+
+
+def test_regulariser_gradient_reaches_input(net, sd, rooms):
+    """the trans_feat output is differentiable on its own (its gradient enters the backward's dT)"""
+    x = _x(rooms[0]).requires_grad_(True)
+    _, tf = net(x)
+    ref64_x = _x(rooms[0]).double().cpu().requires_grad_(True)
+    _, tf64 = ref64.forward(sd, ref64_x)
+    (tf * tf).sum().backward()
+    (tf64 * tf64).sum().backward()
+    got, want = x.grad.cpu().numpy()[:, :6], ref64_x.grad.numpy()[:, :6]
+    assert _sign_agree(got, want) >= 0.999
+
+
+def test_repeat_and_batch_are_bit_identical(sd):
+    from pointsecguard_amd import synthetic
+    net = _net(sd)
+    r = synthetic.make_rooms(8, 11)
+    lab = torch.from_numpy(synthetic.rule_labels(r)).cuda()
+
+    def run(x, l):
+        x = x.clone().requires_grad_(True)
+        logp, tf = net(x)
+        F.nll_loss(logp.reshape(-1, 13), l.reshape(-1), reduction="sum").backward()
+        return logp.detach().cpu().numpy(), tf.detach().cpu().numpy(), x.grad.cpu().numpy()
+
+    x = _x(r)
+    a = run(x, lab)
+    b = run(x, lab)
+    for u, v in zip(a, b):
+        assert u.tobytes() == v.tobytes()
+    singles = [run(x[i:i + 1], lab[i:i + 1]) for i in range(8)]
+    for k in range(3):
+        assert np.concatenate([s[k] for s in singles]).tobytes() == a[k].tobytes()
+
+
+def test_two_streams_two_replicas(sd, rooms):
+    x = _x(rooms[0])
+    nets = [_net(sd), _net(sd)]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    outs = []
+    torch.cuda.synchronize()
+    for n, s in zip(nets, streams):
+        with torch.cuda.stream(s), torch.no_grad():
+            outs.append(n(x))
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
+def test_n1024_matches_restatement(net, sd):
+    from pointsecguard_amd import synthetic
+    r = synthetic.make_rooms(2, 21, num_point=1024)
+    x = _x(r)
+    with torch.no_grad():
+        logp, tf = net(x)
+    lp64, tf64 = ref64.forward(sd, x.double().cpu())
+    assert _close(logp.cpu().numpy(), lp64.numpy())
+    assert _close(tf.cpu().numpy(), tf64.numpy())
+
+
+def test_bad_sizes_and_modes_raise(net, sd):
+    from pointsecguard_amd import _lib
+    from pointsecguard_amd.models.pointnet_sem_seg import get_model
+    with pytest.raises(_lib.PsgError):
+        net(torch.zeros(1, 9, 1000, device="cuda"))
+    with pytest.raises(NotImplementedError):
+        get_model(13, with_rgb=False)
+    with pytest.raises(NotImplementedError):
+        _net(sd).train()(torch.zeros(1, 9, 128, device="cuda"))
+    x = torch.rand(1, 9, 128, device="cuda", requires_grad=True)
+    logp, _ = net(x)
+    net(torch.rand(1, 9, 128, device="cuda"))
+    with pytest.raises(RuntimeError):
+        logp.sum().backward()
+
+
+def test_nb_attack_matches_reference(net, rooms):
+    from pointsecguard_amd.attacks import torchattacks
+    g = _golden("pointnet_nb.npz")
+    x = _x(rooms[0])
+    adv = torchattacks.NB_attack(net, eps=0.1, alpha=0.05, iters=10)(x, rooms[1].astype(np.float64))
+    got = adv[:, 3:6].cpu().numpy()
+    assert (got.view(np.uint32) == g["adv_colour"].view(np.uint32)).mean() >= 0.99
+    assert torch.equal(adv[:, :3], x[:, :3]) and torch.equal(adv[:, 6:], x[:, 6:])
+
+
+def test_tar_nb_attack_matches_reference(net, rooms):
+    from pointsecguard_amd.attacks import torchattacks
+    g = _golden("pointnet_tarnb.npz")
+    x = _x(rooms[0])
+    mask = g["mask"]
+    adv = torchattacks.tar_NB_attack(net, eps=0.1, alpha=0.05, iters=10, target=int(g["target"]), mask=mask)(
+        x, rooms[1].astype(np.float64))
+    got = adv[:, 3:6].cpu().numpy()
+    assert np.array_equal(got[:, :, ~mask], x[:, 3:6].cpu().numpy()[:, :, ~mask])
+    assert (got.view(np.uint32) == g["adv_colour"].view(np.uint32)).mean() >= 0.99
