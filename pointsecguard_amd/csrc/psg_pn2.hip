@@ -170,6 +170,7 @@ struct PackedLayer {
     float *bias = nullptr; // [mb(cout)*32]
     float4 *wf4 = nullptr; // forward packing, k8-major [k8][mb = 4][64] (wave-private chain kernels, psg_chain.cuh)
     float4 *wb4 = nullptr; // transposed packing, k8-major
+    float *wr = nullptr;   // plain rows [cout][cin]: the third layers of the SSG SA levels 1 - 3 (sa_pool_t_sparse)
     int cin = 0, cout = 0;
     // K is padded to a multiple of 8 only (tile_mac runs a tail of 1..3 chunks behind its 4-chunk pipeline)
     int k8f() const { return ceil_div(cin, 8); }
@@ -569,13 +570,25 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     static const bool l1t_colour = psg::env_int("PSG_PN2_L1T_COLOUR", 1) != 0;
     a.w1c = nullptr; a.C1 = L[0].cout; a.w1c_off = 0;
     if (l1t_colour && a.cg_out == 4 && !a.split && P == 32 * NW && (a.C1 == 16 || a.C1 == 32)) a.w1c = m->w1feat[sc];
-    const int main_blocks = std::max(std::max(layer_blocks(a.l3t.k8, a.l3t.mb), layer_blocks(a.l2t.k8, a.l2t.mb)),
+    // max-pool transpose as a sparse weight-row stream (psg_pn2_kernels.cuh: sa_pool_t_sparse) where the level's shapes fit it:
+    // SSG levels 1 - 3 (sa1: C2 = 32 is half a wave's lanes; MSG: KS = 16 and C2 = 96 / 196 / 384).  PSG_PN2_POOLT_SPARSE=0 keeps
+    // the dense transposed layer on the matrix pipe.  The sparse pass needs no dZ3 tile: the buffer is sized without l3t's K.
+    static const bool poolt_sparse = psg::env_int("PSG_PN2_POOLT_SPARSE", 1) != 0;
+    const int C2 = L[2].cin, NT = NW * 64;
+    const int spv = poolt_sparse && L[2].wr && KS == 32 && P <= 64 && (P / KS) * C3 <= NT && C3 % 64 == 0 && !a.w1c &&
+                    (C2 == 64 || C2 == 128 || C2 == 256) ? C2 / 64 : 0;
+    const int l3_blocks = spv ? a.l3t.mb * 4 : layer_blocks(a.l3t.k8, a.l3t.mb);
+    const int main_blocks = std::max(std::max(l3_blocks, layer_blocks(a.l2t.k8, a.l2t.mb)),
                                      a.split ? 0 : layer_blocks(a.l1t.k8, a.l1t.mb)) + PSG_LDS_SPARE;
     a.dsrc_blk = main_blocks;   // the gathered pooled-output gradient is staged behind the activation buffer
     const int blk_floats = P * 8 + PSG_LDS_PAD;
     a.w1c_off = round_up((P / KS) * C3, 4);
     a.pos_off = a.w1c_off + (a.w1c ? round_up(3 * a.C1, 4) : 0);
-    const int blocks = main_blocks + ceil_div(a.pos_off + P, blk_floats);
+    // sparse: item list [NT] int2, count / offset table [NW][32], row starts [P + 1]
+    a.sp_off = round_up(a.pos_off + P, 4);
+    a.w3r = spv ? L[2].wr : nullptr;
+    const int staged = spv ? a.sp_off + 2 * NT + NW * 32 + P + 1 : a.pos_off + P;
+    const int blocks = main_blocks + ceil_div(staged, blk_floats);
     if (std::max(std::max(a.l3t.mb, a.l2t.mb), a.split ? 0 : a.l1t.mb) * (P / 32) > d.maxt_b * NW) {
         set_error("run_sa_bwd level %d scale %d: more than %d tiles per wave in a layer", lvl, sc, d.maxt_b);
         return PSG_ERR_STATE;
@@ -586,6 +599,15 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
         if (a.w1c) return launch_lds_colour(ws, tag, (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st); \
         return launch_lds(ws, tag, (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
+    if (spv) {
+        switch (PSG_CFG_KEY(P, NW, KS, d.maxt_b) * 8 + spv) {
+        case PSG_CFG_KEY(64, 4, 32, 2) * 8 + 1: return launch_lds(ws, tag, (sa_bwd_sparse_kernel<64, 4, 2, 1>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);   // SSG sa2
+        case PSG_CFG_KEY(32, 4, 32, 2) * 8 + 2: return launch_lds(ws, tag, (sa_bwd_sparse_kernel<32, 4, 2, 2>), grid, 4 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa3
+        case PSG_CFG_KEY(32, 8, 32, 2) * 8 + 4: return launch_lds(ws, tag, (sa_bwd_sparse_kernel<32, 8, 2, 4>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa4
+        }
+        set_error("run_sa_bwd: no sparse kernel for P=%d NW=%d MAXT=%d C2=%d", P, NW, d.maxt_b, C2);
+        return PSG_ERR_STATE;
+    }
     switch (PSG_CFG_KEY(P, NW, KS, d.maxt_b)) {
         PSG_SA_BWD_CASE(128, 4, 32, 1);   // SSG sa1, MSG sa1 scale 1
         PSG_SA_BWD_CASE(64, 4, 32, 2);    // SSG sa2
@@ -1259,9 +1281,12 @@ extern "C" int psg_pn2_model_create_arch(psg_ctx *ctx, int arch, const float *co
     m->arch = &A;
     const int NLr = A.n_layers, fp1 = A.fp_first[0];
     std::vector<std::vector<float>> wf(NLr), wb(NLr), bs(NLr), wf4(NLr), wb4(NLr);
-    std::vector<bool> sa_first(NLr, false);
+    std::vector<bool> sa_first(NLr, false), sa_rows(NLr, false);
     for (int l = 0; l < 4; ++l)
-        for (int s = 0; s < A.ns; ++s) sa_first[A.sc[l][s].l0] = A.sa_perm;
+        for (int s = 0; s < A.ns; ++s) {
+            sa_first[A.sc[l][s].l0] = A.sa_perm;
+            sa_rows[A.sc[l][s].l0 + 2] = A.id == PSG_PN2_ARCH_SSG && l >= 1;   // (run_sa_bwd: the levels that may run sparse)
+        }
     size_t total = 0;
     for (int i = 0; i < NLr; ++i) {
         if (!weights[i] || !biases[i]) { delete m; set_error("psg_pn2_model_create: layer %d is null", i); return PSG_ERR_ARG; }
@@ -1276,7 +1301,8 @@ extern "C" int psg_pn2_model_create_arch(psg_ctx *ctx, int arch, const float *co
             if (cout == 128) wf4[i] = k8_major(wf[i], 4, ceil_div(cin, 8));
             wb4[i] = k8_major_padded(wb[i], 4, ceil_div(cout, 8), round_up(ceil_div(cout, 8), 4));
         }
-        total += ((wf[i].size() + wb[i].size() + bs[i].size() + wf4[i].size() + wb4[i].size()) * 4 + 5 * 256);
+        total += ((wf[i].size() + wb[i].size() + bs[i].size() + wf4[i].size() + wb4[i].size()) * 4 + 6 * 256);
+        if (sa_rows[i]) total += (size_t)cout * cin * 4;
     }
     // split first layers (arch_split): reference column order of the layer is [rel_xyz(3), feats(D)] (SSG: sa_perm)
     std::vector<float> sxf[8], sff[8], sfb[8], sfbias[8], w0raw;
@@ -1388,6 +1414,10 @@ extern "C" int psg_pn2_model_create_arch(psg_ctx *ctx, int arch, const float *co
         if (!wb4[i].empty()) {
             L.wb4 = bp.take<float4>(wb4[i].size() / 4);
             PSG_CHECK_HIP(psg::copy_sync(L.wb4, wb4[i].data(), wb4[i].size() * 4, hipMemcpyHostToDevice));
+        }
+        if (sa_rows[i]) {
+            L.wr = bp.take<float>((size_t)L.cout * L.cin);
+            PSG_CHECK_HIP(psg::copy_sync(L.wr, weights[i], (size_t)L.cout * L.cin * 4, hipMemcpyHostToDevice));
         }
     }
     *out = m;

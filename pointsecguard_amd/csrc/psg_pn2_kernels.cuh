@@ -76,6 +76,10 @@ struct SaBwdArgs {
     const float *w1c;
     int C1, w1c_off;      // first layer's width (16 or 32); float offset of the LDS copy from the start of the staging block
     int pos_off;          // float offset (staging block) of the LDS copy of the workgroup's P output slots
+    // sparse max-pool transpose (sa_pool_t_sparse; kernels with SPV > 0 only): the third layer's weights as plain rows [C3][C2],
+    // and the float offset (staging block) of the item list, its per-chunk offset table and the row starts
+    const float *w3r;
+    int sp_off;
     int diag;             // timing diagnostics only (-DPSG_DIAG_BUILD libraries only)
 };
 
@@ -369,11 +373,168 @@ __device__ __forceinline__ void sa_l1t_colour(const SaBwdArgs &a, const float *_
     if (h == 0 && pj >= 0) *(float4 *)(orow + (size_t)pj * 4) = make_float4(g0 + o0, g1 + o1, g2 + o2, 0.0f);   // padding rows are not listed
 }
 
-template <int P, int NW, int MAXT, int KS = 32>
-__global__ __launch_bounds__(NW * 64) void sa_bwd_kernel(SaBwdArgs a)
+// Sparse max-pool transpose (round 8).  The max-pool gradient reaches ONE sample per (group, channel), so dZ3 is 31/32 zeros and
+// the dense first layer of the backward (W3^T dZ3 on the matrix pipe, K = C3) multiplies mostly zeros.  Here the non-zero
+// entries of dZ3 become one flat item list per workgroup, sorted by sample row (stable: ascending channel inside a row), and
+// dZ2[row] = sum over the row's items (c, d) of d * W3[c] is a stream of plain weight rows:
+//   1. ranks: the lanes of a wave hold 64 consecutive channels of one group (thread t = channel t of the workgroup's G groups);
+//      six ballots on the key bits give each lane the lanes with its key, hence its rank among them and their count, which the
+//      lowest of them writes to tab[wave][key];
+//   2. wave 0 turns the counts into row starts (an exclusive scan over the P rows) and per-chunk list offsets;
+//   3. every item is scattered to its slot {row << 16 | channel, gradient};
+//   4. the waves take runs of the list cut at row boundaries, about T / NW items each; lanes span the C2 output columns
+//      (SPV = C2 / 64 floats per lane: one wave covers a whole weight row), the list is read 64 entries at a time and
+//      broadcast with v_readlane, and 16 weight rows are in flight per wave.  All addresses of a batch are known before its
+//      first FMA - the round-5 pass (row by row: compact, then fetch) had a dependent list / gradient / weights chain per row.
+//      A row's sum stays in registers and is stored once, in the tile layout layer_bwd writes; rows without items store zeros;
+//   5. the layer-2 ReLU mask is applied tile by tile, from the slots the forward wrote (mask words fetched before the stream).
+// Each output element is one fmaf chain over ascending channels, owned by one lane: no atomics, bit-reproducible.  (Not
+// bit-identical to the dense layer: a 32x32x2 MFMA adds two k-products in one step.)  SSG levels 1 - 3 only: KS = 32, P <= 64,
+// G * C3 <= NT, C2 in {64, 128, 256} (run_sa_bwd checks).
+template <int SPV> struct SpVec;
+template <> struct SpVec<1> { using T = float; };
+template <> struct SpVec<2> { using T = float2; };
+template <> struct SpVec<4> { using T = float4; };
+
+template <int P, int NW, int MAXT, int SPV>
+__device__ __forceinline__ void sa_pool_t_sparse(const SaBwdArgs &a, float *__restrict__ buf0, float *__restrict__ dsrc, int key,
+                                                 size_t wg)
+{
+    using L = Lds<P>;
+    using VT = typename SpVec<SPV>::T;
+    constexpr int KS = 32, C2 = 64 * SPV, NT = NW * 64, PB = P / 32, U = 16;
+    static_assert(P <= 64, "one scan lane per row");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int2 *items = (int2 *)(dsrc + a.sp_off);   // [NT]
+    int *tab = (int *)(items + NT);            // [NW][KS]: counts, then list offsets (zeroed by the caller before its barrier)
+    int *rs = tab + NW * KS;                   // [P + 1] row starts
+    // 1. rank among the lanes with the same key (key KS = no gradient)
+    unsigned long long same = ~0ull;
+#pragma unroll
+    for (int bit = 0; bit < 6; ++bit) {
+        const unsigned long long bb = __ballot((key >> bit) & 1);
+        same &= ((key >> bit) & 1) ? bb : ~bb;
+    }
+    const int rank = __popcll(same & ((1ull << lane) - 1ull));
+    if (key < KS && rank == 0) tab[wave * KS + key] = __popcll(same);
+    __syncthreads();
+    // 2. row r = g * KS + k (lane r of wave 0): chunks g * cpg .. g * cpg + cpg - 1 hold the channels of group g
+    if (wave == 0) {
+        const int cpg = a.C3 >> 6, g = lane / KS, k = lane & (KS - 1);
+        int tot = 0;
+        if (lane < P)
+            for (int q = 0; q < cpg; ++q) tot += tab[(g * cpg + q) * KS + k];
+        int inc = tot;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(inc, o);
+            if (lane >= o) inc += v;
+        }
+        int run = inc - tot;
+        if (lane < P) {
+            rs[lane] = run;
+            for (int q = 0; q < cpg; ++q) {
+                int *t = tab + (g * cpg + q) * KS + k;
+                const int c = *t;
+                *t = run;
+                run += c;
+            }
+        }
+        if (lane == 63) rs[P] = inc;   // (lanes >= P count nothing)
+    }
+    __syncthreads();
+    // 3. scatter
+    if (key < KS) {
+        const int g = tid / a.C3, c = tid - g * a.C3;
+        items[tab[wave * KS + key] + rank] = make_int2(((g * KS + key) << 16) | c, __float_as_int(dsrc[tid]));
+    }
+    // mask words of this wave's tiles of dZ2 (layer_bwd's slots), fetched now so that they arrive under the stream
+    const int ntask = (C2 / 32) * PB;
+    unsigned msk[MAXT];
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+        const int task = wave + i * NW;
+        msk[i] = 0xFFFFu;
+        if (task < ntask && a.l3t.mask) msk[i] = a.l3t.mask[(wg * ntask + task) * 64 + lane];
+    }
+    __syncthreads();
+    // 4. stream: this wave's rows [r_lo, r_hi) = the rows whose start lies in its share [lo, hi) of the T items
+    const int T = __builtin_amdgcn_readfirstlane(rs[P]);
+    const int lo = wave * T / NW, hi = (wave + 1) * T / NW;
+    const int rsl = lane < P ? rs[lane] : 0x7fffffff;
+    const int r_lo = __popcll(__ballot(rsl < lo));
+    const int r_hi = wave == NW - 1 ? P : __popcll(__ballot(rsl < hi));
+    const int e_lo = __builtin_amdgcn_readfirstlane(rs[r_lo]), e_hi = __builtin_amdgcn_readfirstlane(rs[r_hi]);
+    const float *wr = a.w3r + lane * SPV;
+    float acc[SPV];
+#pragma unroll
+    for (int e = 0; e < SPV; ++e) acc[e] = 0.0f;
+    int cur = r_lo;
+    auto put = [&](int r) {
+        float *o = buf0 + L::off(lane * SPV, r);
+        if constexpr (SPV == 4) *(float4 *)o = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        else if constexpr (SPV == 2) *(float2 *)o = make_float2(acc[0], acc[1]);
+        else *o = acc[0];
+#pragma unroll
+        for (int e = 0; e < SPV; ++e) acc[e] = 0.0f;
+    };
+    for (int w0 = e_lo; w0 < e_hi; w0 += 64) {
+        const int n = min(64, e_hi - w0);
+        const int2 mine = lane < n ? items[w0 + lane] : make_int2(0, 0);
+        for (int q = 0; q < n; q += U) {
+            VT w[U];
+            int xs[U];
+            float ds[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                xs[u] = __builtin_amdgcn_readlane(mine.x, q + u);
+                ds[u] = __int_as_float(__builtin_amdgcn_readlane(mine.y, q + u));
+                if (q + u < n) w[u] = *(const VT *)(wr + (size_t)(xs[u] & 0xFFFF) * C2);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (q + u < n) {
+                    const int row = xs[u] >> 16;
+                    while (cur < row) put(cur++);
+                    const float *wv = (const float *)&w[u];
+#pragma unroll
+                    for (int e = 0; e < SPV; ++e) acc[e] = fmaf(ds[u], wv[e], acc[e]);
+                }
+            }
+        }
+    }
+    while (cur < r_hi) put(cur++);
+    __syncthreads();
+    // 5. ReLU mask of layer 2, tile by tile (register r of lane (j, h) = element g = r / 4, component r % 4 of its float4s)
+    const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+        const int task = wave + i * NW;
+        if (task < ntask) {
+            const int mb = task / PB, pb = task - mb * PB;
+            float *o = buf0 + (size_t)(mb * 4) * L::BLK + (pb * 32 + j) * 8 + 4 * h;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float4 v = *(float4 *)(o + (size_t)g * L::BLK);
+                v.x = __uint_as_float(__float_as_uint(v.x) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g, 1));
+                v.y = __uint_as_float(__float_as_uint(v.y) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 1, 1));
+                v.z = __uint_as_float(__float_as_uint(v.z) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 2, 1));
+                v.w = __uint_as_float(__float_as_uint(v.w) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 3, 1));
+                *(float4 *)(o + (size_t)g * L::BLK) = v;
+            }
+        }
+    }
+}
+
+// SPV > 0: the max-pool transpose runs as the sparse stream above (sa_pool_t_sparse) instead of dZ3 in LDS + the dense l3t
+// (the kernels sa_bwd_kernel / sa_bwd_sparse_kernel below)
+template <int P, int NW, int MAXT, int KS, int SPV>
+__device__ __forceinline__ void sa_bwd_body(const SaBwdArgs &a)
 {
     using L = Lds<P>;
     static_assert(KS == 32 || KS == 16, "groups of 32 or 16 samples");
+    constexpr bool SPARSE = SPV > 0;
+    static_assert(!SPARSE || KS == 32, "sparse max-pool transpose: groups of 32 samples");
     constexpr int G = P / KS, NT = NW * 64;
     extern __shared__ float lds[];
     float *buf0 = lds;   // the one activation buffer (layers run in place)
@@ -389,18 +550,27 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_kernel(SaBwdArgs a)
     const int nblk = a.C3 >> 3;
     constexpr int NTASK = 4;   // (point, 8-channel block) tasks per thread: P * C3 / 8 / NT = 4 for every SSG level (<= 4 for MSG)
     uint2 am_pre[NTASK];
+    int key = KS;   // sparse: the arg-max sample of channel slot tid of the G groups (KS = no gradient)
+    if constexpr (SPARSE) {
+        if (tid < G * a.C3) {
+            const int v = a.arg[((size_t)b * a.S + s0) * a.C3 + tid];
+            key = v == 255 ? KS : v;
+        }
+    } else {
 #pragma unroll
-    for (int i = 0; i < NTASK; ++i) {
-        const int t = tid + i * NT;
-        am_pre[i] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-        if (t < P * nblk && !PSG_DIAGBIT(a, 1)) {
-            const int pnt = t % P, blk = t / P;
-            am_pre[i] = *(const uint2 *)(a.arg + ((size_t)b * a.S + s0 + pnt / KS) * a.C3 + blk * 8);
+        for (int i = 0; i < NTASK; ++i) {
+            const int t = tid + i * NT;
+            am_pre[i] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+            if (t < P * nblk && !PSG_DIAGBIT(a, 1)) {
+                const int pnt = t % P, blk = t / P;
+                am_pre[i] = *(const uint2 *)(a.arg + ((size_t)b * a.S + s0 + pnt / KS) * a.C3 + blk * 8);
+            }
         }
     }
     // dout[s][c] = skip-link gradient (plain rows) + transposed 3-NN interpolation + transposed grouping of the
     // next level, every sum in a fixed order (ascending fine point / grouped row)
     float *dsrc = lds + (size_t)a.dsrc_blk * L::BLK;   // staging block(s) behind the activation buffer
+    if (SPARSE && tid < NW * KS) ((int *)(dsrc + a.sp_off) + 2 * NT)[tid] = 0;   // sa_pool_t_sparse's count table
     // the rows' slots in the consumer's lists: read now (one coalesced load), used after the last layer - fetched there they
     // were a cache-line miss at the tail of every workgroup
     int32_t *s_pos = (int32_t *)(dsrc + a.pos_off);
@@ -459,32 +629,36 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_kernel(SaBwdArgs a)
         dsrc[t] = acc;
     }
     __syncthreads();
-    // max-pool backward: dZ3[c][g*32+k] = dout[g][c] if k == arg[g][c] else 0.
-    // One (point, 8-channel block) per thread; arg/dout reads are broadcasts across the 32 samples.
+    if constexpr (SPARSE) {
+        if (!PSG_DIAGBIT(a, 8)) sa_pool_t_sparse<P, NW, MAXT, SPV>(a, buf0, dsrc, key, wg);
+    } else {
+        // max-pool backward: dZ3[c][g*32+k] = dout[g][c] if k == arg[g][c] else 0.
+        // One (point, 8-channel block) per thread; arg/dout reads are broadcasts across the 32 samples.
 #pragma unroll
-    for (int i = 0; i < NTASK; ++i) {
-        const int t = tid + i * NT;
-        if (t >= P * nblk || PSG_DIAGBIT(a, 1)) break;
-        const int pnt = t % P, blk = t / P;
-        const int g = pnt / KS, k = pnt & (KS - 1);
-        const uint2 am = am_pre[i];
-        const float *dp = dsrc + (size_t)g * a.C3 + blk * 8;
-        const float4 d0 = *(const float4 *)dp, d1 = *(const float4 *)(dp + 4);
-        float4 v0, v1;
-        v0.x = (int)(am.x & 0xFF) == k ? d0.x : 0.f;
-        v0.y = (int)((am.x >> 8) & 0xFF) == k ? d0.y : 0.f;
-        v0.z = (int)((am.x >> 16) & 0xFF) == k ? d0.z : 0.f;
-        v0.w = (int)(am.x >> 24) == k ? d0.w : 0.f;
-        v1.x = (int)(am.y & 0xFF) == k ? d1.x : 0.f;
-        v1.y = (int)((am.y >> 8) & 0xFF) == k ? d1.y : 0.f;
-        v1.z = (int)((am.y >> 16) & 0xFF) == k ? d1.z : 0.f;
-        v1.w = (int)(am.y >> 24) == k ? d1.w : 0.f;
-        float *dst = buf0 + (size_t)blk * L::BLK + pnt * 8;
-        *(float4 *)dst = v0;
-        *(float4 *)(dst + 4) = v1;
+        for (int i = 0; i < NTASK; ++i) {
+            const int t = tid + i * NT;
+            if (t >= P * nblk || PSG_DIAGBIT(a, 1)) break;
+            const int pnt = t % P, blk = t / P;
+            const int g = pnt / KS, k = pnt & (KS - 1);
+            const uint2 am = am_pre[i];
+            const float *dp = dsrc + (size_t)g * a.C3 + blk * 8;
+            const float4 d0 = *(const float4 *)dp, d1 = *(const float4 *)(dp + 4);
+            float4 v0, v1;
+            v0.x = (int)(am.x & 0xFF) == k ? d0.x : 0.f;
+            v0.y = (int)((am.x >> 8) & 0xFF) == k ? d0.y : 0.f;
+            v0.z = (int)((am.x >> 16) & 0xFF) == k ? d0.z : 0.f;
+            v0.w = (int)(am.x >> 24) == k ? d0.w : 0.f;
+            v1.x = (int)(am.y & 0xFF) == k ? d1.x : 0.f;
+            v1.y = (int)((am.y >> 8) & 0xFF) == k ? d1.y : 0.f;
+            v1.z = (int)((am.y >> 16) & 0xFF) == k ? d1.z : 0.f;
+            v1.w = (int)(am.y >> 24) == k ? d1.w : 0.f;
+            float *dst = buf0 + (size_t)blk * L::BLK + pnt * 8;
+            *(float4 *)dst = v0;
+            *(float4 *)(dst + 4) = v1;
+        }
+        __syncthreads();
+        if (!PSG_DIAGBIT(a, 8)) layer_bwd<P, NW, MAXT>(a.l3t, buf0, wg);
     }
-    __syncthreads();
-    if (!PSG_DIAGBIT(a, 8)) layer_bwd<P, NW, MAXT>(a.l3t, buf0, wg);
     if (!PSG_DIAGBIT(a, 16)) __syncthreads();
     if (!PSG_DIAGBIT(a, 8)) layer_bwd<P, NW, MAXT>(a.l2t, buf0, wg);
     if (!PSG_DIAGBIT(a, 16)) __syncthreads();
@@ -533,6 +707,13 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_kernel(SaBwdArgs a)
         if (pos[j] >= 0) orow[(size_t)pos[j] * a.cg_out + c] = buf0[L::off(c, j)];   // padding rows are not listed
     }
 }
+
+template <int P, int NW, int MAXT, int KS = 32>
+__global__ __launch_bounds__(NW * 64) void sa_bwd_kernel(SaBwdArgs a) { sa_bwd_body<P, NW, MAXT, KS, 0>(a); }
+
+// SSG levels 1 - 3 with the sparse max-pool transpose (run_sa_bwd: PSG_PN2_POOLT_SPARSE); SPV = C2 / 64
+template <int P, int NW, int MAXT, int SPV>
+__global__ __launch_bounds__(NW * 64) void sa_bwd_sparse_kernel(SaBwdArgs a) { sa_bwd_body<P, NW, MAXT, 32, SPV>(a); }
 
 // ------------------------------------------------------------------------------------------ FP fwd
 // FP split (round 5): the 3-NN interpolation is linear, so the interpolated part of a module's first layer commutes with it,
