@@ -53,6 +53,50 @@ void capture_note(CaptureCounters *own, int tried, int failed, int replays, int 
     g_capture[0] += tried; g_capture[1] += failed; g_capture[2] += replays; g_capture[3] += eager;
 }
 
+bool GraphSlot::capture(hipStream_t st, const std::function<int()> &body)
+{
+    bool ok = false;
+    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        const int crc = body();
+        hipGraph_t graph = nullptr;
+        const hipError_t e = hipStreamEndCapture(st, &graph);
+        ok = crc == PSG_OK && e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+        if (!ok) exec = nullptr;
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+    (void)hipGetLastError();
+    capture_failed = !ok;
+    capture_note(&cap, 1, ok ? 0 : 1, 0, 0);
+    return ok;
+}
+
+hipError_t GraphSlot::forget(hipStream_t st)
+{
+    if (exec) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return e;
+        destroy();
+    }
+    capture_failed = false;
+    return hipSuccess;
+}
+
+hipError_t GraphSlot::replay(hipStream_t st, int n)
+{
+    capture_note(&cap, 0, 0, n, 0);
+    for (int i = 0; i < n; ++i) {
+        const hipError_t e = hipGraphLaunch(exec, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+void GraphSlot::destroy()
+{
+    if (exec) (void)hipGraphExecDestroy(exec);
+    exec = nullptr;
+}
+
 hipError_t memset_sync(void *dst, int value, size_t bytes)
 {
     if (bytes == 0) return hipSuccess;

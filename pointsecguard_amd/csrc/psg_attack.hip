@@ -1007,12 +1007,10 @@ static int nu_window_steps(const psg_nu_window_args *a, const float *dconsts_row
 // replay.  The handle remembers ONE window shape: the first window of a shape runs eagerly (it also sets kernel
 // attributes outside any capture), the second is captured, later ones are replayed.
 struct psg_nu_graph {
-    hipGraphExec_t exec = nullptr;
+    psg::GraphSlot slot;
     psg_nu_window_args key;
     uint64_t key_model_gen = 0, key_ws_gen = 0;   // generation numbers of key.model / key.ws: addresses can be re-used (psg_common.h)
     bool have_key = false;
-    bool capture_failed = false;    // the capture of this key failed once: its windows stay eager, no retry at every window
-    psg::CaptureCounters cap;
     float *dconsts = nullptr;       // device [PSG_NU_GRAPH_MAX_STEPS][4]
     float host[PSG_NU_GRAPH_MAX_STEPS * 4];
 };
@@ -1029,7 +1027,7 @@ extern "C" int psg_nu_graph_create(psg_nu_graph **out)
 extern "C" int psg_nu_graph_destroy(psg_nu_graph *g)
 {
     if (!g) return PSG_OK;
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
+    g->slot.destroy();
     (void)hipFree(g->dconsts);
     delete g;
     return PSG_OK;
@@ -1048,7 +1046,8 @@ static bool nu_same_shape(const psg_nu_graph *g, psg_nu_window_args y)
 extern "C" int psg_nu_graph_stats(const psg_nu_graph *g, long long *out4)
 {
     PSG_REQUIRE(g && out4, "psg_nu_graph_stats: null argument");
-    out4[0] = g->cap.tried; out4[1] = g->cap.failed; out4[2] = g->cap.replays; out4[3] = g->cap.eager;
+    const psg::CaptureCounters &c = g->slot.cap;
+    out4[0] = c.tried; out4[1] = c.failed; out4[2] = c.replays; out4[3] = c.eager;
     return PSG_OK;
 }
 
@@ -1073,46 +1072,21 @@ extern "C" int psg_pn2_nu_window(const psg_nu_window_args *a, psg_nu_graph *grap
     }
     PSG_CHECK_HIP(hipMemcpyAsync(graph->dconsts, graph->host, (size_t)a->n_steps * 16, hipMemcpyHostToDevice, st));
     const bool same = graph->have_key && nu_same_shape(graph, *a);
-    if (same && graph->exec) {
-        PSG_CHECK_HIP(hipGraphLaunch(graph->exec, st));
-        psg::capture_note(&graph->cap, 0, 0, 1, 0);
+    psg::GraphSlot &slot = graph->slot;
+    // second window of this shape: capture it, then replay (a failed capture is counted - psg_nu_graph_stats,
+    // psg_capture_stats - and the shape is not tried again: its windows run eagerly below)
+    if (same && !slot.exec && !slot.capture_failed) slot.capture(st, [&] { return nu_window_steps(a, graph->dconsts, stream); });
+    if (same && slot.exec) {
+        PSG_CHECK_HIP(slot.replay(st));
         return PSG_OK;
     }
-    if (same && !graph->capture_failed) {
-        // second window of this shape: capture it, then replay.  A capture that fails (refused on the legacy default stream,
-        // or invalidated - DESIGN 5i names what can do that) has executed nothing: the window runs eagerly below and a genuine
-        // launch error shows again there; the failure is COUNTED (psg_nu_graph_stats, psg_capture_stats) and this shape is
-        // not tried again.
-        bool ok = false;
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int crc = nu_window_steps(a, graph->dconsts, stream);
-            hipGraph_t gr = nullptr;
-            const hipError_t e = hipStreamEndCapture(st, &gr);
-            ok = crc == PSG_OK && e == hipSuccess && gr && hipGraphInstantiate(&graph->exec, gr, nullptr, nullptr, 0) == hipSuccess;
-            if (!ok) graph->exec = nullptr;
-            if (gr) (void)hipGraphDestroy(gr);
-        }
-        (void)hipGetLastError();
-        graph->capture_failed = !ok;
-        psg::capture_note(&graph->cap, 1, ok ? 0 : 1, 0, 0);
-        if (ok) {
-            PSG_CHECK_HIP(hipGraphLaunch(graph->exec, st));
-            psg::capture_note(&graph->cap, 0, 0, 1, 0);
-            return PSG_OK;
-        }
-    }
     if (!same) {
-        if (graph->exec) {              // another shape: forget the old one
-            PSG_CHECK_HIP(hipStreamSynchronize(st));
-            (void)hipGraphExecDestroy(graph->exec);
-            graph->exec = nullptr;
-        }
+        PSG_CHECK_HIP(slot.forget(st));              // another shape: forget the old one
         graph->key = *a;
         graph->key_model_gen = psg::pn2_model_generation(a->model);
         graph->key_ws_gen = psg::pn2_ws_generation(a->ws);
         graph->have_key = true;
-        graph->capture_failed = false;
     }
-    psg::capture_note(&graph->cap, 0, 0, 0, 1);
+    slot.note_eager();
     return nu_window_steps(a, graph->dconsts, stream);
 }

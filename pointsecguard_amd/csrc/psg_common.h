@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -72,11 +73,30 @@ int pn2_forward_lean(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *x0,
 int pn2_backward_colour(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *dlogp, float *dx0_out, psg_stream stream);
 uint64_t pn2_ws_generation(const psg_pn2_ws *ws);
 
-// hipGraph bookkeeping of the three replayed loops (psg_pn2_nu_window, psg_gcn_nb_attack, psg_rla_bim_attack): a capture that
+// hipGraph bookkeeping of the replayed loops (psg_pn2_nb_attack, psg_pn2_nu_window, psg_gcn_nb_attack, psg_rla_bim_attack): a capture that
 // fails falls back to the eager launches - correct, but slower - so it is COUNTED, per handle and for the process
 // (psg_capture_stats), and a handle whose capture failed does not try again for the same key.
 struct CaptureCounters { long long tried = 0, failed = 0, replays = 0, eager = 0; };
 void capture_note(CaptureCounters *own, int tried, int failed, int replays, int eager);
+
+// One instantiated hipGraph of a handle and the capture-or-replay sequence around it (psg_api.hip).  The KEY - what the graph
+// is valid for - and the policy - when to capture, on which stream to replay - stay with the call site; this is the one
+// copy of the fragile part.
+struct GraphSlot {
+    hipGraphExec_t exec = nullptr;
+    bool capture_failed = false;     // the capture for the current key failed once: stay eager instead of trying in every call
+    CaptureCounters cap;
+    // Captures the launches `body` enqueues on `st` (ThreadLocal mode) and instantiates them into `exec`; counted.  A capture
+    // that fails (refused on the legacy default stream, or invalidated - the notes on copy_sync / memset_sync above and DESIGN
+    // 5i name what can do that) has executed nothing: false, `exec` stays null, `capture_failed` is set so that the key is not
+    // tried again, and the caller runs the body eagerly - where a genuine launch error shows again.
+    bool capture(hipStream_t st, const std::function<int()> &body);
+    // the key changed: wait for replays in flight on `st`, drop the graph, allow a new capture
+    hipError_t forget(hipStream_t st);
+    hipError_t replay(hipStream_t st, int n = 1);     // n launches of `exec` on `st`, counted
+    void note_eager(int n = 1) { capture_note(&cap, 0, 0, 0, n); }     // n bodies ran eagerly although a graph was wanted
+    void destroy();                  // in the handle's destructor
+};
 
 // Optional per-launch HIP-event timing of a workspace (psg_*_prof_enable / psg_*_prof_read): pairs of events recorded on
 // the LAUNCH stream around a launch (or a group of launches) with a tag and the algorithmic FLOPs of that launch; off in
@@ -129,6 +149,47 @@ struct EvScope {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+
+// Model weights: a device copy of `h`, recorded on the model's `allocs` (which its destroy frees).  Null when the allocation
+// or the copy failed - after a failed copy the block is already on `allocs` -; model creation turns that into PSG_ERR_HIP.
+template <typename T> T *upload(std::vector<void *> &allocs, const std::vector<T> &h)
+{
+    void *p = nullptr;
+    if (hipMalloc(&p, h.size() * sizeof(T)) != hipSuccess) return nullptr;
+    allocs.push_back(p);
+    if (copy_sync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return (T *)p;
+}
+
+// Workspace arenas: every block 256-byte aligned, carved in a fixed order.  With a null base `take` only counts.
+struct Bump {
+    char *base = nullptr;
+    size_t off = 0;
+    template <typename T> T *take(size_t n)
+    {
+        off = (off + 255) & ~(size_t)255;
+        T *p = base ? (T *)(base + off) : nullptr;
+        off += n * sizeof(T);
+        return p;
+    }
+};
+// Runs `layout(Bump &)` twice: without a base for the size (rounded up to 256 bytes -> *bytes), then on the allocated *arena.
+// A failed hipMalloc is reported under the entry point's name `who`; the caller still owns its handle.
+template <typename Layout> int carve_arena(void **arena, size_t *bytes, const char *who, Layout &&layout)
+{
+    Bump size;
+    layout(size);
+    *bytes = (size.off + 255) & ~(size_t)255;
+    const hipError_t e = hipMalloc(arena, *bytes);
+    if (e != hipSuccess) {
+        set_error("%s: hipMalloc(%zu) failed: %s", who, *bytes, hipGetErrorString(e));
+        return PSG_ERR_HIP;
+    }
+    Bump bp;
+    bp.base = (char *)*arena;
+    layout(bp);
+    return PSG_OK;
+}
 
 }  // namespace psg
 

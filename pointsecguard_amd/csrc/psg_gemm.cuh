@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psg_common.h"
 #include "psg_mlp.cuh"
 
 namespace psg {
@@ -24,20 +25,20 @@ namespace psg {
 enum GemmEpi { EPI_LINEAR = 0, EPI_RELU_AFFINE = 1, EPI_KNN_DIST = 2, EPI_LRELU = 3 };   // LRELU: leaky_relu(0.2), sign bits to mask_out
 
 struct GemmArgs {
-    const float *in;      // [rows][ld_in]
-    const float *w;       // [M][ld_w]
-    const float *bias;    // [M] or null
-    const float *gbias;   // per-group bias [rows / group_rows][M] or null (broadcast concat term)
-    const float *scale;   // [M] affine applied AFTER the ReLU (Conv -> ReLU -> BatchNorm order), or null
-    const float *shift;   // [M]
-    const float *sq;      // EPI_KNN_DIST: [rows] squared norms (same array indexes rows and columns)
-    float *out;           // [rows][ld_out]
-    uint32_t *mask_out;   // ReLU bits out: [rows][ceil(M/32)] words, or null
-    const uint32_t *mask_in;  // multiply the result by these bits (backward through the producer's ReLU), or null
-    int rows, K, M, ld_in, ld_w, ld_out, group_rows;
-    int accumulate;       // 1: out += result;  2: out = addend + result (out is not read)
-    const float *addend;  // with accumulate: out = (out + addend[row][c]) + result  (rows of ld_add floats), or null
-    int ld_add;
+    const float *in = nullptr;      // [rows][ld_in]
+    const float *w = nullptr;       // [M][ld_w]
+    const float *bias = nullptr;    // [M] or null
+    const float *gbias = nullptr;   // per-group bias [rows / group_rows][M] or null (broadcast concat term)
+    const float *scale = nullptr;   // [M] affine applied AFTER the ReLU (Conv -> ReLU -> BatchNorm order), or null
+    const float *shift = nullptr;   // [M]
+    const float *sq = nullptr;      // EPI_KNN_DIST: [rows] squared norms (same array indexes rows and columns)
+    float *out = nullptr;           // [rows][ld_out]
+    uint32_t *mask_out = nullptr;   // ReLU bits out: [rows][ceil(M/32)] words, or null
+    const uint32_t *mask_in = nullptr;  // multiply the result by these bits (backward through the producer's ReLU), or null
+    int rows = 0, K = 0, M = 0, ld_in = 0, ld_w = 0, ld_out = 0, group_rows = 1;
+    int accumulate = 0;             // 1: out += result;  2: out = addend + result (out is not read)
+    const float *addend = nullptr;  // with accumulate: out = (out + addend[row][c]) + result  (rows of ld_add floats), or null
+    int ld_add = 0;
     // derivative of a leaky ReLU applied to what is STORED (after accumulate / addend): out *= (bit ? 1 : post_slope).  The
     // last contributor of a gradient buffer applies the activation's derivative itself instead of a separate pass.
     const uint32_t *post_mask = nullptr;   // [rows][ceil(M/32)] words, or null
@@ -47,6 +48,14 @@ struct GemmArgs {
     const float *pre_add = nullptr;
     int ld_pre = 0;
 };
+
+inline GemmArgs gemm_args(const float *in, int ld_in, const float *w, int ld_w, float *out, int ld_out, int rows, int K, int M)
+{
+    GemmArgs a;
+    a.in = in; a.ld_in = ld_in; a.w = w; a.ld_w = ld_w; a.out = out; a.ld_out = ld_out;
+    a.rows = rows; a.K = K; a.M = M;
+    return a;
+}
 
 // TQ x TI = 32-row x 32-channel MFMA tiles per wave (2 x 2 by default; 1 x 1 gives 64 x 64 workgroup tiles, i.e. four
 // times as many workgroups, for the per-vertex GEMMs of a single 4096-point room that would otherwise occupy 16-32 CUs)
@@ -420,6 +429,22 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(GemmArgs a)
             }
         }
     }
+}
+
+// gemm_rows_kernel<WM, WN> on 64 WM x 64 WN workgroup tiles - or, when that grid has fewer than `small_below` workgroups, on
+// 64 x 64 tiles, one MFMA tile per wave and four times as many workgroups (the per-vertex / per-room GEMMs that would
+// otherwise leave most of the 256 CUs idle; K is short there, so the launch is latency-bound: 4 ResGCN rooms 31.6 -> 11 us).
+// The tile shape changes which workgroup computes an element, not its k order: same results.  Never for ASC_K.
+template <int WM, int WN, int EPI, bool ASC>
+int launch_gemm(const GemmArgs &a, size_t small_below, hipStream_t st)
+{
+    const dim3 grid(ceil_div(a.rows, 64 * WM), ceil_div(a.M, 64 * WN));
+    if (!ASC && (size_t)grid.x * grid.y < small_below)
+        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, ASC, 1, 1>), dim3(ceil_div(a.rows, 64), ceil_div(a.M, 64)), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((gemm_rows_kernel<WM, WN, EPI, ASC>), grid, dim3(256), 0, st, a);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
 }
 
 }  // namespace psg

@@ -17,28 +17,10 @@ using namespace psg;
 
 namespace {
 
-GemmArgs ops_args(const float *in, int ld_in, const float *w, int ld_w, float *out, int ld_out, int rows, int K, int M)
-{
-    GemmArgs a;
-    a.in = in; a.w = w; a.bias = nullptr; a.gbias = nullptr; a.scale = nullptr; a.shift = nullptr; a.sq = nullptr;
-    a.out = out; a.mask_out = nullptr; a.mask_in = nullptr;
-    a.rows = rows; a.K = K; a.M = M; a.ld_in = ld_in; a.ld_w = ld_w; a.ld_out = ld_out; a.group_rows = 1;
-    a.accumulate = 0; a.addend = nullptr; a.ld_add = 0;
-    return a;
-}
-
 template <int EPI>
 int ops_gemm(const GemmArgs &a, hipStream_t st)
 {
-    dim3 grid(ceil_div(a.rows, 128), ceil_div(a.M, 128));
-    if ((size_t)grid.x * grid.y < 128) {   // few 128-wide tiles: 64 x 64 tiles, one MFMA tile per wave
-        dim3 small(ceil_div(a.rows, 64), ceil_div(a.M, 64));
-        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, false, 1, 1>), small, dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, false>), grid, dim3(256), 0, st, a);
-    }
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
+    return launch_gemm<2, 2, EPI, false>(a, 128, st);
 }
 
 // rows[(b, s, k)][:] = [xyz[b][g] - new_xyz[b][s] (3), feat[b][g][0..D)]  with g = gidx[b][s][k]
@@ -189,7 +171,7 @@ extern "C" int psg_pw_mlp_fwd(const float *in, int ld_in, int rows, int K, const
 {
     PSG_REQUIRE(in && w && out && rows > 0 && K > 0 && M > 0, "psg_pw_mlp_fwd: bad argument");
     PSG_REQUIRE((!scale && !shift) || (relu && scale && shift), "psg_pw_mlp_fwd: the affine follows the ReLU (needs relu, scale and shift)");
-    GemmArgs a = ops_args(in, ld_in, w, K, out, ld_out, rows, K, M);
+    GemmArgs a = gemm_args(in, ld_in, w, K, out, ld_out, rows, K, M);
     a.bias = bias;
     a.scale = scale; a.shift = shift;
     a.mask_out = mask_out;
@@ -201,7 +183,7 @@ extern "C" int psg_pw_mlp_bwd(const float *dout, int ld_dout, int rows, int M, c
                               float *din, int ld_din, psg_stream stream)
 {
     PSG_REQUIRE(dout && wT && din && rows > 0 && K > 0 && M > 0, "psg_pw_mlp_bwd: bad argument");
-    GemmArgs a = ops_args(dout, ld_dout, wT, M, din, ld_din, rows, M, K);
+    GemmArgs a = gemm_args(dout, ld_dout, wT, M, din, ld_din, rows, M, K);
     a.mask_in = mask_below;
     return ops_gemm<EPI_LINEAR>(a, (hipStream_t)stream);
 }

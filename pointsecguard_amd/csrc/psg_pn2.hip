@@ -245,14 +245,13 @@ struct psg_pn2_ws {
     int32_t *nb_labels;       // [B][N]
     int32_t *nb_starts;       // [F][4][B]
     uint8_t *nb_mask;         // [N]
-    hipGraphExec_t nb_exec = nullptr;
+    psg::GraphSlot nb;
     struct NbKey { uint64_t model_gen; float eps, alpha; int iters, targeted, target, has_mask, has_labels, pad; } nb_key{};   // (no padding bytes: compared with memcmp)
-    bool nb_have_key = false, nb_capture_failed = false;
+    bool nb_have_key = false;
     // the graph is captured and replayed on a non-blocking stream of the workspace, fenced against the caller's stream with two
     // events: the reference's harness calls from the legacy default stream, which cannot capture
     hipStream_t nb_stream = nullptr;
     hipEvent_t nb_ev[2] = {nullptr, nullptr};
-    psg::CaptureCounters cap;
     // optional per-launch HIP-event timing (psg_pn2_prof_enable); off in normal operation
     // attack loops: module outputs nobody reads are not written (fp2 - fp4 under the FP split: the finer module gathers T rows)
     bool lean = false;
@@ -330,18 +329,6 @@ std::vector<float> k8_major_padded(const std::vector<float> &packed, int mb, int
                       out.begin() + ((size_t)k * mb + m) * 256);
     return out;
 }
-
-struct Bump {
-    char *base = nullptr;
-    size_t off = 0;
-    template <typename T> T *take(size_t n)
-    {
-        off = (off + 255) & ~(size_t)255;
-        T *p = base ? (T *)(base + off) : nullptr;
-        off += n * sizeof(T);
-        return p;
-    }
-};
 
 FwdLayer fwd_layer(const PackedLayer &p, bool relu, uint16_t *mask)
 {
@@ -1193,10 +1180,8 @@ __global__ void dx0_gather_pgd_kernel(const int32_t *__restrict__ inv_off, const
     }
 }
 
-size_t ws_layout(psg_pn2_ws *ws, char *base)
+void ws_layout(psg_pn2_ws *ws, Bump &bp)
 {
-    Bump bp;
-    bp.base = base;
     const ArchDesc &A = *ws->arch;
     const int B = ws->B, F = ws->F;
     const size_t PR = (size_t)F * B;
@@ -1262,7 +1247,6 @@ size_t ws_layout(psg_pn2_ws *ws, char *base)
     ws->nb_labels = bp.take<int32_t>((size_t)B * ws->N);
     ws->nb_starts = bp.take<int32_t>((size_t)F * 4 * B);
     ws->nb_mask = bp.take<uint8_t>((size_t)ws->N);
-    return (bp.off + 255) & ~(size_t)255;
 }
 
 }  // namespace
@@ -1451,14 +1435,10 @@ extern "C" int psg_pn2_ws_create_arch(psg_ctx *ctx, int arch, int batch, int n_p
     ws->ctx = ctx; ws->arch = &arch_of(arch); ws->B = batch; ws->N = n_point; ws->F = max_forwards;
     ws->Nl[0] = n_point;
     for (int l = 0; l < 4; ++l) ws->Nl[l + 1] = kS[l];
-    ws->bytes = ws_layout(ws, nullptr);
-    hipError_t e = hipMalloc(&ws->arena, ws->bytes);
-    if (e != hipSuccess) {
-        set_error("psg_pn2_ws_create: hipMalloc(%zu) failed: %s", ws->bytes, hipGetErrorString(e));
+    if (int rc = carve_arena(&ws->arena, &ws->bytes, "psg_pn2_ws_create", [&](Bump &bp) { ws_layout(ws, bp); })) {
         delete ws;
-        return PSG_ERR_HIP;
+        return rc;
     }
-    ws_layout(ws, (char *)ws->arena);
     *out = ws;
     return PSG_OK;
 }
@@ -1471,7 +1451,7 @@ extern "C" int psg_pn2_ws_create(psg_ctx *ctx, int batch, int n_point, int max_f
 extern "C" int psg_pn2_ws_destroy(psg_pn2_ws *ws)
 {
     if (!ws) return PSG_OK;
-    if (ws->nb_exec) (void)hipGraphExecDestroy(ws->nb_exec);
+    ws->nb.destroy();
     for (hipEvent_t e : ws->nb_ev) if (e) (void)hipEventDestroy(e);
     if (ws->nb_stream) (void)hipStreamDestroy(ws->nb_stream);
     if (ws->arena) (void)hipFree(ws->arena);
@@ -1793,7 +1773,7 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
     if (use_graph && B <= 16 && !ws->prof_on) {
         const psg_pn2_ws::NbKey key{m->gen, eps, alpha, iters, targeted ? 1 : 0, targeted ? target : 0, mask ? 1 : 0, targeted ? 0 : 1, 0};
         const bool same = ws->nb_have_key && memcmp(&key, &ws->nb_key, sizeof(key)) == 0;
-        if (same && !ws->nb_capture_failed) {
+        if (same && !ws->nb.capture_failed) {
             if (!ws->nb_stream) {
                 PSG_CHECK_HIP(hipStreamCreateWithFlags(&ws->nb_stream, hipStreamNonBlocking));
                 for (hipEvent_t &e : ws->nb_ev) PSG_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1802,23 +1782,8 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
             // the graph stream starts after everything the caller's stream holds so far (the copies above included) ..
             PSG_CHECK_HIP(hipEventRecord(ws->nb_ev[0], st));
             PSG_CHECK_HIP(hipStreamWaitEvent(gs, ws->nb_ev[0], 0));
-            if (!ws->nb_exec) {
-                bool ok = false;
-                if (hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    const int crc = body(gs);
-                    hipGraph_t gr = nullptr;
-                    const hipError_t e = hipStreamEndCapture(gs, &gr);
-                    ok = crc == PSG_OK && e == hipSuccess && gr && hipGraphInstantiate(&ws->nb_exec, gr, nullptr, nullptr, 0) == hipSuccess;
-                    if (!ok) ws->nb_exec = nullptr;
-                    if (gr) (void)hipGraphDestroy(gr);
-                }
-                (void)hipGetLastError();
-                ws->nb_capture_failed = !ok;
-                psg::capture_note(&ws->cap, 1, ok ? 0 : 1, 0, 0);
-            }
-            if (ws->nb_exec) {
-                PSG_CHECK_HIP(hipGraphLaunch(ws->nb_exec, gs));
-                psg::capture_note(&ws->cap, 0, 0, 1, 0);
+            if (ws->nb.exec || ws->nb.capture(gs, [&] { return body(gs); })) {
+                PSG_CHECK_HIP(ws->nb.replay(gs));
                 ws->planned = iters; ws->fwd_slot = iters - 1; ws->x0_fwd = ws->x0;      // (the host-side state the eager body leaves)
                 // .. and the caller's stream goes on after the attack
                 PSG_CHECK_HIP(hipEventRecord(ws->nb_ev[1], gs));
@@ -1827,16 +1792,11 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
             }
         }
         if (!same) {
-            if (ws->nb_exec) {
-                PSG_CHECK_HIP(hipStreamSynchronize(st));
-                (void)hipGraphExecDestroy(ws->nb_exec);
-                ws->nb_exec = nullptr;
-            }
+            PSG_CHECK_HIP(ws->nb.forget(st));
             ws->nb_key = key;
             ws->nb_have_key = true;
-            ws->nb_capture_failed = false;
         }
-        psg::capture_note(&ws->cap, 0, 0, 0, 1);
+        ws->nb.note_eager();
     }
     if ((rc = body(st))) return rc;
     return psg_to_channel_major(ws->x0, B, 9, N, adv_out, st);

@@ -48,30 +48,11 @@ constexpr int LDIM[NL][2] = {{64, 6}, {128, 64}, {1024, 128}, {512, 1024}, {256,
                              {512, 1088}, {256, 512}, {128, 256}, {13, 128}};
 static_assert(sizeof(LDIM) / sizeof(LDIM[0]) == NL, "layer table");
 
-GemmArgs gargs(const float *in, int ld_in, const float *w, int ld_w, float *out, int ld_out, int rows, int K, int M)
-{
-    GemmArgs a;
-    a.in = in; a.w = w; a.bias = nullptr; a.gbias = nullptr; a.scale = nullptr; a.shift = nullptr; a.sq = nullptr;
-    a.out = out; a.mask_out = nullptr; a.mask_in = nullptr;
-    a.rows = rows; a.K = K; a.M = M; a.ld_in = ld_in; a.ld_w = ld_w; a.ld_out = ld_out; a.group_rows = 1;
-    a.accumulate = 0; a.addend = nullptr; a.ld_add = 0;
-    return a;
-}
-
-// 128 x 128 tiles, or 64 x 64 tiles when the larger ones would leave most of the 256 CUs idle (the per-room and per-batch
-// GEMMs); the tile shape changes which workgroup computes an element, not its k order, so the results are the same
+// 128 x 128 tiles, or 64 x 64 tiles for the per-room and per-batch GEMMs (psg_gemm.cuh)
 template <int EPI>
 int run_gemm(const GemmArgs &a, hipStream_t st)
 {
-    const dim3 big(ceil_div(a.rows, 128), ceil_div(a.M, 128));
-    if ((size_t)big.x * big.y < 384) {
-        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, false, 1, 1>), dim3(ceil_div(a.rows, 64), ceil_div(a.M, 64)), dim3(256), 0,
-                           st, a);
-    } else {
-        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, false>), big, dim3(256), 0, st, a);
-    }
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
+    return launch_gemm<2, 2, EPI, false>(a, 384, st);
 }
 
 // ---- 128 -> 1024 layer with the max-pool epilogue.  in [rows][K] (rows = B*N, N a multiple of PT), w [M][K], bias [M].
@@ -435,23 +416,23 @@ int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, fl
     };
     // fc1 -> fc2 -> fc3 (+ identity, folded into fc3's bias) of a transform net on the pooled vector
     auto tail = [&](int which, int lf1, float *f1, uint32_t *mf1, float *f2, uint32_t *mf2, float *out, int kk) -> int {
-        GemmArgs a = gargs(ws->pool + which * GF, 3 * GF, W(lf1), GF, f1, 512, B, GF, 512);
+        GemmArgs a = gemm_args(ws->pool + which * GF, 3 * GF, W(lf1), GF, f1, 512, B, GF, 512);
         a.bias = Bi(lf1); a.mask_out = mf1;
         if (int r = run_gemm<EPI_RELU_AFFINE>(a, st)) return r;
-        a = gargs(f1, 512, W(lf1 + 1), 512, f2, 256, B, 512, 256);
+        a = gemm_args(f1, 512, W(lf1 + 1), 512, f2, 256, B, 512, 256);
         a.bias = Bi(lf1 + 1); a.mask_out = mf2;
         if (int r = run_gemm<EPI_RELU_AFFINE>(a, st)) return r;
-        a = gargs(f2, 256, W(lf1 + 2), 256, out, kk, B, 256, kk);
+        a = gemm_args(f2, 256, W(lf1 + 2), 256, out, kk, B, 256, kk);
         a.bias = Bi(lf1 + 2);
         return run_gemm<EPI_LINEAR>(a, st);
     };
 
     // ---- STN3d on x[:, :6]
     {
-        GemmArgs a = gargs(x, 9, W(L_A1), 6, ws->a1, 64, R, 6, 64);
+        GemmArgs a = gemm_args(x, 9, W(L_A1), 6, ws->a1, 64, R, 6, 64);
         a.bias = Bi(L_A1);
         if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
-        a = gargs(ws->a1, 64, W(L_A2), 64, ws->a2, 128, R, 64, 128);
+        a = gemm_args(ws->a1, 64, W(L_A2), 64, ws->a2, 128, R, 64, 128);
         a.bias = Bi(L_A2);
         if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
         if ((rc = pool_layer(ws->a2, L_A3, 1, 0))) return rc;
@@ -459,22 +440,22 @@ int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, fl
     }
     // ---- encoder conv1 with trans folded in per room: W1f_b = [W[:, 0:3] trans_b^T | W[:, 3:6]]
     {
-        GemmArgs a = gargs(W(L_C1), 6, ws->trans, 3, ws->t1, B * 3, 64, 3, B * 3);
+        GemmArgs a = gemm_args(W(L_C1), 6, ws->trans, 3, ws->t1, B * 3, 64, 3, B * 3);
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
         hipLaunchKernelGGL(pn_c1_assemble_kernel, dim3(grid1((size_t)B * 512)), dim3(256), 0, st, ws->t1, W(L_C1), B, ws->w1f);
         PSG_LAUNCH_CHECK();
         for (int b = 0; b < B; ++b) {
-            a = gargs(x + (size_t)b * N * 9, 9, ws->w1f + b * 512, 8, ws->h + (size_t)b * N * 64, 64, N, 6, 64);
+            a = gemm_args(x + (size_t)b * N * 9, 9, ws->w1f + b * 512, 8, ws->h + (size_t)b * N * 64, 64, N, 6, 64);
             a.bias = Bi(L_C1); a.mask_out = ws->mh + (size_t)b * N * 2;
             if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
         }
     }
     // ---- STNkd on h
     {
-        GemmArgs a = gargs(ws->h, 64, W(L_K1), 64, ws->k1, 64, R, 64, 64);
+        GemmArgs a = gemm_args(ws->h, 64, W(L_K1), 64, ws->k1, 64, R, 64, 64);
         a.bias = Bi(L_K1);
         if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
-        a = gargs(ws->k1, 64, W(L_K2), 64, ws->k2, 128, R, 64, 128);
+        a = gemm_args(ws->k1, 64, W(L_K2), 64, ws->k2, 128, R, 64, 128);
         a.bias = Bi(L_K2);
         if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
         if ((rc = pool_layer(ws->k2, L_K3, 1, 1))) return rc;
@@ -483,12 +464,12 @@ int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, fl
     // ---- trans_feat folded into conv2 and into the head's pointfeat columns: (W T_b^T)[o][i] = sum_j W[o][j] T_b[i][j],
     // one GEMM for all rooms (the B transforms stacked as the [B*64][64] weight operand)
     {
-        GemmArgs a = gargs(W(L_C2), 64, ws->tf, 64, ws->c2f, B * 64, 128, 64, B * 64);
+        GemmArgs a = gemm_args(W(L_C2), 64, ws->tf, 64, ws->c2f, B * 64, 128, 64, B * 64);
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-        a = gargs(W(L_H1) + GF, 1088, ws->tf, 64, ws->h1pf, B * 64, 512, 64, B * 64);
+        a = gemm_args(W(L_H1) + GF, 1088, ws->tf, 64, ws->h1pf, B * 64, 512, 64, B * 64);
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
         for (int b = 0; b < B; ++b) {
-            a = gargs(ws->h + (size_t)b * N * 64, 64, ws->c2f + b * 64, B * 64, ws->e2 + (size_t)b * N * 128, 128, N, 64, 128);
+            a = gemm_args(ws->h + (size_t)b * N * 64, 64, ws->c2f + b * 64, B * 64, ws->e2 + (size_t)b * N * 128, 128, N, 64, 128);
             a.bias = Bi(L_C2);
             if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
         }
@@ -496,21 +477,21 @@ int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, fl
     }
     // ---- head: conv1's global columns as a per-room bias, the pointfeat columns with trans_feat folded in
     {
-        GemmArgs a = gargs(ws->pool + 2 * GF, 3 * GF, W(L_H1), 1088, ws->gb, 512, B, GF, 512);
+        GemmArgs a = gemm_args(ws->pool + 2 * GF, 3 * GF, W(L_H1), 1088, ws->gb, 512, B, GF, 512);
         a.bias = Bi(L_H1);
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
         for (int b = 0; b < B; ++b) {
-            a = gargs(ws->h + (size_t)b * N * 64, 64, ws->h1pf + b * 64, B * 64, ws->z1 + (size_t)b * N * 512, 512, N, 64, 512);
+            a = gemm_args(ws->h + (size_t)b * N * 64, 64, ws->h1pf + b * 64, B * 64, ws->z1 + (size_t)b * N * 512, 512, N, 64, 512);
             a.gbias = ws->gb + b * 512; a.group_rows = N; a.mask_out = ws->m1 + (size_t)b * N * 16;
             if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
         }
-        a = gargs(ws->z1, 512, W(L_H2), 512, ws->z2, 256, R, 512, 256);
+        a = gemm_args(ws->z1, 512, W(L_H2), 512, ws->z2, 256, R, 512, 256);
         a.bias = Bi(L_H2); a.mask_out = ws->m2;
         if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
-        a = gargs(ws->z2, 256, W(L_H3), 256, ws->z3, 128, R, 256, 128);
+        a = gemm_args(ws->z2, 256, W(L_H3), 256, ws->z3, 128, R, 256, 128);
         a.bias = Bi(L_H3); a.mask_out = ws->m3;
         if ((rc = run_gemm<EPI_RELU_AFFINE>(a, st))) return rc;
-        a = gargs(ws->z3, 128, W(L_H4), 128, ws->logits, NCLS, R, 128, NCLS);
+        a = gemm_args(ws->z3, 128, W(L_H4), 128, ws->logits, NCLS, R, 128, NCLS);
         a.bias = Bi(L_H4);
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
         hipLaunchKernelGGL(pn_log_softmax_kernel, dim3(grid1(R)), dim3(256), 0, st, ws->logits, (size_t)R, ws->logp);
@@ -530,21 +511,21 @@ int backward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *dlogp
     // ---- head transposes through the stored ReLU bits
     hipLaunchKernelGGL(pn_log_softmax_bwd_kernel, dim3(grid1(R)), dim3(256), 0, st, ws->logp, dlogp, (size_t)R, ws->dz4);
     PSG_LAUNCH_CHECK();
-    GemmArgs a = gargs(ws->dz4, NCLS, m->h4t, NCLS, ws->dz3, 128, R, NCLS, 128);
+    GemmArgs a = gemm_args(ws->dz4, NCLS, m->h4t, NCLS, ws->dz3, 128, R, NCLS, 128);
     a.mask_in = ws->m3;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-    a = gargs(ws->dz3, 128, m->h3t, 128, ws->dz2, 256, R, 128, 256);
+    a = gemm_args(ws->dz3, 128, m->h3t, 128, ws->dz2, 256, R, 128, 256);
     a.mask_in = ws->m2;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-    a = gargs(ws->dz2, 256, m->h2t, 256, ws->dz1, 512, R, 256, 512);
+    a = gemm_args(ws->dz2, 256, m->h2t, 256, ws->dz1, 512, R, 256, 512);
     a.mask_in = ws->m1;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
     // pointfeat gradient (dense part) and the global branch: column sum of dz1, then W1g^T
-    a = gargs(ws->dz1, 512, m->h1pt, 512, ws->dpf, 64, R, 512, 64);
+    a = gemm_args(ws->dz1, 512, m->h1pt, 512, ws->dpf, 64, R, 512, 64);
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
     hipLaunchKernelGGL(pn_colsum_kernel, dim3(512 / 64, B), dim3(256), 0, st, ws->dz1, N, 512, ws->s1);
     PSG_LAUNCH_CHECK();
-    a = gargs(ws->s1, 512, m->h1gt, 512, ws->dg, GF, B, 512, GF);
+    a = gemm_args(ws->s1, 512, m->h1gt, 512, ws->dg, GF, B, 512, GF);
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
     // encoder max-pool (no ReLU before it): arg-max rows through conv3^T and conv2^T into dpf
     PoolBwdArgs pa{};
@@ -560,21 +541,21 @@ int backward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *dlogp
     hipLaunchKernelGGL(pn_transpose_kernel, tg, dim3(256), 0, st, ws->dpf, N, 64, ws->dpft);
     PSG_LAUNCH_CHECK();
     for (int b = 0; b < B; ++b) {
-        a = gargs(ws->ht + (size_t)b * 64 * N, N, ws->dpft + (size_t)b * 64 * N, N, ws->dtf + (size_t)b * 4096, 64, 64, N, 64);
+        a = gemm_args(ws->ht + (size_t)b * 64 * N, N, ws->dpft + (size_t)b * 64 * N, N, ws->dtf + (size_t)b * 4096, 64, 64, N, 64);
         if (dtf_up) { a.accumulate = 2; a.addend = dtf_up + (size_t)b * 4096; a.ld_add = 64; }
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-        a = gargs(ws->dpf + (size_t)b * N * 64, 64, ws->tf + (size_t)b * 4096, 64, ws->dh + (size_t)b * N * 64, 64, N, 64, 64);
+        a = gemm_args(ws->dpf + (size_t)b * N * 64, 64, ws->tf + (size_t)b * 4096, 64, ws->dh + (size_t)b * N * 64, 64, N, 64, 64);
         a.mask_in = ws->mh + (size_t)b * N * 2;
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
     }
     // STNkd: fc3^T, fc2^T, fc1^T, then its max-pool sparsely through conv3^T, conv2^T, conv1^T into dh
-    a = gargs(ws->dtf, 4096, m->fk3t, 4096, ws->dfk2, 256, B, 4096, 256);
+    a = gemm_args(ws->dtf, 4096, m->fk3t, 4096, ws->dfk2, 256, B, 4096, 256);
     a.mask_in = ws->mfk2;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-    a = gargs(ws->dfk2, 256, m->fk2t, 256, ws->dfk1, 512, B, 256, 512);
+    a = gemm_args(ws->dfk2, 256, m->fk2t, 256, ws->dfk1, 512, B, 256, 512);
     a.mask_in = ws->mfk1;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-    a = gargs(ws->dfk1, 512, m->fk1t, 512, ws->dgk, GF, B, 512, GF);
+    a = gemm_args(ws->dfk1, 512, m->fk1t, 512, ws->dgk, GF, B, 512, GF);
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
     pa.coef = ws->dgk; pa.pool = ws->pool + GF; pa.idx = ws->pidx + GF; pa.relu_pool = 1;
     pa.w3 = m->w[L_K3]; pa.act2 = ws->k2; pa.w2 = m->w[L_K2]; pa.act1 = ws->k1; pa.w1 = m->w[L_K1]; pa.out_mask = ws->h;
@@ -582,18 +563,18 @@ int backward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *dlogp
     hipLaunchKernelGGL(pn_pool_bwd_kernel, dim3(GF, B), dim3(128), 0, st, pa);
     PSG_LAUNCH_CHECK();
     // encoder conv1^T (unfolded weights: d(xyz . trans) and d rgb), then the input transform
-    a = gargs(ws->dh, 64, m->c1t, 64, ws->dxu, 8, R, 64, 6);
+    a = gemm_args(ws->dh, 64, m->c1t, 64, ws->dxu, 8, R, 64, 6);
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
     hipLaunchKernelGGL(pn_xyz_bwd_kernel, dim3(B), dim3(256), 0, st, ws->x0in, ws->dxu, ws->trans, N, dx0_out, ws->dtrans);
     PSG_LAUNCH_CHECK();
     // STN3d: fc3^T, fc2^T, fc1^T, then its max-pool sparsely through conv3^T, conv2^T, conv1^T into dx0[:, 0:6]
-    a = gargs(ws->dtrans, 9, m->f3t, 9, ws->df2, 256, B, 9, 256);
+    a = gemm_args(ws->dtrans, 9, m->f3t, 9, ws->df2, 256, B, 9, 256);
     a.mask_in = ws->mf2;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-    a = gargs(ws->df2, 256, m->f2t, 256, ws->df1, 512, B, 256, 512);
+    a = gemm_args(ws->df2, 256, m->f2t, 256, ws->df1, 512, B, 256, 512);
     a.mask_in = ws->mf1;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
-    a = gargs(ws->df1, 512, m->f1t, 512, ws->dgs, GF, B, 512, GF);
+    a = gemm_args(ws->df1, 512, m->f1t, 512, ws->dgs, GF, B, 512, GF);
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
     pa.coef = ws->dgs; pa.pool = ws->pool; pa.idx = ws->pidx; pa.relu_pool = 1;
     pa.w3 = m->w[L_A3]; pa.act2 = ws->a2; pa.w2 = m->w[L_A2]; pa.act1 = ws->a1; pa.w1 = m->w[L_A1]; pa.out_mask = nullptr;
@@ -601,15 +582,6 @@ int backward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *dlogp
     hipLaunchKernelGGL(pn_pool_bwd_kernel, dim3(GF, B), dim3(128), 0, st, pa);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
-}
-
-template <typename T> T *upload(psg_pointnet_model *m, const std::vector<T> &h)
-{
-    void *p = nullptr;
-    if (hipMalloc(&p, h.size() * sizeof(T)) != hipSuccess) return nullptr;
-    m->allocs.push_back(p);
-    if (psg::copy_sync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return (T *)p;
 }
 
 // [in][out] transpose of columns [c0, c0 + cols) of a row-major [rows][ld] matrix
@@ -634,12 +606,12 @@ extern "C" int psg_pointnet_model_create(psg_ctx *ctx, const float *const *weigh
     bool ok = true;
     for (int l = 0; l < NL && ok; ++l) {
         const int M = LDIM[l][0], K = LDIM[l][1];
-        m->w[l] = upload(m, std::vector<float>(weights[l], weights[l] + (size_t)M * K));
-        m->b[l] = upload(m, std::vector<float>(biases[l], biases[l] + M));
+        m->w[l] = upload(m->allocs, std::vector<float>(weights[l], weights[l] + (size_t)M * K));
+        m->b[l] = upload(m->allocs, std::vector<float>(biases[l], biases[l] + M));
         ok = m->w[l] && m->b[l];
     }
     auto T = [&](int l, int c0, int cols) {
-        float *p = upload(m, transpose_cols(weights[l], LDIM[l][0], LDIM[l][1], c0, cols));
+        float *p = upload(m->allocs, transpose_cols(weights[l], LDIM[l][0], LDIM[l][1], c0, cols));
         ok = ok && p;
         return p;
     };
@@ -677,40 +649,29 @@ extern "C" int psg_pointnet_ws_create(psg_ctx *ctx, int batch, int n_point, psg_
     auto *ws = new psg_pointnet_ws();
     ws->ctx = ctx; ws->B = batch; ws->N = n_point;
     const size_t B = batch, R = (size_t)batch * n_point, T = R / PT;
-    // carve the arena: every block 256-byte aligned
-    struct Item { void **p; size_t bytes; };
-    std::vector<Item> items;
-    auto F = [&](float **p, size_t n) { items.push_back({(void **)p, n * 4}); };
-    auto I = [&](int32_t **p, size_t n) { items.push_back({(void **)p, n * 4}); };
-    auto U = [&](uint32_t **p, size_t n) { items.push_back({(void **)p, n * 4}); };
-    F(&ws->a1, R * 64); F(&ws->a2, R * 128); F(&ws->h, R * 64); F(&ws->k1, R * 64); F(&ws->k2, R * 128); F(&ws->e2, R * 128);
-    F(&ws->z1, R * 512); F(&ws->z2, R * 256); F(&ws->z3, R * 128); F(&ws->logits, R * NCLS); F(&ws->logp, R * NCLS);
-    U(&ws->mh, R * 2); U(&ws->m1, R * 16); U(&ws->m2, R * 8); U(&ws->m3, R * 4);
-    F(&ws->part_val, T * GF); I(&ws->part_idx, T * GF); F(&ws->pool, B * 3 * GF); I(&ws->pidx, B * 3 * GF);
-    F(&ws->f1, B * 512); F(&ws->f2, B * 256); F(&ws->trans, B * 9); F(&ws->fk1, B * 512); F(&ws->fk2, B * 256); F(&ws->tf, B * 4096);
-    U(&ws->mf1, B * 16); U(&ws->mf2, B * 8); U(&ws->mfk1, B * 16); U(&ws->mfk2, B * 8);
-    F(&ws->t1, 64 * B * 3); F(&ws->w1f, B * 512); F(&ws->c2f, 128 * B * 64); F(&ws->h1pf, 512 * B * 64); F(&ws->gb, B * 512);
-    F(&ws->x0in, R * 9);
-    F(&ws->dz4, R * NCLS); F(&ws->dz3, R * 128); F(&ws->dz2, R * 256); F(&ws->dz1, R * 512); F(&ws->s1, B * 512); F(&ws->dg, B * GF);
-    F(&ws->dpf, R * 64); F(&ws->ht, R * 64); F(&ws->dpft, R * 64); F(&ws->dtf, B * 4096); F(&ws->dfk2, B * 256);
-    F(&ws->dfk1, B * 512); F(&ws->dgk, B * GF); F(&ws->dh, R * 64); F(&ws->dxu, R * 8); F(&ws->dtrans, B * 9);
-    F(&ws->df2, B * 256); F(&ws->df1, B * 512); F(&ws->dgs, B * GF);
-    F(&ws->x0, R * 9); F(&ws->ori, R * 3); F(&ws->dlogp, R * NCLS); F(&ws->dx0, R * 9);
-    I(&ws->labels, R);
-    items.push_back({(void **)&ws->mask, (size_t)n_point});
-    size_t total = 0;
-    for (const Item &it : items) total += (it.bytes + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&ws->arena, total);
-    if (e != hipSuccess) {
-        set_error("psg_pointnet_ws_create: hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+    auto layout = [&](Bump &bp) {
+        auto F = [&](float **p, size_t n) { *p = bp.take<float>(n); };
+        auto I = [&](int32_t **p, size_t n) { *p = bp.take<int32_t>(n); };
+        auto U = [&](uint32_t **p, size_t n) { *p = bp.take<uint32_t>(n); };
+        F(&ws->a1, R * 64); F(&ws->a2, R * 128); F(&ws->h, R * 64); F(&ws->k1, R * 64); F(&ws->k2, R * 128); F(&ws->e2, R * 128);
+        F(&ws->z1, R * 512); F(&ws->z2, R * 256); F(&ws->z3, R * 128); F(&ws->logits, R * NCLS); F(&ws->logp, R * NCLS);
+        U(&ws->mh, R * 2); U(&ws->m1, R * 16); U(&ws->m2, R * 8); U(&ws->m3, R * 4);
+        F(&ws->part_val, T * GF); I(&ws->part_idx, T * GF); F(&ws->pool, B * 3 * GF); I(&ws->pidx, B * 3 * GF);
+        F(&ws->f1, B * 512); F(&ws->f2, B * 256); F(&ws->trans, B * 9); F(&ws->fk1, B * 512); F(&ws->fk2, B * 256); F(&ws->tf, B * 4096);
+        U(&ws->mf1, B * 16); U(&ws->mf2, B * 8); U(&ws->mfk1, B * 16); U(&ws->mfk2, B * 8);
+        F(&ws->t1, 64 * B * 3); F(&ws->w1f, B * 512); F(&ws->c2f, 128 * B * 64); F(&ws->h1pf, 512 * B * 64); F(&ws->gb, B * 512);
+        F(&ws->x0in, R * 9);
+        F(&ws->dz4, R * NCLS); F(&ws->dz3, R * 128); F(&ws->dz2, R * 256); F(&ws->dz1, R * 512); F(&ws->s1, B * 512); F(&ws->dg, B * GF);
+        F(&ws->dpf, R * 64); F(&ws->ht, R * 64); F(&ws->dpft, R * 64); F(&ws->dtf, B * 4096); F(&ws->dfk2, B * 256);
+        F(&ws->dfk1, B * 512); F(&ws->dgk, B * GF); F(&ws->dh, R * 64); F(&ws->dxu, R * 8); F(&ws->dtrans, B * 9);
+        F(&ws->df2, B * 256); F(&ws->df1, B * 512); F(&ws->dgs, B * GF);
+        F(&ws->x0, R * 9); F(&ws->ori, R * 3); F(&ws->dlogp, R * NCLS); F(&ws->dx0, R * 9);
+        I(&ws->labels, R);
+        ws->mask = bp.take<uint8_t>((size_t)n_point);
+    };
+    if (int rc = carve_arena(&ws->arena, &ws->bytes, "psg_pointnet_ws_create", layout)) {
         delete ws;
-        return PSG_ERR_HIP;
-    }
-    ws->bytes = total;
-    size_t off = 0;
-    for (const Item &it : items) {
-        *it.p = (char *)ws->arena + off;
-        off += (it.bytes + 255) & ~(size_t)255;
+        return rc;
     }
     // the dense dxu columns 6:8 are never written by the GEMM (M = 6): keep them defined
     if (psg::memset_sync(ws->dxu, 0, R * 8 * sizeof(float)) != hipSuccess) {

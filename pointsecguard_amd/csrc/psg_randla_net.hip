@@ -243,32 +243,14 @@ int rl_gemm(const GemmArgs &a, hipStream_t st)
         PSG_LAUNCH_CHECK();
         return PSG_OK;
     }
-    dim3 grid(ceil_div(a.rows, 128), ceil_div(a.M, 128));
-    if ((size_t)grid.x * grid.y < RL_SMALL_TILE_BELOW) {   // few 128-wide tiles: 64 x 64 tiles, one MFMA tile per wave
-        dim3 small(ceil_div(a.rows, 64), ceil_div(a.M, 64));
-        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, false, 1, 1>), small, dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, false>), grid, dim3(256), 0, st, a);
-    }
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-GemmArgs rl_args(const float *in, int ld_in, const float *w, int ld_w, float *out, int ld_out, int rows, int K, int M)
-{
-    GemmArgs a;
-    a.in = in; a.w = w; a.bias = nullptr; a.gbias = nullptr; a.scale = nullptr; a.shift = nullptr; a.sq = nullptr;
-    a.out = out; a.mask_out = nullptr; a.mask_in = nullptr;
-    a.rows = rows; a.K = K; a.M = M; a.ld_in = ld_in; a.ld_w = ld_w; a.ld_out = ld_out; a.group_rows = 1;
-    a.accumulate = 0; a.addend = nullptr; a.ld_add = 0;
-    return a;
+    return launch_gemm<2, 2, EPI, false>(a, RL_SMALL_TILE_BELOW, st);
 }
 
 // out = [leaky_relu](in . W^T + b), sign bits to `mask` ([rows][ceil(cout/32)] words) when given
 int conv_fwd(const RLayer &L, const float *in, int ld_in, float *out, int ld_out, int rows, bool act, uint32_t *mask,
              hipStream_t st)
 {
-    GemmArgs a = rl_args(in, ld_in, L.w, L.cin, out, ld_out, rows, L.cin, L.cout);
+    GemmArgs a = gemm_args(in, ld_in, L.w, L.cin, out, ld_out, rows, L.cin, L.cout);
     a.bias = L.b;
     a.mask_out = mask;
     return act ? rl_gemm<EPI_LRELU>(a, st) : rl_gemm<EPI_LINEAR>(a, st);
@@ -300,7 +282,7 @@ __global__ void lrelu_bwd_kernel(float *__restrict__ g, int ld, const uint32_t *
 int conv_bwd(const RLayer &L, const float *dz, int ld_dz, float *din, int ld_din, int rows, int accumulate, hipStream_t st,
              const uint32_t *lrelu_mask = nullptr)
 {
-    GemmArgs a = rl_args(dz, ld_dz, L.wt, L.cout, din, ld_din, rows, L.cout, L.cin);
+    GemmArgs a = gemm_args(dz, ld_dz, L.wt, L.cout, din, ld_din, rows, L.cout, L.cin);
     a.accumulate = accumulate;
     a.post_mask = lrelu_mask;
     a.post_slope = kSlope;
@@ -1132,27 +1114,17 @@ struct psg_rla_ws {
     uint64_t xyz_branch_model = 0;   // generation number (not the address: a freed model's address can come back) of the model whose xyz-branch features (fxyz1 / fxyz2) are resident
     // hipGraph of one BIM iteration (forward, loss gradient, backward, update: ~150 short launches), valid for the
     // (model, eps, alpha, metric) below; every captured kernel works on workspace buffers, so it is cloud-independent
-    hipGraphExec_t bim_exec = nullptr;
+    psg::GraphSlot bim;
     uint64_t bim_model_gen = 0;      // the model's generation number, not its address (psg_common.h)
     float bim_eps = 0.f, bim_alpha = 0.f;
     int bim_metric = -1;
-    bool bim_capture_failed = false; // the capture for this key failed once: stay eager instead of trying in every call
-    psg::CaptureCounters cap;
 };
 
 namespace {
 
-template <typename T> T *upload(psg_rla_model *m, const std::vector<T> &h)
-{
-    void *p = nullptr;
-    if (hipMalloc(&p, h.size() * sizeof(T)) != hipSuccess) return nullptr;
-    (void)psg::copy_sync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    m->allocs.push_back(p);
-    return (T *)p;
-}
-
 // tensors[6 * i .. 6 * i + 5] = weight [cout][cin], bias or null, bn gamma, beta, mean, var or null
-RLayer make_layer(psg_rla_model *m, const float *const *t, int cin, int cout)
+// (`ok` is cleared when an upload fails)
+RLayer make_layer(psg_rla_model *m, const float *const *t, int cin, int cout, bool &ok)
 {
     std::vector<float> w((size_t)cout * cin), wt((size_t)cin * cout), b(cout, 0.0f);
     for (int o = 0; o < cout; ++o) {
@@ -1167,8 +1139,10 @@ RLayer make_layer(psg_rla_model *m, const float *const *t, int cin, int cout)
     }
     RLayer L;
     L.cin = cin; L.cout = cout;
-    L.w = upload(m, w); L.wt = upload(m, wt);
-    L.b = (t[1] || t[2]) ? upload(m, b) : nullptr;
+    const bool has_bias = t[1] || t[2];
+    L.w = upload(m->allocs, w); L.wt = upload(m->allocs, wt);
+    L.b = has_bias ? upload(m->allocs, b) : nullptr;
+    ok = ok && L.w && L.wt && (L.b || !has_bias);
     return L;
 }
 
@@ -1185,8 +1159,9 @@ extern "C" int psg_rla_model_create(psg_ctx *ctx, const float *const *tensors, i
     for (int l = 0; l < PSG_RLA_NUM_LAYERS; ++l)
         if (!tensors[6 * l]) { delete m; set_error("psg_rla_model_create: weight of layer %d is null", l); return PSG_ERR_ARG; }
     int li = 0;
+    bool ok = true;
     auto next = [&](int cin, int cout) {
-        RLayer L = make_layer(m, tensors + 6 * li, cin, cout);
+        RLayer L = make_layer(m, tensors + 6 * li, cin, cout, ok);
         ++li;
         return L;
     };
@@ -1209,8 +1184,11 @@ extern "C" int psg_rla_model_create(psg_ctx *ctx, const float *const *tensors, i
         feat = skip;
     }
     m->fc1 = next(feat, 64); m->fc2 = next(64, 32); m->fc = next(32, RNCLS);
-    for (void *p : m->allocs)
-        if (!p) { set_error("psg_rla_model_create: device allocation failed"); return PSG_ERR_HIP; }
+    if (!ok) {
+        psg_rla_model_destroy(m);
+        set_error("psg_rla_model_create: device allocation or upload failed");
+        return PSG_ERR_HIP;
+    }
     *out = m;
     return PSG_OK;
 }
@@ -1241,91 +1219,79 @@ extern "C" int psg_rla_ws_create_batch(psg_ctx *ctx, int n_points, int batch, ps
     { const char *nf = psg::env_str("PSG_RLA_NO_FUSE16"); ws->fuse16 = !(nf && atoi(nf)); }
     { const char *at = psg::env_str("PSG_RLA_ATOMICS"); ws->use_inv = !(at && atoi(at)); }
     { const char *ns = psg::env_str("PSG_RLA_NO_SPLIT"); ws->split = !(ns && atoi(ns)) && ws->use_inv; }
-    for (int pass = 0; pass < 2; ++pass) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            off = (off + 255) & ~(size_t)255;
-            char *p = pass ? (char *)ws->arena + off : nullptr;
-            off += bytes;
-            return (void *)p;
-        };
+    auto layout = [&](Bump &bp) {
         const size_t N = (size_t)ws->N;
-        ws->xyz_all = (float *)take(N * 3 * 4);
+        ws->xyz_all = bp.take<float>(N * 3);
         int n = ws->N, nc = n_points, d_in = 8;
         size_t max_edge = 0;
         for (int i = 0; i < RL; ++i) {
             LevelBuf &L = ws->lv[i];
             L.n = n; L.n_sub = n / kRatio[i]; L.d = kDout[i]; L.h = L.d / 2; L.d_in = d_in;
             L.nc = nc; L.nc_sub = nc / kRatio[i];
-            L.xyz = i == 0 ? ws->xyz_all : (float *)take((size_t)n * 3 * 4);
+            L.xyz = i == 0 ? ws->xyz_all : bp.take<float>((size_t)n * 3);
             const size_t E = (size_t)n * RK, d = L.d, h = L.h;
             max_edge = std::max(max_edge, E * d);
-            L.neigh = (int32_t *)take(E * 4); L.up = (int32_t *)take((size_t)n * 4);
-            L.inv_off = (int32_t *)take(((size_t)n + 1) * 4); L.inv_ent = (int32_t *)take(E * 4);
-            L.invu_off = (int32_t *)take(((size_t)L.n_sub + 1) * 4); L.invu_ent = (int32_t *)take((size_t)n * 4);
-            L.invp_off = (int32_t *)take(((size_t)n + 1) * 4); L.invp_ent = (int32_t *)take((size_t)L.n_sub * RK * 4);
-            L.relpos = (float *)take(E * 10 * 4); L.fxyz1 = (float *)take(E * h * 4); L.fxyz2 = (float *)take(E * h * 4);
-            L.fpc = (float *)take((size_t)n * h * 4); L.cat1 = (float *)take(E * d * 4); L.a1 = (float *)take(E * d * 4);
-            L.agg1 = (float *)take((size_t)n * d * 4); L.fagg1 = (float *)take((size_t)n * h * 4);
-            L.cat2 = (float *)take(E * d * 4); L.a2 = (float *)take(E * d * 4); L.agg2 = (float *)take((size_t)n * d * 4);
-            L.fagg2 = (float *)take((size_t)n * d * 4); L.m2 = (float *)take((size_t)n * 2 * d * 4);
-            L.sc = (float *)take((size_t)n * 2 * d * 4); L.enc = (float *)take((size_t)n * 2 * d * 4);
-            L.samp = (float *)take((size_t)L.n_sub * 2 * d * 4);
-            L.m_fpc = (uint32_t *)take((size_t)n * ceil_div((int)h, 32) * 4); L.m_fagg1 = (uint32_t *)take((size_t)n * ceil_div((int)h, 32) * 4);
-            L.m_fagg2 = (uint32_t *)take((size_t)n * ceil_div((int)d, 32) * 4); L.m_enc = (uint32_t *)take((size_t)n * (2 * d / 32) * 4);
-            L.arg = (uint8_t *)take((size_t)L.n_sub * 2 * d);
+            L.neigh = bp.take<int32_t>(E); L.up = bp.take<int32_t>((size_t)n);
+            L.inv_off = bp.take<int32_t>(((size_t)n + 1)); L.inv_ent = bp.take<int32_t>(E);
+            L.invu_off = bp.take<int32_t>(((size_t)L.n_sub + 1)); L.invu_ent = bp.take<int32_t>((size_t)n);
+            L.invp_off = bp.take<int32_t>(((size_t)n + 1)); L.invp_ent = bp.take<int32_t>((size_t)L.n_sub * RK);
+            L.relpos = bp.take<float>(E * 10); L.fxyz1 = bp.take<float>(E * h); L.fxyz2 = bp.take<float>(E * h);
+            L.fpc = bp.take<float>((size_t)n * h); L.cat1 = bp.take<float>(E * d); L.a1 = bp.take<float>(E * d);
+            L.agg1 = bp.take<float>((size_t)n * d); L.fagg1 = bp.take<float>((size_t)n * h);
+            L.cat2 = bp.take<float>(E * d); L.a2 = bp.take<float>(E * d); L.agg2 = bp.take<float>((size_t)n * d);
+            L.fagg2 = bp.take<float>((size_t)n * d); L.m2 = bp.take<float>((size_t)n * 2 * d);
+            L.sc = bp.take<float>((size_t)n * 2 * d); L.enc = bp.take<float>((size_t)n * 2 * d);
+            L.samp = bp.take<float>((size_t)L.n_sub * 2 * d);
+            L.m_fpc = bp.take<uint32_t>((size_t)n * ceil_div((int)h, 32)); L.m_fagg1 = bp.take<uint32_t>((size_t)n * ceil_div((int)h, 32));
+            L.m_fagg2 = bp.take<uint32_t>((size_t)n * ceil_div((int)d, 32)); L.m_enc = bp.take<uint32_t>((size_t)n * (2 * d / 32));
+            L.arg = bp.take<uint8_t>((size_t)L.n_sub * 2 * d);
             n = L.n_sub; nc = L.nc_sub; d_in = 2 * L.d;
         }
         const int n5 = ws->lv[RL - 1].n_sub;
-        ws->xyz_last = (float *)take((size_t)n5 * 3 * 4);
-        ws->f0 = (float *)take(N * 8 * 4); ws->m_f0 = (uint32_t *)take(N * 4);
-        ws->dec0 = (float *)take((size_t)n5 * 1024 * 4); ws->m_dec0 = (uint32_t *)take((size_t)n5 * 32 * 4);
+        ws->xyz_last = bp.take<float>((size_t)n5 * 3);
+        ws->f0 = bp.take<float>(N * 8); ws->m_f0 = bp.take<uint32_t>(N);
+        ws->dec0 = bp.take<float>((size_t)n5 * 1024); ws->m_dec0 = bp.take<uint32_t>((size_t)n5 * 32);
         int feat = 1024;
         for (int j = 0; j < RL; ++j) {
             const LevelBuf &L = ws->lv[RL - 1 - j];        // decoder layer j produces features at level RL-1-j's points
             const int skip = j == RL - 1 ? 2 * kDout[0] : 2 * kDout[RL - 2 - j];
-            ws->dec_cat[j] = (float *)take((size_t)L.n * (skip + feat) * 4);
-            ws->dec_out[j] = (float *)take((size_t)L.n * skip * 4);
-            ws->m_dec[j] = (uint32_t *)take((size_t)L.n * ceil_div(skip, 32) * 4);
+            ws->dec_cat[j] = bp.take<float>((size_t)L.n * (skip + feat));
+            ws->dec_out[j] = bp.take<float>((size_t)L.n * skip);
+            ws->m_dec[j] = bp.take<uint32_t>((size_t)L.n * ceil_div(skip, 32));
             max_edge = std::max(max_edge, (size_t)L.n * (skip + feat));
             feat = skip;
         }
-        ws->fc1o = (float *)take(N * 64 * 4); ws->fc2o = (float *)take(N * 32 * 4);
-        ws->m_fc1 = (uint32_t *)take(N * 2 * 4); ws->m_fc2 = (uint32_t *)take(N * 4);
-        ws->logits = (float *)take(N * RNCLS * 4); ws->dlogits = (float *)take(N * RNCLS * 4);
-        ws->scratch_a = (float *)take(max_edge * 4); ws->scratch_b = (float *)take(max_edge * 4);
+        ws->fc1o = bp.take<float>(N * 64); ws->fc2o = bp.take<float>(N * 32);
+        ws->m_fc1 = bp.take<uint32_t>(N * 2); ws->m_fc2 = bp.take<uint32_t>(N);
+        ws->logits = bp.take<float>(N * RNCLS); ws->dlogits = bp.take<float>(N * RNCLS);
+        ws->scratch_a = bp.take<float>(max_edge); ws->scratch_b = bp.take<float>(max_edge);
         ws->scratch_bytes = max_edge * 4;
-        ws->d_f0 = (float *)take(N * 8 * 4);
+        ws->d_f0 = bp.take<float>(N * 8);
         // gradient accumulators (targets of atomics / of several consumers): one contiguous block, zeroed by ONE memset
         // at the start of a backward pass instead of ~25 small ones spread over it
-        off = (off + 255) & ~(size_t)255;
-        const size_t acc_begin = off;
+        bp.off = (bp.off + 255) & ~(size_t)255;
+        const size_t acc_begin = bp.off;
         for (int i = 0; i < RL; ++i) {
             LevelBuf &L = ws->lv[i];
-            L.d_enc = (float *)take((size_t)L.n * 2 * L.d * 4); L.d_samp = (float *)take((size_t)L.n_sub * 2 * L.d * 4);
-            L.d_fpc = (float *)take((size_t)L.n * L.h * 4); L.d_fagg1 = (float *)take((size_t)L.n * L.h * 4);
+            L.d_enc = bp.take<float>((size_t)L.n * 2 * L.d); L.d_samp = bp.take<float>((size_t)L.n_sub * 2 * L.d);
+            L.d_fpc = bp.take<float>((size_t)L.n * L.h); L.d_fagg1 = bp.take<float>((size_t)L.n * L.h);
         }
-        ws->d_dec0 = (float *)take((size_t)n5 * 1024 * 4);
+        ws->d_dec0 = bp.take<float>((size_t)n5 * 1024);
         for (int j = 0; j < RL; ++j) {
             const LevelBuf &L = ws->lv[RL - 1 - j];
             const int skip = j == RL - 1 ? 2 * kDout[0] : 2 * kDout[RL - 2 - j];
-            ws->d_dec_out[j] = (float *)take((size_t)L.n * skip * 4);
+            ws->d_dec_out[j] = bp.take<float>((size_t)L.n * skip);
         }
-        off = (off + 255) & ~(size_t)255;
-        ws->acc = pass ? (char *)ws->arena + acc_begin : nullptr;
-        ws->acc_bytes = off - acc_begin;
-        ws->d_fc1o = (float *)take(N * 64 * 4); ws->d_fc2o = (float *)take(N * 32 * 4);
-        ws->feat = (float *)take(N * 6 * 4); ws->dfeat = (float *)take(N * 6 * 4); ws->ori = (float *)take(N * 3 * 4);
-        ws->delta = (float *)take(N * 3 * 4); ws->norms = (float *)take((size_t)(2 * batch > 4 ? 2 * batch : 4) * 4); ws->labels = (int32_t *)take(N * 4);
-        if (!pass) {
-            ws->bytes = (off + 255) & ~(size_t)255;
-            hipError_t e = hipMalloc(&ws->arena, ws->bytes);
-            if (e != hipSuccess) {
-                set_error("psg_rla_ws_create: hipMalloc(%zu) failed: %s", ws->bytes, hipGetErrorString(e));
-                delete ws;
-                return PSG_ERR_HIP;
-            }
-        }
+        bp.off = (bp.off + 255) & ~(size_t)255;
+        ws->acc = bp.base ? bp.base + acc_begin : nullptr;
+        ws->acc_bytes = bp.off - acc_begin;
+        ws->d_fc1o = bp.take<float>(N * 64); ws->d_fc2o = bp.take<float>(N * 32);
+        ws->feat = bp.take<float>(N * 6); ws->dfeat = bp.take<float>(N * 6); ws->ori = bp.take<float>(N * 3);
+        ws->delta = bp.take<float>(N * 3); ws->norms = bp.take<float>((size_t)(2 * batch > 4 ? 2 * batch : 4)); ws->labels = bp.take<int32_t>(N);
+    };
+    if (int rc = carve_arena(&ws->arena, &ws->bytes, "psg_rla_ws_create", layout)) {
+        delete ws;
+        return rc;
     }
     *out = ws;
     return PSG_OK;
@@ -1334,7 +1300,7 @@ extern "C" int psg_rla_ws_create_batch(psg_ctx *ctx, int n_points, int batch, ps
 extern "C" int psg_rla_ws_destroy(psg_rla_ws *ws)
 {
     if (!ws) return PSG_OK;
-    if (ws->bim_exec) (void)hipGraphExecDestroy(ws->bim_exec);
+    ws->bim.destroy();
     if (ws->arena) (void)hipFree(ws->arena);
     ws->prof.destroy();
     delete ws;
@@ -1476,9 +1442,9 @@ extern "C" int psg_rla_forward(psg_rla_model *m, psg_rla_ws *ws, const float *fe
             if ((rc = conv_fwd(E.lfa_mlp1, L.relpos, 10, L.fxyz1, h, (int)ne, true, nullptr, st))) return rc;
             if ((rc = conv_fwd(E.lfa_mlp2, L.fxyz1, h, L.fxyz2, h, (int)ne, true, nullptr, st))) return rc;
             if (ws->split && d > 16) {   // S2 = fxyz . W2^T (the position-encoding half of the score layer), kept in the cat buffers
-                GemmArgs g1 = rl_args(L.fxyz1, h, E.att1_fc.w + h, d, L.cat1, d, (int)ne, h, d);
+                GemmArgs g1 = gemm_args(L.fxyz1, h, E.att1_fc.w + h, d, L.cat1, d, (int)ne, h, d);
                 if ((rc = rl_gemm<EPI_LINEAR>(g1, st))) return rc;
-                GemmArgs g2 = rl_args(L.fxyz2, h, E.att2_fc.w + h, d, L.cat2, d, (int)ne, h, d);
+                GemmArgs g2 = gemm_args(L.fxyz2, h, E.att2_fc.w + h, d, L.cat2, d, (int)ne, h, d);
                 if ((rc = rl_gemm<EPI_LINEAR>(g2, st))) return rc;
             }
         }
@@ -1486,7 +1452,7 @@ extern "C" int psg_rla_forward(psg_rla_model *m, psg_rla_ws *ws, const float *fe
         const bool split = d > 16 && ws->split;         // levels 1-4: scores = T[neigh] + S2 (att_pool_split_*_kernel)
         if (split) {
             float *T1 = L.a1;                            // [n][d], kept for the backward (the attention weights are recomputed there from T + S2)
-            GemmArgs g = rl_args(L.fpc, h, E.att1_fc.w, d, T1, d, n, h, d);
+            GemmArgs g = gemm_args(L.fpc, h, E.att1_fc.w, d, T1, d, n, h, d);
             g.bias = E.att1_fc.b;
             if ((rc = rl_gemm<EPI_LINEAR>(g, st))) return rc;
             {
@@ -1512,7 +1478,7 @@ extern "C" int psg_rla_forward(psg_rla_model *m, psg_rla_ws *ws, const float *fe
         if ((rc = conv_fwd(E.att1_mlp, L.agg1, d, L.fagg1, h, n, true, L.m_fagg1, st))) return rc;
         if (split) {
             float *T2 = L.a2;                            // [n][d], kept for the backward like T1
-            GemmArgs g = rl_args(L.fagg1, h, E.att2_fc.w, d, T2, d, n, h, d);
+            GemmArgs g = gemm_args(L.fagg1, h, E.att2_fc.w, d, T2, d, n, h, d);
             g.bias = E.att2_fc.b;
             if ((rc = rl_gemm<EPI_LINEAR>(g, st))) return rc;
             {
@@ -1540,7 +1506,7 @@ extern "C" int psg_rla_forward(psg_rla_model *m, psg_rla_ws *ws, const float *fe
         // operand of mlp2's pre-activation sum (round 5: (acc + bias) + shortcut, the order of the separate add pass it replaces)
         if ((rc = conv_fwd(E.shortcut, fin, L.d_in, L.sc, 2 * d, n, false, nullptr, st))) return rc;
         {
-            GemmArgs g = rl_args(L.fagg2, d, E.mlp2.w, E.mlp2.cin, L.enc, 2 * d, n, E.mlp2.cin, E.mlp2.cout);
+            GemmArgs g = gemm_args(L.fagg2, d, E.mlp2.w, E.mlp2.cin, L.enc, 2 * d, n, E.mlp2.cin, E.mlp2.cout);
             g.bias = E.mlp2.b; g.mask_out = L.m_enc; g.pre_add = L.sc; g.ld_pre = 2 * d;
             if ((rc = rl_gemm<EPI_LRELU>(g, st))) return rc;
         }
@@ -1658,7 +1624,7 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
             hipLaunchKernelGGL(gather_inv_kernel<false>, dim3(blocks_for((size_t)n * h)), dim3(256), 0, st, ddir, h, h, L.inv_off, L.inv_ent,
                                (size_t)n * h, df_);
             PSG_LAUNCH_CHECK();
-            GemmArgs g = rl_args(dT, d, fc.wt, d, df_, h, n, d, h);     // rows i < h of W^T: df[.][i] += sum_c dT[.][c] W[c][i]
+            GemmArgs g = gemm_args(dT, d, fc.wt, d, df_, h, n, d, h);     // rows i < h of W^T: df[.][i] += sum_c dT[.][c] W[c][i]
             g.accumulate = 1;
             g.post_mask = mask_;                                        // last contributor of df_: the activation's derivative
             g.post_slope = kSlope;
@@ -1899,37 +1865,16 @@ extern "C" int psg_rla_bim_attack(psg_rla_model *m, psg_rla_ws *ws, const float 
     static const bool use_graph = !((psg::env_int("PSG_RLA_NO_GRAPH", 0) != 0)) && !trace_sync_enabled();   // (the tracer synchronises after every launch)
     if (use_graph && !ws->prof.on && iters - it >= 2) {
         const bool same_key = ws->bim_model_gen == m->gen && ws->bim_eps == eps && ws->bim_alpha == alpha && ws->bim_metric == l2_metric;
-        if (!same_key) {
-            if (ws->bim_exec) {
-                PSG_CHECK_HIP(hipStreamSynchronize(st));
-                (void)hipGraphExecDestroy(ws->bim_exec);
-                ws->bim_exec = nullptr;
-            }
-            ws->bim_capture_failed = false;
-        }
-        if (!ws->bim_exec && !ws->bim_capture_failed) {
-            // a capture that fails (refused on the legacy stream, or invalidated) has executed nothing: the iterations run
-            // eagerly below - and show a genuine launch error there -, the failure is counted (psg_capture_stats) and this
-            // key is not tried again
-            bool ok = false;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int crc = iteration();
-                hipGraph_t graph = nullptr;
-                const hipError_t e = hipStreamEndCapture(st, &graph);
-                ok = crc == PSG_OK && e == hipSuccess && graph && hipGraphInstantiate(&ws->bim_exec, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (!ok) ws->bim_exec = nullptr;
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();
+        if (!same_key) PSG_CHECK_HIP(ws->bim.forget(st));
+        if (!ws->bim.exec && !ws->bim.capture_failed) {
+            ws->bim.capture(st, iteration);
             ws->bim_model_gen = m->gen; ws->bim_eps = eps; ws->bim_alpha = alpha; ws->bim_metric = l2_metric;
-            ws->bim_capture_failed = !ok;
-            psg::capture_note(&ws->cap, 1, ok ? 0 : 1, 0, 0);
         }
-        if (ws->bim_exec) {
-            psg::capture_note(&ws->cap, 0, 0, iters - it, 0);
-            for (; it < iters; ++it) PSG_CHECK_HIP(hipGraphLaunch(ws->bim_exec, st));
+        if (ws->bim.exec) {
+            PSG_CHECK_HIP(ws->bim.replay(st, iters - it));
+            it = iters;
         } else {
-            psg::capture_note(&ws->cap, 0, 0, 0, iters - it);
+            ws->bim.note_eager(iters - it);
         }
     }
     for (; it < iters; ++it)

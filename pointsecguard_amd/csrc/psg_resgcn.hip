@@ -35,33 +35,12 @@ constexpr int GC = 64;      // n_filters
 constexpr int NCLS = 13;
 constexpr int KNB = 16;     // k
 
+// (PSG_GEMM_SMALL_BELOW: the workgroup count below which launch_gemm takes 64 x 64 tiles, for A/B runs)
 template <int WM, int WN, int EPI, bool ASC>
 int launch_gemm(const GemmArgs &a, hipStream_t st)
 {
-    constexpr int BR = 64 * WM, BN = 64 * WN;
-    dim3 grid(ceil_div(a.rows, BR), ceil_div(a.M, BN));
     static const size_t small_below = (size_t)psg::env_int("PSG_GEMM_SMALL_BELOW", 384);
-    if (!ASC && (size_t)grid.x * grid.y < small_below) {
-        // too few 128-wide tiles to fill 256 CUs with more than one workgroup each (the per-vertex GEMMs of up to ~8 rooms:
-        // K = 64, so a tile is two short k-steps and the launch is latency-bound): 64 x 64 tiles, one MFMA tile per wave,
-        // four times as many workgroups (4 rooms: 31.6 -> 11 us per launch)
-        dim3 small(ceil_div(a.rows, 64), ceil_div(a.M, 64));
-        hipLaunchKernelGGL((gemm_rows_kernel<2, 2, EPI, ASC, 1, 1>), small, dim3(256), 0, st, a);
-        PSG_LAUNCH_CHECK();
-        return PSG_OK;
-    }
-    hipLaunchKernelGGL((gemm_rows_kernel<WM, WN, EPI, ASC>), grid, dim3(256), 0, st, a);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-GemmArgs gemm_args(const float *in, int ld_in, const float *w, int ld_w, float *out, int ld_out, int rows, int K, int M)
-{
-    GemmArgs a;
-    a.in = in; a.w = w; a.bias = nullptr; a.gbias = nullptr; a.scale = nullptr; a.shift = nullptr; a.sq = nullptr;
-    a.out = out; a.mask_out = nullptr; a.mask_in = nullptr;
-    a.rows = rows; a.K = K; a.M = M; a.ld_in = ld_in; a.ld_w = ld_w; a.ld_out = ld_out; a.group_rows = 1; a.accumulate = 0; a.addend = nullptr; a.ld_add = 0;
-    return a;
+    return psg::launch_gemm<WM, WN, EPI, ASC>(a, small_below, st);
 }
 
 // ---- squared norms with the reference's summation order (SURVEY 8a'): for C = 64 torch.sum(x*x, -1) uses
@@ -961,25 +940,14 @@ struct psg_gcn_ws {
     // hipGraph of one interior PGD iteration (forward, CE, backward, step): ~300 short launches replayed as one
     // graph launch; valid for (model, eps, alpha) below, rebuilt when they change
     int32_t *nb_labels;        // [B*N] the attack's labels, copied so that the captured kernels' arguments never change
-    hipGraphExec_t nb_exec = nullptr;
+    psg::GraphSlot nb;
     uint64_t nb_model_gen = 0;       // the model's generation number, not its address (psg_common.h)
     float nb_eps = 0.f, nb_alpha = 0.f;
     bool nb_fixed = false;
-    bool nb_capture_failed = false;  // the capture for this key failed once: stay eager instead of trying in every call
-    psg::CaptureCounters cap;
     EvLog prof;              // psg_gcn_prof_enable
 };
 
 namespace {
-
-template <typename T> T *dev_upload(psg_gcn_model *m, const std::vector<T> &h)
-{
-    void *p = nullptr;
-    if (hipMalloc(&p, h.size() * sizeof(T)) != hipSuccess) return nullptr;
-    (void)psg::copy_sync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    m->allocs.push_back(p);
-    return (T *)p;
-}
 
 void bn_affine(const float *g, const float *b, const float *mu, const float *var, int n, std::vector<float> &s,
                std::vector<float> &t)
@@ -1085,6 +1053,12 @@ extern "C" int psg_gcn_model_create_cfg(psg_ctx *ctx, const float *const *tensor
     auto *m = new psg_gcn_model();
     m->ctx = ctx; m->n_blocks = n_blocks; m->fdim = GC * n_blocks;
     m->block = block; m->conv = conv;
+    bool ok = true;
+    auto dev_upload = [&](const std::vector<float> &h) {
+        float *p = upload(m->allocs, h);
+        ok = ok && p;
+        return p;
+    };
     int ti = 0;
     for (int e = 0; e < n_blocks; ++e) {
         const int C = e == 0 ? 9 : (block == PSG_GCN_BLOCK_DENSE ? GC * e : GC);
@@ -1105,27 +1079,27 @@ extern "C" int psg_gcn_model_create_cfg(psg_ctx *ctx, const float *const *tensor
             for (int c = 0; c < C; ++c) wt[(size_t)c * 2 * GC + r] = wcat[(size_t)r * C + c];
         EdgeLayer L;
         L.C = C;
-        L.wcat = dev_upload(m, wcat); L.bcat = dev_upload(m, bcat); L.wcat_t = dev_upload(m, wt);
+        L.wcat = dev_upload(wcat); L.bcat = dev_upload(bcat); L.wcat_t = dev_upload(wt);
         if (C == GC) {
             std::vector<float> wk((size_t)2 * GC * C);
             for (int r = 0; r < 2 * GC; ++r)
                 for (int c = 0; c < C; ++c) wk[((size_t)(c >> 3) * 2 * GC + r) * 8 + (c & 7)] = wcat[(size_t)r * C + c];
-            L.wcat_k8 = dev_upload(m, wk);
+            L.wcat_k8 = dev_upload(wk);
         }
-        L.scale = dev_upload(m, s); L.shift = dev_upload(m, t);
+        L.scale = dev_upload(s); L.shift = dev_upload(t);
         if (conv == PSG_GCN_CONV_MR) {
             std::vector<float> wplain(W, W + (size_t)GC * 2 * C), wtr((size_t)2 * C * GC);
             for (int o = 0; o < GC; ++o)
                 for (int k = 0; k < 2 * C; ++k) wtr[(size_t)k * GC + o] = W[(size_t)o * 2 * C + k];
-            L.w = dev_upload(m, wplain); L.w_t = dev_upload(m, wtr);
-            L.b = dev_upload(m, std::vector<float>(b, b + GC));
+            L.w = dev_upload(wplain); L.w_t = dev_upload(wtr);
+            L.b = dev_upload(std::vector<float>(b, b + GC));
             L.arg_off = m->arg_total;
             m->arg_total += (size_t)C;
         }
         m->edge.push_back(L);
     }
     const int F = m->fdim;
-    auto up = [&](const float *p, size_t n) { return dev_upload(m, std::vector<float>(p, p + n)); };
+    auto up = [&](const float *p, size_t n) { return dev_upload(std::vector<float>(p, p + n)); };
     // fold the duplicated feature columns of a dense backbone (see above): src has `lead` leading columns kept as
     // they are, then the concatenation cur_0 | cur_1 | ... with cur_i = y_0 .. y_i
     std::vector<std::vector<float>> folded;
@@ -1151,17 +1125,17 @@ extern "C" int psg_gcn_model_create_cfg(psg_ctx *ctx, const float *const *tensor
     std::vector<float> s, t;
     m->wf = up(fold_dense(tensors[ti], 1024, 0), (size_t)1024 * F); m->bf = up(tensors[ti + 1], 1024);
     bn_affine(tensors[ti + 2], tensors[ti + 3], tensors[ti + 4], tensors[ti + 5], 1024, s, t);
-    m->sf = dev_upload(m, s); m->tf = dev_upload(m, t); ti += 6;
+    m->sf = dev_upload(s); m->tf = dev_upload(t); ti += 6;
     const float *W1 = fold_dense(tensors[ti], 512, 1024);
     m->wp1 = up(W1, (size_t)512 * (1024 + F)); m->bp1 = up(tensors[ti + 1], 512);
     std::vector<float> s1v, t1v;
     bn_affine(tensors[ti + 2], tensors[ti + 3], tensors[ti + 4], tensors[ti + 5], 512, s1v, t1v);
-    m->s1 = dev_upload(m, s1v); m->t1 = dev_upload(m, t1v); ti += 6;
+    m->s1 = dev_upload(s1v); m->t1 = dev_upload(t1v); ti += 6;
     const float *W2 = tensors[ti];
     m->wp2 = up(W2, (size_t)256 * 512); m->bp2 = up(tensors[ti + 1], 256);
     std::vector<float> s2v, t2v;
     bn_affine(tensors[ti + 2], tensors[ti + 3], tensors[ti + 4], tensors[ti + 5], 256, s2v, t2v);
-    m->s2 = dev_upload(m, s2v); m->t2 = dev_upload(m, t2v); ti += 6;
+    m->s2 = dev_upload(s2v); m->t2 = dev_upload(t2v); ti += 6;
     const float *W3 = tensors[ti];
     m->wp3 = up(W3, (size_t)NCLS * 256); m->bp3 = up(tensors[ti + 1], NCLS);
     // transposes for the input-gradient pass, BatchNorm scales folded in
@@ -1174,10 +1148,13 @@ extern "C" int psg_gcn_model_create_cfg(psg_ctx *ctx, const float *const *tensor
         for (int k = 0; k < F; ++k) w1bst[(size_t)k * 512 + o] = W1[(size_t)o * (1024 + F) + 1024 + k] * s1v[o];
         for (int k = 0; k < 1024; ++k) w1ast[(size_t)k * 512 + o] = W1[(size_t)o * (1024 + F) + k] * s1v[o];
     }
-    m->wp3_t = dev_upload(m, w3t); m->wp2_st = dev_upload(m, w2st); m->wp1b_st = dev_upload(m, w1bst);
-    m->wp1a_st = dev_upload(m, w1ast);
-    for (void *p : m->allocs)
-        if (!p) { set_error("psg_gcn_model_create: device allocation failed"); return PSG_ERR_HIP; }
+    m->wp3_t = dev_upload(w3t); m->wp2_st = dev_upload(w2st); m->wp1b_st = dev_upload(w1bst);
+    m->wp1a_st = dev_upload(w1ast);
+    if (!ok) {
+        psg_gcn_model_destroy(m);
+        set_error("psg_gcn_model_create: device allocation or upload failed");
+        return PSG_ERR_HIP;
+    }
     *out = m;
     return PSG_OK;
 }
@@ -1232,63 +1209,51 @@ extern "C" int psg_gcn_ws_create_cfg(psg_ctx *ctx, int batch, int n_point, int n
     ws->NP2 = 1;
     while (ws->NP2 < n_point) ws->NP2 <<= 1;
     const size_t R = (size_t)batch * n_point;
-    for (int pass = 0; pass < 2; ++pass) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            off = (off + 255) & ~(size_t)255;
-            char *p = pass ? (char *)ws->arena + off : nullptr;
-            off += bytes;
-            return (void *)p;
-        };
-        ws->feats = (float *)take(R * ws->fdim * 4);
-        ws->dfeats = (float *)take(R * ws->fdim * 4);
-        ws->dist = (float *)take(R * n_point * 4);
-        ws->sq = (float *)take(R * 4);
-        ws->xp = (float *)take(knn_xp_bytes(R));
-        ws->bp = take(knn_bp_bytes(R));
-        ws->knn_stats = psg::env_str("PSG_GCN_KNN_STATS") ? (unsigned long long *)take(8 * sizeof(unsigned long long)) : nullptr;
-        ws->pq = (float *)take(R * ws->pq_w * 4);
-        ws->pq2 = (float *)take(R * 2 * GC * 4);
-        ws->dpq = (float *)take(R * ws->pq_w * 4);
-        ws->dpq2 = (float *)take(R * 2 * GC * 4);
+    auto layout = [&](Bump &bp) {
+        ws->feats = bp.take<float>(R * ws->fdim);
+        ws->dfeats = bp.take<float>(R * ws->fdim);
+        ws->dist = bp.take<float>(R * n_point);
+        ws->sq = bp.take<float>(R);
+        ws->xp = (float *)bp.take<char>(knn_xp_bytes(R));
+        ws->bp = bp.take<char>(knn_bp_bytes(R));
+        ws->knn_stats = psg::env_str("PSG_GCN_KNN_STATS") ? bp.take<unsigned long long>(8) : nullptr;
+        ws->pq = bp.take<float>(R * ws->pq_w);
+        ws->pq2 = bp.take<float>(R * 2 * GC);
+        ws->dpq = bp.take<float>(R * ws->pq_w);
+        ws->dpq2 = bp.take<float>(R * 2 * GC);
         if (conv == PSG_GCN_CONV_MR) {
-            ws->arg_mr = (uint8_t *)take(R * arg_total);
-            ws->mask_mr = (uint32_t *)take((size_t)n_blocks * R * 2 * 4);
+            ws->arg_mr = bp.take<uint8_t>(R * arg_total);
+            ws->mask_mr = bp.take<uint32_t>((size_t)n_blocks * R * 2);
         }
-        ws->nbr = (int32_t *)take((size_t)n_blocks * R * KNB * 4);
-        ws->arg = (uint8_t *)take((size_t)n_blocks * R * GC);
-        ws->fused = (float *)take(R * 1024 * 4);
-        ws->mask_f = (uint32_t *)take(R * 32 * 4);
-        ws->mask1 = (uint32_t *)take(R * 16 * 4);
-        ws->mask2 = (uint32_t *)take(R * 8 * 4);
-        ws->fmax = (float *)take((size_t)batch * 1024 * 4);
-        ws->farg = (int32_t *)take((size_t)batch * 1024 * 4);
-        ws->fkeys = (unsigned long long *)take((size_t)batch * 1024 * 8);
-        ws->gb1 = (float *)take((size_t)batch * 512 * 4);
-        ws->h1 = (float *)take(R * 512 * 4);
-        ws->h2 = (float *)take(R * 256 * 4);
-        ws->g2 = (float *)take(R * 256 * 4);
-        ws->g1 = (float *)take(R * 512 * 4);
-        ws->g1sum = (float *)take((size_t)batch * 512 * 4);
-        ws->g1part = (float *)take((size_t)batch * ceil_div(n_point, 64) * 512 * 4);
-        ws->gfvec = (float *)take((size_t)batch * 1024 * 4);
-        ws->gcur = (float *)take(R * GC * 4);
-        ws->logits = (float *)take(R * NCLS * 4);
-        ws->dlogits = (float *)take(R * NCLS * 4);
-        ws->x0 = (float *)take(R * 9 * 4);
-        ws->ori = (float *)take(R * 3 * 4);
-        ws->dx0 = (float *)take(R * 9 * 4);
-        ws->xyz = (float *)take(R * 3 * 4);
-        ws->nb_labels = (int32_t *)take(R * 4);
-        if (!pass) {
-            ws->bytes = (off + 255) & ~(size_t)255;
-            hipError_t e = hipMalloc(&ws->arena, ws->bytes);
-            if (e != hipSuccess) {
-                set_error("psg_gcn_ws_create: hipMalloc(%zu) failed: %s", ws->bytes, hipGetErrorString(e));
-                delete ws;
-                return PSG_ERR_HIP;
-            }
-        }
+        ws->nbr = bp.take<int32_t>((size_t)n_blocks * R * KNB);
+        ws->arg = bp.take<uint8_t>((size_t)n_blocks * R * GC);
+        ws->fused = bp.take<float>(R * 1024);
+        ws->mask_f = bp.take<uint32_t>(R * 32);
+        ws->mask1 = bp.take<uint32_t>(R * 16);
+        ws->mask2 = bp.take<uint32_t>(R * 8);
+        ws->fmax = bp.take<float>((size_t)batch * 1024);
+        ws->farg = bp.take<int32_t>((size_t)batch * 1024);
+        ws->fkeys = bp.take<unsigned long long>((size_t)batch * 1024);
+        ws->gb1 = bp.take<float>((size_t)batch * 512);
+        ws->h1 = bp.take<float>(R * 512);
+        ws->h2 = bp.take<float>(R * 256);
+        ws->g2 = bp.take<float>(R * 256);
+        ws->g1 = bp.take<float>(R * 512);
+        ws->g1sum = bp.take<float>((size_t)batch * 512);
+        ws->g1part = bp.take<float>((size_t)batch * ceil_div(n_point, 64) * 512);
+        ws->gfvec = bp.take<float>((size_t)batch * 1024);
+        ws->gcur = bp.take<float>(R * GC);
+        ws->logits = bp.take<float>(R * NCLS);
+        ws->dlogits = bp.take<float>(R * NCLS);
+        ws->x0 = bp.take<float>(R * 9);
+        ws->ori = bp.take<float>(R * 3);
+        ws->dx0 = bp.take<float>(R * 9);
+        ws->xyz = bp.take<float>(R * 3);
+        ws->nb_labels = bp.take<int32_t>(R);
+    };
+    if (int rc = carve_arena(&ws->arena, &ws->bytes, "psg_gcn_ws_create", layout)) {
+        delete ws;
+        return rc;
     }
     if (ws->knn_stats) (void)psg::memset_sync(ws->knn_stats, 0, 8 * sizeof(unsigned long long));
     *out = ws;
@@ -1303,7 +1268,7 @@ extern "C" int psg_gcn_ws_create(psg_ctx *ctx, int batch, int n_point, int n_blo
 extern "C" int psg_gcn_ws_destroy(psg_gcn_ws *ws)
 {
     if (!ws) return PSG_OK;
-    if (ws->nb_exec) (void)hipGraphExecDestroy(ws->nb_exec);
+    ws->nb.destroy();
     if (ws->arena) (void)hipFree(ws->arena);
     ws->prof.destroy();
     delete ws;
@@ -1740,37 +1705,16 @@ extern "C" int psg_gcn_nb_attack(psg_gcn_model *m, psg_gcn_ws *ws, const float *
     static const bool use_graph = !((psg::env_int("PSG_GCN_NO_GRAPH", 0) != 0)) && !trace_sync_enabled();   // (the tracer synchronises after every launch)
     if (use_graph && !ws->prof.on && iters - 1 - it >= 2) {
         const bool same_key = ws->nb_model_gen == m->gen && ws->nb_eps == eps && ws->nb_alpha == alpha && ws->nb_fixed == ws->fixed_graphs;
-        if (!same_key) {
-            if (ws->nb_exec) {
-                PSG_CHECK_HIP(hipStreamSynchronize(st));
-                (void)hipGraphExecDestroy(ws->nb_exec);
-                ws->nb_exec = nullptr;
-            }
-            ws->nb_capture_failed = false;
-        }
-        if (!ws->nb_exec && !ws->nb_capture_failed) {
-            // a capture that fails (refused on the legacy stream, or invalidated) has executed nothing: the iterations run
-            // eagerly below - and show a genuine launch error there -, the failure is counted (psg_capture_stats) and this
-            // key is not tried again
-            bool ok = false;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int crc = iteration(false);
-                hipGraph_t graph = nullptr;
-                const hipError_t e = hipStreamEndCapture(st, &graph);
-                ok = crc == PSG_OK && e == hipSuccess && graph && hipGraphInstantiate(&ws->nb_exec, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (!ok) ws->nb_exec = nullptr;
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();
+        if (!same_key) PSG_CHECK_HIP(ws->nb.forget(st));
+        if (!ws->nb.exec && !ws->nb.capture_failed) {
+            ws->nb.capture(st, [&] { return iteration(false); });
             ws->nb_model_gen = m->gen; ws->nb_eps = eps; ws->nb_alpha = alpha; ws->nb_fixed = ws->fixed_graphs;
-            ws->nb_capture_failed = !ok;
-            psg::capture_note(&ws->cap, 1, ok ? 0 : 1, 0, 0);
         }
-        if (ws->nb_exec) {
-            psg::capture_note(&ws->cap, 0, 0, iters - 1 - it, 0);
-            for (; it < iters - 1; ++it) PSG_CHECK_HIP(hipGraphLaunch(ws->nb_exec, st));
+        if (ws->nb.exec) {
+            PSG_CHECK_HIP(ws->nb.replay(st, iters - 1 - it));
+            it = iters - 1;
         } else {
-            psg::capture_note(&ws->cap, 0, 0, 0, iters - 1 - it);
+            ws->nb.note_eager(iters - 1 - it);
         }
     }
     for (; it < iters; ++it)
