@@ -429,6 +429,57 @@ int psg_nu_graph_stats(const psg_nu_graph *graph, long long *out4);
  * psg_rla_bim_attack; for the last two the unit is an attack iteration). */
 int psg_capture_stats(long long *out4);
 
+/* The same window on the vanilla PointNet network: per step psg_nu_tanh_color(_rooms), the PointNet forward, the f-loss
+ * gradient, the PointNet input-gradient backward (no upstream gradient of trans_feat), psg_smooth_knn_rooms,
+ * psg_nu_adam_step(_rooms), psg_nu_step_latch.  The fields are those of psg_nu_window_args without the plan slots (this
+ * network draws no FPS starts).  fused_head != 0: the seam between forward and backward - log-softmax, f-loss gradient,
+ * log-softmax backward - is one kernel on the head's logits (same dz and pred bit for bit; logp / dlogp are not used);
+ * fused_head == 0: the three kernels, as the per-step entry points run them (dlogp required; logp, if given, receives the
+ * step's log-probs).  `graph` as for the PointNet++ window; the captured sequence is a single chain on `stream`. */
+typedef struct psg_pointnet_nu_window_args {
+    psg_pointnet_model *model;
+    psg_pointnet_ws *ws;         /* created for G*rows rooms of N points */
+    int step0, n_steps;
+    int G, rows, N, mode;
+    int use_target, target;
+    int neighbour, warm_first;
+    int adam_t0, fused_head;
+    float kappa, tsign, c_smooth, c_l2, lr, beta1, beta2, eps;
+    float *w, *m, *v;            /* [G*rows][N][3] */
+    const uint8_t *mask;         /* [G][N] (rows = 1) or [N] (G = 1), nullable for NU_attack */
+    const int32_t *n_mask;       /* [G], modes 1 and 2 */
+    float *x0;                   /* [G*rows][N][9] */
+    const float *ori;            /* [G*rows][N][3] */
+    const int32_t *labels;       /* [G*rows][N] */
+    float *logp, *dlogp, *dx0;   /* [G*rows][N][13] nullable, [..][13] (fused_head == 0), [..][9] */
+    float *sgrad;                /* [G][N][3] */
+    int32_t *pred;               /* [G*rows][N] */
+    float *scal;                 /* [3][G], zero before the first window */
+    int32_t *nn_state;           /* [G][N][neighbour] */
+    float *hist;                 /* history rows [5][G] of the window's steps, row of step0 first */
+    float *out;                  /* [G*rows][9][N] */
+    uint8_t *active;             /* [G] */
+    int32_t *exit_step;          /* [G] */
+} psg_pointnet_nu_window_args;
+int psg_pointnet_nu_window(const psg_pointnet_nu_window_args *args, psg_nu_graph *graph, psg_stream stream);
+
+/* The seam of that window on its own: logits [B][N][13] (N a multiple of PSG_POINTNET_POINT_TILE) -> dz_out [B][N][13] (the
+ * gradient of the logits), pred_out [B][N], and the f sums ADDED to f_sum ([B] when per_room, else one float).  With both
+ * scratch arrays ([B][N][13] each) it runs the three kernels of the per-step path, without them the fused kernel.
+ * logits and dz_out must be 16-byte aligned (the fused kernel moves them as 16-byte words). */
+int psg_pointnet_nu_head(const float *logits, const int32_t *labels, int target, int B, int N, int per_room, float kappa,
+                         float tsign, float *logp_scratch, float *dlogp_scratch, float *dz_out, float *f_sum,
+                         int32_t *pred_out, psg_stream stream);
+
+/* The restart of tar_NU_attack (target.py:127-132) for the groups flags [G] selects (non-zero), in one launch: the group's
+ * noise block [rows][3][n_mask[g]] (at float offset noise_off[g] of `noise`, laid out as torch.empty(rows, 3, k).uniform_
+ * fills it) is added to the masked colours, entry j to the j-th masked point in ascending order; ALL nine channels of the
+ * group's rows are clamped to [0, 1]; extra_l2[g] = sum((x0 - x0_orig)^2) over channels 0:3 and 6:9 in a fixed order.
+ * x0 / x0_orig [G*rows][N][9], mask_groups [G][N].  Groups that are not flagged are left untouched, extra_l2 included. */
+int psg_nu_restart_rooms(float *x0, const float *x0_orig, const uint8_t *mask_groups, const int32_t *n_mask,
+                         const uint8_t *flags, const float *noise, const long long *noise_off, int G, int rows, int N,
+                         float *extra_l2, psg_stream stream);
+
 /* Segmentation statistics of NB_nontarget_test_semseg.py:199-205: for every class l accumulates
  * seen[l] += #(gt==l), inter[l] += #(pred==l & gt==l), uni[l] += #(pred==l | gt==l) where
  * pred = argmax(logp) (first index on ties).  counters: int64 [3][n_cls] = seen, inter, uni.

@@ -90,6 +90,9 @@ SIGNATURES = {
     "psg_nu_graph_destroy": (ci, [vp]),
     "psg_nu_graph_stats": (ci, [vp, c_ll]),
     "psg_capture_stats": (ci, [c_ll]),
+    "psg_pointnet_nu_window": (ci, [vp, vp, vp]),
+    "psg_pointnet_nu_head": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp, vp, vp]),
+    "psg_nu_restart_rooms": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp]),
     "psg_nu_step_latch": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp]),
     "psg_nu_tanh_color_rooms": (ci, [vp, vp, ci, ci, vp, vp]),
     "psg_nu_f_loss_grad_rooms": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp]),
@@ -151,6 +154,16 @@ class NuWindowArgs(ctypes.Structure):
     _fields_ = ([("model", vp), ("ws", vp)] +
                 [(n, ci) for n in ("slot0", "step0", "n_steps", "G", "rows", "N", "mode", "use_target", "target", "neighbour",
                                    "warm_first", "adam_t0")] +
+                [(n, cf) for n in ("kappa", "tsign", "c_smooth", "c_l2", "lr", "beta1", "beta2", "eps")] +
+                [(n, vp) for n in ("w", "m", "v", "mask", "n_mask", "x0", "ori", "labels", "logp", "dlogp", "dx0", "sgrad", "pred",
+                                   "scal", "nn_state", "hist", "out", "active", "exit_step")])
+
+
+class PointnetNuWindowArgs(ctypes.Structure):
+    """psg_pointnet_nu_window_args of include/psg.h, field for field."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("step0", "n_steps", "G", "rows", "N", "mode", "use_target", "target", "neighbour", "warm_first",
+                                   "adam_t0", "fused_head")] +
                 [(n, cf) for n in ("kappa", "tsign", "c_smooth", "c_l2", "lr", "beta1", "beta2", "eps")] +
                 [(n, vp) for n in ("w", "m", "v", "mask", "n_mask", "x0", "ori", "labels", "logp", "dlogp", "dx0", "sgrad", "pred",
                                    "scal", "nn_state", "hist", "out", "active", "exit_step")])

@@ -28,6 +28,7 @@ import torch
 from pointsecguard_amd import _lib, runtime
 from pointsecguard_amd.models.pointnet2_sem_seg import draw_fps_starts, upload
 
+from . import pointnet as pointnet_net
 from ._common import labels_to_device, mask_to_device, psg_model
 
 BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
@@ -67,6 +68,7 @@ class _NuState:
         self.active = torch.empty(G, device=dev, dtype=torch.uint8)
         self.exit = torch.empty(G, device=dev, dtype=torch.int32)
         self.n_mask = torch.empty(G, device=dev, dtype=torch.int32)
+        self.restart_l2 = f32(G)                                     # psg_nu_restart_rooms: sum((x - x_orig)^2), channels 0:3 and 6:9
         self.out = f32(B, 9, N)
         # one graph handle per window position inside a geometry plan (a captured window holds its plan slots)
         self.graphs = [ctypes.c_void_p() for _ in range(PLAN_AHEAD // CHUNK)]
@@ -91,10 +93,36 @@ def _state(net, dev, G, rows, N, neighbour):
     return cache[key]
 
 
-def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, trace, starts_fn, G, rows):
+def _pointnet_restart(S, x0, again, n_mask, G, rows, N, dev, extra_l2):
+    """The restart of target.py:127-132 for the attacks `again` of a PointNet state: the noise is drawn as the PointNet++ code
+    of _nu_core draws it - per attack, in ascending order, from the device generator - and placed by ONE psg_nu_restart_rooms
+    launch for all of them (mask-order scatter, clamp of all nine channels, the extra L2 per attack into extra_l2)."""
+    offs, flags, total = np.zeros(G, np.int64), np.zeros(G, np.uint8), 0
+    blocks = []
+    for g in again:
+        blocks.append(torch.empty(rows, 3, int(n_mask[g]), device=dev, dtype=torch.float32).uniform_(0, 1).reshape(-1))
+        offs[g], flags[g] = total, 1
+        total += blocks[-1].numel()
+    noise = torch.cat(blocks)
+    ctl = torch.from_numpy(np.concatenate([offs.view(np.uint8), flags])).to(dev)          # one upload: offsets, flags
+    _lib.call("psg_nu_restart_rooms", runtime.ptr(x0), runtime.ptr(S.x0_orig), runtime.ptr(S.mask), runtime.ptr(S.n_mask),
+              ctypes.c_void_p(ctl.data_ptr() + 8 * G), runtime.ptr(noise), runtime.ptr(ctl), G, rows, N, runtime.ptr(S.restart_l2),
+              runtime.stream())
+    extra_l2[again] = S.restart_l2.cpu().numpy().astype(np.float64)[again]               # one read-back for all of them
+
+
+def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, trace, starts_fn, G, rows, record=None):
     """G attacks of `rows` batch rows each, advanced together: (1, B) = the reference's call on a batch of B rows (its batch
     semantics: Smooth term and mask of batch row 0, counts over all rows), (R, 1) = R one-room calls in lockstep.
-    masks: bool numpy [G, N] or None.  Returns (out [G*rows, 9, N], exited [G] = step of the exit test or -1, steps done)."""
+    masks: bool numpy [G, N] or None.  Returns (out [G*rows, 9, N], exited [G] = step of the exit test or -1, steps done).
+
+    The same loop serves the vanilla PointNet (pointnet.is_pointnet): its windows are psg_pointnet_nu_window calls, it has no
+    geometry plan (no FPS starts, nothing drawn from or given back to the CPU generator) and its restart is one
+    psg_nu_restart_rooms launch; window boundaries, read-backs, halving and the restart test are the code below for both.
+    `record(step, row [5, G], extra_l2 [G], was_active [G])` (tests) receives every step's history row without changing the
+    windows (`trace` reads back after every step, so it cannot observe them), and `record(step, None, extra_l2, restarting [G])`
+    when attacks restart after `step`."""
+    pointnet = pointnet_net.is_pointnet(atk.model)
     net = psg_model(atk.model)
     dev = atk.device
     images = images.detach().to(dev).float().contiguous()
@@ -104,7 +132,10 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
     S = _state(net, dev, G, rows, N, neighbour)
     model = net._packed()
     net._generation += 1
-    ws = net._workspace(B, N, max(CHUNK + 1, min(int(plan_ahead), PLAN_AHEAD)))      # plan slots: what a plan can hold, no more
+    if pointnet:
+        ws = net._workspace(B, N)
+    else:
+        ws = net._workspace(B, N, max(CHUNK + 1, min(int(plan_ahead), PLAN_AHEAD)))  # plan slots: what a plan can hold, no more
     use_target = targeted_variant and target is not None
     mode = 0 if not targeted_variant else (2 if use_target else 1)
     S.labels.copy_(labels_to_device(labels, dev))
@@ -132,9 +163,11 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
     prev_cost = np.full((atk.steps, G), 1e10)
     lr, adam_t = float(atk.lr), 0
     tsign = float(atk._targeted)
-    planned_until, rng_at = 0, None
+    planned_until, rng_at = (atk.steps, None) if pointnet else (0, None)           # (PointNet: nothing to plan)
+    plan_base = 0
     exited = np.full(G, -1, np.int64)                                # step at which an attack's exit test fired (-1: running)
-    win = _lib.NuWindowArgs(
+    win_args, win_entry = (_lib.PointnetNuWindowArgs, "psg_pointnet_nu_window") if pointnet else (_lib.NuWindowArgs, "psg_pn2_nu_window")
+    win = win_args(
         model=model.handle.value, ws=ws.handle.value, G=G, rows=rows, N=N, mode=mode, use_target=int(use_target),
         target=int(target) if use_target else 0, neighbour=int(neighbour), kappa=float(atk.kappa), tsign=tsign, c_smooth=float(atk.c),
         c_l2=float(atk.c), beta1=BETA1, beta2=BETA2, eps=ADAM_EPS, w=w.data_ptr(), m=m.data_ptr(), v=v.data_ptr(),
@@ -142,6 +175,9 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
         labels=S.labels.data_ptr(), logp=S.logp.data_ptr(), dlogp=S.dlogp.data_ptr(), dx0=S.dx0.data_ptr(), sgrad=S.sgrad.data_ptr(),
         pred=S.pred.data_ptr(), scal=S.scal.data_ptr(), nn_state=S.nn_state.data_ptr(), hist=S.hist.data_ptr(), out=S.out.data_ptr(),
         active=S.active.data_ptr(), exit_step=S.exit.data_ptr())
+    if pointnet:
+        win.fused_head = 1 if pointnet_net.fused_head else 0
+        win.logp = None                                  # (scratch of the three-kernel head's log-probs: nobody reads a copy)
 
     step = 0
     while step < atk.steps:
@@ -176,10 +212,14 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
         # full windows of the same shape are replayed as a hipGraph (psg_pn2_nu_window)
         window_end = 1 if step == 0 else ((step - 1) // CHUNK + 1) * CHUNK + 1          # [0], [1..10], [11..20], ..
         n_run = 1 if trace is not None else min(planned_until, window_end) - step
-        win.slot0, win.step0, win.n_steps = step - plan_base, step, n_run
+        win.step0, win.n_steps = step, n_run
         win.adam_t0, win.lr, win.warm_first = adam_t, lr, 1 if step > 0 else 0
-        graph = S.graphs[((step - plan_base) // CHUNK) % len(S.graphs)] if n_run == CHUNK and (step - plan_base) % CHUNK == 0 else None
-        _lib.call("psg_pn2_nu_window", ctypes.byref(win), graph, st())
+        if pointnet:
+            graph = S.graphs[0] if n_run == CHUNK else None              # (no plan slots in the key: one handle serves every window)
+        else:
+            win.slot0 = step - plan_base
+            graph = S.graphs[((step - plan_base) // CHUNK) % len(S.graphs)] if n_run == CHUNK and (step - plan_base) % CHUNK == 0 else None
+        _lib.call(win_entry, ctypes.byref(win), graph, st())
         adam_t += n_run
         last = step + n_run - 1
         # ---- the reference's control flow, per attack, where the reference's host work needs the values (ONE read-back)
@@ -193,6 +233,8 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
             prev_cost[s_i] = np.where(was_active, cost, prev_cost[s_i])
             if trace is not None:
                 trace(s_i, cost, f_loss, sm_loss, l2_loss, was_active, S)
+            if record is not None:
+                record(s_i, hrows[s_i - step].copy(), extra_l2.copy(), was_active.copy())
         step = last + 1
         active = exited < 0                              # after this step's exits (nontarget.py:95-96, target.py:116-121)
         if not active.any():
@@ -206,19 +248,25 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
             v.zero_()
         if last > 10 and last % 10 == 0:                 # target.py:127-132, attack by attack
             again = np.nonzero(active & (cost >= prev_cost[last - 10]))[0]
-            for g in again:                              # the noise draws stay per attack, in order
-                k = int(n_mask[g])
-                noise = torch.empty(rows, 3, k, device=dev, dtype=torch.float32).uniform_(0, 1)
-                col = x0[g * rows:(g + 1) * rows, :, 3:6].transpose(1, 2)        # view [rows, 3, N]
-                col[:, :, mask_b[g]] = col[:, :, mask_b[g]] + noise
-            if len(again):
-                ridx = torch.from_numpy(np.concatenate([np.arange(g * rows, (g + 1) * rows) for g in again])).to(dev)
-                clamped = x0[ridx].clamp_(min=0, max=1)                   # ALL channels, like the reference
-                x0[ridx] = clamped
-                d = clamped - S.x0_orig[ridx]
-                sums = ((d[:, :, 0:3] ** 2).sum(dim=(1, 2)) + (d[:, :, 6:9] ** 2).sum(dim=(1, 2))).reshape(len(again), rows)
-                extra_l2[again] = sums.sum(dim=1).cpu().numpy().astype(np.float64)   # one read-back for all of them
-                planned_until = step                     # xyz may have moved: rebuild the plan before the next forward
+            if record is not None and len(again):
+                record(last, None, extra_l2.copy(), np.isin(np.arange(G), again))        # a restart event: who restarts after `last`
+            if pointnet:
+                if len(again):
+                    _pointnet_restart(S, x0, again, n_mask, G, rows, N, dev, extra_l2)
+            else:
+                for g in again:                              # the noise draws stay per attack, in order
+                    k = int(n_mask[g])
+                    noise = torch.empty(rows, 3, k, device=dev, dtype=torch.float32).uniform_(0, 1)
+                    col = x0[g * rows:(g + 1) * rows, :, 3:6].transpose(1, 2)        # view [rows, 3, N]
+                    col[:, :, mask_b[g]] = col[:, :, mask_b[g]] + noise
+                if len(again):
+                    ridx = torch.from_numpy(np.concatenate([np.arange(g * rows, (g + 1) * rows) for g in again])).to(dev)
+                    clamped = x0[ridx].clamp_(min=0, max=1)                   # ALL channels, like the reference
+                    x0[ridx] = clamped
+                    d = clamped - S.x0_orig[ridx]
+                    sums = ((d[:, :, 0:3] ** 2).sum(dim=(1, 2)) + (d[:, :, 6:9] ** 2).sum(dim=(1, 2))).reshape(len(again), rows)
+                    extra_l2[again] = sums.sum(dim=1).cpu().numpy().astype(np.float64)   # one read-back for all of them
+                    planned_until = step                     # xyz may have moved: rebuild the plan before the next forward
     if rng_at is not None and planned_until > step:
         # draws of forwards that never ran go back to the generator - all but those of the window the attack stopped in
         # (rounds 3-5 drew window by window: the generator is left where it was left then)
@@ -230,7 +278,8 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
     return out, exited, step
 
 
-def nu_attack(atk, images, labels, mask, target, neighbour, targeted_variant=False, trace=None, starts_fn=None, return_steps=False):
+def nu_attack(atk, images, labels, mask, target, neighbour, targeted_variant=False, trace=None, starts_fn=None, return_steps=False,
+              record=None):
     """NU_attack.forward / tar_NU_attack.forward on a batch (the reference's call).  `starts_fn(step, n_plan)` (tests) supplies
     the [n_plan, 4, B] FPS start indices of a geometry window instead of the generator draws; `trace` (tests) is called
     after every step with the step's scalars and the state tensors (and makes the loop read back after every step);
@@ -244,11 +293,11 @@ def nu_attack(atk, images, labels, mask, target, neighbour, targeted_variant=Fal
         def tr(step, cost, f, sm, l2, was_active, S):
             trace(step=step, cost=float(cost[0]), f=float(f[0]), smooth=float(sm[0]), l2=float(l2[0]), w=S.w, m=S.m, v=S.v, dx0=S.dx0,
                   x0=S.x0, pred=S.pred)
-    out, exited, steps_done = _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr, starts_fn, 1, B)
+    out, exited, steps_done = _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr, starts_fn, 1, B, record=record)
     return (out, int(exited[0]) + 1 if exited[0] >= 0 else steps_done) if return_steps else out
 
 
-def nu_attack_rooms(atk, images, labels, masks, target, neighbour, targeted_variant=False, trace=None, starts_fn=None):
+def nu_attack_rooms(atk, images, labels, masks, target, neighbour, targeted_variant=False, trace=None, starts_fn=None, record=None):
     """R independent ONE-ROOM attacks advanced in lockstep: what `nu_attack` does when it is called once per room
     (`images[r:r+1]`, `labels[r:r+1]`, `masks[r]`), with one launch per operation for all rooms instead of R
     (psg_*_rooms entry points; the network kernels simply see a batch of R).  This is how BASELINE configs[2] is applied
@@ -290,7 +339,7 @@ def nu_attack_rooms(atk, images, labels, masks, target, neighbour, targeted_vari
             trace(step=step, cost=cost, f=f, smooth=sm, l2=l2, w=S.w, m=S.m, v=S.v, dx0=S.dx0, x0=S.x0, pred=S.pred,
                   active=was_active.copy())
     try:
-        out, exited, steps_done = _nu_core(atk, images, labels, mk, target, neighbour, targeted_variant, tr, starts_fn, R, 1)
+        out, exited, steps_done = _nu_core(atk, images, labels, mk, target, neighbour, targeted_variant, tr, starts_fn, R, 1, record=record)
     finally:
         atk.lr = lr_at_call
     return out, np.where(exited >= 0, exited + 1, steps_done).astype(np.int64)

@@ -8,12 +8,17 @@ NB_attack / tar_NB_attack: one fused, stream-ordered libpsg call (psg_pointnet_n
 CE-on-log-probs gradient, input-gradient backward, sign step + L-inf projection).  This network draws no random
 numbers, so unlike the PointNet++ path there are no FPS starts.
 
-NU_attack / tar_NU_attack: a per-step host loop over the shared NU kernels (psg_nu_tanh_color, psg_pointnet_forward,
-psg_nu_f_loss_grad, psg_pointnet_backward, psg_smooth_knn, psg_nu_adam_step, psg_nu_step_latch) with the reference's
-control flow (PointNet/attacks/torchattacks/attacks/nontarget.py:52-105, target.py:62-133): the accuracy exits, and for
-tar_NU the learning-rate halving with a fresh optimiser every 50 steps and the restart noise after every 10th step
-whose cost did not fall.  It is not the PointNet++ NU core: that one exists for FPS plans and hipGraph windows, which
-this network does not have.
+NU_attack / tar_NU_attack: the window loop of nu.py (`_nu_core`, shared with PointNet++): steps [0], [1..10], [11..20], ..
+are one psg_pointnet_nu_window call each, replayed as a hipGraph from the third full window on, with one read-back per
+window; `forward` is one attack on the batch (G = 1, rows = B), `forward_rooms` R one-room attacks in lockstep.  The
+reference's control flow (PointNet/attacks/torchattacks/attacks/nontarget.py:52-105, target.py:62-133) sits between the
+windows: the accuracy exits, and for tar_NU the learning-rate halving with a fresh optimiser every 50 steps and the restart
+noise after every 10th step whose cost did not fall (psg_nu_restart_rooms).  This network has no FPS plan, so nothing is
+drawn from the CPU generator.
+
+`nu_step` / `nu_attack(trace=...)` below is the per-step host loop over the single entry points (psg_nu_tanh_color,
+psg_pointnet_forward, psg_nu_f_loss_grad, psg_pointnet_backward, psg_smooth_knn, psg_nu_adam_step, psg_nu_step_latch) with a
+read-back after every step: what a `trace` callback gets, and the checker the window path is tested against.
 """
 import ctypes
 
@@ -25,6 +30,9 @@ from pointsecguard_amd import _lib, runtime
 from ._common import labels_to_device, mask_to_device
 
 BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
+# The windows run the seam between forward and backward as one kernel (pn_nu_head_kernel); False selects the three-kernel
+# sequence instead (log-softmax, f-loss gradient, log-softmax backward): same images, for tools/pointnet_time.py's comparison.
+fused_head = True
 
 
 def is_pointnet(model):
@@ -88,8 +96,14 @@ def nu_step(net, S, labels, mask, n_mask, target, mode, kappa, tsign, c, neighbo
               int(step), st())
 
 
-def nu_attack(atk, images, labels, mask=None, target=None, neighbour=10, targeted_variant=False, trace=None):
-    """NU_attack.forward (targeted_variant=False) / tar_NU_attack.forward on a batch, the reference's call."""
+def nu_attack(atk, images, labels, mask=None, target=None, neighbour=10, targeted_variant=False, trace=None, return_steps=False,
+              record=None):
+    """NU_attack.forward (targeted_variant=False) / tar_NU_attack.forward on a batch, the reference's call: through the
+    windows of nu.py, or with a `trace` callback through the per-step loop below (a read-back after every step)."""
+    if trace is None:
+        from . import nu
+        return nu.nu_attack(atk, images, labels, mask, target, neighbour, targeted_variant=targeted_variant, return_steps=return_steps,
+                            record=record)
     net = atk.model
     dev = atk.device
     images = images.detach().to(dev).float().contiguous()

@@ -965,6 +965,85 @@ extern "C" int psg_nu_step_latch(const int32_t *pred, const int32_t *labels, int
     return PSG_OK;
 }
 
+// ---- Restart of tar_NU_attack (target.py:127-132) for the groups `flags` selects, one workgroup per group of `rows` batch
+// rows:  colour[:, :, mask] += noise;  x.clamp_(0, 1) on ALL nine channels;  extra_l2 = sum((x - x_orig)^2) over channels
+// 0:3 and 6:9.  The group's noise block is [rows][3][k] (k = its mask count) as torch.empty(rows, 3, k).uniform_() lays it
+// out: entry j of a channel belongs to the j-th masked point in ascending order, i.e. to the point's rank within the mask -
+// a ballot prefix count per 256-point chunk plus the running count of the chunks before it.  Each chunk's 256 x 9 floats
+// are then one contiguous piece handled as coalesced dwords.  The sum has a fixed order: per thread over its elements in
+// ascending order, then a tree over the 256 threads.  Groups that are not flagged are not touched.
+__global__ __launch_bounds__(256) void nu_restart_rooms_kernel(float *__restrict__ x0, const float *__restrict__ x0_orig,
+                                                                const uint8_t *__restrict__ mask, const int32_t *__restrict__ n_mask,
+                                                                const uint8_t *__restrict__ flags, const float *__restrict__ noise,
+                                                                const long long *__restrict__ noise_off, int rows, int N,
+                                                                float *__restrict__ extra_l2)
+{
+    __shared__ int s_rank[256];
+    __shared__ int s_cnt[4];
+    __shared__ float s_red[256];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!flags[g]) return;                                   // (uniform over the workgroup)
+    const uint8_t *mk = mask + (size_t)g * N;
+    const int k = n_mask[g];
+    const float *nz = noise + noise_off[g];
+    float acc = 0.0f;
+    for (int row = 0; row < rows; ++row) {
+        const size_t r = (size_t)g * rows + row;
+        int before = 0;                                      // masked points of this row's earlier chunks
+        for (int p0 = 0; p0 < N; p0 += 256) {
+            const int p = p0 + tid;
+            const bool in = p < N && mk[p] != 0;
+            const unsigned long long bal = __ballot(in);
+            if (lane == 0) s_cnt[wave] = __popcll(bal);
+            __syncthreads();
+            int pre = before;
+            for (int w = 0; w < wave; ++w) pre += s_cnt[w];
+            s_rank[tid] = in ? pre + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
+            before += (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+            __syncthreads();
+            const int np = min(256, N - p0);
+            float *xc = x0 + (r * N + p0) * 9;
+            const float *oc = x0_orig + (r * N + p0) * 9;
+            for (int e = tid; e < np * 9; e += 256) {
+                const int pl = e / 9, ch = e % 9, rk = s_rank[pl];
+                float v = xc[e];
+                if (ch >= 3 && ch < 6) {
+                    if (rk >= 0 && rk < k) v = v + nz[((size_t)row * 3 + (ch - 3)) * k + rk];
+                    v = fminf(fmaxf(v, 0.0f), 1.0f);
+                } else {
+                    v = fminf(fmaxf(v, 0.0f), 1.0f);
+                    const float d = v - oc[e];
+                    acc += d * d;
+                }
+                xc[e] = v;
+            }
+            __syncthreads();                                 // s_rank / s_cnt are rewritten by the next chunk
+        }
+    }
+    s_red[tid] = acc;
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) s_red[tid] += s_red[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) extra_l2[g] = s_red[0];
+}
+
+// x0 / x0_orig [G*rows][N][9]; mask_groups [G][N], n_mask [G]; flags [G] bytes (non-zero: restart this group); noise: the
+// flagged groups' blocks [rows][3][n_mask[g]], group g's at float offset noise_off[g]; extra_l2 [G] (written for flagged
+// groups only).
+extern "C" int psg_nu_restart_rooms(float *x0, const float *x0_orig, const uint8_t *mask_groups, const int32_t *n_mask,
+                                    const uint8_t *flags, const float *noise, const long long *noise_off, int G, int rows, int N,
+                                    float *extra_l2, psg_stream stream)
+{
+    PSG_REQUIRE(x0 && x0_orig && mask_groups && n_mask && flags && noise && noise_off && extra_l2, "psg_nu_restart_rooms: null argument");
+    PSG_REQUIRE(G > 0 && G <= 65535 && rows > 0 && N > 0, "psg_nu_restart_rooms: G=%d rows=%d N=%d out of range", G, rows, N);
+    hipLaunchKernelGGL(nu_restart_rooms_kernel, dim3(G), dim3(256), 0, (hipStream_t)stream, x0, x0_orig, mask_groups, n_mask, flags, noise,
+                       noise_off, rows, N, extra_l2);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
 // One step sequence of a window (shared by the eager and the captured path); dconsts: the step's device row or null.
 static int nu_window_steps(const psg_nu_window_args *a, const float *dconsts_rows, psg_stream stream)
 {
@@ -1008,8 +1087,8 @@ static int nu_window_steps(const psg_nu_window_args *a, const float *dconsts_row
 // attributes outside any capture), the second is captured, later ones are replayed.
 struct psg_nu_graph {
     psg::GraphSlot slot;
-    psg_nu_window_args key;
-    uint64_t key_model_gen = 0, key_ws_gen = 0;   // generation numbers of key.model / key.ws: addresses can be re-used (psg_common.h)
+    std::vector<unsigned char> key;               // the window's argument block, step0 / adam_t0 / lr zeroed
+    uint64_t key_model_gen = 0, key_ws_gen = 0;   // generation numbers of the key's model / ws: addresses can be re-used (psg_common.h)
     bool have_key = false;
     float *dconsts = nullptr;       // device [PSG_NU_GRAPH_MAX_STEPS][4]
     float host[PSG_NU_GRAPH_MAX_STEPS * 4];
@@ -1033,14 +1112,6 @@ extern "C" int psg_nu_graph_destroy(psg_nu_graph *g)
     return PSG_OK;
 }
 
-static bool nu_same_shape(const psg_nu_graph *g, psg_nu_window_args y)
-{
-    psg_nu_window_args x = g->key;
-    x.step0 = y.step0 = 0; x.adam_t0 = y.adam_t0 = 0; x.lr = y.lr = 0.0f;      // what the device row carries
-    return memcmp(&x, &y, sizeof(x)) == 0 && g->key_model_gen == psg::pn2_model_generation(y.model) &&
-           g->key_ws_gen == psg::pn2_ws_generation(y.ws);
-}
-
 // out4 = {captures tried, captures failed, windows replayed as a graph, windows that ran eagerly} of this handle (the two
 // eager windows every shape starts with included)
 extern "C" int psg_nu_graph_stats(const psg_nu_graph *g, long long *out4)
@@ -1051,42 +1122,55 @@ extern "C" int psg_nu_graph_stats(const psg_nu_graph *g, long long *out4)
     return PSG_OK;
 }
 
-extern "C" int psg_pn2_nu_window(const psg_nu_window_args *a, psg_nu_graph *graph, psg_stream stream)
+void psg::nu_set_step_consts(const float *row) { g_nu_dconsts = row; }
+
+int psg::nu_graph_window(psg_nu_graph *graph, const void *key, size_t key_bytes, uint64_t model_gen, uint64_t ws_gen, int n_steps,
+                         int step0, int adam_t0, float lr, float beta1, float beta2, hipStream_t st,
+                         const std::function<int(const float *)> &steps)
 {
-    PSG_REQUIRE(a && a->model && a->ws && a->w && a->m && a->v && a->x0 && a->ori && a->labels && a->logp && a->dlogp && a->dx0 &&
-                    a->sgrad && a->pred && a->scal && a->nn_state && a->hist && a->out && a->active && a->exit_step,
-                "psg_pn2_nu_window: null argument");
-    PSG_REQUIRE(a->n_steps > 0 && a->G > 0 && a->rows > 0 && (a->G == 1 || a->rows == 1), "psg_pn2_nu_window: (G, rows) must be (1, B) or (R, 1)");
-    hipStream_t st = (hipStream_t)stream;
     // (PSG_NU_NO_GRAPH=1: eager windows, for counter passes - per-dispatch counter rows need per-dispatch launches)
     static const bool no_graph = psg::env_int("PSG_NU_NO_GRAPH", 0) != 0;
-    if (!graph || no_graph || a->n_steps > PSG_NU_GRAPH_MAX_STEPS || psg::trace_sync_enabled()) return nu_window_steps(a, nullptr, stream);
+    if (!graph || no_graph || n_steps > PSG_NU_GRAPH_MAX_STEPS || psg::trace_sync_enabled()) return steps(nullptr);
     // the step-dependent constants of this window (torch.optim.Adam: step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t))
-    for (int i = 0; i < a->n_steps; ++i) {
-        const int t = a->adam_t0 + i + 1;
-        const double bc1 = 1.0 - pow((double)a->beta1, (double)t), bc2 = 1.0 - pow((double)a->beta2, (double)t);
-        graph->host[4 * i] = __builtin_bit_cast(float, a->step0 + i);
-        graph->host[4 * i + 1] = (float)((double)a->lr / bc1);
+    for (int i = 0; i < n_steps; ++i) {
+        const int t = adam_t0 + i + 1;
+        const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+        graph->host[4 * i] = __builtin_bit_cast(float, step0 + i);
+        graph->host[4 * i + 1] = (float)((double)lr / bc1);
         graph->host[4 * i + 2] = (float)sqrt(bc2);
         graph->host[4 * i + 3] = 0.0f;
     }
-    PSG_CHECK_HIP(hipMemcpyAsync(graph->dconsts, graph->host, (size_t)a->n_steps * 16, hipMemcpyHostToDevice, st));
-    const bool same = graph->have_key && nu_same_shape(graph, *a);
+    PSG_CHECK_HIP(hipMemcpyAsync(graph->dconsts, graph->host, (size_t)n_steps * 16, hipMemcpyHostToDevice, st));
+    const bool same = graph->have_key && graph->key.size() == key_bytes && memcmp(graph->key.data(), key, key_bytes) == 0 &&
+                      graph->key_model_gen == model_gen && graph->key_ws_gen == ws_gen;
     psg::GraphSlot &slot = graph->slot;
     // second window of this shape: capture it, then replay (a failed capture is counted - psg_nu_graph_stats,
     // psg_capture_stats - and the shape is not tried again: its windows run eagerly below)
-    if (same && !slot.exec && !slot.capture_failed) slot.capture(st, [&] { return nu_window_steps(a, graph->dconsts, stream); });
+    if (same && !slot.exec && !slot.capture_failed) slot.capture(st, [&] { return steps(graph->dconsts); });
     if (same && slot.exec) {
         PSG_CHECK_HIP(slot.replay(st));
         return PSG_OK;
     }
     if (!same) {
         PSG_CHECK_HIP(slot.forget(st));              // another shape: forget the old one
-        graph->key = *a;
-        graph->key_model_gen = psg::pn2_model_generation(a->model);
-        graph->key_ws_gen = psg::pn2_ws_generation(a->ws);
+        graph->key.assign((const unsigned char *)key, (const unsigned char *)key + key_bytes);
+        graph->key_model_gen = model_gen;
+        graph->key_ws_gen = ws_gen;
         graph->have_key = true;
     }
     slot.note_eager();
-    return nu_window_steps(a, graph->dconsts, stream);
+    return steps(graph->dconsts);
+}
+
+extern "C" int psg_pn2_nu_window(const psg_nu_window_args *a, psg_nu_graph *graph, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws && a->w && a->m && a->v && a->x0 && a->ori && a->labels && a->logp && a->dlogp && a->dx0 &&
+                    a->sgrad && a->pred && a->scal && a->nn_state && a->hist && a->out && a->active && a->exit_step,
+                "psg_pn2_nu_window: null argument");
+    PSG_REQUIRE(a->n_steps > 0 && a->G > 0 && a->rows > 0 && (a->G == 1 || a->rows == 1), "psg_pn2_nu_window: (G, rows) must be (1, B) or (R, 1)");
+    psg_nu_window_args key = *a;
+    key.step0 = 0; key.adam_t0 = 0; key.lr = 0.0f;      // what the device row carries
+    return psg::nu_graph_window(graph, &key, sizeof(key), psg::pn2_model_generation(a->model), psg::pn2_ws_generation(a->ws), a->n_steps,
+                                a->step0, a->adam_t0, a->lr, a->beta1, a->beta2, (hipStream_t)stream,
+                                [&](const float *rows) { return nu_window_steps(a, rows, stream); });
 }

@@ -315,6 +315,107 @@ __global__ void pn_log_softmax_bwd_kernel(const float *__restrict__ logp, const 
     for (int c = 0; c < NCLS; ++c) dz[r * NCLS + c] = dlogp[r * NCLS + c] - expf(logp[r * NCLS + c]) * s;
 }
 
+// ---- The seam between forward and backward of one NU optimiser step in ONE kernel: logits -> dz, pred, f sums.  What
+// pn_log_softmax_kernel, nu_f_loss_grad_kernel (psg_attack.hip) and pn_log_softmax_bwd_kernel compute through three
+// [rows][13] arrays in HBM, with the same per-element operations in the same order, so dz and pred are bit-identical to
+// that sequence.  The three parts keep the floating-point contraction mode of the translation units they come from (the
+// f-loss is compiled without contraction, the two log-softmax kernels with it): the products of one part never fuse into
+// the sums of the next.
+// 256 rows per workgroup: their 256 x 13 logits are one contiguous piece, read as coalesced 16-byte words into LDS; a thread
+// then owns one row (stride 13 dwords: conflict-free) with the classes in registers - every class loop is unrolled and the
+// label's class is picked by compares, not by indexing -, writes dz back into its LDS row, and the piece leaves as 16-byte
+// words again.  f sums as in nu_f_loss_grad_kernel: a wave's 64 values by xor shuffles, the workgroup's waves in ascending
+// order, one float atomicAdd per workgroup (per wave where a workgroup spans two rooms) into the room's sum.
+__global__ __launch_bounds__(256) void pn_nu_head_kernel(const float *__restrict__ logits, const int32_t *__restrict__ labels, int target,
+                                                         int rows, float kappa, float tsign, float *__restrict__ dz,
+                                                         float *__restrict__ f_sum, int32_t *__restrict__ pred, int rows_per_sum)
+{
+    __shared__ __attribute__((aligned(16))) float s_z[256 * NCLS];
+    __shared__ float s_part[4];
+    const int tid = threadIdx.x, r0 = blockIdx.x * 256, nr = min(256, rows - r0);      // nr is a multiple of 128
+    const float4 *src = (const float4 *)(logits + (size_t)r0 * NCLS);
+    for (int i = tid; i < nr * NCLS / 4; i += 256) ((float4 *)s_z)[i] = src[i];
+    __syncthreads();
+    const int r = r0 + tid;
+    float fval = 0.0f;
+    if (tid < nr) {
+        float *row = s_z + tid * NCLS;
+        float lp[NCLS], g[NCLS];
+        {   // pn_log_softmax_kernel
+            float v[NCLS], m = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) { v[c] = row[c]; m = fmaxf(m, v[c]); }
+            float s = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) s += expf(v[c] - m);
+            const float ls = logf(s);
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) lp[c] = (v[c] - m) - ls;
+        }
+        {   // nu_f_loss_grad_kernel
+#pragma clang fp contract(off)
+            float p[NCLS];
+            float m = -INFINITY;
+            int am = 0;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) {
+                p[c] = lp[c];
+                if (p[c] > m) { m = p[c]; am = c; }
+            }
+            pred[r] = am;
+            float s = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) { p[c] = expf(p[c] - m); s += p[c]; }
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) p[c] = p[c] / s;
+            const int y = labels ? labels[r] : target;
+            float oth = -1.0f, py = 0.0f, poi = 0.0f;
+            int oi = 0;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) {
+                if (c == y) py = p[c];
+                if (c != y && p[c] > oth) { oth = p[c]; oi = c; }
+            }
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c)
+                if (c == oi) poi = p[c];
+            if (oth < 0.0f) oth = 0.0f;
+            const float val = tsign * (py - oth);
+            const bool pass = val >= -kappa;
+            fval = pass ? val : -kappa;
+            const float gy = pass ? tsign : 0.0f, go = pass ? -tsign : 0.0f;
+            const float dot = gy * py + go * poi;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) {
+                const float gc = c == y ? gy : (c == oi ? go : 0.0f);
+                g[c] = p[c] * (gc - dot);
+            }
+        }
+        {   // pn_log_softmax_bwd_kernel
+            float s = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) s += g[c];
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) row[c] = g[c] - expf(lp[c]) * s;
+        }
+    }
+    __syncthreads();
+    float4 *dst = (float4 *)(dz + (size_t)r0 * NCLS);
+    for (int i = tid; i < nr * NCLS / 4; i += 256) dst[i] = ((const float4 *)s_z)[i];
+    for (int o = 32; o >= 1; o >>= 1) fval += __shfl_xor(fval, o);
+    if (rows_per_sum == 0 || rows_per_sum % 256 == 0) {
+        if ((tid & 63) == 0) s_part[tid >> 6] = fval;
+        __syncthreads();
+        if (tid == 0) {
+            float tot = 0.0f;
+            for (int w = 0; w < 4; ++w) tot += s_part[w];
+            atomicAdd(f_sum + (rows_per_sum ? r0 / rows_per_sum : 0), tot);
+        }
+    } else if ((tid & 63) == 0 && r < rows) {
+        atomicAdd(f_sum + r / rows_per_sum, fval);
+    }
+}
+
 // Input transform backward, one workgroup per room.  dxu [B*N][8]: columns 0:3 = d(xyz . trans), 3:6 = d rgb.
 //   dx0[p] = [trans . dxu_p[0:3], dxu_p[3:6], 0, 0, 0]   (channels 6:9 are not read by the network: x[:, :6])
 //   dtrans[b][i][j] = sum_p xyz_p[i] dxu_p[j]             (per-thread partials, then a fixed-order tree)
@@ -365,6 +466,7 @@ inline unsigned grid1(size_t n, int bs = 256) { return (unsigned)((n + bs - 1) /
 
 struct psg_pointnet_model {
     psg_ctx *ctx;
+    uint64_t gen = 0;      // psg::next_generation(): what a hipGraph key compares instead of the handle's address
     float *w[NL], *b[NL];
     // transposes for the backward: [in][out] of the named layer (H1p / H1g: the pointfeat / global column blocks of conv1)
     float *f3t, *f2t, *f1t, *fk3t, *fk2t, *fk1t, *h4t, *h3t, *h2t, *h1pt, *h1gt, *c1t;
@@ -373,6 +475,7 @@ struct psg_pointnet_model {
 
 struct psg_pointnet_ws {
     psg_ctx *ctx;
+    uint64_t gen = 0;
     int B, N;
     void *arena = nullptr;
     size_t bytes = 0;
@@ -396,7 +499,8 @@ struct psg_pointnet_ws {
 
 namespace {
 
-int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, float *logp_out, hipStream_t st)
+// with_logp = false stops at the head's logits (ws->logits): the NU window's pn_nu_head_kernel takes them from there
+int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, float *logp_out, hipStream_t st, bool with_logp = true)
 {
     const int B = ws->B, N = ws->N, R = B * N, T = R / PT;
     int rc;
@@ -494,6 +598,10 @@ int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, fl
         a = gemm_args(ws->z3, 128, W(L_H4), 128, ws->logits, NCLS, R, 128, NCLS);
         a.bias = Bi(L_H4);
         if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
+        if (!with_logp) {
+            ws->have_fwd = true;
+            return PSG_OK;
+        }
         hipLaunchKernelGGL(pn_log_softmax_kernel, dim3(grid1(R)), dim3(256), 0, st, ws->logits, (size_t)R, ws->logp);
         PSG_LAUNCH_CHECK();
         if (logp_out && logp_out != ws->logp)
@@ -503,14 +611,17 @@ int forward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *x0, fl
     return PSG_OK;
 }
 
+// dlogp == null: ws->dz4 already holds the gradient of the logits (written by pn_nu_head_kernel)
 int backward_impl(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *dlogp, const float *dtf_up, float *dx0_out,
                   hipStream_t st)
 {
     const int B = ws->B, N = ws->N, R = B * N;
     int rc;
     // ---- head transposes through the stored ReLU bits
-    hipLaunchKernelGGL(pn_log_softmax_bwd_kernel, dim3(grid1(R)), dim3(256), 0, st, ws->logp, dlogp, (size_t)R, ws->dz4);
-    PSG_LAUNCH_CHECK();
+    if (dlogp) {
+        hipLaunchKernelGGL(pn_log_softmax_bwd_kernel, dim3(grid1(R)), dim3(256), 0, st, ws->logp, dlogp, (size_t)R, ws->dz4);
+        PSG_LAUNCH_CHECK();
+    }
     GemmArgs a = gemm_args(ws->dz4, NCLS, m->h4t, NCLS, ws->dz3, 128, R, NCLS, 128);
     a.mask_in = ws->m3;
     if ((rc = run_gemm<EPI_LINEAR>(a, st))) return rc;
@@ -603,6 +714,7 @@ extern "C" int psg_pointnet_model_create(psg_ctx *ctx, const float *const *weigh
     PSG_CHECK_HIP(hipSetDevice(ctx->device));
     auto *m = new psg_pointnet_model();
     m->ctx = ctx;
+    m->gen = next_generation();
     bool ok = true;
     for (int l = 0; l < NL && ok; ++l) {
         const int M = LDIM[l][0], K = LDIM[l][1];
@@ -648,6 +760,7 @@ extern "C" int psg_pointnet_ws_create(psg_ctx *ctx, int batch, int n_point, psg_
     PSG_CHECK_HIP(hipSetDevice(ctx->device));
     auto *ws = new psg_pointnet_ws();
     ws->ctx = ctx; ws->B = batch; ws->N = n_point;
+    ws->gen = next_generation();
     const size_t B = batch, R = (size_t)batch * n_point, T = R / PT;
     auto layout = [&](Bump &bp) {
         auto F = [&](float **p, size_t n) { *p = bp.take<float>(n); };
@@ -745,4 +858,99 @@ extern "C" int psg_pointnet_nb_attack(psg_pointnet_model *m, psg_pointnet_ws *ws
             return rc;
     }
     return psg_to_channel_major(ws->x0, B, 9, N, adv_out, st);
+}
+
+// The window's seam on its own (tests, tools): logits [B][N][13] -> dz, pred, f sums (one per room when per_room, else one).
+// With both scratch arrays the three-kernel sequence the per-step entry points run, else pn_nu_head_kernel.
+extern "C" int psg_pointnet_nu_head(const float *logits, const int32_t *labels, int target, int B, int N, int per_room, float kappa,
+                                    float tsign, float *logp_scratch, float *dlogp_scratch, float *dz_out, float *f_sum,
+                                    int32_t *pred_out, psg_stream stream)
+{
+    PSG_REQUIRE(logits && dz_out && f_sum && pred_out && B > 0 && N > 0, "psg_pointnet_nu_head: bad argument");
+    PSG_REQUIRE(N % PT == 0, "psg_pointnet_nu_head: N=%d must be a multiple of the point tile %d", N, PT);
+    PSG_REQUIRE(labels || (target >= 0 && target < NCLS), "psg_pointnet_nu_head: target class %d out of range", target);
+    PSG_REQUIRE(!logp_scratch == !dlogp_scratch, "psg_pointnet_nu_head: give both scratch arrays or neither");
+    PSG_REQUIRE(((uintptr_t)logits | (uintptr_t)dz_out) % 16 == 0, "psg_pointnet_nu_head: logits and dz_out must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t R = (size_t)B * N;
+    if (!logp_scratch) {
+        hipLaunchKernelGGL(pn_nu_head_kernel, dim3(grid1(R)), dim3(256), 0, st, logits, labels, target, (int)R, kappa, tsign, dz_out, f_sum,
+                           pred_out, per_room ? N : 0);
+        PSG_LAUNCH_CHECK();
+        return PSG_OK;
+    }
+    hipLaunchKernelGGL(pn_log_softmax_kernel, dim3(grid1(R)), dim3(256), 0, st, logits, R, logp_scratch);
+    PSG_LAUNCH_CHECK();
+    if (int rc = per_room ? psg_nu_f_loss_grad_rooms(logp_scratch, labels, target, B, N, NCLS, kappa, tsign, dlogp_scratch, f_sum, pred_out, stream)
+                          : psg_nu_f_loss_grad(logp_scratch, labels, target, (int)R, NCLS, kappa, tsign, dlogp_scratch, f_sum, pred_out, stream))
+        return rc;
+    hipLaunchKernelGGL(pn_log_softmax_bwd_kernel, dim3(grid1(R)), dim3(256), 0, st, logp_scratch, dlogp_scratch, R, dz_out);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+// ---- NU_attack / tar_NU_attack windows on this network (include/psg.h: psg_pointnet_nu_window_args) ----------------------
+// One step sequence of a window, shared by the eager and the captured path; dconsts_rows: the window's device rows or null.
+// Everything in it is a launch or an asynchronous device-to-device copy on `stream`: the forward and the backward take all
+// their buffers from the workspace arena (psg_pointnet_ws_create), so a window can be captured as a single chain.
+static int pn_nu_window_steps(const psg_pointnet_nu_window_args *a, const float *dconsts_rows, psg_stream stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const bool rooms = a->G > 1;
+    const int B = a->G * a->rows, N = a->N, G = a->G;
+    int rc = PSG_OK;
+    for (int i = 0; i < a->n_steps && rc == PSG_OK; ++i) {
+        const int step = a->step0 + i, adam_t = a->adam_t0 + i + 1;
+        const int32_t *f_labels = a->use_target ? nullptr : a->labels;
+        const int f_target = a->use_target ? a->target : 0;
+        if ((rc = rooms ? psg_nu_tanh_color_rooms(a->w, a->mask, B, N, a->x0, stream) : psg_nu_tanh_color(a->w, a->mask, B, N, a->x0, stream)))
+            break;
+        if (a->fused_head) {
+            if ((rc = forward_impl(a->model, a->ws, a->x0, nullptr, st, false))) break;
+            hipLaunchKernelGGL(pn_nu_head_kernel, dim3(grid1((size_t)B * N)), dim3(256), 0, st, a->ws->logits, f_labels, f_target, B * N,
+                               a->kappa, a->tsign, a->ws->dz4, a->scal, a->pred, rooms ? N : 0);
+            PSG_LAUNCH_CHECK();
+            if ((rc = backward_impl(a->model, a->ws, nullptr, nullptr, a->dx0, st))) break;
+        } else {
+            if ((rc = forward_impl(a->model, a->ws, a->x0, a->logp, st))) break;
+            if ((rc = rooms ? psg_nu_f_loss_grad_rooms(a->ws->logp, f_labels, f_target, B, N, NCLS, a->kappa, a->tsign, a->dlogp, a->scal,
+                                                       a->pred, stream)
+                            : psg_nu_f_loss_grad(a->ws->logp, f_labels, f_target, B * N, NCLS, a->kappa, a->tsign, a->dlogp, a->scal, a->pred,
+                                                 stream)))
+                break;
+            if ((rc = backward_impl(a->model, a->ws, a->dlogp, nullptr, a->dx0, st))) break;
+        }
+        if ((rc = psg_smooth_knn_rooms(a->x0 + 3, 9, (size_t)N * 9, a->ori, 3, (size_t)N * 3, G, N, a->neighbour, a->scal + G, a->sgrad,
+                                       a->nn_state, (i > 0 || a->warm_first) ? 1 : 0, stream)))
+            break;
+        nu_set_step_consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
+        rc = rooms ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr,
+                                            a->beta1, a->beta2, a->eps, adam_t, B, N, a->active, a->scal + 2 * G, stream)
+                   : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr, a->beta1,
+                                      a->beta2, a->eps, adam_t, B, N, a->scal + 2, stream);
+        if (rc == PSG_OK)
+            rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, a->rows, N,
+                                   a->mode, a->scal, a->hist + (size_t)i * 5 * G, a->x0, a->out, a->active, a->exit_step, step, stream);
+        nu_set_step_consts(nullptr);
+    }
+    nu_set_step_consts(nullptr);
+    return rc;
+}
+
+extern "C" int psg_pointnet_nu_window(const psg_pointnet_nu_window_args *a, psg_nu_graph *graph, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws && a->w && a->m && a->v && a->x0 && a->ori && a->labels && a->dx0 && a->sgrad && a->pred &&
+                    a->scal && a->nn_state && a->hist && a->out && a->active && a->exit_step,
+                "psg_pointnet_nu_window: null argument");
+    PSG_REQUIRE(a->fused_head || a->dlogp, "psg_pointnet_nu_window: the three-kernel head needs the dlogp scratch");
+    PSG_REQUIRE(a->n_steps > 0 && a->G > 0 && a->rows > 0 && (a->G == 1 || a->rows == 1),
+                "psg_pointnet_nu_window: (G, rows) must be (1, B) or (R, 1)");
+    PSG_REQUIRE(a->G * a->rows == a->ws->B && a->N == a->ws->N, "psg_pointnet_nu_window: the workspace is for %d x %d points, not %d x %d",
+                a->ws->B, a->ws->N, a->G * a->rows, a->N);
+    PSG_REQUIRE(a->mode == 0 || (a->mask && a->n_mask), "psg_pointnet_nu_window: modes 1 and 2 need mask and n_mask");
+    PSG_REQUIRE(a->use_target ? (a->target >= 0 && a->target < NCLS) : 1, "psg_pointnet_nu_window: target class %d out of range", a->target);
+    psg_pointnet_nu_window_args key = *a;
+    key.step0 = 0; key.adam_t0 = 0; key.lr = 0.0f;      // what the device row carries
+    return nu_graph_window(graph, &key, sizeof(key), a->model->gen, a->ws->gen, a->n_steps, a->step0, a->adam_t0, a->lr, a->beta1,
+                           a->beta2, (hipStream_t)stream, [&](const float *rows) { return pn_nu_window_steps(a, rows, stream); });
 }
