@@ -118,7 +118,9 @@ size_t psg_pn2_ws_bytes(const psg_pn2_ws *ws);
  * While enabled every kernel launch of plan_build / forward / backward / nb_attack on this workspace is
  * bracketed by two events.  prof_read (blocking: waits for the events) sums the elapsed ms and counts per
  * kernel tag: 0-3 sa1-4 fwd, 4-7 fp1-4 fwd (4 = fp1+head), 8-11 fp1-4 bwd, 12-15 sa1-4 bwd, 16 fps,
- * 17 ball query, 18 three_nn, 19 gather, 20 ce grad, 21 pgd step, 22 gradient memset.  n_tags >= 23. */
+ * 17 ball query, 18 three_nn, 19 gather, 20 ce grad, 21 pgd step, 22 input-gradient gather, 23 / 24 per-point first
+ * layers fwd / bwd, 25-27 psg_pn2_backward_full only: g_rel rows, 3-NN weight gradients, per-level coordinate sums.
+ * n_tags >= 28. */
 int psg_pn2_prof_enable(psg_pn2_ws *ws, int on);
 int psg_pn2_prof_read(psg_pn2_ws *ws, int n_tags, double *total_ms, int *counts);
 
@@ -149,11 +151,20 @@ int psg_pn2_forward(psg_pn2_model *model, psg_pn2_ws *ws, int forward, const flo
 
 /* Input-gradient backward of the forward that last ran in `ws` (what autograd derives for a leaf on
  * the input features): dlogp [batch][n_point][13] = d loss / d log-probs;
- * dx0_out [batch][n_point][9] = d loss / d input features (geometry treated as constant: channels
- * 3:9 are exact, channels 0:3 exclude the paths through relative coordinates and 3-NN weights,
- * which no attack uses).  No weight gradients (the attack path never needs them). */
+ * dx0_out [batch][n_point][9] = d loss / d input features with the geometry treated as constant: channels
+ * 3:9 are exact; channels 0:3 hold the feature path only and exclude the paths through relative coordinates and
+ * 3-NN weights (the colour attacks never read them; psg_pn2_backward_full adds them).  No weight gradients (the
+ * attack path never needs them). */
 int psg_pn2_backward(psg_pn2_model *model, psg_pn2_ws *ws, int forward, const float *dlogp, float *dx0_out,
                      psg_stream stream);
+/* The same contract with the COMPLETE derivative in dx0_out[.][0:3]: what the reference's autograd returns for a leaf on
+ * the whole [B, 9, N] input - the feature path plus the relative coordinates of the four SA levels (pointnet_util.py:
+ * 126-140, new_xyz = xyz[fps_idx] included) and the 3-NN interpolation weights of the four FP levels (:301-309), with the
+ * FPS / ball-query / 3-NN indices constant.  Channels 3:9 are byte-identical to psg_pn2_backward.  No float atomics: two
+ * runs are bit-equal.  PSG_PN2_ARCH_SSG only, with the split first layers (the default; not under PSG_PN2_SPLIT=0):
+ * anything else returns PSG_ERR_ARG with a message, never a partial gradient. */
+int psg_pn2_backward_full(psg_pn2_model *model, psg_pn2_ws *ws, int forward, const float *dlogp, float *dx0_out,
+                          psg_stream stream);
 
 /* The per-iteration launches of psg_pn2_nb_attack one at a time (round 6), so that a caller - the teacher-forced parity
  * tests - can drive exactly the kernels the fused attack loop runs between nontarget.py:29 and :39 / target.py:31 and :43:
@@ -263,6 +274,12 @@ int psg_ce_logp_grad(const float *logp, const int32_t *labels, int target, int r
  * grad [B][N][9] (channels 3:6 read), ori [B][N][3], mask (nullable) [N] uint8 shared by all rooms. */
 int psg_pgd_step(float *x, const float *grad, const float *ori, const uint8_t *mask, int B, int N, float alpha,
                  float eps, float dir, int last, psg_stream stream);
+
+/* The same update on either three-channel field of the rooms: c0 = 3 is psg_pgd_step (colours); c0 = 0 moves the
+ * coordinates, channels 0:3 (the reference's loop body with the slice 0:3: sign step, eta clamped to +-eps, NO clamp to
+ * [0, 1] - coordinates are metres).  ori [B][N][3] = the clean values of that field; grad channels c0:c0+3 are read. */
+int psg_pgd_step_field(float *x, const float *grad, const float *ori, const uint8_t *mask, int B, int N, int c0,
+                       float alpha, float eps, float dir, int last, psg_stream stream);
 
 /* Fused NB_attack / tar_NB_attack on a batch (nontarget.py:18-42, target.py:18-45):
  * plan_build for `iters` forwards, then iters x (forward, CE grad, backward, pgd_step), all

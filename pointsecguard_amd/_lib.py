@@ -62,6 +62,7 @@ SIGNATURES = {
     "psg_pn2_plan_ptr": (vp, [vp, ci, ci, ci, ci]),
     "psg_pn2_forward": (ci, [vp, vp, ci, vp, vp, vp, vp]),
     "psg_pn2_backward": (ci, [vp, vp, ci, vp, vp, vp]),
+    "psg_pn2_backward_full": (ci, [vp, vp, ci, vp, vp, vp]),
     "psg_pn2_forward_lean": (ci, [vp, vp, ci, vp, vp, vp]),
     "psg_pn2_backward_colour": (ci, [vp, vp, ci, vp, vp, vp]),
     "psg_pn2_backward_colour_pgd": (ci, [vp, vp, ci, vp, vp, vp, vp, cf, cf, cf, ci, vp]),
@@ -71,6 +72,7 @@ SIGNATURES = {
     "psg_to_channel_major": (ci, [vp, ci, ci, ci, vp, vp]),
     "psg_ce_logp_grad": (ci, [vp, vp, ci, ci, ci, ci, cf, vp, vp, vp]),
     "psg_pgd_step": (ci, [vp, vp, vp, vp, ci, ci, cf, cf, cf, ci, vp]),
+    "psg_pgd_step_field": (ci, [vp, vp, vp, vp, ci, ci, ci, cf, cf, cf, ci, vp]),
     "psg_pn2_nb_attack": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, ci, ci, ci, vp, vp]),
     "psg_pointnet_model_create": (ci, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]),
     "psg_pointnet_model_destroy": (ci, [vp]),

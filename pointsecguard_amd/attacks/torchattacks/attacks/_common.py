@@ -11,6 +11,16 @@ def psg_model(model):
     return model
 
 
+FIELDS = ("color", "coord", "both")
+
+
+def check_field(field):
+    """The perturbed field of NB_attack / tar_NB_attack: colours 3:6 (the reference's attack), coordinates 0:3, or both."""
+    if field not in FIELDS:
+        raise ValueError("field must be one of %s, got %r" % (FIELDS, field))
+    return field
+
+
 def labels_to_device(labels, device, pin=False):
     """The harness hands labels over as float64 numpy (NB_nontarget_test_semseg.py:171); the reference
     casts with torch.tensor(labels, dtype=int64) (nontarget.py:25)."""

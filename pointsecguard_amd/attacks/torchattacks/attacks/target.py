@@ -5,7 +5,7 @@ import torch
 from pointsecguard_amd.models.pointnet2_sem_seg import draw_fps_starts, upload
 
 from ..attack import Attack
-from ._common import mask_to_device, psg_model
+from ._common import check_field, mask_to_device, psg_model
 from .pointnet import is_pointnet, nb_attack as pointnet_nb_attack
 
 
@@ -13,7 +13,8 @@ class tar_NB_attack(Attack):
     """Targeted norm-bounded attack: only colours under `mask` move (on every batch row), descent on
     CE(mean) of batch row 0 towards `target` (target.py:26,36-43: labels[0] / outputs[0] only)."""
 
-    def __init__(self, model, eps=0.3, alpha=2 / 255, iters=40, target=None, mask=None):
+    def __init__(self, model, eps=0.3, alpha=2 / 255, iters=40, target=None, mask=None, field="color", coord_eps=None,
+                 coord_alpha=None):
         super(tar_NB_attack, self).__init__("tar_NB_attack", model)
         self.model = model
         self.eps = eps
@@ -21,9 +22,14 @@ class tar_NB_attack(Attack):
         self.iters = iters
         self.target = target
         self.mask = mask
+        self.field = check_field(field)      # extension of the reference API: see NB_attack
+        self.coord_eps = coord_eps
+        self.coord_alpha = coord_alpha
 
     def forward(self, images, labels):
         if is_pointnet(self.model):
+            if self.field != "color":
+                raise NotImplementedError("field=%r is implemented for the PointNet++ SSG network" % self.field)
             if self.target is None or self.mask is None:
                 raise ValueError("tar_NB_attack needs target and mask")
             return pointnet_nb_attack(self, images, None, mask=self.mask, target=self.target)
@@ -34,8 +40,11 @@ class tar_NB_attack(Attack):
         B, C, N = images.shape
         mask = mask_to_device(self.mask, N, self.device)
         starts = upload(draw_fps_starts(B, N, self.iters, pinned=True), self.device, pin=True)
-        ws = net._workspace(B, N, self.iters)
+        ws = net._workspace(B, N, self.iters if self.field == "color" else 1)   # (the coordinate fields rebuild plan slot 0)
         net._generation += 1
+        if self.field != "color":
+            return ws.field_attack(net._packed(), images, None, starts, self.eps, self.alpha, self.iters, self.field,
+                                   coord_eps=self.coord_eps, coord_alpha=self.coord_alpha, mask=mask, target=int(self.target))
         return ws.nb_attack(net._packed(), images, None, starts, self.eps, self.alpha, self.iters, mask=mask,
                             target=int(self.target))
 

@@ -95,6 +95,27 @@ __global__ void pgd_step_kernel(float *__restrict__ x, const float *__restrict__
     }
 }
 
+// The same update on either three-channel field of the rooms: c0 = 3 colours (projection onto the eps ball and [0, 1]),
+// c0 = 0 coordinates (eps ball only: metres, not colours)
+__global__ void pgd_step_field_kernel(float *__restrict__ x, const float *__restrict__ grad, const float *__restrict__ ori,
+                                      const uint8_t *__restrict__ mask, int N, size_t total, int c0, float step, float eps, int last)
+{
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total * 3; t += (size_t)gridDim.x * blockDim.x) {
+        size_t pt = t / 3;
+        int ch = (int)(t % 3);
+        if (mask && !mask[pt % N]) continue;
+        size_t xi = pt * 9 + c0 + ch;
+        float g = grad[xi];
+        float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
+        float stepped = __fadd_rn(x[xi], __fmul_rn(step, sg));
+        float o = ori[t];
+        float eta = fminf(fmaxf(__fsub_rn(stepped, o), -eps), eps);
+        float proj = __fadd_rn(o, eta);
+        if (c0 == 3) proj = fminf(fmaxf(proj, 0.0f), 1.0f);
+        x[xi] = last ? stepped : proj;
+    }
+}
+
 __global__ void seg_stats_kernel(const float *__restrict__ logp, const int32_t *__restrict__ labels, int rows,
                                  int n_cls, unsigned long long *__restrict__ counters, int32_t *__restrict__ pred_out)
 {
@@ -170,6 +191,18 @@ extern "C" int psg_pgd_step(float *x, const float *grad, const float *ori, const
     size_t total = (size_t)B * N;
     hipLaunchKernelGGL(pgd_step_kernel, dim3(grid_for(total * 3)), dim3(256), 0, (hipStream_t)stream, x, grad, ori, mask,
                        N, total, dir * alpha, eps, last);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_pgd_step_field(float *x, const float *grad, const float *ori, const uint8_t *mask, int B, int N, int c0,
+                                  float alpha, float eps, float dir, int last, psg_stream stream)
+{
+    PSG_REQUIRE(x && grad && ori && B > 0 && N > 0, "psg_pgd_step_field: bad argument");
+    PSG_REQUIRE(c0 == 0 || c0 == 3, "psg_pgd_step_field: channel offset %d is neither 0 (coordinates) nor 3 (colours)", c0);
+    size_t total = (size_t)B * N;
+    hipLaunchKernelGGL(pgd_step_field_kernel, dim3(grid_for(total * 3)), dim3(256), 0, (hipStream_t)stream, x, grad, ori, mask,
+                       N, total, c0, dir * alpha, eps, last);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
 }

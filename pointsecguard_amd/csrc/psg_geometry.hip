@@ -14,21 +14,12 @@
 // reads cloud (p % n_clouds) of a [n_clouds][N][3] array, so the level-0 xyz of a room is shared by
 // all attack iterations while deeper levels have one cloud per problem.
 #include "psg_common.h"
+#include "psg_sqdist.cuh"
 
 namespace {
 
-__device__ __forceinline__ float sumsq3(float x, float y, float z)
-{
-    return __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
-}
-
-// square_distance(src, dst) for one pair: ((-2*dot) + |src|^2) + |dst|^2, dot = FMA chain over k
-__device__ __forceinline__ float sqdist(float sx, float sy, float sz, float ssq, float dx, float dy, float dz,
-                                        float dsq)
-{
-    float dot = __fmaf_rn(sz, dz, __fmaf_rn(sy, dy, __fmul_rn(sx, dx)));
-    return __fadd_rn(__fadd_rn(__fmul_rn(-2.0f, dot), ssq), dsq);
-}
+using psg::sqdist;   // square_distance for one pair, the pinned fp32 order (psg_sqdist.cuh)
+using psg::sumsq3;
 
 typedef float v2f __attribute__((ext_vector_type(2)));   // operand of the packed-fp32 pipe (v_pk_*_f32)
 

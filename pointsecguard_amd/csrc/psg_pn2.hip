@@ -22,6 +22,7 @@
 #include "psg_common.h"
 #include "psg_pn2_kernels.cuh"
 #include "psg_chain.cuh"
+#include "psg_pn2_geomgrad.cuh"
 
 using namespace psg;
 
@@ -198,6 +199,7 @@ struct psg_pn2_model {
     PackedLayer fa[3], fb[3];
     bool fsplit[3] = {false, false, false};
     float *w1feat[2] = {nullptr, nullptr};               // level 0, per scale: the first layer's feature columns as plain rows [C1][9] (sa_l1t_colour)
+    float *w1x[4] = {nullptr, nullptr, nullptr, nullptr}; // SSG split levels: the first layer's xyz columns as plain rows [3][C1] (sa_grel_kernel)
     void *arena = nullptr;
 };
 
@@ -236,6 +238,11 @@ struct psg_pn2_ws {
     // gradients (every buffer has exactly one writer: nothing is zeroed or accumulated into)
     float *dact[7];
     float *dx0;           // [B][N][9]
+    // coordinate gradient (psg_pn2_backward_full, SSG): g_rel rows of the split SA levels, dL/dd of the FP levels' three
+    // neighbours, and the coordinate gradient of the points of levels 1 - 4
+    float4 *grel[4];      // [B][S_l*K] list order (levels 1 - 3)
+    float4 *fpg[4];       // [B][N_l]
+    float *gxyz[5];       // [B][N_l][3] (levels 1 - 4)
     // attack state
     float *x0, *ori;      // [B][N][9], [B][N][3]
     unsigned long long *dbg;  // diagnostics scratch (diagnostic builds, bit 256), 4 words per workgroup
@@ -345,7 +352,8 @@ BwdLayer bwd_layer(const PackedLayer &p, const uint16_t *mask)
 
 // kernel tags of the per-launch profile (psg_pn2_prof_read)
 enum { TAG_SA_FWD = 0, TAG_FP_FWD = 4, TAG_FP_BWD = 8, TAG_SA_BWD = 12, TAG_FPS = 16, TAG_BALL = 17, TAG_NN = 18,
-       TAG_GATHER = 19, TAG_CE = 20, TAG_PGD = 21, TAG_ZERO = 22, TAG_PW_FWD = 23, TAG_PW_BWD = 24, TAG_COUNT = 25 };
+       TAG_GATHER = 19, TAG_CE = 20, TAG_PGD = 21, TAG_ZERO = 22, TAG_PW_FWD = 23, TAG_PW_BWD = 24,
+       TAG_GEOM_GREL = 25, TAG_GEOM_WGRAD = 26, TAG_GEOM_GX = 27, TAG_COUNT = 28 };   // 25-27: psg_pn2_backward_full only
 
 struct ProfScope {
     psg_pn2_ws *ws;
@@ -1247,6 +1255,13 @@ void ws_layout(psg_pn2_ws *ws, Bump &bp)
     ws->nb_labels = bp.take<int32_t>((size_t)B * ws->N);
     ws->nb_starts = bp.take<int32_t>((size_t)F * 4 * B);
     ws->nb_mask = bp.take<uint8_t>((size_t)ws->N);
+    for (int l = 0; l < 4; ++l) {   // (behind everything else: the offsets of the buffers above do not depend on them)
+        const bool full = A.id == PSG_PN2_ARCH_SSG;
+        ws->grel[l] = full && l >= 1 ? bp.take<float4>((size_t)B * kS[l] * A.sc[l][0].K) : nullptr;
+        ws->fpg[l] = full ? bp.take<float4>((size_t)B * ws->Nl[l]) : nullptr;
+        ws->gxyz[l + 1] = full ? bp.take<float>((size_t)B * ws->Nl[l + 1] * 3) : nullptr;
+    }
+    ws->gxyz[0] = nullptr;
 }
 
 }  // namespace
@@ -1334,9 +1349,23 @@ extern "C" int psg_pn2_model_create_arch(psg_ctx *ctx, int arch, const float *co
             for (int f = 0; f < D; ++f) w1f_host[sc][(size_t)o * D + f] = weights[li][(size_t)o * cin + fo + f];
         total += w1f_host[sc].size() * 4 + 256;
     }
+    std::vector<float> w1x_host[4];
+    for (int l = 1; l < 4; ++l) {   // SSG column order of a first layer: [rel_xyz(3), feats(D)]
+        if (A.id != PSG_PN2_ARCH_SSG || !m->split[l]) continue;
+        const int li = A.sc[l][0].l0, cin = A.cin[li], cout = A.cout[li];
+        w1x_host[l].resize((size_t)3 * cout);
+        for (int o = 0; o < cout; ++o)
+            for (int c = 0; c < 3; ++c) w1x_host[l][(size_t)c * cout + o] = weights[li][(size_t)o * cin + c];
+        total += w1x_host[l].size() * 4 + 256;
+    }
     PSG_CHECK_HIP(hipMalloc(&m->arena, total));
     Bump bp;
     bp.base = (char *)m->arena;
+    for (int l = 1; l < 4; ++l) {
+        if (w1x_host[l].empty()) continue;
+        m->w1x[l] = bp.take<float>(w1x_host[l].size());
+        PSG_CHECK_HIP(psg::copy_sync(m->w1x[l], w1x_host[l].data(), w1x_host[l].size() * 4, hipMemcpyHostToDevice));
+    }
     for (int sc = 0; sc < A.ns; ++sc) {
         m->w1feat[sc] = bp.take<float>(w1f_host[sc].size());
         PSG_CHECK_HIP(psg::copy_sync(m->w1feat[sc], w1f_host[sc].data(), w1f_host[sc].size() * 4, hipMemcpyHostToDevice));
@@ -1606,7 +1635,7 @@ extern "C" int psg_pn2_forward(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const 
 }
 
 static int backward_impl(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, const float *dlogp,
-                         float *dx0, int c_lo, int c_hi, hipStream_t st, const PgdFuse *pgd = nullptr)
+                         float *dx0, int c_lo, int c_hi, hipStream_t st, const PgdFuse *pgd = nullptr, bool rel0 = false)
 {
     const ArchDesc &A = *m->arch;
     int rc;
@@ -1617,7 +1646,8 @@ static int backward_impl(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float 
     if ((rc = run_fp_bwd<3>(m, ws, fwd, nullptr, nullptr, st))) return rc;
     for (int l = 3; l >= 0; --l) {
         for (int sc = 0; sc < A.ns; ++sc) {
-            if ((rc = run_sa_bwd(m, ws, l, sc, fwd, l ? 0 : c_lo, l ? A.C[l] : c_hi, st))) return rc;
+            // (rel0, psg_pn2_backward_full: level 0 also stores the three rel_xyz columns 9..11 of its rows; same values in 0..8)
+            if ((rc = run_sa_bwd(m, ws, l, sc, fwd, l ? 0 : c_lo, l ? A.C[l] : (rel0 ? A.C[0] + 3 : c_hi), st))) return rc;
             if (m->split[l] && (rc = run_pw_bwd(m, ws, l, sc, fwd, st))) return rc;
         }
     }
@@ -1655,6 +1685,99 @@ extern "C" int psg_pn2_backward(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const
     }
     // the log_softmax backward reads the log-probs of the resident forward, kept in ws->logp
     return backward_impl(m, ws, fwd, ws->logp, dlogp, dx0_out, 0, 9, (hipStream_t)stream);
+}
+
+// The geometric paths of the coordinate gradient, added to channels 0:3 of dx0 (which hold the feature-path gradient):
+// psg_pn2_geomgrad.cuh.  Levels from the coarsest down: a level's gradient is complete before it goes down through fps.
+static int geometry_grad(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *dx0, hipStream_t st)
+{
+    const ArchDesc &A = *m->arch;
+    const int B = ws->B;
+    const size_t prob = (size_t)fwd * B;
+    auto xyz_of = [&](int l) { return l == 0 ? ws->xyz0 : ws->xyz[l] + prob * ws->Nl[l] * 3; };
+    // level 0 is not split: its rows are the grouped-input gradient in LDS channel order [feats(C[0]), rel_xyz(3)]
+    const int ld0 = gsa_stride(A, 0), rel0_col = A.C[0];
+    for (int l = 1; l < 4; ++l) {   // g_rel rows of the split levels
+        const int C1 = A.cout[A.sc[l][0].l0], g_rows = kS[l] * A.sc[l][0].K;
+        ProfScope prof(ws, TAG_GEOM_GREL, st);
+        hipLaunchKernelGGL(sa_grel_kernel, dim3(std::min(256, ceil_div(g_rows, GG_NT / GG_LANES)), B), dim3(GG_NT),
+                           (size_t)3 * C1 * sizeof(float), st, ws->gsa[l][0], ws->ginv_off[l][0] + prob * (ws->Nl[l] + 1), ws->Nl[l],
+                           g_rows, m->w1x[l], C1, ws->grel[l]);
+        PSG_LAUNCH_CHECK();
+    }
+    for (int l = 0; l < 4; ++l) {   // dL/dd of every fine point's three neighbours
+        const bool fs = l < 3 && m->fsplit[l];
+        const int C = fs ? A.cout[A.fp_first[l]] : A.cin[A.fp_first[l]] - (l == 0 ? 0 : A.C[l]);
+        const float *src = fs ? ws->tfp[l] : ws->act[fp_in2_slot(l)];
+        ProfScope prof(ws, TAG_GEOM_WGRAD, st);
+        hipLaunchKernelGGL(fp_wgrad_kernel, dim3(std::min(512, ceil_div(ws->Nl[l], GG_NT / GG_LANES)), B), dim3(GG_NT), 0, st,
+                           ws->dint[l], src, C, ws->nn_idx[l] + prob * ws->Nl[l] * 3, xyz_of(l), xyz_of(l + 1), ws->Nl[l],
+                           ws->Nl[l + 1], ws->fpg[l]);
+        PSG_LAUNCH_CHECK();
+    }
+    for (int L = 4; L >= 0; --L) {
+        GxArgs a{};
+        const int n = ws->Nl[L];
+        a.n = n;
+        a.xyz = xyz_of(L);
+        if (L <= 3) {
+            a.src_off = ws->ginv_off[L][0] + prob * (n + 1);
+            a.src_n = kS[L] * A.sc[L][0].K;
+            if (L == 0) { a.src_rows = ws->gsa[0][0]; a.src_ld = ld0; a.src_col = rel0_col; }
+            else { a.src_rows = (const float *)ws->grel[L]; a.src_ld = 4; a.src_col = 0; }
+            a.nn_idx = ws->nn_idx[L] + prob * n * 3;
+            a.fpg = ws->fpg[L];
+            a.xyz_c = xyz_of(L + 1);
+            a.n_c = ws->Nl[L + 1];
+        }
+        if (L >= 1) {
+            const int lf = L - 1;
+            a.K = A.sc[lf][0].K;
+            a.grp_n = kS[lf] * a.K;
+            a.grp_pos = ws->ginv_pos[lf][0] + prob * a.grp_n;
+            if (lf == 0) { a.grp_rows = ws->gsa[0][0]; a.grp_ld = ld0; a.grp_col = rel0_col; }
+            else { a.grp_rows = (const float *)ws->grel[lf]; a.grp_ld = 4; a.grp_col = 0; }
+            a.n_f = ws->Nl[lf];
+            a.cinv_off = ws->inv_off[lf] + prob * (n + 1);
+            a.cinv_ent = ws->inv_ent[lf] + prob * a.n_f * 3;
+            a.f_nn_idx = ws->nn_idx[lf] + prob * a.n_f * 3;
+            a.f_fpg = ws->fpg[lf];
+            a.xyz_f = xyz_of(lf);
+        }
+        a.out = L == 0 ? dx0 : ws->gxyz[L];
+        a.out_ld = L == 0 ? 9 : 3;
+        a.accumulate = L == 0 ? 1 : 0;
+        ProfScope prof(ws, TAG_GEOM_GX, st);   // (with the level's gx_fps_down_kernel)
+        hipLaunchKernelGGL(gx_level_kernel, dim3(std::min(2048, ceil_div(B * n, GG_NT))), dim3(GG_NT), 0, st, a, B);
+        PSG_LAUNCH_CHECK();
+        if (L <= 3) {
+            hipLaunchKernelGGL(gx_fps_down_kernel, dim3(std::min(2048, ceil_div(B * kS[L], GG_NT))), dim3(GG_NT), 0, st,
+                               (const float *)ws->gxyz[L + 1], (const int32_t *)(ws->fps[L] + prob * kS[L]), B, kS[L], n, a.out, a.out_ld);
+            PSG_LAUNCH_CHECK();
+        }
+    }
+    return PSG_OK;
+}
+
+extern "C" int psg_pn2_backward_full(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *dlogp, float *dx0_out,
+                                     psg_stream stream)
+{
+    PSG_REQUIRE(m && ws && dlogp && dx0_out, "psg_pn2_backward_full: null argument");
+    PSG_REQUIRE(m->arch == ws->arch, "psg_pn2_backward_full: model and workspace were created for different architectures");
+    PSG_REQUIRE(m->arch->id == PSG_PN2_ARCH_SSG, "psg_pn2_backward_full: the coordinate gradient is implemented for the SSG "
+                "network only (MSG: use psg_pn2_backward, whose channels 0:3 exclude the geometric paths)");
+    PSG_REQUIRE(m->split[1] && m->split[2] && m->split[3] && m->w1x[1] && m->w1x[2] && m->w1x[3],
+                "psg_pn2_backward_full: needs the split first layers of SA levels 1 - 3 (model created under PSG_PN2_SPLIT=0)");
+    PSG_REQUIRE(ws->grel[1] && arch_split(*ws->arch, 1), "psg_pn2_backward_full: workspace created under PSG_PN2_SPLIT=0");
+    PSG_REQUIRE(!m->split[0] && gsa_stride(*m->arch, 0) == m->arch->C[0] + 3,
+                "psg_pn2_backward_full: level 0's rows are expected whole, [feats, rel_xyz]");
+    if (ws->fwd_slot != fwd) {
+        set_error("psg_pn2_backward_full: forward %d is not the one resident in the workspace (%d)", fwd, ws->fwd_slot);
+        return PSG_ERR_STATE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = backward_impl(m, ws, fwd, ws->logp, dlogp, dx0_out, 0, 9, st, nullptr, true)) return rc;
+    return geometry_grad(m, ws, fwd, dx0_out, st);
 }
 
 // The colour channels (3..5) of the input gradient only: what the NU loop's Adam step reads (psg_attack.hip: nu_window_steps).

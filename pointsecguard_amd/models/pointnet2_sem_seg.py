@@ -75,15 +75,23 @@ class _PN2Function(torch.autograd.Function):
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the same "
                                "module; only the most recent forward can be back-propagated")
         ws = ctx.ws
-        dx0 = ws.backward(ctx.model, 0, dlogp.contiguous().float())
+        dx0 = ws.backward(ctx.model, 0, dlogp.contiguous().float(), full=ctx.module.input_grad == "full")
         B, N = ws.batch, ws.n_point
         dx = torch.empty(B, 9, N, device=dlogp.device, dtype=torch.float32)
         _lib.call("psg_to_channel_major", runtime.ptr(dx0), B, 9, N, runtime.ptr(dx), runtime.stream())
         return dx, None
 
 
+INPUT_GRADS = ("features", "full")
+
+
 class get_model(nn.Module):
     L4_CHANNELS = 512
+    # What backward returns in channels 0:3 of the input gradient.  "features" (default): the feature path only, geometry
+    # constant - all the colour attacks need.  "full": the complete derivative the reference's autograd returns for a leaf on
+    # the whole input, through the relative coordinates and the 3-NN weights as well (psg_pn2_backward_full).  Channels 3:9
+    # are the same bytes either way; l4_points stays non-differentiable.
+    input_grad = "features"
 
     def __init__(self, num_classes):
         super(get_model, self).__init__()
@@ -132,6 +140,8 @@ class get_model(nn.Module):
         runtime.require_cuda(xyz, "xyz")
         if xyz.dim() != 3 or xyz.shape[1] != 9:
             raise ValueError("expected input [B, 9, N], got %s" % (tuple(xyz.shape),))
+        if self.input_grad not in INPUT_GRADS:
+            raise ValueError("input_grad must be one of %s (got %r)" % (INPUT_GRADS, self.input_grad))
         x, l4_points = _PN2Function.apply(xyz, self)
         return x, l4_points
 

@@ -174,14 +174,62 @@ class PN2Workspace:
             _lib.call("psg_pn2_forward", model.handle, self.handle, slot, ptr(x0), ptr(logp), ptr(l4), stream())
         return logp
 
-    def backward(self, model, slot, dlogp, dx0=None, colour_only=False):
-        """colour_only=True: the backward of the fused attack loops - channels 3..5 of dx0 only (the rest is zero here)."""
+    def backward(self, model, slot, dlogp, dx0=None, colour_only=False, full=False):
+        """colour_only=True: the backward of the fused attack loops - channels 3..5 of dx0 only (the rest is zero here).
+        full=True: psg_pn2_backward_full - channels 0:3 are the complete derivative, geometric paths included (SSG)."""
         require_cuda(dlogp, "dlogp", torch.float32)
+        assert not (colour_only and full)
         if dx0 is None:
             dx0 = (torch.zeros if colour_only else torch.empty)(self.batch, self.n_point, 9, device=dlogp.device, dtype=torch.float32)
-        _lib.call("psg_pn2_backward_colour" if colour_only else "psg_pn2_backward", model.handle, self.handle, slot, ptr(dlogp),
-                  ptr(dx0), stream())
+        name = "psg_pn2_backward_colour" if colour_only else ("psg_pn2_backward_full" if full else "psg_pn2_backward")
+        _lib.call(name, model.handle, self.handle, slot, ptr(dlogp), ptr(dx0), stream())
         return dx0
+
+    def field_attack(self, model, images, labels, starts, eps, alpha, iters, field, coord_eps=None, coord_alpha=None,
+                     mask=None, target=None):
+        """NB_attack / tar_NB_attack on the coordinate field (field = "coord") or on coordinates and colours together
+        ("both"): the reference's loop body (nontarget.py:28-39, target.py:31-43) with the slice 0:3 beside / instead of
+        3:6.  Geometry moves with the points, so every iteration rebuilds the plan from the current xyz (starts
+        [iters][4][B]: four FPS draws per iteration) - a stream-ordered host loop of plan_build(n_forward = 1), forward,
+        psg_ce_logp_grad, psg_pn2_backward_full and one psg_pgd_step_field per field, with no read-back inside.  Like the
+        reference, the returned fields are the un-projected last step."""
+        require_cuda(images, "images", torch.float32)
+        require_cuda(starts, "starts", torch.int32)
+        if field not in ("coord", "both"):
+            raise _lib.PsgError("field must be 'color', 'coord' or 'both' (got %r)" % (field,))
+        B, N = self.batch, self.n_point
+        assert images.shape == (B, 9, N) and starts.numel() == iters * 4 * B
+        if labels is not None:
+            require_cuda(labels, "labels", torch.int32)
+        if mask is not None:
+            require_cuda(mask, "mask", torch.uint8)
+        coord_eps = eps if coord_eps is None else coord_eps
+        coord_alpha = alpha if coord_alpha is None else coord_alpha
+        dev = images.device
+        x0 = torch.empty(B, N, 9, device=dev, dtype=torch.float32)
+        _lib.call("psg_to_point_major", ptr(images), B, 9, N, ptr(x0), stream())
+        ori_xyz, ori_rgb = x0[:, :, 0:3].contiguous(), x0[:, :, 3:6].contiguous()
+        logp = torch.empty(B, N, NUM_CLASSES, device=dev, dtype=torch.float32)
+        dlogp = torch.empty_like(logp)
+        dx0 = torch.empty_like(x0)
+        starts = starts.reshape(iters, 4 * B)
+        direction = 1.0 if target is None else -1.0
+        for it in range(iters):
+            last = 1 if it == iters - 1 else 0
+            _lib.call("psg_pn2_plan_build", self.handle, ptr(x0), ptr(starts[it]), 1, stream())
+            _lib.call("psg_pn2_forward", model.handle, self.handle, 0, ptr(x0), ptr(logp), None, stream())
+            # non-targeted: CE_sum over all rooms / N (nontarget.py:34); targeted: CE_mean of room 0 (target.py:36-39)
+            _lib.call("psg_ce_logp_grad", ptr(logp), ptr(labels) if target is None else None, 0 if target is None else int(target),
+                      B * N, B * N if target is None else N, NUM_CLASSES, 1.0 / N, ptr(dlogp), None, stream())
+            _lib.call("psg_pn2_backward_full", model.handle, self.handle, 0, ptr(dlogp), ptr(dx0), stream())
+            _lib.call("psg_pgd_step_field", ptr(x0), ptr(dx0), ptr(ori_xyz), ptr(mask), B, N, 0, float(coord_alpha),
+                      float(coord_eps), direction, last, stream())
+            if field == "both":
+                _lib.call("psg_pgd_step_field", ptr(x0), ptr(dx0), ptr(ori_rgb), ptr(mask), B, N, 3, float(alpha), float(eps),
+                          direction, last, stream())
+        out = torch.empty_like(images)
+        _lib.call("psg_to_channel_major", ptr(x0), B, 9, N, ptr(out), stream())
+        return out
 
     def backward_pgd(self, model, slot, dlogp, x0, ori, alpha, eps, mask=None, descent=False, last=False):
         """The colour-only backward with the NB / tar_NB update applied to x0 in place by the gradient's last gather (what
@@ -212,7 +260,8 @@ class PN2Workspace:
 
     PROF_TAGS = ("sa1_fwd", "sa2_fwd", "sa3_fwd", "sa4_fwd", "fp1_head_fwd", "fp2_fwd", "fp3_fwd", "fp4_fwd",
                  "fp1_head_bwd", "fp2_bwd", "fp3_bwd", "fp4_bwd", "sa1_bwd", "sa2_bwd", "sa3_bwd", "sa4_bwd",
-                 "fps", "ball_query", "three_nn", "gather", "ce_grad", "pgd_step", "dx0_gather", "pw_fwd", "pw_bwd")
+                 "fps", "ball_query", "three_nn", "gather", "ce_grad", "pgd_step", "dx0_gather", "pw_fwd", "pw_bwd",
+                 "geom_grel", "geom_wgrad", "geom_gx")
 
     def prof_enable(self, on=True):
         _lib.call("psg_pn2_prof_enable", self.handle, 1 if on else 0)
