@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unordered_set>
 
 #include "psg_common.h"
 
@@ -129,15 +130,30 @@ bool trace_sync_enabled()
     return on;
 }
 
-void trace_sync_point(const char *file, int line)
+void trace_sync_point(const char *site)
 {
     static unsigned long n = 0;
-    const char *base = strrchr(file, '/');
-    fprintf(stderr, "[psg trace] launch %lu at %s:%d issued\n", ++n, base ? base + 1 : file, line);
+    const char *base = strrchr(site, '/');
+    fprintf(stderr, "[psg trace] launch %lu at %s issued\n", ++n, base ? base + 1 : site);
     fflush(stderr);
     hipError_t e = hipDeviceSynchronize();
     fprintf(stderr, "[psg trace] launch %lu done (%s)\n", n, hipGetErrorString(e));
     fflush(stderr);
+}
+
+hipError_t allow_big_lds(const void *kern)
+{
+    static std::mutex mu;
+    static std::unordered_set<const void *> done;
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count(kern)) return hipSuccess;
+    // (the 160 KiB of a workgroup hold the kernel's static __shared__ arrays too: the dynamic part may take what they leave)
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, kern);
+    if (e == hipSuccess) e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
+    if (e == hipSuccess) done.insert(kern);
+    if (trace_sync_enabled()) fprintf(stderr, "[psg trace] LDS opt-in %zu (%s)\n", done.size(), hipGetErrorString(e));
+    return e;
 }
 
 void set_error(const char *fmt, ...)

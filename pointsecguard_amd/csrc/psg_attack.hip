@@ -904,9 +904,7 @@ static int smooth_knn_launch(const float *adv_color, int adv_stride, size_t adv_
     const dim3 grid(psg::ceil_div(N, SM_T / (wide ? 4 : 16)), B);
 #define PSG_SMOOTH_LAUNCH(NBT, SUB)                                                                                              \
     do {                                                                                                                         \
-        if (lds > 48 * 1024)                                                                                                     \
-            PSG_CHECK_HIP(hipFuncSetAttribute((const void *)smooth_knn_kernel<NBT, SUB>,                                         \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
+        if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)smooth_knn_kernel<NBT, SUB>));                       \
         hipLaunchKernelGGL((smooth_knn_kernel<NBT, SUB>), grid, dim3(SM_T), lds, (hipStream_t)stream, adv_color, adv_stride,     \
                            ref_color, ref_stride, N, nb, dist_sum, grad_out, symmetric, adv_room_stride, ref_room_stride,        \
                            nn_io, have_prev);                                                                                    \

@@ -22,7 +22,7 @@ hipError_t copy_sync(void *dst, const void *src, size_t bytes, hipMemcpyKind kin
 // legacy stream - and its hipDeviceSynchronize - INVALIDATE a hipStreamCaptureModeThreadLocal capture in progress on any
 // stream of the process, blocking or not (the caller gets hipErrorStreamCaptureImplicit / ...Unsupported, the capturing
 // thread's next launch hipErrorStreamCaptureInvalidated); hipMalloc / hipFree, stream and event creation,
-// hipFuncSetAttribute, async work on stream 0 and hipStreamSynchronize do not.  So no entry point that can run beside a
+// the LDS opt-in (allow_big_lds), async work on stream 0 and hipStreamSynchronize do not.  So no entry point that can run beside a
 // capture (creation, upload, forward / backward / attack) uses the legacy-stream forms; only the test read-backs
 // (psg_*_debug_read, psg_gcn_knn_stats, psg_rla_sampler_possibility) synchronise the device.
 hipError_t memset_sync(void *dst, int value, size_t bytes);
@@ -54,14 +54,27 @@ int env_int(const char *name, int dflt);
 // Diagnosis only (PSG_TRACE_SYNC=1, eager launches outside any stream capture): after every checked launch the device is
 // synchronised and the launch site is written to stderr, so that a run that stops shows the last launch that completed
 // and the one that did not (tools/profile_round.sh gmfma_trace; DESIGN.md section 4, "the counter-pass hang").
+// A site is "file:line", optionally "#variant" behind it, without whitespace: PSG_SITE where the launch is written.  A launch
+// helper takes the site from its CALLER (psg_pn2.hip: launch_lds), so that paths which share the helper - or one source
+// line: PSG_SITE "#colour" - keep sites of their own; tests/test_gpu_alt_paths.py tells the switch-selected paths apart by them.
 bool trace_sync_enabled();
-void trace_sync_point(const char *file, int line);
+void trace_sync_point(const char *site);
 
-#define PSG_LAUNCH_CHECK()                                                                       \
+#define PSG_STR_(x) #x
+#define PSG_STR(x) PSG_STR_(x)
+#define PSG_SITE __FILE__ ":" PSG_STR(__LINE__)
+#define PSG_LAUNCH_CHECK_AT(site)                                                                \
     do {                                                                                         \
         PSG_CHECK_HIP(hipGetLastError());                                                        \
-        if (psg::trace_sync_enabled()) psg::trace_sync_point(__FILE__, __LINE__);                 \
+        if (psg::trace_sync_enabled()) psg::trace_sync_point(site);                               \
     } while (0)
+#define PSG_LAUNCH_CHECK() PSG_LAUNCH_CHECK_AT(PSG_SITE)
+
+// The one dynamic-LDS opt-in of the library (psg_api.hip): a launch that asks for more than 48 KiB calls this first.  The
+// kernel is opted into the device maximum (160 KiB less its static LDS; the attribute changes neither code nor occupancy) by ONE driver call per
+// kernel and process - memoised under a mutex: the one-call-per-room NU harness launches from twelve host threads - so a
+// launch path never reaches the driver for a kernel that is opted in.  Under PSG_TRACE_SYNC every driver call is printed.
+hipError_t allow_big_lds(const void *kern);
 
 // Every model / workspace handle gets a process-unique, never re-used generation number at creation.  The hipGraph keys of the
 // replayed loops compare THESE, not handle addresses: the allocator may hand a new handle the address of a freed one, and a

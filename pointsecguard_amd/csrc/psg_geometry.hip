@@ -492,9 +492,7 @@ int launch_fps(const float *xyz, int n_clouds, int P, int N, int S, const int32_
                hipStream_t st)
 {
     size_t lds = (size_t)NT * PPT * 3 * 4 + 2 * (NT / 64) * 8;
-    if (lds > 48 * 1024)
-        PSG_CHECK_HIP(hipFuncSetAttribute((const void *)fps_kernel<NT, PPT>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)fps_kernel<NT, PPT>));
     hipLaunchKernelGGL((fps_kernel<NT, PPT>), dim3(P), dim3(NT), lds, st, xyz, n_clouds, N, S, start, out);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
@@ -560,19 +558,13 @@ extern "C" int psg_ball_query(psg_ctx *ctx, const float *xyz, int n_clouds, cons
     const size_t soa = (size_t)((N + 255) & ~255) * 4 * sizeof(float);
     if (!scan_only && N >= 2048 && N <= 4096 && r2 > 0.0f && r2 < 1e30f) {
         const size_t lds = soa + (size_t)(2 * BQG_CELLS + 1) * 4 + (size_t)((N + 255) & ~255) * 2;
-        static bool big = false;
-        if (!big) {
-            PSG_CHECK_HIP(hipFuncSetAttribute((const void *)ball_query_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            big = true;
-        }
+        if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)ball_query_grid_kernel));
         hipLaunchKernelGGL(ball_query_grid_kernel, dim3(psg::ceil_div(S, BQG_CPB), P), dim3(BQ_THREADS), lds, (hipStream_t)stream, xyz,
                            n_clouds, new_xyz, N, S, r2, K, out_idx);
         PSG_LAUNCH_CHECK();
         return PSG_OK;
     }
-    if (soa > 48 * 1024)
-        PSG_CHECK_HIP(hipFuncSetAttribute((const void *)ball_query_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)soa));
+    if (soa > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)ball_query_kernel));
     hipLaunchKernelGGL(ball_query_kernel, dim3(psg::ceil_div(S, BQ_CPB), P), dim3(BQ_THREADS), soa,
                        (hipStream_t)stream, xyz, n_clouds, new_xyz, N, S, r2, K, out_idx);
     PSG_LAUNCH_CHECK();
@@ -586,9 +578,7 @@ extern "C" int psg_three_nn(psg_ctx *ctx, const float *xyz1, int n_clouds1, cons
     PSG_REQUIRE(P > 0 && n_clouds1 > 0 && N > 0 && S >= 3, "psg_three_nn: bad sizes (need S >= 3)");
     PSG_REQUIRE(S <= 8192, "psg_three_nn: S=%d exceeds the LDS-resident limit 8192", S);
     size_t lds = (size_t)2 * ((S + 1) / 2) * sizeof(float4);
-    if (lds > 48 * 1024)
-        PSG_CHECK_HIP(hipFuncSetAttribute((const void *)three_nn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)lds));
+    if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)three_nn_kernel));
     hipLaunchKernelGGL(three_nn_kernel, dim3(psg::ceil_div(N, NN_THREADS), P), dim3(NN_THREADS), lds,
                        (hipStream_t)stream, xyz1, n_clouds1, xyz2, N, S, out_idx, out_w);
     PSG_LAUNCH_CHECK();

@@ -82,9 +82,8 @@ hipError_t knn_setup()
     static std::once_flag once;
     static hipError_t rc = hipSuccess;
     std::call_once(once, [] {
-        rc = hipFuncSetAttribute((const void *)knn_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_fused_lds_bytes());
-        if (rc == hipSuccess)
-            rc = hipFuncSetAttribute((const void *)knn_bf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_bf_lds_bytes());
+        rc = allow_big_lds((const void *)knn_fused_kernel);
+        if (rc == hipSuccess) rc = allow_big_lds((const void *)knn_bf_kernel);
     });
     return rc;
 }

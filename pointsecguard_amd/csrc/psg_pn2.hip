@@ -15,8 +15,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <unordered_set>
 #include <vector>
 
 #include "psg_common.h"
@@ -259,13 +257,9 @@ struct psg_pn2_ws {
     // events: the reference's harness calls from the legacy default stream, which cannot capture
     hipStream_t nb_stream = nullptr;
     hipEvent_t nb_ev[2] = {nullptr, nullptr};
-    // optional per-launch HIP-event timing (psg_pn2_prof_enable); off in normal operation
     // attack loops: module outputs nobody reads are not written (fp2 - fp4 under the FP split: the finer module gathers T rows)
-    bool lean = false;
-    bool prof_on = false;
-    std::vector<hipEvent_t> prof_ev;   // pairs
-    std::vector<int> prof_tag;
-    size_t prof_used = 0;
+    bool lean = false;        // (set and cleared by psg::pn2_forward_lean only)
+    psg::EvLog prof;          // optional per-launch HIP-event timing (psg_pn2_prof_enable); off in normal operation
 };
 
 namespace psg {
@@ -315,18 +309,8 @@ std::vector<float> pack_bwd(const float *w, int cin, int cout, const std::vector
     return out;
 }
 
-// [mb][k8][64] float4 -> [k8][mb][64] float4 (one k8-step of all four 32-row blocks contiguous)
-std::vector<float> k8_major(const std::vector<float> &packed, int mb, int k8)
-{
-    std::vector<float> out((size_t)mb * k8 * 256, 0.0f);
-    for (int m = 0; m < mb; ++m)
-        for (int k = 0; k < k8; ++k)
-            std::copy(packed.begin() + ((size_t)m * k8 + k) * 256, packed.begin() + ((size_t)m * k8 + k + 1) * 256,
-                      out.begin() + ((size_t)k * mb + m) * 256);
-    return out;
-}
-
-// same, zero-padding k8 up to k8_pad chunks (the wave-private chain kernels want multiples of 4)
+// [mb][k8][64] float4 -> [k8_pad][mb][64] float4 (one k8-step of all four 32-row blocks contiguous), k8 zero-padded up to
+// k8_pad chunks (the wave-private chain kernels want multiples of 4 on their backward side)
 std::vector<float> k8_major_padded(const std::vector<float> &packed, int mb, int k8, int k8_pad)
 {
     std::vector<float> out((size_t)mb * k8_pad * 256, 0.0f);
@@ -355,82 +339,18 @@ enum { TAG_SA_FWD = 0, TAG_FP_FWD = 4, TAG_FP_BWD = 8, TAG_SA_BWD = 12, TAG_FPS 
        TAG_GATHER = 19, TAG_CE = 20, TAG_PGD = 21, TAG_ZERO = 22, TAG_PW_FWD = 23, TAG_PW_BWD = 24,
        TAG_GEOM_GREL = 25, TAG_GEOM_WGRAD = 26, TAG_GEOM_GX = 27, TAG_COUNT = 28 };   // 25-27: psg_pn2_backward_full only
 
-struct ProfScope {
-    psg_pn2_ws *ws;
-    hipStream_t st;
-    hipEvent_t stop = nullptr;
-    ProfScope(psg_pn2_ws *w, int tag, hipStream_t s) : ws(w), st(s)
-    {
-        if (!ws->prof_on) return;
-        if (ws->prof_used + 2 > ws->prof_ev.size()) {
-            for (int i = 0; i < 256; ++i) {
-                hipEvent_t e;
-                if (hipEventCreate(&e) != hipSuccess) return;
-                ws->prof_ev.push_back(e);
-            }
-        }
-        hipEvent_t start = ws->prof_ev[ws->prof_used];
-        stop = ws->prof_ev[ws->prof_used + 1];
-        ws->prof_used += 2;
-        ws->prof_tag.push_back(tag);
-        (void)hipEventRecord(start, st);
-    }
-    ~ProfScope()
-    {
-        if (stop) (void)hipEventRecord(stop, st);
-    }
-};
-
-// opt a kernel into the full 160 KiB of dynamic LDS once (not per launch)
-hipError_t allow_big_lds(const void *kern)
-{
-    static std::mutex mu;
-    static std::unordered_set<const void *> done;
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.count(kern)) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) done.insert(kern);
-    return e;
-}
-
+// Every launch with a dynamic LDS buffer of `blocks8` blocks of `blk` floats goes through here: size check, the shared LDS
+// opt-in above 48 KiB, the profile scope and the launch check.  `site` is the CALLER's launch site (PSG_SITE, psg_common.h).
 template <typename KernelT, typename ArgsT>
-int launch_lds(psg_pn2_ws *ws, int tag, KernelT kern, dim3 grid, int threads, int blocks8, int blk, const ArgsT &args,
-               hipStream_t st)
+int launch_lds(psg_pn2_ws *ws, int tag, const char *site, KernelT kern, dim3 grid, int threads, int blocks8, int blk,
+               const ArgsT &args, hipStream_t st)
 {
     size_t lds = (size_t)blocks8 * blk * sizeof(float);
     if (lds > 160 * 1024) { set_error("LDS request %zu exceeds 160 KiB", lds); return PSG_ERR_ARG; }
-    if (lds > 48 * 1024) PSG_CHECK_HIP(allow_big_lds((const void *)kern));
-    ProfScope prof(ws, tag, st);
+    if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)kern));
+    EvScope prof(&ws->prof, tag, 0.0, st);
     hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, args);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// (the same, from a launch site of its own: sa1 backward with the colour columns on the vector pipe)
-template <typename KernelT, typename ArgsT>
-int launch_lds_colour(psg_pn2_ws *ws, int tag, KernelT kern, dim3 grid, int threads, int blocks8, int blk, const ArgsT &args,
-                      hipStream_t st)
-{
-    size_t lds = (size_t)blocks8 * blk * sizeof(float);
-    if (lds > 160 * 1024) { set_error("LDS request %zu exceeds 160 KiB", lds); return PSG_ERR_ARG; }
-    if (lds > 48 * 1024) PSG_CHECK_HIP(allow_big_lds((const void *)kern));
-    ProfScope prof(ws, tag, st);
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, args);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// (the same, from a launch site of its own: the tracer tells the FP-split kernels from the whole ones, tests/test_gpu_alt_paths.py)
-template <typename KernelT, typename ArgsT>
-int launch_lds_fp_split(psg_pn2_ws *ws, int tag, KernelT kern, dim3 grid, int threads, int blocks8, int blk, const ArgsT &args,
-                        hipStream_t st)
-{
-    size_t lds = (size_t)blocks8 * blk * sizeof(float);
-    if (lds > 160 * 1024) { set_error("LDS request %zu exceeds 160 KiB", lds); return PSG_ERR_ARG; }
-    if (lds > 48 * 1024) PSG_CHECK_HIP(allow_big_lds((const void *)kern));
-    ProfScope prof(ws, tag, st);
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, args);
-    PSG_LAUNCH_CHECK();
+    PSG_LAUNCH_CHECK_AT(site);
     return PSG_OK;
 }
 
@@ -478,17 +398,17 @@ int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const
     const int tag = TAG_SA_FWD + lvl;
 #define PSG_SA_FWD_CASE(P_, NW_, KS_, MT_) \
     case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
-        return launch_lds(ws, tag, sa_fwd_kernel<P_, NW_, KS_, MT_>, grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
+        return launch_lds(ws, tag, PSG_SITE, sa_fwd_kernel<P_, NW_, KS_, MT_>, grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
     if (split) {
         switch (PSG_CFG_KEY(P, NW, KS, d.maxt_f)) {
-        case PSG_CFG_KEY(128, 4, 32, 1): return launch_lds(ws, tag, (sa_fwd_kernel<128, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<128>::BLK, a, st);
-        case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, (sa_fwd_kernel<64, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);
-        case PSG_CFG_KEY(32, 4, 32, 1): return launch_lds(ws, tag, (sa_fwd_kernel<32, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<32>::BLK, a, st);
-        case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, (sa_fwd_kernel<32, 8, 32, 1, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);
-        case PSG_CFG_KEY(64, 4, 16, 1): return launch_lds(ws, tag, (sa_fwd_kernel<64, 4, 16, 1, true>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);   // MSG sa2 scale 0
-        case PSG_CFG_KEY(64, 8, 32, 1): return launch_lds(ws, tag, (sa_fwd_kernel<64, 8, 32, 1, true>), grid, 8 * 64, blocks, Lds<64>::BLK, a, st);   // MSG sa2 scale 1
-        case PSG_CFG_KEY(32, 8, 16, 1): return launch_lds(ws, tag, (sa_fwd_kernel<32, 8, 16, 1, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // MSG sa3 / sa4 scale 0
-        case PSG_CFG_KEY(32, 8, 32, 2): return launch_lds(ws, tag, (sa_fwd_kernel<32, 8, 32, 2, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // MSG sa4 scale 1
+        case PSG_CFG_KEY(128, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<128, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<128>::BLK, a, st);
+        case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<64, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);
+        case PSG_CFG_KEY(32, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<32>::BLK, a, st);
+        case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 8, 32, 1, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);
+        case PSG_CFG_KEY(64, 4, 16, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<64, 4, 16, 1, true>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);   // MSG sa2 scale 0
+        case PSG_CFG_KEY(64, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<64, 8, 32, 1, true>), grid, 8 * 64, blocks, Lds<64>::BLK, a, st);   // MSG sa2 scale 1
+        case PSG_CFG_KEY(32, 8, 16, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 8, 16, 1, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // MSG sa3 / sa4 scale 0
+        case PSG_CFG_KEY(32, 8, 32, 2): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 8, 32, 2, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // MSG sa4 scale 1
         }
         set_error("run_sa_fwd: no split kernel for P=%d NW=%d K=%d MAXT=%d", P, NW, KS, d.maxt_f);
         return PSG_ERR_STATE;
@@ -592,13 +512,13 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     const int tag = TAG_SA_BWD + lvl;
 #define PSG_SA_BWD_CASE(P_, NW_, KS_, MT_) \
     case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
-        if (a.w1c) return launch_lds_colour(ws, tag, (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st); \
-        return launch_lds(ws, tag, (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
+        if (a.w1c) return launch_lds(ws, tag, PSG_SITE "#colour", (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st); \
+        return launch_lds(ws, tag, PSG_SITE, (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
     if (spv) {
         switch (PSG_CFG_KEY(P, NW, KS, d.maxt_b) * 8 + spv) {
-        case PSG_CFG_KEY(64, 4, 32, 2) * 8 + 1: return launch_lds(ws, tag, (sa_bwd_sparse_kernel<64, 4, 2, 1>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);   // SSG sa2
-        case PSG_CFG_KEY(32, 4, 32, 2) * 8 + 2: return launch_lds(ws, tag, (sa_bwd_sparse_kernel<32, 4, 2, 2>), grid, 4 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa3
-        case PSG_CFG_KEY(32, 8, 32, 2) * 8 + 4: return launch_lds(ws, tag, (sa_bwd_sparse_kernel<32, 8, 2, 4>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa4
+        case PSG_CFG_KEY(64, 4, 32, 2) * 8 + 1: return launch_lds(ws, tag, PSG_SITE, (sa_bwd_sparse_kernel<64, 4, 2, 1>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);   // SSG sa2
+        case PSG_CFG_KEY(32, 4, 32, 2) * 8 + 2: return launch_lds(ws, tag, PSG_SITE, (sa_bwd_sparse_kernel<32, 4, 2, 2>), grid, 4 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa3
+        case PSG_CFG_KEY(32, 8, 32, 2) * 8 + 4: return launch_lds(ws, tag, PSG_SITE, (sa_bwd_sparse_kernel<32, 8, 2, 4>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa4
         }
         set_error("run_sa_bwd: no sparse kernel for P=%d NW=%d MAXT=%d C2=%d", P, NW, d.maxt_b, C2);
         return PSG_ERR_STATE;
@@ -671,7 +591,7 @@ int run_pw_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
     const PackedLayer &F = m->sf[lvl][sc];
     const int B = ws->B, N = ws->Nl[lvl];
     if (lvl == 0) {
-        ProfScope prof(ws, TAG_PW_FWD, st);
+        EvScope prof(&ws->prof, TAG_PW_FWD, 0.0, st);
         const size_t rows = (size_t)B * N;
         hipLaunchKernelGGL(pw9_fwd_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, ws->x0_fwd, m->w0f, m->b0f, rows, ws->tfeat[0][0]);
         PSG_LAUNCH_CHECK();
@@ -691,7 +611,7 @@ int run_pw_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
     a.diag = 0; a.dbg = ws->dbg;
     if (a.layer[0].mb > NW || N % P) { set_error("run_pw_fwd level %d: unsupported shape", lvl); return PSG_ERR_STATE; }
     const int blocks = layer_blocks(a.layer[0].k8, a.layer[0].mb) + PSG_LDS_SPARE;
-    return launch_lds(ws, TAG_PW_FWD, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
+    return launch_lds(ws, TAG_PW_FWD, PSG_SITE, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
 }
 
 // dsum[lvl - 1] = dact[lvl - 1] (skip-link rows of the coarser FP module; level 3 feeds fp4 only: its skip part is that gather,
@@ -716,17 +636,9 @@ int run_pw_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
         return PSG_ERR_STATE;
     }
     const int blocks = layer_blocks(a.wt.k8, a.wt.mb) + PSG_LDS_SPARE;
-    const size_t lds = (size_t)blocks * Lds<P>::BLK * sizeof(float);
-    ProfScope prof(ws, TAG_PW_BWD, st);
-    if (a.wt.mb > NW) {     // MSG level 3: 512 feature channels = 16 output tiles on 8 waves
-        if (lds > 48 * 1024) PSG_CHECK_HIP(allow_big_lds((const void *)pw_bwd_kernel<P, NW, 2>));
-        hipLaunchKernelGGL((pw_bwd_kernel<P, NW, 2>), dim3(N / P, B), dim3(NW * 64), lds, st, a);
-    } else {
-        if (lds > 48 * 1024) PSG_CHECK_HIP(allow_big_lds((const void *)pw_bwd_kernel<P, NW, 1>));
-        hipLaunchKernelGGL((pw_bwd_kernel<P, NW, 1>), dim3(N / P, B), dim3(NW * 64), lds, st, a);
-    }
-    PSG_LAUNCH_CHECK();      // (a launch site of its own: the tracer tells the split path from the whole one, tests/test_gpu_alt_paths.py)
-    return PSG_OK;
+    if (a.wt.mb > NW)       // MSG level 3: 512 feature channels = 16 output tiles on 8 waves
+        return launch_lds(ws, TAG_PW_BWD, PSG_SITE, (pw_bwd_kernel<P, NW, 2>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
+    return launch_lds(ws, TAG_PW_BWD, PSG_SITE, (pw_bwd_kernel<P, NW, 1>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
 }
 
 template <int LVL, int P>
@@ -752,7 +664,7 @@ int run_fp_fwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStre
         }
         w.head = fwd_layer(m->L[head + 1], false, nullptr);
         w.N = N; w.S = S; w.n_cls = NCLS;
-        ProfScope prof(ws, TAG_FP_FWD + 0, st);
+        EvScope prof(&ws->prof, TAG_FP_FWD + 0, 0.0, st);
         hipLaunchKernelGGL(fp1_fwd_wave_kernel, dim3(N / 32, B), dim3(64), (size_t)16 * WBLK * sizeof(float), st, w);
         PSG_LAUNCH_CHECK();
         return PSG_OK;
@@ -821,10 +733,10 @@ int run_fp_fwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStre
     blocks += PSG_LDS_SPARE;
     if constexpr (LVL == 3) if (big) {
         if (a.C1 % 4 || a.C2 % 4 || (a.C1 % 512) || !a.feat1) { set_error("run_fp_fwd: streamed fp4 wants C1 a multiple of 512"); return PSG_ERR_STATE; }
-        return launch_lds(ws, TAG_FP_FWD + LVL, (fp_fwd_kernel<P, NW, true>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
+        return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, true>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
     }
-    if (a.tsrc) return launch_lds_fp_split(ws, TAG_FP_FWD + LVL, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
-    return launch_lds(ws, TAG_FP_FWD + LVL, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
+    if (a.tsrc) return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
+    return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
 }
 
 template <int LVL, int P>
@@ -845,7 +757,7 @@ int run_fp_bwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, c
         }
         w.dint_out = ws->dint[0];
         w.N = N; w.n_cls = NCLS;
-        ProfScope prof(ws, TAG_FP_BWD + 0, st);
+        EvScope prof(&ws->prof, TAG_FP_BWD + 0, 0.0, st);
         hipLaunchKernelGGL(fp1_bwd_wave_kernel, dim3(N / 32, B), dim3(64), (size_t)16 * WBLK * sizeof(float), st, w);
         PSG_LAUNCH_CHECK();
         return PSG_OK;
@@ -917,18 +829,18 @@ int run_fp_bwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, c
     }
     blocks += PSG_LDS_SPARE;
     const dim3 grid(N / P, B);
-    if constexpr (LVL == 3) if (big) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 1, true>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+    if constexpr (LVL == 3) if (big) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 1, true>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
     // (fp1 + head: 128-wide layers on 4 waves, one tile per wave at 32 points, one pair at 64; the 8-wave modules have
     // ragged layers)
     if constexpr (P == 64) {
         // (fp1 + head at 64 points: two tiles = one pair per wave)
-        if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+        if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
     } else {
-        if (maxt == 1) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 1, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+        if (maxt == 1) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 1, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
     }
     if constexpr (LVL > 0 && P == 32) {
-        if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
-        if (maxt == 3) return launch_lds(ws, TAG_FP_BWD + LVL, (fp_bwd_kernel<P, NW, 3, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+        if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+        if (maxt == 3) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 3, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
     }
     set_error("run_fp_bwd<%d>: no kernel for MAXT=%d", LVL, maxt);
     return PSG_ERR_STATE;
@@ -1297,7 +1209,7 @@ extern "C" int psg_pn2_model_create_arch(psg_ctx *ctx, int arch, const float *co
         bs[i].assign((size_t)ceil_div(cout, 32) * 32, 0.0f);
         std::copy(biases[i], biases[i] + cout, bs[i].begin());
         if ((i >= fp1 && i < fp1 + 3) || i >= A.head) {   // fp1 + head run as wave-private chains: k8-major packings of the 128-wide sides
-            if (cout == 128) wf4[i] = k8_major(wf[i], 4, ceil_div(cin, 8));
+            if (cout == 128) wf4[i] = k8_major_padded(wf[i], 4, ceil_div(cin, 8), ceil_div(cin, 8));
             wb4[i] = k8_major_padded(wb[i], 4, ceil_div(cout, 8), round_up(ceil_div(cout, 8), 4));
         }
         total += ((wf[i].size() + wb[i].size() + bs[i].size() + wf4[i].size() + wb4[i].size()) * 4 + 6 * 256);
@@ -1484,7 +1396,7 @@ extern "C" int psg_pn2_ws_destroy(psg_pn2_ws *ws)
     for (hipEvent_t e : ws->nb_ev) if (e) (void)hipEventDestroy(e);
     if (ws->nb_stream) (void)hipStreamDestroy(ws->nb_stream);
     if (ws->arena) (void)hipFree(ws->arena);
-    for (hipEvent_t e : ws->prof_ev) (void)hipEventDestroy(e);
+    ws->prof.destroy();
     delete ws;
     return PSG_OK;
 }
@@ -1502,23 +1414,14 @@ extern "C" int psg_pn2_debug_read(psg_pn2_ws *ws, unsigned long long *host_out, 
 extern "C" int psg_pn2_prof_enable(psg_pn2_ws *ws, int on)
 {
     PSG_REQUIRE(ws, "psg_pn2_prof_enable: null workspace");
-    ws->prof_on = on != 0;
-    ws->prof_used = 0;
-    ws->prof_tag.clear();
+    ws->prof.reset(on != 0);
     return PSG_OK;
 }
 
 extern "C" int psg_pn2_prof_read(psg_pn2_ws *ws, int n_tags, double *total_ms, int *counts)
 {
     PSG_REQUIRE(ws && total_ms && counts && n_tags >= TAG_COUNT, "psg_pn2_prof_read: need room for %d tags", TAG_COUNT);
-    for (int i = 0; i < n_tags; ++i) { total_ms[i] = 0.0; counts[i] = 0; }
-    for (size_t i = 0; i < ws->prof_tag.size(); ++i) {
-        float ms = 0.f;
-        PSG_CHECK_HIP(hipEventSynchronize(ws->prof_ev[2 * i + 1]));
-        PSG_CHECK_HIP(hipEventElapsedTime(&ms, ws->prof_ev[2 * i], ws->prof_ev[2 * i + 1]));
-        total_ms[ws->prof_tag[i]] += ms;
-        counts[ws->prof_tag[i]] += 1;
-    }
+    if (ws->prof.read(n_tags, total_ms, counts, nullptr)) { set_error("psg_pn2_prof_read: event query failed"); return PSG_ERR_HIP; }
     return PSG_OK;
 }
 
@@ -1543,33 +1446,33 @@ extern "C" int psg_pn2_plan_build(psg_pn2_ws *ws, const float *x0, const int32_t
         hipLaunchKernelGGL(gather_starts_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, starts, start_l, l, B, P);
         PSG_LAUNCH_CHECK();
         {
-            ProfScope prof(ws, TAG_FPS, st);
+            EvScope prof(&ws->prof, TAG_FPS, 0.0, st);
             if ((rc = psg_fps(ws->ctx, ws->xyz[l], n_clouds, P, Np, S, start_l, ws->fps[l], st))) return rc;
         }
         {
-            ProfScope prof(ws, TAG_GATHER, st);
+            EvScope prof(&ws->prof, TAG_GATHER, 0.0, st);
             if ((rc = psg_gather_points(ws->ctx, ws->xyz[l], n_clouds, P, Np, 3, ws->fps[l], S, ws->xyz[l + 1], st)))
                 return rc;
         }
         for (int sc = 0; sc < ws->arch->ns; ++sc) {
             const ScaleDesc &d = ws->arch->sc[l][sc];
-            ProfScope prof(ws, TAG_BALL, st);
+            EvScope prof(&ws->prof, TAG_BALL, 0.0, st);
             if ((rc = psg_ball_query(ws->ctx, ws->xyz[l], n_clouds, ws->xyz[l + 1], P, Np, S, d.r2, d.K,
                                      ws->gidx[l][sc], st)))
                 return rc;
             const size_t inv_lds = (size_t)(Np + 1) * 4 + (size_t)S * d.K * 2;
-            if (inv_lds > 48 * 1024) PSG_CHECK_HIP(allow_big_lds((const void *)build_inv_group_kernel));
+            if (inv_lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)build_inv_group_kernel));
             hipLaunchKernelGGL(build_inv_group_kernel, dim3(P), dim3(INV_NT), inv_lds, st, ws->gidx[l][sc], S * d.K, Np, d.K,
                                ws->ginv_off[l][sc], ws->ginv_pos[l][sc]);
             PSG_LAUNCH_CHECK();
         }
         {
-            ProfScope prof(ws, TAG_NN, st);
+            EvScope prof(&ws->prof, TAG_NN, 0.0, st);
             if ((rc = psg_three_nn(ws->ctx, ws->xyz[l], n_clouds, ws->xyz[l + 1], P, Np, S, ws->nn_idx[l], ws->nn_w[l],
                                    st)))
                 return rc;
             const size_t nn_lds = (size_t)(S + 1) * 4 + (size_t)3 * Np * 6;
-            if (nn_lds > 48 * 1024) PSG_CHECK_HIP(allow_big_lds((const void *)build_inv_nn_kernel));
+            if (nn_lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)build_inv_nn_kernel));
             hipLaunchKernelGGL(build_inv_nn_kernel, dim3(P), dim3(INV_NT), nn_lds, st, ws->nn_idx[l], ws->nn_w[l],
                                Np, S, ws->inv_off[l], ws->inv_ent[l]);
             PSG_LAUNCH_CHECK();
@@ -1652,7 +1555,7 @@ static int backward_impl(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float 
         }
     }
     {
-        ProfScope prof(ws, TAG_ZERO, st);   // (tag kept: the slot that used to be the gradient memset)
+        EvScope prof(&ws->prof, TAG_ZERO, 0.0, st);   // (tag kept: the slot that used to be the gradient memset)
         const bool compact = c_hi - c_lo == 3;
         const size_t total = (size_t)ws->B * ws->N * (compact ? 1 : c_hi - c_lo);
         const dim3 grid((unsigned)std::min<size_t>(8192, (total + 255) / 256));
@@ -1674,15 +1577,23 @@ static int backward_impl(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float 
     return PSG_OK;
 }
 
+// What every backward entry point `who` asks of its (non-null) handles: one architecture, and forward `fwd` is the one whose
+// activations, masks and log-probs the workspace holds.
+static int require_resident(const psg_pn2_model *m, const psg_pn2_ws *ws, int fwd, const char *who)
+{
+    PSG_REQUIRE(m->arch == ws->arch, "%s: model and workspace were created for different architectures", who);
+    if (ws->fwd_slot != fwd) {
+        set_error("%s: forward %d is not the one resident in the workspace (%d)", who, fwd, ws->fwd_slot);
+        return PSG_ERR_STATE;
+    }
+    return PSG_OK;
+}
+
 extern "C" int psg_pn2_backward(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *dlogp, float *dx0_out,
                                 psg_stream stream)
 {
     PSG_REQUIRE(m && ws && dlogp && dx0_out, "psg_pn2_backward: null argument");
-    PSG_REQUIRE(m->arch == ws->arch, "psg_pn2_backward: model and workspace were created for different architectures");
-    if (ws->fwd_slot != fwd) {
-        set_error("psg_pn2_backward: forward %d is not the one resident in the workspace (%d)", fwd, ws->fwd_slot);
-        return PSG_ERR_STATE;
-    }
+    if (int rc = require_resident(m, ws, fwd, "psg_pn2_backward")) return rc;
     // the log_softmax backward reads the log-probs of the resident forward, kept in ws->logp
     return backward_impl(m, ws, fwd, ws->logp, dlogp, dx0_out, 0, 9, (hipStream_t)stream);
 }
@@ -1699,7 +1610,7 @@ static int geometry_grad(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *dx0, 
     const int ld0 = gsa_stride(A, 0), rel0_col = A.C[0];
     for (int l = 1; l < 4; ++l) {   // g_rel rows of the split levels
         const int C1 = A.cout[A.sc[l][0].l0], g_rows = kS[l] * A.sc[l][0].K;
-        ProfScope prof(ws, TAG_GEOM_GREL, st);
+        EvScope prof(&ws->prof, TAG_GEOM_GREL, 0.0, st);
         hipLaunchKernelGGL(sa_grel_kernel, dim3(std::min(256, ceil_div(g_rows, GG_NT / GG_LANES)), B), dim3(GG_NT),
                            (size_t)3 * C1 * sizeof(float), st, ws->gsa[l][0], ws->ginv_off[l][0] + prob * (ws->Nl[l] + 1), ws->Nl[l],
                            g_rows, m->w1x[l], C1, ws->grel[l]);
@@ -1709,7 +1620,7 @@ static int geometry_grad(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *dx0, 
         const bool fs = l < 3 && m->fsplit[l];
         const int C = fs ? A.cout[A.fp_first[l]] : A.cin[A.fp_first[l]] - (l == 0 ? 0 : A.C[l]);
         const float *src = fs ? ws->tfp[l] : ws->act[fp_in2_slot(l)];
-        ProfScope prof(ws, TAG_GEOM_WGRAD, st);
+        EvScope prof(&ws->prof, TAG_GEOM_WGRAD, 0.0, st);
         hipLaunchKernelGGL(fp_wgrad_kernel, dim3(std::min(512, ceil_div(ws->Nl[l], GG_NT / GG_LANES)), B), dim3(GG_NT), 0, st,
                            ws->dint[l], src, C, ws->nn_idx[l] + prob * ws->Nl[l] * 3, xyz_of(l), xyz_of(l + 1), ws->Nl[l],
                            ws->Nl[l + 1], ws->fpg[l]);
@@ -1747,7 +1658,7 @@ static int geometry_grad(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *dx0, 
         a.out = L == 0 ? dx0 : ws->gxyz[L];
         a.out_ld = L == 0 ? 9 : 3;
         a.accumulate = L == 0 ? 1 : 0;
-        ProfScope prof(ws, TAG_GEOM_GX, st);   // (with the level's gx_fps_down_kernel)
+        EvScope prof(&ws->prof, TAG_GEOM_GX, 0.0, st);   // (with the level's gx_fps_down_kernel)
         hipLaunchKernelGGL(gx_level_kernel, dim3(std::min(2048, ceil_div(B * n, GG_NT))), dim3(GG_NT), 0, st, a, B);
         PSG_LAUNCH_CHECK();
         if (L <= 3) {
@@ -1763,7 +1674,6 @@ extern "C" int psg_pn2_backward_full(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, 
                                      psg_stream stream)
 {
     PSG_REQUIRE(m && ws && dlogp && dx0_out, "psg_pn2_backward_full: null argument");
-    PSG_REQUIRE(m->arch == ws->arch, "psg_pn2_backward_full: model and workspace were created for different architectures");
     PSG_REQUIRE(m->arch->id == PSG_PN2_ARCH_SSG, "psg_pn2_backward_full: the coordinate gradient is implemented for the SSG "
                 "network only (MSG: use psg_pn2_backward, whose channels 0:3 exclude the geometric paths)");
     PSG_REQUIRE(m->split[1] && m->split[2] && m->split[3] && m->w1x[1] && m->w1x[2] && m->w1x[3],
@@ -1771,10 +1681,7 @@ extern "C" int psg_pn2_backward_full(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, 
     PSG_REQUIRE(ws->grel[1] && arch_split(*ws->arch, 1), "psg_pn2_backward_full: workspace created under PSG_PN2_SPLIT=0");
     PSG_REQUIRE(!m->split[0] && gsa_stride(*m->arch, 0) == m->arch->C[0] + 3,
                 "psg_pn2_backward_full: level 0's rows are expected whole, [feats, rel_xyz]");
-    if (ws->fwd_slot != fwd) {
-        set_error("psg_pn2_backward_full: forward %d is not the one resident in the workspace (%d)", fwd, ws->fwd_slot);
-        return PSG_ERR_STATE;
-    }
+    if (int rc = require_resident(m, ws, fwd, "psg_pn2_backward_full")) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = backward_impl(m, ws, fwd, ws->logp, dlogp, dx0_out, 0, 9, st, nullptr, true)) return rc;
     return geometry_grad(m, ws, fwd, dx0_out, st);
@@ -1796,11 +1703,7 @@ int pn2_forward_lean(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *x0,
 int pn2_backward_colour(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *dlogp, float *dx0_out, psg_stream stream)
 {
     PSG_REQUIRE(m && ws && dlogp && dx0_out, "pn2_backward_colour: null argument");
-    PSG_REQUIRE(m->arch == ws->arch, "pn2_backward_colour: model and workspace were created for different architectures");
-    if (ws->fwd_slot != fwd) {
-        set_error("pn2_backward_colour: forward %d is not the one resident in the workspace (%d)", fwd, ws->fwd_slot);
-        return PSG_ERR_STATE;
-    }
+    if (int rc = require_resident(m, ws, fwd, "pn2_backward_colour")) return rc;
     return backward_impl(m, ws, fwd, ws->logp, dlogp, dx0_out, 3, 6, (hipStream_t)stream);
 }
 }  // namespace psg
@@ -1820,12 +1723,8 @@ extern "C" int psg_pn2_backward_colour_pgd(psg_pn2_model *m, psg_pn2_ws *ws, int
                                            const uint8_t *mask, float alpha, float eps, float dir, int last, psg_stream stream)
 {
     PSG_REQUIRE(m && ws && dlogp && x && ori, "psg_pn2_backward_colour_pgd: null argument");
-    PSG_REQUIRE(m->arch == ws->arch, "psg_pn2_backward_colour_pgd: model and workspace were created for different architectures");
     PSG_REQUIRE(dir == 1.0f || dir == -1.0f, "psg_pn2_backward_colour_pgd: dir must be +1 or -1");
-    if (ws->fwd_slot != fwd) {
-        set_error("psg_pn2_backward_colour_pgd: forward %d is not the one resident in the workspace (%d)", fwd, ws->fwd_slot);
-        return PSG_ERR_STATE;
-    }
+    if (int rc = require_resident(m, ws, fwd, "psg_pn2_backward_colour_pgd")) return rc;
     const PgdFuse pf{x, ori, mask, dir * alpha, eps, last ? 1 : 0};
     return backward_impl(m, ws, fwd, ws->logp, dlogp, ws->dx0, 3, 6, (hipStream_t)stream, &pf);
 }
@@ -1858,13 +1757,10 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
         if ((r = psg_pn2_plan_build(ws, ws->x0, ws->nb_starts, iters, st))) return r;
         const int rows = B * N;
         for (int it = 0; it < iters; ++it) {
-            ws->lean = true;
-            r = psg_pn2_forward(m, ws, it, ws->x0, ws->logp, nullptr, st);
-            ws->lean = false;
-            if (r) return r;
+            if ((r = psg::pn2_forward_lean(m, ws, it, ws->x0, ws->logp, st))) return r;
             // non-targeted: CE_sum over all rooms / N (nontarget.py:34); targeted: CE_mean of room 0 (target.py:36-39)
             {
-                ProfScope prof(ws, TAG_CE, st);
+                EvScope prof(&ws->prof, TAG_CE, 0.0, st);
                 if ((r = psg_ce_logp_grad(ws->logp, labels_ws, target, rows, targeted ? N : rows, NCLS, 1.0f / (float)N, ws->dlogp,
                                           nullptr, st)))
                     return r;
@@ -1876,7 +1772,7 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
                 if ((r = backward_impl(m, ws, it, ws->logp, ws->dlogp, ws->dx0, 3, 6, st, &pf))) return r;
             } else {
                 if ((r = backward_impl(m, ws, it, ws->logp, ws->dlogp, ws->dx0, 3, 6, st))) return r;
-                ProfScope prof(ws, TAG_PGD, st);
+                EvScope prof(&ws->prof, TAG_PGD, 0.0, st);
                 if ((r = psg_pgd_step(ws->x0, ws->dx0, ws->ori, mask_ws, B, N, alpha, eps, targeted ? -1.0f : 1.0f, it == iters - 1, st)))
                     return r;
             }
@@ -1893,7 +1789,7 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
     // interleave, while the eager launches were never launch-bound here (a launch is 20 - 50 us of GPU work against ~5 us
     // of host time; the graphs of the ResGCN / RandLA-Net / NU loops replace one-room launches of 5 - 15 us: +23 .. +60 %).
     static const bool use_graph = psg::env_int("PSG_PN2_GRAPH", 0) != 0 && !psg::trace_sync_enabled();
-    if (use_graph && B <= 16 && !ws->prof_on) {
+    if (use_graph && B <= 16 && !ws->prof.on) {
         const psg_pn2_ws::NbKey key{m->gen, eps, alpha, iters, targeted ? 1 : 0, targeted ? target : 0, mask ? 1 : 0, targeted ? 0 : 1, 0};
         const bool same = ws->nb_have_key && memcmp(&key, &ws->nb_key, sizeof(key)) == 0;
         if (same && !ws->nb.capture_failed) {

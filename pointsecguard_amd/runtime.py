@@ -69,24 +69,46 @@ def _hip_memcpy_d2d(dst_ptr, src_ptr, nbytes):
         raise _lib.PsgError("hipMemcpyAsync failed with %d" % rc)
 
 
+class _Handle:
+    """Owner of one libpsg handle: `handle` is filled in by the subclass's create call and given to the library's
+    `_destroy` symbol when the object goes."""
+    _destroy = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                getattr(_lib.load(), self._destroy)(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def _as_ndarray(v):
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v
+
+
+def _as_f64(sd, key):
+    return np.asarray(_as_ndarray(sd[key]), np.float64)
+
+
+def _fold_conv_bn(sd, conv, bn, eps):
+    """Eval-mode BatchNorm `bn` (or None) folded into the conv / linear layer `conv` before it: fp64 (w [out][in], b [out])."""
+    w = _as_f64(sd, conv + ".weight")
+    w = w.reshape(w.shape[0], -1)
+    b = _as_f64(sd, conv + ".bias")
+    if bn is not None:
+        s = _as_f64(sd, bn + ".weight") / np.sqrt(_as_f64(sd, bn + ".running_var") + eps)
+        w = w * s[:, None]
+        b = (b - _as_f64(sd, bn + ".running_mean")) * s + _as_f64(sd, bn + ".bias")
+    return w, b
+
+
 def fold_state_dict(sd, eps=1e-5, msg=False):
     """Eval-mode BatchNorm folded into the preceding 1x1 conv, in the layer order of
     psg_pn2_model_create.  sd: mapping name -> tensor/ndarray with the reference's state_dict keys
     (sa{1-4}.mlp_convs.N.weight ..., fp{1-4}..., conv1, bn1, conv2).  fp64 math, fp32 result."""
-    def arr(k):
-        v = sd[k]
-        if isinstance(v, torch.Tensor):
-            v = v.detach().cpu().numpy()
-        return np.asarray(v, np.float64)
-
     def fold(conv, bn):
-        w = arr(conv + ".weight")
-        w = w.reshape(w.shape[0], -1)
-        b = arr(conv + ".bias")
-        if bn is not None:
-            s = arr(bn + ".weight") / np.sqrt(arr(bn + ".running_var") + eps)
-            w = w * s[:, None]
-            b = (b - arr(bn + ".running_mean")) * s + arr(bn + ".bias")
+        w, b = _fold_conv_bn(sd, conv, bn, eps)
         return np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32)
 
     out = []
@@ -107,8 +129,9 @@ def fold_state_dict(sd, eps=1e-5, msg=False):
     return out
 
 
-class PN2Model:
+class PN2Model(_Handle):
     """Device-resident MFMA-packed weights of get_model (psg_pn2_model)."""
+    _destroy = "psg_pn2_model_destroy"
 
     def __init__(self, folded, device=None, arch=ARCH_SSG):
         n = ARCH_LAYERS[arch]
@@ -124,17 +147,10 @@ class PN2Model:
         _lib.check(lib.psg_pn2_model_create_arch(self.ctx, arch, ws, bs, n, ctypes.byref(self.handle)),
                    "psg_pn2_model_create_arch")
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().psg_pn2_model_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class PN2Workspace:
+class PN2Workspace(_Handle):
     """Geometry plan + activations + gradient buffers for a batch (psg_pn2_ws)."""
+    _destroy = "psg_pn2_ws_destroy"
 
     def __init__(self, batch, n_point, max_forwards, device=None, arch=ARCH_SSG):
         self.ctx = context(device)
@@ -143,14 +159,6 @@ class PN2Workspace:
         _lib.check(_lib.load().psg_pn2_ws_create_arch(self.ctx, arch, batch, n_point, max_forwards,
                                                       ctypes.byref(self.handle)), "psg_pn2_ws_create_arch")
         self.device = torch.device("cuda", torch.cuda.current_device())
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().psg_pn2_ws_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
     @property
     def nbytes(self):
@@ -315,29 +323,18 @@ def fold_pointnet_state_dict(sd, eps=1e-5, dtype=np.float32):
     """Eval-mode BatchNorm folded into the preceding conv / linear layer of pointnet_sem_seg.get_model, and the STN
     identities of pointnet.py:41-47 / 77-83 added to the fc3 biases, in the layer order of psg_pointnet_model_create.
     sd: the reference's state_dict keys.  fp64 math, `dtype` result (fp32 for the device): [(w [out][in], b [out])] * 19."""
-    def arr(k):
-        v = sd[k]
-        if isinstance(v, torch.Tensor):
-            v = v.detach().cpu().numpy()
-        return np.asarray(v, np.float64)
-
     out = []
     for layer, bn, iden in POINTNET_LAYERS:
-        w = arr(layer + ".weight")
-        w = w.reshape(w.shape[0], -1)
-        b = arr(layer + ".bias")
-        if bn is not None:
-            s = arr(bn + ".weight") / np.sqrt(arr(bn + ".running_var") + eps)
-            w = w * s[:, None]
-            b = (b - arr(bn + ".running_mean")) * s + arr(bn + ".bias")
+        w, b = _fold_conv_bn(sd, layer, bn, eps)
         if iden:
             b = b + np.eye(iden).reshape(-1)
         out.append((np.ascontiguousarray(w, dtype), np.ascontiguousarray(b, dtype)))
     return out
 
 
-class PointNetModel:
+class PointNetModel(_Handle):
     """Device-resident BN-folded weights of pointnet_sem_seg.get_model (psg_pointnet_model)."""
+    _destroy = "psg_pointnet_model_destroy"
 
     def __init__(self, folded, device=None):
         n = len(POINTNET_LAYERS)
@@ -351,17 +348,10 @@ class PointNetModel:
         self.handle = ctypes.c_void_p()
         _lib.check(_lib.load().psg_pointnet_model_create(self.ctx, ws, bs, ctypes.byref(self.handle)), "psg_pointnet_model_create")
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().psg_pointnet_model_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class PointNetWorkspace:
+class PointNetWorkspace(_Handle):
     """Activations, ReLU bits, pooled arg-max sets and gradient buffers for (batch, n_point) (psg_pointnet_ws)."""
+    _destroy = "psg_pointnet_ws_destroy"
 
     def __init__(self, batch, n_point, device=None):
         if n_point % POINTNET_POINT_TILE:
@@ -371,14 +361,6 @@ class PointNetWorkspace:
         self.handle = ctypes.c_void_p()
         _lib.check(_lib.load().psg_pointnet_ws_create(self.ctx, batch, n_point, ctypes.byref(self.handle)), "psg_pointnet_ws_create")
         self.device = torch.device("cuda", torch.cuda.current_device())
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().psg_pointnet_ws_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
     def forward(self, model, x0, logp=None, extras=False):
         """x0 [B][N][9] point-major -> logp [B][N][13]; extras=True also returns (trans [B,3,3], trans_feat [B,64,64],
@@ -491,10 +473,7 @@ def gcn_tensor_list(sd, n_blocks):
     """state_dict (reference key names, ResGCN/sem_seg_dense/architecture.py) -> the flat fp32 tensor list of
     psg_gcn_model_create."""
     def a(k):
-        v = sd[k]
-        if isinstance(v, torch.Tensor):
-            v = v.detach().cpu().numpy()
-        v = np.ascontiguousarray(v, np.float32)
+        v = np.ascontiguousarray(_as_ndarray(sd[k]), np.float32)
         return v.reshape(v.shape[0], -1) if v.ndim > 1 else v
 
     out = []
@@ -513,7 +492,9 @@ GCN_BLOCK_RES, GCN_BLOCK_PLAIN, GCN_BLOCK_DENSE = 0, 1, 2   # PSG_GCN_BLOCK_* / 
 GCN_CONV_EDGE, GCN_CONV_MR = 0, 1
 
 
-class GCNModel:
+class GCNModel(_Handle):
+    _destroy = "psg_gcn_model_destroy"
+
     def __init__(self, sd, n_blocks, device=None, block=GCN_BLOCK_RES, conv=GCN_CONV_EDGE):
         self.ctx = context(device)
         self.n_blocks, self.block, self.conv = n_blocks, block, conv
@@ -523,16 +504,10 @@ class GCNModel:
         _lib.check(_lib.load().psg_gcn_model_create_cfg(self.ctx, arr, len(self._keep), n_blocks, block, conv,
                                                         ctypes.byref(self.handle)), "psg_gcn_model_create_cfg")
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().psg_gcn_model_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
+class GCNWorkspace(_Handle):
+    _destroy = "psg_gcn_ws_destroy"
 
-class GCNWorkspace:
     def __init__(self, batch, n_point, n_blocks, device=None, block=GCN_BLOCK_RES, conv=GCN_CONV_EDGE):
         self.ctx = context(device)
         self.batch, self.n_point, self.n_blocks = batch, n_point, n_blocks
@@ -540,14 +515,6 @@ class GCNWorkspace:
         _lib.check(_lib.load().psg_gcn_ws_create_cfg(self.ctx, batch, n_point, n_blocks, block, conv,
                                                      ctypes.byref(self.handle)), "psg_gcn_ws_create_cfg")
         self.device = torch.device("cuda", torch.cuda.current_device())
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().psg_gcn_ws_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
     def knn(self, x, dilation):
         require_cuda(x, "x", torch.float32)

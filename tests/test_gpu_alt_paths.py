@@ -16,8 +16,9 @@
                      inverse-graph gather
 
 The switches are read once per process, so each case runs the relevant parity tests in ONE child interpreter with the
-switch set and the launch tracer on (PSG_TRACE_SYNC=1 prints the source line of every launch; the child runs with -s so
-the library's stderr reaches this process): the child must pass, and
+switch set and the launch tracer on (PSG_TRACE_SYNC=1 prints the site of every launch - the source line where the launch is
+written, or, for a launch helper, its CALLER's line with an optional #variant; the child runs with -s so the library's
+stderr reaches this process): the child must pass, and
 its set of launch sites must differ from the default child's - the switch really selected other kernels."""
 import os
 import re
