@@ -658,6 +658,24 @@ int psg_rla_prof_read_kernels(psg_rla_ws *ws, int n_tags, double *total_ms, int 
 int psg_rla_set_cloud(psg_rla_ws *ws, const float *xyz, psg_stream stream);
 /* what: 0 neighbour idx [n_l][16], 1 up-sampling idx [n_l]; device pointers into the workspace (tests) */
 const int32_t *psg_rla_index_ptr(const psg_rla_ws *ws, int what, int level);
+/* Read-only tap into the workspace (tests): the device pointer of a named buffer with its row and column counts; NULL
+ * with the error string set for an unknown `what` or `level`.  Launches nothing, allocates nothing, does not synchronise.
+ * `level` = encoder level 0..4 for the per-level buffers, decoder layer j = 0..4 for the dec buffers, 0 otherwise.
+ * float32 unless noted; n = rows of the level, d = its d_out, h = d / 2.
+ *   forward state, valid from a forward call until the next backward call (which recycles agg1 / agg2 / fagg2: copy first):
+ *     0 f0 [N][8]  1 dec0 [n5][1024]  2 dec_cat[j]  3 dec_out[j]  4 fc1o [N][64]  5 fc2o [N][32]  6 logits [N][13]
+ *     10 fpc [n][h]  11 agg1 [n][d]  12 fagg1 [n][h]  13 agg2 [n][d]  14 fagg2 [n][d]  15 sc [n][2d]  16 enc [n][2d]
+ *     17 samp [n_sub][2d]  18 arg [n_sub][2d] (bytes)  19 relpos [16n][10]  20 fxyz1 [16n][h]  21 fxyz2 [16n][h]
+ *     leaky-ReLU sign bits, uint32 words, cols = words per row, bit c%32 of word c/32 = (pre-activation > 0):
+ *     30 m_f0  31 m_fpc  32 m_fagg1  33 m_fagg2  34 m_enc  35 m_dec0  36 m_dec[j]  37 m_fc1  38 m_fc2
+ *   gradient state, valid from a backward call until the next forward call:
+ *     40 d_fc2o  41 d_fc1o  42 d_dec_out[j]  43 d_dec0  44 d_samp  45 d_enc  46 d_fagg1  47 d_fpc  51 d_f0
+ *     48 g_fagg2 (lives in agg2)  49 g_agg2 (lives in fagg2)  50 g_agg1 (lives in agg1)
+ *   geometry (int32), valid from the cloud call on, unless the float-atomics switch is set (never built: NULL, error set):
+ *     60 inv_off [n+1]  61 inv_ent [16n]  62 invu_off [n_sub+1]  63 invu_ent [n]  64 invp_off [n+1]  65 invp_ent [16 n_sub]
+ * The per-edge attention buffers (a1 / cat1 / a2 / cat2) change meaning with the path (T and S2 on the split path, scores
+ * and the concatenation on the unfused one, unused on the fused one) and are not exposed. */
+const void *psg_rla_debug_ptr(const psg_rla_ws *ws, int what, int level, int *rows_out, int *cols_out);
 /* features [n_points][6] = (xyz, rgb) -> logits [n_points][13] */
 int psg_rla_forward(psg_rla_model *model, psg_rla_ws *ws, const float *features, float *logits_out, psg_stream stream);
 /* d loss / d logits -> d loss / d features [n_points][6] (through the feature path only: the relative-position branch

@@ -135,6 +135,7 @@ SIGNATURES = {
     "psg_rla_prof_read_kernels": (ci, [vp, ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "psg_rla_set_cloud": (ci, [vp, vp, vp]),
     "psg_rla_index_ptr": (vp, [vp, ci, ci]),
+    "psg_rla_debug_ptr": (vp, [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "psg_rla_forward": (ci, [vp, vp, vp, vp, vp]),
     "psg_rla_backward": (ci, [vp, vp, vp, vp, vp]),
     "psg_rla_colper_grad": (ci, [vp, vp, ci, vp, vp, vp]),

@@ -1421,6 +1421,83 @@ extern "C" const int32_t *psg_rla_index_ptr(const psg_rla_ws *ws, int what, int 
     return what == 0 ? ws->lv[level].neigh : (what == 1 ? ws->lv[level].up : nullptr);
 }
 
+// Read-only tap into the workspace (include/psg.h lists the codes and the two validity windows): a pointer, a row count
+// and a column count; no launch, no allocation, no synchronisation.
+extern "C" const void *psg_rla_debug_ptr(const psg_rla_ws *ws, int what, int level, int *rows_out, int *cols_out)
+{
+    if (!ws) { set_error("psg_rla_debug_ptr: null workspace"); return nullptr; }
+    const bool per_dec = what == 2 || what == 3 || what == 36 || what == 42;
+    const bool per_level = (what >= 10 && what <= 21) || (what >= 31 && what <= 34) || (what >= 44 && what <= 50) || what >= 60;
+    if (level < 0 || level >= RL || (!per_dec && !per_level && level != 0)) {
+        set_error("psg_rla_debug_ptr: level=%d out of range for what=%d", level, what);
+        return nullptr;
+    }
+    if (what >= 60 && what <= 65 && !ws->use_inv) {
+        set_error("psg_rla_debug_ptr: the inverse lists (what=%d) are not built under PSG_RLA_ATOMICS", what);
+        return nullptr;
+    }
+    const LevelBuf &L = ws->lv[level];
+    const LevelBuf &D = ws->lv[RL - 1 - level];          // decoder layer j = level works on level RL-1-j's rows
+    const int skip = level == RL - 1 ? 2 * kDout[0] : 2 * kDout[RL - 2 - level];
+    const int feat = level == 0 ? 1024 : 2 * kDout[RL - 1 - level];   // decoder j's coarse input width
+    const int N = ws->N, n5 = ws->lv[RL - 1].n_sub, n = L.n, d = L.d, h = L.h, E = L.n * RK;
+    const void *p = nullptr;
+    int r = 0, c = 0;
+    auto put = [&](const void *ptr, int rows, int cols) { p = ptr; r = rows; c = cols; };
+    switch (what) {
+    case 0: put(ws->f0, N, 8); break;
+    case 1: put(ws->dec0, n5, 1024); break;
+    case 2: put(ws->dec_cat[level], D.n, skip + feat); break;
+    case 3: put(ws->dec_out[level], D.n, skip); break;
+    case 4: put(ws->fc1o, N, 64); break;
+    case 5: put(ws->fc2o, N, 32); break;
+    case 6: put(ws->logits, N, RNCLS); break;
+    case 10: put(L.fpc, n, h); break;
+    case 11: put(L.agg1, n, d); break;
+    case 12: put(L.fagg1, n, h); break;
+    case 13: put(L.agg2, n, d); break;
+    case 14: put(L.fagg2, n, d); break;
+    case 15: put(L.sc, n, 2 * d); break;
+    case 16: put(L.enc, n, 2 * d); break;
+    case 17: put(L.samp, L.n_sub, 2 * d); break;
+    case 18: put(L.arg, L.n_sub, 2 * d); break;                       // bytes
+    case 19: put(L.relpos, E, 10); break;
+    case 20: put(L.fxyz1, E, h); break;
+    case 21: put(L.fxyz2, E, h); break;
+    case 30: put(ws->m_f0, N, 1); break;                              // mask words: cols = 32-bit words per row
+    case 31: put(L.m_fpc, n, ceil_div(h, 32)); break;
+    case 32: put(L.m_fagg1, n, ceil_div(h, 32)); break;
+    case 33: put(L.m_fagg2, n, ceil_div(d, 32)); break;
+    case 34: put(L.m_enc, n, 2 * d / 32); break;
+    case 35: put(ws->m_dec0, n5, 32); break;
+    case 36: put(ws->m_dec[level], D.n, ceil_div(skip, 32)); break;
+    case 37: put(ws->m_fc1, N, 2); break;
+    case 38: put(ws->m_fc2, N, 1); break;
+    case 40: put(ws->d_fc2o, N, 32); break;
+    case 41: put(ws->d_fc1o, N, 64); break;
+    case 42: put(ws->d_dec_out[level], D.n, skip); break;
+    case 43: put(ws->d_dec0, n5, 1024); break;
+    case 44: put(L.d_samp, L.n_sub, 2 * d); break;
+    case 45: put(L.d_enc, n, 2 * d); break;
+    case 46: put(L.d_fagg1, n, h); break;
+    case 47: put(L.d_fpc, n, h); break;
+    case 48: put(L.agg2, n, d); break;                                // g_fagg2
+    case 49: put(L.fagg2, n, d); break;                               // g_agg2
+    case 50: put(L.agg1, n, d); break;                                // g_agg1
+    case 51: put(ws->d_f0, N, 8); break;
+    case 60: put(L.inv_off, n + 1, 1); break;
+    case 61: put(L.inv_ent, E, 1); break;
+    case 62: put(L.invu_off, L.n_sub + 1, 1); break;
+    case 63: put(L.invu_ent, n, 1); break;
+    case 64: put(L.invp_off, n + 1, 1); break;
+    case 65: put(L.invp_ent, L.n_sub * RK, 1); break;
+    default: set_error("psg_rla_debug_ptr: unknown buffer code what=%d", what); return nullptr;
+    }
+    if (rows_out) *rows_out = r;
+    if (cols_out) *cols_out = c;
+    return p;
+}
+
 extern "C" int psg_rla_forward(psg_rla_model *m, psg_rla_ws *ws, const float *features, float *logits_out, psg_stream stream)
 {
     ProfBind bind(ws);

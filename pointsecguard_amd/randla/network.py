@@ -109,6 +109,28 @@ class RandLAWorkspace:
         runtime._hip_memcpy_d2d(out.data_ptr(), src, out.numel() * 4)
         return out
 
+    # psg_rla_debug_ptr codes (include/psg.h): name -> (code, element type)
+    DEBUG = {"f0": 0, "dec0": 1, "dec_cat": 2, "dec_out": 3, "fc1o": 4, "fc2o": 5, "logits": 6,
+             "fpc": 10, "agg1": 11, "fagg1": 12, "agg2": 13, "fagg2": 14, "sc": 15, "enc": 16, "samp": 17, "arg": 18,
+             "relpos": 19, "fxyz1": 20, "fxyz2": 21,
+             "m_f0": 30, "m_fpc": 31, "m_fagg1": 32, "m_fagg2": 33, "m_enc": 34, "m_dec0": 35, "m_dec": 36, "m_fc1": 37, "m_fc2": 38,
+             "d_fc2o": 40, "d_fc1o": 41, "d_dec_out": 42, "d_dec0": 43, "d_samp": 44, "d_enc": 45, "d_fagg1": 46, "d_fpc": 47,
+             "g_fagg2": 48, "g_agg2": 49, "g_agg1": 50, "d_f0": 51,
+             "inv_off": 60, "inv_ent": 61, "invu_off": 62, "invu_ent": 63, "invp_off": 64, "invp_ent": 65}
+
+    def debug(self, what, level=0):
+        """A workspace buffer by name (tests): a [rows, cols] copy taken on the current stream, float32 except `arg`
+        (uint8), the m_* sign-bit words and the inverse lists (int32).  Forward buffers are valid until backward()."""
+        code = self.DEBUG[what]
+        rows, cols = ctypes.c_int(), ctypes.c_int()
+        src = _lib.load().psg_rla_debug_ptr(self.handle, code, level, ctypes.byref(rows), ctypes.byref(cols))
+        if not src:
+            raise _lib.PsgError("psg_rla_debug_ptr(%s, %d): %s" % (what, level, _lib.load().psg_last_error().decode()))
+        dtype = torch.uint8 if what == "arg" else (torch.int32 if code >= 30 and code < 40 or code >= 60 else torch.float32)
+        out = torch.empty(rows.value, cols.value, dtype=dtype, device=self.device)
+        runtime._hip_memcpy_d2d(out.data_ptr(), src, out.numel() * out.element_size())
+        return out
+
     def forward(self, model, features):
         runtime.require_cuda(features, "features", torch.float32)
         assert tuple(features.shape) == (self.n_points, 6)

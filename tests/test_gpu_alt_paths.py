@@ -2,6 +2,8 @@
 
   PSG_FP1_WAVE=1     wave-private fp1 + head chain (psg_chain.cuh) instead of the workgroup-cooperative kernels
   PSG_RLA_ATOMICS=1  RandLA-Net backward scatters with float atomics instead of the inverse-list gathers
+  PSG_RLA_NO_FUSE16=1  RandLA-Net level 0: the unfused gather / score GEMM / softmax chain instead of lfa16_fwd / _bwd_kernel
+  PSG_RLA_NO_SPLIT=1   RandLA-Net levels 1-4: gather + per-edge score GEMM instead of att_pool_split_fwd / _bwd_kernel
   PSG_RLA_NO_DIRECT=1  RandLA-Net: the narrow layers (<= 64 output channels) on the LDS-tiled GEMM / the row-per-thread vector
                      kernel (rounds 1-4) instead of the barrier-free direct MFMA kernel (round 5)
   PSG_GCN_PQ_FUSION=1  ResGCN: a block's edge pass also computes the next block's per-vertex [P | Q] product
@@ -39,6 +41,8 @@ def child(test_file, keyword, extra_env):
     env.pop("PSG_GCN_EDGE_BWD", None)
     env.pop("PSG_PN2_SPLIT", None)
     env.pop("PSG_RLA_NO_DIRECT", None)
+    env.pop("PSG_RLA_NO_FUSE16", None)
+    env.pop("PSG_RLA_NO_SPLIT", None)
     env.pop("PSG_PN2_FPSPLIT", None)
     env.pop("PSG_PN2_L1T_COLOUR", None)
     env.pop("PSG_PN2_PGD_FUSE", None)
@@ -55,6 +59,11 @@ def child(test_file, keyword, extra_env):
     ("test_gpu_parity.py", "forward_vs_reference or backward_vs_reference or forward_backward_vs_oracle_batch", "PSG_FP1_WAVE"),
     ("test_randla_net.py", "forward_backward_vs_oracle or bim_attack_vs_oracle", "PSG_RLA_ATOMICS"),
     ("test_randla_net.py", "forward_backward_vs_oracle or bim_attack_vs_oracle", "PSG_RLA_NO_DIRECT"),
+    # the stage-by-stage float64 checks (ragged 8704-point cloud: every row count off its tile) on each RandLA path
+    ("test_randla_stages.py", "(forward_stages or backward_stages) and n8704", "PSG_RLA_NO_FUSE16"),
+    ("test_randla_stages.py", "(forward_stages or backward_stages) and n8704", "PSG_RLA_NO_SPLIT"),
+    ("test_randla_stages.py", "(forward_stages or backward_stages) and n8704", "PSG_RLA_ATOMICS"),
+    ("test_randla_stages.py", "(forward_stages or backward_stages) and n8704", "PSG_RLA_NO_DIRECT"),
     ("test_gpu_resgcn28.py", "not knn_on_reference_features", "PSG_GCN_PQ_FUSION"),
     ("test_gpu_resgcn.py", "forward_backward or nb_attack", "PSG_GCN_EDGE_BWD=atomic"),
     ("test_gpu_parity.py", "forward_vs_reference or backward_vs_reference or forward_backward_vs_oracle_batch or nb_attack_steps_vs_reference",
