@@ -583,11 +583,23 @@ __global__ void pw9_fwd_kernel(const float *__restrict__ x0, const float *__rest
     *(float4 *)(out + n * 32 + c0) = make_float4(r[0], r[1], r[2], r[3]);
 }
 
+// PSG_PN2_PW_SIZED=0 keeps the per-point launches of the split SA levels as they were: the forward product on the borrowed
+// fp_fwd_kernel<32, 8> (a skip part only), its gradient on pw_bwd_kernel<32, 8> whatever the layer's width (A/B runs,
+// tests/test_gpu_pw_sized.py).  Default: workgroups with as many waves as the layer has output tiles (run_pw_fwd, run_pw_bwd).
+// Either way every tile runs the same k-loop over the whole K: the two paths are bit-identical.
+inline bool pw_sized()
+{
+    static const bool v = psg::env_int("PSG_PN2_PW_SIZED", 1) != 0;
+    return v;
+}
+
 // Per-point side of a split SA level (arch_split): T = act[lvl - 1] . W1f^T + b1 for the Nl[lvl] points of every room, one
-// launch of the cooperative row-MLP kernel (fp_fwd_kernel with a skip part only: C2 = 0, one layer, no ReLU).
+// launch of pw_fwd_kernel (psg_pn2_kernels.cuh): 2 waves per 32-point tile where the layer has 2 output blocks (level 1), else
+// 4 waves and one workgroup per 4 output blocks (level 3, 8 blocks: two workgroups per tile, so that 64 rooms' 128 tiles
+// cover the chip's 256 CUs).
 int run_pw_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipStream_t st)
 {
-    constexpr int P = 32, NW = 8;
+    constexpr int P = 32;
     const PackedLayer &F = m->sf[lvl][sc];
     const int B = ws->B, N = ws->Nl[lvl];
     if (lvl == 0) {
@@ -597,6 +609,20 @@ int run_pw_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
         PSG_LAUNCH_CHECK();
         return PSG_OK;
     }
+    if (pw_sized()) {
+        PwFwdArgs p;
+        p.in = ws->act[lvl - 1]; p.out = ws->tfeat[lvl][sc];
+        p.l = fwd_layer(F, false, nullptr);
+        p.N = N; p.D = F.cin; p.C1 = F.cout;
+        if (N % P || p.D % 8 || p.C1 % 32) { set_error("run_pw_fwd level %d: unsupported shape", lvl); return PSG_ERR_STATE; }
+        if (p.l.mb <= 2) {
+            const int blocks = layer_blocks(p.l.k8, 2) + PSG_LDS_SPARE;
+            return launch_lds(ws, TAG_PW_FWD, PSG_SITE "#nw2", (pw_fwd_kernel<P, 2>), dim3(N / P, B, 1), 2 * 64, blocks, Lds<P>::BLK, p, st);
+        }
+        const int blocks = layer_blocks(p.l.k8, 4) + PSG_LDS_SPARE;
+        return launch_lds(ws, TAG_PW_FWD, PSG_SITE "#nw4", (pw_fwd_kernel<P, 4>), dim3(N / P, B, ceil_div(p.l.mb, 4)), 4 * 64, blocks, Lds<P>::BLK, p, st);
+    }
+    constexpr int NW = 8;
     FpFwdArgs a;
     a.feat1 = ws->act[lvl - 1]; a.C1 = F.cin;
     a.feat2 = ws->act[lvl - 1]; a.C2 = 0;
@@ -617,6 +643,8 @@ int run_pw_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
 // dsum[lvl - 1] = dact[lvl - 1] (skip-link rows of the coarser FP module; level 3 feeds fp4 only: its skip part is that gather,
 // done in sa_bwd) + (sum of the dZ1 rows of level lvl per source point) . W1f
 // (MSG: the second scale of a level adds its product to what the first one wrote)
+// Four waves where the transposed layer has at most four output tiles (SSG levels 1 and 2: D = 64 / 128), eight otherwise; a
+// point's list is walked by one wave in list order whatever the wave count (pw_bwd_gather_rows), so the sums do not change.
 int run_pw_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipStream_t st)
 {
     constexpr int P = 32, NW = 8;
@@ -634,6 +662,10 @@ int run_pw_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
     if ((a.C1 != 64 && a.C1 != 128 && a.C1 != 256) || a.wt.mb > 2 * NW || N % P || a.D % 32) {
         set_error("run_pw_bwd level %d: unsupported shape", lvl);
         return PSG_ERR_STATE;
+    }
+    if (pw_sized() && a.wt.mb <= 4) {    // (D <= 128: one float4 piece of a skip-link row per thread)
+        const int blocks = layer_blocks(a.wt.k8, a.wt.mb) + PSG_LDS_SPARE;
+        return launch_lds(ws, TAG_PW_BWD, PSG_SITE "#nw4", (pw_bwd_kernel<P, 4, 1, 1>), dim3(N / P, B), 4 * 64, blocks, Lds<P>::BLK, a, st);
     }
     const int blocks = layer_blocks(a.wt.k8, a.wt.mb) + PSG_LDS_SPARE;
     if (a.wt.mb > NW)       // MSG level 3: 512 feature channels = 16 output tiles on 8 waves

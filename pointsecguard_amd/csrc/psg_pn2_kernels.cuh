@@ -1299,7 +1299,8 @@ __device__ __forceinline__ void pw_bwd_gather_rows(const PwBwdArgs &a, int b, in
     }
 }
 
-template <int P, int NW, int MAXT = 1>
+// MAXQ = float4 pieces of a skip-link row per thread (32 lanes on a row): D <= 128 * MAXQ.
+template <int P, int NW, int MAXT = 1, int MAXQ = 4>
 __global__ __launch_bounds__(NW * 64) void pw_bwd_kernel(PwBwdArgs a)
 {
     using L = Lds<P>;
@@ -1317,7 +1318,7 @@ __global__ __launch_bounds__(NW * 64) void pw_bwd_kernel(PwBwdArgs a)
     __syncthreads();
     // the skip-link rows this thread will add at the end: issued now, so the round trip runs under the layer (fetched inside the
     // store loop below they were a chain of misses at the tail of the workgroup); up to 8 pieces per thread (D <= 512)
-    constexpr int RG = NT / 32, ROWS = P / RG, MAXQ = 4;
+    constexpr int RG = NT / 32, ROWS = P / RG;
     const int ql = tid & 31, rg = tid >> 5;
     const float *sb = a.skip ? a.skip + ((size_t)b * a.N + n0) * a.D : nullptr;
     float4 sk[ROWS][MAXQ];
@@ -1348,6 +1349,54 @@ __global__ __launch_bounds__(NW * 64) void pw_bwd_kernel(PwBwdArgs a)
                 }
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------ per-point product, forward
+// T = in . W1f^T + b1 for P = 32 points per workgroup (run_pw_fwd): the one layer of the split SA levels' per-point side.  It used to
+// be a launch of fp_fwd_kernel<32, 8> with an empty interpolated part - eight waves whatever the layer's width
+// (two of them with a tile at level 1, four at level 2) and a point's three neighbour entries read for nothing.  Here a
+// workgroup has as many waves as it has output blocks, at most NW: blockIdx.z picks the NW blocks of 32 output channels it
+// computes (level 3: 8 blocks = two workgroups of 4 waves per point tile, 256 workgroups at 64 rooms instead of 128 on 256
+// CUs; each reads the tile's input rows, which the second finds in L2).  Every tile runs layer_fwd's k-loop and epilogue over
+// the whole K: the rows are bit-identical to the borrowed kernel's.
+struct PwFwdArgs {
+    const float *in;    // [B][N][D]
+    float *out;         // [B][N][C1]
+    FwdLayer l;         // W1f with the layer's bias: k8 = D / 8, mb = C1 / 32, no ReLU, no mask
+    int N, D, C1;
+};
+
+template <int P, int NW>
+__global__ __launch_bounds__(NW * 64) void pw_fwd_kernel(PwFwdArgs a)
+{
+    using L = Lds<P>;
+    constexpr int NT = NW * 64, RG = NT / 32;
+    extern __shared__ float lds[];
+    float *buf0 = lds;
+    const int tid = threadIdx.x, ql = tid & 31, rg = tid >> 5;
+    int bx, b;
+    xcd_tile(bx, b);
+    const int n0 = bx * P;
+    const size_t wg = (size_t)b * gridDim.x + bx;
+    const float *ib = a.in + ((size_t)b * a.N + n0) * a.D;
+    for (int j = rg; j < P; j += RG) {
+        const unsigned o = __umul24((unsigned)j, (unsigned)a.D);
+        for (int q = ql; q < (a.D >> 2); q += 32) *(float4 *)(buf0 + L::off(4 * q, j)) = *(const float4 *)(ib + (o + 4u * q));
+    }
+    __syncthreads();
+    FwdLayer l = a.l;   // this workgroup's output blocks [mb0, mb0 + l.mb), computed in place into LDS blocks 0 .. 4 * l.mb
+    const int mb0 = (int)blockIdx.z * NW;
+    l.w += (size_t)mb0 * l.k8 * 64;
+    l.bias += mb0 * 32;
+    l.mb = min(NW, a.l.mb - mb0);
+    layer_fwd<P, NW, 1>(l, buf0, wg);
+    __syncthreads();
+    const int cq = l.mb * 8;    // float4 pieces of this workgroup's share of a row
+    float *ob = a.out + ((size_t)b * a.N + n0) * a.C1 + mb0 * 32;
+    for (int j = rg; j < P; j += RG) {
+        const unsigned o = __umul24((unsigned)j, (unsigned)a.C1);
+        for (int q = ql; q < cq; q += 32) *(float4 *)(ob + (o + 4u * q)) = *(const float4 *)(buf0 + L::off(4 * q, j));
     }
 }
 
