@@ -214,6 +214,7 @@ struct psg_pn2_ws {
     int32_t *fps[4];      // [F*B][S_l]
     float *xyz[5];        // xyz[l+1]: [F*B][S_l][3]; xyz[0] = xyz0
     int32_t *gidx[4][2];  // [F*B][S_l][K]
+    int32_t *ball0[2];    // per level-0 scale: [B][N][K] the room's ball query with every point as centroid, or null (ball_table_mode)
     int32_t *nn_idx[4];   // [F*B][N_l][3]
     float *nn_w[4];
     int32_t *inv_off[4];  // inverse 3-NN lists (CSR by coarse point): [F*B][S_l + 1]
@@ -593,6 +594,27 @@ inline bool pw_sized()
     return v;
 }
 
+// Level-0 ball query of a plan (psg_pn2_plan_build).  A plan of n_forward forwards queries n_forward x 1024 centroids per room,
+// every one of them a point of the room; the table route queries each of the room's N points once and copies rows
+// (group_from_table_kernel).  It is taken when the plan asks for at least BALL_TABLE_C x N centroids per room: the colour
+// attacks' plans (40 forwards: 40 960 against 4 096; the NU plans: 10 or 11 forwards), not a one-forward evaluation plan, and
+// not the coordinate attacks, which rebuild a one-forward plan whenever xyz moves (the table would be built for 1024 rows).
+// PSG_PN2_BALL_TABLE=0: always the direct query (A/B runs, tests/test_gpu_ball_table.py); =2: the table for every plan (the
+// measurement of the threshold).  Integer results: the two routes are equal or one is wrong.
+constexpr int BALL_TABLE_C = 2;
+static_assert(1 * 1024 < BALL_TABLE_C * 1024, "a one-forward plan stays on the direct route at every n_point a workspace accepts");
+inline int ball_table_mode()
+{
+    static const int v = psg::env_int("PSG_PN2_BALL_TABLE", 1);
+    return v;
+}
+inline bool ball_table_route(int n_forward, int N)
+{
+    const int mode = ball_table_mode();
+    if (mode == 0 || mode == 2) return mode == 2;
+    return (long long)n_forward * kS[0] >= (long long)BALL_TABLE_C * N;
+}
+
 // Per-point side of a split SA level (arch_split): T = act[lvl - 1] . W1f^T + b1 for the Nl[lvl] points of every room, one
 // launch of pw_fwd_kernel (psg_pn2_kernels.cuh): 2 waves per 32-point tile where the layer has 2 output blocks (level 1), else
 // 4 waves and one workgroup per 4 output blocks (level 3, 8 blocks: two workgroups per tile, so that 64 rooms' 128 tiles
@@ -913,6 +935,23 @@ __global__ void gather_starts_kernel(const int32_t *__restrict__ starts, int32_t
     if (p < P) out[p] = starts[((size_t)(p / B) * 4 + level) * B + (p % B)];
 }
 
+// Level-0 groups of a many-forward plan from the room's ball table (psg_pn2_plan_build): a level-0 centroid IS a point of the
+// room (xyz[1] = xyz0[fps]: psg_gather_points copies the three floats), and the ball query of a centroid - the first K
+// indices in index order with sqdist(centroid, .) <= r^2 - depends on nothing but the centroid's bits and the room, so
+// gidx[p][s][0:K] = table[p % B][fps[p][s]][0:K].  A row is K int32 (128 or 64 bytes): K / 4 lanes copy it as int4, 8 or 16 rows
+// per wave; the lanes of a row read the same fps word (one broadcast load).
+__global__ void group_from_table_kernel(const int32_t *__restrict__ table, const int32_t *__restrict__ fps, int B, int N, int S,
+                                        int K4, size_t rows, int32_t *__restrict__ gidx)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t row = t / K4;
+    if (row >= rows) return;
+    const int part = (int)(t - row * K4);
+    const size_t p = row / S;
+    const int4 *src = (const int4 *)(table + ((p % B) * N + (size_t)fps[row]) * K4 * 4);
+    ((int4 *)gidx)[t] = src[part];
+}
+
 constexpr int INV_NT = 1024;
 
 // Inverse of the 3-NN tables: for every coarse point the (fine point, weight) pairs that interpolate from it,
@@ -1206,6 +1245,9 @@ void ws_layout(psg_pn2_ws *ws, Bump &bp)
         ws->gxyz[l + 1] = full ? bp.take<float>((size_t)B * ws->Nl[l + 1] * 3) : nullptr;
     }
     ws->gxyz[0] = nullptr;
+    // (last of all, for the same reason) the per-room level-0 ball tables, where a plan of this workspace can reach the table route
+    for (int s = 0; s < 2; ++s)
+        ws->ball0[s] = s < A.ns && ball_table_route(F, ws->N) ? bp.take<int32_t>((size_t)B * ws->N * A.sc[0][s].K) : nullptr;
 }
 
 }  // namespace
@@ -1488,10 +1530,24 @@ extern "C" int psg_pn2_plan_build(psg_pn2_ws *ws, const float *x0, const int32_t
         }
         for (int sc = 0; sc < ws->arch->ns; ++sc) {
             const ScaleDesc &d = ws->arch->sc[l][sc];
+            // level 0 of a many-forward plan (ball_table_route): the room's own points as the centroid set (S = N), in a profile
+            // scope of its own (psg_pn2_prof_read counts one launch more under TAG_BALL), then one row copy per (problem, centroid)
+            const bool table = l == 0 && ws->ball0[sc] && ball_table_route(n_forward, Np);
+            if (table) {
+                PSG_REQUIRE(d.K % 4 == 0, "psg_pn2_plan_build: nsample=%d is no multiple of 4", d.K);
+                EvScope prof(&ws->prof, TAG_BALL, 0.0, st);
+                if ((rc = psg_ball_query(ws->ctx, ws->xyz0, B, ws->xyz0, B, Np, Np, d.r2, d.K, ws->ball0[sc], st))) return rc;
+            }
             EvScope prof(&ws->prof, TAG_BALL, 0.0, st);
-            if ((rc = psg_ball_query(ws->ctx, ws->xyz[l], n_clouds, ws->xyz[l + 1], P, Np, S, d.r2, d.K,
-                                     ws->gidx[l][sc], st)))
+            if (table) {
+                const size_t rows = (size_t)P * S, items = rows * (d.K / 4);
+                hipLaunchKernelGGL(group_from_table_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, ws->ball0[sc],
+                                   ws->fps[0], B, Np, S, d.K / 4, rows, ws->gidx[0][sc]);
+                PSG_LAUNCH_CHECK_AT(PSG_SITE "#table");
+            } else if ((rc = psg_ball_query(ws->ctx, ws->xyz[l], n_clouds, ws->xyz[l + 1], P, Np, S, d.r2, d.K, ws->gidx[l][sc],
+                                            st))) {
                 return rc;
+            }
             const size_t inv_lds = (size_t)(Np + 1) * 4 + (size_t)S * d.K * 2;
             if (inv_lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)build_inv_group_kernel));
             hipLaunchKernelGGL(build_inv_group_kernel, dim3(P), dim3(INV_NT), inv_lds, st, ws->gidx[l][sc], S * d.K, Np, d.K,
