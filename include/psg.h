@@ -263,7 +263,8 @@ int psg_to_channel_major(const float *src_nc, int B, int C, int N, float *dst_cn
 /* d/dlogp of scale * sum_i CE(logp_i, y_i) with CE applied ON TOP of the log-probs (a second
  * log_softmax), nontarget.py:26,34 / target.py:27,39.  labels [rows] int32, or a single class
  * when labels == NULL (`target`).  rows_active: only the first rows_active rows get a gradient
- * (target.py:36 uses batch row 0 only); the rest are zeroed.  cost_out (nullable): 1 float, += cost. */
+ * (target.py:36 uses batch row 0 only); the rest are zeroed.  cost_out (nullable): 1 float, += cost.
+ * Every label must lie in [0, n_cls): the kernel does not check them. */
 int psg_ce_logp_grad(const float *logp, const int32_t *labels, int target, int rows, int rows_active, int n_cls,
                      float scale, float *dlogp_out, float *cost_out, psg_stream stream);
 
@@ -341,14 +342,17 @@ int psg_nu_tanh_color(const float *w, const uint8_t *mask, int B, int N, float *
 
 /* f-loss (nontarget.py:119-128 / target.py:148-168): per point clamp(tsign*(p_y - max_{k!=y} p_k), min=-kappa)
  * on p = softmax(log-probs); y = labels[row] or `target` when labels == NULL.  Writes d(sum f)/d(logp),
- * adds the sum to *f_sum (nullable) and the arg-max class to pred_out (nullable). */
+ * adds the sum to *f_sum (nullable) and the arg-max class to pred_out (nullable).  Every label must lie in
+ * [0, n_cls): the kernel indexes the row with it unchecked (the same holds for the _rooms entry point). */
 int psg_nu_f_loss_grad(const float *logp, const int32_t *labels, int target, int rows, int n_cls, float kappa,
                        float tsign, float *dlogp_out, float *f_sum, int32_t *pred_out, psg_stream stream);
 
 /* f-loss of the ResGCN NU attacks on raw logits [rows][n_cls] (ResGCN/.../attacks/colper.py:108-113,
  * tcolper.py:145-163); the reference's one-hot masking makes a 0 take part in each max.  mode 0 = NU_attack.f over
  * all rows; mode 1 = tar_NU non_f, mode 2 = tar_NU tar_f (class `target`), both over batch row 0 under `mask` only.
- * Writes scale * d(sum f)/d(logits), adds sum f to *f_sum (nullable), arg-max class to pred_out (nullable). */
+ * Writes scale * d(sum f)/d(logits), adds sum f to *f_sum (nullable), arg-max class to pred_out (nullable).
+ * Each max is torch.max's: the FIRST maximum among the class slots, the zeroed ones included, takes the gradient.
+ * Every label must lie in [0, n_cls): the kernel indexes the row with it unchecked. */
 int psg_gcn_f_loss_grad(const float *logits, const int32_t *labels, int target, const uint8_t *mask, int mode, int rows,
                         int n_point, int n_cls, float kappa, float tsign, float scale, float *dlogits_out, float *f_sum,
                         int32_t *pred_out, psg_stream stream);
@@ -500,7 +504,7 @@ int psg_nu_restart_rooms(float *x0, const float *x0_orig, const uint8_t *mask_gr
 /* Segmentation statistics of NB_nontarget_test_semseg.py:199-205: for every class l accumulates
  * seen[l] += #(gt==l), inter[l] += #(pred==l & gt==l), uni[l] += #(pred==l | gt==l) where
  * pred = argmax(logp) (first index on ties).  counters: int64 [3][n_cls] = seen, inter, uni.
- * pred_out (nullable) int32 [rows]. */
+ * pred_out (nullable) int32 [rows].  Every label must lie in [0, n_cls): the counters are indexed with it unchecked. */
 int psg_seg_stats(const float *logp, const int32_t *labels, int rows, int n_cls, long long *counters,
                   int32_t *pred_out, psg_stream stream);
 

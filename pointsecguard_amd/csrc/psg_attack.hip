@@ -454,13 +454,18 @@ __global__ void gcn_f_loss_grad_kernel(const float *__restrict__ z, const int32_
         const bool counted = mode == 0 || (r < N && (!mask || mask[r]));
         if (counted) {
             const int y = (mode == 2 || !labels) ? target : labels[r];
-            float oth = 0.0f;       // the zeroed slot of the true class takes part in the max
+            // the zeroed slot of the true class takes part in the max, and torch.max returns its FIRST maximum: a class
+            // at exactly 0 (all others <= 0) takes the gradient when it stands before the true class, not after it
+            float oth = -INFINITY;
             int oi = -1;
-            for (int c = 0; c < n_cls; ++c)
-                if (c != y && v[c] > oth) { oth = v[c]; oi = c; }
+            for (int c = 0; c < n_cls; ++c) {
+                const float s = c == y ? 0.0f : v[c];
+                if (s > oth) { oth = s; oi = c == y ? -1 : c; }
+            }
             float own = v[y];
             bool own_live = true;
-            if (mode == 0 && !(own > 0.0f)) { own = 0.0f; own_live = false; }
+            // mode 0: max(onehot * z) - the other slots hold 0; a true-class logit of exactly 0 is the first maximum only in slot 0
+            if (mode == 0 && !(own > 0.0f)) { own_live = own == 0.0f && y == 0; own = 0.0f; }
             const float jv = mode == 2 ? oth : own, iv = mode == 2 ? own : oth;
             const float val = tsign * (jv - iv);
             const bool pass = val >= -kappa;
