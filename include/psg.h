@@ -501,6 +501,73 @@ int psg_nu_restart_rooms(float *x0, const float *x0_orig, const uint8_t *mask_gr
                          const uint8_t *flags, const float *noise, const long long *noise_off, int G, int rows, int N,
                          float *extra_l2, psg_stream stream);
 
+/* ---- NU attacks on the COORDINATE field (channels 0:3) of the PointNet++ SSG network: an extension of the reference API,
+ * rooms form only (B independent one-room attacks in lockstep, B >= 1).  The attack variable delta [B][N][3] (metres) is
+ * optimised directly by Adam - no tanh space, coordinates have no box -, xyz = ori_xyz + delta. */
+
+/* The Smooth term (nontarget.py:131-135) on coordinates: the contract of psg_smooth_knn_rooms (strided rows, per-room strides
+ * in floats, nb <= 16, N <= 8192, dist_sum_rooms [B] added to, grad_out [B][N][3] written) with the distance evaluated on
+ * DIRECT differences, d^2 = fma(dz, dz, fma(dy, dy, dx * dx)), dx = a.x - r.x, d = sqrt(d^2): |d_fp32 - d| <= 4 * 2^-24 d,
+ * where the matmul expansion of psg_smooth_knn_rooms leaves ~1e-3 m on coordinates in metres.  Neighbours by (distance,
+ * index), the lower index first; the gradient sum_j (a - r_j) / d_j adds up in ascending rank order and a neighbour at
+ * d_j == 0 adds exactly zero.  room_active [B] (nullable = all): an inactive room is not touched (sum, gradient, lists).
+ * nn_out (nullable): int32 [B][N][nb] receives every point's neighbour indices in rank order (a room with fewer than nb
+ * references leaves the missing ranks as they are). */
+int psg_smooth_knn_xyz_rooms(const float *adv_xyz, int adv_stride, size_t adv_room_stride, const float *ref_xyz,
+                             int ref_stride, size_t ref_room_stride, int B, int N, int nb, float *dist_sum_rooms,
+                             float *grad_out, const uint8_t *room_active, int32_t *nn_out, psg_stream stream);
+/* x0[b][i][0:3] = ori_xyz[b][i] + delta[b][i] for the points under mask_rooms [B][N] (nullable = all) of active rooms;
+ * every other byte of x0 [B][N][9] stays. */
+int psg_nu_coord_apply_rooms(const float *delta, const float *ori_xyz, const uint8_t *mask_rooms, int B, int N,
+                             const uint8_t *room_active, float *x0, psg_stream stream);
+/* One optimiser step on delta: g = dx0[.][0:3] + 2 coord_c delta + coord_c sgrad_xyz (nullable), then torch.optim.Adam's
+ * single-tensor update (betas, eps, bias correction for `step` >= 1, step size coord_lr) of delta / m / v [B][N][3] in
+ * place, on masked points of active rooms.  Adds sum(delta^2) of the delta the step started from to l2_sum_rooms [B]
+ * (nullable); the slot of an inactive room is not touched. */
+int psg_nu_coord_adam_step_rooms(float *delta, float *m, float *v, const uint8_t *mask_rooms, const float *dx0,
+                                 const float *sgrad_xyz, float coord_c, float coord_lr, float beta1, float beta2, float eps,
+                                 int step, int B, int N, const uint8_t *room_active, float *l2_sum_rooms, psg_stream stream);
+
+/* ONE step of NU_attack / tar_NU_attack(field = "coord" | "both") for G one-room attacks, enqueued on `stream`:
+ * psg_nu_coord_apply_rooms (both: + psg_nu_tanh_color_rooms), psg_pn2_plan_build(n_forward = 1) from the moved points
+ * into plan slot 0, psg_pn2_forward, psg_nu_f_loss_grad_rooms, psg_pn2_backward_full, (both: psg_smooth_knn_rooms on the
+ * colours,) psg_smooth_knn_xyz_rooms, (both: psg_nu_adam_step(_rooms) on w,) psg_nu_coord_adam_step_rooms,
+ * psg_nu_step_latch - whose exit snapshot therefore carries the moved coordinates and lags the optimiser by one step,
+ * like the colour loop.  Cost = f + c (Smooth_rgb + L2_rgb) + coord_c (Smooth_xyz + L2_xyz), the colour terms with
+ * field both only.  PSG_PN2_ARCH_SSG with the split first layers only: anything else returns PSG_ERR_ARG with a message
+ * before anything is enqueued.  N must be a multiple of 64 (psg_nu_f_loss_grad_rooms). */
+#define PSG_NU_FIELD_COORD 1
+#define PSG_NU_FIELD_BOTH 2
+typedef struct psg_nu_field_args {
+    psg_pn2_model *model;
+    psg_pn2_ws *ws;              /* created for G rooms of N points; plan slot 0 is rebuilt by every step */
+    int step, adam_t;            /* the step's number (exit latch); optimiser steps since the optimiser was created, this one included (>= 1) */
+    int G, N, mode;              /* mode: see psg_nu_step_latch */
+    int use_target, target;      /* the f-loss takes `target` instead of the labels */
+    int neighbour, warm;         /* Smooth terms: neighbour count; 1 = nn_state holds the previous step's colour lists */
+    int field;                   /* PSG_NU_FIELD_COORD or PSG_NU_FIELD_BOTH */
+    float kappa, tsign, c, lr, coord_c, coord_lr, beta1, beta2, eps;
+    float *w, *m, *v;            /* [G][N][3] colour variable and moments (field both) */
+    float *delta, *m_xyz, *v_xyz;   /* [G][N][3] coordinate variable and moments */
+    const float *ori_xyz;        /* [G][N][3] the clean coordinates */
+    const uint8_t *mask;         /* [G][N], nullable for NU_attack */
+    const int32_t *n_mask;       /* [G], modes 1 and 2 */
+    float *x0;                   /* [G][N][9] */
+    const float *ori;            /* [G][N][3] the clean colours (field both) */
+    const int32_t *labels;       /* [G][N] */
+    const int32_t *starts;       /* [4][G] this step's FPS start indices */
+    float *logp, *dlogp, *dx0;   /* [G][N][13], [..][13], [..][9] scratch */
+    float *sgrad, *sgrad_xyz;    /* [G][N][3] each (sgrad: field both) */
+    int32_t *pred;               /* [G][N] */
+    float *scal;                 /* [5][G] f, Smooth_rgb, L2_rgb, Smooth_xyz, L2_xyz; zero before the first step */
+    int32_t *nn_state;           /* [G][N][neighbour] (field both) */
+    float *hist;                 /* this step's history row [7][G]: the latch's five entries, then Smooth_xyz, L2_xyz */
+    float *out;                  /* [G][9][N] */
+    uint8_t *active;             /* [G] */
+    int32_t *exit_step;          /* [G] */
+} psg_nu_field_args;
+int psg_pn2_nu_field_step(const psg_nu_field_args *args, psg_stream stream);
+
 /* Segmentation statistics of NB_nontarget_test_semseg.py:199-205: for every class l accumulates
  * seen[l] += #(gt==l), inter[l] += #(pred==l & gt==l), uni[l] += #(pred==l | gt==l) where
  * pred = argmax(logp) (first index on ties).  counters: int64 [3][n_cls] = seen, inter, uni.

@@ -100,6 +100,10 @@ SIGNATURES = {
     "psg_nu_f_loss_grad_rooms": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp]),
     "psg_smooth_knn_rooms": (ci, [vp, ci, ctypes.c_size_t, vp, ci, ctypes.c_size_t, ci, ci, ci, vp, vp, vp, ci, vp]),
     "psg_nu_adam_step_rooms": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, cf, ci, ci, ci, vp, vp, vp]),
+    "psg_smooth_knn_xyz_rooms": (ci, [vp, ci, ctypes.c_size_t, vp, ci, ctypes.c_size_t, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "psg_nu_coord_apply_rooms": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
+    "psg_nu_coord_adam_step_rooms": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, ci, ci, vp, vp, vp]),
+    "psg_pn2_nu_field_step": (ci, [vp, vp]),
     "psg_gcn_model_create": (ci, [vp, ctypes.POINTER(vp), ci, ci, ctypes.POINTER(vp)]),
     "psg_gcn_model_create_cfg": (ci, [vp, ctypes.POINTER(vp), ci, ci, ci, ci, ctypes.POINTER(vp)]),
     "psg_gcn_model_destroy": (ci, [vp]),
@@ -170,6 +174,16 @@ class PointnetNuWindowArgs(ctypes.Structure):
                 [(n, cf) for n in ("kappa", "tsign", "c_smooth", "c_l2", "lr", "beta1", "beta2", "eps")] +
                 [(n, vp) for n in ("w", "m", "v", "mask", "n_mask", "x0", "ori", "labels", "logp", "dlogp", "dx0", "sgrad", "pred",
                                    "scal", "nn_state", "hist", "out", "active", "exit_step")])
+
+
+class NuFieldArgs(ctypes.Structure):
+    """psg_nu_field_args of include/psg.h, field for field."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("step", "adam_t", "G", "N", "mode", "use_target", "target", "neighbour", "warm", "field")] +
+                [(n, cf) for n in ("kappa", "tsign", "c", "lr", "coord_c", "coord_lr", "beta1", "beta2", "eps")] +
+                [(n, vp) for n in ("w", "m", "v", "delta", "m_xyz", "v_xyz", "ori_xyz", "mask", "n_mask", "x0", "ori", "labels",
+                                   "starts", "logp", "dlogp", "dx0", "sgrad", "sgrad_xyz", "pred", "scal", "nn_state", "hist", "out",
+                                   "active", "exit_step")])
 
 
 _lib = None

@@ -49,14 +49,26 @@ class NB_attack(Attack):
 
 
 class NU_attack(Attack):
-    def __init__(self, model, c=1e-4, kappa=0, steps=1000, lr=0.01):
+    """Norm-unbounded attack (Adam on f + c (Smooth + L2)).  `field` is an extension of the reference API, like NB_attack's:
+    "color" (default) is the reference's attack on channels 3:6 and runs exactly the code path it always ran; "coord" moves
+    channels 0:3 (delta in metres optimised directly, cost f + coord_c (Smooth_xyz + L2_xyz), step size coord_lr), "both"
+    the two fields together - PointNet++ SSG only, one room per call or `forward_rooms` (nu_field.py).  coord_c / coord_lr
+    default to c / lr."""
+
+    def __init__(self, model, c=1e-4, kappa=0, steps=1000, lr=0.01, field="color", coord_c=None, coord_lr=None):
         super(NU_attack, self).__init__("NU_attack", model)
         self.c = c
         self.kappa = kappa
         self.steps = steps
         self.lr = lr
+        self.field = check_field(field)
+        self.coord_c = coord_c
+        self.coord_lr = coord_lr
 
     def forward(self, images, labels):
+        if self.field != "color":
+            from .nu_field import nu_field_attack
+            return nu_field_attack(self, images, labels, mask=None, target=None, neighbour=10)
         if is_pointnet(self.model):
             from .pointnet import nu_attack as pointnet_nu_attack
             return pointnet_nu_attack(self, images, labels, mask=None, target=None, neighbour=10)
@@ -66,5 +78,8 @@ class NU_attack(Attack):
     def forward_rooms(self, images, labels):
         """Extension of the reference API: the attack applied to every room of `images` [R, 9, N] on its own (R calls with
         batches of one), all rooms advanced in lockstep; returns (adversarial images, optimiser steps run per room)."""
+        if self.field != "color":             # (one room and more; the colour path keeps its R >= 2 rule)
+            from .nu_field import nu_field_attack_rooms
+            return nu_field_attack_rooms(self, images, labels, None, None, neighbour=10)
         from .nu import nu_attack_rooms
         return nu_attack_rooms(self, images, labels, None, None, neighbour=10)

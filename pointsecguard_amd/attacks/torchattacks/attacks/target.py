@@ -50,7 +50,14 @@ class tar_NB_attack(Attack):
 
 
 class tar_NU_attack(Attack):
-    def __init__(self, model, c=1e-4, kappa=0, steps=1000, lr=0.01, target=None, mask=None):
+    """Targeted norm-unbounded attack.  `field` / `coord_c` / `coord_lr` are an extension of the reference API, see NU_attack:
+    "color" (default) runs exactly the code path it always ran.  With field != "color" (PointNet++ SSG, one room per call or
+    `forward_rooms`) the learning-rate halving with a fresh optimiser every 50 steps stays - both learning rates halve, all
+    moments are zeroed - but the restart of target.py:127-132 is NOT applied: it is uniform [0, 1] noise followed by a clamp
+    of all nine channels to the colour box, which has no coordinate counterpart and would wipe the perturbation."""
+
+    def __init__(self, model, c=1e-4, kappa=0, steps=1000, lr=0.01, target=None, mask=None, field="color", coord_c=None,
+                 coord_lr=None):
         super(tar_NU_attack, self).__init__("tar_NU_attack", model)
         self.c = c
         self.kappa = kappa
@@ -58,8 +65,14 @@ class tar_NU_attack(Attack):
         self.lr = lr
         self.target = target
         self.mask = mask
+        self.field = check_field(field)
+        self.coord_c = coord_c
+        self.coord_lr = coord_lr
 
     def forward(self, images, labels):
+        if self.field != "color":
+            from .nu_field import nu_field_attack
+            return nu_field_attack(self, images, labels, mask=self.mask, target=self.target, neighbour=5, targeted_variant=True)
         if is_pointnet(self.model):
             from .pointnet import nu_attack as pointnet_nu_attack
             return pointnet_nu_attack(self, images, labels, mask=self.mask, target=self.target, neighbour=5,
@@ -72,5 +85,8 @@ class tar_NU_attack(Attack):
         with batches of one and `mask = masks[r]` compute), all rooms advanced in lockstep with one launch per operation.
         Returns (adversarial images [R, 9, N], optimiser steps run per room); see nu.nu_attack_rooms for the two
         bookkeeping differences from R sequential calls (order of RNG consumption; at most 50 steps)."""
+        if self.field != "color":
+            from .nu_field import nu_field_attack_rooms
+            return nu_field_attack_rooms(self, images, labels, masks, self.target, neighbour=5, targeted_variant=True)
         from .nu import nu_attack_rooms
         return nu_attack_rooms(self, images, labels, masks, self.target, neighbour=5, targeted_variant=True)

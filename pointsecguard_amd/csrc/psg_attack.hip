@@ -1210,3 +1210,6 @@ extern "C" int psg_pn2_nu_window(const psg_nu_window_args *a, psg_nu_graph *grap
                                 a->step0, a->adam_t0, a->lr, a->beta1, a->beta2, (hipStream_t)stream,
                                 [&](const float *rows) { return nu_window_steps(a, rows, stream); });
 }
+
+// NU attacks on the coordinate field of the PointNet++ SSG network (kernels and entry points)
+#include "psg_nu_field.cuh"

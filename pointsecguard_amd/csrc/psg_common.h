@@ -85,6 +85,9 @@ int pn2_forward_lean(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *x0,
 // psg_pn2_backward for the colour channels of the input gradient only (the NU loop; psg_pn2.hip)
 int pn2_backward_colour(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *dlogp, float *dx0_out, psg_stream stream);
 uint64_t pn2_ws_generation(const psg_pn2_ws *ws);
+// The model / workspace requirements of psg_pn2_backward_full (SSG, split first layers) under the caller's name `who`, for
+// entry points that enqueue other work before they reach it (psg_pn2_nu_field_step): PSG_OK or PSG_ERR_ARG with a message.
+int pn2_full_grad_check(const psg_pn2_model *m, const psg_pn2_ws *ws, const char *who);
 
 // hipGraph bookkeeping of the replayed loops (psg_pn2_nb_attack, psg_pn2_nu_window, psg_gcn_nb_attack, psg_rla_bim_attack): a capture that
 // fails falls back to the eager launches - correct, but slower - so it is COUNTED, per handle and for the process

@@ -1,0 +1,303 @@
+// NU attacks on the COORDINATE field of the PointNet++ SSG network; included by psg_attack.hip.
+// An extension of the reference API (the reference ships the colour half only): delta [G][N][3] in metres is optimised
+// directly by Adam - no tanh space, coordinates have no box -, xyz = ori_xyz + delta on masked points of active rooms.
+// Rooms form only: G independent one-room attacks in lockstep.
+//
+// Three kernels and the step that strings them with the existing entry points:
+//   smooth_knn_xyz_kernel      the Smooth term (nontarget.py:131-135) on channels 0:3 with DIRECT differences
+//   nu_coord_apply_kernel      x0[.][0:3] = ori_xyz + delta
+//   nu_coord_adam_kernel       gradient assembly + torch.optim.Adam on delta, per-room sum(delta^2)
+//   psg_pn2_nu_field_step      apply, plan, forward, f-loss, full backward, Smooth term(s), Adam step(s), latch
+#pragma once
+
+namespace {
+
+// Smooth term on coordinates.  smooth_knn_kernel evaluates |a|^2 + |r|^2 - 2 a.r like torch.cdist's matmul path, which is
+// what the reference's colours in [0, 1] see; on coordinates in metres that expansion cancels to noise of the order of a
+// millimetre - more than the perturbation, whose own distance |delta| is the dominant term.  Here
+//   d^2 = fma(dz, dz, fma(dy, dy, dx * dx)),  dx = a.x - r.x, ..,  d = sqrt(d^2):
+// one rounding per difference, three in the chain, one in the root, |d_fp32 - d| <= 4 * 2^-24 d.
+// Structure of the colour kernel: the room's reference points in LDS as three planes split into SUB runs (run s holds the
+// references s, s + SUB, ..), SUB lanes per query, each scanning its run with a sorted top-NBT in registers, then nb pops
+// of the SUB-way merge by (distance, index), lower index first.  The scan compares d^2 against a bound that is never below
+// the square of the distance bound (so it only admits more), the root is taken and compared exactly on the few
+// candidates that pass.  One configuration serves every launch: SUB = 8, 128 queries per workgroup of 1024 threads.
+constexpr int SMX_SUB = 8;
+constexpr int SMX_T = 1024;
+constexpr int SMX_REFRESH = 64;
+
+template <int NBT>
+__global__ __launch_bounds__(SMX_T) void smooth_knn_xyz_kernel(const float *__restrict__ adv, int adv_stride, size_t adv_room_stride,
+                                                               const float *__restrict__ ref, int ref_stride, size_t ref_room_stride,
+                                                               int N, int nb, float *__restrict__ dist_sum, float *__restrict__ grad,
+                                                               const uint8_t *__restrict__ room_active, int32_t *__restrict__ nn_out)
+{
+    if (room_active && !room_active[blockIdx.y]) return;            // (uniform over the workgroup) an inactive room is untouched
+    if (nn_out) nn_out += (size_t)blockIdx.y * N * nb;
+    adv += blockIdx.y * adv_room_stride;
+    ref += blockIdx.y * ref_room_stride;
+    grad += (size_t)blockIdx.y * N * 3;
+    if (dist_sum) dist_sum += blockIdx.y;
+    constexpr int QPB = SMX_T / SMX_SUB;
+    const int tps = ((N + SMX_SUB - 1) / SMX_SUB + 3) & ~3, run = tps + 8;
+    extern __shared__ float s_xyz[];
+    float *s_x = s_xyz, *s_y = s_xyz + SMX_SUB * run, *s_z = s_xyz + 2 * SMX_SUB * run;
+    for (int p = threadIdx.x; p < SMX_SUB * tps; p += SMX_T) {
+        const int sr = p / tps, t = p - sr * tps, i = sr + SMX_SUB * t;
+        // slots past N: every difference is -inf, d^2 = +inf, and +inf passes no bound
+        float x = INFINITY, y = INFINITY, z = INFINITY;
+        if (i < N) { x = ref[(size_t)i * ref_stride]; y = ref[(size_t)i * ref_stride + 1]; z = ref[(size_t)i * ref_stride + 2]; }
+        s_x[sr * run + t] = x; s_y[sr * run + t] = y; s_z[sr * run + t] = z;
+    }
+    __syncthreads();
+    const int ql = threadIdx.x / SMX_SUB, sub = threadIdx.x % SMX_SUB;
+    const int i = blockIdx.x * QPB + ql;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    if (i < N) { ax = adv[(size_t)i * adv_stride]; ay = adv[(size_t)i * adv_stride + 1]; az = adv[(size_t)i * adv_stride + 2]; }
+    float bd[NBT];
+    int bi[NBT];
+#pragma unroll
+    for (int t = 0; t < NBT; ++t) { bd[t] = INFINITY; bi[t] = 0x7FFFFFFF; }
+    // thr (a distance): a candidate is wanted only below min(this lane's worst kept distance, the nb-th smallest distance
+    // the query's lanes hold together at the last refresh) - exact for the reason given in smooth_knn_kernel: what is
+    // kept has a lower index than anything scanned later, so a later candidate AT the bound loses the tie.
+    // thr2 >= thr^2 (a few ulps up, and never 0): sqrt(d2) rounded < thr implies d2 < thr^2 <= thr2.
+    float thr = i < N ? INFINITY : -INFINITY, thr2 = thr;
+    const sm_v2f ax2 = {ax, ax}, ay2 = {ay, ay}, az2 = {az, az};
+    const float *px = s_x + sub * run, *py = s_y + sub * run, *pz = s_z + sub * run;
+    for (int t0 = 0; t0 < tps; t0 += SMX_REFRESH) {
+        const int t1 = t0 + SMX_REFRESH < tps ? t0 + SMX_REFRESH : tps;
+        for (int t = t0; t < t1; t += 4) {
+            const float4 X = *(const float4 *)(px + t), Y = *(const float4 *)(py + t), Z = *(const float4 *)(pz + t);
+            // two references per instruction; per component exactly fma(dz, dz, fma(dy, dy, dx * dx)) on rounded differences
+            const sm_v2f dxa = ax2 - sm_v2f{X.x, X.y}, dxb = ax2 - sm_v2f{X.z, X.w};
+            const sm_v2f dya = ay2 - sm_v2f{Y.x, Y.y}, dyb = ay2 - sm_v2f{Y.z, Y.w};
+            const sm_v2f dza = az2 - sm_v2f{Z.x, Z.y}, dzb = az2 - sm_v2f{Z.z, Z.w};
+            sm_v2f da = dxa * dxa, db = dxb * dxb;
+            da = __builtin_elementwise_fma(dya, dya, da); db = __builtin_elementwise_fma(dyb, dyb, db);
+            da = __builtin_elementwise_fma(dza, dza, da); db = __builtin_elementwise_fma(dzb, dzb, db);
+            const float d2[4] = {da[0], da[1], db[0], db[1]};
+            if (fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3])) < thr2) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (d2[u] < thr2) {
+                        float cd = sqrtf(d2[u]);
+                        if (cd < thr) {
+                            int ci = sub + SMX_SUB * (t + u);
+#pragma unroll
+                            for (int k = 0; k < NBT; ++k) {   // sorted insertion with static indexing (arrays stay in registers)
+                                if (cd < bd[k]) {
+                                    float td = bd[k]; int ti = bi[k];
+                                    bd[k] = cd; bi[k] = ci;
+                                    cd = td; ci = ti;
+                                }
+                            }
+                            thr = fminf(thr, bd[NBT - 1]);
+                            thr2 = __fadd_rn(__fmul_rn(__fmul_rn(thr, thr), 1.000001f), 1e-30f);
+                        }
+                    }
+                }
+            }
+        }
+        if (t1 < tps) {   // another chunk follows (uniform over the workgroup)
+            float cdist[NBT];
+            int cidx[NBT];
+#pragma unroll
+            for (int t = 0; t < NBT; ++t) { cdist[t] = bd[t]; cidx[t] = bi[t]; }
+            float kth = INFINITY;
+            int kidx;
+            for (int t = 0; t < nb; ++t) smooth_pop_min<NBT, SMX_SUB>(cdist, cidx, kth, kidx);
+            if (kth < thr) {
+                thr = kth;
+                thr2 = __fadd_rn(__fmul_rn(__fmul_rn(thr, thr), 1.000001f), 1e-30f);
+            }
+        }
+    }
+    // SUB-way merge: nb times the smallest head by (distance, index); the gradient adds up in ascending rank order
+    float local = 0.0f, gx = 0.f, gy = 0.f, gz = 0.f;
+    for (int t = 0; t < nb; ++t) {
+        float best;
+        int bidx;
+        smooth_pop_min<NBT, SMX_SUB>(bd, bi, best, bidx);
+        if (bidx == 0x7FFFFFFF) break;   // fewer than nb references (uniform over the query's lanes)
+        if (sub == 0 && i < N) {
+            if (nn_out) nn_out[(size_t)i * nb + t] = bidx;
+            local += best;
+            if (best > 0.0f) {           // a neighbour at distance 0 (the point's own original before it moved) adds exactly 0
+                const int pos = (bidx % SMX_SUB) * run + bidx / SMX_SUB;
+                gx += __fdiv_rn(__fsub_rn(ax, s_x[pos]), best);
+                gy += __fdiv_rn(__fsub_rn(ay, s_y[pos]), best);
+                gz += __fdiv_rn(__fsub_rn(az, s_z[pos]), best);
+            }
+        }
+    }
+    if (sub == 0 && i < N) { grad[(size_t)i * 3] = gx; grad[(size_t)i * 3 + 1] = gy; grad[(size_t)i * 3 + 2] = gz; }
+    for (int o = 32; o >= 1; o >>= 1) local += __shfl_xor(local, o);
+    if ((threadIdx.x & 63) == 0 && dist_sum) atomicAdd(dist_sum, local);
+}
+
+// x0[b][i][0:3] = ori_xyz + delta on masked points of active rooms; every other byte of x0 stays
+__global__ void nu_coord_apply_kernel(const float *__restrict__ delta, const float *__restrict__ ori_xyz, const uint8_t *__restrict__ mask,
+                                      const uint8_t *__restrict__ room_active, float *__restrict__ x0, int N)
+{
+    const size_t y = blockIdx.y;
+    if (room_active && !room_active[y]) return;
+    const size_t o3 = y * (size_t)N * 3;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < (size_t)N * 3; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t pt = t / 3;
+        if (mask && !mask[y * N + pt]) continue;
+        x0[(y * N + pt) * 9 + t % 3] = __fadd_rn(ori_xyz[o3 + t], delta[o3 + t]);
+    }
+}
+
+// g = dx0[0:3] + 2 coord_c delta + coord_c sgrad_xyz, then torch.optim.Adam's single-tensor update of delta / m / v
+// (the operation order of nu_adam_step_kernel), on masked points of active rooms; sum(delta^2) of the delta the step
+// STARTED from is added to the room's L2 slot (one atomic per workgroup).
+__global__ __launch_bounds__(256) void nu_coord_adam_kernel(float *__restrict__ delta, float *__restrict__ m, float *__restrict__ v,
+                                                             const uint8_t *__restrict__ mask, const float *__restrict__ dx0,
+                                                             const float *__restrict__ sgrad, float coord_c, float beta1, float beta2,
+                                                             float eps, float step_size, float bc2_sqrt, int N,
+                                                             const uint8_t *__restrict__ room_active, float *__restrict__ l2_sum)
+{
+    const size_t y = blockIdx.y;
+    if (room_active && !room_active[y]) return;
+    const size_t o3 = y * (size_t)N * 3;
+    float l2 = 0.0f;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < (size_t)N * 3; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t pt = t / 3;
+        if (mask && !mask[y * N + pt]) continue;
+        const float d = delta[o3 + t];
+        l2 += d * d;
+        float g = dx0[(y * N + pt) * 9 + t % 3] + coord_c * 2.0f * d;
+        if (sgrad) g += coord_c * sgrad[o3 + t];
+        const float m0 = m[o3 + t], v0 = v[o3 + t];
+        const float mm = __fadd_rn(m0, __fmul_rn(__fsub_rn(g, m0), 1.0f - beta1));
+        const float vv = __fadd_rn(__fmul_rn(v0, beta2), __fmul_rn(1.0f - beta2, __fmul_rn(g, g)));
+        m[o3 + t] = mm;
+        v[o3 + t] = vv;
+        const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2_sqrt), eps);
+        delta[o3 + t] = __fadd_rn(d, __fmul_rn(-step_size, __fdiv_rn(mm, denom)));
+    }
+    for (int o = 32; o >= 1; o >>= 1) l2 += __shfl_xor(l2, o);
+    if (!l2_sum) return;
+    __shared__ float s_l2[4];
+    if ((threadIdx.x & 63) == 0) s_l2[threadIdx.x >> 6] = l2;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(l2_sum + y, (s_l2[0] + s_l2[1]) + (s_l2[2] + s_l2[3]));
+}
+
+// the step's Smooth_xyz / L2_xyz sums (scal rows 3, 4) into rows 5, 6 of the history row, zeroed for the next step - what
+// the latch does for rows 0..2
+__global__ void nu_field_hist_tail_kernel(float *__restrict__ scal, float *__restrict__ hist_step, int G)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * G) return;
+    hist_step[5 * G + t] = scal[3 * G + t];
+    scal[3 * G + t] = 0.0f;
+}
+
+}  // namespace
+
+extern "C" int psg_smooth_knn_xyz_rooms(const float *adv_xyz, int adv_stride, size_t adv_room_stride, const float *ref_xyz,
+                                        int ref_stride, size_t ref_room_stride, int B, int N, int nb, float *dist_sum_rooms,
+                                        float *grad_out, const uint8_t *room_active, int32_t *nn_out, psg_stream stream)
+{
+    PSG_REQUIRE(adv_xyz && ref_xyz && grad_out && adv_xyz != ref_xyz && N > 0 && B > 0 && B <= 65535 && adv_stride >= 3 && ref_stride >= 3,
+                "psg_smooth_knn_xyz_rooms: bad argument");
+    PSG_REQUIRE(nb > 0 && nb <= SM_MAX_NB, "psg_smooth_knn_xyz_rooms: neighbour count %d out of range (1..%d)", nb, SM_MAX_NB);
+    PSG_REQUIRE(N <= 8192, "psg_smooth_knn_xyz_rooms: N=%d exceeds the LDS-resident limit 8192", N);
+    const size_t lds = (size_t)3 * SMX_SUB * ((((N + SMX_SUB - 1) / SMX_SUB + 3) & ~3) + 8) * sizeof(float);
+    const dim3 grid(psg::ceil_div(N, SMX_T / SMX_SUB), B);
+#define PSG_SMOOTH_XYZ_LAUNCH(NBT)                                                                                               \
+    do {                                                                                                                         \
+        if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)smooth_knn_xyz_kernel<NBT>));                        \
+        hipLaunchKernelGGL((smooth_knn_xyz_kernel<NBT>), grid, dim3(SMX_T), lds, (hipStream_t)stream, adv_xyz, adv_stride,       \
+                           adv_room_stride, ref_xyz, ref_stride, ref_room_stride, N, nb, dist_sum_rooms, grad_out, room_active,  \
+                           nn_out);                                                                                              \
+    } while (0)
+    // list length per lane: the two neighbour counts the attacks use (tar_NU 5, NU 10), else 16
+    if (nb <= 5) PSG_SMOOTH_XYZ_LAUNCH(5);
+    else if (nb <= 10) PSG_SMOOTH_XYZ_LAUNCH(10);
+    else PSG_SMOOTH_XYZ_LAUNCH(16);
+#undef PSG_SMOOTH_XYZ_LAUNCH
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_nu_coord_apply_rooms(const float *delta, const float *ori_xyz, const uint8_t *mask_rooms, int B, int N,
+                                        const uint8_t *room_active, float *x0, psg_stream stream)
+{
+    PSG_REQUIRE(delta && ori_xyz && x0 && B > 0 && B <= 65535 && N > 0, "psg_nu_coord_apply_rooms: bad argument");
+    hipLaunchKernelGGL(nu_coord_apply_kernel, dim3(std::min(grid_for((size_t)N * 3), 12), B), dim3(256), 0, (hipStream_t)stream, delta,
+                       ori_xyz, mask_rooms, room_active, x0, N);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_nu_coord_adam_step_rooms(float *delta, float *m, float *v, const uint8_t *mask_rooms, const float *dx0,
+                                            const float *sgrad_xyz, float coord_c, float coord_lr, float beta1, float beta2, float eps,
+                                            int step, int B, int N, const uint8_t *room_active, float *l2_sum_rooms, psg_stream stream)
+{
+    PSG_REQUIRE(delta && m && v && dx0 && B > 0 && B <= 65535 && N > 0 && step >= 1, "psg_nu_coord_adam_step_rooms: bad argument");
+    // torch.optim.Adam (single tensor): step_size = lr / (1 - beta1^t), denom = sqrt(v) / sqrt(1 - beta2^t) + eps
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    const float step_size = (float)((double)coord_lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    hipLaunchKernelGGL(nu_coord_adam_kernel, dim3(std::min(grid_for((size_t)N * 3), 12), B), dim3(256), 0, (hipStream_t)stream, delta, m, v,
+                       mask_rooms, dx0, sgrad_xyz, coord_c, beta1, beta2, eps, step_size, bc2_sqrt, N, room_active, l2_sum_rooms);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+// One whole step of the coordinate-field NU attacks, enqueued on the caller's stream (no graph: the plan is rebuilt from the
+// moved points every step, and its FPS starts change with it).
+extern "C" int psg_pn2_nu_field_step(const psg_nu_field_args *a, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws && a->delta && a->m_xyz && a->v_xyz && a->ori_xyz && a->x0 && a->labels && a->starts && a->logp &&
+                    a->dlogp && a->dx0 && a->sgrad_xyz && a->pred && a->scal && a->hist && a->out && a->active && a->exit_step,
+                "psg_pn2_nu_field_step: null argument");
+    PSG_REQUIRE(a->field == PSG_NU_FIELD_COORD || a->field == PSG_NU_FIELD_BOTH, "psg_pn2_nu_field_step: field %d is neither coord (%d) nor both (%d)",
+                a->field, PSG_NU_FIELD_COORD, PSG_NU_FIELD_BOTH);
+    const bool both = a->field == PSG_NU_FIELD_BOTH;
+    PSG_REQUIRE(!both || (a->w && a->m && a->v && a->ori && a->sgrad && a->nn_state), "psg_pn2_nu_field_step: field both needs the colour state");
+    PSG_REQUIRE(a->G > 0 && a->N > 0 && a->adam_t >= 1 && a->step >= 0, "psg_pn2_nu_field_step: G=%d N=%d adam_t=%d step=%d out of range", a->G,
+                a->N, a->adam_t, a->step);
+    PSG_REQUIRE(a->mode >= 0 && a->mode <= 2 && (a->mode == 0 || (a->mask && a->n_mask)), "psg_pn2_nu_field_step: modes 1 and 2 need mask and n_mask");
+    if (int rc = psg::pn2_full_grad_check(a->model, a->ws, "psg_pn2_nu_field_step")) return rc;
+    const int G = a->G, N = a->N;
+    const int32_t *f_labels = a->use_target ? nullptr : a->labels;
+    const int f_target = a->use_target ? a->target : 0;
+    int rc;
+    if ((rc = psg_nu_coord_apply_rooms(a->delta, a->ori_xyz, a->mask, G, N, a->active, a->x0, stream))) return rc;
+    if (both && (rc = psg_nu_tanh_color_rooms(a->w, a->mask, G, N, a->x0, stream))) return rc;
+    if ((rc = psg_pn2_plan_build(a->ws, a->x0, a->starts, 1, stream))) return rc;
+    if ((rc = psg_pn2_forward(a->model, a->ws, 0, a->x0, a->logp, nullptr, stream))) return rc;
+    if ((rc = psg_nu_f_loss_grad_rooms(a->logp, f_labels, f_target, G, N, PSG_PN2_NUM_CLASSES, a->kappa, a->tsign, a->dlogp, a->scal, a->pred,
+                                       stream)))
+        return rc;
+    if ((rc = psg_pn2_backward_full(a->model, a->ws, 0, a->dlogp, a->dx0, stream))) return rc;
+    if (both) {
+        if ((rc = psg_smooth_knn_rooms(a->x0 + 3, 9, (size_t)N * 9, a->ori, 3, (size_t)N * 3, G, N, a->neighbour, a->scal + G, a->sgrad,
+                                       a->nn_state, a->warm ? 1 : 0, stream)))
+            return rc;
+    }
+    if ((rc = psg_smooth_knn_xyz_rooms(a->x0, 9, (size_t)N * 9, a->ori_xyz, 3, (size_t)N * 3, G, N, a->neighbour, a->scal + 3 * G, a->sgrad_xyz,
+                                       a->active, nullptr, stream)))
+        return rc;
+    if (both) {
+        // (psg_nu_adam_step_rooms serves two rooms and more; one room is the batch-of-one call of the same kernel)
+        rc = G > 1 ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c, a->c, a->lr, a->beta1, a->beta2,
+                                            a->eps, a->adam_t, G, N, a->active, a->scal + 2 * G, stream)
+                   : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c, a->c, a->lr, a->beta1, a->beta2, a->eps,
+                                      a->adam_t, 1, N, a->scal + 2, stream);
+        if (rc) return rc;
+    }
+    if ((rc = psg_nu_coord_adam_step_rooms(a->delta, a->m_xyz, a->v_xyz, a->mask, a->dx0, a->sgrad_xyz, a->coord_c, a->coord_lr, a->beta1,
+                                           a->beta2, a->eps, a->adam_t, G, N, a->active, a->scal + 4 * G, stream)))
+        return rc;
+    if ((rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, 1, N, a->mode,
+                                a->scal, a->hist, a->x0, a->out, a->active, a->exit_step, a->step, stream)))
+        return rc;
+    hipLaunchKernelGGL(nu_field_hist_tail_kernel, dim3(psg::ceil_div(2 * G, 256)), dim3(256), 0, (hipStream_t)stream, a->scal, a->hist, G);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}

@@ -1779,6 +1779,16 @@ extern "C" int psg_pn2_backward_full(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, 
 // Same launches as psg_pn2_backward except at level 0: compact 16-byte rows, the first layer's three colour columns on the vector
 // pipe, one gather thread per point; dx0_out[.][3..5] are written, the other six channels of a row are left untouched.
 namespace psg {
+int pn2_full_grad_check(const psg_pn2_model *m, const psg_pn2_ws *ws, const char *who)
+{
+    PSG_REQUIRE(m && ws, "%s: null model / workspace", who);
+    PSG_REQUIRE(m->arch->id == PSG_PN2_ARCH_SSG && ws->arch->id == PSG_PN2_ARCH_SSG,
+                "%s: the coordinate gradient is implemented for the SSG network only", who);
+    PSG_REQUIRE(m->split[1] && m->split[2] && m->split[3] && m->w1x[1] && m->w1x[2] && m->w1x[3] && !m->split[0] && ws->grel[1] &&
+                    arch_split(*ws->arch, 1),
+                "%s: needs the split first layers of SA levels 1 - 3 (model or workspace created under PSG_PN2_SPLIT=0)", who);
+    return PSG_OK;
+}
 // psg_pn2_forward without the module outputs only ws.activation() reads (the NU loop)
 int pn2_forward_lean(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *x0, float *logp_out, psg_stream stream)
 {
