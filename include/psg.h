@@ -207,7 +207,10 @@ int psg_group_rows_bwd(const float *drows, const int32_t *gidx, int B, int N, in
                        float *dfeat, psg_stream stream);
 /* one shared 1x1 convolution over rows (Conv -> BN(eval) -> ReLU, pointnet_util.py:200-203, 317-319):
  * out = [relu](in . w^T + bias) [* scale + shift], w [M][K]; scale / shift (or NULL): BatchNorm AFTER the ReLU, ResGCN's
- * BasicConv order (torch_nn.py:55-75); mask_out: ReLU bits [rows][ceil(M/32)] words or NULL. */
+ * BasicConv order (torch_nn.py:55-75); mask_out: ReLU bits [rows][ceil(M/32)] words or NULL (written with relu only).
+ * Bit (c & 31) of word c >> 5 of a row is set where the pre-activation of channel c is > 0 (strictly).  Every word of
+ * every row is written; the bits of the last word that lie at channels >= M are written as 0.  Columns >= M of an output
+ * row with ld_out > M are not touched. */
 int psg_pw_mlp_fwd(const float *in, int ld_in, int rows, int K, const float *w, const float *bias, int relu, int M,
                    float *out, int ld_out, uint32_t *mask_out, const float *scale, const float *shift, psg_stream stream);
 /* its input gradient: din = (dout . w) * [ReLU bits of the layer below, or NULL]; wT [K][M] = w transposed. */
@@ -217,7 +220,9 @@ int psg_pw_mlp_bwd(const float *dout, int ld_dout, int rows, int M, const float 
 int psg_apply_relu_bits(float *g, int ld, const uint32_t *bits, const float *scale, int rows, int M, psg_stream stream);
 /* PointNetSetAbstraction.forward after grouping, pointnet_util.py:200-205: n_layers shared layers over the grouped rows
  * [n_groups*K][cin], max over the K samples.  scratch_a/b: [rows][max width]; masks[l]: ReLU bits of layer l (or NULL array);
- * out [n_groups][widths[n-1]], arg: winning sample (first on ties, like torch.max). */
+ * out [n_groups][widths[n-1]], arg: winning sample (first on ties, like torch.max).  arg is a byte, so forward AND
+ * backward require 1 <= K <= 255; both require 1 <= n_layers <= 8 and n_groups * K <= INT_MAX (anything else is
+ * PSG_ERR_ARG before a launch). */
 int psg_sa_mlp_max_fwd(const float *rows_in, int n_groups, int K, int cin, int n_layers, const int *widths,
                        const float *const *w, const float *const *bias, float *scratch_a, float *scratch_b,
                        uint32_t *const *masks, float *out, uint8_t *arg, psg_stream stream);

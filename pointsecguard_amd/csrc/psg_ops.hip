@@ -9,6 +9,7 @@
 // input-gradient transposes of each.  Parameter gradients are not produced: the attack path differentiates w.r.t. the
 // input only (SURVEY.md 3.1 "Backward dataflow actually needed").
 #include <algorithm>
+#include <climits>
 
 #include "psg_common.h"
 #include "psg_gemm.cuh"
@@ -208,6 +209,7 @@ extern "C" int psg_sa_mlp_max_fwd(const float *rows_in, int n_groups, int K, int
 {
     PSG_REQUIRE(rows_in && widths && w && bias && scratch_a && scratch_b && out && arg && n_layers >= 1 && n_layers <= 8 &&
                     K >= 1 && K <= 255, "psg_sa_mlp_max_fwd: bad argument");
+    PSG_REQUIRE(n_groups >= 1 && (long long)n_groups * K <= INT_MAX, "psg_sa_mlp_max_fwd: n_groups * K must fit an int");
     const int rows = n_groups * K;
     const float *cur = rows_in;
     int c = cin;
@@ -230,8 +232,9 @@ extern "C" int psg_sa_mlp_max_bwd(const float *dout, const uint8_t *arg, int n_g
                                   const int *widths, const float *const *wT, const uint32_t *const *masks, float *scratch_a,
                                   float *scratch_b, float *drows_in, psg_stream stream)
 {
-    PSG_REQUIRE(dout && arg && widths && wT && masks && scratch_a && scratch_b && drows_in && n_layers >= 1 && n_layers <= 8,
-                "psg_sa_mlp_max_bwd: bad argument");
+    PSG_REQUIRE(dout && arg && widths && wT && masks && scratch_a && scratch_b && drows_in && n_layers >= 1 && n_layers <= 8 &&
+                    K >= 1 && K <= 255, "psg_sa_mlp_max_bwd: bad argument");    // arg is a byte: the forward's limit on K
+    PSG_REQUIRE(n_groups >= 1 && (long long)n_groups * K <= INT_MAX, "psg_sa_mlp_max_bwd: n_groups * K must fit an int");
     const int rows = n_groups * K;
     const int c_last = widths[n_layers - 1];
     const size_t total = (size_t)rows * c_last;

@@ -160,10 +160,16 @@ def test_gemm_interior_tiles_equal_the_general_path():
     """psg_gemm.cuh stages the operands of INTERIOR tiles (whole tile inside both matrices, 16-byte aligned rows, K a multiple
     of 32) without bounds tests and reads their epilogue terms as float4 (round 4).  The same product through the general
     path - forced by a row stride that is not a multiple of 4, by a ragged K, by M / rows that leave edge tiles - must be
-    bit-identical on the common outputs, ReLU bits included; values are checked against float64."""
+    bit-identical on the common outputs, ReLU bits included; values are checked against float64.  512 x 96 x 256 runs the
+    64 x 64 one-tile-per-wave instantiation (4 x 2 large tiles are fewer than psg_pw_mlp_fwd's 128), 2048 x 64 x 1024 the
+    128 x 128 one (16 x 8 tiles, and still 16 x 8 with M short by 40 or rows short by 3)."""
+    for rows, K, M in ((512, 96, 256), (2048, 64, 1024)):
+        interior_equals_general(rows, K, M)
+
+
+def interior_equals_general(rows, K, M):
     from pointsecguard_amd import _lib, runtime
     rng = np.random.default_rng(42)
-    rows, K, M = 512, 96, 256
     x = rng.standard_normal((rows, K)).astype(np.float32)
     w = (rng.standard_normal((M, K)) * 0.2).astype(np.float32)
     b = rng.standard_normal(M).astype(np.float32)
@@ -191,6 +197,8 @@ def test_gemm_interior_tiles_equal_the_general_path():
     m2 = M - 40                                                                 # ragged M: the last column tile is an edge tile
     got, bits = run(x, K, rows, K, m2, dw[:m2].contiguous())
     assert np.array_equal(got, ref[:, :m2])
+    assert np.array_equal(bits[:, :m2 // 32], ref_bits[:, :m2 // 32])           # the whole words; the partial last one below
+    assert np.array_equal(bits[:, m2 // 32].view(np.uint32), ref_bits[:, m2 // 32].view(np.uint32) & np.uint32((1 << (m2 % 32)) - 1))
     # ragged K (general path) against the interior path on the zero-padded operands
     k2 = K - 5
     w2 = dw[:, :k2].contiguous()
