@@ -397,6 +397,28 @@ int psg_nu_adam_step_rooms(float *w, float *m, float *v, const uint8_t *mask_roo
                            float beta1, float beta2, float eps, int step, int B, int N, const uint8_t *room_active,
                            float *l2_sum_rooms, psg_stream stream);
 
+/* The ResGCN f-loss (colper.py:108-113, tcolper.py:145-163) for G INDEPENDENT one-room attacks in one launch: per room what
+ * psg_gcn_f_loss_grad does for a batch of one with that room's mask row (mask_rooms [G][N], nullable in mode 0) - the same
+ * decisions (torch.max's first maximum, the zeroed slots taking part), dlogits_out [G][N][n_cls] and pred_out [G][N]
+ * bit for bit.  Adds sum f of room g to f_sum_rooms[g] with one float atomic per workgroup. */
+int psg_gcn_f_loss_grad_rooms(const float *logits, const int32_t *labels, int target, const uint8_t *mask_rooms, int mode,
+                              int G, int N, int n_cls, float kappa, float tsign, float scale, float *dlogits_out,
+                              float *f_sum_rooms, int32_t *pred_out, psg_stream stream);
+
+/* smooth(adv, adv) of the ResGCN NU attacks (colper.py:115-120, tcolper.py:165-170) for G rooms: every colour's nb nearest
+ * colours of its OWN room, the gradient flowing through both ends of every pair.  Strided rows and per-room strides in
+ * floats, nb <= 16, N <= 8192; dist_sum_rooms [G] is added to, grad_out [G][N][3] written, a room with room_active[g] == 0
+ * (nullable = all active) is not touched (sum, gradient, lists).  nn_out (nullable; the call then keeps the lists in a
+ * scratch buffer of its own): int32 [G][N][nb], every colour's neighbours in rank order (with fewer than nb colours in the
+ * room the missing ranks stay as they are).  Pair values are psg_smooth_knn's: d^2 = fma(-2 a.z, r.z, fma(-2 a.y, r.y,
+ * -2 a.x * r.x)) + |a|^2 + |r|^2 clamped at 0 (the cdist expansion), neighbours strictly by (distance, index) - the one-room
+ * kernel can order references at EXACTLY the same distance otherwise, DESIGN.md section 5m -, a pair at d == 0 adds exactly zero, u = (a - r) / d goes with + to the query and with - to the neighbour.  No float atomics on the
+ * gradient and a FIXED order: a colour's own terms in ascending rank, then the terms it receives as a neighbour in
+ * ascending index of the colour they come from.  Two launches for all rooms. */
+int psg_smooth_knn_sym_rooms(const float *adv_color, int adv_stride, size_t adv_room_stride, int G, int N, int nb,
+                             float *dist_sum_rooms, float *grad_out, const uint8_t *room_active, int32_t *nn_out,
+                             psg_stream stream);
+
 /* Per-step statistics and exit latch of the NU attacks: what the reference evaluates on the host after every optimiser
  * step - nontarget.py:87,95-96 (`correct / 4096 < 1 / 13`), target.py:105-121 (`target_acc` > 0.9, or < 1 / 13 for the
  * untargeted goal) - for G attacks of `rows` batch rows each (rows = B: one call on a batch; rows = 1: rooms in lockstep).
@@ -669,6 +691,43 @@ int psg_gcn_set_graphs(psg_gcn_ws *ws, const int32_t *nbr, psg_stream stream);
 /* parity-test read-back: neighbour table of EdgeConv `block` [batch][n_point][16]; block outputs [batch][n_point][64*n_blocks] */
 const int32_t *psg_gcn_edge_ptr(const psg_gcn_ws *ws, int block);
 const float *psg_gcn_feats_ptr(const psg_gcn_ws *ws);
+
+/* A WINDOW of consecutive optimiser steps of the ResGCN NU_attack / tar_NU_attack (colper.py:62-95, tcolper.py:85-132) for
+ * G one-room attacks in lockstep (rooms form only: the workspace is for G rooms of N points), enqueued by ONE call.  Per
+ * step: psg_nu_tanh_color_rooms, psg_gcn_forward, psg_gcn_f_loss_grad_rooms (scale c_f), psg_gcn_backward,
+ * psg_smooth_knn_sym_rooms, psg_nu_adam_step_rooms (c_smooth, c_l2; psg_nu_adam_step at G = 1: the same arithmetic),
+ * psg_nu_step_latch (rows = 1) - cost = c_f f + c_smooth Smooth + c_l2 L2, (c_f, c_l2) = (c, 1) for NU_attack and (1, c)
+ * for tar_NU_attack.  Graphs set by psg_gcn_set_graphs are used.  The fields are those of psg_pointnet_nu_window_args;
+ * `logits` / `dlogits` [G][N][13] are scratch.  The reference's host work sits between windows. */
+typedef struct psg_gcn_nu_window_args {
+    psg_gcn_model *model;
+    psg_gcn_ws *ws;              /* created for G rooms of N points */
+    int step0, n_steps;
+    int G, N, mode;              /* mode: see psg_nu_step_latch */
+    int use_target, target;
+    int neighbour;
+    int adam_t0;
+    float kappa, tsign, c_f, c_smooth, c_l2, lr, beta1, beta2, eps;
+    float *w, *m, *v;            /* [G][N][3] */
+    const uint8_t *mask;         /* [G][N], nullable for NU_attack */
+    const int32_t *n_mask;       /* [G], modes 1 and 2 */
+    float *x0;                   /* [G][N][9] */
+    const float *ori;            /* [G][N][3] */
+    const int32_t *labels;       /* [G][N] */
+    float *logits, *dlogits, *dx0; /* [G][N][13], [..][13], [..][9] scratch */
+    float *sgrad;                /* [G][N][3] */
+    int32_t *pred;               /* [G][N] */
+    float *scal;                 /* [3][G], zero before the first window */
+    int32_t *nn_state;           /* [G][N][neighbour] */
+    float *hist;                 /* history rows [5][G] of the window's steps, row of step0 first */
+    float *out;                  /* [G][9][N] */
+    uint8_t *active;             /* [G] */
+    int32_t *exit_step;          /* [G] */
+} psg_gcn_nu_window_args;
+/* `graph` as for psg_pn2_nu_window (first window of a shape eager, second captured, later ones replayed, the step constants
+ * read from a device row); the captured sequence is a single chain on `stream`.  A failed capture is counted in
+ * psg_nu_graph_stats, not retried, and the window runs eagerly; while psg_gcn_prof_enable is on no graph is used. */
+int psg_gcn_nu_window(const psg_gcn_nu_window_args *args, psg_nu_graph *graph, psg_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * RandLA-Net input pipeline (first piece): exact k-nearest neighbours of 3-D points.

@@ -86,6 +86,8 @@ SIGNATURES = {
     "psg_nu_f_loss_grad": (ci, [vp, vp, ci, ci, ci, cf, cf, vp, vp, vp, vp]),
     "psg_gcn_f_loss_grad": (ci, [vp, vp, ci, vp, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp]),
     "psg_smooth_knn": (ci, [vp, ci, vp, ci, ci, ci, vp, vp, vp]),
+    "psg_gcn_f_loss_grad_rooms": (ci, [vp, vp, ci, vp, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp]),
+    "psg_smooth_knn_sym_rooms": (ci, [vp, ci, ctypes.c_size_t, ci, ci, ci, vp, vp, vp, vp, vp]),
     "psg_nu_adam_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, cf, ci, ci, ci, vp, vp]),
     "psg_pn2_nu_window": (ci, [vp, vp, vp]),
     "psg_nu_graph_create": (ci, [ctypes.POINTER(vp)]),
@@ -121,6 +123,7 @@ SIGNATURES = {
     "psg_gcn_set_graphs": (ci, [vp, vp, vp]),
     "psg_gcn_edge_ptr": (vp, [vp, ci]),
     "psg_gcn_feats_ptr": (vp, [vp]),
+    "psg_gcn_nu_window": (ci, [vp, vp, vp]),
     "psg_knn_points": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
     "psg_rla_sampler_create": (ci, [vp, vp, vp, ci, ctypes.POINTER(vp)]),
     "psg_rla_sampler_destroy": (ci, [vp]),
@@ -173,6 +176,15 @@ class PointnetNuWindowArgs(ctypes.Structure):
                                    "adam_t0", "fused_head")] +
                 [(n, cf) for n in ("kappa", "tsign", "c_smooth", "c_l2", "lr", "beta1", "beta2", "eps")] +
                 [(n, vp) for n in ("w", "m", "v", "mask", "n_mask", "x0", "ori", "labels", "logp", "dlogp", "dx0", "sgrad", "pred",
+                                   "scal", "nn_state", "hist", "out", "active", "exit_step")])
+
+
+class GcnNuWindowArgs(ctypes.Structure):
+    """psg_gcn_nu_window_args of include/psg.h, field for field."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("step0", "n_steps", "G", "N", "mode", "use_target", "target", "neighbour", "adam_t0")] +
+                [(n, cf) for n in ("kappa", "tsign", "c_f", "c_smooth", "c_l2", "lr", "beta1", "beta2", "eps")] +
+                [(n, vp) for n in ("w", "m", "v", "mask", "n_mask", "x0", "ori", "labels", "logits", "dlogits", "dx0", "sgrad", "pred",
                                    "scal", "nn_state", "hist", "out", "active", "exit_step")])
 
 

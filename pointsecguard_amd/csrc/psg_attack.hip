@@ -439,51 +439,32 @@ __global__ void gcn_f_loss_grad_kernel(const float *__restrict__ z, const int32_
 {
     int r = blockIdx.x * blockDim.x + threadIdx.x;
     float fval = 0.0f;
-    if (r < rows) {
-        const float *zr = z + (size_t)r * n_cls;
-        float v[MAXC];
-        float m = -INFINITY;
-        int am = 0;
-        for (int c = 0; c < n_cls; ++c) {
-            v[c] = zr[c];
-            if (v[c] > m) { m = v[c]; am = c; }
-        }
-        if (pred) pred[r] = am;
-        float *g = dz + (size_t)r * n_cls;
-        for (int c = 0; c < n_cls; ++c) g[c] = 0.0f;
-        const bool counted = mode == 0 || (r < N && (!mask || mask[r]));
-        if (counted) {
-            const int y = (mode == 2 || !labels) ? target : labels[r];
-            // the zeroed slot of the true class takes part in the max, and torch.max returns its FIRST maximum: a class
-            // at exactly 0 (all others <= 0) takes the gradient when it stands before the true class, not after it
-            float oth = -INFINITY;
-            int oi = -1;
-            for (int c = 0; c < n_cls; ++c) {
-                const float s = c == y ? 0.0f : v[c];
-                if (s > oth) { oth = s; oi = c == y ? -1 : c; }
-            }
-            float own = v[y];
-            bool own_live = true;
-            // mode 0: max(onehot * z) - the other slots hold 0; a true-class logit of exactly 0 is the first maximum only in slot 0
-            if (mode == 0 && !(own > 0.0f)) { own_live = own == 0.0f && y == 0; own = 0.0f; }
-            const float jv = mode == 2 ? oth : own, iv = mode == 2 ? own : oth;
-            const float val = tsign * (jv - iv);
-            const bool pass = val >= -kappa;
-            fval = pass ? val : -kappa;
-            if (pass) {
-                const float gs = tsign * scale;
-                if (mode == 2) {
-                    if (oi >= 0) g[oi] += gs;
-                    g[y] -= gs;
-                } else {
-                    if (own_live) g[y] += gs;
-                    if (oi >= 0) g[oi] -= gs;
-                }
-            }
-        }
-    }
+#include "psg_gcn_f_loss_row.cuh"
     for (int o = 32; o >= 1; o >>= 1) fval += __shfl_xor(fval, o);
     if ((threadIdx.x & 63) == 0 && f_sum) atomicAdd(f_sum, fval);
+}
+
+// The same rows for G one-room attacks in lockstep (psg_gcn_f_loss_grad_rooms): blockIdx.y = room, every room under its own
+// mask row - what the kernel above does for a batch of one.  One atomic per workgroup into the room's sum.
+__global__ __launch_bounds__(256) void gcn_f_loss_grad_rooms_kernel(const float *__restrict__ z, const int32_t *__restrict__ labels,
+                                                                     int target, const uint8_t *__restrict__ mask, int mode, int N,
+                                                                     int n_cls, float kappa, float tsign, float scale,
+                                                                     float *__restrict__ dz, float *__restrict__ f_sum,
+                                                                     int32_t *__restrict__ pred)
+{
+    const size_t base = (size_t)blockIdx.y * N;
+    z += base * n_cls; dz += base * n_cls;
+    if (pred) pred += base;
+    if (labels) labels += base;
+    if (mask) mask += base;
+    const int rows = N, r = blockIdx.x * blockDim.x + threadIdx.x;
+    float fval = 0.0f;
+#include "psg_gcn_f_loss_row.cuh"
+    for (int o = 32; o >= 1; o >>= 1) fval += __shfl_xor(fval, o);
+    __shared__ float s_part[4];
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = fval;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(f_sum + blockIdx.y, (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]));
 }
 
 // Smooth loss (nontarget.py:131-135): for every adversarial colour of a room the `nb` smallest Euclidean distances to the
@@ -532,151 +513,112 @@ __global__ __launch_bounds__(SM_T) void smooth_knn_kernel(const float *__restric
                                                           size_t adv_room_stride, size_t ref_room_stride,
                                                           int32_t *__restrict__ nn_io, int have_prev)
 {
-    // blockIdx.y = room of a lockstep batch (psg_smooth_knn_rooms; a single launch of the one-room entry has one slice)
+    // Equal distances INSIDE one lane's list: the insertion below moves a displaced entry past the entries of equal distance
+    // behind it (the compare is strict for the carried entry too), so references at exactly the same distance from a query can
+    // leave a lane in descending index order - and, with a full list, the lower index can be the one that falls out.  Between
+    // lanes the merge is by (distance, index).  The results of the PointNet / PointNet++ NU loops and of the one-room ResGCN
+    // loop are pinned with this behaviour, so it stays; smooth_knn_sym_own_kernel runs the same text with the stable insertion.
+    constexpr bool SM_STABLE_TIES = false;
+#include "psg_smooth_knn_body.cuh"
+}
+
+// ---- smooth(adv, adv) of the ResGCN NU attacks for G rooms in lockstep, WITHOUT float atomics on the gradient
+// (psg_smooth_knn_sym_rooms; colper.py:115-120).  Two launches:
+//   1. the scan above with the room's own colours as references, one-sided: grad[i] = sum over i's neighbours in ascending
+//      rank of u(i, j) = (a_i - a_j) / d(i, j), the lists to nn, the distances to the room's sum.  A room that has left its
+//      loop is skipped.
+//   2. smooth_sym_incoming_kernel: grad[i] -= u(k, i) for every k that holds i among its neighbours, in ascending k.
+// The second pass finds those k without inverse lists (at nb = 10, N = 4096 the flat lists alone are 160 KB: a room's would
+// not fit beside anything in LDS, and in memory they need a counting pass, a scan and a sort): colour i is a neighbour of
+// k exactly when (d(k, i), i) <= (d(k, j*), j*) for k's LAST neighbour j* - the selection is a total order by (distance,
+// index) - so every workgroup stages each k's colour and that key (one gather per k) in 24-byte LDS slots, 2048 k at a
+// time, and a colour's 16 lanes walk the k in ascending order 16 at a time, evaluating d(k, i) with k in the query's role
+// exactly as pass 1 did (the expansion is not symmetric in fp32).  Hits are rare (nb per N), the wave branches on a ballot.
+template <int NBT, int SM_SUB>
+__global__ __launch_bounds__(SM_T) void smooth_knn_sym_own_kernel(const float *__restrict__ adv, int adv_stride, int N, int nb,
+                                                                  float *__restrict__ dist_sum, float *__restrict__ grad,
+                                                                  size_t adv_room_stride, int32_t *__restrict__ nn_io,
+                                                                  const uint8_t *__restrict__ room_active)
+{
+    if (room_active && !room_active[blockIdx.y]) return;
+    // one-sided, the room's own colours as references, no warm start; equal distances strictly by index (see above)
+    constexpr bool SM_STABLE_TIES = true;
+    const float *ref = adv;
+    const int ref_stride = adv_stride, symmetric = 0, have_prev = 0;
+    const size_t ref_room_stride = adv_room_stride;
+#include "psg_smooth_knn_body.cuh"
+}
+
+constexpr int SI_T = 1024;                  // threads of the second pass
+constexpr int SI_SUB = 16;                  // lanes per colour
+constexpr int SI_TILE = 2048;               // k staged at a time: 2048 x (16 + 8) bytes = 48 KB
+
+__global__ __launch_bounds__(SI_T) void smooth_sym_incoming_kernel(const float *__restrict__ adv, int adv_stride, size_t adv_room_stride,
+                                                                   int N, int nb, const int32_t *__restrict__ nn,
+                                                                   float *__restrict__ grad, const uint8_t *__restrict__ room_active)
+{
+    if (room_active && !room_active[blockIdx.y]) return;
     adv += blockIdx.y * adv_room_stride;
-    ref += blockIdx.y * ref_room_stride;
+    nn += (size_t)blockIdx.y * N * nb;
     grad += (size_t)blockIdx.y * N * 3;
-    if (dist_sum) dist_sum += blockIdx.y;
-    if (nn_io) nn_io += (size_t)blockIdx.y * N * nb;
-    constexpr int SM_QPB = SM_T / SM_SUB;                   // queries per workgroup
-    // Reference colours in LDS as four planes x, y, z, |r|^2, each split into SUB runs: run s holds the references
-    // s, s + SUB, s + 2 SUB, .. (the ones lane s of a query scans) contiguously, so one ds_read_b128 per plane brings four of
-    // them and two references share every instruction of the distance arithmetic on the packed-fp32 pipe.  Runs are 8 floats
-    // apart beyond their length (the SUB lanes of a query read different runs at the same offset: different banks); slots
-    // past N hold |r|^2 = inf and are never admitted.
-    const int tps = ((N + SM_SUB - 1) / SM_SUB + 3) & ~3, run = tps + 8;
-    extern __shared__ float s_pl[];
-    float *s_x = s_pl, *s_y = s_pl + SM_SUB * run, *s_z = s_pl + 2 * SM_SUB * run, *s_q = s_pl + 3 * SM_SUB * run;
-    for (int p = threadIdx.x; p < SM_SUB * tps; p += SM_T) {
-        const int sr = p / tps, t = p - sr * tps, i = sr + SM_SUB * t;
-        float x = 0.f, y = 0.f, z = 0.f, q = INFINITY;
-        if (i < N) {
-            x = ref[(size_t)i * ref_stride]; y = ref[(size_t)i * ref_stride + 1]; z = ref[(size_t)i * ref_stride + 2];
-            q = x * x + y * y + z * z;
-        }
-        s_x[sr * run + t] = x; s_y[sr * run + t] = y; s_z[sr * run + t] = z; s_q[sr * run + t] = q;
+    __shared__ float4 s_k[SI_TILE];         // {-2 x, -2 y, -2 z, |a|^2} of colour k, as the query of pass 1 holds them
+    __shared__ float2 s_key[SI_TILE];       // k's last neighbour: {clamped d^2, index bits}; d^2 = -1: no such k
+    const int sub = threadIdx.x % SI_SUB;
+    const int i = blockIdx.x * (SI_T / SI_SUB) + threadIdx.x / SI_SUB;
+    const int last = (nb < N ? nb : N) - 1;                     // rank of the last neighbour every colour holds
+    float rx = 0.f, ry = 0.f, rz = 0.f, rq = 0.f;
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    if (i < N) {
+        rx = adv[(size_t)i * adv_stride]; ry = adv[(size_t)i * adv_stride + 1]; rz = adv[(size_t)i * adv_stride + 2];
+        rq = rx * rx + ry * ry + rz * rz;                       // |r|^2 as pass 1 stages it
+        gx = grad[(size_t)i * 3]; gy = grad[(size_t)i * 3 + 1]; gz = grad[(size_t)i * 3 + 2];   // own terms (pass 1)
     }
-    __syncthreads();
-    const int ql = threadIdx.x / SM_SUB, sub = threadIdx.x % SM_SUB;
-    const int i = blockIdx.x * SM_QPB + ql;
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    if (i < N) { ax = adv[(size_t)i * adv_stride]; ay = adv[(size_t)i * adv_stride + 1]; az = adv[(size_t)i * adv_stride + 2]; }
-    float bd[NBT];
-    int bi[NBT];
-#pragma unroll
-    for (int t = 0; t < NBT; ++t) { bd[t] = INFINITY; bi[t] = 0x7FFFFFFF; }
-    // torch.cdist evaluates |a|^2 + |r|^2 - 2 a.r through a matmul (euclid_dist, clamp_min(0), sqrt): the
-    // cancellation noise (~1e-7 in d^2, ~3e-4 in d) is part of the reference's loss surface -- it is what
-    // keeps the gradient of a colour that has barely moved from its original near 0 instead of a unit
-    // vector of rounding noise -- so the same expansion is used here (not bit-identical to MKL's order).
-    const float asq = ax * ax + ay * ay + az * az;
-    const sm_v2f m2x = {-2.0f * ax, -2.0f * ax}, m2y = {-2.0f * ay, -2.0f * ay}, m2z = {-2.0f * az, -2.0f * az}, asq2 = {asq, asq};
-    // thr: a candidate is looked at only below min(this lane's worst kept distance, the nb-th smallest distance the
-    // query's SUB lanes hold TOGETHER at the last refresh).  The common bound is what keeps the insertion branch rare:
-    // a wave serves 64 / SUB queries, it runs the insertion network whenever ANY lane passes, and a lane's own
-    // list only tightens as NBT / n.  Exact: everything kept at a refresh has a lower index than anything scanned later,
-    // so a later candidate at exactly the bound loses the (distance, index) tie and '<' drops nothing that is wanted.
-    // (The filter compares the distance BEFORE its clamp at 0: a negative one passes a positive bound either way, and
-    // against a bound of 0 it only enters the insertion code, where the clamped value is refused like every other 0.)
-    float thr = i < N ? INFINITY : -INFINITY;
-    if (nn_io && have_prev) {
-        // The optimiser moves a colour a little per step, so the nb references that were nearest one step ago are a sharp
-        // and RIGOROUS start: the largest of their current distances bounds the nb-th smallest distance from above
-        // (they are nb distinct references), and only the handful of references inside that ball ever reach the
-        // insertion code.  The bound is taken a few ulps up so that the reference defining it passes the '<'.
-        float m = -1.0f;
-        bool ok = i < N;
-        for (int t = sub; t < nb; t += SM_SUB) {
-            const int jn = ok ? nn_io[(size_t)i * nb + t] : 0;
-            if (jn < 0 || jn >= N) { ok = false; break; }
-            const int pos = (jn % SM_SUB) * run + jn / SM_SUB;
-            float d2 = __fmaf_rn(m2z[0], s_z[pos], __fmaf_rn(m2y[0], s_y[pos], __fmul_rn(m2x[0], s_x[pos])));
-            d2 = __fadd_rn(__fadd_rn(d2, asq), s_q[pos]);
-            m = fmaxf(m, fmaxf(d2, 0.0f));
-        }
-        unsigned bad = ok ? 0u : 1u;
-#pragma unroll
-        for (int o = 1; o < SM_SUB; o <<= 1) {
-            m = fmaxf(m, __shfl_xor(m, o));
-            bad |= (unsigned)__shfl_xor((int)bad, o);
-        }
-        if (!bad && i < N && m >= 0.0f) thr = m * 1.000001f + 1e-30f;
-    }
-    const float *px = s_x + sub * run, *py = s_y + sub * run, *pz = s_z + sub * run, *pq = s_q + sub * run;
-    for (int t0 = 0; t0 < tps; t0 += SM_REFRESH) {
-        const int t1 = t0 + SM_REFRESH < tps ? t0 + SM_REFRESH : tps;
-        for (int t = t0; t < t1; t += 4) {
-            const float4 X = *(const float4 *)(px + t), Y = *(const float4 *)(py + t), Z = *(const float4 *)(pz + t),
-                         Q = *(const float4 *)(pq + t);
-            // two references per instruction; per component exactly fma(m2z, z, fma(m2y, y, m2x * x)) then (+ asq) + q
-            sm_v2f da = m2x * sm_v2f{X.x, X.y}, db = m2x * sm_v2f{X.z, X.w};
-            da = __builtin_elementwise_fma(m2y, sm_v2f{Y.x, Y.y}, da); db = __builtin_elementwise_fma(m2y, sm_v2f{Y.z, Y.w}, db);
-            da = __builtin_elementwise_fma(m2z, sm_v2f{Z.x, Z.y}, da); db = __builtin_elementwise_fma(m2z, sm_v2f{Z.z, Z.w}, db);
-            da = (da + asq2) + sm_v2f{Q.x, Q.y};
-            db = (db + asq2) + sm_v2f{Q.z, Q.w};
-            const float d2[4] = {da[0], da[1], db[0], db[1]};
-            if (fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3])) < thr) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (d2[u] < thr) {
-                        float cd = fmaxf(d2[u], 0.0f);
-                        int ci = sub + SM_SUB * (t + u);
-#pragma unroll
-                        for (int k = 0; k < NBT; ++k) {   // sorted insertion with static indexing (arrays stay in registers)
-                            if (cd < bd[k]) {
-                                float td = bd[k]; int ti = bi[k];
-                                bd[k] = cd; bi[k] = ci;
-                                cd = td; ci = ti;
-                            }
-                        }
-                        thr = fminf(thr, bd[NBT - 1]);
-                    }
+    for (int k0 = 0; k0 < N; k0 += SI_TILE) {
+        if (k0) __syncthreads();
+        for (int t = threadIdx.x; t < SI_TILE; t += SI_T) {
+            const int k = k0 + t;
+            float4 q = {0.f, 0.f, 0.f, 0.f};
+            float2 key = {-1.0f, 0.0f};
+            if (k < N) {
+                const float ax = adv[(size_t)k * adv_stride], ay = adv[(size_t)k * adv_stride + 1], az = adv[(size_t)k * adv_stride + 2];
+                q = float4{-2.0f * ax, -2.0f * ay, -2.0f * az, ax * ax + ay * ay + az * az};
+                const int j = nn[(size_t)k * nb + last];
+                if (j >= 0 && j < N) {
+                    const float jx = adv[(size_t)j * adv_stride], jy = adv[(size_t)j * adv_stride + 1], jz = adv[(size_t)j * adv_stride + 2];
+                    float d2 = __fmaf_rn(q.z, jz, __fmaf_rn(q.y, jy, __fmul_rn(q.x, jx)));
+                    d2 = __fadd_rn(__fadd_rn(d2, q.w), jx * jx + jy * jy + jz * jz);
+                    key = float2{fmaxf(d2, 0.0f), __int_as_float(j)};
                 }
             }
+            s_k[t] = q;
+            s_key[t] = key;
         }
-        if (t1 < tps) {   // another chunk follows (uniform over the workgroup)
-            float cdist[NBT];
-            int cidx[NBT];
-#pragma unroll
-            for (int t = 0; t < NBT; ++t) { cdist[t] = bd[t]; cidx[t] = bi[t]; }
-            float kth = INFINITY;
-            int kidx;
-            for (int t = 0; t < nb; ++t) smooth_pop_min<NBT, SM_SUB>(cdist, cidx, kth, kidx);
-            thr = fminf(thr, kth);
-        }
-    }
-    // SUB-way merge: nb times the smallest head by (distance, index); every lane of the query follows the same sequence
-    float local = 0.0f, gx = 0.f, gy = 0.f, gz = 0.f;
-    for (int t = 0; t < nb; ++t) {
-        float best;
-        int bidx;
-        smooth_pop_min<NBT, SM_SUB>(bd, bi, best, bidx);
-        if (bidx == 0x7FFFFFFF) break;   // fewer than nb references (uniform over the query's lanes)
-        if (sub == 0 && i < N) {
-            if (nn_io) nn_io[(size_t)i * nb + t] = bidx;          // next step's start
-            const float d = sqrtf(best);
-            local += d;
-            if (d > 0.0f) {
-                const int pos = (bidx % SM_SUB) * run + bidx / SM_SUB;
-                const float ux = (ax - s_x[pos]) / d, uy = (ay - s_y[pos]) / d, uz = (az - s_z[pos]) / d;
-                gx += ux; gy += uy; gz += uz;
-                if (symmetric) {  // the neighbour is an adversarial colour too: it receives the opposite pull
-                    atomicAdd(grad + (size_t)bidx * 3, -ux);
-                    atomicAdd(grad + (size_t)bidx * 3 + 1, -uy);
-                    atomicAdd(grad + (size_t)bidx * 3 + 2, -uz);
-                }
+        __syncthreads();
+        const int nt = min(SI_TILE, N - k0);
+        for (int t = sub; t < nt + sub; t += SI_SUB) {          // (the 16 lanes of a colour stay together: t - sub < nt)
+            const bool in = t < nt && i < N;
+            const float4 q = s_k[in ? t : 0];
+            const float2 key = s_key[in ? t : 0];
+            float d2 = __fmaf_rn(q.z, rz, __fmaf_rn(q.y, ry, __fmul_rn(q.x, rx)));
+            d2 = fmaxf(__fadd_rn(__fadd_rn(d2, q.w), rq), 0.0f);
+            const bool hit = in && (d2 < key.x || (d2 == key.x && i <= __float_as_int(key.y)));
+            const unsigned long long bal = __ballot(hit);
+            if (bal == 0ull) continue;                           // (uniform over the wave)
+            float ux = 0.f, uy = 0.f, uz = 0.f;
+            if (hit) {
+                const float d = sqrtf(d2);
+                if (d > 0.0f) { ux = (-0.5f * q.x - rx) / d; uy = (-0.5f * q.y - ry) / d; uz = (-0.5f * q.z - rz) / d; }
+            }
+            // the hits of this colour's 16 lanes, in lane (= ascending k) order; the lanes of a colour see the same bits
+            unsigned mine = (unsigned)(bal >> (threadIdx.x & 48)) & 0xFFFFu;
+            while (mine) {
+                const int s = __ffs(mine) - 1;
+                mine &= mine - 1;
+                gx -= __shfl(ux, s, SI_SUB); gy -= __shfl(uy, s, SI_SUB); gz -= __shfl(uz, s, SI_SUB);
             }
         }
     }
-    if (sub == 0 && i < N) {
-        if (symmetric) {
-            atomicAdd(grad + (size_t)i * 3, gx); atomicAdd(grad + (size_t)i * 3 + 1, gy); atomicAdd(grad + (size_t)i * 3 + 2, gz);
-        } else {
-            grad[(size_t)i * 3] = gx; grad[(size_t)i * 3 + 1] = gy; grad[(size_t)i * 3 + 2] = gz;
-        }
-    }
-    for (int o = 32; o >= 1; o >>= 1) local += __shfl_xor(local, o);
-    if ((threadIdx.x & 63) == 0 && dist_sum) atomicAdd(dist_sum, local);
+    if (sub == 0 && i < N) { grad[(size_t)i * 3] = gx; grad[(size_t)i * 3 + 1] = gy; grad[(size_t)i * 3 + 2] = gz; }
 }
 
 // Gradient assembly + torch.optim.Adam single-tensor update on w (fp32, torch's operation order).
@@ -891,6 +833,20 @@ extern "C" int psg_gcn_f_loss_grad(const float *logits, const int32_t *labels, i
     return PSG_OK;
 }
 
+extern "C" int psg_gcn_f_loss_grad_rooms(const float *logits, const int32_t *labels, int target, const uint8_t *mask_rooms, int mode,
+                                         int G, int N, int n_cls, float kappa, float tsign, float scale, float *dlogits_out,
+                                         float *f_sum_rooms, int32_t *pred_out, psg_stream stream)
+{
+    PSG_REQUIRE(logits && dlogits_out && f_sum_rooms && G > 0 && G <= 65535 && N > 0, "psg_gcn_f_loss_grad_rooms: bad argument");
+    PSG_REQUIRE(mode >= 0 && mode <= 2, "psg_gcn_f_loss_grad_rooms: mode %d out of range", mode);
+    PSG_REQUIRE(n_cls > 1 && n_cls <= MAXC, "psg_gcn_f_loss_grad_rooms: n_cls=%d out of range", n_cls);
+    PSG_REQUIRE((mode != 2 && labels) || (target >= 0 && target < n_cls), "psg_gcn_f_loss_grad_rooms: labels / target missing");
+    hipLaunchKernelGGL(gcn_f_loss_grad_rooms_kernel, dim3(psg::ceil_div(N, 256), G), dim3(256), 0, (hipStream_t)stream, logits, labels,
+                       target, mask_rooms, mode, N, n_cls, kappa, tsign, scale, dlogits_out, f_sum_rooms, pred_out);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
 static int smooth_knn_launch(const float *adv_color, int adv_stride, size_t adv_room_stride, const float *ref_color, int ref_stride,
                              size_t ref_room_stride, int B, int N, int nb, float *dist_sum, float *grad_out, psg_stream stream,
                              int32_t *nn_io = nullptr, int have_prev = 0)
@@ -942,6 +898,58 @@ extern "C" int psg_smooth_knn_rooms(const float *adv_color, int adv_stride, size
     PSG_REQUIRE(adv_color != ref_color, "psg_smooth_knn_rooms: the symmetric variant is one room at a time");
     return smooth_knn_launch(adv_color, adv_stride, adv_room_stride, ref_color, ref_stride, ref_room_stride, B, N, nb,
                              dist_sum_rooms, grad_out, stream, nn_state, nn_state ? have_prev : 0);
+}
+
+// smooth(adv, adv) for G rooms without float atomics on the gradient: see smooth_knn_sym_own_kernel.  The lists the second
+// pass reads go to nn_out, or - the caller wants none - to a scratch buffer this host thread keeps and grows (never inside a
+// stream capture: the NU windows always pass their lists).
+extern "C" int psg_smooth_knn_sym_rooms(const float *adv_color, int adv_stride, size_t adv_room_stride, int G, int N, int nb,
+                                        float *dist_sum_rooms, float *grad_out, const uint8_t *room_active, int32_t *nn_out,
+                                        psg_stream stream)
+{
+    PSG_REQUIRE(adv_color && grad_out && dist_sum_rooms && N > 0 && G > 0 && G <= 65535 && adv_stride >= 3,
+                "psg_smooth_knn_sym_rooms: bad argument");
+    PSG_REQUIRE(nb > 0 && nb <= SM_MAX_NB, "psg_smooth_knn_sym_rooms: neighbour count %d out of range (1..%d)", nb, SM_MAX_NB);
+    PSG_REQUIRE(N <= 8192, "psg_smooth_knn_sym_rooms: N=%d exceeds the LDS-resident limit 8192", N);
+    hipStream_t st = (hipStream_t)stream;
+    if (!nn_out) {
+        static thread_local int32_t *scratch = nullptr;
+        static thread_local size_t scratch_n = 0;
+        const size_t need = (size_t)G * N * nb;
+        if (need > scratch_n) {
+            PSG_CHECK_HIP(hipStreamSynchronize(st));            // (launches that still read the old block)
+            if (scratch) (void)hipFree(scratch);
+            scratch = nullptr; scratch_n = 0;
+            PSG_CHECK_HIP(hipMalloc((void **)&scratch, need * sizeof(int32_t)));
+            scratch_n = need;
+        }
+        nn_out = scratch;
+    }
+    const bool wide = (size_t)G * psg::ceil_div(N, SM_T / 4) >= 256;   // as smooth_knn_launch
+    const int sub = wide ? 4 : 16;
+    const size_t lds = (size_t)4 * sub * ((((N + sub - 1) / sub + 3) & ~3) + 8) * sizeof(float);
+    const dim3 grid(psg::ceil_div(N, SM_T / sub), G);
+#define PSG_SMOOTH_SYM_LAUNCH(NBT, SUB)                                                                                          \
+    do {                                                                                                                         \
+        if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)smooth_knn_sym_own_kernel<NBT, SUB>));               \
+        hipLaunchKernelGGL((smooth_knn_sym_own_kernel<NBT, SUB>), grid, dim3(SM_T), lds, st, adv_color, adv_stride, N, nb,       \
+                           dist_sum_rooms, grad_out, adv_room_stride, nn_out, room_active);                                      \
+    } while (0)
+    if (wide) {
+        if (nb <= 5) PSG_SMOOTH_SYM_LAUNCH(5, 4);
+        else if (nb <= 8) PSG_SMOOTH_SYM_LAUNCH(8, 4);
+        else PSG_SMOOTH_SYM_LAUNCH(16, 4);
+    } else {
+        if (nb <= 5) PSG_SMOOTH_SYM_LAUNCH(5, 16);
+        else if (nb <= 8) PSG_SMOOTH_SYM_LAUNCH(8, 16);
+        else PSG_SMOOTH_SYM_LAUNCH(16, 16);
+    }
+#undef PSG_SMOOTH_SYM_LAUNCH
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(smooth_sym_incoming_kernel, dim3(psg::ceil_div(N, SI_T / SI_SUB), G), dim3(SI_T), 0, st, adv_color, adv_stride,
+                       adv_room_stride, N, nb, nn_out, grad_out, room_active);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
 }
 
 extern "C" int psg_nu_adam_step(float *w, float *m, float *v, const uint8_t *mask, const float *dx0, const float *x0,

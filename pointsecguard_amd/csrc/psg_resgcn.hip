@@ -19,6 +19,7 @@
 //     column sum + mat-vec (backward).
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "psg_common.h"
@@ -900,6 +901,7 @@ struct psg_gcn_model {
 };
 
 struct psg_gcn_ws {
+    uint64_t gen = psg::next_generation();   // never re-used: what the replayed NU windows are keyed on (psg_common.h)
     psg_ctx *ctx;
     int B, N, NP2, n_blocks, fdim;
     int block = PSG_GCN_BLOCK_RES, conv = PSG_GCN_CONV_EDGE;
@@ -1720,4 +1722,72 @@ extern "C" int psg_gcn_nb_attack(psg_gcn_model *m, psg_gcn_ws *ws, const float *
     for (; it < iters; ++it)
         if ((rc = iteration(it == iters - 1))) return rc;
     return psg_to_channel_major(ws->x0, B, 9, N, adv_out, st);
+}
+
+// ====================================================================================== NU attack windows
+// colper.NU_attack / tcolper.tar_NU_attack (ResGCN/sem_seg_dense/attacks/torchattacks/attacks/colper.py:62-95,
+// tcolper.py:85-132) for G one-room attacks in lockstep: one step sequence of a window, shared by the eager and the captured
+// path; dconsts_rows: the window's device rows or null.  Everything in it is a launch or an asynchronous device-to-device
+// copy on `stream` (the forward and backward are the ones psg_gcn_nb_attack captures), so a window is a single chain.
+// The head's xyz graph is rebuilt by every forward: freezing it inside a window has not been measured, and a restart's
+// clamp moves xyz between windows.
+static int gcn_nu_window_steps(const psg_gcn_nu_window_args *a, const float *dconsts_rows, psg_stream stream)
+{
+    const int G = a->G, N = a->N;
+    int rc = PSG_OK;
+    for (int i = 0; i < a->n_steps && rc == PSG_OK; ++i) {
+        const int step = a->step0 + i, adam_t = a->adam_t0 + i + 1;
+        const int f_target = a->use_target ? a->target : 0;
+        if ((rc = psg_nu_tanh_color_rooms(a->w, a->mask, G, N, a->x0, stream))) break;
+        if ((rc = psg_gcn_forward(a->model, a->ws, a->x0, a->logits, stream))) break;
+        if ((rc = psg_gcn_f_loss_grad_rooms(a->logits, a->labels, f_target, a->mask, a->mode, G, N, NCLS, a->kappa, a->tsign, a->c_f,
+                                            a->dlogits, a->scal, a->pred, stream)))
+            break;
+        if ((rc = psg_gcn_backward(a->model, a->ws, a->dlogits, a->dx0, stream))) break;
+        if ((rc = psg_smooth_knn_sym_rooms(a->x0 + 3, 9, (size_t)N * 9, G, N, a->neighbour, a->scal + G, a->sgrad, a->active,
+                                           a->nn_state, stream)))
+            break;
+        nu_set_step_consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
+        // (psg_nu_adam_step_rooms is the lockstep form for two rooms and more; one room is the batch form at B = 1: the same
+        // arithmetic, and its speculative steps past the exit are discarded with the latch's snapshot either way)
+        rc = G > 1 ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr,
+                                            a->beta1, a->beta2, a->eps, adam_t, G, N, a->active, a->scal + 2 * G, stream)
+                   : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr, a->beta1,
+                                      a->beta2, a->eps, adam_t, 1, N, a->scal + 2, stream);
+        if (rc == PSG_OK)
+            rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, 1, N,
+                                   a->mode, a->scal, a->hist + (size_t)i * 5 * G, a->x0, a->out, a->active, a->exit_step, step, stream);
+        nu_set_step_consts(nullptr);
+    }
+    nu_set_step_consts(nullptr);
+    return rc;
+}
+
+extern "C" int psg_gcn_nu_window(const psg_gcn_nu_window_args *a, psg_nu_graph *graph, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws && a->w && a->m && a->v && a->x0 && a->ori && a->labels && a->logits && a->dlogits && a->dx0 &&
+                    a->sgrad && a->pred && a->scal && a->nn_state && a->hist && a->out && a->active && a->exit_step,
+                "psg_gcn_nu_window: null argument");
+    PSG_REQUIRE(a->n_steps > 0 && a->G > 0 && a->N > 0, "psg_gcn_nu_window: n_steps=%d G=%d N=%d out of range", a->n_steps, a->G, a->N);
+    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->N,
+                "psg_gcn_nu_window: rooms form only - the workspace is for %d rooms of %d points, the window for %d of %d", a->ws->B,
+                a->ws->N, a->G, a->N);
+    PSG_REQUIRE(a->model->n_blocks == a->ws->n_blocks && a->model->block == a->ws->block && a->model->conv == a->ws->conv,
+                "psg_gcn_nu_window: model / workspace configuration mismatch");
+    PSG_REQUIRE(a->mode >= 0 && a->mode <= 2, "psg_gcn_nu_window: mode %d out of range", a->mode);
+    PSG_REQUIRE(a->mode == 0 || (a->mask && a->n_mask), "psg_gcn_nu_window: modes 1 and 2 need mask and n_mask");
+    PSG_REQUIRE((a->mode == 2) == (a->use_target != 0), "psg_gcn_nu_window: mode 2 is the one that takes a target class");
+    PSG_REQUIRE(!a->use_target || (a->target >= 0 && a->target < NCLS), "psg_gcn_nu_window: target class %d out of range", a->target);
+    PSG_REQUIRE(a->neighbour > 0 && a->neighbour <= 16 && a->N <= 8192, "psg_gcn_nu_window: neighbour=%d (1..16) / N=%d (<= 8192) out of range",
+                a->neighbour, a->N);
+    // what a captured window is valid for: the argument block without what the device rows carry, and whether the forward
+    // builds its graphs or takes the ones psg_gcn_set_graphs supplied (the two enqueue different launches)
+    struct Key { psg_gcn_nu_window_args a; int fixed_graphs; } key;
+    memset(&key, 0, sizeof(key));
+    key.a = *a;
+    key.a.step0 = 0; key.a.adam_t0 = 0; key.a.lr = 0.0f;
+    key.fixed_graphs = a->ws->fixed_graphs ? 1 : 0;
+    return nu_graph_window(a->ws->prof.on ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, a->n_steps, a->step0,
+                           a->adam_t0, a->lr, a->beta1, a->beta2, (hipStream_t)stream,
+                           [&](const float *rows) { return gcn_nu_window_steps(a, rows, stream); });
 }

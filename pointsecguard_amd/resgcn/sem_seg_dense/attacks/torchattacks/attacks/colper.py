@@ -44,3 +44,9 @@ class NU_attack(Attack):
     def forward(self, images, labels):
         from .nu import gcn_nu_attack
         return gcn_nu_attack(self, images, labels, neighbour=10)
+
+    def forward_rooms(self, images, labels):
+        """R >= 1 one-room attacks in lockstep (nu.gcn_nu_attack_rooms): images [R, 9, N, 1], labels [R, N] ->
+        (adv [R, 9, N, 1], steps_run [R]); per room what `forward` computes on that room alone."""
+        from .nu import gcn_nu_attack_rooms
+        return gcn_nu_attack_rooms(self, images, labels, neighbour=10)

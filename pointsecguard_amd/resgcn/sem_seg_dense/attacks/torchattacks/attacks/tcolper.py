@@ -62,3 +62,10 @@ class tar_NU_attack(Attack):
     def forward(self, images, labels):
         from .nu import gcn_nu_attack
         return gcn_nu_attack(self, images, labels, mask=self.mask, target=self.target, neighbour=5, targeted_variant=True)
+
+    def forward_rooms(self, images, labels, masks):
+        """R >= 1 one-room attacks in lockstep (nu.gcn_nu_attack_rooms), room r under masks[r]: images [R, 9, N, 1], labels
+        [R, N], masks [R, N] bool -> (adv [R, 9, N, 1], steps_run [R]).  Every room starts from this object's lr, which is
+        put back on return (R fresh attack objects, as the reference's harness builds them)."""
+        from .nu import gcn_nu_attack_rooms
+        return gcn_nu_attack_rooms(self, images, labels, masks=masks, target=self.target, neighbour=5, targeted_variant=True)

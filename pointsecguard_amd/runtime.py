@@ -576,6 +576,12 @@ class GCNWorkspace(_Handle):
                   int(iters), ptr(out), stream())
         return out
 
+    def nu_window(self, args, graph=None):
+        """psg_gcn_nu_window: the optimiser steps args.step0 .. args.step0 + args.n_steps - 1 of the ResGCN NU attacks for
+        args.G rooms in lockstep, in one call (args: _lib.GcnNuWindowArgs whose model / ws fields hold the handles; graph:
+        a psg_nu_graph handle that lets full windows of one shape be replayed, or None)."""
+        _lib.call("psg_gcn_nu_window", ctypes.byref(args), graph, stream())
+
     def edges(self, block):
         src = _lib.load().psg_gcn_edge_ptr(self.handle, block)
         out = torch.empty(self.batch, self.n_point, 16, dtype=torch.int32, device=self.device)
