@@ -139,7 +139,12 @@ int psg_pn2_plan_build(psg_pn2_ws *ws, const float *x0, const int32_t *starts, i
 
 /* Read-back of plan slices for parity tests (device pointers into the workspace).
  * what: 0 fps idx [S_l], 1 group idx [S_l][K] (MSG: scale 0, K = 16), 2 nn idx [N_l][3], 3 nn weights [N_l][3],
- * 4 xyz of level+1, 5 group idx of MSG scale 1 [S_l][32] (null for SSG) */
+ * 4 xyz of level+1, 5 group idx of MSG scale 1 [S_l][32] (null for SSG);
+ * packed SA forward (SSG, null under PSG_PN2_PACK=0): 6 valid rows per group, int32 [S_l]; 7 workgroup segmentation, int32
+ * [S_l / G_l + 2] = {workgroups in use, first group of each, S_l} (G_l = 4, 2, 1, 1 groups per unpacked workgroup);
+ * 8 (forward 0 only) the arg-max bytes [S_l][C3_l] that the resident forward left for `room`; 9 the workgroup descriptors,
+ * int32 [S_l / G_l][4] = {first group | groups << 16 (0: workgroup not in use), valid rows - 1 of its groups, five bits each, six
+ * to a word} */
 const void *psg_pn2_plan_ptr(const psg_pn2_ws *ws, int what, int level, int forward, int room);
 
 /* get_model.forward (pointnet2_sem_seg.py:22-40) with the geometry of plan slot `forward`.

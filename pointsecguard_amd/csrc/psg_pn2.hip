@@ -157,6 +157,14 @@ bool arch_fp_split(const ArchDesc &A, int lvl)
     return on && lvl <= 2 && !(lvl == 0 && wave1);
 }
 
+// SSG: the SA forward kernels run a group's valid rows only (psg_pn2_kernels.cuh, sa_fwd_packed_kernel).  PSG_PN2_PACK=0 keeps the
+// unpacked kernels everywhere (A/B runs, tests/test_gpu_sa_pack.py); MSG (16-sample scales) always runs them.
+bool arch_pack(const ArchDesc &A)
+{
+    static const bool on = psg::env_int("PSG_PN2_PACK", 1) != 0;
+    return on && A.id == PSG_PN2_ARCH_SSG;
+}
+
 const ArchDesc &arch_of(int id)
 {
     static const ArchDesc ssg = make_ssg(), msg = make_msg();
@@ -214,6 +222,9 @@ struct psg_pn2_ws {
     int32_t *fps[4];      // [F*B][S_l]
     float *xyz[5];        // xyz[l+1]: [F*B][S_l][3]; xyz[0] = xyz0
     int32_t *gidx[4][2];  // [F*B][S_l][K]
+    int32_t *pk_cnt[4];   // packed SA forward (arch_pack): [F*B][S_l] valid rows of each group
+    int32_t *pk_seg[4];   // [F*B][S_l / G_l + 2] workgroup segmentation (psg_pn2_kernels.cuh: sa_pack_plan_kernel)
+    int4 *pk_desc[4];     // [F*B][S_l / G_l] what the packed kernel's workgroups read: one descriptor each
     int32_t *ball0[2];    // per level-0 scale: [B][N][K] the room's ball query with every point as centroid, or null (ball_table_mode)
     int32_t *nn_idx[4];   // [F*B][N_l][3]
     float *nn_w[4];
@@ -338,7 +349,7 @@ BwdLayer bwd_layer(const PackedLayer &p, const uint16_t *mask)
 // kernel tags of the per-launch profile (psg_pn2_prof_read)
 enum { TAG_SA_FWD = 0, TAG_FP_FWD = 4, TAG_FP_BWD = 8, TAG_SA_BWD = 12, TAG_FPS = 16, TAG_BALL = 17, TAG_NN = 18,
        TAG_GATHER = 19, TAG_CE = 20, TAG_PGD = 21, TAG_ZERO = 22, TAG_PW_FWD = 23, TAG_PW_BWD = 24,
-       TAG_GEOM_GREL = 25, TAG_GEOM_WGRAD = 26, TAG_GEOM_GX = 27, TAG_COUNT = 28 };   // 25-27: psg_pn2_backward_full only
+       TAG_GEOM_GREL = 25, TAG_GEOM_WGRAD = 26, TAG_GEOM_GX = 27, TAG_PACK_PLAN = 28, TAG_COUNT = 29 };   // 25-27: psg_pn2_backward_full only
 
 // Every launch with a dynamic LDS buffer of `blocks8` blocks of `blk` floats goes through here: size check, the shared LDS
 // opt-in above 48 KiB, the profile scope and the launch check.  `site` is the CALLER's launch site (PSG_SITE, psg_common.h).
@@ -397,6 +408,23 @@ int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const
     }
     const dim3 grid(S / (P / KS), B);
     const int tag = TAG_SA_FWD + lvl;
+    a.pk_desc = nullptr; a.pk_tab_off = 0;
+    // packed rows (SSG as shipped: level 0 whole, levels 1 - 3 split); any other first-layer form keeps the unpacked kernels
+    const int blk = P * 8 + PSG_LDS_PAD;                           // Lds<P>::BLK
+    // (LDS: the [P][C3] pool rows over the activation buffer; the row maps behind the buffer, the group starts in pool row P - 1)
+    if (ws->pk_cnt[lvl] && KS == 32 && d.maxt_f == 1 && split == (lvl >= 1) && a.nb3 * (P / 32) == 2 * NW &&
+        blocks * blk + 2 * P <= (P - 1) * a.C3 && (P * a.C3) % blk == 0) {
+        a.pk_desc = ws->pk_desc[lvl] + prob * grid.x;
+        a.pk_tab_off = blocks * blk;
+        const int pblocks = P * a.C3 / blk;
+        switch (PSG_CFG_KEY(P, NW, KS, split ? 1 : 0)) {
+        case PSG_CFG_KEY(128, 4, 32, 0): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<128, 4, false>), grid, 4 * 64, pblocks, blk, a, st);
+        case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<64, 4, true>), grid, 4 * 64, pblocks, blk, a, st);
+        case PSG_CFG_KEY(32, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 4, true>), grid, 4 * 64, pblocks, blk, a, st);
+        case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 8, true>), grid, 8 * 64, pblocks, blk, a, st);
+        }
+        a.pk_desc = nullptr; a.pk_tab_off = 0;
+    }
 #define PSG_SA_FWD_CASE(P_, NW_, KS_, MT_) \
     case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
         return launch_lds(ws, tag, PSG_SITE, sa_fwd_kernel<P_, NW_, KS_, MT_>, grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
@@ -1245,6 +1273,13 @@ void ws_layout(psg_pn2_ws *ws, Bump &bp)
         ws->gxyz[l + 1] = full ? bp.take<float>((size_t)B * ws->Nl[l + 1] * 3) : nullptr;
     }
     ws->gxyz[0] = nullptr;
+    for (int l = 0; l < 4; ++l) {
+        const bool pk = arch_pack(A);
+        ws->pk_cnt[l] = pk ? bp.take<int32_t>(PR * kS[l]) : nullptr;
+        ws->pk_seg[l] = pk ? bp.take<int32_t>(PR * (kS[l] / (A.sc[l][0].P / 32) + 2)) : nullptr;
+        bp.off = (bp.off + 15) & ~(size_t)15;
+        ws->pk_desc[l] = pk ? bp.take<int4>(PR * (kS[l] / (A.sc[l][0].P / 32))) : nullptr;
+    }
     // (last of all, for the same reason) the per-room level-0 ball tables, where a plan of this workspace can reach the table route
     for (int s = 0; s < 2; ++s)
         ws->ball0[s] = s < A.ns && ball_table_route(F, ws->N) ? bp.take<int32_t>((size_t)B * ws->N * A.sc[0][s].K) : nullptr;
@@ -1553,6 +1588,12 @@ extern "C" int psg_pn2_plan_build(psg_pn2_ws *ws, const float *x0, const int32_t
             hipLaunchKernelGGL(build_inv_group_kernel, dim3(P), dim3(INV_NT), inv_lds, st, ws->gidx[l][sc], S * d.K, Np, d.K,
                                ws->ginv_off[l][sc], ws->ginv_pos[l][sc]);
             PSG_LAUNCH_CHECK();
+            if (ws->pk_cnt[l] && sc == 0) {
+                EvScope prof_pack(&ws->prof, TAG_PACK_PLAN, 0.0, st);
+                hipLaunchKernelGGL(sa_pack_plan_kernel, dim3(P), dim3(256), 0, st, ws->gidx[l][0], S, Np, d.P, ws->pk_cnt[l],
+                                   ws->pk_seg[l], ws->pk_desc[l]);
+                PSG_LAUNCH_CHECK();
+            }
         }
         {
             EvScope prof(&ws->prof, TAG_NN, 0.0, st);
@@ -1581,6 +1622,10 @@ extern "C" const void *psg_pn2_plan_ptr(const psg_pn2_ws *ws, int what, int leve
     case 3: return ws->nn_w[level] + p * ws->Nl[level] * 3;
     case 4: return ws->xyz[level + 1] + p * kS[level] * 3;
     case 5: return ws->arch->ns > 1 ? ws->gidx[level][1] + p * kS[level] * ws->arch->sc[level][1].K : nullptr;
+    case 6: return ws->pk_cnt[level] ? ws->pk_cnt[level] + p * kS[level] : nullptr;
+    case 7: return ws->pk_seg[level] ? ws->pk_seg[level] + p * (kS[level] / (ws->arch->sc[level][0].P / 32) + 2) : nullptr;
+    case 9: return ws->pk_desc[level] ? ws->pk_desc[level] + p * (kS[level] / (ws->arch->sc[level][0].P / 32)) : nullptr;
+    case 8: return forward == 0 ? ws->arg[level][0] + (size_t)room * kS[level] * ws->arch->c3(level, 0) : nullptr;
     default: return nullptr;
     }
 }

@@ -41,6 +41,10 @@ struct SaFwdArgs {
     const float *tfeat;
     int ldt;
     int diag;              // timing diagnostics only (-DPSG_DIAG_BUILD libraries only): skip sections, results are then wrong
+    // packed kernels (sa_fwd_packed_kernel): the plan's workgroup descriptors (sa_pack_plan_kernel) and the float offset of the
+    // workgroup's row maps behind the LDS activation buffer
+    const int4 *pk_desc;   // [B][gridDim.x] one descriptor per workgroup (below)
+    int pk_tab_off;
 };
 
 struct SaBwdArgs {
@@ -192,8 +196,10 @@ __device__ __forceinline__ void sa_layer1_split(const SaFwdArgs &a, int b, int s
     }
 }
 
-template <int P, int NW, int KS = 32, int MAXT = 1, bool SPLIT = false>
-__global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
+// the workgroup (bx, b) of sa_fwd_kernel: groups [bx * G, (bx + 1) * G) of room b (also what sa_fwd_packed_kernel runs for a
+// workgroup of full groups on that boundary)
+template <int P, int NW, int KS, int MAXT, bool SPLIT>
+__device__ __forceinline__ void sa_fwd_body(SaFwdArgs a, int bx, int b)
 {
     using L = Lds<P>;
     static_assert(KS == 32 || KS == 16, "groups of 32 or 16 samples");
@@ -201,8 +207,6 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
     extern __shared__ float lds[];
     float *buf0 = lds;   // the one activation buffer (layers run in place)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int bx, b;
-    xcd_tile(bx, b);
     const int s0 = bx * G;
     const size_t wg = (size_t)b * gridDim.x + bx;
 
@@ -337,6 +341,361 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
         acc = tile_mac<L::BLK, true>(a.w3 + (size_t)nb * a.k8_3 * 64 + lane, a.k8_3, buf0 + (g * 32 + jj) * 8 + 4 * h,
                                      acc);
         pool(acc, nb, g);
+    }
+}
+
+template <int P, int NW, int KS = 32, int MAXT = 1, bool SPLIT = false>
+__global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
+{
+    int bx, b;
+    xcd_tile(bx, b);
+    sa_fwd_body<P, NW, KS, MAXT, SPLIT>(a, bx, b);
+}
+
+// ------------------------------------------------------------------------------------------ SA fwd, packed
+// query_ball_point fills a group of 32 with copies of its first member (pointnet_util.py:104-106), and a 0.1 m ball of a
+// 4096-point room holds about five points: most grouped rows are bit-for-bit copies of row 0 of their group.  A copy has row
+// 0's MLP output, never wins the max-pool (a tie goes to the lowest row) and gets no gradient, so the forward runs the VALID rows
+// only: cnt[s] = the leading rows of group s up to the first k > 0 with gidx[k] == gidx[0] (the rule of build_inv_group_kernel;
+// an empty ball, gidx[0] = Np, counts as 32 rows and behaves as in sa_fwd_kernel).
+//
+// Plan (sa_pack_plan_kernel, once per psg_pn2_plan_build, one workgroup per problem): the counts, and a greedy segmentation of
+// the S groups into workgroups - consecutive groups while their valid rows stay BELOW the kernel's P rows (the last row of the
+// LDS pool holds the workgroup's group table) and within SA_PACK_GCAP groups; the one workgroup that holds P rows is P / 32 full
+// groups, which pools in registers.  seg[0] = workgroups in use, seg[1 + i] = first group of workgroup i, seg[1 + seg[0]] = S.
+// A group has at most 32 rows, so a closed workgroup holds at least P / 32 groups: the unpacked grid (S / (P / 32) per problem)
+// is the worst case and stays the launch grid - nothing is read back, surplus workgroups read their descriptor and return.
+// What a workgroup reads is ONE 16-byte descriptor (a uniform load; counts and segment tables would be three dependent loads
+// in front of the gather): x = first group | groups << 16 (0 groups: surplus), y / z / w = cnt - 1 of its groups, five bits
+// each, six to a word.  cnt and seg stay in the plan for read-back (psg_pn2_plan_ptr).
+constexpr int SA_PACK_GCAP = 16;
+
+__device__ __forceinline__ int sa_pack_cnt(const int4 &d, int i)
+{
+    const int w = i < 6 ? d.y : (i < 12 ? d.z : d.w);
+    return ((w >> (5 * (i % 6))) & 31) + 1;
+}
+
+__global__ __launch_bounds__(256) void sa_pack_plan_kernel(const int32_t *__restrict__ gidx, int S, int Np, int P,
+                                                           int32_t *__restrict__ cnt, int32_t *__restrict__ seg,
+                                                           int4 *__restrict__ desc)
+{
+    __shared__ int s_cnt[1024];
+    const size_t p = blockIdx.x;
+    const int32_t *gi = gidx + p * S * 32;
+    for (int s = threadIdx.x; s < S; s += 256) {
+        const int32_t *row = gi + (size_t)s * 32;
+        const int first = row[0];
+        int n = 32;
+        if (first < Np) {
+            n = 1;
+            while (n < 32 && row[n] != first) ++n;
+        }
+        s_cnt[s] = n;
+        cnt[p * S + s] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int gx = S / (P / 32);
+        int32_t *sg = seg + p * (gx + 2);
+        int4 *dg = desc + p * gx;
+        int nseg = 0, s = 0;
+        while (s < S) {
+            sg[1 + nseg] = s;
+            int rows = 0, g = 0;
+            int4 d = make_int4(s, 0, 0, 0);
+            while (s < S && g < SA_PACK_GCAP) {
+                const int c = s_cnt[s];
+                if (!(rows + c < P || (rows + c == P && rows == 32 * g && g + 1 == P / 32))) break;
+                const int f = (c - 1) << (5 * (g % 6));
+                if (g < 6) d.y |= f; else if (g < 12) d.z |= f; else d.w |= f;
+                rows += c; ++s; ++g;
+            }
+            d.x |= g << 16;
+            dg[nseg] = d;
+            ++nseg;
+        }
+        sg[0] = nseg;
+        sg[1 + nseg] = S;
+        for (int i = nseg; i < gx; ++i) dg[i] = make_int4(0, 0, 0, 0);
+    }
+}
+
+// The kernel: sa_fwd_kernel's chain (KS = 32, one tile per wave in the first two layers) over the workgroup's packed rows.
+//   * rows: the valid rows of the descriptor's groups in order, nrows <= P of them in nblk = ceil(nrows / 32) blocks;
+//     the tail of the last block repeats the last valid row (tile columns are independent: it changes nothing and is never read);
+//   * layers run over the nblk active blocks only, every valid row through the k-loop and epilogue it had unpacked: the values are
+//     the same bits;
+//   * ReLU masks go to the slots of the UNPACKED layout (workgroup s / G, tile (mb, s % G), lane (h, k)), one 2-byte store per
+//     lane: the backward kernels read them where they always did.  The words of padding rows are not written: their gradient
+//     rows are exactly zero before the mask is applied (AND with a zero) and are not stored (gpos_out = -1);
+//   * max-pool: groups are runs of packed rows that may cross a block, so the last layer's tiles go to LDS as plain rows
+//     [row][C3] (over the dead activation buffer: P x C3 floats, twice the buffer) and one thread per (group, channel) scans
+//     the group's rows in ascending order with a strict compare - the lowest row that attains the maximum, as the in-register
+//     pool finds it; 255 for a maximum <= 0.  A workgroup whose groups are all full (nothing to skip) pools in registers as
+//     sa_fwd_kernel does.
+// LDS: P x C3 floats and not a byte more (32 / 32 / 32 / 64 KiB at levels 0 - 3, against 16 / 16 / 16 / 32 KiB unpacked: five
+// workgroups of levels 0 - 2 per CU are exactly the 160 KiB, which is also what 88 VGPRs allow).  The row tables live inside:
+// the group starts in pool row P - 1, which a packed workgroup never fills (the plan keeps it below P rows), the row maps
+// behind the activation buffer in the half of the pool that is dead until the last layer is done.
+__device__ __forceinline__ void sa_pool32(const SaFwdArgs &a, const f32x16 &acc, int h, int jj, size_t row, int nb)
+{
+    float best = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
+#pragma unroll
+    for (int r = 3; r < 15; r += 2) best = fmaxf(fmaxf(best, acc[r]), acc[r + 1]);
+    best = fmaxf(best, acc[15]);
+    int bidx = acc_row(15, h);
+#pragma unroll
+    for (int r = 14; r >= 0; --r) bidx = acc[r] == best ? acc_row(r, h) : bidx;
+    best = best > 0.0f ? best : 0.0f;
+    float ob = __shfl_xor(best, 32);
+    int oi = __shfl_xor(bidx, 32);
+    if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+    if (h == 0) {
+        a.out[row * a.ld_out + a.c_out + nb * 32 + jj] = best;
+        a.arg[row * a.C3 + nb * 32 + jj] = best > 0.0f ? (uint8_t)bidx : (uint8_t)255;
+    }
+}
+
+// slot of the mask word of unpacked row om = group * 32 + sample, tile row mb of a layer with lmb 32-channel blocks
+template <int P>
+__device__ __forceinline__ size_t sa_pack_mask_slot(int om, int b, int gx, int mb, int lmb, int h)
+{
+    constexpr int G = P / 32;
+    const int s = om >> 5, k = om & 31;
+    const size_t wgo = (size_t)b * gx + s / G;
+    return ((wgo * lmb + mb) * G + (s % G)) * 64 + h * 32 + k;
+}
+
+template <int P, int NW>
+__device__ __forceinline__ void sa_layer_fwd_packed(const FwdLayer &L, float *__restrict__ buf, int nblk, int first,
+                                                    const int *__restrict__ omap, int b)
+{
+    constexpr int BLK = Lds<P>::BLK;
+    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+    const bool act = first < L.mb * nblk;
+    int mb = 0, pb = 0;
+    f32x16 c;
+    if (act) {
+        mb = first / nblk; pb = first - mb * nblk;
+        const float4 *bp = (const float4 *)(L.bias + mb * 32 + 4 * h);
+        const float4 bq0 = bp[0], bq1 = bp[2], bq2 = bp[4], bq3 = bp[6];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c[r] = 0.0f;
+        c = tile_mac<BLK, false>(L.w + (size_t)mb * L.k8 * 64 + lane, L.k8, buf + (pb * 32 + j) * 8 + 4 * h, c);
+        c[0] += bq0.x; c[1] += bq0.y; c[2] += bq0.z; c[3] += bq0.w;
+        c[4] += bq1.x; c[5] += bq1.y; c[6] += bq1.z; c[7] += bq1.w;
+        c[8] += bq2.x; c[9] += bq2.y; c[10] += bq2.z; c[11] += bq2.w;
+        c[12] += bq3.x; c[13] += bq3.y; c[14] += bq3.z; c[15] += bq3.w;
+        if (L.relu) {
+            const unsigned m = relu_bits(c);
+            const int om = omap[pb * 32 + j];
+            if (L.mask && om >= 0) L.mask[sa_pack_mask_slot<P>(om, b, gridDim.x, mb, L.mb, h)] = (uint16_t)m;
+        }
+    }
+    __syncthreads();
+    if (act) store_tile<P>(buf, mb, pb * 32 + j, h, c);
+}
+
+template <int P, int NW, bool SPLIT>
+__global__ __launch_bounds__(NW * 64) void sa_fwd_packed_kernel(SaFwdArgs a)
+{
+    using L = Lds<P>;
+    constexpr int PB = P / 32, NT = NW * 64, GCAP = SA_PACK_GCAP;
+    static_assert(GCAP >= PB && GCAP < 64, "a workgroup's groups: at least P / 32, and one scan lane each");
+    extern __shared__ float lds[];
+    float *buf0 = lds;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int bx, b;
+    xcd_tile(bx, b);
+    const size_t wg = (size_t)b * gridDim.x + bx;
+    const int4 desc = a.pk_desc[wg];
+    const int ng = desc.x >> 16, sA = desc.x & 0xFFFF;
+    if (ng == 0) return;                                        // surplus workgroup (uniform: no barrier has been reached)
+    if (ng == PB && (sA & (PB - 1)) == 0) {
+        // P / 32 groups on an unpacked workgroup's boundary: if they are all full there is nothing to skip, and the rows, mask
+        // slots and pool are sa_fwd_kernel's own - its body runs, at its cost (rooms of full balls: tools/sa_pack_probe.py)
+        int rows = 0;
+        for (int i = 0; i < PB; ++i) rows += sa_pack_cnt(desc, i);
+        if (rows == P) {
+            sa_fwd_body<P, NW, 32, 1, SPLIT>(a, sA / PB, b);
+            return;
+        }
+    }
+    int *gstart = (int *)(lds + (size_t)(P - 1) * a.C3);        // [GCAP + 1] first packed row of each group, then nrows
+    int *omap = (int *)(lds + a.pk_tab_off);                    // [P] unpacked row (group * 32 + sample) of a packed row, -1 = tail
+    int *srcl = omap + P;                                       // [P] its source point (both dead before the pool is written)
+    int nrows = 0;
+    for (int i = 0; i < ng; ++i) {                              // (uniform; the pool scan at the end reads the starts from LDS)
+        if (tid == i) gstart[i] = nrows;
+        nrows += sa_pack_cnt(desc, i);
+    }
+    if (tid == ng) gstart[ng] = nrows;
+    const int nblk = (nrows + 31) >> 5;
+    {
+        // packed row j of this thread (the parts of the unsplit gather each find it themselves: a search over <= GCAP starts)
+        const int j = tid % P, part = tid / P;
+        constexpr int NPART = NT / P > 0 ? NT / P : 1;
+        if (tid < NPART * P && j < nblk * 32) {
+            const int pe = min(j, nrows - 1);
+            int g = 0, st = 0, c = sa_pack_cnt(desc, 0);
+            while (st + c <= pe) { st += c; ++g; c = sa_pack_cnt(desc, g); }   // (pe < nrows: ends at a group < ng)
+            const int k = pe - st, s = sA + g;
+            const int src = a.gidx[((size_t)b * a.S + s) * 32 + k];
+            if (part == 0) {
+                omap[j] = j < nrows ? s * 32 + k : -1;
+                srcl[j] = src;
+            }
+            const float *xr = a.xyz + ((size_t)b * a.Np + src) * a.xyz_stride;
+            const float *cr = a.new_xyz + ((size_t)b * a.S + s) * 3;
+            if (SPLIT) {
+                if (part == 0) {
+                    *(float4 *)(buf0 + j * 8) = make_float4(xr[0] - cr[0], xr[1] - cr[1], xr[2] - cr[2], 0.0f);
+                    *(float4 *)(buf0 + j * 8 + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            } else {
+                const float *frow = a.feat + ((size_t)b * a.Np + src) * a.D;
+                if ((a.D & 3) == 0) {
+                    const float4 *f4 = (const float4 *)frow;
+                    for (int q = part; q < (a.D >> 2); q += NPART) *(float4 *)(buf0 + L::off(4 * q, j)) = f4[q];
+                    if (part == 0) {
+                        *(float4 *)(buf0 + L::off(a.D, j)) = make_float4(xr[0] - cr[0], xr[1] - cr[1], xr[2] - cr[2], 0.0f);
+                        if ((a.D & 7) == 0) *(float4 *)(buf0 + L::off(a.D + 4, j)) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                } else if (part == 0) {
+                    // sa1: D = 9 -> [f0..f8, rx, ry, rz, 0, 0, 0, 0] (two 8-channel blocks)
+                    float f[9];
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) f[c] = frow[c];
+                    *(float4 *)(buf0 + L::off(0, j)) = make_float4(f[0], f[1], f[2], f[3]);
+                    *(float4 *)(buf0 + L::off(4, j)) = make_float4(f[4], f[5], f[6], f[7]);
+                    *(float4 *)(buf0 + L::off(8, j)) = make_float4(f[8], xr[0] - cr[0], xr[1] - cr[1], xr[2] - cr[2]);
+                    *(float4 *)(buf0 + L::off(12, j)) = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                for (int blk = ((a.D + 3) >> 3) + 1 + part; blk < a.l1.k8; blk += NPART) {
+                    float *z = buf0 + (size_t)blk * L::BLK + j * 8;
+                    *(float4 *)z = make_float4(0.f, 0.f, 0.f, 0.f);
+                    *(float4 *)(z + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int jj = lane & 31, h = lane >> 5;
+    const int first = (wave + (int)(wg & (NW - 1))) & (NW - 1);
+    if (SPLIT) {
+        // sa_layer1_split over the active blocks: the rows of T into the accumulators, one k8-chunk of relative coordinates
+        const FwdLayer &L1 = a.l1;
+        const bool act = first < L1.mb * nblk;
+        int mb = 0, pb = 0;
+        f32x16 c;
+        if (act) {
+            mb = first / nblk; pb = first - mb * nblk;
+            const int src = srcl[pb * 32 + jj];
+            const float *trows = a.tfeat + (size_t)b * a.Np * a.ldt;
+            const float4 *tp = (const float4 *)(trows + __umul24((unsigned)src, (unsigned)a.ldt) + mb * 32 + 4 * h);
+            const float4 t0 = tp[0], t1 = tp[2], t2 = tp[4], t3 = tp[6];
+            c[0] = t0.x; c[1] = t0.y; c[2] = t0.z; c[3] = t0.w;
+            c[4] = t1.x; c[5] = t1.y; c[6] = t1.z; c[7] = t1.w;
+            c[8] = t2.x; c[9] = t2.y; c[10] = t2.z; c[11] = t2.w;
+            c[12] = t3.x; c[13] = t3.y; c[14] = t3.z; c[15] = t3.w;
+            const float4 wx = L1.w[(size_t)mb * 64 + lane];
+            const float4 rx = *(const float4 *)(buf0 + (pb * 32 + jj) * 8 + 4 * h);
+            c = mfma4<false>(wx, rx, c);
+            mfma_fence(c);
+            const unsigned m = relu_bits(c);
+            const int om = omap[pb * 32 + jj];
+            if (L1.mask && om >= 0) L1.mask[sa_pack_mask_slot<P>(om, b, gridDim.x, mb, L1.mb, h)] = (uint16_t)m;
+        }
+        __syncthreads();
+        if (act) store_tile<P>(buf0, mb, pb * 32 + jj, h, c);
+    } else {
+        sa_layer_fwd_packed<P, NW>(a.l1, buf0, nblk, first, omap, b);
+    }
+    __syncthreads();
+    sa_layer_fwd_packed<P, NW>(a.l2, buf0, nblk, first, omap, b);
+    __syncthreads();
+
+    // last layer, tile flipped (D[point][channel]): two tiles per wave, as sa_fwd_kernel deals them
+    f32x16 c0, c1;
+    int nb0 = 0, nb1 = 0, g0 = 0, g1 = 0;
+    bool act0 = false, act1 = false;
+    if constexpr (PSG_MLP_PAIRS && PB >= 2) {
+        // the point blocks g, g + 1 of one output block on one weight stream; an odd last block pairs with a block nobody reads
+        const int hp = (nblk + 1) >> 1;
+        if (wave < a.nb3 * hp) {
+            nb0 = nb1 = wave / hp;
+            g0 = 2 * (wave - nb0 * hp); g1 = g0 + 1;
+            act0 = true; act1 = g1 < nblk;
+            const float bias = a.b3[nb0 * 32 + jj];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { c0[r] = bias; c1[r] = bias; }
+            tile_mac_x2<L::BLK, true>(a.w3 + (size_t)nb0 * a.k8_3 * 64 + lane, a.k8_3, buf0 + (g0 * 32 + jj) * 8 + 4 * h, c0, c1);
+        }
+    } else if constexpr (PB >= 2) {
+        // -DPSG_MLP_PAIRS=0: single tiles (output block, point block), two per wave at most
+        const int nt = a.nb3 * nblk;
+        act0 = wave < nt; act1 = wave + NW < nt;
+        nb0 = wave / nblk; g0 = wave - nb0 * nblk;
+        nb1 = (wave + NW) / nblk; g1 = wave + NW - nb1 * nblk;
+        if (act0) {
+            const float bias0 = a.b3[nb0 * 32 + jj];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c0[r] = bias0;
+            c0 = tile_mac<L::BLK, true>(a.w3 + (size_t)nb0 * a.k8_3 * 64 + lane, a.k8_3, buf0 + (g0 * 32 + jj) * 8 + 4 * h, c0);
+        }
+        if (act1) {
+            const float bias1 = a.b3[nb1 * 32 + jj];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c1[r] = bias1;
+            c1 = tile_mac<L::BLK, true>(a.w3 + (size_t)nb1 * a.k8_3 * 64 + lane, a.k8_3, buf0 + (g1 * 32 + jj) * 8 + 4 * h, c1);
+        }
+    } else {
+        nb0 = wave; nb1 = wave + NW;
+        act0 = nb0 < a.nb3; act1 = nb1 < a.nb3;
+        const float bias0 = act0 ? a.b3[nb0 * 32 + jj] : 0.0f, bias1 = act1 ? a.b3[nb1 * 32 + jj] : 0.0f;
+        if (act0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c0[r] = bias0;
+            c0 = tile_mac<L::BLK, true>(a.w3 + (size_t)nb0 * a.k8_3 * 64 + lane, a.k8_3, buf0 + jj * 8 + 4 * h, c0);
+        }
+        if (act1) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c1[r] = bias1;
+            c1 = tile_mac<L::BLK, true>(a.w3 + (size_t)nb1 * a.k8_3 * 64 + lane, a.k8_3, buf0 + jj * 8 + 4 * h, c1);
+        }
+    }
+    if (nrows == P) {               // P / 32 full groups (the plan packs nothing else into P rows): block g is group sA + g
+        if (act0) sa_pool32(a, c0, h, jj, (size_t)b * a.S + sA + g0, nb0);
+        if (act1) sa_pool32(a, c1, h, jj, (size_t)b * a.S + sA + g1, nb1);
+        return;
+    }
+    __syncthreads();                // the activation buffer is dead: the tiles go over it as plain rows [row][C3]
+    float *pool = lds;
+    if (act0) {                     // (rows < nrows <= P - 1 only: row P - 1 holds gstart)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (g0 * 32 + acc_row(r, h) < nrows) pool[(size_t)(g0 * 32 + acc_row(r, h)) * a.C3 + nb0 * 32 + jj] = c0[r];
+    }
+    if (act1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (g1 * 32 + acc_row(r, h) < nrows) pool[(size_t)(g1 * 32 + acc_row(r, h)) * a.C3 + nb1 * 32 + jj] = c1[r];
+    }
+    __syncthreads();
+    for (int t = tid; t < ng * a.C3; t += NT) {
+        const int g = t / a.C3, c = t - g * a.C3;
+        const int r0 = gstart[g], n = gstart[g + 1] - r0;
+        const float *col = pool + (size_t)r0 * a.C3 + c;
+        float best = col[0];
+        int bi = 0;
+        for (int k = 1; k < n; ++k) {
+            const float v = col[(size_t)k * a.C3];
+            if (v > best) { best = v; bi = k; }
+        }
+        const size_t row = (size_t)b * a.S + sA + g;
+        a.out[row * a.ld_out + a.c_out + c] = best > 0.0f ? best : 0.0f;
+        a.arg[row * a.C3 + c] = best > 0.0f ? (uint8_t)bi : (uint8_t)255;
     }
 }
 

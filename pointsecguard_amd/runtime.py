@@ -11,6 +11,8 @@ from . import _lib
 SA_NPOINT = (1024, 256, 64, 16)   # PointNet/models/pointnet2_sem_seg.py:9-12 (reference)
 SA_RADIUS = (0.1, 0.2, 0.4, 0.8)
 NSAMPLE = 32
+SA_PACK_GROUPS = (4, 2, 1, 1)     # SSG: groups per unpacked SA workgroup (psg_pn2.hip: P / 32); plan_tensor(7, ...)
+SA_WIDTH3 = (64, 128, 256, 512)   # SSG: width of each SA level's last layer; plan_tensor(8, ...)
 NUM_CLASSES = 13
 ARCH_SSG, ARCH_MSG = 0, 1          # PSG_PN2_ARCH_* of include/psg.h
 ARCH_LAYERS = {ARCH_SSG: 23, ARCH_MSG: 35}
@@ -269,7 +271,7 @@ class PN2Workspace(_Handle):
     PROF_TAGS = ("sa1_fwd", "sa2_fwd", "sa3_fwd", "sa4_fwd", "fp1_head_fwd", "fp2_fwd", "fp3_fwd", "fp4_fwd",
                  "fp1_head_bwd", "fp2_bwd", "fp3_bwd", "fp4_bwd", "sa1_bwd", "sa2_bwd", "sa3_bwd", "sa4_bwd",
                  "fps", "ball_query", "three_nn", "gather", "ce_grad", "pgd_step", "dx0_gather", "pw_fwd", "pw_bwd",
-                 "geom_grel", "geom_wgrad", "geom_gx")
+                 "geom_grel", "geom_wgrad", "geom_gx", "sa_pack_plan")
 
     def prof_enable(self, on=True):
         _lib.call("psg_pn2_prof_enable", self.handle, 1 if on else 0)
@@ -289,7 +291,11 @@ class PN2Workspace(_Handle):
         shape, dt = {0: ((SA_NPOINT[level],), torch.int32), 1: ((SA_NPOINT[level], k0), torch.int32),
                      2: ((n_l[level], 3), torch.int32), 3: ((n_l[level], 3), torch.float32),
                      4: ((SA_NPOINT[level], 3), torch.float32),
-                     5: ((SA_NPOINT[level], MSG_NSAMPLE[1]), torch.int32)}[what]
+                     5: ((SA_NPOINT[level], MSG_NSAMPLE[1]), torch.int32),
+                     6: ((SA_NPOINT[level],), torch.int32),                              # packed SA forward: valid rows per group
+                     7: ((SA_NPOINT[level] // SA_PACK_GROUPS[level] + 2,), torch.int32),  # and the workgroup segmentation
+                     8: ((SA_NPOINT[level], SA_WIDTH3[level] // 4), torch.int32),        # arg-max bytes, four to a word
+                     9: ((SA_NPOINT[level] // SA_PACK_GROUPS[level], 4), torch.int32)}[what]   # workgroup descriptors
         src = _lib.load().psg_pn2_plan_ptr(self.handle, what, level, forward, room)
         if not src:
             raise _lib.PsgError("psg_pn2_plan_ptr: bad slice")
