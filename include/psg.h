@@ -144,7 +144,11 @@ int psg_pn2_plan_build(psg_pn2_ws *ws, const float *x0, const int32_t *starts, i
  * [S_l / G_l + 2] = {workgroups in use, first group of each, S_l} (G_l = 4, 2, 1, 1 groups per unpacked workgroup);
  * 8 (forward 0 only) the arg-max bytes [S_l][C3_l] that the resident forward left for `room`; 9 the workgroup descriptors,
  * int32 [S_l / G_l][4] = {first group | groups << 16 (0: workgroup not in use), valid rows - 1 of its groups, five bits each, six
- * to a word} */
+ * to a word}.
+ * The SA backward of a level runs over the same packed rows through the same descriptors where PSG_PN2_PACK_BWD (read once per
+ * process) names the level: unset or 1 = every level that has the kernel (level 0), 0 = none (the unpacked backward kernels and
+ * the unpacked-keyed ReLU masks), L followed by level digits (L0) = exactly those levels, an error at launch where a named level
+ * has no packed backward kernel.  Results are the same bytes under every value. */
 const void *psg_pn2_plan_ptr(const psg_pn2_ws *ws, int what, int level, int forward, int room);
 
 /* get_model.forward (pointnet2_sem_seg.py:22-40) with the geometry of plan slot `forward`.

@@ -165,6 +165,28 @@ bool arch_pack(const ArchDesc &A)
     return on && A.id == PSG_PN2_ARCH_SSG;
 }
 
+// The SA backward of a packed level runs the same packed rows (psg_pn2_kernels.cuh, sa_bwd_packed_kernel), and the level's
+// forward then keys its ReLU masks by packed workgroup.  PSG_PN2_PACK_BWD, read once per process, names the levels: unset or
+// 1 = every level that has a packed backward kernel (level 0 is what is built), 0 = none (the unpacked backward kernels and the
+// unpacked-keyed masks, as before round 17), L followed by level digits (L0, L02) = exactly those levels; a level named that
+// way that has no packed backward kernel is an error at its launch, not a fall-back (bit 8: levels named explicitly).
+constexpr int kPackBwdBuilt = 1 << 0;
+int pack_bwd_levels()
+{
+    static const int levels = [] {
+        const char *v = psg::env_str("PSG_PN2_PACK_BWD");
+        if (!v || !*v) return kPackBwdBuilt;
+        if (*v == 'L' || *v == 'l') {
+            int mask = 1 << 8;
+            for (const char *c = v + 1; *c; ++c)
+                if (*c >= '0' && *c <= '3') mask |= 1 << (*c - '0');
+            return mask;
+        }
+        return atoi(v) != 0 ? kPackBwdBuilt : 0;
+    }();
+    return levels;
+}
+
 const ArchDesc &arch_of(int id)
 {
     static const ArchDesc ssg = make_ssg(), msg = make_msg();
@@ -375,6 +397,18 @@ inline int gsa_stride(const ArchDesc &A, int lvl)
 
 #define PSG_CFG_KEY(P, NW, KS, MT) ((P) * 10000 + (NW) * 1000 + (KS) * 10 + (MT))
 
+// Does the backward of SA level lvl run packed?  The ONE place that decides it: run_sa_fwd keys the level's ReLU masks by it and
+// run_sa_bwd picks the kernel by it.  Needs the plan's descriptors (SSG under PSG_PN2_PACK) and the level named by
+// PSG_PN2_PACK_BWD; by default also the configuration the kernel is built for - SSG as shipped: level 0 whole, level 1 split, so
+// that the pooled-output gradient of level 0 arrives as plain rows - and any other (PSG_PN2_SPLIT) keeps the unpacked backward.
+bool sa_pack_bwd_level(const psg_pn2_model *m, const psg_pn2_ws *ws, int lvl)
+{
+    const int levels = pack_bwd_levels();
+    if (!ws->pk_cnt[lvl] || !((levels >> lvl) & 1)) return false;
+    if (levels >> 8) return true;                                  // named explicitly: run_sa_fwd / run_sa_bwd fail where it does not fit
+    return lvl == 0 && !m->split_fwd[0] && !m->split[0] && m->split[1];
+}
+
 int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const float *x0, hipStream_t st)
 {
     const ArchDesc &A = *m->arch;
@@ -412,11 +446,19 @@ int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const
     // packed rows (SSG as shipped: level 0 whole, levels 1 - 3 split); any other first-layer form keeps the unpacked kernels
     const int blk = P * 8 + PSG_LDS_PAD;                           // Lds<P>::BLK
     // (LDS: the [P][C3] pool rows over the activation buffer; the row maps behind the buffer, the group starts in pool row P - 1)
+    const bool pkm = sa_pack_bwd_level(m, ws, lvl);                  // masks keyed by packed workgroup: the backward runs packed
     if (ws->pk_cnt[lvl] && KS == 32 && d.maxt_f == 1 && split == (lvl >= 1) && a.nb3 * (P / 32) == 2 * NW &&
         blocks * blk + 2 * P <= (P - 1) * a.C3 && (P * a.C3) % blk == 0) {
         a.pk_desc = ws->pk_desc[lvl] + prob * grid.x;
         a.pk_tab_off = blocks * blk;
         const int pblocks = P * a.C3 / blk;
+        if (pkm) {
+            switch (PSG_CFG_KEY(P, NW, KS, split ? 1 : 0)) {
+            case PSG_CFG_KEY(128, 4, 32, 0): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<128, 4, false, true>), grid, 4 * 64, pblocks, blk, a, st);
+            }
+            set_error("run_sa_fwd level %d: PSG_PN2_PACK_BWD names a level without a packed-key forward kernel (P=%d NW=%d)", lvl, P, NW);
+            return PSG_ERR_STATE;
+        }
         switch (PSG_CFG_KEY(P, NW, KS, split ? 1 : 0)) {
         case PSG_CFG_KEY(128, 4, 32, 0): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<128, 4, false>), grid, 4 * 64, pblocks, blk, a, st);
         case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<64, 4, true>), grid, 4 * 64, pblocks, blk, a, st);
@@ -424,6 +466,10 @@ int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const
         case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 8, true>), grid, 8 * 64, pblocks, blk, a, st);
         }
         a.pk_desc = nullptr; a.pk_tab_off = 0;
+    }
+    if (pkm) {
+        set_error("run_sa_fwd level %d: the packed backward (PSG_PN2_PACK_BWD) needs the packed forward, which this configuration does not run", lvl);
+        return PSG_ERR_STATE;
     }
 #define PSG_SA_FWD_CASE(P_, NW_, KS_, MT_) \
     case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
@@ -531,7 +577,17 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     // sparse: item list [NT] int2, count / offset table [NW][32], row starts [P + 1]
     a.sp_off = round_up(a.pos_off + P, 4);
     a.w3r = spv ? L[2].wr : nullptr;
-    const int staged = spv ? a.sp_off + 2 * NT + NW * 32 + P + 1 : a.pos_off + P;
+    // packed backward: the same packed rows as the level's forward, masks at the packed key (sa_pack_bwd_level).  Its row map
+    // [P] lies behind the output slots; the pooled-output gradient must be plain rows (the split level above sums them per point)
+    const bool packed = sa_pack_bwd_level(m, ws, lvl);
+    if (packed) {
+        if (spv || a.split || !a.dout || a.nninv_off || a.ginv_off || ((a.ld | a.c_off) & 3) || (C3 & 7) ||
+            PSG_CFG_KEY(P, NW, KS, d.maxt_b) != PSG_CFG_KEY(128, 4, 32, 1)) {
+            set_error("run_sa_bwd level %d: PSG_PN2_PACK_BWD names a level without a packed backward kernel in this configuration", lvl);
+            return PSG_ERR_STATE;
+        }
+    }
+    const int staged = spv ? a.sp_off + 2 * NT + NW * 32 + P + 1 : a.pos_off + P + (packed ? P : 0);
     const int blocks = main_blocks + ceil_div(staged, blk_floats);
     if (std::max(std::max(a.l3t.mb, a.l2t.mb), a.split ? 0 : a.l1t.mb) * (P / 32) > d.maxt_b * NW) {
         set_error("run_sa_bwd level %d scale %d: more than %d tiles per wave in a layer", lvl, sc, d.maxt_b);
@@ -539,6 +595,11 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     }
     const dim3 grid(S / (P / KS), B);
     const int tag = TAG_SA_BWD + lvl;
+    if (packed) {
+        const SaBwdPackedArgs pa{a, ws->pk_desc[lvl] + prob * grid.x};
+        if (a.w1c) return launch_lds(ws, tag, PSG_SITE "#colour#bwd#packed", (sa_bwd_packed_kernel<128, 4, 1, 0>), grid, 4 * 64, blocks, Lds<128>::BLK, pa, st);
+        return launch_lds(ws, tag, PSG_SITE "#bwd#packed", (sa_bwd_packed_kernel<128, 4, 1, 0>), grid, 4 * 64, blocks, Lds<128>::BLK, pa, st);
+    }
 #define PSG_SA_BWD_CASE(P_, NW_, KS_, MT_) \
     case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
         if (a.w1c) return launch_lds(ws, tag, PSG_SITE "#colour", (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st); \

@@ -87,6 +87,13 @@ struct SaBwdArgs {
     int diag;             // timing diagnostics only (-DPSG_DIAG_BUILD libraries only)
 };
 
+// sa_bwd_packed_kernel: the above (its row map [P] lies behind the P output slots at pos_off) and the workgroup descriptors the
+// packed forward of the level ran on
+struct SaBwdPackedArgs {
+    SaBwdArgs a;
+    const int4 *pk_desc;  // [B][gridDim.x]
+};
+
 struct FpFwdArgs {
     const float *feat1;     // skip features [B][N][C1] or null
     const float *feat2;     // coarse features [B][S][C2]
@@ -197,9 +204,10 @@ __device__ __forceinline__ void sa_layer1_split(const SaFwdArgs &a, int b, int s
 }
 
 // the workgroup (bx, b) of sa_fwd_kernel: groups [bx * G, (bx + 1) * G) of room b (also what sa_fwd_packed_kernel runs for a
-// workgroup of full groups on that boundary)
-template <int P, int NW, int KS, int MAXT, bool SPLIT>
-__device__ __forceinline__ void sa_fwd_body(SaFwdArgs a, int bx, int b)
+// workgroup of full groups on that boundary).  wg keys the workgroup's ReLU mask slots: the linear index of (bx, b), or
+// (KEYED) the packed workgroup's own where the masks are keyed by packed workgroup (sa_fwd_packed_kernel, PKM)
+template <int P, int NW, int KS, int MAXT, bool SPLIT, bool KEYED = false>
+__device__ __forceinline__ void sa_fwd_body(SaFwdArgs a, int bx, int b, size_t key = 0)
 {
     using L = Lds<P>;
     static_assert(KS == 32 || KS == 16, "groups of 32 or 16 samples");
@@ -208,7 +216,7 @@ __device__ __forceinline__ void sa_fwd_body(SaFwdArgs a, int bx, int b)
     float *buf0 = lds;   // the one activation buffer (layers run in place)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s0 = bx * G;
-    const size_t wg = (size_t)b * gridDim.x + bx;
+    const size_t wg = KEYED ? key : (size_t)b * gridDim.x + bx;
 
     if (SPLIT) {
         // block 0 of the buffer = [x_j - c_i, 0 x 5] of the P grouped rows; the feature part arrives through T (below)
@@ -380,7 +388,7 @@ __global__ __launch_bounds__(256) void sa_pack_plan_kernel(const int32_t *__rest
                                                            int32_t *__restrict__ cnt, int32_t *__restrict__ seg,
                                                            int4 *__restrict__ desc)
 {
-    __shared__ int s_cnt[1024];
+    __shared__ int s_cnt[1024], s_next[1024], s_first[1025], s_nseg;
     const size_t p = blockIdx.x;
     const int32_t *gi = gidx + p * S * 32;
     for (int s = threadIdx.x; s < S; s += 256) {
@@ -395,29 +403,42 @@ __global__ __launch_bounds__(256) void sa_pack_plan_kernel(const int32_t *__rest
         cnt[p * S + s] = n;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int gx = S / (P / 32);
-        int32_t *sg = seg + p * (gx + 2);
-        int4 *dg = desc + p * gx;
-        int nseg = 0, s = 0;
-        while (s < S) {
-            sg[1 + nseg] = s;
-            int rows = 0, g = 0;
-            int4 d = make_int4(s, 0, 0, 0);
-            while (s < S && g < SA_PACK_GCAP) {
-                const int c = s_cnt[s];
-                if (!(rows + c < P || (rows + c == P && rows == 32 * g && g + 1 == P / 32))) break;
-                const int f = (c - 1) << (5 * (g % 6));
-                if (g < 6) d.y |= f; else if (g < 12) d.z |= f; else d.w |= f;
-                rows += c; ++s; ++g;
-            }
-            d.x |= g << 16;
-            dg[nseg] = d;
-            ++nseg;
+    // every group's segment end, had a segment begun there (the greedy rule, at most SA_PACK_GCAP steps): all S in parallel
+    for (int s0 = threadIdx.x; s0 < S; s0 += 256) {
+        int s = s0, rows = 0, g = 0;
+        while (s < S && g < SA_PACK_GCAP) {
+            const int c = s_cnt[s];
+            if (!(rows + c < P || (rows + c == P && rows == 32 * g && g + 1 == P / 32))) break;
+            rows += c; ++s; ++g;
         }
-        sg[0] = nseg;
-        sg[1 + nseg] = S;
-        for (int i = nseg; i < gx; ++i) dg[i] = make_int4(0, 0, 0, 0);
+        s_next[s0] = s;
+    }
+    __syncthreads();
+    // the chain of segment starts is all that stays serial: one LDS read per segment
+    const int gx = S / (P / 32);
+    int32_t *sg = seg + p * (gx + 2);
+    int4 *dg = desc + p * gx;
+    if (threadIdx.x == 0) {
+        int nseg = 0;
+        for (int s = 0; s < S; s = s_next[s]) s_first[nseg++] = s;
+        s_first[nseg] = S;
+        s_nseg = nseg;
+    }
+    __syncthreads();
+    const int nseg = s_nseg;
+    for (int i = threadIdx.x; i <= nseg; i += 256) sg[1 + i] = s_first[i];
+    if (threadIdx.x == 0) sg[0] = nseg;
+    for (int i = threadIdx.x; i < gx; i += 256) {
+        int4 d = make_int4(0, 0, 0, 0);
+        if (i < nseg) {
+            const int lo = s_first[i], n = s_first[i + 1] - lo;
+            d.x = lo | (n << 16);
+            for (int g = 0; g < n; ++g) {
+                const int f = (s_cnt[lo + g] - 1) << (5 * (g % 6));
+                if (g < 6) d.y |= f; else if (g < 12) d.z |= f; else d.w |= f;
+            }
+        }
+        dg[i] = d;
     }
 }
 
@@ -428,7 +449,8 @@ __global__ __launch_bounds__(256) void sa_pack_plan_kernel(const int32_t *__rest
 //     the same bits;
 //   * ReLU masks go to the slots of the UNPACKED layout (workgroup s / G, tile (mb, s % G), lane (h, k)), one 2-byte store per
 //     lane: the backward kernels read them where they always did.  The words of padding rows are not written: their gradient
-//     rows are exactly zero before the mask is applied (AND with a zero) and are not stored (gpos_out = -1);
+//     rows are exactly zero before the mask is applied (AND with a zero) and are not stored (gpos_out = -1).  Where the level's
+//     backward runs packed too (PKM, below) the words are keyed by packed workgroup and block instead;
 //   * max-pool: groups are runs of packed rows that may cross a block, so the last layer's tiles go to LDS as plain rows
 //     [row][C3] (over the dead activation buffer: P x C3 floats, twice the buffer) and one thread per (group, channel) scans
 //     the group's rows in ascending order with a strict compare - the lowest row that attains the maximum, as the in-register
@@ -467,11 +489,11 @@ __device__ __forceinline__ size_t sa_pack_mask_slot(int om, int b, int gx, int m
     return ((wgo * lmb + mb) * G + (s % G)) * 64 + h * 32 + k;
 }
 
-template <int P, int NW>
+template <int P, int NW, bool PKM>
 __device__ __forceinline__ void sa_layer_fwd_packed(const FwdLayer &L, float *__restrict__ buf, int nblk, int first,
-                                                    const int *__restrict__ omap, int b)
+                                                    const int *__restrict__ omap, int b, size_t wg)
 {
-    constexpr int BLK = Lds<P>::BLK;
+    constexpr int BLK = Lds<P>::BLK, PB = P / 32;
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     const bool act = first < L.mb * nblk;
     int mb = 0, pb = 0;
@@ -489,15 +511,24 @@ __device__ __forceinline__ void sa_layer_fwd_packed(const FwdLayer &L, float *__
         c[12] += bq3.x; c[13] += bq3.y; c[14] += bq3.z; c[15] += bq3.w;
         if (L.relu) {
             const unsigned m = relu_bits(c);
-            const int om = omap[pb * 32 + j];
-            if (L.mask && om >= 0) L.mask[sa_pack_mask_slot<P>(om, b, gridDim.x, mb, L.mb, h)] = (uint16_t)m;
+            if constexpr (PKM) {
+                if (L.mask) L.mask[((wg * L.mb + mb) * PB + pb) * 64 + lane] = (uint16_t)m;
+            } else {
+                const int om = omap[pb * 32 + j];
+                if (L.mask && om >= 0) L.mask[sa_pack_mask_slot<P>(om, b, gridDim.x, mb, L.mb, h)] = (uint16_t)m;
+            }
         }
     }
     __syncthreads();
     if (act) store_tile<P>(buf, mb, pb * 32 + j, h, c);
 }
 
-template <int P, int NW, bool SPLIT>
+// PKM (the levels whose backward is sa_bwd_packed_kernel; psg_pn2.hip: sa_pack_bwd_level): the ReLU mask word of tile (mb, pb)
+// goes to slot ((wg * L.mb + mb) * PB + pb) * 64 + lane of the PACKED workgroup wg - where layer_bwd looks for task mb * PB + pb
+// of workgroup wg, so the level's backward runs on the same packed rows.  One coalesced store per wave and no row map; the
+// words of tail rows land in slots this workgroup owns (their gradient is zero).  The buffers keep their size: wg, mb and pb
+// stay inside the unpacked extents.  PKM = false is the kernel of round 16, instruction for instruction.
+template <int P, int NW, bool SPLIT, bool PKM = false>
 __global__ __launch_bounds__(NW * 64) void sa_fwd_packed_kernel(SaFwdArgs a)
 {
     using L = Lds<P>;
@@ -518,7 +549,9 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_packed_kernel(SaFwdArgs a)
         int rows = 0;
         for (int i = 0; i < PB; ++i) rows += sa_pack_cnt(desc, i);
         if (rows == P) {
-            sa_fwd_body<P, NW, 32, 1, SPLIT>(a, sA / PB, b);
+            // (the mask key is separate from the group origin: unpacked-keyed, slot sA / PB is this workgroup's; packed-keyed
+            // it belongs to another workgroup)
+            sa_fwd_body<P, NW, 32, 1, SPLIT, PKM>(a, sA / PB, b, wg);
             return;
         }
     }
@@ -543,7 +576,7 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_packed_kernel(SaFwdArgs a)
             const int k = pe - st, s = sA + g;
             const int src = a.gidx[((size_t)b * a.S + s) * 32 + k];
             if (part == 0) {
-                omap[j] = j < nrows ? s * 32 + k : -1;
+                if constexpr (!PKM) omap[j] = j < nrows ? s * 32 + k : -1;
                 srcl[j] = src;
             }
             const float *xr = a.xyz + ((size_t)b * a.Np + src) * a.xyz_stride;
@@ -604,16 +637,20 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_packed_kernel(SaFwdArgs a)
             c = mfma4<false>(wx, rx, c);
             mfma_fence(c);
             const unsigned m = relu_bits(c);
-            const int om = omap[pb * 32 + jj];
-            if (L1.mask && om >= 0) L1.mask[sa_pack_mask_slot<P>(om, b, gridDim.x, mb, L1.mb, h)] = (uint16_t)m;
+            if constexpr (PKM) {
+                if (L1.mask) L1.mask[((wg * L1.mb + mb) * PB + pb) * 64 + lane] = (uint16_t)m;
+            } else {
+                const int om = omap[pb * 32 + jj];
+                if (L1.mask && om >= 0) L1.mask[sa_pack_mask_slot<P>(om, b, gridDim.x, mb, L1.mb, h)] = (uint16_t)m;
+            }
         }
         __syncthreads();
         if (act) store_tile<P>(buf0, mb, pb * 32 + jj, h, c);
     } else {
-        sa_layer_fwd_packed<P, NW>(a.l1, buf0, nblk, first, omap, b);
+        sa_layer_fwd_packed<P, NW, PKM>(a.l1, buf0, nblk, first, omap, b, wg);
     }
     __syncthreads();
-    sa_layer_fwd_packed<P, NW>(a.l2, buf0, nblk, first, omap, b);
+    sa_layer_fwd_packed<P, NW, PKM>(a.l2, buf0, nblk, first, omap, b, wg);
     __syncthreads();
 
     // last layer, tile flipped (D[point][channel]): two tiles per wave, as sa_fwd_kernel deals them
@@ -887,8 +924,9 @@ __device__ __forceinline__ void sa_pool_t_sparse(const SaBwdArgs &a, float *__re
 
 // SPV > 0: the max-pool transpose runs as the sparse stream above (sa_pool_t_sparse) instead of dZ3 in LDS + the dense l3t
 // (the kernels sa_bwd_kernel / sa_bwd_sparse_kernel below)
-template <int P, int NW, int MAXT, int KS, int SPV>
-__device__ __forceinline__ void sa_bwd_body(const SaBwdArgs &a)
+// KEYED (sa_bwd_packed_kernel, a workgroup of full groups): the workgroup (kbx, kb) with its ReLU masks at the slots of workgroup kwg
+template <int P, int NW, int MAXT, int KS, int SPV, bool KEYED = false>
+__device__ __forceinline__ void sa_bwd_body(const SaBwdArgs &a, int kbx = 0, int kb = 0, size_t kwg = 0)
 {
     using L = Lds<P>;
     static_assert(KS == 32 || KS == 16, "groups of 32 or 16 samples");
@@ -899,9 +937,10 @@ __device__ __forceinline__ void sa_bwd_body(const SaBwdArgs &a)
     float *buf0 = lds;   // the one activation buffer (layers run in place)
     const int tid = threadIdx.x;
     int bx, b;
-    xcd_tile(bx, b);
+    if constexpr (KEYED) { bx = kbx; b = kb; }
+    else xcd_tile(bx, b);
     const int s0 = bx * G;
-    const size_t wg = (size_t)b * gridDim.x + bx;
+    const size_t wg = KEYED ? kwg : (size_t)b * gridDim.x + bx;
 
     // gradient of the pooled output: read directly, or gathered (no atomics, fixed summation order) from the
     // interpolated-part rows of the feature-propagation module that upsampled this level
@@ -1073,6 +1112,182 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_kernel(SaBwdArgs a) { sa_bwd_b
 // SSG levels 1 - 3 with the sparse max-pool transpose (run_sa_bwd: PSG_PN2_POOLT_SPARSE); SPV = C2 / 64
 template <int P, int NW, int MAXT, int SPV>
 __global__ __launch_bounds__(NW * 64) void sa_bwd_sparse_kernel(SaBwdArgs a) { sa_bwd_body<P, NW, MAXT, 32, SPV>(a); }
+
+// ------------------------------------------------------------------------------------------ SA bwd, packed
+// The backward of a level whose forward ran packed (sa_fwd_packed_kernel<.., PKM>), over the same packed rows through the same
+// descriptors: a padding row's gradient is exactly zero before any mask is applied and is never stored (gpos_out = -1), so
+// the transposed layers run over the workgroup's nblk = ceil(nrows / 32) active blocks only.  Launched on the unpacked grid
+// (fixed launch shape, nothing read back); a surplus workgroup returns on its zero descriptor.
+//   * masks: read at the packed key ((wg * L.mb + mb) * PB + pb) * 64 + lane, where the packed forward stored them;
+//   * tile columns are independent and every valid row passes through the k-loops and epilogues it had unpacked: the rows
+//     stored are the same bytes as sa_bwd_kernel's;
+//   * a workgroup of P / 32 full groups on an unpacked boundary runs sa_bwd_body with that origin and its own mask key, at
+//     sa_bwd_kernel's cost (rooms with nothing to skip); an unaligned one takes the packed path with nrows == P;
+//   * stores go to gsa_out through gpos_out[group * 32 + sample], looked up through the row map: the consumers see the
+//     layout they always saw.
+// SPV = 0 (dense max-pool transpose, SSG level 0) is what is built: the pooled-output gradient of that level arrives as plain
+// rows (a.dout = the per-point sums of the split level above: run_sa_bwd checks), so dZ3 is built per (packed row, 8-channel
+// block) straight from those rows and the arg-max bytes - the loads sa_bwd_kernel issues per (row, block), without its
+// staging pass.  LDS: sa_bwd_kernel's of the level plus the row map [P] in its staging block (the same number of blocks).
+template <int P, int NW, int MAXT>
+__device__ __forceinline__ void sa_layer_bwd_packed(const BwdLayer &L, float *__restrict__ buf, int nblk, size_t wg)
+{
+    constexpr int PB = P / 32, BLK = Lds<P>::BLK;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int ntask = L.mb * nblk;
+    const int first = (wave + (int)(wg & (NW - 1))) & (NW - 1);
+    f32x16 acc[MAXT];
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+        const int task = first + i * NW;
+        if (task < ntask) {
+            const int mb = task / nblk, pb = task - mb * nblk;
+            unsigned m = 0xFFFFu;
+            if (L.mask) m = L.mask[((wg * L.mb + mb) * PB + pb) * 64 + lane];
+            f32x16 c;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c[r] = 0.0f;
+            c = tile_mac<BLK, false>(L.w + (size_t)mb * L.k8 * 64 + lane, L.k8, buf + (pb * 32 + j) * 8 + 4 * h, c);
+            apply_bits(c, m);
+            acc[i] = c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+        const int task = first + i * NW;
+        if (task < ntask) {
+            const int mb = task / nblk, pb = task - mb * nblk;
+            store_tile<P>(buf, mb, pb * 32 + j, h, acc[i]);
+        }
+    }
+}
+
+template <int P, int NW, int MAXT, int SPV>
+__global__ __launch_bounds__(NW * 64) void sa_bwd_packed_kernel(SaBwdPackedArgs pa)
+{
+    const SaBwdArgs &a = pa.a;
+    using L = Lds<P>;
+    static_assert(SPV == 0 && MAXT == 1 && P == 32 * NW, "built: the dense level, one tile per wave");
+    constexpr int PB = P / 32, NT = NW * 64, KS = 32;
+    extern __shared__ float lds[];
+    float *buf0 = lds;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    int bx, b;
+    xcd_tile(bx, b);
+    const size_t wg = (size_t)b * gridDim.x + bx;
+    const int4 desc = pa.pk_desc[wg];
+    const int ng = desc.x >> 16, sA = desc.x & 0xFFFF;
+    if (ng == 0) return;                                        // surplus workgroup (uniform: no barrier has been reached)
+    // packed row tid lies in group rg_g, which starts at packed row rg_st (a uniform walk over the descriptor's counts: the
+    // per-lane search of the forward would index the descriptor by lane)
+    int nrows = 0, rg_g = 0, rg_st = 0;
+    for (int i = 0; i < ng; ++i) {
+        if (tid >= nrows) { rg_g = i; rg_st = nrows; }
+        nrows += sa_pack_cnt(desc, i);
+    }
+    if (ng == PB && (sA & (PB - 1)) == 0 && nrows == P) {       // nothing to skip: sa_bwd_kernel's body, masks at this key
+        sa_bwd_body<P, NW, MAXT, KS, 0, true>(a, sA / PB, b, wg);
+        return;
+    }
+    const int nblk = (nrows + 31) >> 5, nact = nblk * 32;
+    float *dsrc = lds + (size_t)a.dsrc_blk * L::BLK;
+    int32_t *s_pos = (int32_t *)(dsrc + a.pos_off);             // [P] output slot of a packed row, -1 = padding or tail
+    int *s_row = s_pos + P;                                     // [P] local group << 5 | sample of a packed row, -1 = tail
+    if (tid < P) {
+        int om = -1, pj = -1;
+        if (tid < nrows) {
+            const int k = tid - rg_st;
+            om = (rg_g << 5) | k;
+            pj = a.gpos_out[(size_t)b * a.S * KS + (size_t)(sA + rg_g) * KS + k];
+        }
+        s_row[tid] = om;
+        s_pos[tid] = pj;
+    }
+    if (a.w1c && tid < 3 * a.C1) {   // sa_bwd_body's table [half][column][C1 / 2] of the wanted columns
+        const int kh = a.C1 >> 1, hh = tid / (3 * kh), r = (tid / kh) % 3, cc = tid % kh;
+        dsrc[a.w1c_off + tid] = a.w1c[(hh * kh + cc) * a.D + a.c_lo + r];
+    }
+    __syncthreads();
+    // max-pool backward over the active blocks: dZ3[c][row] = dout[group][c] if sample == arg[group][c] else 0; a half-wave
+    // takes (8-channel block, 32-row block) q = blk * nblk + pb, nblk rounds for every thread
+    {
+        const float *drows = a.dout + (size_t)b * a.S * a.ld + a.c_off;
+        const uint8_t *arows = a.arg + (size_t)b * a.S * a.C3;
+        const int nq = nblk * (a.C3 >> 3);
+        const int rcp = (65536 + nblk - 1) / nblk;              // q / nblk = q * rcp >> 16 (q < 2^9, nblk <= P / 32)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                           // (P * C3 / 8 tasks at most: four per thread, run_sa_bwd checks)
+            const int q = (tid >> 5) + i * (NT / 32);
+            if (q < nq) {
+                const int blk = (q * rcp) >> 16, pb = q - blk * nblk, j = pb * 32 + (tid & 31);
+                const int om = s_row[j];
+                float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+                if (om >= 0) {
+                    const int s = sA + (om >> 5), k = om & 31;
+                    const uint2 am = *(const uint2 *)(arows + (size_t)s * a.C3 + blk * 8);
+                    const float *dp = drows + (size_t)s * a.ld + blk * 8;
+                    const float4 d0 = *(const float4 *)dp, d1 = *(const float4 *)(dp + 4);
+                    v0.x = (int)(am.x & 0xFF) == k ? d0.x : 0.f;
+                    v0.y = (int)((am.x >> 8) & 0xFF) == k ? d0.y : 0.f;
+                    v0.z = (int)((am.x >> 16) & 0xFF) == k ? d0.z : 0.f;
+                    v0.w = (int)(am.x >> 24) == k ? d0.w : 0.f;
+                    v1.x = (int)(am.y & 0xFF) == k ? d1.x : 0.f;
+                    v1.y = (int)((am.y >> 8) & 0xFF) == k ? d1.y : 0.f;
+                    v1.z = (int)((am.y >> 16) & 0xFF) == k ? d1.z : 0.f;
+                    v1.w = (int)(am.y >> 24) == k ? d1.w : 0.f;
+                }
+                float *dst = buf0 + (size_t)blk * L::BLK + j * 8;
+                *(float4 *)dst = v0;
+                *(float4 *)(dst + 4) = v1;
+            }
+        }
+    }
+    __syncthreads();
+    sa_layer_bwd_packed<P, NW, MAXT>(a.l3t, buf0, nblk, wg);
+    __syncthreads();
+    sa_layer_bwd_packed<P, NW, MAXT>(a.l2t, buf0, nblk, wg);
+    __syncthreads();
+    if (a.w1c) {   // colour-only request: wave w takes block w (sa_l1t_colour), its slots from the row map
+        if (wave < nblk) {
+            float *orowc = a.gsa_out + (size_t)b * a.S * KS * 4;
+            if (a.C1 == 32) sa_l1t_colour<P, NW, 32>(a, buf0, dsrc + a.w1c_off, s_pos, orowc);
+            else sa_l1t_colour<P, NW, 16>(a, buf0, dsrc + a.w1c_off, s_pos, orowc);
+        }
+        return;
+    }
+    if (!a.split) {
+        sa_layer_bwd_packed<P, NW, MAXT>(a.l1t, buf0, nblk, wg);   // (no mask: run_sa_bwd leaves l1t.mask null)
+        __syncthreads();
+    }
+    // the three store paths of sa_bwd_body over the active rows
+    const int nc = a.c_hi - a.c_lo;
+    const int32_t *pos = s_pos;
+    float *orow = a.gsa_out + (size_t)b * a.S * KS * a.cg_out;
+    if (a.cg_out == 4) {
+        for (int j = tid; j < nact; j += NT) {
+            const float4 v = make_float4(buf0[L::off(a.c_lo, j)], buf0[L::off(a.c_lo + 1, j)], buf0[L::off(a.c_lo + 2, j)], 0.0f);
+            if (pos[j] >= 0) *(float4 *)(orow + (size_t)pos[j] * 4) = v;
+        }
+        return;
+    }
+    if (((nc | a.c_lo | a.cg_out) & 3) == 0) {
+        constexpr int RG = NT / 32;
+        const int ql = tid & 31, rg = tid >> 5;
+        for (int j = rg; j < nact; j += RG) {
+            const int pj = pos[j];
+            if (pj < 0) continue;
+            float *o = orow + (size_t)pj * a.cg_out + a.c_lo;
+            for (int q = ql; q < (nc >> 2); q += 32) *(float4 *)(o + 4 * q) = *(const float4 *)(buf0 + L::off(a.c_lo + 4 * q, j));
+        }
+        return;
+    }
+    for (int t = tid; t < nact * nc; t += NT) {
+        const int j = t / nc, c = a.c_lo + (t - j * nc);
+        if (pos[j] >= 0) orow[(size_t)pos[j] * a.cg_out + c] = buf0[L::off(c, j)];
+    }
+}
 
 // ------------------------------------------------------------------------------------------ FP fwd
 // FP split (round 5): the 3-NN interpolation is linear, so the interpolated part of a module's first layer commutes with it,

@@ -3,9 +3,11 @@
 
 At --shrink 0.25 every level-0 ball of a 4096-point room is full: the packed SA forward (PSG_PN2_PACK, default on) has nothing
 to skip there and must cost what the unpacked kernel does.  Run once per value of PSG_PN2_PACK (read once per process) and
-compare the sa*_fwd rows; the other rows are kernels the switch does not touch and show the run-to-run spread.
+compare the sa*_fwd rows; the other rows are kernels the switch does not touch and show the run-to-run spread.  The same holds
+for the packed SA backward (PSG_PN2_PACK_BWD, default on where a level has the kernel): run under PSG_PN2_PACK_BWD=0 and unset,
+alternated, and compare the sa*_bwd rows - full workgroups run the unpacked backward body there.
 
-usage: [PSG_PN2_PACK=0] tools/sa_pack_probe.py [--rooms 64] [--shrink 0.25] [--iters 20] [--out FILE.json]"""
+usage: [PSG_PN2_PACK=0] [PSG_PN2_PACK_BWD=0] tools/sa_pack_probe.py [--rooms 64] [--shrink 0.25] [--iters 20] [--out FILE.json]"""
 import argparse
 import json
 import os
@@ -54,9 +56,11 @@ def main():
         iteration()
     torch.cuda.synchronize()
     prof = ws.prof_read()
-    res = {"PSG_PN2_PACK": os.environ.get("PSG_PN2_PACK", "1"), "rooms": R, "shrink": a.shrink,
-           "us_per_launch": {k: round(1000.0 * ms / n, 2) for k, (ms, n) in sorted(prof.items())}}
+    us = {k: round(1000.0 * ms / n, 2) for k, (ms, n) in sorted(prof.items())}
+    res = {"PSG_PN2_PACK": os.environ.get("PSG_PN2_PACK", "1"), "PSG_PN2_PACK_BWD": os.environ.get("PSG_PN2_PACK_BWD", "1"),
+           "rooms": R, "shrink": a.shrink, "us_per_launch": us}
     print(json.dumps(res))
+    print("sa backward:", " ".join("%s %.2f" % (k, v) for k, v in us.items() if k.startswith("sa") and k.endswith("_bwd")))
     if a.out:
         with open(a.out, "w") as fh:
             json.dump(res, fh, indent=1)
