@@ -848,6 +848,69 @@ int psg_rla_nu_adam_step(const float *xs, float *dws, float *m, float *v, const 
 int psg_rla_bim_attack(psg_rla_model *model, psg_rla_ws *ws, const float *features, const int32_t *labels, float eps,
                        float alpha, int iters, int l2_metric, float *adv_features_out, psg_stream stream);
 
+/* NUattack / tar_NUattack on G clouds of n points in lockstep.  Every buffer is cloud-major; `active` [G] is a byte per cloud
+ * (NULL: every cloud is active) and an inactive cloud is not touched by any of these calls.  No float atomics: two runs give
+ * the same bits, and a cloud's results do not depend on which other clouds are active.
+ *
+ * psg_rla_nu_color_clouds: feat [G][n][6] columns 3..5 = adv(d_ws) with psg_rla_nu_color's arithmetic (mask [G][n] or NULL:
+ * only those points move) and dist2[g] = |adv - x|_2^2, summed in double in a fixed order by PSG_RLA_NU_PARTS workgroups per
+ * cloud (partials: [G][PSG_RLA_NU_PARTS] doubles of scratch) and rounded to float once. */
+#define PSG_RLA_NU_PARTS 32
+int psg_rla_nu_color_clouds(const float *xs, const float *dws, const uint8_t *mask, const uint8_t *active, int G, int n, float *feat,
+                            float *dist2, double *partials, psg_stream stream);
+/* psg_rla_nu_adam_step's update of every active cloud with its own dist2[g].  lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) is computed
+ * in double on the host; inside a replayed window it is read from the window's step-constant device row instead. */
+int psg_rla_nu_adam_clouds(const float *xs, float *dws, float *m, float *v, const uint8_t *mask, const uint8_t *active,
+                           const float *feat, const float *dfeat, const float *dist2, int G, int n, float c, float lr, int t,
+                           psg_stream stream);
+/* The evaluation the reference makes after every optimiser step (NUattack.py:190-213, tar_NUattack.py:235), for every active
+ * cloud: pred [G][n] = the first maximum of logits [G][n][13], n_correct = #(pred == labels), n_hits = #(mask & pred == ys)
+ * (0 without a mask); hist_row [G][3] = {n_correct, n_hits, dist2[g]}.  The exit test is in integers: mode 0
+ * den * n_correct < num * n, mode 1 den * n_hits > num * n_mask[g].  When it fires, can_exit != 0 and step >= 1 (the
+ * unperturbed start is never tested), the cloud is snapshot - out_adv [G][n][3] = the colours of feat, out_pred [G][n],
+ * out_stats [G][3] = the history row - exit_step[g] = step and active[g] = 0; final != 0 snapshots every active cloud
+ * without marking an exit.  scratch: [G][2 * PSG_RLA_NU_PARTS + 1] int32.  active and exit_step are required here. */
+int psg_rla_nu_latch_clouds(const float *logits, const int32_t *labels, const int32_t *ys, const uint8_t *mask, const int32_t *n_mask,
+                            const float *feat, const float *dist2, int G, int n, int mode, int num, int den, int step, int can_exit,
+                            int final, float *hist_row, int32_t *pred, float *out_adv, int32_t *out_pred, float *out_stats,
+                            uint8_t *active, int32_t *exit_step, int32_t *scratch, psg_stream stream);
+
+/* One window of the lockstep attack: for each of n_steps optimiser steps with Adam index t = adam_t0 + i (adam_t0 >= 1):
+ * colour, psg_rla_forward, latch of evaluation index t - 1 (history row i; exits from index 1 on), the masked hinge gradient
+ * against ys (psg_rla_colper_grad_masked, sign +1), psg_rla_backward, Adam.  tail_eval != 0 appends colour, forward and a
+ * latch with final = 1 of the last step (history row n_steps).  Nothing returns to the host inside a window.  `graph` as for
+ * the other windows (first window of a shape eager, second captured, later ones replayed; a single chain on `stream`); no
+ * graph is used while psg_rla_prof_enable is on, before the first psg_rla_forward of (cloud, model), or when n_steps plus
+ * the tail exceed PSG_NU_GRAPH_MAX_STEPS.  ws: a workspace of
+ * G clouds of N points with the clouds set. */
+typedef struct psg_rla_nu_window_args {
+    psg_rla_model *model;
+    psg_rla_ws *ws;
+    int n_steps, G, N, mode;
+    int num, den;                /* the exit threshold num / den */
+    int adam_t0, tail_eval;
+    float cs, lr;
+    const float *xs;             /* [G][N][3] clean colours */
+    float *dws, *m, *v;          /* [G][N][3] */
+    const uint8_t *mask;         /* [G][N], nullable (required in mode 1) */
+    const int32_t *n_mask;       /* [G], mode 1 */
+    const int32_t *labels, *ys;  /* [G][N]: the true labels, the labels the hinge is taken against */
+    float *feat;                 /* [G][N][6], xyz in columns 0..2 */
+    float *logits, *dlogits;     /* [G][N][13] */
+    float *dfeat;                /* [G][N][6] */
+    float *dist2;                /* [G] */
+    double *partials;            /* [G][PSG_RLA_NU_PARTS] */
+    int32_t *pred;               /* [G][N] */
+    int32_t *scratch;            /* [G][2 * PSG_RLA_NU_PARTS + 1] */
+    float *hist;                 /* [n_steps + (tail_eval != 0)][G][3] */
+    float *out_adv;              /* [G][N][3] */
+    int32_t *out_pred;           /* [G][N] */
+    float *out_stats;            /* [G][3] */
+    uint8_t *active;             /* [G] */
+    int32_t *exit_step;          /* [G], -1 before */
+} psg_rla_nu_window_args;
+int psg_rla_nu_window(const psg_rla_nu_window_args *args, psg_nu_graph *graph, psg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

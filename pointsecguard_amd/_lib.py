@@ -151,6 +151,10 @@ SIGNATURES = {
     "psg_rla_nu_color": (ci, [vp, vp, vp, ci, vp, vp, vp]),
     "psg_rla_nu_adam_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, ci, vp]),
     "psg_rla_bim_attack": (ci, [vp, vp, vp, vp, cf, cf, ci, ci, vp, vp]),
+    "psg_rla_nu_color_clouds": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
+    "psg_rla_nu_adam_clouds": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, ci, vp]),
+    "psg_rla_nu_latch_clouds": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "psg_rla_nu_window": (ci, [vp, vp, vp]),
     "psg_seg_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
     "psg_vote_add": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]),
     "psg_vote_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
@@ -186,6 +190,18 @@ class GcnNuWindowArgs(ctypes.Structure):
                 [(n, cf) for n in ("kappa", "tsign", "c_f", "c_smooth", "c_l2", "lr", "beta1", "beta2", "eps")] +
                 [(n, vp) for n in ("w", "m", "v", "mask", "n_mask", "x0", "ori", "labels", "logits", "dlogits", "dx0", "sgrad", "pred",
                                    "scal", "nn_state", "hist", "out", "active", "exit_step")])
+
+
+RLA_NU_PARTS = 32        # PSG_RLA_NU_PARTS of include/psg.h
+
+
+class RlaNuWindowArgs(ctypes.Structure):
+    """psg_rla_nu_window_args of include/psg.h, field for field."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("n_steps", "G", "N", "mode", "num", "den", "adam_t0", "tail_eval")] +
+                [(n, cf) for n in ("cs", "lr")] +
+                [(n, vp) for n in ("xs", "dws", "m", "v", "mask", "n_mask", "labels", "ys", "feat", "logits", "dlogits", "dfeat", "dist2",
+                                   "partials", "pred", "scratch", "hist", "out_adv", "out_pred", "out_stats", "active", "exit_step")])
 
 
 class NuFieldArgs(ctypes.Structure):

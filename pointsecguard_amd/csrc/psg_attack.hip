@@ -1167,10 +1167,11 @@ extern "C" int psg_nu_graph_stats(const psg_nu_graph *g, long long *out4)
 }
 
 void psg::nu_set_step_consts(const float *row) { g_nu_dconsts = row; }
+const float *psg::nu_step_consts() { return g_nu_dconsts; }
 
 int psg::nu_graph_window(psg_nu_graph *graph, const void *key, size_t key_bytes, uint64_t model_gen, uint64_t ws_gen, int n_steps,
                          int step0, int adam_t0, float lr, float beta1, float beta2, hipStream_t st,
-                         const std::function<int(const float *)> &steps)
+                         const std::function<int(const float *)> &steps, const float *slot3)
 {
     // (PSG_NU_NO_GRAPH=1: eager windows, for counter passes - per-dispatch counter rows need per-dispatch launches)
     static const bool no_graph = psg::env_int("PSG_NU_NO_GRAPH", 0) != 0;
@@ -1182,7 +1183,7 @@ int psg::nu_graph_window(psg_nu_graph *graph, const void *key, size_t key_bytes,
         graph->host[4 * i] = __builtin_bit_cast(float, step0 + i);
         graph->host[4 * i + 1] = (float)((double)lr / bc1);
         graph->host[4 * i + 2] = (float)sqrt(bc2);
-        graph->host[4 * i + 3] = 0.0f;
+        graph->host[4 * i + 3] = slot3 ? slot3[i] : 0.0f;     // (psg_rla_nu_window: TF1 Adam's lr_t)
     }
     PSG_CHECK_HIP(hipMemcpyAsync(graph->dconsts, graph->host, (size_t)n_steps * 16, hipMemcpyHostToDevice, st));
     const bool same = graph->have_key && graph->key.size() == key_bytes && memcmp(graph->key.data(), key, key_bytes) == 0 &&

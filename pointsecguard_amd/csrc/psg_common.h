@@ -114,16 +114,19 @@ struct GraphSlot {
     void destroy();                  // in the handle's destructor
 };
 
-// The capture-or-replay policy of the NU windows (psg_attack.hip), shared by psg_pn2_nu_window and psg_pointnet_nu_window:
-// writes the step constants {step, lr / (1 - beta1^t), sqrt(1 - beta2^t), 0} of the window's n_steps steps into the handle's
+// The capture-or-replay policy of the NU windows (psg_attack.hip), shared by psg_pn2_nu_window, psg_pointnet_nu_window,
+// psg_gcn_nu_window and psg_rla_nu_window:
+// writes the step constants {step, lr / (1 - beta1^t), sqrt(1 - beta2^t), slot3 ? slot3[i] : 0} of the window's n_steps steps into the handle's
 // device rows, then runs `steps(rows)` eagerly (first window of a `key`, or after a failed capture), captures it (second
 // window) or replays the captured graph.  `key` is the window's argument block with what the device rows carry zeroed;
 // model_gen / ws_gen are the generation numbers of its handles.  graph == null: `steps(nullptr)`, eagerly.
 int nu_graph_window(psg_nu_graph *graph, const void *key, size_t key_bytes, uint64_t model_gen, uint64_t ws_gen, int n_steps,
                     int step0, int adam_t0, float lr, float beta1, float beta2, hipStream_t st,
-                    const std::function<int(const float *)> &steps);
-// While set (per host thread), psg_nu_adam_step(_rooms) and psg_nu_step_latch read their step constants from this device row.
+                    const std::function<int(const float *)> &steps, const float *slot3 = nullptr);
+// While set (per host thread), psg_nu_adam_step(_rooms), psg_nu_step_latch, psg_rla_nu_adam_clouds and psg_rla_nu_latch_clouds
+// read their step constants from this device row.
 void nu_set_step_consts(const float *row);
+const float *nu_step_consts();
 
 // Optional per-launch HIP-event timing of a workspace (psg_*_prof_enable / psg_*_prof_read): pairs of events recorded on
 // the LAUNCH stream around a launch (or a group of launches) with a tag and the algorithmic FLOPs of that launch; off in

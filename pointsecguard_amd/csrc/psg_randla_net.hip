@@ -1087,6 +1087,7 @@ struct LevelBuf {
 };
 
 struct psg_rla_ws {
+    uint64_t gen = psg::next_generation();   // never re-used (psg_common.h): what a replayed NU window is keyed on
     psg_ctx *ctx;
     int N = 0;                      // rows of all clouds: B * Nc
     int B = 1, Nc = 0;              // clouds per workspace (independent: every index stays inside its cloud), points per cloud
@@ -1958,4 +1959,266 @@ extern "C" int psg_rla_bim_attack(psg_rla_model *m, psg_rla_ws *ws, const float 
         if ((rc = iteration())) return rc;
     PSG_CHECK_HIP(hipMemcpyAsync(adv_features_out, ws->feat, N * 6 * 4, hipMemcpyDeviceToDevice, st));
     return PSG_OK;
+}
+
+// ---- NUattack / tar_NUattack on G clouds in lockstep (the batch workspace: one launch of every network kernel serves all
+// clouds).  blockIdx.y = cloud; a cloud whose `active` byte is clear is skipped by whole workgroups.  The reductions use no
+// float atomics: PSG_RLA_NU_PARTS workgroups per cloud each own a fixed slice and write one partial, a second kernel adds the
+// partials in index order - the same bits in every run, whatever the other clouds do.
+namespace {
+constexpr int kNuParts = PSG_RLA_NU_PARTS;
+
+__global__ __launch_bounds__(256) void nu_color_clouds_kernel(const float *__restrict__ xs, const float *__restrict__ dws,
+                                                              const uint8_t *__restrict__ mask, const uint8_t *__restrict__ active,
+                                                              size_t n, float *__restrict__ feat, double *__restrict__ partials)
+{
+    __shared__ double s_part[4];
+    const int g = blockIdx.y;
+    if (active && !active[g]) return;
+    const size_t base = (size_t)g * n;
+    double s = 0.0;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * 3; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t / 3;
+        const int c = (int)(t % 3);
+        const float x = xs[base * 3 + t];
+        const float w = atanhf(2.0f * kNuBound * x - kNuBound) + dws[base * 3 + t];
+        float adv = 0.5f * (tanhf(w) + 1.0f);
+        if (mask && !mask[base + i]) adv = x;
+        feat[(base + i) * 6 + 3 + c] = adv;
+        const double d = (double)adv - (double)x;       // exact; the sum is of the colours as written, like sq_norm_kernel's
+        s += d * d;
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[(size_t)g * gridDim.x + blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+}
+
+__global__ void nu_dist2_clouds_kernel(const double *__restrict__ partials, const uint8_t *__restrict__ active, int G, int parts,
+                                       float *__restrict__ dist2)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G || (active && !active[g])) return;
+    double tot = 0.0;
+    for (int p = 0; p < parts; ++p) tot += partials[(size_t)g * parts + p];
+    dist2[g] = (float)tot;
+}
+
+// nu_adam_kernel's update, expression for expression, with the cloud's own distance
+__global__ void nu_adam_clouds_kernel(const float *__restrict__ xs, float *__restrict__ dws, float *__restrict__ m, float *__restrict__ v,
+                                      const uint8_t *__restrict__ mask, const uint8_t *__restrict__ active,
+                                      const float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ dist2,
+                                      size_t n, float c, float lr_arg, const float *__restrict__ consts, float b1, float b2, float eps)
+{
+    const int g = blockIdx.y;
+    if (active && !active[g]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * 3) return;
+    const float lr_t = consts ? consts[3] : lr_arg;
+    const size_t i = (size_t)g * n + t / 3;
+    const int ch = (int)(t % 3);
+    t += (size_t)g * n * 3;
+    const float x = xs[t];
+    const float w = atanhf(2.0f * kNuBound * x - kNuBound) + dws[t];
+    const float th = tanhf(w);
+    const float adv = feat[i * 6 + 3 + ch];
+    const float dist = sqrtf(dist2[g]);
+    float gr = (dist > 0.0f ? (adv - x) / dist : 0.0f) + c * dfeat[i * 6 + 3 + ch];
+    gr *= (mask && !mask[i]) ? 0.0f : 0.5f * (1.0f - th * th);
+    const float mm = b1 * m[t] + (1.0f - b1) * gr;
+    const float vv = b2 * v[t] + (1.0f - b2) * gr * gr;
+    m[t] = mm;
+    v[t] = vv;
+    dws[t] -= lr_t * mm / (sqrtf(vv) + eps);
+}
+
+// Latch, first half: pred = first maximum of the 13 logits; every workgroup counts its slice of the cloud into
+// scratch[g][1 + 2 part + {0, 1}] = {#(pred == labels), #(mask & pred == ys)}; scratch[g][0] = was the cloud active when the
+// latch began (the second half clears `active`, so its workgroups must not read it)
+__global__ __launch_bounds__(256) void nu_latch_count_kernel(const float *__restrict__ logits, const int32_t *__restrict__ labels,
+                                                             const int32_t *__restrict__ ys, const uint8_t *__restrict__ mask,
+                                                             const uint8_t *__restrict__ active, int n, int32_t *__restrict__ pred,
+                                                             int32_t *__restrict__ scratch)
+{
+    __shared__ int s_cnt[4][2];
+    const int g = blockIdx.y, parts = gridDim.x;
+    int32_t *sc = scratch + (size_t)g * (2 * parts + 1);
+    const bool live = active[g] != 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) sc[0] = live ? 1 : 0;
+    if (!live) return;
+    const int chunk = (n + parts - 1) / parts;
+    const int lo = min(n, (int)blockIdx.x * chunk), hi = min(n, lo + chunk);
+    int c0 = 0, c1 = 0;
+    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+        const size_t r = (size_t)g * n + i;
+        const float *z = logits + r * RNCLS;
+        float best = z[0];
+        int bi = 0;
+        for (int k = 1; k < RNCLS; ++k)
+            if (z[k] > best) { best = z[k]; bi = k; }
+        pred[r] = bi;
+        c0 += bi == labels[r] ? 1 : 0;
+        c1 += (mask && mask[r] && bi == ys[r]) ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor(c0, o); c1 += __shfl_xor(c1, o); }
+    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6][0] = c0; s_cnt[threadIdx.x >> 6][1] = c1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sc[1 + 2 * blockIdx.x] = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0];
+        sc[2 + 2 * blockIdx.x] = s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1] + s_cnt[3][1];
+    }
+}
+
+// Latch, second half: every workgroup of a live cloud adds the cloud's counts, takes the exit decision (integers) and, for a
+// snapshot, copies its slice; workgroup 0 writes the history row, the snapshot's statistics, exit_step and active.
+__global__ __launch_bounds__(256) void nu_latch_commit_kernel(const float *__restrict__ feat, const int32_t *__restrict__ pred,
+                                                              const float *__restrict__ dist2, const int32_t *__restrict__ n_mask,
+                                                              const int32_t *__restrict__ scratch, int n, int mode, int num, int den,
+                                                              int step_arg, int can_exit, int final, const float *__restrict__ consts,
+                                                              float *__restrict__ hist_row, float *__restrict__ out_adv,
+                                                              int32_t *__restrict__ out_pred, float *__restrict__ out_stats,
+                                                              uint8_t *__restrict__ active, int32_t *__restrict__ exit_step)
+{
+    const int g = blockIdx.y, parts = gridDim.x;
+    const int32_t *sc = scratch + (size_t)g * (2 * parts + 1);
+    if (!sc[0]) return;
+    const int step = consts ? __builtin_bit_cast(int, consts[0]) : step_arg;
+    int nc = 0, nh = 0;
+    for (int p = 0; p < parts; ++p) { nc += sc[1 + 2 * p]; nh += sc[2 + 2 * p]; }
+    const bool fire = mode == 0 ? (long long)den * nc < (long long)num * n : (long long)den * nh > (long long)num * n_mask[g];
+    const bool exits = fire && can_exit && step >= 1;
+    if (exits || final) {
+        const int chunk = (n + parts - 1) / parts;
+        const int lo = min(n, (int)blockIdx.x * chunk), hi = min(n, lo + chunk);
+        for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+            const size_t r = (size_t)g * n + i;
+            out_adv[r * 3] = feat[r * 6 + 3];
+            out_adv[r * 3 + 1] = feat[r * 6 + 4];
+            out_adv[r * 3 + 2] = feat[r * 6 + 5];
+            out_pred[r] = pred[r];
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const float row[3] = {(float)nc, (float)nh, dist2[g]};
+        for (int k = 0; k < 3; ++k) hist_row[g * 3 + k] = row[k];
+        if (exits || final)
+            for (int k = 0; k < 3; ++k) out_stats[g * 3 + k] = row[k];
+        if (exits) { exit_step[g] = step; active[g] = 0; }
+    }
+}
+}  // namespace
+
+extern "C" int psg_rla_nu_color_clouds(const float *xs, const float *dws, const uint8_t *mask, const uint8_t *active, int G, int n,
+                                       float *feat, float *dist2, double *partials, psg_stream stream)
+{
+    PSG_REQUIRE(xs && dws && feat && dist2 && partials, "psg_rla_nu_color_clouds: null argument");
+    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_nu_color_clouds: G=%d n=%d out of range", G, n);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nu_color_clouds_kernel, dim3(kNuParts, G), dim3(256), 0, st, xs, dws, mask, active, (size_t)n, feat, partials);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nu_dist2_clouds_kernel, dim3(ceil_div(G, 64)), dim3(64), 0, st, partials, active, G, kNuParts, dist2);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_rla_nu_adam_clouds(const float *xs, float *dws, float *m, float *v, const uint8_t *mask, const uint8_t *active,
+                                      const float *feat, const float *dfeat, const float *dist2, int G, int n, float c, float lr, int t,
+                                      psg_stream stream)
+{
+    PSG_REQUIRE(xs && dws && m && v && feat && dfeat && dist2 && t >= 1, "psg_rla_nu_adam_clouds: bad argument");
+    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_nu_adam_clouds: G=%d n=%d out of range", G, n);
+    const double b1 = 0.9, b2 = 0.999;
+    const float lr_t = (float)((double)lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t)));
+    hipLaunchKernelGGL(nu_adam_clouds_kernel, dim3(blocks_for((size_t)n * 3), G), dim3(256), 0, (hipStream_t)stream, xs, dws, m, v, mask,
+                       active, feat, dfeat, dist2, (size_t)n, c, lr_t, psg::nu_step_consts(), 0.9f, 0.999f, 1e-8f);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_rla_nu_latch_clouds(const float *logits, const int32_t *labels, const int32_t *ys, const uint8_t *mask,
+                                       const int32_t *n_mask, const float *feat, const float *dist2, int G, int n, int mode, int num,
+                                       int den, int step, int can_exit, int final, float *hist_row, int32_t *pred, float *out_adv,
+                                       int32_t *out_pred, float *out_stats, uint8_t *active, int32_t *exit_step, int32_t *scratch,
+                                       psg_stream stream)
+{
+    PSG_REQUIRE(logits && labels && feat && dist2 && hist_row && pred && out_adv && out_pred && out_stats && active && exit_step && scratch,
+                "psg_rla_nu_latch_clouds: null argument");
+    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_nu_latch_clouds: G=%d n=%d out of range", G, n);
+    PSG_REQUIRE(mode == 0 || mode == 1, "psg_rla_nu_latch_clouds: mode %d out of range", mode);
+    PSG_REQUIRE(!mask || ys, "psg_rla_nu_latch_clouds: a mask needs ys");
+    PSG_REQUIRE(mode == 0 || (mask && n_mask), "psg_rla_nu_latch_clouds: mode 1 needs mask and n_mask");
+    PSG_REQUIRE(num >= 0 && den > 0 && step >= 0, "psg_rla_nu_latch_clouds: num=%d den=%d step=%d out of range", num, den, step);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nu_latch_count_kernel, dim3(kNuParts, G), dim3(256), 0, st, logits, labels, ys, mask, (const uint8_t *)active, n, pred,
+                       scratch);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nu_latch_commit_kernel, dim3(kNuParts, G), dim3(256), 0, st, feat, (const int32_t *)pred, dist2, n_mask,
+                       (const int32_t *)scratch, n, mode, num, den, step, can_exit, final, psg::nu_step_consts(), hist_row, out_adv, out_pred,
+                       out_stats, active, exit_step);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+// One step sequence of a window, shared by the eager and the captured path; rows: the window's step-constant device rows
+// {evaluation index, -, -, lr_t} or null.  Everything in it is a launch on `stream`: a single chain.
+static int rla_nu_window_steps(const psg_rla_nu_window_args *a, const float *rows, psg_stream stream)
+{
+    const int G = a->G, N = a->N;
+    const int total = a->n_steps + (a->tail_eval ? 1 : 0);
+    int rc = PSG_OK;
+    for (int i = 0; i < total && rc == PSG_OK; ++i) {
+        const int t = a->adam_t0 + i;                // Adam index of the step; the forward before it evaluates index t - 1
+        const bool tail = i == a->n_steps;
+        if ((rc = psg_rla_nu_color_clouds(a->xs, a->dws, a->mask, a->active, G, N, a->feat, a->dist2, a->partials, stream))) break;
+        if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
+        psg::nu_set_step_consts(rows ? rows + 4 * i : nullptr);
+        // (a captured window serves every later one: there the latch's own `step >= 1` rule keeps the start from exiting)
+        rc = psg_rla_nu_latch_clouds(a->logits, a->labels, a->ys, a->mask, a->n_mask, a->feat, a->dist2, G, N, a->mode, a->num, a->den,
+                                     t - 1, (rows || t - 1 >= 1) ? 1 : 0, tail ? 1 : 0, a->hist + (size_t)i * 3 * G, a->pred, a->out_adv,
+                                     a->out_pred, a->out_stats, a->active, a->exit_step, a->scratch, stream);
+        if (rc == PSG_OK && !tail) {
+            if ((rc = psg_rla_colper_grad_masked(a->logits, a->ys, a->mask, 1.0f, G * N, a->dlogits, nullptr, stream)) == PSG_OK &&
+                (rc = psg_rla_backward(a->model, a->ws, a->dlogits, a->dfeat, stream)) == PSG_OK)
+                rc = psg_rla_nu_adam_clouds(a->xs, a->dws, a->m, a->v, a->mask, a->active, a->feat, a->dfeat, a->dist2, G, N, a->cs, a->lr, t,
+                                            stream);
+        }
+        psg::nu_set_step_consts(nullptr);
+    }
+    psg::nu_set_step_consts(nullptr);
+    return rc;
+}
+
+extern "C" int psg_rla_nu_window(const psg_rla_nu_window_args *a, psg_nu_graph *graph, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws && a->xs && a->dws && a->m && a->v && a->labels && a->ys && a->feat && a->logits && a->dlogits &&
+                    a->dfeat && a->dist2 && a->partials && a->pred && a->scratch && a->hist && a->out_adv && a->out_pred && a->out_stats &&
+                    a->active && a->exit_step,
+                "psg_rla_nu_window: null argument");
+    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->Nc, "psg_rla_nu_window: the workspace is for %d clouds of %d points, the window for %d of %d",
+                a->ws->B, a->ws->Nc, a->G, a->N);
+    PSG_REQUIRE(a->n_steps >= 1 && a->n_steps <= PSG_NU_GRAPH_MAX_STEPS, "psg_rla_nu_window: n_steps=%d outside 1..%d", a->n_steps,
+                PSG_NU_GRAPH_MAX_STEPS);
+    PSG_REQUIRE(a->adam_t0 >= 1, "psg_rla_nu_window: adam_t0=%d (the first step is 1)", a->adam_t0);
+    PSG_REQUIRE(a->mode == 0 || a->mode == 1, "psg_rla_nu_window: mode %d out of range", a->mode);
+    PSG_REQUIRE(a->mode == 0 || (a->mask && a->n_mask), "psg_rla_nu_window: mode 1 needs mask and n_mask");
+    PSG_REQUIRE(a->num >= 0 && a->den > 0, "psg_rla_nu_window: threshold %d / %d out of range", a->num, a->den);
+    if (!a->ws->cloud_set) { set_error("psg_rla_nu_window: psg_rla_set_cloud has not been called"); return PSG_ERR_STATE; }
+    ProfBind bind(a->ws);
+    // what a captured window is valid for: the argument block without what the device rows carry
+    psg_rla_nu_window_args key;
+    memset(&key, 0, sizeof(key));
+    key = *a;
+    key.adam_t0 = 0; key.lr = 0.0f;
+    const int total = a->n_steps + (a->tail_eval ? 1 : 0);
+    float lr_rows[PSG_NU_GRAPH_MAX_STEPS + 1];
+    const double b1 = 0.9, b2 = 0.999;
+    for (int i = 0; i < total; ++i) {      // psg_rla_nu_adam_clouds' lr_t (the tail's row has no Adam step)
+        const int t = a->adam_t0 + i;
+        lr_rows[i] = i < a->n_steps ? (float)((double)a->lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t))) : 0.0f;
+    }
+    // no graph while the profiler is on (per-launch events) or before the first forward of (cloud, model), which computes the
+    // xyz branch: a capture would either bake it in or, replayed after a new cloud, skip it
+    const bool plain = a->ws->prof.on || a->ws->xyz_branch_model != a->model->gen;
+    return nu_graph_window(plain ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, total, a->adam_t0 - 1, a->adam_t0 - 1, a->lr,
+                           0.9f, 0.999f, (hipStream_t)stream, [&](const float *rows) { return rla_nu_window_steps(a, rows, stream); }, lr_rows);
 }

@@ -9,7 +9,13 @@ keep that loop on the host over the step entry points (forward, masked hinge gra
 one small read-back per iteration, like the reference's session.run.  `batch_attack` takes the cloud's features [N, 6]
 (xyz, rgb) and labels [N] instead of the reference's flattened data_batch list; the returned metric tuples are the
 reference's, the adversarial colours stay available as `.last_adv`.  Network parity is UNPINNED (oracle/randla_net.py).
+
+`NUattack.batch_attack_clouds` / `tar_NUattack.batch_attack_clouds` are the lockstep form of the two NU attacks: G clouds
+advance together on one cloud-batch workspace, CHUNK optimiser steps per library call (`psg_rla_nu_window`), one read-back
+per window; the accuracy exits are taken per cloud on the device, in integers.  `batch_attack` stays the one-cloud path.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -84,6 +90,7 @@ class _StepAttack:
         self.model, self.batch_size = model, batch_size
         self.iteration, self.logger, self.last_adv = None, None, None
         self._ws = {}
+        self._clouds, self.last_steps = {}, None        # the lockstep NU attacks (batch_attack_clouds)
 
     def _setup(self, features, labels):
         f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
@@ -200,6 +207,45 @@ class tar_NBattack(TBIM):
             self.rand_init_eps = float(np.asarray(kwargs["rand_init_magnitude"]).reshape(-1)[0])
 
 
+CHUNK = 10  # optimiser steps per device-side window (the CHUNK of the other networks' NU attacks)
+
+
+class _CloudsState:
+    """Device buffers of G clouds of N points attacked in lockstep, their cloud-batch workspace and the graph handle of the
+    full windows (every full window of one call shape has the same argument block)."""
+
+    def __init__(self, n, G):
+        self.ws = network.RandLAWorkspace(n, batch=G)
+        dev = self.ws.device
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+        R = G * n
+        self.dws, self.m, self.v = f32(R, 3), f32(R, 3), f32(R, 3)
+        self.xs, self.feat, self.dfeat = f32(R, 3), f32(R, 6), f32(R, 6)
+        self.logits, self.dlogits = f32(R, 13), f32(R, 13)
+        self.labels, self.ys, self.pred, self.out_pred = i32(R), i32(R), i32(R), i32(R)
+        self.mask = torch.zeros(R, dtype=torch.uint8, device=dev)
+        self.n_mask = i32(G)
+        self.dist2, self.out_stats, self.out_adv = f32(G), f32(G, 3), f32(R, 3)
+        self.partials = torch.zeros(G, _lib.RLA_NU_PARTS, dtype=torch.float64, device=dev)
+        self.scratch = i32(G, 2 * _lib.RLA_NU_PARTS + 1)
+        self.hist = f32(CHUNK + 1, G, 3)
+        self.active = torch.zeros(G, dtype=torch.uint8, device=dev)
+        self.exit = i32(G)
+        # two handles: the full windows, and a full window that is also the last one (it carries the tail evaluation)
+        self.graph, self.graph_tail = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph))
+        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph_tail))
+
+    def __del__(self):
+        try:
+            for g in (self.graph, self.graph_tail):
+                if g:
+                    _lib.load().psg_nu_graph_destroy(g)
+        except Exception:
+            pass
+
+
 class NUattack(_StepAttack):
     """NUattack.py:12-245: Adam (lr 0.01) on d_ws with adv = (tanh(atanh(2 b x - b) + d_ws) + 1) / 2, loss =
     |adv - x|_2 + cs * score, score = the colper hinge against the labels (goal 'ut': NUattack.py:47-48 keeps the un-negated
@@ -265,6 +311,100 @@ class NUattack(_StepAttack):
         return out
 
 
+    # the accuracy exit as an integer ratio: mode 0 `correct / n < num / den`, mode 1 `hits / points > num / den`
+    EXIT_MODE, EXIT_RATIO = 0, (1, 13)
+    window_hook = None      # tests, tools: called after every window's read-back with (first step, steps, tail, state, history rows)
+
+    def _run_clouds(self, features, labels, ys_h, mask_h):
+        """The lockstep loop: features [G, N, 6], labels / ys_h [G, N] (host), mask_h [G, N] bool or None.  -> the state,
+        pred0 [G, N], per cloud the snapshot's pred [G, N], {n_correct, n_hits, dist2} [G, 3] and the exit steps [G]."""
+        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
+        f = f.float().cuda().contiguous()
+        if f.dim() != 3 or f.shape[2] != 6 or f.shape[0] < 1:
+            raise ValueError("features must be [G, N, 6] (xyz, rgb) of G >= 1 clouds, got %s" % (tuple(f.shape),))
+        G, n = int(f.shape[0]), int(f.shape[1])
+        if tuple(ys_h.shape) != (G, n):
+            raise ValueError("labels must be [G, N] = %s, got %s" % ((G, n), tuple(ys_h.shape)))
+        if self.iteration < 1:
+            raise ValueError("iteration must be positive")
+        if (n, G) not in self._clouds:
+            self._clouds[(n, G)] = _CloudsState(n, G)
+        S = self._clouds[(n, G)]
+        ws = S.ws
+        S.feat.copy_(f.reshape(G * n, 6))
+        S.xs.copy_(S.feat[:, 3:6])
+        ws.set_cloud(S.feat[:, 0:3].contiguous())
+        pred0 = ws.forward(self.model, S.feat).argmax(1).cpu().numpy().reshape(G, n)
+        S.labels.copy_(torch.from_numpy(np.ascontiguousarray(labels, np.int32).reshape(-1)))
+        S.ys.copy_(torch.from_numpy(np.ascontiguousarray(ys_h, np.int32).reshape(-1)))
+        if mask_h is not None:
+            S.mask.copy_(torch.from_numpy(np.ascontiguousarray(mask_h, np.uint8).reshape(-1)))
+            S.n_mask.copy_(torch.from_numpy(mask_h.reshape(G, n).sum(1).astype(np.int32)))
+        for t in (S.dws, S.m, S.v, S.dist2, S.out_stats, S.out_adv, S.out_pred):
+            t.zero_()
+        S.active.fill_(1)
+        S.exit.fill_(-1)
+        win = _lib.RlaNuWindowArgs()
+        win.model, win.ws = self.model.handle, ws.handle
+        win.G, win.N, win.mode = G, n, self.EXIT_MODE
+        win.num, win.den = int(self.EXIT_RATIO[0]), int(self.EXIT_RATIO[1])
+        win.cs, win.lr = self.cs, self.lr
+        for name, t in (("xs", S.xs), ("dws", S.dws), ("m", S.m), ("v", S.v), ("labels", S.labels), ("ys", S.ys), ("feat", S.feat),
+                        ("logits", S.logits), ("dlogits", S.dlogits), ("dfeat", S.dfeat), ("dist2", S.dist2), ("partials", S.partials),
+                        ("pred", S.pred), ("scratch", S.scratch), ("hist", S.hist), ("out_adv", S.out_adv), ("out_pred", S.out_pred),
+                        ("out_stats", S.out_stats), ("active", S.active), ("exit_step", S.exit)):
+            setattr(win, name, t.data_ptr())
+        win.mask = S.mask.data_ptr() if mask_h is not None else None
+        win.n_mask = S.n_mask.data_ptr() if mask_h is not None else None
+        chunk = max(1, min(int(self.chunk), CHUNK))
+        exited = np.full(G, -1, np.int64)
+        t0 = 1
+        while t0 <= self.iteration:                      # windows [1..W], [W+1..2W], ..; the last one is cut to the cap
+            n_run = min(chunk, self.iteration - t0 + 1)
+            tail = t0 + n_run - 1 == self.iteration       # .. and evaluates its last step, snapshotting the clouds still running
+            win.n_steps, win.adam_t0, win.tail_eval = n_run, t0, 1 if tail else 0
+            graph = None if n_run != CHUNK else (S.graph_tail if tail else S.graph)      # cut windows run eagerly
+            _lib.call("psg_rla_nu_window", ctypes.byref(win), graph, runtime.stream())
+            rows = n_run + (1 if tail else 0)
+            back = torch.cat([S.hist[:rows].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
+            exited = back[rows * G * 3:].astype(np.int64)
+            if self.window_hook is not None:
+                self.window_hook(t0, n_run, tail, S, back[:rows * G * 3].reshape(rows, G, 3))
+            t0 += n_run
+            if (exited >= 0).all():
+                break
+        self.last_adv = S.out_adv.reshape(G, n, 3).clone()
+        self.last_steps = np.where(exited >= 0, exited, self.iteration)
+        return S, pred0, S.out_pred.cpu().numpy().reshape(G, n), S.out_stats.cpu().numpy().astype(np.float64), G, n
+
+    chunk = CHUNK           # steps per window (tests shorten it; at most CHUNK)
+
+    def batch_attack_clouds(self, features, labels):
+        """G clouds in lockstep: features [G, N, 6], labels [G, N] -> a list of G tuples, each the reference's
+        (acc, original_accuracy, new_dists, mIoU, original_mIoU, rand_acc, rand_mIoU) of that cloud (NUattack.py:233), the
+        fields `batch_attack` returns.  Every cloud has its own early exit; one that exits stops moving."""
+        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64)
+        S, pred0, pred, stats, G, n = self._run_clouds(features, lab, lab, None)
+        dist = np.sqrt(stats[:, 2])
+        # random noise of the same l_2 size (NUattack.py:236-252): numpy's global generator, once per cloud in cloud order - a
+        # seeded run consumes the stream as G consecutive batch_attack calls do; then one forward for the G noisy clouds
+        rnd = S.feat.clone()
+        noise = np.empty((G, n, 3), np.float32)
+        for g in range(G):
+            z = np.random.uniform(0, 1, size=(n, 3))
+            noise[g] = (z / np.linalg.norm(z) * dist[g]).astype(np.float32)
+        rnd[:, 3:6] = torch.clamp(S.xs + torch.from_numpy(noise.reshape(G * n, 3)).cuda(), 0, 1)
+        rpred = S.ws.forward(self.model, rnd).argmax(1).cpu().numpy().reshape(G, n)
+        outs = []
+        for g in range(G):
+            out = (float(np.sum(pred[g] == lab[g]) / n), float(np.sum(pred0[g] == lab[g]) / n), float(dist[g]), _mean_iou(pred[g], lab[g]),
+                   _mean_iou(pred0[g], lab[g]), float(np.sum(rpred[g] == lab[g]) / n), _mean_iou(rpred[g], lab[g]))
+            if self.logger is not None:
+                self.logger.info("acc={}, original_acc={}, new_dists={}, mIoU={}, original_mIoU={}, rand_acc={}, rand_mIoU={}".format(*out))
+            outs.append(out)
+        return outs
+
+
 class tar_NUattack(NUattack):
     """tar_NUattack.py:12-244: the masked variant - only the points of class `ori` move (tar_NUattack.py:41), the hinge is
     taken against the target labels on those points (:105-110), the loop stops when more than 95 % of them are predicted as
@@ -299,3 +439,31 @@ class tar_NUattack(NUattack):
             self.logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
                              "original_other_mIoU={}".format(*out))
         return out
+
+    EXIT_MODE, EXIT_RATIO = 1, (19, 20)
+
+    def batch_attack_clouds(self, features, labels, target=None, ori=2):
+        """G clouds in lockstep -> a list of G tuples (target_points, sr, other_acc, original_other_accuracy, new_dists,
+        other_mIoU, original_other_mIoU), the fields `batch_attack` returns.  Raises ValueError, before any device work, when
+        a cloud has no point of class `ori`."""
+        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64)
+        if lab.ndim != 2:
+            raise ValueError("labels must be [G, N], got %s" % (lab.shape,))
+        mask_h = lab == ori
+        target_points = mask_h.sum(1).astype(np.float64)
+        if (target_points == 0).any():
+            raise ValueError("no point of the origin class %d in cloud(s) %s (tester_S3DIS.py:253-256 skips such clouds)" %
+                             (ori, ", ".join(str(g) for g in np.flatnonzero(target_points == 0))))
+        ys_target = np.where(mask_h, target, lab)
+        S, pred0, pred, stats, G, n = self._run_clouds(features, lab, ys_target, mask_h)
+        outs = []
+        for g in range(G):
+            mk, tp = mask_h[g], target_points[g]
+            out = (float(tp), float(np.sum(pred[g][mk] == ys_target[g][mk]) / tp),
+                   float(np.sum(pred[g][~mk] == ys_target[g][~mk]) / (n - tp)), float(np.sum(pred0[g][~mk] == lab[g][~mk]) / (n - tp)),
+                   float(np.sqrt(stats[g, 2])), _mean_iou(pred[g][~mk], lab[g][~mk]), _mean_iou(pred0[g][~mk], lab[g][~mk]))
+            if self.logger is not None:
+                self.logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
+                                 "original_other_mIoU={}".format(*out))
+            outs.append(out)
+        return outs
