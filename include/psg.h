@@ -146,9 +146,11 @@ int psg_pn2_plan_build(psg_pn2_ws *ws, const float *x0, const int32_t *starts, i
  * int32 [S_l / G_l][4] = {first group | groups << 16 (0: workgroup not in use), valid rows - 1 of its groups, five bits each, six
  * to a word}.
  * The SA backward of a level runs over the same packed rows through the same descriptors where PSG_PN2_PACK_BWD (read once per
- * process) names the level: unset or 1 = every level that has the kernel (level 0), 0 = none (the unpacked backward kernels and
- * the unpacked-keyed ReLU masks), L followed by level digits (L0) = exactly those levels, an error at launch where a named level
- * has no packed backward kernel.  Results are the same bytes under every value. */
+ * process) names the level: unset or 1 = the default set (levels 0 and 1: the levels whose launch is faster packed; levels 2 and
+ * 3 have the kernel and are slower with it), 0 = none (the unpacked backward kernels and the unpacked-keyed ReLU masks), L followed
+ * by level digits (L0, L0123) = exactly those levels, an error at launch where a named level does not fit the packed kernel's
+ * configuration (SSG as shipped: level 0 whole, levels 1 - 3 split with the sparse max-pool transpose).  Results are the same
+ * bytes under every value. */
 const void *psg_pn2_plan_ptr(const psg_pn2_ws *ws, int what, int level, int forward, int room);
 
 /* get_model.forward (pointnet2_sem_seg.py:22-40) with the geometry of plan slot `forward`.

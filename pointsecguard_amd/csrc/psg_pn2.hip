@@ -167,10 +167,13 @@ bool arch_pack(const ArchDesc &A)
 
 // The SA backward of a packed level runs the same packed rows (psg_pn2_kernels.cuh, sa_bwd_packed_kernel), and the level's
 // forward then keys its ReLU masks by packed workgroup.  PSG_PN2_PACK_BWD, read once per process, names the levels: unset or
-// 1 = every level that has a packed backward kernel (level 0 is what is built), 0 = none (the unpacked backward kernels and the
-// unpacked-keyed masks, as before round 17), L followed by level digits (L0, L02) = exactly those levels; a level named that
-// way that has no packed backward kernel is an error at its launch, not a fall-back (bit 8: levels named explicitly).
-constexpr int kPackBwdBuilt = 1 << 0;
+// 1 = the default set kPackBwdBuilt, 0 = none (the unpacked backward kernels and the unpacked-keyed masks, as before round 17),
+// L followed by level digits (L0, L02) = exactly those levels; a level named that way that does not fit the packed kernel's
+// configuration is an error at its launch, not a fall-back (bit 8: levels named explicitly).
+// Every level has a packed backward kernel; the default set holds the levels whose launch is faster packed in the headline
+// rooms, measured per level: levels 0 and 1.  Levels 2 and 3 are slower packed (too few
+// workgroups are left to hide the sparse stream's latency) and run packed only where named (L2, L3).
+constexpr int kPackBwdBuilt = (1 << 0) | (1 << 1);
 int pack_bwd_levels()
 {
     static const int levels = [] {
@@ -397,16 +400,32 @@ inline int gsa_stride(const ArchDesc &A, int lvl)
 
 #define PSG_CFG_KEY(P, NW, KS, MT) ((P) * 10000 + (NW) * 1000 + (KS) * 10 + (MT))
 
+// Max-pool transpose as a sparse weight-row stream (psg_pn2_kernels.cuh: sa_pool_t_sparse) where the level's shapes fit it:
+// SSG levels 1 - 3 (sa1: C2 = 32 is half a wave's lanes; MSG: KS = 16 and C2 = 96 / 196 / 384).  PSG_PN2_POOLT_SPARSE=0 keeps
+// the dense transposed layer on the matrix pipe.  Returns SPV = C2 / 64, or 0 for the dense layer.
+int sa_sparse_spv(const ScaleDesc &d, const PackedLayer *L, bool w1c)
+{
+    static const bool poolt_sparse = psg::env_int("PSG_PN2_POOLT_SPARSE", 1) != 0;
+    const int C3 = L[2].cout, C2 = L[2].cin, NT = d.NW * 64;
+    return poolt_sparse && L[2].wr && d.K == 32 && d.P <= 64 && (d.P / d.K) * C3 <= NT && C3 % 64 == 0 && !w1c &&
+           (C2 == 64 || C2 == 128 || C2 == 256) ? C2 / 64 : 0;
+}
+
 // Does the backward of SA level lvl run packed?  The ONE place that decides it: run_sa_fwd keys the level's ReLU masks by it and
 // run_sa_bwd picks the kernel by it.  Needs the plan's descriptors (SSG under PSG_PN2_PACK) and the level named by
 // PSG_PN2_PACK_BWD; by default also the configuration the kernel is built for - SSG as shipped: level 0 whole, level 1 split, so
 // that the pooled-output gradient of level 0 arrives as plain rows - and any other (PSG_PN2_SPLIT) keeps the unpacked backward.
+// Levels 1 - 3 qualify in the shipped configuration only: forward and backward split (the forward then takes the packed path,
+// run_sa_fwd; the rows stored are dZ1), the max-pool transpose as the sparse stream (sa_sparse_spv), and the pooled gradient
+// as plain rows (levels 1 and 2: the level above split) or level 3's nninv gather.
 bool sa_pack_bwd_level(const psg_pn2_model *m, const psg_pn2_ws *ws, int lvl)
 {
     const int levels = pack_bwd_levels();
     if (!ws->pk_cnt[lvl] || !((levels >> lvl) & 1)) return false;
     if (levels >> 8) return true;                                  // named explicitly: run_sa_fwd / run_sa_bwd fail where it does not fit
-    return lvl == 0 && !m->split_fwd[0] && !m->split[0] && m->split[1];
+    if (lvl == 0) return !m->split_fwd[0] && !m->split[0] && m->split[1];
+    return m->split_fwd[lvl] && m->split[lvl] && (lvl == 3 || m->split[lvl + 1]) &&
+           sa_sparse_spv(m->arch->sc[lvl][0], &m->L[m->arch->sc[lvl][0].l0], false) > 0;
 }
 
 int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const float *x0, hipStream_t st)
@@ -455,6 +474,9 @@ int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const
         if (pkm) {
             switch (PSG_CFG_KEY(P, NW, KS, split ? 1 : 0)) {
             case PSG_CFG_KEY(128, 4, 32, 0): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<128, 4, false, true>), grid, 4 * 64, pblocks, blk, a, st);
+            case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<64, 4, true, true>), grid, 4 * 64, pblocks, blk, a, st);
+            case PSG_CFG_KEY(32, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 4, true, true>), grid, 4 * 64, pblocks, blk, a, st);
+            case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 8, true, true>), grid, 8 * 64, pblocks, blk, a, st);
             }
             set_error("run_sa_fwd level %d: PSG_PN2_PACK_BWD names a level without a packed-key forward kernel (P=%d NW=%d)", lvl, P, NW);
             return PSG_ERR_STATE;
@@ -560,13 +582,10 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     static const bool l1t_colour = psg::env_int("PSG_PN2_L1T_COLOUR", 1) != 0;
     a.w1c = nullptr; a.C1 = L[0].cout; a.w1c_off = 0;
     if (l1t_colour && a.cg_out == 4 && !a.split && P == 32 * NW && (a.C1 == 16 || a.C1 == 32)) a.w1c = m->w1feat[sc];
-    // max-pool transpose as a sparse weight-row stream (psg_pn2_kernels.cuh: sa_pool_t_sparse) where the level's shapes fit it:
-    // SSG levels 1 - 3 (sa1: C2 = 32 is half a wave's lanes; MSG: KS = 16 and C2 = 96 / 196 / 384).  PSG_PN2_POOLT_SPARSE=0 keeps
-    // the dense transposed layer on the matrix pipe.  The sparse pass needs no dZ3 tile: the buffer is sized without l3t's K.
-    static const bool poolt_sparse = psg::env_int("PSG_PN2_POOLT_SPARSE", 1) != 0;
+    // max-pool transpose as a sparse weight-row stream (sa_sparse_spv).  The sparse pass needs no dZ3 tile: the buffer is sized
+    // without l3t's K.
     const int C2 = L[2].cin, NT = NW * 64;
-    const int spv = poolt_sparse && L[2].wr && KS == 32 && P <= 64 && (P / KS) * C3 <= NT && C3 % 64 == 0 && !a.w1c &&
-                    (C2 == 64 || C2 == 128 || C2 == 256) ? C2 / 64 : 0;
+    const int spv = sa_sparse_spv(d, L, a.w1c != nullptr);
     const int l3_blocks = spv ? a.l3t.mb * 4 : layer_blocks(a.l3t.k8, a.l3t.mb);
     const int main_blocks = std::max(std::max(l3_blocks, layer_blocks(a.l2t.k8, a.l2t.mb)),
                                      a.split ? 0 : layer_blocks(a.l1t.k8, a.l1t.mb)) + PSG_LDS_SPARE;
@@ -579,15 +598,23 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     a.w3r = spv ? L[2].wr : nullptr;
     // packed backward: the same packed rows as the level's forward, masks at the packed key (sa_pack_bwd_level).  Its row map
     // [P] lies behind the output slots; the pooled-output gradient must be plain rows (the split level above sums them per point)
+    // Levels 1 - 3 (sparse): split, G * C3 == NT (a batch of the packed kernel is one unpacked workgroup's pass), one tile per
+    // wave in l2t and the mask pass, the pooled gradient as plain rows or (level 3) the nninv gather alone; the first packed row
+    // of each group [SA_PACK_GCAP + 1] lies behind the sparse pass's row starts.
     const bool packed = sa_pack_bwd_level(m, ws, lvl);
     if (packed) {
-        if (spv || a.split || !a.dout || a.nninv_off || a.ginv_off || ((a.ld | a.c_off) & 3) || (C3 & 7) ||
-            PSG_CFG_KEY(P, NW, KS, d.maxt_b) != PSG_CFG_KEY(128, 4, 32, 1)) {
+        const bool dense0 = !spv && !a.split && a.dout && !a.nninv_off && !a.ginv_off && !((a.ld | a.c_off) & 3) && !(C3 & 7) &&
+                            PSG_CFG_KEY(P, NW, KS, d.maxt_b) == PSG_CFG_KEY(128, 4, 32, 1);
+        const bool sparse = spv && a.split && m->split_fwd[lvl] && !a.ginv_off && (a.dout != nullptr) != (a.nninv_off != nullptr) &&
+                            (P / KS) * C3 == NT && std::max(a.l3t.mb, a.l2t.mb) * (P / 32) <= NW &&
+                            (PSG_CFG_KEY(P, NW, KS, spv) == PSG_CFG_KEY(64, 4, 32, 1) || PSG_CFG_KEY(P, NW, KS, spv) == PSG_CFG_KEY(32, 4, 32, 2) ||
+                             PSG_CFG_KEY(P, NW, KS, spv) == PSG_CFG_KEY(32, 8, 32, 4));
+        if (!dense0 && !sparse) {
             set_error("run_sa_bwd level %d: PSG_PN2_PACK_BWD names a level without a packed backward kernel in this configuration", lvl);
             return PSG_ERR_STATE;
         }
     }
-    const int staged = spv ? a.sp_off + 2 * NT + NW * 32 + P + 1 : a.pos_off + P + (packed ? P : 0);
+    const int staged = spv ? a.sp_off + 2 * NT + NW * 32 + P + 1 + (packed ? SA_PACK_GCAP + 1 : 0) : a.pos_off + P + (packed ? P : 0);
     const int blocks = main_blocks + ceil_div(staged, blk_floats);
     if (std::max(std::max(a.l3t.mb, a.l2t.mb), a.split ? 0 : a.l1t.mb) * (P / 32) > d.maxt_b * NW) {
         set_error("run_sa_bwd level %d scale %d: more than %d tiles per wave in a layer", lvl, sc, d.maxt_b);
@@ -597,6 +624,11 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     const int tag = TAG_SA_BWD + lvl;
     if (packed) {
         const SaBwdPackedArgs pa{a, ws->pk_desc[lvl] + prob * grid.x};
+        switch (spv) {
+        case 1: return launch_lds(ws, tag, PSG_SITE "#sa2#bwd#packed", (sa_bwd_packed_kernel<64, 4, 1, 1>), grid, 4 * 64, blocks, Lds<64>::BLK, pa, st);   // SSG sa2
+        case 2: return launch_lds(ws, tag, PSG_SITE "#sa3#bwd#packed", (sa_bwd_packed_kernel<32, 4, 1, 2>), grid, 4 * 64, blocks, Lds<32>::BLK, pa, st);   // SSG sa3
+        case 4: return launch_lds(ws, tag, PSG_SITE "#sa4#bwd#packed", (sa_bwd_packed_kernel<32, 8, 1, 4>), grid, 8 * 64, blocks, Lds<32>::BLK, pa, st);   // SSG sa4
+        }
         if (a.w1c) return launch_lds(ws, tag, PSG_SITE "#colour#bwd#packed", (sa_bwd_packed_kernel<128, 4, 1, 0>), grid, 4 * 64, blocks, Lds<128>::BLK, pa, st);
         return launch_lds(ws, tag, PSG_SITE "#bwd#packed", (sa_bwd_packed_kernel<128, 4, 1, 0>), grid, 4 * 64, blocks, Lds<128>::BLK, pa, st);
     }

@@ -792,9 +792,32 @@ template <> struct SpVec<1> { using T = float; };
 template <> struct SpVec<2> { using T = float2; };
 template <> struct SpVec<4> { using T = float4; };
 
-template <int P, int NW, int MAXT, int SPV>
+// register r of lane (j, h) = element g = r / 4, component r % 4 of its float4s: the ReLU mask word m over tile (mb, pb) of dZ2
+template <int P>
+__device__ __forceinline__ void sa_mask_tile(float *__restrict__ buf0, int mb, int pb, int j, int h, unsigned m)
+{
+    using L = Lds<P>;
+    float *o = buf0 + (size_t)(mb * 4) * L::BLK + (pb * 32 + j) * 8 + 4 * h;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float4 v = *(float4 *)(o + (size_t)g * L::BLK);
+        v.x = __uint_as_float(__float_as_uint(v.x) & (unsigned)__builtin_amdgcn_sbfe((int)m, 4 * g, 1));
+        v.y = __uint_as_float(__float_as_uint(v.y) & (unsigned)__builtin_amdgcn_sbfe((int)m, 4 * g + 1, 1));
+        v.z = __uint_as_float(__float_as_uint(v.z) & (unsigned)__builtin_amdgcn_sbfe((int)m, 4 * g + 2, 1));
+        v.w = __uint_as_float(__float_as_uint(v.w) & (unsigned)__builtin_amdgcn_sbfe((int)m, 4 * g + 3, 1));
+        *(float4 *)(o + (size_t)g * L::BLK) = v;
+    }
+}
+
+// PACKED (sa_bwd_packed_kernel, one batch of G = P / 32 groups of a packed workgroup): the item of thread tid is (key, dval)
+// instead of (key, dsrc[tid]); a finished row r = g * 32 + k of the batch goes to PACKED row gst[g] + k of the buffer, and only
+// where k is below the group's count gst[g + 1] - gst[g] (a row at or past the count holds no item: the forward's arg-max is
+// below the count); steps 1 - 4 only - the mask pass belongs to the caller, once, after its last batch.
+// Timing diagnosis (diagnostic builds only): PSG_DIAG bit 128 = no stream (step 4), 1024 = no list build and no stream (steps
+// 1 - 4), 2048 = no mask pass (step 5; sa_bwd_body then skips l2t as well).
+template <int P, int NW, int MAXT, int SPV, bool PACKED = false>
 __device__ __forceinline__ void sa_pool_t_sparse(const SaBwdArgs &a, float *__restrict__ buf0, float *__restrict__ dsrc, int key,
-                                                 size_t wg)
+                                                 size_t wg, const int *__restrict__ gst = nullptr, float dval = 0.0f)
 {
     using L = Lds<P>;
     using VT = typename SpVec<SPV>::T;
@@ -804,122 +827,168 @@ __device__ __forceinline__ void sa_pool_t_sparse(const SaBwdArgs &a, float *__re
     int2 *items = (int2 *)(dsrc + a.sp_off);   // [NT]
     int *tab = (int *)(items + NT);            // [NW][KS]: counts, then list offsets (zeroed by the caller before its barrier)
     int *rs = tab + NW * KS;                   // [P + 1] row starts
-    // 1. rank among the lanes with the same key (key KS = no gradient)
-    unsigned long long same = ~0ull;
+    if (!PSG_DIAGBIT(a, 1024)) {
+        // 1. rank among the lanes with the same key (key KS = no gradient)
+        unsigned long long same = ~0ull;
 #pragma unroll
-    for (int bit = 0; bit < 6; ++bit) {
-        const unsigned long long bb = __ballot((key >> bit) & 1);
-        same &= ((key >> bit) & 1) ? bb : ~bb;
-    }
-    const int rank = __popcll(same & ((1ull << lane) - 1ull));
-    if (key < KS && rank == 0) tab[wave * KS + key] = __popcll(same);
-    __syncthreads();
-    // 2. row r = g * KS + k (lane r of wave 0): chunks g * cpg .. g * cpg + cpg - 1 hold the channels of group g
-    if (wave == 0) {
-        const int cpg = a.C3 >> 6, g = lane / KS, k = lane & (KS - 1);
-        int tot = 0;
-        if (lane < P)
-            for (int q = 0; q < cpg; ++q) tot += tab[(g * cpg + q) * KS + k];
-        int inc = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
+        for (int bit = 0; bit < 6; ++bit) {
+            const unsigned long long bb = __ballot((key >> bit) & 1);
+            same &= ((key >> bit) & 1) ? bb : ~bb;
         }
-        int run = inc - tot;
-        if (lane < P) {
-            rs[lane] = run;
-            for (int q = 0; q < cpg; ++q) {
-                int *t = tab + (g * cpg + q) * KS + k;
-                const int c = *t;
-                *t = run;
-                run += c;
+        const int rank = __popcll(same & ((1ull << lane) - 1ull));
+        if (key < KS && rank == 0) tab[wave * KS + key] = __popcll(same);
+        __syncthreads();
+        // 2. row r = g * KS + k (lane r of wave 0): chunks g * cpg .. g * cpg + cpg - 1 hold the channels of group g
+        if (wave == 0) {
+            const int cpg = a.C3 >> 6, g = lane / KS, k = lane & (KS - 1);
+            int tot = 0;
+            if (lane < P)
+                for (int q = 0; q < cpg; ++q) tot += tab[(g * cpg + q) * KS + k];
+            int inc = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(inc, o);
+                if (lane >= o) inc += v;
             }
+            int run = inc - tot;
+            if (lane < P) {
+                rs[lane] = run;
+                for (int q = 0; q < cpg; ++q) {
+                    int *t = tab + (g * cpg + q) * KS + k;
+                    const int c = *t;
+                    *t = run;
+                    run += c;
+                }
+            }
+            if (lane == 63) rs[P] = inc;   // (lanes >= P count nothing)
         }
-        if (lane == 63) rs[P] = inc;   // (lanes >= P count nothing)
-    }
-    __syncthreads();
-    // 3. scatter
-    if (key < KS) {
-        const int g = tid / a.C3, c = tid - g * a.C3;
-        items[tab[wave * KS + key] + rank] = make_int2(((g * KS + key) << 16) | c, __float_as_int(dsrc[tid]));
-    }
+        __syncthreads();
+        // 3. scatter
+        if (key < KS) {
+            const int g = tid / a.C3, c = tid - g * a.C3;
+            items[tab[wave * KS + key] + rank] = make_int2(((g * KS + key) << 16) | c, __float_as_int(PACKED ? dval : dsrc[tid]));
+        }
+    }   // (PSG_DIAG bit 1024)
     // mask words of this wave's tiles of dZ2 (layer_bwd's slots), fetched now so that they arrive under the stream
     const int ntask = (C2 / 32) * PB;
     unsigned msk[MAXT];
+    if constexpr (!PACKED) {
 #pragma unroll
-    for (int i = 0; i < MAXT; ++i) {
-        const int task = wave + i * NW;
-        msk[i] = 0xFFFFu;
-        if (task < ntask && a.l3t.mask) msk[i] = a.l3t.mask[(wg * ntask + task) * 64 + lane];
+        for (int i = 0; i < MAXT; ++i) {
+            const int task = wave + i * NW;
+            msk[i] = 0xFFFFu;
+            if (task < ntask && a.l3t.mask && !PSG_DIAGBIT(a, 2048)) msk[i] = a.l3t.mask[(wg * ntask + task) * 64 + lane];
+        }
     }
     __syncthreads();
-    // 4. stream: this wave's rows [r_lo, r_hi) = the rows whose start lies in its share [lo, hi) of the T items
-    const int T = __builtin_amdgcn_readfirstlane(rs[P]);
-    const int lo = wave * T / NW, hi = (wave + 1) * T / NW;
-    const int rsl = lane < P ? rs[lane] : 0x7fffffff;
-    const int r_lo = __popcll(__ballot(rsl < lo));
-    const int r_hi = wave == NW - 1 ? P : __popcll(__ballot(rsl < hi));
-    const int e_lo = __builtin_amdgcn_readfirstlane(rs[r_lo]), e_hi = __builtin_amdgcn_readfirstlane(rs[r_hi]);
-    const float *wr = a.w3r + lane * SPV;
-    float acc[SPV];
-#pragma unroll
-    for (int e = 0; e < SPV; ++e) acc[e] = 0.0f;
-    int cur = r_lo;
-    auto put = [&](int r) {
-        float *o = buf0 + L::off(lane * SPV, r);
-        if constexpr (SPV == 4) *(float4 *)o = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        else if constexpr (SPV == 2) *(float2 *)o = make_float2(acc[0], acc[1]);
-        else *o = acc[0];
+    if (!PSG_DIAGBIT(a, 128 | 1024)) {
+        // 4. stream: this wave's rows [r_lo, r_hi) = the rows whose start lies in its share [lo, hi) of the T items
+        const int T = __builtin_amdgcn_readfirstlane(rs[P]);
+        const int lo = wave * T / NW, hi = (wave + 1) * T / NW;
+        const int rsl = lane < P ? rs[lane] : 0x7fffffff;
+        const int r_lo = __popcll(__ballot(rsl < lo));
+        const int r_hi = wave == NW - 1 ? P : __popcll(__ballot(rsl < hi));
+        const int e_lo = __builtin_amdgcn_readfirstlane(rs[r_lo]), e_hi = __builtin_amdgcn_readfirstlane(rs[r_hi]);
+        const float *wr = a.w3r + lane * SPV;
+        float acc[SPV];
 #pragma unroll
         for (int e = 0; e < SPV; ++e) acc[e] = 0.0f;
-    };
-    for (int w0 = e_lo; w0 < e_hi; w0 += 64) {
-        const int n = min(64, e_hi - w0);
-        const int2 mine = lane < n ? items[w0 + lane] : make_int2(0, 0);
-        for (int q = 0; q < n; q += U) {
-            VT w[U];
-            int xs[U];
-            float ds[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                xs[u] = __builtin_amdgcn_readlane(mine.x, q + u);
-                ds[u] = __int_as_float(__builtin_amdgcn_readlane(mine.y, q + u));
-                if (q + u < n) w[u] = *(const VT *)(wr + (size_t)(xs[u] & 0xFFFF) * C2);
+        int cur = r_lo;
+        // PACKED: lane r holds where the batch's row r goes in the packed buffer, -1 for a row at or past its group's count
+        // (one LDS look-up per batch; put() then reads it with a scalar lane index, no memory access inside the stream)
+        int dstv = -1;
+        if constexpr (PACKED) {
+            if (lane < P) {
+                const int st = gst[lane >> 5], k = lane & 31;
+                if (k < gst[(lane >> 5) + 1] - st) dstv = st + k;
             }
+            if (lane < KS) tab[wave * KS + lane] = 0;   // this wave's counts for the next batch (its own slice: read above, dead now)
+        }
+        auto put = [&](int r) {
+            if constexpr (PACKED) {
+                r = __builtin_amdgcn_readlane(dstv, r);
+                if (r < 0) return;   // (no item ever names such a row: acc is still zero)
+            }
+            float *o = buf0 + L::off(lane * SPV, r);
+            if constexpr (SPV == 4) *(float4 *)o = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            else if constexpr (SPV == 2) *(float2 *)o = make_float2(acc[0], acc[1]);
+            else *o = acc[0];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (q + u < n) {
-                    const int row = xs[u] >> 16;
-                    while (cur < row) put(cur++);
-                    const float *wv = (const float *)&w[u];
+            for (int e = 0; e < SPV; ++e) acc[e] = 0.0f;
+        };
+        for (int w0 = e_lo; w0 < e_hi; w0 += 64) {
+            const int n = min(64, e_hi - w0);
+            const int2 mine = lane < n ? items[w0 + lane] : make_int2(0, 0);
+            for (int q = 0; q < n; q += U) {
+                VT w[U];
+                int xs[U];
+                float ds[U];
 #pragma unroll
-                    for (int e = 0; e < SPV; ++e) acc[e] = fmaf(ds[u], wv[e], acc[e]);
+                for (int u = 0; u < U; ++u) {
+                    xs[u] = __builtin_amdgcn_readlane(mine.x, q + u);
+                    ds[u] = __int_as_float(__builtin_amdgcn_readlane(mine.y, q + u));
+                    if (q + u < n) w[u] = *(const VT *)(wr + (size_t)(xs[u] & 0xFFFF) * C2);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (q + u < n) {
+                        const int row = xs[u] >> 16;
+                        while (cur < row) put(cur++);
+                        const float *wv = (const float *)&w[u];
+#pragma unroll
+                        for (int e = 0; e < SPV; ++e) acc[e] = fmaf(ds[u], wv[e], acc[e]);
+                    }
+                }
+            }
+        }
+        while (cur < r_hi) put(cur++);
+    }   // (PSG_DIAG bits 128, 1024)
+    if constexpr (!PACKED) {
+        __syncthreads();
+        // 5. ReLU mask of layer 2, tile by tile
+        const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int i = 0; i < MAXT; ++i) {
+            const int task = wave + i * NW;
+            if (task < ntask && !PSG_DIAGBIT(a, 2048)) {   // (sa_mask_tile, in place)
+                const int mb = task / PB, pb = task - mb * PB;
+                float *o = buf0 + (size_t)(mb * 4) * L::BLK + (pb * 32 + j) * 8 + 4 * h;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    float4 v = *(float4 *)(o + (size_t)g * L::BLK);
+                    v.x = __uint_as_float(__float_as_uint(v.x) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g, 1));
+                    v.y = __uint_as_float(__float_as_uint(v.y) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 1, 1));
+                    v.z = __uint_as_float(__float_as_uint(v.z) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 2, 1));
+                    v.w = __uint_as_float(__float_as_uint(v.w) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 3, 1));
+                    *(float4 *)(o + (size_t)g * L::BLK) = v;
                 }
             }
         }
     }
-    while (cur < r_hi) put(cur++);
-    __syncthreads();
-    // 5. ReLU mask of layer 2, tile by tile (register r of lane (j, h) = element g = r / 4, component r % 4 of its float4s)
-    const int j = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < MAXT; ++i) {
-        const int task = wave + i * NW;
-        if (task < ntask) {
-            const int mb = task / PB, pb = task - mb * PB;
-            float *o = buf0 + (size_t)(mb * 4) * L::BLK + (pb * 32 + j) * 8 + 4 * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float4 v = *(float4 *)(o + (size_t)g * L::BLK);
-                v.x = __uint_as_float(__float_as_uint(v.x) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g, 1));
-                v.y = __uint_as_float(__float_as_uint(v.y) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 1, 1));
-                v.z = __uint_as_float(__float_as_uint(v.z) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 2, 1));
-                v.w = __uint_as_float(__float_as_uint(v.w) & (unsigned)__builtin_amdgcn_sbfe((int)msk[i], 4 * g + 3, 1));
-                *(float4 *)(o + (size_t)g * L::BLK) = v;
-            }
-        }
+}
+
+// level 3's pooled-output gradient (sa_bwd_body's nninv gather for one (group, channel), the same chain): dout[s][c] = sum over
+// the fine points whose 3-NN lists contain s of w * dint[p][c], in list order
+__device__ __forceinline__ float sa_nninv_grad(const SaBwdArgs &a, int b, int s, int c)
+{
+    const int32_t *off = a.nninv_off + (size_t)b * (a.S + 1) + s;
+    const int2 *ent = a.nninv_ent + (size_t)b * 3 * a.n_fine;
+    const float *drows = a.dint + (size_t)b * a.n_fine * a.ld + a.c_off + c;
+    const int e1 = off[1];
+    int e = off[0];
+    float acc = 0.0f;
+    for (; e + 4 <= e1; e += 4) {
+        const int2 p0 = ent[e], p1 = ent[e + 1], p2 = ent[e + 2], p3 = ent[e + 3];
+        const float v0 = drows[(size_t)p0.x * a.ld], v1 = drows[(size_t)p1.x * a.ld], v2 = drows[(size_t)p2.x * a.ld],
+                    v3 = drows[(size_t)p3.x * a.ld];
+        acc += __int_as_float(p0.y) * v0; acc += __int_as_float(p1.y) * v1;
+        acc += __int_as_float(p2.y) * v2; acc += __int_as_float(p3.y) * v3;
     }
+    for (; e < e1; ++e) {
+        const int2 pe = ent[e];
+        acc += __int_as_float(pe.y) * drows[(size_t)pe.x * a.ld];
+    }
+    return acc;
 }
 
 // SPV > 0: the max-pool transpose runs as the sparse stream above (sa_pool_t_sparse) instead of dZ3 in LDS + the dense l3t
@@ -979,6 +1048,7 @@ __device__ __forceinline__ void sa_bwd_body(const SaBwdArgs &a, int kbx = 0, int
     }
     for (int t = tid; t < G * a.C3; t += NT) {
         const int g = t / a.C3, c = t - g * a.C3;
+        if (PSG_DIAGBIT(a, 4096)) { dsrc[t] = 0.0f; continue; }   // (timing diagnosis: no pooled-gradient prologue)
         const int cc = a.c_off + c;
         float acc = a.dout ? a.dout[((size_t)b * a.S + s0 + g) * a.ld + cc] : 0.0f;
         if (a.nninv_off) {
@@ -1058,7 +1128,7 @@ __device__ __forceinline__ void sa_bwd_body(const SaBwdArgs &a, int kbx = 0, int
         if (!PSG_DIAGBIT(a, 8)) layer_bwd<P, NW, MAXT>(a.l3t, buf0, wg);
     }
     if (!PSG_DIAGBIT(a, 16)) __syncthreads();
-    if (!PSG_DIAGBIT(a, 8)) layer_bwd<P, NW, MAXT>(a.l2t, buf0, wg);
+    if (!PSG_DIAGBIT(a, 8 | 2048)) layer_bwd<P, NW, MAXT>(a.l2t, buf0, wg);
     if (!PSG_DIAGBIT(a, 16)) __syncthreads();
     if constexpr (P == 32 * NW) {
         if (a.w1c) {   // colour-only request at level 0: three columns of the first layer on the vector pipe (sa_l1t_colour)
@@ -1125,7 +1195,7 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_sparse_kernel(SaBwdArgs a) { s
 //     sa_bwd_kernel's cost (rooms with nothing to skip); an unaligned one takes the packed path with nrows == P;
 //   * stores go to gsa_out through gpos_out[group * 32 + sample], looked up through the row map: the consumers see the
 //     layout they always saw.
-// SPV = 0 (dense max-pool transpose, SSG level 0) is what is built: the pooled-output gradient of that level arrives as plain
+// SPV = 0 (dense max-pool transpose, SSG level 0): the pooled-output gradient of that level arrives as plain
 // rows (a.dout = the per-point sums of the split level above: run_sa_bwd checks), so dZ3 is built per (packed row, 8-channel
 // block) straight from those rows and the arg-max bytes - the loads sa_bwd_kernel issues per (row, block), without its
 // staging pass.  LDS: sa_bwd_kernel's of the level plus the row map [P] in its staging block (the same number of blocks).
@@ -1164,12 +1234,87 @@ __device__ __forceinline__ void sa_layer_bwd_packed(const BwdLayer &L, float *__
     }
 }
 
+// The sparse levels (SPV > 0: SSG levels 1 - 3, split, the rows stored are dZ1).  The max-pool transpose stays the sparse stream
+// of sa_pool_t_sparse - per (row, column) one fmaf chain from 0 over the row's items in ascending channel order, which the
+// dense transposed layer does not reproduce bit for bit - so the items are NOT packed: the workgroup's ng groups pass through
+// the stream in batches of G = P / 32 groups (G * C3 = NT: a batch is exactly the pass of one unpacked workgroup, thread tid =
+// channel tid of the batch's groups, the same key and gradient per thread, the same lists), and only where a finished row
+// goes changes: batch row g * 32 + k to packed row gstart[g0 + g] + k.  What shrinks is behind the stream: the mask pass, l2t
+// and the stores run once over the nblk active blocks of ng groups, and there are ng / G times fewer workgroup lifetimes.
+//   * every valid row is written exactly once, zero rows included: the waves' row ranges [r_lo, r_hi) partition the batch's P
+//     rows, and put() stores each row below its group's count; rows at or past the count are never named by an item (the
+//     packed forward's scan returns bi < n, the in-register pool of a full group any of its 32 rows), so nothing is dropped;
+//   * a batch without a live item (T = 0): lo = hi = 0 in every wave, r_lo = 0, r_hi = 0 but for the last wave, which owns
+//     all P rows with e_lo = e_hi = rs[0] = rs[P] = 0 - the item loop does not run and put() zero-fills the batch's rows;
+//   * a last batch of fewer than G groups: the threads of the missing groups hold key KS (no item), and gstart[ng ..] = nrows
+//     gives their rows the count 0;
+//   * three barriers per batch (after the counts, the scan and the scatter).  A wave zeroes ITS slice of the count table
+//     behind the scatter's barrier and writes only that slice in the next batch's step 1, so a wave that has finished its
+//     stream goes straight on to the next batch's ranks; the row starts and the item list are rewritten only behind the
+//     counts' barrier, which every wave reaches after its stream.  The rows of different batches are disjoint: the buffer
+//     needs no barrier between them;
+//   * the mask word of this wave's tile is loaded before the first batch.  Loading batch i + 1's arg-max bytes and gradient
+//     values before batch i's list build was tried and dropped: 100.4 against 100.7 us per level-1 launch, inside the 0.2 %
+//     two traces of one library differ by.
+// LDS: the staging of sa_bwd_sparse_kernel (its dsrc slots stay unused: a thread's gradient value stays in its register) and
+// gstart [SA_PACK_GCAP + 1] behind the row starts - the same number of blocks at all three levels (run_sa_bwd).
+template <int P, int NW, int SPV>
+__device__ __forceinline__ void sa_bwd_packed_sparse(const SaBwdArgs &a, float *__restrict__ buf0, float *__restrict__ dsrc,
+                                                     const int4 &desc, int b, size_t wg, int nrows)
+{
+    using L = Lds<P>;
+    constexpr int G = P / 32, PB = P / 32, NT = NW * 64, KS = 32, C2 = 64 * SPV, GCAP = SA_PACK_GCAP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ng = desc.x >> 16, sA = desc.x & 0xFFFF;
+    const int nblk = (nrows + 31) >> 5;
+    int *tab = (int *)(dsrc + a.sp_off) + 2 * NT;               // sa_pool_t_sparse's count table [NW][32], row starts [P + 1]
+    int *gstart = tab + NW * KS + P + 1;                        // [GCAP + 1] first packed row of each group; nrows from ng on
+    {
+        int st = 0;
+        for (int i = 0; i < ng; ++i) {                          // (uniform)
+            if (tid == i) gstart[i] = st;
+            st += sa_pack_cnt(desc, i);
+        }
+        if (tid >= ng && tid <= GCAP) gstart[tid] = nrows;
+    }
+    // the tail of the last block: zeroed once (no batch writes it)
+    for (int t = tid; t < (nblk * 32 - nrows) * (C2 / 4); t += NT) {
+        const int r = nrows + t / (C2 / 4), q = t % (C2 / 4);
+        *(float4 *)(buf0 + L::off(4 * q, r)) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    // layer 2's ReLU mask word of this wave's tile (mb, pb) of dZ2, at the packed key the forward stored it at
+    const int mb = wave / nblk, pb = wave - mb * nblk;
+    const bool mtile = wave < (C2 / 32) * nblk;
+    unsigned msk = 0xFFFFu;
+    if (mtile && a.l3t.mask) msk = a.l3t.mask[((wg * (C2 / 32) + mb) * PB + pb) * 64 + lane];
+    // thread tid = channel c of group gl of a batch (G * C3 == NT: run_sa_bwd checks)
+    const int gl = tid / a.C3, c = tid - gl * a.C3;
+    const uint8_t *arow = a.arg + ((size_t)b * a.S + sA) * a.C3 + c;
+    const bool plain = !a.nninv_off;                            // (plain rows, or level 3's gather: uniform)
+    const float *drow = plain ? a.dout + ((size_t)b * a.S + sA) * a.ld + a.c_off + c : nullptr;
+    if (tid < NW * KS) tab[tid] = 0;
+    __syncthreads();
+    for (int g0 = 0; g0 < ng; g0 += G) {
+        int key = KS;   // the arg-max sample of channel c of group g0 + gl (KS = no gradient, or no such group) and its gradient
+        float dv = 0.0f;
+        if (g0 + gl < ng) {
+            const int v = arow[(size_t)(g0 + gl) * a.C3];
+            key = v == 255 ? KS : v;
+            dv = plain ? drow[(size_t)(g0 + gl) * a.ld] : sa_nninv_grad(a, b, sA + g0 + gl, c);
+        }
+        sa_pool_t_sparse<P, NW, 1, SPV, true>(a, buf0, dsrc, key, wg, gstart + g0, dv);
+    }
+    __syncthreads();
+    if (mtile) sa_mask_tile<P>(buf0, mb, pb, lane & 31, lane >> 5, msk);
+    __syncthreads();
+}
+
 template <int P, int NW, int MAXT, int SPV>
 __global__ __launch_bounds__(NW * 64) void sa_bwd_packed_kernel(SaBwdPackedArgs pa)
 {
     const SaBwdArgs &a = pa.a;
     using L = Lds<P>;
-    static_assert(SPV == 0 && MAXT == 1 && P == 32 * NW, "built: the dense level, one tile per wave");
+    static_assert(MAXT == 1 && (SPV > 0 ? P <= 64 : P == 32 * NW), "one tile per wave in every layer");
     constexpr int PB = P / 32, NT = NW * 64, KS = 32;
     extern __shared__ float lds[];
     float *buf0 = lds;
@@ -1188,78 +1333,87 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_packed_kernel(SaBwdPackedArgs 
         nrows += sa_pack_cnt(desc, i);
     }
     if (ng == PB && (sA & (PB - 1)) == 0 && nrows == P) {       // nothing to skip: sa_bwd_kernel's body, masks at this key
-        sa_bwd_body<P, NW, MAXT, KS, 0, true>(a, sA / PB, b, wg);
+        // (the sparse levels: the two tiles a wave may hold in sa_bwd_sparse_kernel, so that the body is the one that kernel runs)
+        sa_bwd_body<P, NW, (SPV > 0 ? 2 : MAXT), KS, SPV, true>(a, sA / PB, b, wg);
         return;
     }
     const int nblk = (nrows + 31) >> 5, nact = nblk * 32;
     float *dsrc = lds + (size_t)a.dsrc_blk * L::BLK;
     int32_t *s_pos = (int32_t *)(dsrc + a.pos_off);             // [P] output slot of a packed row, -1 = padding or tail
-    int *s_row = s_pos + P;                                     // [P] local group << 5 | sample of a packed row, -1 = tail
-    if (tid < P) {
-        int om = -1, pj = -1;
-        if (tid < nrows) {
-            const int k = tid - rg_st;
-            om = (rg_g << 5) | k;
-            pj = a.gpos_out[(size_t)b * a.S * KS + (size_t)(sA + rg_g) * KS + k];
+    if constexpr (SPV > 0) {
+        // the sparse levels: dZ2 of the packed rows by batches of the sparse stream, masked (ends behind a barrier)
+        if (tid < P) s_pos[tid] = tid < nrows ? a.gpos_out[(size_t)b * a.S * KS + (size_t)(sA + rg_g) * KS + tid - rg_st] : -1;
+        sa_bwd_packed_sparse<P, NW, SPV>(a, buf0, dsrc, desc, b, wg, nrows);
+    } else {
+        int *s_row = s_pos + P;                                     // [P] local group << 5 | sample of a packed row, -1 = tail
+        if (tid < P) {
+            int om = -1, pj = -1;
+            if (tid < nrows) {
+                const int k = tid - rg_st;
+                om = (rg_g << 5) | k;
+                pj = a.gpos_out[(size_t)b * a.S * KS + (size_t)(sA + rg_g) * KS + k];
+            }
+            s_row[tid] = om;
+            s_pos[tid] = pj;
         }
-        s_row[tid] = om;
-        s_pos[tid] = pj;
-    }
-    if (a.w1c && tid < 3 * a.C1) {   // sa_bwd_body's table [half][column][C1 / 2] of the wanted columns
-        const int kh = a.C1 >> 1, hh = tid / (3 * kh), r = (tid / kh) % 3, cc = tid % kh;
-        dsrc[a.w1c_off + tid] = a.w1c[(hh * kh + cc) * a.D + a.c_lo + r];
-    }
-    __syncthreads();
-    // max-pool backward over the active blocks: dZ3[c][row] = dout[group][c] if sample == arg[group][c] else 0; a half-wave
-    // takes (8-channel block, 32-row block) q = blk * nblk + pb, nblk rounds for every thread
-    {
-        const float *drows = a.dout + (size_t)b * a.S * a.ld + a.c_off;
-        const uint8_t *arows = a.arg + (size_t)b * a.S * a.C3;
-        const int nq = nblk * (a.C3 >> 3);
-        const int rcp = (65536 + nblk - 1) / nblk;              // q / nblk = q * rcp >> 16 (q < 2^9, nblk <= P / 32)
+        if (a.w1c && tid < 3 * a.C1) {   // sa_bwd_body's table [half][column][C1 / 2] of the wanted columns
+            const int kh = a.C1 >> 1, hh = tid / (3 * kh), r = (tid / kh) % 3, cc = tid % kh;
+            dsrc[a.w1c_off + tid] = a.w1c[(hh * kh + cc) * a.D + a.c_lo + r];
+        }
+        __syncthreads();
+        // max-pool backward over the active blocks: dZ3[c][row] = dout[group][c] if sample == arg[group][c] else 0; a half-wave
+        // takes (8-channel block, 32-row block) q = blk * nblk + pb, nblk rounds for every thread
+        {
+            const float *drows = a.dout + (size_t)b * a.S * a.ld + a.c_off;
+            const uint8_t *arows = a.arg + (size_t)b * a.S * a.C3;
+            const int nq = nblk * (a.C3 >> 3);
+            const int rcp = (65536 + nblk - 1) / nblk;              // q / nblk = q * rcp >> 16 (q < 2^9, nblk <= P / 32)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {                           // (P * C3 / 8 tasks at most: four per thread, run_sa_bwd checks)
-            const int q = (tid >> 5) + i * (NT / 32);
-            if (q < nq) {
-                const int blk = (q * rcp) >> 16, pb = q - blk * nblk, j = pb * 32 + (tid & 31);
-                const int om = s_row[j];
-                float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-                if (om >= 0) {
-                    const int s = sA + (om >> 5), k = om & 31;
-                    const uint2 am = *(const uint2 *)(arows + (size_t)s * a.C3 + blk * 8);
-                    const float *dp = drows + (size_t)s * a.ld + blk * 8;
-                    const float4 d0 = *(const float4 *)dp, d1 = *(const float4 *)(dp + 4);
-                    v0.x = (int)(am.x & 0xFF) == k ? d0.x : 0.f;
-                    v0.y = (int)((am.x >> 8) & 0xFF) == k ? d0.y : 0.f;
-                    v0.z = (int)((am.x >> 16) & 0xFF) == k ? d0.z : 0.f;
-                    v0.w = (int)(am.x >> 24) == k ? d0.w : 0.f;
-                    v1.x = (int)(am.y & 0xFF) == k ? d1.x : 0.f;
-                    v1.y = (int)((am.y >> 8) & 0xFF) == k ? d1.y : 0.f;
-                    v1.z = (int)((am.y >> 16) & 0xFF) == k ? d1.z : 0.f;
-                    v1.w = (int)(am.y >> 24) == k ? d1.w : 0.f;
+            for (int i = 0; i < 4; ++i) {                           // (P * C3 / 8 tasks at most: four per thread, run_sa_bwd checks)
+                const int q = (tid >> 5) + i * (NT / 32);
+                if (q < nq) {
+                    const int blk = (q * rcp) >> 16, pb = q - blk * nblk, j = pb * 32 + (tid & 31);
+                    const int om = s_row[j];
+                    float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+                    if (om >= 0) {
+                        const int s = sA + (om >> 5), k = om & 31;
+                        const uint2 am = *(const uint2 *)(arows + (size_t)s * a.C3 + blk * 8);
+                        const float *dp = drows + (size_t)s * a.ld + blk * 8;
+                        const float4 d0 = *(const float4 *)dp, d1 = *(const float4 *)(dp + 4);
+                        v0.x = (int)(am.x & 0xFF) == k ? d0.x : 0.f;
+                        v0.y = (int)((am.x >> 8) & 0xFF) == k ? d0.y : 0.f;
+                        v0.z = (int)((am.x >> 16) & 0xFF) == k ? d0.z : 0.f;
+                        v0.w = (int)(am.x >> 24) == k ? d0.w : 0.f;
+                        v1.x = (int)(am.y & 0xFF) == k ? d1.x : 0.f;
+                        v1.y = (int)((am.y >> 8) & 0xFF) == k ? d1.y : 0.f;
+                        v1.z = (int)((am.y >> 16) & 0xFF) == k ? d1.z : 0.f;
+                        v1.w = (int)(am.y >> 24) == k ? d1.w : 0.f;
+                    }
+                    float *dst = buf0 + (size_t)blk * L::BLK + j * 8;
+                    *(float4 *)dst = v0;
+                    *(float4 *)(dst + 4) = v1;
                 }
-                float *dst = buf0 + (size_t)blk * L::BLK + j * 8;
-                *(float4 *)dst = v0;
-                *(float4 *)(dst + 4) = v1;
             }
         }
+        __syncthreads();
+        sa_layer_bwd_packed<P, NW, MAXT>(a.l3t, buf0, nblk, wg);
+        __syncthreads();
     }
-    __syncthreads();
-    sa_layer_bwd_packed<P, NW, MAXT>(a.l3t, buf0, nblk, wg);
-    __syncthreads();
     sa_layer_bwd_packed<P, NW, MAXT>(a.l2t, buf0, nblk, wg);
     __syncthreads();
-    if (a.w1c) {   // colour-only request: wave w takes block w (sa_l1t_colour), its slots from the row map
-        if (wave < nblk) {
-            float *orowc = a.gsa_out + (size_t)b * a.S * KS * 4;
-            if (a.C1 == 32) sa_l1t_colour<P, NW, 32>(a, buf0, dsrc + a.w1c_off, s_pos, orowc);
-            else sa_l1t_colour<P, NW, 16>(a, buf0, dsrc + a.w1c_off, s_pos, orowc);
+    if constexpr (SPV == 0) {   // (the sparse levels are split and store dZ1: run_sa_bwd checks)
+        if (a.w1c) {   // colour-only request: wave w takes block w (sa_l1t_colour), its slots from the row map
+            if (wave < nblk) {
+                float *orowc = a.gsa_out + (size_t)b * a.S * KS * 4;
+                if (a.C1 == 32) sa_l1t_colour<P, NW, 32>(a, buf0, dsrc + a.w1c_off, s_pos, orowc);
+                else sa_l1t_colour<P, NW, 16>(a, buf0, dsrc + a.w1c_off, s_pos, orowc);
+            }
+            return;
         }
-        return;
-    }
-    if (!a.split) {
-        sa_layer_bwd_packed<P, NW, MAXT>(a.l1t, buf0, nblk, wg);   // (no mask: run_sa_bwd leaves l1t.mask null)
-        __syncthreads();
+        if (!a.split) {
+            sa_layer_bwd_packed<P, NW, MAXT>(a.l1t, buf0, nblk, wg);   // (no mask: run_sa_bwd leaves l1t.mask null)
+            __syncthreads();
+        }
     }
     // the three store paths of sa_bwd_body over the active rows
     const int nc = a.c_hi - a.c_lo;
