@@ -565,6 +565,26 @@ int psg_nu_coord_apply_rooms(const float *delta, const float *ori_xyz, const uin
 int psg_nu_coord_adam_step_rooms(float *delta, float *m, float *v, const uint8_t *mask_rooms, const float *dx0,
                                  const float *sgrad_xyz, float coord_c, float coord_lr, float beta1, float beta2, float eps,
                                  int step, int B, int N, const uint8_t *room_active, float *l2_sum_rooms, psg_stream stream);
+/* The same step with separate weights, g = dx0[.][0:3] + 2 c_l2 delta + c_smooth sgrad_xyz (the ResGCN costs weigh the two
+ * terms differently); with c_smooth == c_l2 the results of psg_nu_coord_adam_step_rooms bit for bit.  Inside a window of
+ * psg_gcn_nu_field_window the step size coord_lr / (1 - beta1^t) and sqrt(1 - beta2^t) come from the window's device row
+ * (slots 3 and 2) instead of the arguments - the same values. */
+int psg_nu_coord_adam_step_rooms_w(float *delta, float *m, float *v, const uint8_t *mask_rooms, const float *dx0,
+                                   const float *sgrad_xyz, float c_smooth, float c_l2, float coord_lr, float beta1, float beta2,
+                                   float eps, int step, int B, int N, const uint8_t *room_active, float *l2_sum_rooms,
+                                   psg_stream stream);
+/* smooth(adv, adv) on coordinates: the ResGCN Smooth term (colper.py:115-120, tcolper.py:165-170) on channels 0:3 for G rooms
+ * in lockstep - every point takes the nb nearest points of its OWN moved room, itself included, and the gradient flows
+ * through both ends of every pair.  The contract of psg_smooth_knn_sym_rooms (strided rows, per-room stride in floats,
+ * nb <= 16, N <= 8192, dist_sum_rooms [G] added to, grad_out [G][N][3] written, an inactive room not touched in sum,
+ * gradient or lists, nn_out nullable with a scratch buffer of the call's own) with the pair values of
+ * psg_smooth_knn_xyz_rooms: d = sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) on direct differences, neighbours by (distance,
+ * index), u = (a_i - a_j) / d with + to the query and - to the neighbour, a pair at d == 0 adds exactly zero.  No float
+ * atomics on the gradient and a FIXED order: a point's own terms in ascending rank, then the terms it receives as a
+ * neighbour in ascending index of the point they come from.  Two launches for all rooms. */
+int psg_smooth_knn_xyz_sym_rooms(const float *adv_xyz, int adv_stride, size_t adv_room_stride, int G, int N, int nb,
+                                 float *dist_sum_rooms, float *grad_out, const uint8_t *room_active, int32_t *nn_out,
+                                 psg_stream stream);
 
 /* ONE step of NU_attack / tar_NU_attack(field = "coord" | "both") for G one-room attacks, enqueued on `stream`:
  * psg_nu_coord_apply_rooms (both: + psg_nu_tanh_color_rooms), psg_pn2_plan_build(n_forward = 1) from the moved points
@@ -739,6 +759,59 @@ typedef struct psg_gcn_nu_window_args {
  * read from a device row); the captured sequence is a single chain on `stream`.  A failed capture is counted in
  * psg_nu_graph_stats, not retried, and the window runs eagerly; while psg_gcn_prof_enable is on no graph is used. */
 int psg_gcn_nu_window(const psg_gcn_nu_window_args *args, psg_nu_graph *graph, psg_stream stream);
+
+/* ---- ResGCN attacks on the COORDINATE field (channels 0:3): an extension of the reference API.
+ * The kNN graphs are constants of the derivative, so psg_gcn_backward's dx0[.][0:3] is the exact coordinate gradient; the
+ * head's xyz graph is rebuilt from the moved points by every forward (graphs set by psg_gcn_set_graphs still win). */
+
+/* NB_attack with field = PSG_NU_FIELD_COORD | PSG_NU_FIELD_BOTH: iters x (psg_gcn_forward, psg_ce_logp_grad (mean),
+ * psg_gcn_backward, psg_pgd_step_field at c0 = 0 with (coord_alpha, coord_eps) - sign ascent, eta clamped to +-coord_eps, no
+ * [0, 1] clamp - and, both, at c0 = 3 with (alpha, eps)); channels 6:9 stay as given; images / adv_out [batch][9][n_point],
+ * the un-projected last step is returned like psg_gcn_nb_attack's.  First and last iteration run eagerly, the interior
+ * ones are captured once (a holder of the workspace's own, keyed on the model, field, both eps, both alpha and whether
+ * graphs are set) and replayed; on the legacy default stream and while psg_gcn_prof_enable is on the loop stays eager.
+ * Arguments are checked before anything is enqueued. */
+int psg_gcn_nb_attack_field(psg_gcn_model *model, psg_gcn_ws *ws, const float *images, const int32_t *labels, int field, float eps,
+                            float alpha, float coord_eps, float coord_alpha, int iters, float *adv_out, psg_stream stream);
+
+/* A WINDOW of optimiser steps of NU_attack / tar_NU_attack with field = coord | both for G one-room attacks in lockstep.
+ * The variable delta [G][N][3] (metres, zero at the start, no tanh space) is optimised by Adam, xyz = ori_xyz + delta on
+ * masked points of active rooms.  Per step, in the order of psg_gcn_nu_window: psg_nu_coord_apply_rooms (both: +
+ * psg_nu_tanh_color_rooms), psg_gcn_forward, psg_gcn_f_loss_grad_rooms (scale c_f), psg_gcn_backward, (both:
+ * psg_smooth_knn_sym_rooms on the colours,) psg_smooth_knn_xyz_sym_rooms, (both: psg_nu_adam_step(_rooms) on w,)
+ * psg_nu_coord_adam_step_rooms_w (c_smooth_xyz, c_l2_xyz, coord_lr), psg_nu_step_latch, then Smooth_xyz and L2_xyz into
+ * rows 5, 6 of the step's history row.  Cost = c_f f + c_smooth_xyz Smooth_xyz + c_l2_xyz L2_xyz (+ c_smooth Smooth +
+ * c_l2 L2 with both).  `graph` as for psg_gcn_nu_window; the device row's slot 3 carries coord_lr / (1 - beta1^t).
+ * Refusals are psg_gcn_nu_window's; field 0 is refused too (the colour path has its own entry). */
+typedef struct psg_gcn_nu_field_window_args {
+    psg_gcn_model *model;
+    psg_gcn_ws *ws;              /* created for G rooms of N points */
+    int step0, n_steps;
+    int G, N, mode;              /* mode: see psg_nu_step_latch */
+    int use_target, target;
+    int neighbour;
+    int adam_t0;
+    int field;                   /* PSG_NU_FIELD_COORD or PSG_NU_FIELD_BOTH */
+    float kappa, tsign, c_f, c_smooth, c_l2, lr, c_smooth_xyz, c_l2_xyz, coord_lr, beta1, beta2, eps;
+    float *w, *m, *v;            /* [G][N][3] colour variable and moments (field both) */
+    float *delta, *mx, *vx;      /* [G][N][3] coordinate variable and moments */
+    const float *ori_xyz;        /* [G][N][3] the clean coordinates */
+    const uint8_t *mask;         /* [G][N], nullable for NU_attack */
+    const int32_t *n_mask;       /* [G], modes 1 and 2 */
+    float *x0;                   /* [G][N][9] */
+    const float *ori;            /* [G][N][3] the clean colours (field both) */
+    const int32_t *labels;       /* [G][N] */
+    float *logits, *dlogits, *dx0; /* [G][N][13], [..][13], [..][9] scratch */
+    float *sgrad, *sgrad_xyz;    /* [G][N][3] each (sgrad: field both) */
+    int32_t *pred;               /* [G][N] */
+    float *scal;                 /* [5][G] f, Smooth, L2, Smooth_xyz, L2_xyz; zero before the first window */
+    int32_t *nn_state, *nn_xyz;  /* [G][N][neighbour] colour (field both) and coordinate neighbour lists */
+    float *hist;                 /* history rows [7][G] of the window's steps, row of step0 first */
+    float *out;                  /* [G][9][N] */
+    uint8_t *active;             /* [G] */
+    int32_t *exit_step;          /* [G] */
+} psg_gcn_nu_field_window_args;
+int psg_gcn_nu_field_window(const psg_gcn_nu_field_window_args *args, psg_nu_graph *graph, psg_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * RandLA-Net input pipeline (first piece): exact k-nearest neighbours of 3-D points.

@@ -105,6 +105,8 @@ SIGNATURES = {
     "psg_smooth_knn_xyz_rooms": (ci, [vp, ci, ctypes.c_size_t, vp, ci, ctypes.c_size_t, ci, ci, ci, vp, vp, vp, vp, vp]),
     "psg_nu_coord_apply_rooms": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "psg_nu_coord_adam_step_rooms": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, ci, ci, vp, vp, vp]),
+    "psg_nu_coord_adam_step_rooms_w": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, cf, ci, ci, ci, vp, vp, vp]),
+    "psg_smooth_knn_xyz_sym_rooms": (ci, [vp, ci, ctypes.c_size_t, ci, ci, ci, vp, vp, vp, vp, vp]),
     "psg_pn2_nu_field_step": (ci, [vp, vp]),
     "psg_gcn_model_create": (ci, [vp, ctypes.POINTER(vp), ci, ci, ctypes.POINTER(vp)]),
     "psg_gcn_model_create_cfg": (ci, [vp, ctypes.POINTER(vp), ci, ci, ci, ci, ctypes.POINTER(vp)]),
@@ -124,6 +126,8 @@ SIGNATURES = {
     "psg_gcn_edge_ptr": (vp, [vp, ci]),
     "psg_gcn_feats_ptr": (vp, [vp]),
     "psg_gcn_nu_window": (ci, [vp, vp, vp]),
+    "psg_gcn_nb_attack_field": (ci, [vp, vp, vp, vp, ci, cf, cf, cf, cf, ci, vp, vp]),
+    "psg_gcn_nu_field_window": (ci, [vp, vp, vp]),
     "psg_knn_points": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
     "psg_rla_sampler_create": (ci, [vp, vp, vp, ci, ctypes.POINTER(vp)]),
     "psg_rla_sampler_destroy": (ci, [vp]),
@@ -190,6 +194,17 @@ class GcnNuWindowArgs(ctypes.Structure):
                 [(n, cf) for n in ("kappa", "tsign", "c_f", "c_smooth", "c_l2", "lr", "beta1", "beta2", "eps")] +
                 [(n, vp) for n in ("w", "m", "v", "mask", "n_mask", "x0", "ori", "labels", "logits", "dlogits", "dx0", "sgrad", "pred",
                                    "scal", "nn_state", "hist", "out", "active", "exit_step")])
+
+
+class GcnNuFieldWindowArgs(ctypes.Structure):
+    """psg_gcn_nu_field_window_args of include/psg.h, field for field."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("step0", "n_steps", "G", "N", "mode", "use_target", "target", "neighbour", "adam_t0", "field")] +
+                [(n, cf) for n in ("kappa", "tsign", "c_f", "c_smooth", "c_l2", "lr", "c_smooth_xyz", "c_l2_xyz", "coord_lr", "beta1",
+                                   "beta2", "eps")] +
+                [(n, vp) for n in ("w", "m", "v", "delta", "mx", "vx", "ori_xyz", "mask", "n_mask", "x0", "ori", "labels", "logits",
+                                   "dlogits", "dx0", "sgrad", "sgrad_xyz", "pred", "scal", "nn_state", "nn_xyz", "hist", "out",
+                                   "active", "exit_step")])
 
 
 RLA_NU_PARTS = 32        # PSG_RLA_NU_PARTS of include/psg.h

@@ -127,6 +127,8 @@ int nu_graph_window(psg_nu_graph *graph, const void *key, size_t key_bytes, uint
 // read their step constants from this device row.
 void nu_set_step_consts(const float *row);
 const float *nu_step_consts();
+// scal rows 3, 4 (Smooth_xyz, L2_xyz of the coordinate-field NU steps) into rows 5, 6 of hist_step [7][G], zeroed (psg_attack.hip)
+int nu_field_hist_tail(float *scal, float *hist_step, int G, hipStream_t st);
 
 // Optional per-launch HIP-event timing of a workspace (psg_*_prof_enable / psg_*_prof_read): pairs of events recorded on
 // the LAUNCH stream around a launch (or a group of launches) with a tag and the algorithmic FLOPs of that launch; off in

@@ -8,6 +8,10 @@
 //   nu_coord_apply_kernel      x0[.][0:3] = ori_xyz + delta
 //   nu_coord_adam_kernel       gradient assembly + torch.optim.Adam on delta, per-room sum(delta^2)
 //   psg_pn2_nu_field_step      apply, plan, forward, f-loss, full backward, Smooth term(s), Adam step(s), latch
+// and, for the same attacks on ResGCN (the window that strings them is psg_gcn_nu_field_window in
+// psg_resgcn.hip), at the end of the file:
+//   smooth_xyz_sym_incoming_kernel   second pass of smooth(adv, adv) on coordinates (psg_smooth_knn_xyz_sym_rooms)
+//   nu_coord_adam_w_kernel           the Adam step with separate Smooth / L2 weights and device-row step constants
 #pragma once
 
 namespace {
@@ -298,6 +302,205 @@ extern "C" int psg_pn2_nu_field_step(const psg_nu_field_args *a, psg_stream stre
                                 a->scal, a->hist, a->x0, a->out, a->active, a->exit_step, a->step, stream)))
         return rc;
     hipLaunchKernelGGL(nu_field_hist_tail_kernel, dim3(psg::ceil_div(2 * G, 256)), dim3(256), 0, (hipStream_t)stream, a->scal, a->hist, G);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+namespace {
+
+// ---- smooth(adv, adv) on COORDINATES for G rooms in lockstep (psg_smooth_knn_xyz_sym_rooms; the ResGCN Smooth of
+// colper.py:115-120 / tcolper.py:165-170 on channels 0:3).  The two-launch scheme of
+// psg_smooth_knn_sym_rooms on direct differences:
+//   1. smooth_knn_xyz_kernel with the room's own points as references, one-sided: grad[i] = sum over i's neighbours in
+//      ascending rank of u(i, j) = (a_i - a_j) / d(i, j), the lists to nn, the distances to the room's sum.
+//   2. smooth_xyz_sym_incoming_kernel: grad[i] -= u(k, i) for every k that holds i among its neighbours, in ascending k.
+// Point i is a neighbour of k exactly when (d(k, i), i) <= (d(k, j*), j*) for k's LAST neighbour j*: pass 1 selects by the
+// total order (distance, index) on d = sqrtf(fma(dz, dz, fma(dy, dy, dx * dx))), so the membership test compares THAT d,
+// never d^2 (two different d^2 can round to one d, and the index then decides).  The direct-difference distance is
+// BIT-SYMMETRIC in its two points - a - b and b - a differ in sign only, the squares and everything after them are the same
+// operations on the same values - so d(k, i) evaluated here with k in the query's role is the d(i, k) any other evaluation
+// gives; the colour kernel's expansion is not, which is why it re-evaluates in pass 1's orientation.
+// Every workgroup stages each k's point with a pre-test bound and k's key (one gather per k) in 24-byte LDS slots, 2048 k at
+// a time; a point's 16 lanes walk the k in ascending order 16 at a time.  The pre-test is pass 1's: d^2 against a bound a
+// few ulps above key^2 (it only admits more), the root is taken and compared exactly on what passes.
+constexpr int SXI_T = 1024;                 // threads of the second pass
+constexpr int SXI_SUB = 16;                 // lanes per point
+constexpr int SXI_TILE = 2048;              // k staged at a time: 2048 x (16 + 8) bytes = 48 KB
+
+__global__ __launch_bounds__(SXI_T) void smooth_xyz_sym_incoming_kernel(const float *__restrict__ adv, int adv_stride, size_t adv_room_stride,
+                                                                        int N, int nb, const int32_t *__restrict__ nn,
+                                                                        float *__restrict__ grad, const uint8_t *__restrict__ room_active)
+{
+    if (room_active && !room_active[blockIdx.y]) return;
+    adv += blockIdx.y * adv_room_stride;
+    nn += (size_t)blockIdx.y * N * nb;
+    grad += (size_t)blockIdx.y * N * 3;
+    __shared__ float4 s_k[SXI_TILE];        // {x, y, z of point k, bound on d^2 (-1: no such k)}
+    __shared__ float2 s_key[SXI_TILE];      // k's last neighbour: {d(k, j*), index bits}
+    const int sub = threadIdx.x % SXI_SUB;
+    const int i = blockIdx.x * (SXI_T / SXI_SUB) + threadIdx.x / SXI_SUB;
+    const int last = (nb < N ? nb : N) - 1;                     // rank of the last neighbour every point actually holds
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    if (i < N) {
+        rx = adv[(size_t)i * adv_stride]; ry = adv[(size_t)i * adv_stride + 1]; rz = adv[(size_t)i * adv_stride + 2];
+        gx = grad[(size_t)i * 3]; gy = grad[(size_t)i * 3 + 1]; gz = grad[(size_t)i * 3 + 2];   // own terms (pass 1)
+    }
+    for (int k0 = 0; k0 < N; k0 += SXI_TILE) {
+        if (k0) __syncthreads();
+        for (int t = threadIdx.x; t < SXI_TILE; t += SXI_T) {
+            const int k = k0 + t;
+            float4 q = {0.f, 0.f, 0.f, -1.0f};
+            float2 key = {-1.0f, 0.0f};
+            if (k < N) {
+                q.x = adv[(size_t)k * adv_stride]; q.y = adv[(size_t)k * adv_stride + 1]; q.z = adv[(size_t)k * adv_stride + 2];
+                const int j = nn[(size_t)k * nb + last];
+                if (j >= 0 && j < N) {
+                    const float dx = __fsub_rn(q.x, adv[(size_t)j * adv_stride]), dy = __fsub_rn(q.y, adv[(size_t)j * adv_stride + 1]),
+                                dz = __fsub_rn(q.z, adv[(size_t)j * adv_stride + 2]);
+                    const float d = sqrtf(__fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx))));
+                    key = float2{d, __int_as_float(j)};
+                    // sqrt(d2) rounded <= d implies d2 <= d^2 (1 + 3 ulp) < the bound; a NaN / inf key admits nothing
+                    q.w = d < INFINITY ? __fadd_rn(__fmul_rn(__fmul_rn(d, d), 1.000001f), 1e-30f) : -1.0f;
+                }
+            }
+            s_k[t] = q;
+            s_key[t] = key;
+        }
+        __syncthreads();
+        const int nt = min(SXI_TILE, N - k0);
+        for (int t = sub; t < nt + sub; t += SXI_SUB) {         // (the 16 lanes of a point stay together: t - sub < nt)
+            const bool in = t < nt && i < N;
+            const float4 q = s_k[in ? t : 0];
+            const float dx = __fsub_rn(q.x, rx), dy = __fsub_rn(q.y, ry), dz = __fsub_rn(q.z, rz);   // k in the query's role
+            const float d2 = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
+            const bool cand = in && d2 <= q.w;
+            if (__ballot(cand) == 0ull) continue;               // (uniform over the wave)
+            bool hit = false;
+            float ux = 0.f, uy = 0.f, uz = 0.f;
+            if (cand) {
+                const float2 key = s_key[t];
+                const float d = sqrtf(d2);
+                hit = d < key.x || (d == key.x && i <= __float_as_int(key.y));
+                if (hit && d > 0.0f) { ux = __fdiv_rn(dx, d); uy = __fdiv_rn(dy, d); uz = __fdiv_rn(dz, d); }
+            }
+            const unsigned long long bal = __ballot(hit);
+            // the hits of this point's 16 lanes, in lane (= ascending k) order; the lanes of a point see the same bits
+            unsigned mine = (unsigned)(bal >> (threadIdx.x & 48)) & 0xFFFFu;
+            while (mine) {
+                const int s = __ffs(mine) - 1;
+                mine &= mine - 1;
+                gx -= __shfl(ux, s, SXI_SUB); gy -= __shfl(uy, s, SXI_SUB); gz -= __shfl(uz, s, SXI_SUB);
+            }
+        }
+    }
+    if (sub == 0 && i < N) { grad[(size_t)i * 3] = gx; grad[(size_t)i * 3 + 1] = gy; grad[(size_t)i * 3 + 2] = gz; }
+}
+
+// nu_coord_adam_kernel with separate weights of the Smooth and the L2 term, g = dx0[0:3] + 2 c_l2 delta + c_smooth sgrad_xyz,
+// and - inside a window that is (or will be) replayed - the step constants from the window's device row: slot 3 carries
+// coord_lr / (1 - beta1^t) (slot 1 is the colour variable's, field "both" runs two learning rates), slot 2 sqrt(1 - beta2^t).
+__global__ __launch_bounds__(256) void nu_coord_adam_w_kernel(float *__restrict__ delta, float *__restrict__ m, float *__restrict__ v,
+                                                               const uint8_t *__restrict__ mask, const float *__restrict__ dx0,
+                                                               const float *__restrict__ sgrad, float c_smooth, float c_l2, float beta1,
+                                                               float beta2, float eps, float step_size, float bc2_sqrt, int N,
+                                                               const uint8_t *__restrict__ room_active, float *__restrict__ l2_sum,
+                                                               const float *__restrict__ dconsts)
+{
+    if (dconsts) { step_size = dconsts[3]; bc2_sqrt = dconsts[2]; }
+    const size_t y = blockIdx.y;
+    if (room_active && !room_active[y]) return;
+    const size_t o3 = y * (size_t)N * 3;
+    float l2 = 0.0f;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < (size_t)N * 3; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t pt = t / 3;
+        if (mask && !mask[y * N + pt]) continue;
+        const float d = delta[o3 + t];
+        l2 += d * d;
+        float g = dx0[(y * N + pt) * 9 + t % 3] + c_l2 * 2.0f * d;
+        if (sgrad) g += c_smooth * sgrad[o3 + t];
+        const float m0 = m[o3 + t], v0 = v[o3 + t];
+        const float mm = __fadd_rn(m0, __fmul_rn(__fsub_rn(g, m0), 1.0f - beta1));
+        const float vv = __fadd_rn(__fmul_rn(v0, beta2), __fmul_rn(1.0f - beta2, __fmul_rn(g, g)));
+        m[o3 + t] = mm;
+        v[o3 + t] = vv;
+        const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2_sqrt), eps);
+        delta[o3 + t] = __fadd_rn(d, __fmul_rn(-step_size, __fdiv_rn(mm, denom)));
+    }
+    for (int o = 32; o >= 1; o >>= 1) l2 += __shfl_xor(l2, o);
+    if (!l2_sum) return;
+    __shared__ float s_l2[4];
+    if ((threadIdx.x & 63) == 0) s_l2[threadIdx.x >> 6] = l2;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(l2_sum + y, (s_l2[0] + s_l2[1]) + (s_l2[2] + s_l2[3]));
+}
+
+}  // namespace
+
+// smooth(adv, adv) on coordinates without float atomics on the gradient: see smooth_xyz_sym_incoming_kernel.  The lists the
+// second pass reads go to nn_out, or - the caller wants none - to a scratch buffer this host thread keeps and grows (never
+// inside a stream capture: the NU windows always pass their lists).
+extern "C" int psg_smooth_knn_xyz_sym_rooms(const float *adv_xyz, int adv_stride, size_t adv_room_stride, int G, int N, int nb,
+                                            float *dist_sum_rooms, float *grad_out, const uint8_t *room_active, int32_t *nn_out,
+                                            psg_stream stream)
+{
+    PSG_REQUIRE(adv_xyz && grad_out && dist_sum_rooms && N > 0 && G > 0 && G <= 65535 && adv_stride >= 3,
+                "psg_smooth_knn_xyz_sym_rooms: bad argument");
+    PSG_REQUIRE(nb > 0 && nb <= SM_MAX_NB, "psg_smooth_knn_xyz_sym_rooms: neighbour count %d out of range (1..%d)", nb, SM_MAX_NB);
+    PSG_REQUIRE(N <= 8192, "psg_smooth_knn_xyz_sym_rooms: N=%d exceeds the LDS-resident limit 8192", N);
+    hipStream_t st = (hipStream_t)stream;
+    if (!nn_out) {
+        static thread_local int32_t *scratch = nullptr;
+        static thread_local size_t scratch_n = 0;
+        const size_t need = (size_t)G * N * nb;
+        if (need > scratch_n) {
+            PSG_CHECK_HIP(hipStreamSynchronize(st));            // (launches that still read the old block)
+            if (scratch) (void)hipFree(scratch);
+            scratch = nullptr; scratch_n = 0;
+            PSG_CHECK_HIP(hipMalloc((void **)&scratch, need * sizeof(int32_t)));
+            scratch_n = need;
+        }
+        nn_out = scratch;
+    }
+    const size_t lds = (size_t)3 * SMX_SUB * ((((N + SMX_SUB - 1) / SMX_SUB + 3) & ~3) + 8) * sizeof(float);
+    const dim3 grid(psg::ceil_div(N, SMX_T / SMX_SUB), G);
+#define PSG_SMOOTH_XYZ_SYM_LAUNCH(NBT)                                                                                           \
+    do {                                                                                                                         \
+        if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)smooth_knn_xyz_kernel<NBT>));                        \
+        hipLaunchKernelGGL((smooth_knn_xyz_kernel<NBT>), grid, dim3(SMX_T), lds, st, adv_xyz, adv_stride, adv_room_stride,       \
+                           adv_xyz, adv_stride, adv_room_stride, N, nb, dist_sum_rooms, grad_out, room_active, nn_out);          \
+    } while (0)
+    if (nb <= 5) PSG_SMOOTH_XYZ_SYM_LAUNCH(5);
+    else if (nb <= 10) PSG_SMOOTH_XYZ_SYM_LAUNCH(10);
+    else PSG_SMOOTH_XYZ_SYM_LAUNCH(16);
+#undef PSG_SMOOTH_XYZ_SYM_LAUNCH
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(smooth_xyz_sym_incoming_kernel, dim3(psg::ceil_div(N, SXI_T / SXI_SUB), G), dim3(SXI_T), 0, st, adv_xyz, adv_stride,
+                       adv_room_stride, N, nb, nn_out, grad_out, room_active);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_nu_coord_adam_step_rooms_w(float *delta, float *m, float *v, const uint8_t *mask_rooms, const float *dx0,
+                                              const float *sgrad_xyz, float c_smooth, float c_l2, float coord_lr, float beta1, float beta2,
+                                              float eps, int step, int B, int N, const uint8_t *room_active, float *l2_sum_rooms,
+                                              psg_stream stream)
+{
+    PSG_REQUIRE(delta && m && v && dx0 && B > 0 && B <= 65535 && N > 0 && step >= 1, "psg_nu_coord_adam_step_rooms_w: bad argument");
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    const float step_size = (float)((double)coord_lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    hipLaunchKernelGGL(nu_coord_adam_w_kernel, dim3(std::min(grid_for((size_t)N * 3), 12), B), dim3(256), 0, (hipStream_t)stream, delta, m, v,
+                       mask_rooms, dx0, sgrad_xyz, c_smooth, c_l2, beta1, beta2, eps, step_size, bc2_sqrt, N, room_active, l2_sum_rooms,
+                       g_nu_dconsts);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+// the step's Smooth_xyz / L2_xyz sums (scal rows 3, 4) into rows 5, 6 of the history row hist_step [7][G], zeroed for the
+// next step (psg_gcn_nu_field_window; psg_pn2_nu_field_step launches the kernel itself)
+int psg::nu_field_hist_tail(float *scal, float *hist_step, int G, hipStream_t st)
+{
+    hipLaunchKernelGGL(nu_field_hist_tail_kernel, dim3(psg::ceil_div(2 * G, 256)), dim3(256), 0, st, scal, hist_step, G);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
 }

@@ -946,6 +946,14 @@ struct psg_gcn_ws {
     uint64_t nb_model_gen = 0;       // the model's generation number, not its address (psg_common.h)
     float nb_eps = 0.f, nb_alpha = 0.f;
     bool nb_fixed = false;
+    // psg_gcn_nb_attack_field: the clean coordinates, and the hipGraph of one interior iteration of the coordinate-field loop
+    // with what it is valid for (a holder of its own: the colour loop's graph above survives a field call and vice versa)
+    float *ori_xyz;            // [B*N][3]
+    psg::GraphSlot nbf;
+    uint64_t nbf_model_gen = 0;
+    int nbf_field = 0;
+    float nbf_eps = 0.f, nbf_alpha = 0.f, nbf_ceps = 0.f, nbf_calpha = 0.f;
+    bool nbf_fixed = false;
     EvLog prof;              // psg_gcn_prof_enable
 };
 
@@ -1252,6 +1260,7 @@ extern "C" int psg_gcn_ws_create_cfg(psg_ctx *ctx, int batch, int n_point, int n
         ws->dx0 = bp.take<float>(R * 9);
         ws->xyz = bp.take<float>(R * 3);
         ws->nb_labels = bp.take<int32_t>(R);
+        ws->ori_xyz = bp.take<float>(R * 3);
     };
     if (int rc = carve_arena(&ws->arena, &ws->bytes, "psg_gcn_ws_create", layout)) {
         delete ws;
@@ -1271,6 +1280,7 @@ extern "C" int psg_gcn_ws_destroy(psg_gcn_ws *ws)
 {
     if (!ws) return PSG_OK;
     ws->nb.destroy();
+    ws->nbf.destroy();
     if (ws->arena) (void)hipFree(ws->arena);
     ws->prof.destroy();
     delete ws;
@@ -1790,4 +1800,156 @@ extern "C" int psg_gcn_nu_window(const psg_gcn_nu_window_args *a, psg_nu_graph *
     return nu_graph_window(a->ws->prof.on ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, a->n_steps, a->step0,
                            a->adam_t0, a->lr, a->beta1, a->beta2, (hipStream_t)stream,
                            [&](const float *rows) { return gcn_nu_window_steps(a, rows, stream); });
+}
+
+// ====================================================================================== coordinate-field attacks
+// An extension of the reference API: the reference's colper.py:17-37 branches on `atype` and ships the
+// colour branch only.  The kNN graphs are constants of the derivative (topk under no_grad), so psg_gcn_backward's dx0[0:3]
+// IS the coordinate gradient; what changes is that the head's xyz graph follows the moved points - it is never frozen here.
+
+// NB_attack with field = coord | both: iters x (forward, CE, backward, psg_pgd_step_field on channels 0:3 - sign step, eta
+// clamped to +-coord_eps, no [0, 1] clamp - and, both, on 3:6); the un-projected last step is returned, as on colours.
+extern "C" int psg_gcn_nb_attack_field(psg_gcn_model *m, psg_gcn_ws *ws, const float *images, const int32_t *labels, int field,
+                                       float eps, float alpha, float coord_eps, float coord_alpha, int iters, float *adv_out,
+                                       psg_stream stream)
+{
+    PSG_REQUIRE(m && ws && images && labels && adv_out, "psg_gcn_nb_attack_field: null argument");
+    PSG_REQUIRE(iters > 0, "psg_gcn_nb_attack_field: iters must be positive");
+    PSG_REQUIRE(field == PSG_NU_FIELD_COORD || field == PSG_NU_FIELD_BOTH,
+                "psg_gcn_nb_attack_field: field %d is neither coord (%d) nor both (%d); colours alone are psg_gcn_nb_attack", field,
+                PSG_NU_FIELD_COORD, PSG_NU_FIELD_BOTH);
+    PSG_REQUIRE(m->n_blocks == ws->n_blocks && m->block == ws->block && m->conv == ws->conv,
+                "psg_gcn_nb_attack_field: model / workspace configuration mismatch");
+    hipStream_t st = (hipStream_t)stream;
+    const int B = ws->B, N = ws->N;
+    const size_t R = (size_t)B * N;
+    const bool both = field == PSG_NU_FIELD_BOTH;
+    int rc;
+    if ((rc = psg_to_point_major(images, B, 9, N, ws->x0, st))) return rc;
+    hipLaunchKernelGGL(extract_color3_kernel, dim3(ceil_div((int)(R * 3), 256)), dim3(256), 0, st, ws->x0, ws->ori, R);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(extract3_kernel, dim3(ceil_div((int)(R * 3), 256)), dim3(256), 0, st, ws->x0, ws->ori_xyz, R);
+    PSG_LAUNCH_CHECK();
+    PSG_CHECK_HIP(hipMemcpyAsync(ws->nb_labels, labels, R * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    ws->head_graph_frozen = false;            // the points move: every forward rebuilds the head's xyz graph
+    auto iteration = [&](bool last) -> int {
+        int r;
+        if ((r = psg_gcn_forward(m, ws, ws->x0, ws->logits, st))) return r;
+        if ((r = psg_ce_logp_grad(ws->logits, ws->nb_labels, 0, (int)R, (int)R, NCLS, 1.0f / (float)R, ws->dlogits, nullptr, st)))
+            return r;
+        if ((r = psg_gcn_backward(m, ws, ws->dlogits, ws->dx0, st))) return r;
+        if ((r = psg_pgd_step_field(ws->x0, ws->dx0, ws->ori_xyz, nullptr, B, N, 0, coord_alpha, coord_eps, 1.0f, last ? 1 : 0, st)))
+            return r;
+        return both ? psg_pgd_step_field(ws->x0, ws->dx0, ws->ori, nullptr, B, N, 3, alpha, eps, 1.0f, last ? 1 : 0, st) : PSG_OK;
+    };
+    // first and last iteration eager, the interior ones captured once (into ws->nbf) and replayed, as in psg_gcn_nb_attack;
+    // the captured sequence is a single chain on `st`.  On the legacy default stream (no capture there), under the
+    // launch tracer and while the workspace is profiling, the loop stays eager.
+    int it = 0;
+    if ((rc = iteration(iters == 1))) return rc;
+    it = 1;
+    static const bool use_graph = !((psg::env_int("PSG_GCN_NO_GRAPH", 0) != 0)) && !trace_sync_enabled();
+    if (use_graph && st && !ws->prof.on && iters - 1 - it >= 2) {
+        const bool same_key = ws->nbf_model_gen == m->gen && ws->nbf_field == field && ws->nbf_eps == eps && ws->nbf_alpha == alpha &&
+                              ws->nbf_ceps == coord_eps && ws->nbf_calpha == coord_alpha && ws->nbf_fixed == ws->fixed_graphs;
+        if (!same_key) PSG_CHECK_HIP(ws->nbf.forget(st));
+        if (!ws->nbf.exec && !ws->nbf.capture_failed) {
+            ws->nbf.capture(st, [&] { return iteration(false); });
+            ws->nbf_model_gen = m->gen; ws->nbf_field = field; ws->nbf_eps = eps; ws->nbf_alpha = alpha;
+            ws->nbf_ceps = coord_eps; ws->nbf_calpha = coord_alpha; ws->nbf_fixed = ws->fixed_graphs;
+        }
+        if (ws->nbf.exec) {
+            PSG_CHECK_HIP(ws->nbf.replay(st, iters - 1 - it));
+            it = iters - 1;
+        } else {
+            ws->nbf.note_eager(iters - 1 - it);
+        }
+    }
+    for (; it < iters; ++it)
+        if ((rc = iteration(it == iters - 1))) return rc;
+    return psg_to_channel_major(ws->x0, B, 9, N, adv_out, st);
+}
+
+// NU_attack / tar_NU_attack with field = coord | both for G one-room attacks in lockstep: the step sequence of
+// gcn_nu_window_steps with delta applied first and the coordinate Smooth term and Adam step added - apply, forward,
+// f-loss, backward, Smooth term(s), Adam step(s), latch, then the two coordinate sums into rows 5, 6 of the history row.
+// Everything is a launch or an asynchronous device-to-device copy on `stream`: a window is a single chain, and - this
+// network has no FPS plan and draws nothing inside a step - it is captured and replayed like the colour windows.
+static int gcn_nu_field_window_steps(const psg_gcn_nu_field_window_args *a, const float *dconsts_rows, psg_stream stream)
+{
+    const int G = a->G, N = a->N;
+    const bool both = a->field == PSG_NU_FIELD_BOTH;
+    int rc = PSG_OK;
+    for (int i = 0; i < a->n_steps && rc == PSG_OK; ++i) {
+        const int step = a->step0 + i, adam_t = a->adam_t0 + i + 1;
+        const int f_target = a->use_target ? a->target : 0;
+        float *hist = a->hist + (size_t)i * 7 * G;
+        if ((rc = psg_nu_coord_apply_rooms(a->delta, a->ori_xyz, a->mask, G, N, a->active, a->x0, stream))) break;
+        if (both && (rc = psg_nu_tanh_color_rooms(a->w, a->mask, G, N, a->x0, stream))) break;
+        if ((rc = psg_gcn_forward(a->model, a->ws, a->x0, a->logits, stream))) break;
+        if ((rc = psg_gcn_f_loss_grad_rooms(a->logits, a->labels, f_target, a->mask, a->mode, G, N, NCLS, a->kappa, a->tsign, a->c_f,
+                                            a->dlogits, a->scal, a->pred, stream)))
+            break;
+        if ((rc = psg_gcn_backward(a->model, a->ws, a->dlogits, a->dx0, stream))) break;
+        if (both && (rc = psg_smooth_knn_sym_rooms(a->x0 + 3, 9, (size_t)N * 9, G, N, a->neighbour, a->scal + G, a->sgrad, a->active,
+                                                   a->nn_state, stream)))
+            break;
+        if ((rc = psg_smooth_knn_xyz_sym_rooms(a->x0, 9, (size_t)N * 9, G, N, a->neighbour, a->scal + 3 * G, a->sgrad_xyz, a->active,
+                                               a->nn_xyz, stream)))
+            break;
+        nu_set_step_consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
+        if (both)
+            rc = G > 1 ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr,
+                                                a->beta1, a->beta2, a->eps, adam_t, G, N, a->active, a->scal + 2 * G, stream)
+                       : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr, a->beta1,
+                                          a->beta2, a->eps, adam_t, 1, N, a->scal + 2, stream);
+        if (rc == PSG_OK)
+            rc = psg_nu_coord_adam_step_rooms_w(a->delta, a->mx, a->vx, a->mask, a->dx0, a->sgrad_xyz, a->c_smooth_xyz, a->c_l2_xyz,
+                                                a->coord_lr, a->beta1, a->beta2, a->eps, adam_t, G, N, a->active, a->scal + 4 * G, stream);
+        if (rc == PSG_OK)
+            rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, 1, N,
+                                   a->mode, a->scal, hist, a->x0, a->out, a->active, a->exit_step, step, stream);
+        nu_set_step_consts(nullptr);
+        if (rc == PSG_OK) rc = psg::nu_field_hist_tail(a->scal, hist, G, (hipStream_t)stream);
+    }
+    nu_set_step_consts(nullptr);
+    return rc;
+}
+
+extern "C" int psg_gcn_nu_field_window(const psg_gcn_nu_field_window_args *a, psg_nu_graph *graph, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws && a->delta && a->mx && a->vx && a->ori_xyz && a->sgrad_xyz && a->nn_xyz && a->x0 && a->labels &&
+                    a->logits && a->dlogits && a->dx0 && a->pred && a->scal && a->hist && a->out && a->active && a->exit_step,
+                "psg_gcn_nu_field_window: null argument");
+    PSG_REQUIRE(a->field == PSG_NU_FIELD_COORD || a->field == PSG_NU_FIELD_BOTH,
+                "psg_gcn_nu_field_window: field %d is neither coord (%d) nor both (%d); colours alone are psg_gcn_nu_window", a->field,
+                PSG_NU_FIELD_COORD, PSG_NU_FIELD_BOTH);
+    PSG_REQUIRE(a->field != PSG_NU_FIELD_BOTH || (a->w && a->m && a->v && a->ori && a->sgrad && a->nn_state),
+                "psg_gcn_nu_field_window: field both needs the colour state");
+    PSG_REQUIRE(a->n_steps > 0 && a->G > 0 && a->N > 0, "psg_gcn_nu_field_window: n_steps=%d G=%d N=%d out of range", a->n_steps, a->G, a->N);
+    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->N,
+                "psg_gcn_nu_field_window: rooms form only - the workspace is for %d rooms of %d points, the window for %d of %d", a->ws->B,
+                a->ws->N, a->G, a->N);
+    PSG_REQUIRE(a->model->n_blocks == a->ws->n_blocks && a->model->block == a->ws->block && a->model->conv == a->ws->conv,
+                "psg_gcn_nu_field_window: model / workspace configuration mismatch");
+    PSG_REQUIRE(a->mode >= 0 && a->mode <= 2, "psg_gcn_nu_field_window: mode %d out of range", a->mode);
+    PSG_REQUIRE(a->mode == 0 || (a->mask && a->n_mask), "psg_gcn_nu_field_window: modes 1 and 2 need mask and n_mask");
+    PSG_REQUIRE((a->mode == 2) == (a->use_target != 0), "psg_gcn_nu_field_window: mode 2 is the one that takes a target class");
+    PSG_REQUIRE(!a->use_target || (a->target >= 0 && a->target < NCLS), "psg_gcn_nu_field_window: target class %d out of range", a->target);
+    PSG_REQUIRE(a->neighbour > 0 && a->neighbour <= 16 && a->N <= 8192,
+                "psg_gcn_nu_field_window: neighbour=%d (1..16) / N=%d (<= 8192) out of range", a->neighbour, a->N);
+    // what a captured window is valid for: the argument block without what the device rows carry (step, both step sizes)
+    struct Key { psg_gcn_nu_field_window_args a; int fixed_graphs; } key;
+    memset(&key, 0, sizeof(key));
+    key.a = *a;
+    key.a.step0 = 0; key.a.adam_t0 = 0; key.a.lr = 0.0f; key.a.coord_lr = 0.0f;
+    key.fixed_graphs = a->ws->fixed_graphs ? 1 : 0;
+    // slot 3 of the device rows: the coordinate variable's step size coord_lr / (1 - beta1^t), as
+    // psg_nu_coord_adam_step_rooms_w computes it from its arguments
+    float slot3[PSG_NU_GRAPH_MAX_STEPS];
+    for (int i = 0; i < a->n_steps && i < PSG_NU_GRAPH_MAX_STEPS; ++i)
+        slot3[i] = (float)((double)a->coord_lr / (1.0 - pow((double)a->beta1, (double)(a->adam_t0 + i + 1))));
+    return nu_graph_window(a->ws->prof.on ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, a->n_steps, a->step0,
+                           a->adam_t0, a->lr, a->beta1, a->beta2, (hipStream_t)stream,
+                           [&](const float *rows) { return gcn_nu_field_window_steps(a, rows, stream); }, slot3);
 }

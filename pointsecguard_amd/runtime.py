@@ -582,6 +582,21 @@ class GCNWorkspace(_Handle):
                   int(iters), ptr(out), stream())
         return out
 
+    def nb_attack_field(self, model, images, labels, field, eps, alpha, coord_eps, coord_alpha, iters, out=None):
+        """psg_gcn_nb_attack_field: NB_attack on the coordinates (field 1) or on coordinates and colours (field 2)."""
+        require_cuda(images, "images", torch.float32)
+        require_cuda(labels, "labels", torch.int32)
+        if out is None:
+            out = torch.empty_like(images)
+        _lib.call("psg_gcn_nb_attack_field", model.handle, self.handle, ptr(images), ptr(labels), int(field), float(eps),
+                  float(alpha), float(coord_eps), float(coord_alpha), int(iters), ptr(out), stream())
+        return out
+
+    def nu_field_window(self, args, graph=None):
+        """psg_gcn_nu_field_window: a window of optimiser steps of the coordinate-field NU attacks (args:
+        _lib.GcnNuFieldWindowArgs; graph as for nu_window)."""
+        _lib.call("psg_gcn_nu_field_window", ctypes.byref(args), graph, stream())
+
     def nu_window(self, args, graph=None):
         """psg_gcn_nu_window: the optimiser steps args.step0 .. args.step0 + args.n_steps - 1 of the ResGCN NU attacks for
         args.G rooms in lockstep, in one call (args: _lib.GcnNuWindowArgs whose model / ws fields hold the handles; graph:
