@@ -860,7 +860,8 @@ int psg_rla_ws_create(psg_ctx *ctx, int n_points, psg_rla_ws **out);
 /* A workspace for `batch` clouds of n_points each that are attacked together (the reference's val_batch_size is 1,
  * helper_tool.py:52, so this is a launch-coalescing device: the clouds stay independent, every neighbour / pooling /
  * interpolation index stays inside its cloud, and one launch of each kernel serves all of them).  Every [n_points][..]
- * argument of the calls below becomes [batch][n_points][..].  l_inf metric only (the l_2 step normalises per cloud). */
+ * argument of the calls below becomes [batch][n_points][..].  Both metrics: the l_2 step of psg_rla_bim_attack takes its two
+ * norms per cloud (one workgroup per cloud, a fixed summation order), as bim.py:84-98 normalises per sample. */
 int psg_rla_ws_create_batch(psg_ctx *ctx, int n_points, int batch, psg_rla_ws **out);
 int psg_rla_ws_destroy(psg_rla_ws *ws);
 size_t psg_rla_ws_bytes(const psg_rla_ws *ws);
@@ -985,6 +986,67 @@ typedef struct psg_rla_nu_window_args {
     int32_t *exit_step;          /* [G], -1 before */
 } psg_rla_nu_window_args;
 int psg_rla_nu_window(const psg_rla_nu_window_args *args, psg_nu_graph *graph, psg_stream stream);
+
+/* TBIM / tar_NBattack (bim.py:277-505) on G clouds of n points in lockstep.  Buffers are cloud-major as above; a cloud whose
+ * `running` / `active` byte is clear is not touched.
+ *
+ * psg_rla_bim_step_clouds: psg_rla_bim_step's update of every running cloud (running [G] bytes, NULL: all) with that cloud's own
+ * norms: norms [2][G] = {|g|^2 of cloud g, |delta|^2 of cloud g}, delta [G][n][3] (both l_2 only).  The norms keep
+ * psg_rla_bim_step's summation order (one workgroup per cloud, double accumulation, the fixed tree), so a cloud's colours are
+ * bit-equal to psg_rla_bim_step on that cloud alone.  No byte of feat, delta or norms of a cloud that is not running is
+ * written, whatever its dfeat holds. */
+int psg_rla_bim_step_clouds(float *feat, const float *dfeat, const float *ori, const uint8_t *running, int G, int n, float eps,
+                            float alpha, int l2_metric, float *norms, float *delta, psg_stream stream);
+/* The evaluation TBIM.batch_attack makes in iteration `it` BEFORE that iteration's update, for every active cloud: pred [G][n] =
+ * the first maximum of logits [G][n][13], n_correct = #(pred == labels), n_hits = #(mask & pred == hit_ys); hist_row [G][3] =
+ * {n_correct, n_hits, 0}.  The cloud leaves when it >= 1 and den * n_hits > num * n_mask[g] (integers): out_pred [G][n] = pred,
+ * out_stats [G][3] = the history row, exit_step[g] = it, leaving[g] = 1 (0 for an active cloud that stays).  final != 0 writes
+ * out_pred and out_stats of every active cloud (the cap; exit_step only where the test fires).  `active` is NOT cleared and the
+ * colours are not snapshot here: the leaving cloud still receives this iteration's update, then psg_rla_tbim_retire_clouds.
+ * Inside a replayed window `it` is read from the window's step-constant device row.  scratch: [G][2 * PSG_RLA_NU_PARTS + 1]. */
+int psg_rla_tbim_latch_clouds(const float *logits, const int32_t *labels, const int32_t *hit_ys, const uint8_t *mask,
+                              const int32_t *n_mask, int G, int n, int num, int den, int it, int final, float *hist_row, int32_t *pred,
+                              int32_t *out_pred, float *out_stats, const uint8_t *active, uint8_t *leaving, int32_t *exit_step,
+                              int32_t *scratch, psg_stream stream);
+/* After the update: every active cloud that is leaving (or, final != 0, every active cloud) gets out_adv [G][n][3] = the colours
+ * of feat [G][n][6], then active[g] = 0 and leaving[g] = 0. */
+int psg_rla_tbim_retire_clouds(const float *feat, int G, int n, int final, float *out_adv, uint8_t *active, uint8_t *leaving,
+                               psg_stream stream);
+
+/* One window of the lockstep TBIM: for each of n_steps iterations it = it0 + i: psg_rla_forward, psg_rla_tbim_latch_clouds
+ * (history row i; final on the window's last step when `final` is set), the masked hinge gradient against loss_ys with `sign`
+ * (psg_rla_colper_grad_masked), psg_rla_backward, psg_rla_bim_step_clouds on the active clouds, psg_rla_tbim_retire_clouds.
+ * There is no tail forward: a cloud's snapshot is the prediction BEFORE the update of its last iteration and the colours AFTER
+ * it, as in TBIM.batch_attack.  hit_ys are the labels the hits are counted against (the target on the origin points), loss_ys
+ * the ones the hinge is taken against (the same for goal 't' / 'tm', the true labels for goal 'ut').  `graph` as for
+ * psg_rla_nu_window: first window of a shape eager, second captured, later ones replayed, a single chain on `stream`; no graph
+ * while psg_rla_prof_enable is on or before the first psg_rla_forward of (cloud, model).  The key is this block without it0. */
+typedef struct psg_rla_tbim_window_args {
+    psg_rla_model *model;
+    psg_rla_ws *ws;
+    int n_steps, G, N, it0;
+    int num, den;                /* the exit threshold num / den */
+    int final, l2_metric;
+    float eps, alpha, sign;      /* sign: -1 for goal 't' / 'tm', +1 for goal 'ut' */
+    const float *ori;            /* [G][N][3] clean colours */
+    const uint8_t *mask;         /* [G][N], required */
+    const int32_t *n_mask;       /* [G], required */
+    const int32_t *labels, *hit_ys, *loss_ys;   /* [G][N] */
+    float *feat;                 /* [G][N][6], xyz in columns 0..2 */
+    float *logits, *dlogits;     /* [G][N][13] */
+    float *dfeat;                /* [G][N][6] */
+    float *norms;                /* [2][G] */
+    float *delta;                /* [G][N][3] */
+    int32_t *pred;               /* [G][N] */
+    int32_t *scratch;            /* [G][2 * PSG_RLA_NU_PARTS + 1] */
+    float *hist;                 /* [n_steps][G][3] */
+    float *out_adv;              /* [G][N][3] */
+    int32_t *out_pred;           /* [G][N] */
+    float *out_stats;            /* [G][3] */
+    uint8_t *active, *leaving;   /* [G] */
+    int32_t *exit_step;          /* [G], -1 before */
+} psg_rla_tbim_window_args;
+int psg_rla_tbim_window(const psg_rla_tbim_window_args *args, psg_nu_graph *graph, psg_stream stream);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,10 @@ SIGNATURES = {
     "psg_rla_nu_adam_clouds": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, ci, vp]),
     "psg_rla_nu_latch_clouds": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "psg_rla_nu_window": (ci, [vp, vp, vp]),
+    "psg_rla_bim_step_clouds": (ci, [vp, vp, vp, vp, ci, ci, cf, cf, ci, vp, vp, vp]),
+    "psg_rla_tbim_latch_clouds": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "psg_rla_tbim_retire_clouds": (ci, [vp, ci, ci, ci, vp, vp, vp, vp]),
+    "psg_rla_tbim_window": (ci, [vp, vp, vp]),
     "psg_seg_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
     "psg_vote_add": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]),
     "psg_vote_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
@@ -217,6 +221,16 @@ class RlaNuWindowArgs(ctypes.Structure):
                 [(n, cf) for n in ("cs", "lr")] +
                 [(n, vp) for n in ("xs", "dws", "m", "v", "mask", "n_mask", "labels", "ys", "feat", "logits", "dlogits", "dfeat", "dist2",
                                    "partials", "pred", "scratch", "hist", "out_adv", "out_pred", "out_stats", "active", "exit_step")])
+
+
+class RlaTbimWindowArgs(ctypes.Structure):
+    """psg_rla_tbim_window_args of include/psg.h, field for field (4 bytes of padding follow the three floats)."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("n_steps", "G", "N", "it0", "num", "den", "final", "l2_metric")] +
+                [(n, cf) for n in ("eps", "alpha", "sign")] +
+                [(n, vp) for n in ("ori", "mask", "n_mask", "labels", "hit_ys", "loss_ys", "feat", "logits", "dlogits", "dfeat", "norms",
+                                   "delta", "pred", "scratch", "hist", "out_adv", "out_pred", "out_stats", "active", "leaving",
+                                   "exit_step")])
 
 
 class NuFieldArgs(ctypes.Structure):

@@ -2222,3 +2222,232 @@ extern "C" int psg_rla_nu_window(const psg_rla_nu_window_args *a, psg_nu_graph *
     return nu_graph_window(plain ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, total, a->adam_t0 - 1, a->adam_t0 - 1, a->lr,
                            0.9f, 0.999f, (hipStream_t)stream, [&](const float *rows) { return rla_nu_window_steps(a, rows, stream); }, lr_rows);
 }
+
+// ---- TBIM / tar_NBattack (bim.py:277-505) on G clouds in lockstep.  blockIdx.y = cloud (blockIdx.x for the one-workgroup-per-
+// cloud kernels); a cloud that is not running is skipped by whole workgroups.  The update is psg_rla_bim_step's, expression for
+// expression, with the cloud's own norms; the latch has TBIM.batch_attack's ordering: the exit is decided on the forward BEFORE
+// the iteration's update, the leaving cloud still takes that update, and only then are its colours snapshot and it is retired.
+namespace {
+// sq_norm_kernel for the running clouds only: the same strides, the same double accumulation, the same tree
+__global__ __launch_bounds__(1024) void sq_norm_clouds_kernel(const float *__restrict__ a, int ld, int c0, size_t nc,
+                                                              const uint8_t *__restrict__ running, float *__restrict__ out)
+{
+    __shared__ double s_part[16];
+    if (running && !running[blockIdx.x]) return;
+    const float *p = a + (size_t)blockIdx.x * nc * ld;
+    double s = 0.0;
+    for (size_t t = threadIdx.x; t < nc * 3; t += blockDim.x) {
+        const float v = p[(t / 3) * ld + c0 + (t % 3)];
+        s += (double)v * (double)v;
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_part[w];
+        out[blockIdx.x] = (float)tot;
+    }
+}
+
+__global__ void bim_linf_clouds_kernel(float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ ori,
+                                       const uint8_t *__restrict__ running, size_t n, float alpha, float eps)
+{
+    const int cl = blockIdx.y;
+    if (running && !running[cl]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * 3) return;
+    const size_t i = (size_t)cl * n + t / 3;
+    const int c = (int)(t % 3);
+    t += (size_t)cl * n * 3;
+    const float g = dfeat[i * 6 + 3 + c], x = ori[t];
+    const float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
+    float v = feat[i * 6 + 3 + c] + alpha * sg;
+    v = fminf(fmaxf(v, x - eps), x + eps);
+    feat[i * 6 + 3 + c] = fminf(fmaxf(v, 0.0f), 1.0f);
+}
+
+__global__ void bim_l2_delta_clouds_kernel(const float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ ori,
+                                           const uint8_t *__restrict__ running, size_t n, float alpha,
+                                           const float *__restrict__ gnorm2, float *__restrict__ delta)
+{
+    const int cl = blockIdx.y;
+    if (running && !running[cl]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * 3) return;
+    const size_t i = (size_t)cl * n + t / 3;
+    const int c = (int)(t % 3);
+    t += (size_t)cl * n * 3;
+    const float gn = fmaxf(1e-12f, sqrtf(gnorm2[cl]));
+    delta[t] = feat[i * 6 + 3 + c] - ori[t] + alpha * (dfeat[i * 6 + 3 + c] / gn);
+}
+
+__global__ void bim_l2_apply_clouds_kernel(float *__restrict__ feat, const float *__restrict__ ori, const float *__restrict__ delta,
+                                           const uint8_t *__restrict__ running, size_t n, float eps, const float *__restrict__ dnorm2)
+{
+    const int cl = blockIdx.y;
+    if (running && !running[cl]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * 3) return;
+    const size_t i = (size_t)cl * n + t / 3;
+    const int c = (int)(t % 3);
+    t += (size_t)cl * n * 3;
+    const float dn = sqrtf(dnorm2[cl]);
+    const float scale = dn > eps ? eps / dn : 1.0f;
+    feat[i * 6 + 3 + c] = fminf(fmaxf(ori[t] + delta[t] * scale, 0.0f), 1.0f);
+}
+
+// TBIM latch, second half (the first is nu_latch_count_kernel): every workgroup of a live cloud adds the cloud's counts and
+// takes the exit decision (integers); a leaving cloud (or, final, every live one) gets its slice of out_pred; workgroup 0 writes
+// the history row, the statistics, exit_step and the leaving byte.  `active` is read by nobody here and written by nobody.
+__global__ __launch_bounds__(256) void tbim_latch_commit_kernel(const int32_t *__restrict__ pred, const int32_t *__restrict__ n_mask,
+                                                                const int32_t *__restrict__ scratch, int n, int num, int den, int it_arg,
+                                                                int final, const float *__restrict__ consts, float *__restrict__ hist_row,
+                                                                int32_t *__restrict__ out_pred, float *__restrict__ out_stats,
+                                                                uint8_t *__restrict__ leaving, int32_t *__restrict__ exit_step)
+{
+    const int g = blockIdx.y, parts = gridDim.x;
+    const int32_t *sc = scratch + (size_t)g * (2 * parts + 1);
+    if (!sc[0]) return;
+    const int it = consts ? __builtin_bit_cast(int, consts[0]) : it_arg;
+    int nc = 0, nh = 0;
+    for (int p = 0; p < parts; ++p) { nc += sc[1 + 2 * p]; nh += sc[2 + 2 * p]; }
+    const bool exits = it >= 1 && (long long)den * nh > (long long)num * n_mask[g];
+    if (exits || final) {
+        const int chunk = (n + parts - 1) / parts;
+        const int lo = min(n, (int)blockIdx.x * chunk), hi = min(n, lo + chunk);
+        for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+            const size_t r = (size_t)g * n + i;
+            out_pred[r] = pred[r];
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const float row[3] = {(float)nc, (float)nh, 0.0f};
+        for (int k = 0; k < 3; ++k) hist_row[g * 3 + k] = row[k];
+        if (exits || final)
+            for (int k = 0; k < 3; ++k) out_stats[g * 3 + k] = row[k];
+        if (exits) exit_step[g] = it;
+        leaving[g] = exits ? 1 : 0;
+    }
+}
+
+// one workgroup per cloud: the flags are read before anything is written, the colours copied, then the flags cleared
+__global__ __launch_bounds__(1024) void tbim_retire_kernel(const float *__restrict__ feat, size_t n, int final, float *__restrict__ out_adv,
+                                                           uint8_t *__restrict__ active, uint8_t *__restrict__ leaving)
+{
+    const int g = blockIdx.x;
+    const bool go = active[g] != 0 && (leaving[g] != 0 || final != 0);
+    __syncthreads();
+    if (!go) return;
+    const size_t base = (size_t)g * n;
+    for (size_t t = threadIdx.x; t < n * 3; t += blockDim.x) out_adv[base * 3 + t] = feat[(base + t / 3) * 6 + 3 + (t % 3)];
+    if (threadIdx.x == 0) { active[g] = 0; leaving[g] = 0; }
+}
+}  // namespace
+
+extern "C" int psg_rla_bim_step_clouds(float *feat, const float *dfeat, const float *ori, const uint8_t *running, int G, int n, float eps,
+                                       float alpha, int l2_metric, float *norms, float *delta, psg_stream stream)
+{
+    PSG_REQUIRE(feat && dfeat && ori && (!l2_metric || (norms && delta)), "psg_rla_bim_step_clouds: null argument");
+    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_bim_step_clouds: G=%d n=%d out of range", G, n);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)n;
+    const dim3 grid(blocks_for(N * 3), G);
+    if (!l2_metric) {
+        hipLaunchKernelGGL(bim_linf_clouds_kernel, grid, dim3(256), 0, st, feat, dfeat, ori, running, N, alpha, eps);
+        PSG_LAUNCH_CHECK();
+        return PSG_OK;
+    }
+    hipLaunchKernelGGL(sq_norm_clouds_kernel, dim3(G), dim3(1024), 0, st, dfeat, 6, 3, N, running, norms);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bim_l2_delta_clouds_kernel, grid, dim3(256), 0, st, (const float *)feat, dfeat, ori, running, N, alpha,
+                       (const float *)norms, delta);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sq_norm_clouds_kernel, dim3(G), dim3(1024), 0, st, (const float *)delta, 3, 0, N, running, norms + G);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bim_l2_apply_clouds_kernel, grid, dim3(256), 0, st, feat, ori, (const float *)delta, running, N, eps,
+                       (const float *)(norms + G));
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_rla_tbim_latch_clouds(const float *logits, const int32_t *labels, const int32_t *hit_ys, const uint8_t *mask,
+                                         const int32_t *n_mask, int G, int n, int num, int den, int it, int final, float *hist_row,
+                                         int32_t *pred, int32_t *out_pred, float *out_stats, const uint8_t *active, uint8_t *leaving,
+                                         int32_t *exit_step, int32_t *scratch, psg_stream stream)
+{
+    PSG_REQUIRE(logits && labels && hit_ys && hist_row && pred && out_pred && out_stats && active && leaving && exit_step && scratch,
+                "psg_rla_tbim_latch_clouds: null argument");
+    PSG_REQUIRE(mask && n_mask, "psg_rla_tbim_latch_clouds: mask and n_mask are required");
+    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_tbim_latch_clouds: G=%d n=%d out of range", G, n);
+    PSG_REQUIRE(num >= 0 && den > 0 && it >= 0, "psg_rla_tbim_latch_clouds: num=%d den=%d it=%d out of range", num, den, it);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nu_latch_count_kernel, dim3(kNuParts, G), dim3(256), 0, st, logits, labels, hit_ys, mask, active, n, pred, scratch);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tbim_latch_commit_kernel, dim3(kNuParts, G), dim3(256), 0, st, (const int32_t *)pred, n_mask,
+                       (const int32_t *)scratch, n, num, den, it, final, psg::nu_step_consts(), hist_row, out_pred, out_stats, leaving,
+                       exit_step);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_rla_tbim_retire_clouds(const float *feat, int G, int n, int final, float *out_adv, uint8_t *active, uint8_t *leaving,
+                                          psg_stream stream)
+{
+    PSG_REQUIRE(feat && out_adv && active && leaving, "psg_rla_tbim_retire_clouds: null argument");
+    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_tbim_retire_clouds: G=%d n=%d out of range", G, n);
+    hipLaunchKernelGGL(tbim_retire_kernel, dim3(G), dim3(1024), 0, (hipStream_t)stream, feat, (size_t)n, final, out_adv, active, leaving);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+// One step sequence of a TBIM window, shared by the eager and the captured path; rows: the window's step-constant device rows
+// {iteration index, -, -, -} or null.  Everything in it is a launch on `stream`: a single chain.
+static int rla_tbim_window_steps(const psg_rla_tbim_window_args *a, const float *rows, psg_stream stream)
+{
+    const int G = a->G, N = a->N;
+    int rc = PSG_OK;
+    for (int i = 0; i < a->n_steps && rc == PSG_OK; ++i) {
+        const int final = (a->final && i == a->n_steps - 1) ? 1 : 0;
+        if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
+        psg::nu_set_step_consts(rows ? rows + 4 * i : nullptr);
+        rc = psg_rla_tbim_latch_clouds(a->logits, a->labels, a->hit_ys, a->mask, a->n_mask, G, N, a->num, a->den, a->it0 + i, final,
+                                       a->hist + (size_t)i * 3 * G, a->pred, a->out_pred, a->out_stats, a->active, a->leaving, a->exit_step,
+                                       a->scratch, stream);
+        psg::nu_set_step_consts(nullptr);
+        if (rc == PSG_OK && (rc = psg_rla_colper_grad_masked(a->logits, a->loss_ys, a->mask, a->sign, G * N, a->dlogits, nullptr, stream)) == PSG_OK &&
+            (rc = psg_rla_backward(a->model, a->ws, a->dlogits, a->dfeat, stream)) == PSG_OK &&
+            (rc = psg_rla_bim_step_clouds(a->feat, a->dfeat, a->ori, a->active, G, N, a->eps, a->alpha, a->l2_metric, a->norms, a->delta,
+                                          stream)) == PSG_OK)
+            rc = psg_rla_tbim_retire_clouds(a->feat, G, N, final, a->out_adv, a->active, a->leaving, stream);
+    }
+    psg::nu_set_step_consts(nullptr);
+    return rc;
+}
+
+extern "C" int psg_rla_tbim_window(const psg_rla_tbim_window_args *a, psg_nu_graph *graph, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws && a->ori && a->labels && a->hit_ys && a->loss_ys && a->feat && a->logits && a->dlogits && a->dfeat &&
+                    a->pred && a->scratch && a->hist && a->out_adv && a->out_pred && a->out_stats && a->active && a->leaving && a->exit_step,
+                "psg_rla_tbim_window: null argument");
+    PSG_REQUIRE(a->mask && a->n_mask, "psg_rla_tbim_window: mask and n_mask are required");
+    PSG_REQUIRE(!a->l2_metric || (a->norms && a->delta), "psg_rla_tbim_window: the l_2 metric needs norms and delta");
+    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->Nc, "psg_rla_tbim_window: the workspace is for %d clouds of %d points, the window for %d of %d",
+                a->ws->B, a->ws->Nc, a->G, a->N);
+    PSG_REQUIRE(a->n_steps >= 1 && a->n_steps <= PSG_NU_GRAPH_MAX_STEPS, "psg_rla_tbim_window: n_steps=%d outside 1..%d", a->n_steps,
+                PSG_NU_GRAPH_MAX_STEPS);
+    PSG_REQUIRE(a->it0 >= 0, "psg_rla_tbim_window: it0=%d (the first iteration is 0)", a->it0);
+    PSG_REQUIRE(a->num >= 0 && a->den > 0, "psg_rla_tbim_window: threshold %d / %d out of range", a->num, a->den);
+    if (!a->ws->cloud_set) { set_error("psg_rla_tbim_window: psg_rla_set_cloud has not been called"); return PSG_ERR_STATE; }
+    ProfBind bind(a->ws);
+    // what a captured window is valid for: the argument block (padding bytes as the caller holds them) without what the device
+    // rows carry
+    psg_rla_tbim_window_args key;
+    memcpy(&key, a, sizeof(key));
+    key.it0 = 0;
+    // no graph while the profiler is on (per-launch events) or before the first forward of (cloud, model), which computes the
+    // xyz branch: a capture would either bake it in or, replayed after a new cloud, skip it
+    const bool plain = a->ws->prof.on || a->ws->xyz_branch_model != a->model->gen;
+    return nu_graph_window(plain ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, a->n_steps, a->it0, a->it0, 0.0f, 0.9f, 0.999f,
+                           (hipStream_t)stream, [&](const float *rows) { return rla_tbim_window_steps(a, rows, stream); });
+}

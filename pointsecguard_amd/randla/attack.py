@@ -13,6 +13,8 @@ reference's, the adversarial colours stay available as `.last_adv`.  Network par
 `NUattack.batch_attack_clouds` / `tar_NUattack.batch_attack_clouds` are the lockstep form of the two NU attacks: G clouds
 advance together on one cloud-batch workspace, CHUNK optimiser steps per library call (`psg_rla_nu_window`), one read-back
 per window; the accuracy exits are taken per cloud on the device, in integers.  `batch_attack` stays the one-cloud path.
+`TBIM.batch_attack_clouds` (and `tar_NBattack`'s) is the same for the targeted BIM: CHUNK iterations per library call
+(`psg_rla_tbim_window`), the `sr > 0.9` exit per cloud on the device, the exiting iteration's update still applied.
 """
 import ctypes
 
@@ -178,6 +180,100 @@ class TBIM(_StepAttack):
                              "original_other_mIoU={}".format(*out))
         return out
 
+    # the lockstep form: the exit `hits / points > 0.90` as an integer ratio, steps per window, the tests' and tools' hook
+    EXIT_RATIO = (9, 10)
+    chunk = 10              # iterations per window (tests shorten it; at most CHUNK)
+    window_hook = None      # called after every window's read-back with (first iteration, iterations, final, state, history rows)
+
+    def batch_attack_clouds(self, features, labels, target=None, ori=2):
+        """G clouds in lockstep: features [G, N, 6], labels [G, N] -> a list of G tuples (target_points, sr, other_acc,
+        original_other_accuracy, new_dists, other_mIoU, original_other_mIoU), the fields `batch_attack` returns.  Every cloud
+        has its own exit; like there, the update of the exiting iteration is still applied: `last_adv` [G, N, 3] holds the
+        colours after it, the tuple the prediction before it.  `last_steps` [G]: gradient steps taken per cloud.  Raises
+        ValueError before any device work on unset config, bad shapes, iteration < 1 or a cloud without a point of `ori`."""
+        if self.eps is None or self.alpha is None or self.iteration is None:
+            raise ValueError("call config(magnitude=..., alpha=..., iteration=...) first")
+        if self.iteration < 1:
+            raise ValueError("iteration must be positive")
+        if target is None:
+            raise ValueError("target: the class the points of class `ori` are pushed to")
+        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
+        if f.dim() != 3 or f.shape[2] != 6 or f.shape[0] < 1:
+            raise ValueError("features must be [G, N, 6] (xyz, rgb) of G >= 1 clouds, got %s" % (tuple(f.shape),))
+        G, n = int(f.shape[0]), int(f.shape[1])
+        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int32)
+        if lab.shape != (G, n):
+            raise ValueError("labels must be [G, N] = %s, got %s" % ((G, n), lab.shape))
+        mask_h = lab == ori
+        target_points = mask_h.sum(1).astype(np.float64)
+        if (target_points == 0).any():
+            raise ValueError("no point of the origin class %d in cloud(s) %s (tester_S3DIS.py:311-314 skips such clouds)" %
+                             (ori, ", ".join(str(g) for g in np.flatnonzero(target_points == 0))))
+        ys_target = np.where(mask_h, target, lab).astype(np.int32)
+        targeted = self.goal in ("t", "tm")
+        f = f.float().cuda().contiguous()
+        key = (n, G)
+        if key not in self._clouds:
+            self._clouds[key] = _TbimCloudsState(n, G)
+        S = self._clouds[key]
+        ws = S.ws
+        S.feat.copy_(f.reshape(G * n, 6))
+        S.xs.copy_(S.feat[:, 3:6])                       # the clean colours
+        ws.set_cloud(S.feat[:, 0:3].contiguous())
+        pred0 = ws.forward(self.model, S.feat).argmax(1).cpu().numpy().reshape(G, n)
+        S.labels.copy_(torch.from_numpy(lab.reshape(-1)))
+        S.hit_ys.copy_(torch.from_numpy(ys_target.reshape(-1)))
+        S.ys.copy_(torch.from_numpy((ys_target if targeted else lab).reshape(-1)))       # the labels of the hinge
+        S.mask.copy_(torch.from_numpy(mask_h.astype(np.uint8).reshape(-1)))
+        S.n_mask.copy_(torch.from_numpy(mask_h.sum(1).astype(np.int32)))
+        for t in (S.norms, S.out_stats, S.out_adv, S.out_pred, S.leaving):
+            t.zero_()
+        S.active.fill_(1)
+        S.exit.fill_(-1)
+        win = _lib.RlaTbimWindowArgs()
+        win.model, win.ws = self.model.handle, ws.handle
+        win.G, win.N, win.l2_metric = G, n, 1 if self.distance_metric == "l_2" else 0
+        win.num, win.den = int(self.EXIT_RATIO[0]), int(self.EXIT_RATIO[1])
+        win.eps, win.alpha, win.sign = self.eps, self.alpha, -1.0 if targeted else 1.0
+        for name, t in (("ori", S.xs), ("mask", S.mask), ("n_mask", S.n_mask), ("labels", S.labels), ("hit_ys", S.hit_ys),
+                        ("loss_ys", S.ys), ("feat", S.feat), ("logits", S.logits), ("dlogits", S.dlogits), ("dfeat", S.dfeat),
+                        ("norms", S.norms), ("delta", S.dws), ("pred", S.pred), ("scratch", S.scratch), ("hist", S.hist),
+                        ("out_adv", S.out_adv), ("out_pred", S.out_pred), ("out_stats", S.out_stats), ("active", S.active),
+                        ("leaving", S.leaving), ("exit_step", S.exit)):
+            setattr(win, name, t.data_ptr())
+        chunk = max(1, min(int(self.chunk), CHUNK))
+        exited = np.full(G, -1, np.int64)
+        it0 = 0
+        while it0 <= self.iteration:                     # iterations 0 .. iteration (bim.py:470-482: one update before the loop)
+            n_run = min(chunk, self.iteration - it0 + 1)
+            final = it0 + n_run - 1 == self.iteration     # the cap: its last step snapshots the clouds still running
+            win.n_steps, win.it0, win.final = n_run, it0, 1 if final else 0
+            graph = None if n_run != CHUNK else (S.graph_tail if final else S.graph)      # cut windows run eagerly
+            _lib.call("psg_rla_tbim_window", ctypes.byref(win), graph, runtime.stream())
+            back = torch.cat([S.hist[:n_run].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
+            exited = back[n_run * G * 3:].astype(np.int64)
+            if self.window_hook is not None:
+                self.window_hook(it0, n_run, final, S, back[:n_run * G * 3].reshape(n_run, G, 3))
+            it0 += n_run
+            if (exited >= 0).all():
+                break
+        self.last_adv = S.out_adv.reshape(G, n, 3).clone()
+        self.last_steps = np.where(exited >= 0, exited, self.iteration) + 1
+        pred = S.out_pred.cpu().numpy().reshape(G, n)
+        ori_rgb = S.xs.reshape(G, n, 3)
+        outs = []
+        for g in range(G):
+            mk, tp = mask_h[g], float(target_points[g])
+            new_dists = float(torch.linalg.vector_norm(self.last_adv[g] - ori_rgb[g]))
+            out = (tp, float(np.sum(pred[g][mk] == ys_target[g][mk]) / tp), float(np.sum(pred[g][~mk] == ys_target[g][~mk]) / (n - tp)),
+                   float(np.sum(pred0[g][~mk] == lab[g][~mk]) / (n - tp)), new_dists, _mean_iou(pred[g][~mk], lab[g][~mk]),
+                   _mean_iou(pred0[g][~mk], lab[g][~mk]))
+            if self.logger is not None:
+                self.logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
+                                 "original_other_mIoU={}".format(*out))
+            outs.append(out)
+        return outs
+
 
 class NBattack(BIM):
     """NBattack.py:8-48: BIM plus a `rand_init_magnitude` setting.  The reference computes the random start point but never
@@ -244,6 +340,18 @@ class _CloudsState:
                     _lib.load().psg_nu_graph_destroy(g)
         except Exception:
             pass
+
+
+class _TbimCloudsState(_CloudsState):
+    """The same buffers for TBIM.batch_attack_clouds (xs: the clean colours, dws: the l_2 step's delta, ys: the labels of the
+    hinge; graph_tail: a full window that is also the last) plus what only TBIM needs."""
+
+    def __init__(self, n, G):
+        super().__init__(n, G)
+        dev = self.ws.device
+        self.hit_ys = torch.zeros(G * n, dtype=torch.int32, device=dev)      # the labels the hits are counted against
+        self.norms = torch.zeros(2, G, dtype=torch.float32, device=dev)
+        self.leaving = torch.zeros(G, dtype=torch.uint8, device=dev)
 
 
 class NUattack(_StepAttack):
