@@ -863,6 +863,11 @@ int psg_rla_ws_create(psg_ctx *ctx, int n_points, psg_rla_ws **out);
  * argument of the calls below becomes [batch][n_points][..].  Both metrics: the l_2 step of psg_rla_bim_attack takes its two
  * norms per cloud (one workgroup per cloud, a fixed summation order), as bim.py:84-98 normalises per sample. */
 int psg_rla_ws_create_batch(psg_ctx *ctx, int n_points, int batch, psg_rla_ws **out);
+/* A cloud-batch workspace that can also differentiate the relative-position branch (psg_rla_backward_full): level 0 runs the
+ * unfused chain, as under PSG_RLA_NO_FUSE16=1, and the buffers of the coordinate gradient follow everything else in the arena.
+ * psg_rla_forward / psg_rla_backward behave on it as on a PSG_RLA_NO_FUSE16 workspace.  Refused under PSG_RLA_ATOMICS=1 (no
+ * inverse lists).  The workspaces of the two calls above keep their layout, size and kernels. */
+int psg_rla_ws_create_full(psg_ctx *ctx, int n_points, int batch, psg_rla_ws **out);
 int psg_rla_ws_destroy(psg_rla_ws *ws);
 size_t psg_rla_ws_bytes(const psg_rla_ws *ws);
 /* Measurement only: HIP-event timing of every GEMM launch (tag 0: the 1x1 convolutions and attention scores of
@@ -893,6 +898,11 @@ const int32_t *psg_rla_index_ptr(const psg_rla_ws *ws, int what, int level);
  *     48 g_fagg2 (lives in agg2)  49 g_agg2 (lives in fagg2)  50 g_agg1 (lives in agg1)
  *   geometry (int32), valid from the cloud call on, unless the float-atomics switch is set (never built: NULL, error set):
  *     60 inv_off [n+1]  61 inv_ent [16n]  62 invu_off [n_sub+1]  63 invu_ent [n]  64 invp_off [n+1]  65 invp_ent [16 n_sub]
+ *   position-branch gradient, psg_rla_ws_create_full workspaces only (NULL, error set, on any other):
+ *     sign words of the branch's two layers (uint32), valid with fxyz1 / fxyz2:  70 m_fxyz1 [16n][ceil(h/32)]  71 m_fxyz2
+ *     valid from psg_rla_backward_full until the next forward call:
+ *     72 G2 [16n][h]  73 G1 [16n][h] (gradients of the pre-activations of LFAmlp2 / LFAmlp1)  74 g_rp [16n][10]
+ *     75 gxyz [n][3]  76 side_i [16n][4]  77 side_j [16n][4] (what edge (i, k) hands to point i / to neighbour j: x, y, z, 0)
  * The per-edge attention buffers (a1 / cat1 / a2 / cat2) change meaning with the path (T and S2 on the split path, scores
  * and the concatenation on the unfused one, unused on the fused one) and are not exposed. */
 const void *psg_rla_debug_ptr(const psg_rla_ws *ws, int what, int level, int *rows_out, int *cols_out);
@@ -901,6 +911,14 @@ int psg_rla_forward(psg_rla_model *model, psg_rla_ws *ws, const float *features,
 /* d loss / d logits -> d loss / d features [n_points][6] (through the feature path only: the relative-position branch
  * is constant for a colour attack); consumes the resident forward */
 int psg_rla_backward(psg_rla_model *model, psg_rla_ws *ws, const float *dlogits, float *dfeatures_out, psg_stream stream);
+/* The same on a psg_rla_ws_create_full workspace, plus dxyz_out [n_points][3] = d loss / d xyz of psg_rla_set_cloud through the
+ * relative-position branch (RandLANet.py:347-353 and the two LFA MLPs), with the neighbour, sub-sampling and up-sampling
+ * indices constant.  Geometric paths only: a caller whose features carry the same positions adds dfeatures[:, 0:3].  Where
+ * dist == 0 (self edges, coincident points) the distance column contributes exactly zero.  dfeatures_out holds the bytes
+ * psg_rla_backward writes on the same workspace.  No float atomics: two runs give the same bits.  PSG_ERR_ARG, before
+ * anything is enqueued, on a workspace that is not full and on null arguments. */
+int psg_rla_backward_full(psg_rla_model *model, psg_rla_ws *ws, const float *dlogits, float *dfeatures_out, float *dxyz_out,
+                          psg_stream stream);
 /* the attack's loss (bim.py:110-116) and its gradient w.r.t. the logits; loss_out (nullable) device scalar */
 int psg_rla_colper_grad(const float *logits, const int32_t *labels, int n, float *dlogits, float *loss_out, psg_stream stream);
 /* The same with the targeted attacks' mask and sign (TBIM bim.py:393-397 / :350-351, tar_NUattack.py:105-110): ys = the
@@ -913,6 +931,12 @@ int psg_rla_colper_grad_masked(const float *logits, const int32_t *ys, const uin
  * loop reads an accuracy back every iteration (TBIM.batch_attack, bim.py:484-505). */
 int psg_rla_bim_step(float *feat, const float *dfeat, const float *ori, int n, float eps, float alpha, int l2_metric, float *norms,
                      float *delta, psg_stream stream);
+/* The same update (bim.py:84-96) on the coordinate columns 0:3 of feat [n][6] of ONE cloud, with the gradient
+ * g = dfeat[:, 0:3] + dxyz (one fp32 add; dxyz [n][3] from psg_rla_backward_full) and ori_xyz [n][3] the clean positions.  No
+ * clip to a box: coordinates have none.  l_2: norms = 2 floats and delta = [n][3] floats of scratch, the norms in
+ * psg_rla_bim_step's order (one workgroup, double accumulation, a fixed tree). */
+int psg_rla_bim_step_field(float *feat, const float *dfeat, const float *dxyz, const float *ori_xyz, int n, float eps, float alpha,
+                           int l2_metric, float *norms, float *delta, psg_stream stream);
 /* NUattack / tar_NUattack (ares/ares/attack/NUattack.py:12-74, tar_NUattack.py:12-84): adversarial colours of the tanh-space
  * variable d_ws into feat [n][6] columns 3..5 (mask: only those points move) and dist2[0] = |adv - x|_2^2; then one TF1-Adam
  * step (t = 1, 2, ..) on d_ws of loss = |adv - x|_2 + c * score from dfeat = d score / d features. */

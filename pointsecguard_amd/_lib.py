@@ -139,6 +139,7 @@ SIGNATURES = {
     "psg_rla_model_destroy": (ci, [vp]),
     "psg_rla_ws_create": (ci, [vp, ci, ctypes.POINTER(vp)]),
     "psg_rla_ws_create_batch": (ci, [vp, ci, ci, ctypes.POINTER(vp)]),
+    "psg_rla_ws_create_full": (ci, [vp, ci, ci, ctypes.POINTER(vp)]),
     "psg_rla_ws_destroy": (ci, [vp]),
     "psg_rla_ws_bytes": (ctypes.c_size_t, [vp]),
     "psg_rla_prof_enable": (ci, [vp, ci]),
@@ -149,9 +150,11 @@ SIGNATURES = {
     "psg_rla_debug_ptr": (vp, [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "psg_rla_forward": (ci, [vp, vp, vp, vp, vp]),
     "psg_rla_backward": (ci, [vp, vp, vp, vp, vp]),
+    "psg_rla_backward_full": (ci, [vp, vp, vp, vp, vp, vp]),
     "psg_rla_colper_grad": (ci, [vp, vp, ci, vp, vp, vp]),
     "psg_rla_colper_grad_masked": (ci, [vp, vp, vp, cf, ci, vp, vp, vp]),
     "psg_rla_bim_step": (ci, [vp, vp, vp, ci, cf, cf, ci, vp, vp, vp]),
+    "psg_rla_bim_step_field": (ci, [vp, vp, vp, vp, ci, cf, cf, ci, vp, vp, vp]),
     "psg_rla_nu_color": (ci, [vp, vp, vp, ci, vp, vp, vp]),
     "psg_rla_nu_adam_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, ci, vp]),
     "psg_rla_bim_attack": (ci, [vp, vp, vp, vp, cf, cf, ci, ci, vp, vp]),

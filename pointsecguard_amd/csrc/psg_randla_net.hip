@@ -20,6 +20,7 @@
 
 #include "psg_common.h"
 #include "psg_gemm.cuh"
+#include "psg_randla_coord.h"
 
 using namespace psg;
 
@@ -679,6 +680,43 @@ __global__ __launch_bounds__(256) void att_pool_split_bwd_kernel(const float *__
     }
 }
 
+// psg_rla_backward_full: the direct term of the POSITION half, gx[e][c'] = a[e][h + c'] * dagg[i][h + c'], with the attention
+// weights recomputed as above.  A kernel of its own, one thread per (point, position channel): att_pool_split_bwd_kernel stays
+// the code the feature path has always run, so dfeatures keeps its bytes whichever backward is called.
+__global__ __launch_bounds__(256) void att_pool_split_dir_xyz_kernel(const int32_t *__restrict__ neigh, const float *__restrict__ T,
+                                          const float *__restrict__ S2, const float *__restrict__ dagg, int h, size_t total,
+                                          float *__restrict__ gx)
+{
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int d = 2 * h;
+    const size_t n = t / h;
+    const int cx = (int)(t - n * h), c = h + cx;
+    const float g0 = dagg[n * d + c];
+    float av[RK];
+    int nb[RK];
+#pragma unroll
+    for (int k = 0; k < RK; k += 4) {
+        const int4 q = *(const int4 *)(neigh + n * RK + k);
+        nb[k] = q.x; nb[k + 1] = q.y; nb[k + 2] = q.z; nb[k + 3] = q.w;
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < RK; ++k) {
+        av[k] = T[(size_t)nb[k] * d + c] + S2[(n * RK + k) * d + c];
+        m = fmaxf(m, av[k]);
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < RK; ++k) {
+        av[k] = expf(av[k] - m);
+        sum += av[k];
+    }
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int k = 0; k < RK; ++k) gx[(n * RK + k) * h + cx] = (av[k] * inv) * g0;
+}
+
 // ---- inverse lists (transposes of neigh / up) and the gathers that replace the scatter kernels below
 __global__ void iota_kernel(int32_t *__restrict__ v, size_t n)
 {
@@ -1084,6 +1122,12 @@ struct LevelBuf {
     uint8_t *arg;
     float *d_enc, *d_samp;                     // gradients w.r.t. enc [n][2d] and samp [n_sub][2d]
     float *d_fpc, *d_fagg1;                    // [n][h]
+    // full workspaces only (psg_rla_ws_create_full), the position-branch gradient: sign words of fxyz1 / fxyz2 [16n][ceil(h/32)],
+    // G2 / G1 [16n][h] (gradients of the pre-activations of LFAmlp2 / LFAmlp1), g_rp [16n][10], what every edge hands to its
+    // point i and to its neighbour j ([16n] float4 each), gxyz [n][3]
+    uint32_t *m_fxyz1 = nullptr, *m_fxyz2 = nullptr;
+    float *G1 = nullptr, *G2 = nullptr, *g_rp = nullptr, *gxyz = nullptr;
+    float4 *side_i = nullptr, *side_j = nullptr;
 };
 
 struct psg_rla_ws {
@@ -1110,6 +1154,7 @@ struct psg_rla_ws {
     bool fuse16 = true;           // PSG_RLA_NO_FUSE16=1: the unfused chain at level 0 too (A/B runs, tests)
     bool split = true;            // PSG_RLA_NO_SPLIT=1: levels 1-4 through the gather + per-edge score GEMM chain (A/B runs)
     bool use_inv = true;          // PSG_RLA_ATOMICS=1: the scatter kernels with float atomics instead of the inverse-list gathers
+    bool full = false;            // psg_rla_ws_create_full: the buffers of the coordinate gradient, level 0 on the unfused chain
     size_t scratch_bytes = 0;     // of scratch_a and of scratch_b
     EvLog prof;                   // psg_rla_prof_enable
     uint64_t xyz_branch_model = 0;   // generation number (not the address: a freed model's address can come back) of the model whose xyz-branch features (fxyz1 / fxyz2) are resident
@@ -1207,7 +1252,22 @@ extern "C" int psg_rla_ws_create(psg_ctx *ctx, int n_points, psg_rla_ws **out) {
 // A workspace for `batch` clouds of n_points each, attacked together: rows of every buffer are cloud-major, every index
 // (neighbours, pooling, interpolation) stays inside its cloud, so the clouds are as independent as in `batch` workspaces;
 // one launch of every kernel serves them all (the per-cloud network is ~300 launches of 5-35 us per iteration).
+static int rla_ws_create(psg_ctx *ctx, int n_points, int batch, bool full, psg_rla_ws **out);
 extern "C" int psg_rla_ws_create_batch(psg_ctx *ctx, int n_points, int batch, psg_rla_ws **out)
+{
+    return rla_ws_create(ctx, n_points, batch, false, out);
+}
+
+// The same with the buffers of psg_rla_backward_full behind everything else in the arena; level 0 runs the unfused chain, whose
+// transpose leaves the complete per-edge gradient of the concatenation behind (the fused kernel keeps nothing per edge).
+extern "C" int psg_rla_ws_create_full(psg_ctx *ctx, int n_points, int batch, psg_rla_ws **out)
+{
+    { const char *at = psg::env_str("PSG_RLA_ATOMICS");
+      PSG_REQUIRE(!(at && atoi(at)), "psg_rla_ws_create_full: PSG_RLA_ATOMICS=1 builds no inverse lists, which the coordinate gradient gathers through"); }
+    return rla_ws_create(ctx, n_points, batch, true, out);
+}
+
+static int rla_ws_create(psg_ctx *ctx, int n_points, int batch, bool full, psg_rla_ws **out)
 {
     PSG_REQUIRE(ctx && out, "psg_rla_ws_create: null argument");
     PSG_REQUIRE(n_points >= 8192 && n_points <= 65536 && n_points % 512 == 0,
@@ -1220,6 +1280,7 @@ extern "C" int psg_rla_ws_create_batch(psg_ctx *ctx, int n_points, int batch, ps
     { const char *nf = psg::env_str("PSG_RLA_NO_FUSE16"); ws->fuse16 = !(nf && atoi(nf)); }
     { const char *at = psg::env_str("PSG_RLA_ATOMICS"); ws->use_inv = !(at && atoi(at)); }
     { const char *ns = psg::env_str("PSG_RLA_NO_SPLIT"); ws->split = !(ns && atoi(ns)) && ws->use_inv; }
+    if (full) { ws->full = true; ws->fuse16 = false; }
     auto layout = [&](Bump &bp) {
         const size_t N = (size_t)ws->N;
         ws->xyz_all = bp.take<float>(N * 3);
@@ -1289,6 +1350,15 @@ extern "C" int psg_rla_ws_create_batch(psg_ctx *ctx, int n_points, int batch, ps
         ws->d_fc1o = bp.take<float>(N * 64); ws->d_fc2o = bp.take<float>(N * 32);
         ws->feat = bp.take<float>(N * 6); ws->dfeat = bp.take<float>(N * 6); ws->ori = bp.take<float>(N * 3);
         ws->delta = bp.take<float>(N * 3); ws->norms = bp.take<float>((size_t)(2 * batch > 4 ? 2 * batch : 4)); ws->labels = bp.take<int32_t>(N);
+        if (ws->full)
+            for (int i = 0; i < RL; ++i) {
+                LevelBuf &L = ws->lv[i];
+                const size_t E = (size_t)L.n * RK, h = L.h;
+                L.side_i = bp.take<float4>(E); L.side_j = bp.take<float4>(E);
+                L.m_fxyz1 = bp.take<uint32_t>(E * ceil_div((int)h, 32)); L.m_fxyz2 = bp.take<uint32_t>(E * ceil_div((int)h, 32));
+                L.G1 = bp.take<float>(E * h); L.G2 = bp.take<float>(E * h); L.g_rp = bp.take<float>(E * 10);
+                L.gxyz = bp.take<float>((size_t)L.n * 3);
+            }
     };
     if (int rc = carve_arena(&ws->arena, &ws->bytes, "psg_rla_ws_create", layout)) {
         delete ws;
@@ -1433,6 +1503,10 @@ extern "C" const void *psg_rla_debug_ptr(const psg_rla_ws *ws, int what, int lev
         set_error("psg_rla_debug_ptr: level=%d out of range for what=%d", level, what);
         return nullptr;
     }
+    if (what >= 70 && what <= 77 && !ws->full) {
+        set_error("psg_rla_debug_ptr: the coordinate-gradient buffers (what=%d) exist in a psg_rla_ws_create_full workspace only", what);
+        return nullptr;
+    }
     if (what >= 60 && what <= 65 && !ws->use_inv) {
         set_error("psg_rla_debug_ptr: the inverse lists (what=%d) are not built under PSG_RLA_ATOMICS", what);
         return nullptr;
@@ -1492,6 +1566,14 @@ extern "C" const void *psg_rla_debug_ptr(const psg_rla_ws *ws, int what, int lev
     case 63: put(L.invu_ent, n, 1); break;
     case 64: put(L.invp_off, n + 1, 1); break;
     case 65: put(L.invp_ent, L.n_sub * RK, 1); break;
+    case 70: put(L.m_fxyz1, E, ceil_div(h, 32)); break;
+    case 71: put(L.m_fxyz2, E, ceil_div(h, 32)); break;
+    case 72: put(L.G2, E, h); break;
+    case 73: put(L.G1, E, h); break;
+    case 74: put(L.g_rp, E, 10); break;
+    case 75: put(L.gxyz, n, 3); break;
+    case 76: put(L.side_i, E, 4); break;
+    case 77: put(L.side_j, E, 4); break;
     default: set_error("psg_rla_debug_ptr: unknown buffer code what=%d", what); return nullptr;
     }
     if (rows_out) *rows_out = r;
@@ -1517,8 +1599,9 @@ extern "C" int psg_rla_forward(psg_rla_model *m, psg_rla_ws *ws, const float *fe
         const size_t ne = (size_t)n * RK;
         if ((rc = conv_fwd(E.mlp1, fin, L.d_in, L.fpc, h, n, true, L.m_fpc, st))) return rc;
         if (!xyz_ready) {   // the xyz branch depends on the cloud and the weights only: once per (cloud, model)
-            if ((rc = conv_fwd(E.lfa_mlp1, L.relpos, 10, L.fxyz1, h, (int)ne, true, nullptr, st))) return rc;
-            if ((rc = conv_fwd(E.lfa_mlp2, L.fxyz1, h, L.fxyz2, h, (int)ne, true, nullptr, st))) return rc;
+            // (sign words: full workspaces only, null otherwise)
+            if ((rc = conv_fwd(E.lfa_mlp1, L.relpos, 10, L.fxyz1, h, (int)ne, true, L.m_fxyz1, st))) return rc;
+            if ((rc = conv_fwd(E.lfa_mlp2, L.fxyz1, h, L.fxyz2, h, (int)ne, true, L.m_fxyz2, st))) return rc;
             if (ws->split && d > 16) {   // S2 = fxyz . W2^T (the position-encoding half of the score layer), kept in the cat buffers
                 GemmArgs g1 = gemm_args(L.fxyz1, h, E.att1_fc.w + h, d, L.cat1, d, (int)ne, h, d);
                 if ((rc = rl_gemm<EPI_LINEAR>(g1, st))) return rc;
@@ -1618,10 +1701,30 @@ extern "C" int psg_rla_forward(psg_rla_model *m, psg_rla_ws *ws, const float *fe
     return PSG_OK;
 }
 
+static int rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *dlogits, float *dfeatures_out, float *dxyz_out, psg_stream stream);
+
 extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *dlogits, float *dfeatures_out, psg_stream stream)
 {
-    ProfBind bind(ws);
     PSG_REQUIRE(m && ws && dlogits && dfeatures_out, "psg_rla_backward: null argument");
+    return rla_backward(m, ws, dlogits, dfeatures_out, nullptr, stream);
+}
+
+// psg_rla_backward plus the gradient through the relative-position branch, indices constant: per level,
+// deepest first, the pooling transposes w.r.t. the position half (G2, G1 through the two masked layers), g_rp = G1 . W_mlp1,
+// the transpose of relpos per edge and one fixed-order sum per point that also takes the next level's complete gradient
+// (xyz[l + 1] is a prefix of xyz[l]).  dfeatures_out: psg_rla_backward's bytes (the feature path runs the same launches).
+extern "C" int psg_rla_backward_full(psg_rla_model *m, psg_rla_ws *ws, const float *dlogits, float *dfeatures_out, float *dxyz_out,
+                                     psg_stream stream)
+{
+    PSG_REQUIRE(m && ws && dlogits && dfeatures_out && dxyz_out, "psg_rla_backward_full: null argument");
+    PSG_REQUIRE(ws->full, "psg_rla_backward_full: the workspace was not made by psg_rla_ws_create_full");
+    return rla_backward(m, ws, dlogits, dfeatures_out, dxyz_out, stream);
+}
+
+static int rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *dlogits, float *dfeatures_out, float *dxyz_out, psg_stream stream)
+{
+    ProfBind bind(ws);
+    const bool xg = dxyz_out != nullptr;      // the position branch too
     if (!ws->have_fwd) { set_error("psg_rla_backward: no forward is resident in the workspace"); return PSG_ERR_STATE; }
     hipStream_t st = (hipStream_t)stream;
     const int N = ws->N;
@@ -1686,8 +1789,10 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
         const bool split = d > 16 && ws->split;
         // split levels: ds [E][d] and the direct term [E][h] per edge, summed over every point's in-edges (dT [n][d], and
         // straight into the feature gradient), then the score layer's feature half transposed on POINTS: df += dT . W1
+        // gx_ (position branch): the direct term a * dagg of the position half (a kernel of its own), then + ds . W[:, h:] while ds
+        // is still in scratch
         auto split_bwd = [&](const float *fin_, const float *fxyz_, const float *T_, const float *S2_, const float *dagg_, const RLayer &fc,
-                             float *df_, const uint32_t *mask_) -> int {
+                             float *df_, const uint32_t *mask_, float *gx_, const uint32_t *gx_mask_) -> int {
             float *ds = ws->scratch_b, *ddir = ws->scratch_a, *dT = L.m2;
             {
                 const double ne_ = 16.0 * n;
@@ -1696,6 +1801,16 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
                                    h, (size_t)n * d, ds, ddir);
             }
             PSG_LAUNCH_CHECK();
+            if (gx_) {      // the direct term, then rows h .. 2h of W^T: gx[.][c'] += sum_c ds[.][c] W[c][h + c'], then (pooling 2) the sign bits of fxyz2
+                hipLaunchKernelGGL(att_pool_split_dir_xyz_kernel, dim3(blocks_for((size_t)n * h)), dim3(256), 0, st, L.neigh, T_, S2_, dagg_, h,
+                                   (size_t)n * h, gx_);
+                PSG_LAUNCH_CHECK();
+                GemmArgs gg = gemm_args(ds, d, fc.wt + (size_t)h * d, d, gx_, h, (int)ne, d, h);
+                gg.accumulate = 1;
+                gg.post_mask = gx_mask_;
+                gg.post_slope = kSlope;
+                if (int r = rl_gemm<EPI_LINEAR>(gg, st)) return r;
+            }
             hipLaunchKernelGGL(gather_inv_kernel<true>, dim3(blocks_for((size_t)n * d)), dim3(256), 0, st, ds, d, d, L.inv_off, L.inv_ent,
                                (size_t)n * d, dT);
             PSG_LAUNCH_CHECK();
@@ -1708,8 +1823,14 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
             g.post_slope = kSlope;
             return rl_gemm<EPI_LINEAR>(g, st);
         };
+        // unfused chain: columns h .. 2h of the complete dcat [E][2h] in scratch_a are the gradient of the position half
+        auto take_gx = [&](float *gx_) -> int {
+            hipLaunchKernelGGL(copy_cols_kernel, dim3(blocks_for(ne * h)), dim3(256), 0, st, ws->scratch_a, d, h, h, ne, gx_, h, 0);
+            PSG_LAUNCH_CHECK();
+            return PSG_OK;
+        };
         if (split) {
-            if ((rc = split_bwd(L.fagg1, L.fxyz2, L.a2, L.cat2, g_agg2, E.att2_fc, L.d_fagg1, L.m_fagg1))) return rc;
+            if ((rc = split_bwd(L.fagg1, L.fxyz2, L.a2, L.cat2, g_agg2, E.att2_fc, L.d_fagg1, L.m_fagg1, xg ? L.G2 : nullptr, L.m_fxyz2))) return rc;
         } else if (fused16) {
             {
                 EvScope prof(tl_prof, 7, 0.0, st, 4.0 * ((double)n * (2.0 * h + d) + 16.0 * n * (1.0 + h + 8.0)));
@@ -1727,6 +1848,7 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
                                ws->scratch_a, ws->scratch_b);
             PSG_LAUNCH_CHECK();
             if ((rc = conv_bwd(E.att2_fc, ws->scratch_b, d, ws->scratch_a, d, (int)ne, 1, st))) return rc;
+            if (xg && ((rc = take_gx(L.G2)) || (rc = lrelu_bwd(L.G2, h, L.m_fxyz2, (int)ne, h, st)))) return rc;
             if (ws->use_inv)
                 hipLaunchKernelGGL(gather_inv_kernel<false>, dim3(blocks_for((size_t)n * h)), dim3(256), 0, st, ws->scratch_a, 2 * h, h, L.inv_off,
                                    L.inv_ent, (size_t)n * h, L.d_fagg1, L.m_fagg1);
@@ -1738,7 +1860,7 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
         float *g_agg1 = L.agg1;
         if ((rc = conv_bwd(E.att1_mlp, L.d_fagg1, h, g_agg1, d, n, 0, st))) return rc;
         if (split) {
-            if ((rc = split_bwd(L.fpc, L.fxyz1, L.a1, L.cat1, g_agg1, E.att1_fc, L.d_fpc, L.m_fpc))) return rc;
+            if ((rc = split_bwd(L.fpc, L.fxyz1, L.a1, L.cat1, g_agg1, E.att1_fc, L.d_fpc, L.m_fpc, xg ? L.G1 : nullptr, nullptr))) return rc;
         } else if (fused16) {
             {
                 EvScope prof(tl_prof, 7, 0.0, st, 4.0 * ((double)n * (2.0 * h + d) + 16.0 * n * (1.0 + h + 8.0)));
@@ -1756,6 +1878,7 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
                                ws->scratch_a, ws->scratch_b);
             PSG_LAUNCH_CHECK();
             if ((rc = conv_bwd(E.att1_fc, ws->scratch_b, d, ws->scratch_a, d, (int)ne, 1, st))) return rc;
+            if (xg && (rc = take_gx(L.G1))) return rc;
             if (ws->use_inv)
                 hipLaunchKernelGGL(gather_inv_kernel<false>, dim3(blocks_for((size_t)n * h)), dim3(256), 0, st, ws->scratch_a, 2 * h, h, L.inv_off,
                                    L.inv_ent, (size_t)n * h, L.d_fpc, L.m_fpc);
@@ -1766,7 +1889,16 @@ extern "C" int psg_rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *d
         if (!fuse && (rc = lrelu_bwd(L.d_fpc, h, L.m_fpc, n, h, st))) return rc;
         // (level 0: this GEMM completes d_f0, the gradient of fc0's leaky-ReLU output)
         if ((rc = conv_bwd(E.mlp1, L.d_fpc, h, din, L.d_in, n, 1, st, i == 0 ? ws->m_f0 : (const uint32_t *)nullptr))) return rc;
+        if (xg) {
+            // G1 = mask(fxyz1) . (g_fxyz1 + G2 . W_mlp2), g_rp = G1 . W_mlp1, then the geometry (psg_randla_coord.hip)
+            if ((rc = conv_bwd(E.lfa_mlp2, L.G2, h, L.G1, h, (int)ne, 1, st, L.m_fxyz1))) return rc;
+            if ((rc = conv_bwd(E.lfa_mlp1, L.G1, h, L.g_rp, 10, (int)ne, 0, st))) return rc;
+            if ((rc = rla_relpos_bwd(L.relpos, L.g_rp, ne, L.side_i, L.side_j, st))) return rc;
+            if ((rc = rla_point_sum(L.side_i, L.side_j, L.inv_off, L.inv_ent, i + 1 < RL ? ws->lv[i + 1].gxyz : (const float *)nullptr, L.nc,
+                                    L.nc_sub, (size_t)n, L.gxyz, st))) return rc;
+        }
     }
+    if (xg) PSG_CHECK_HIP(hipMemcpyAsync(dxyz_out, ws->lv[0].gxyz, (size_t)N * 3 * 4, hipMemcpyDeviceToDevice, st));
     if ((rc = conv_bwd(m->fc0, ws->d_f0, 8, dfeatures_out, 6, N, 0, st))) return rc;
     ws->have_fwd = false;   // agg / fagg buffers were reused as gradient scratch
     return PSG_OK;

@@ -15,6 +15,12 @@ advance together on one cloud-batch workspace, CHUNK optimiser steps per library
 per window; the accuracy exits are taken per cloud on the device, in integers.  `batch_attack` stays the one-cloud path.
 `TBIM.batch_attack_clouds` (and `tar_NBattack`'s) is the same for the targeted BIM: CHUNK iterations per library call
 (`psg_rla_tbim_window`), the `sr > 0.9` exit per cloud on the device, the exiting iteration's update still applied.
+
+`field="coord" | "both"` (BIM, NBattack, TBIM, tar_NBattack; `batch_attack`, one cloud): the same attacks on the point positions
+(DESIGN.md section 5q).  Every iteration rebuilds the index pyramid on the moved positions (`psg_rla_set_cloud`), runs the
+forward on [positions | rgb], the hinge gradient, `psg_rla_backward_full` (feature path + relative-position branch) and the
+field step `psg_rla_bim_step_field` - under "both" followed by the unchanged colour step, each field normalised and clipped
+on its own with its own (magnitude, alpha); coordinates have no box.  `field="color"` is the code above, byte for byte.
 """
 import ctypes
 
@@ -22,12 +28,72 @@ import numpy as np
 import torch
 
 from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd.attacks.torchattacks.attacks._common import check_field
 from pointsecguard_amd.randla import network
+
+_FIELD_ONLY = ("field=%r: the coordinate field runs in BIM / NBattack / TBIM / tar_NBattack.batch_attack with batch_size == 1 "
+               "(one cloud per call); %s moves colours only")
+
+
+class _FieldState:
+    """Device buffers of the coordinate-field loop of one cloud and its full workspace (network.RandLAWorkspace(full=True))."""
+
+    def __init__(self, n):
+        self.ws = network.RandLAWorkspace(n, full=True)
+        dev = self.ws.device
+        self.norms, self.norms_xyz = (torch.zeros(2, dtype=torch.float32, device=dev) for _ in range(2))
+        self.delta = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        self.dlogits = torch.empty(n, network.NUM_CLASSES, dtype=torch.float32, device=dev)
+        self.ori_xyz = self.ori_rgb = None
+
+    def start(self, feat):
+        self.ori_xyz, self.ori_rgb = feat[:, 0:3].contiguous(), feat[:, 3:6].contiguous()
+
+
+def _field_iteration(atk, S, feat, ys, mask, sign):
+    """One iteration on feat [N, 6] in place, stream-ordered, no read-back: pyramid of the moved positions, forward, hinge
+    gradient against ys (mask, sign: psg_rla_colper_grad_masked), full backward, field step(s).  -> the logits it stepped from."""
+    ws, n, l2 = S.ws, feat.shape[0], 1 if atk.distance_metric == "l_2" else 0
+    ws.set_cloud(feat[:, 0:3].contiguous())
+    logits = ws.forward(atk.model, feat)
+    _lib.call("psg_rla_colper_grad_masked", runtime.ptr(logits), runtime.ptr(ys), None if mask is None else runtime.ptr(mask),
+              float(sign), n, runtime.ptr(S.dlogits), None, runtime.stream())
+    dfeat, dxyz = ws.backward(atk.model, S.dlogits, full=True)
+    coord_eps = atk.eps if atk.coord_eps is None else atk.coord_eps
+    coord_alpha = atk.alpha if atk.coord_alpha is None else atk.coord_alpha
+    _lib.call("psg_rla_bim_step_field", runtime.ptr(feat), runtime.ptr(dfeat), runtime.ptr(dxyz), runtime.ptr(S.ori_xyz), n,
+              coord_eps, coord_alpha, l2, runtime.ptr(S.norms_xyz), runtime.ptr(S.delta), runtime.stream())
+    if atk.field == "both":
+        _lib.call("psg_rla_bim_step", runtime.ptr(feat), runtime.ptr(dfeat), runtime.ptr(S.ori_rgb), n, atk.eps, atk.alpha, l2,
+                  runtime.ptr(S.norms), runtime.ptr(S.delta), runtime.stream())
+    return logits
+
+
+def _field_finish(atk, S, feat):
+    """the moved positions, their l_2 distance (a 0-dim device tensor: float() reads it back), and the workspace left on them,
+    so that a forward on the adversarial features evaluates the attack"""
+    atk.last_adv_xyz = feat[:, 0:3].contiguous()
+    atk.last_dist_xyz = torch.linalg.vector_norm(atk.last_adv_xyz - S.ori_xyz)
+    S.ws.set_cloud(atk.last_adv_xyz)
+
+
+def _config_coord(atk, kwargs):
+    """coord_magnitude / coord_alpha: the coordinate field's own (eps, alpha); unset, they follow magnitude / alpha"""
+    if "coord_magnitude" in kwargs:
+        atk.coord_eps = float(np.asarray(kwargs["coord_magnitude"]).reshape(-1)[0])
+    if "coord_alpha" in kwargs:
+        atk.coord_alpha = float(np.asarray(kwargs["coord_alpha"]).reshape(-1)[0])
 
 
 class BIM:
+    step_hook = None        # tests, tools (non-colour fields): called after every iteration with (iteration, features [N, 6])
+
     def __init__(self, model, batch_size=1, loss="colper", goal="ut", distance_metric="l_inf", session=None,
-                 iteration_callback=None):
+                 iteration_callback=None, field="color"):
+        self.field = check_field(field)
+        if self.field != "color" and batch_size != 1:
+            raise NotImplementedError(_FIELD_ONLY % (field, "batch_size > 1"))
+        self.coord_eps = self.coord_alpha = self.last_adv_xyz = self.last_dist_xyz = None
         if not isinstance(model, network.RandLAModel):
             raise TypeError("model must be a pointsecguard_amd.randla.network.RandLAModel")
         if goal != "ut" or distance_metric not in ("l_inf", "l_2") or iteration_callback is not None:
@@ -47,10 +113,12 @@ class BIM:
             self.alpha = float(np.asarray(kwargs["alpha"]).reshape(-1)[0])
         if "iteration" in kwargs:
             self.iteration = int(kwargs["iteration"])
+        _config_coord(self, kwargs)
 
     def batch_attack(self, features, labels):
         """features [N,6] (xyz, rgb) and labels [N] of one cloud - or [batch_size, N, 6] and [batch_size, N] - (device
-        tensors or numpy) -> adversarial rgb [N,3] / [batch_size, N, 3] after `iteration` updates (device tensor)."""
+        tensors or numpy) -> adversarial rgb [N,3] / [batch_size, N, 3] after `iteration` updates (device tensor).
+        field "coord" / "both" (one cloud): the moved positions are `last_adv_xyz` [N,3], `last_dist_xyz` their l_2 distance."""
         if self.eps is None or self.alpha is None or self.iteration is None:
             raise RuntimeError("call config(magnitude=..., alpha=..., iteration=...) first")
         f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
@@ -62,6 +130,17 @@ class BIM:
             raise ValueError("features must be [N,6] for batch_size=1, [batch_size,N,6] otherwise (batch_size=%d, got %s)" %
                              (self.batch_size, tuple(f.shape)))
         n = f.shape[-2]
+        if self.field != "color":
+            if ("field", n) not in self._ws:
+                self._ws[("field", n)] = _FieldState(n)
+            S, feat = self._ws[("field", n)], f.clone()
+            S.start(feat)
+            for it in range(self.iteration + 1):                 # bim.py:204-232, as below
+                _field_iteration(self, S, feat, y, None, 1.0)
+                if self.step_hook is not None:
+                    self.step_hook(it, feat)
+            _field_finish(self, S, feat)
+            return feat[:, 3:6].contiguous()
         if n not in self._ws:
             self._ws[n] = network.RandLAWorkspace(n, batch=self.batch_size)
         # bim.py:204-232: one update before the loop, then `iteration` more
@@ -84,7 +163,11 @@ def _mean_iou(pred, true):
 class _StepAttack:
     """Shared plumbing of the host-loop attacks: device buffers of one cloud and the step entry points."""
 
-    def __init__(self, model, batch_size=1):
+    step_hook = None        # tests, tools (non-colour fields): called after every iteration with (iteration, features [N, 6])
+
+    def __init__(self, model, batch_size=1, field="color"):
+        self.field = check_field(field)
+        self.coord_eps = self.coord_alpha = self.last_adv_xyz = self.last_dist_xyz = None
         if not isinstance(model, network.RandLAModel):
             raise TypeError("model must be a pointsecguard_amd.randla.network.RandLAModel")
         if batch_size != 1:
@@ -94,16 +177,21 @@ class _StepAttack:
         self._ws = {}
         self._clouds, self.last_steps = {}, None        # the lockstep NU attacks (batch_attack_clouds)
 
-    def _setup(self, features, labels):
+    def _setup(self, features, labels, full=False):
         f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
         y = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
         f = f.float().cuda().contiguous()
         if f.dim() != 2 or f.shape[1] != 6:
             raise ValueError("features must be [N, 6] (xyz, rgb) of one cloud, got %s" % (tuple(f.shape),))
         n = f.shape[0]
-        if n not in self._ws:
-            self._ws[n] = network.RandLAWorkspace(n)
-        ws = self._ws[n]
+        if full:                                             # the coordinate field: a full workspace and its loop's buffers
+            if ("field", n) not in self._ws:
+                self._ws[("field", n)] = _FieldState(n)
+            ws = self._ws[("field", n)].ws
+        else:
+            if n not in self._ws:
+                self._ws[n] = network.RandLAWorkspace(n)
+            ws = self._ws[n]
         ws.set_cloud(f[:, 0:3].contiguous())
         return ws, f.clone(), y.to(torch.int32).cuda().contiguous(), n
 
@@ -122,8 +210,9 @@ class TBIM(_StepAttack):
     stops when more than 90 % of the masked points are predicted as the target (bim.py:504-505).  Note the reference's
     `xs_adv_var = mask * xs_adv_var + (1 - mask) * xs_adv_var` (bim.py:318) is the identity: every colour may move."""
 
-    def __init__(self, model, batch_size=1, loss="colper", goal="t", distance_metric="l_2", session=None, iteration_callback=None):
-        super().__init__(model, batch_size)
+    def __init__(self, model, batch_size=1, loss="colper", goal="t", distance_metric="l_2", session=None, iteration_callback=None,
+                 field="color"):
+        super().__init__(model, batch_size, field)
         if goal not in ("t", "tm", "ut") or distance_metric not in ("l_inf", "l_2") or iteration_callback is not None:
             raise NotImplementedError("implemented: goal 't' / 'tm' / 'ut', l_inf / l_2")
         self.goal, self.distance_metric = goal, distance_metric
@@ -138,13 +227,18 @@ class TBIM(_StepAttack):
             self.iteration = int(kwargs["iteration"])
         if "logger" in kwargs:
             self.logger = kwargs["logger"]
+        _config_coord(self, kwargs)
 
     def batch_attack(self, features, labels, target=None, ori=2):
         """-> (target_points, sr, other_acc, original_other_accuracy, new_dists, other_mIoU, original_other_mIoU),
-        bim.py:508."""
+        bim.py:508.  field "coord" / "both": the same loop on the positions (module docstring); new_dists stays the colour
+        distance, the moved positions are `last_adv_xyz`, their l_2 distance `last_dist_xyz`."""
         if self.eps is None or self.alpha is None or self.iteration is None:
             raise RuntimeError("call config(magnitude=..., alpha=..., iteration=...) first")
-        ws, feat, y, n = self._setup(features, labels)
+        ws, feat, y, n = self._setup(features, labels, full=self.field != "color")
+        S = self._ws[("field", n)] if self.field != "color" else None
+        if S is not None:
+            S.start(feat)
         lab = y.cpu().numpy()
         mask_h = lab == ori
         target_points = float(mask_h.sum())
@@ -163,15 +257,23 @@ class TBIM(_StepAttack):
         sr = other_acc = other_miou = 0.0
         # bim.py:470-482 runs the update once before the loop; its result is the loop's starting point
         for it in range(self.iteration + 1):
-            logits, dfeat = self._grad(ws, self.model, feat, ys, mask, -1.0 if targeted else 1.0)
+            if S is not None:                                # the coordinate field: gradient and update(s) in one go
+                logits = _field_iteration(self, S, feat, ys, mask, -1.0 if targeted else 1.0)
+            else:
+                logits, dfeat = self._grad(ws, self.model, feat, ys, mask, -1.0 if targeted else 1.0)
             pred = logits.argmax(1).cpu().numpy()            # the one read-back of the iteration (the reference's session.run)
             sr = float(np.sum(pred[mask_h] == ys_target[mask_h]) / target_points)
             other_acc = float(np.sum(pred[~mask_h] == ys_target[~mask_h]) / (n - target_points))
             other_miou = _mean_iou(pred[~mask_h], lab[~mask_h])
-            _lib.call("psg_rla_bim_step", runtime.ptr(feat), runtime.ptr(dfeat), runtime.ptr(ori_rgb), n, self.eps, self.alpha,
-                      1 if self.distance_metric == "l_2" else 0, runtime.ptr(norms), runtime.ptr(delta), runtime.stream())
+            if S is None:
+                _lib.call("psg_rla_bim_step", runtime.ptr(feat), runtime.ptr(dfeat), runtime.ptr(ori_rgb), n, self.eps, self.alpha,
+                          1 if self.distance_metric == "l_2" else 0, runtime.ptr(norms), runtime.ptr(delta), runtime.stream())
+            elif self.step_hook is not None:
+                self.step_hook(it, feat)
             if it > 0 and sr > 0.90:                         # (the update before the loop is not followed by the test)
                 break
+        if S is not None:
+            _field_finish(self, S, feat)
         self.last_adv = feat[:, 3:6].contiguous()
         new_dists = float(torch.linalg.vector_norm(self.last_adv - ori_rgb))
         out = (target_points, sr, other_acc, original_other_accuracy, new_dists, other_miou, original_other_miou)
@@ -191,6 +293,8 @@ class TBIM(_StepAttack):
         has its own exit; like there, the update of the exiting iteration is still applied: `last_adv` [G, N, 3] holds the
         colours after it, the tuple the prediction before it.  `last_steps` [G]: gradient steps taken per cloud.  Raises
         ValueError before any device work on unset config, bad shapes, iteration < 1 or a cloud without a point of `ori`."""
+        if self.field != "color":
+            raise NotImplementedError(_FIELD_ONLY % (self.field, "batch_attack_clouds"))
         if self.eps is None or self.alpha is None or self.iteration is None:
             raise ValueError("call config(magnitude=..., alpha=..., iteration=...) first")
         if self.iteration < 1:
@@ -280,8 +384,9 @@ class NBattack(BIM):
     assigns it (`setup_xs` still assigns the clean colours, NBattack.py:27-29), so the attack IS BIM; the setting is
     accepted and, like there, has no effect."""
 
-    def __init__(self, model, batch_size=1, loss="colper", goal="ut", distance_metric="l_2", session=None, iteration_callback=None):
-        super().__init__(model, batch_size, loss, goal, distance_metric, session, iteration_callback)
+    def __init__(self, model, batch_size=1, loss="colper", goal="ut", distance_metric="l_2", session=None, iteration_callback=None,
+                 field="color"):
+        super().__init__(model, batch_size, loss, goal, distance_metric, session, iteration_callback, field)
         self.rand_init_eps = None
 
     def config(self, **kwargs):
@@ -293,8 +398,9 @@ class NBattack(BIM):
 class tar_NBattack(TBIM):
     """NBattack.py:53-65: TBIM plus the same unused `rand_init_magnitude` setting."""
 
-    def __init__(self, model, batch_size=1, loss="colper", goal="t", distance_metric="l_2", session=None, iteration_callback=None):
-        super().__init__(model, batch_size, loss, goal, distance_metric, session, iteration_callback)
+    def __init__(self, model, batch_size=1, loss="colper", goal="t", distance_metric="l_2", session=None, iteration_callback=None,
+                 field="color"):
+        super().__init__(model, batch_size, loss, goal, distance_metric, session, iteration_callback, field)
         self.rand_init_eps = None
 
     def config(self, **kwargs):
@@ -360,7 +466,10 @@ class NUattack(_StepAttack):
     hinge).  One search step of `iteration` Adam steps (the reference returns inside its first search step), stopping early
     when the accuracy falls below 1/13 (:213); then the random-noise baseline of the same l_2 size (:236-252)."""
 
-    def __init__(self, model, batch_size=1, goal="ut", distance_metric="l_2", cw_loss_c=99999.0, confidence=0.0, learning_rate=0.01):
+    def __init__(self, model, batch_size=1, goal="ut", distance_metric="l_2", cw_loss_c=99999.0, confidence=0.0, learning_rate=0.01,
+                 field="color"):
+        if check_field(field) != "color":
+            raise NotImplementedError(_FIELD_ONLY % (field, "NUattack"))
         super().__init__(model, batch_size)
         if goal != "ut" or distance_metric != "l_2":
             raise NotImplementedError("NUattack: goal 'ut', l_2 (tester_S3DIS.py:39)")
@@ -518,7 +627,9 @@ class tar_NUattack(NUattack):
     taken against the target labels on those points (:105-110), the loop stops when more than 95 % of them are predicted as
     the target (:235)."""
 
-    def __init__(self, model, batch_size=1, goal="t", distance_metric="l_2", confidence=0.0, learning_rate=0.01):
+    def __init__(self, model, batch_size=1, goal="t", distance_metric="l_2", confidence=0.0, learning_rate=0.01, field="color"):
+        if check_field(field) != "color":
+            raise NotImplementedError(_FIELD_ONLY % (field, "tar_NUattack"))
         _StepAttack.__init__(self, model, batch_size)
         if goal != "t" or distance_metric != "l_2":
             raise NotImplementedError("tar_NUattack: goal 't', l_2 (tester_S3DIS.py:44)")

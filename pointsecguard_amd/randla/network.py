@@ -49,15 +49,18 @@ class RandLAModel:
 
 class RandLAWorkspace:
     """Activations, index pyramid and attack state of `batch` clouds of n_points each (batch > 1: the clouds are
-    attacked together, one kernel launch serving all of them; tensors are then [batch * n_points, ..], cloud-major)."""
+    attacked together, one kernel launch serving all of them; tensors are then [batch * n_points, ..], cloud-major).
+    full=True: a workspace that can also differentiate the relative-position branch (`backward(.., full=True)`); level 0 then
+    runs the unfused chain."""
 
-    def __init__(self, n_points, device=None, batch=1):
+    def __init__(self, n_points, device=None, batch=1, full=False):
         self.ctx = runtime.context(device)
         self.points_per_cloud, self.batch = n_points, batch
         self.n_points = n_points * batch            # rows of every per-point tensor
         self.handle = ctypes.c_void_p()
-        _lib.check(_lib.load().psg_rla_ws_create_batch(self.ctx, n_points, batch, ctypes.byref(self.handle)),
-                   "psg_rla_ws_create_batch")
+        self.full = bool(full)
+        create = "psg_rla_ws_create_full" if self.full else "psg_rla_ws_create_batch"
+        _lib.check(getattr(_lib.load(), create)(self.ctx, n_points, batch, ctypes.byref(self.handle)), create)
         self.device = torch.device("cuda", torch.cuda.current_device())
 
     def __del__(self):
@@ -116,17 +119,19 @@ class RandLAWorkspace:
              "m_f0": 30, "m_fpc": 31, "m_fagg1": 32, "m_fagg2": 33, "m_enc": 34, "m_dec0": 35, "m_dec": 36, "m_fc1": 37, "m_fc2": 38,
              "d_fc2o": 40, "d_fc1o": 41, "d_dec_out": 42, "d_dec0": 43, "d_samp": 44, "d_enc": 45, "d_fagg1": 46, "d_fpc": 47,
              "g_fagg2": 48, "g_agg2": 49, "g_agg1": 50, "d_f0": 51,
-             "inv_off": 60, "inv_ent": 61, "invu_off": 62, "invu_ent": 63, "invp_off": 64, "invp_ent": 65}
+             "inv_off": 60, "inv_ent": 61, "invu_off": 62, "invu_ent": 63, "invp_off": 64, "invp_ent": 65,
+             "m_fxyz1": 70, "m_fxyz2": 71, "G2": 72, "G1": 73, "g_rp": 74, "gxyz": 75, "side_i": 76, "side_j": 77}
 
     def debug(self, what, level=0):
         """A workspace buffer by name (tests): a [rows, cols] copy taken on the current stream, float32 except `arg`
-        (uint8), the m_* sign-bit words and the inverse lists (int32).  Forward buffers are valid until backward()."""
+        (uint8), the m_* sign-bit words and the inverse lists (int32).  Forward buffers are valid until backward(); the names
+        from m_fxyz1 on exist on a full workspace only, G2 .. side_j from backward(.., full=True) until the next forward."""
         code = self.DEBUG[what]
         rows, cols = ctypes.c_int(), ctypes.c_int()
         src = _lib.load().psg_rla_debug_ptr(self.handle, code, level, ctypes.byref(rows), ctypes.byref(cols))
         if not src:
             raise _lib.PsgError("psg_rla_debug_ptr(%s, %d): %s" % (what, level, _lib.load().psg_last_error().decode()))
-        dtype = torch.uint8 if what == "arg" else (torch.int32 if code >= 30 and code < 40 or code >= 60 else torch.float32)
+        dtype = torch.uint8 if what == "arg" else (torch.int32 if code >= 30 and code < 40 or code >= 60 and code < 72 else torch.float32)
         out = torch.empty(rows.value, cols.value, dtype=dtype, device=self.device)
         runtime._hip_memcpy_d2d(out.data_ptr(), src, out.numel() * out.element_size())
         return out
@@ -138,9 +143,16 @@ class RandLAWorkspace:
         _lib.call("psg_rla_forward", model.handle, self.handle, runtime.ptr(features), runtime.ptr(logits), runtime.stream())
         return logits
 
-    def backward(self, model, dlogits):
+    def backward(self, model, dlogits, full=False):
+        """d loss / d features [N, 6]; full=True (a full workspace): -> (dfeat, dxyz), dxyz [N, 3] the derivative w.r.t. the
+        positions given to set_cloud through the relative-position branch (add dfeat[:, 0:3] when the features carry them)."""
         runtime.require_cuda(dlogits, "dlogits", torch.float32)
         dfeat = torch.empty(self.n_points, 6, dtype=torch.float32, device=dlogits.device)
+        if full:
+            dxyz = torch.empty(self.n_points, 3, dtype=torch.float32, device=dlogits.device)
+            _lib.call("psg_rla_backward_full", model.handle, self.handle, runtime.ptr(dlogits), runtime.ptr(dfeat), runtime.ptr(dxyz),
+                      runtime.stream())
+            return dfeat, dxyz
         _lib.call("psg_rla_backward", model.handle, self.handle, runtime.ptr(dlogits), runtime.ptr(dfeat), runtime.stream())
         return dfeat
 

@@ -1,0 +1,118 @@
+"""Time RandLA-Net's NBattack at 40 960 points with the tester's l_2 settings (magnitude 17, alpha 1.7, bench.py's `randla`
+workload) on the colour field - the fused device loop psg_rla_bim_attack, one cloud - beside the coordinate field, the host loop
+of DESIGN section 5q (pyramid of the moved positions, forward, hinge gradient, psg_rla_backward_full, field step per
+iteration).  One box, one run: after a warm-up of both legs, --runs (at least 3) ALTERNATED timed passes of `color`, `coord`
+(and `both` with --both), each over --clouds clouds of --iters iterations, synchronised around every timed region.  Prints
+min / median / max clouds per second per leg, `coord_over_color`, and the event-timed cost of one psg_rla_set_cloud
+(build_pyramid: five kNN levels, three radix sorts per level) as one JSON line.
+
+    python tools/rla_coord_time.py [--runs 3] [--clouds 2] [--iters 20] [--out profiles/r22_rla_coord.json]
+
+--kernel-trace DIR_OR_CSV reads the CSV of a `rocprofv3 --kernel-trace -- python tools/rla_coord_time.py ...` run made BEFORE
+(timings taken under the profiler are not figures) and adds the durations of the new kernels per grid; --trace-only prints
+those and stops.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+NEW_KERNELS = ("relpos_bwd_kernel", "point_sum_kernel", "att_pool_split_dir_xyz_kernel", "field_sq_norm_kernel", "field_l2_delta_kernel",
+               "field_l2_apply_kernel", "field_linf_kernel")
+N_PTS, MAGNITUDE, ALPHA = 40960, 17.0, 1.7
+
+
+def new_kernel_durations(path):
+    """{kernel @ grid: {calls, median_us, min_us}} of the coordinate-gradient kernels out of a rocprofv3 --kernel-trace CSV"""
+    import csv
+    import re
+    from kernel_trace_by_grid import find_trace
+    rows = {}
+    with open(find_trace(path), newline="") as fh:
+        for r in csv.DictReader(fh):
+            hit = re.search("|".join(NEW_KERNELS), r["Kernel_Name"])
+            if not hit:
+                continue
+            wg = max(int(r["Workgroup_Size_X"]), 1)
+            key = "%s @ %d" % (hit.group(0), int(r["Grid_Size_X"]) // wg)
+            rows.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1000.0)
+    return {k: dict(calls=len(d), median_us=statistics.median(d), min_us=min(d)) for k, d in sorted(rows.items())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--clouds", type=int, default=2)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--both", action="store_true")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-trace", default=None)
+    ap.add_argument("--trace-only", action="store_true")
+    a = ap.parse_args()
+    if a.trace_only:
+        print(json.dumps(dict(kernels_us=new_kernel_durations(a.kernel_trace))))
+        return
+    import torch
+    from pointsecguard_amd.randla import attack, network
+    from pointsecguard_amd.synthetic import randla_params
+    model = network.RandLAModel(randla_params(3))
+    rng = np.random.default_rng(4)
+    clouds = []
+    for _ in range(a.clouds):
+        xyz = (rng.random((N_PTS, 3), dtype=np.float32) * np.array([8, 6, 3], np.float32)).astype(np.float32)
+        f = np.concatenate([xyz, rng.random((N_PTS, 3), dtype=np.float32)], 1)
+        clouds.append((torch.from_numpy(f).cuda(), torch.from_numpy(rng.integers(0, 13, N_PTS).astype(np.int32)).cuda()))
+    legs = {}
+    for field in ("color", "coord") + (("both",) if a.both else ()):
+        atk = attack.NBattack(model, distance_metric="l_2", field=field)
+        atk.config(magnitude=MAGNITUDE, alpha=ALPHA, iteration=a.iters)
+        legs[field] = atk
+
+    def one_pass(atk):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for f, y in clouds:
+            atk.batch_attack(f, y)
+        torch.cuda.synchronize()
+        return len(clouds) / (time.perf_counter() - t0)
+
+    for atk in legs.values():                                   # warm-up: workspaces, the colour loop's graph capture
+        one_pass(atk)
+    rates = {k: [] for k in legs}
+    for _ in range(max(3, a.runs)):
+        for k, atk in legs.items():
+            rates[k].append(one_pass(atk))
+    ws = legs["coord"]._ws[("field", N_PTS)].ws
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    pyramid = []
+    for _ in range(5):
+        ev[0].record()
+        ws.set_cloud(clouds[0][0][:, 0:3].contiguous())
+        ev[1].record()
+        torch.cuda.synchronize()
+        pyramid.append(ev[0].elapsed_time(ev[1]))
+    out = dict(tool="rla_coord_time", n_points=N_PTS, metric="l_2", magnitude=MAGNITUDE, alpha=ALPHA, iterations=a.iters,
+               gradient_steps=a.iters + 1, clouds_per_pass=a.clouds, runs=max(3, a.runs),
+               clouds_per_s={k: dict(min=min(v), median=statistics.median(v), max=max(v)) for k, v in rates.items()},
+               coord_over_color=statistics.median(rates["coord"]) / statistics.median(rates["color"]),
+               ms_per_gradient_step={k: 1e3 / statistics.median(v) / (a.iters + 1) for k, v in rates.items()},
+               set_cloud_ms=dict(min=min(pyramid), median=statistics.median(pyramid), max=max(pyramid)),
+               full_workspace_bytes=ws.nbytes, device=torch.cuda.get_device_name(0))
+    if a.kernel_trace:
+        out["kernels_us"] = new_kernel_durations(a.kernel_trace)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
