@@ -115,7 +115,7 @@ struct GraphSlot {
 };
 
 // The capture-or-replay policy of the NU windows (psg_attack.hip), shared by psg_pn2_nu_window, psg_pointnet_nu_window,
-// psg_gcn_nu_window and psg_rla_nu_window:
+// psg_gcn_nu_window, psg_rla_nu_window and psg_rla_tbim_window:
 // writes the step constants {step, lr / (1 - beta1^t), sqrt(1 - beta2^t), slot3 ? slot3[i] : 0} of the window's n_steps steps into the handle's
 // device rows, then runs `steps(rows)` eagerly (first window of a `key`, or after a failed capture), captures it (second
 // window) or replays the captured graph.  `key` is the window's argument block with what the device rows carry zeroed;

@@ -1,10 +1,11 @@
-// RandLA-Net inference graph + input (colour) gradient + BIM attack loop on gfx950.
+// RandLA-Net on gfx950: the network's kernels, model, workspace, profiling, index pyramid,
+// forward pass and backward pass (input colour gradient; with a full workspace the coordinate gradient too).  The attacks
+// that drive it (BIM, NU / tar_NU, TBIM) are psg_randla_attack.hip; the handles both units share are psg_randla_net.h.
 //
 // Restates RandLA-Net/RandLANet.py:150-190 (inference) and :323-410 (dilated_res_block, building_block,
 // relative_pos_encoding, random_sample, nearest_interpolation, gather_neighbour, att_pooling) of the reference, whose
-// 1x1 convolutions are conv + bias -> batch_normalization(eps 1e-6) -> leaky_relu(0.2) (helper_tf_util.py:115-170), and
-// the BIM update of ares/ares/attack/bim.py:66-98 with its "colper" loss (:110-116).  One cloud per workspace
-// (ConfigS3DIS.val_batch_size = 1, helper_tool.py:52), 5 levels, k = 16.
+// 1x1 convolutions are conv + bias -> batch_normalization(eps 1e-6) -> leaky_relu(0.2) (helper_tf_util.py:115-170).
+// One cloud per workspace (ConfigS3DIS.val_batch_size = 1, helper_tool.py:52) or B independent clouds, 5 levels, k = 16.
 //
 // Every 1x1 convolution is one launch of the fp32-MFMA row GEMM (psg_gemm.cuh) with the BatchNorm affine folded into
 // the weights on the host and bias + leaky_relu (+ sign bits for the backward pass) in its epilogue; the per-edge
@@ -21,27 +22,18 @@
 #include "psg_common.h"
 #include "psg_gemm.cuh"
 #include "psg_randla_coord.h"
+#include "psg_randla_net.h"
 
 using namespace psg;
 
 namespace {
 
-constexpr int RL = 5;            // encoder levels
-constexpr int RK = 16;           // neighbours
-constexpr int RNCLS = 13;
 const int kDout[RL] = {16, 64, 128, 256, 512};
 const int kRatio[RL] = {4, 4, 4, 4, 2};
 constexpr float kSlope = 0.2f;
 #ifndef RL_SMALL_TILE_BELOW
 #define RL_SMALL_TILE_BELOW 256
 #endif
-
-struct RLayer {
-    float *w = nullptr;    // [cout][cin]  BatchNorm scale folded in
-    float *wt = nullptr;   // [cin][cout]
-    float *b = nullptr;    // [cout] folded bias, or null
-    int cin = 0, cout = 0;
-};
 
 // Skinny layers (K, M <= 32: everything at level 0 -- 8/16-wide features over 40 960 points or 655 360 edge rows): the
 // MFMA row GEMM would spend a 128-column tile on 8-32 useful columns, so these run one row per thread on the vector
@@ -989,185 +981,6 @@ __global__ void interp_concat_bwd_kernel(const float *__restrict__ dcat, int cs,
     else if (g != 0.0f) atomicAdd(dcoarse + (size_t)up[n] * cc + (c - cs), g);
 }
 
-// "colper" loss of the BIM attack (bim.py:110-116): sum_n max(0, max_k((1 - onehot) * z)_k - z_y); gradient w.r.t. z.
-// mask (TBIM / tar_NUattack, bim.py:393-397, tar_NUattack.py:105-110): the per-point loss is multiplied by mask[n] (the
-// points of the origin class); `sign` multiplies the gradient (goal 't': grad = -grad, bim.py:350-351).
-__global__ void colper_grad_kernel(const float *__restrict__ z, const int32_t *__restrict__ y, const uint8_t *__restrict__ mask,
-                                   float sign, int n, float *__restrict__ dz, float *__restrict__ loss)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    float l = 0.0f;
-    if (i < n) {
-        const float *zi = z + (size_t)i * RNCLS;
-        const int yi = y[i];
-        float other = 0.0f;          // the masked entry of the true class is 0 and takes part in the max
-        int oi = yi;
-        for (int k = 0; k < RNCLS; ++k)
-            if (k != yi && zi[k] > other) { other = zi[k]; oi = k; }
-        const float real = zi[yi];
-        const bool on = other - real > 0.0f && (!mask || mask[i]);
-        l = on ? other - real : 0.0f;
-        for (int k = 0; k < RNCLS; ++k) dz[(size_t)i * RNCLS + k] = 0.0f;
-        if (on) {
-            dz[(size_t)i * RNCLS + yi] = -sign;
-            if (oi != yi) dz[(size_t)i * RNCLS + oi] = sign;
-        }
-    }
-    if (loss) {
-        for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o);
-        if ((threadIdx.x & 63) == 0 && l != 0.0f) atomicAdd(loss, l);
-    }
-}
-
-// BIM update of the colours (bim.py:84-98), goal 'ut' (ascent).  l_inf: clip(adv + alpha*sign(g), x-eps, x+eps);
-// l_2: x + clip_by_norm(adv - x + alpha * g/|g|, eps); then clip to [0, 1], PER CLOUD: norms[b] = |g_b|^2,
-// norms[B + b] = |delta_b|^2 for the B clouds of a cloud-batch workspace.
-// squared norm of the colour part of ONE CLOUD per workgroup (blockIdx.x = cloud): every thread adds its strided elements in
-// double, then a fixed tree - one writer, a fixed order: the l_2 update is bit-reproducible (the atomic sum it replaces was
-// reproducible to rounding only) and a cloud-batch workspace gets one norm per cloud, as bim.py:84-98 normalises per sample.
-__global__ __launch_bounds__(1024) void sq_norm_kernel(const float *__restrict__ a, int ld, int c0, size_t nc, float *__restrict__ out)
-{
-    __shared__ double s_part[16];
-    const float *p = a + (size_t)blockIdx.x * nc * ld;
-    double s = 0.0;
-    for (size_t t = threadIdx.x; t < nc * 3; t += blockDim.x) {
-        const float v = p[(t / 3) * ld + c0 + (t % 3)];
-        s += (double)v * (double)v;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_part[w];
-        out[blockIdx.x] = (float)tot;
-    }
-}
-
-__global__ void bim_linf_kernel(float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ ori, size_t n,
-                                float alpha, float eps)
-{
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const size_t i = t / 3;
-    const int c = (int)(t % 3);
-    const float g = dfeat[i * 6 + 3 + c], x = ori[t];
-    const float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
-    float v = feat[i * 6 + 3 + c] + alpha * sg;
-    v = fminf(fmaxf(v, x - eps), x + eps);
-    feat[i * 6 + 3 + c] = fminf(fmaxf(v, 0.0f), 1.0f);
-}
-
-__global__ void bim_l2_delta_kernel(const float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ ori,
-                                    size_t n, size_t nc, float alpha, const float *__restrict__ gnorm2, float *__restrict__ delta)
-{
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const size_t i = t / 3;
-    const int c = (int)(t % 3);
-    const float gn = fmaxf(1e-12f, sqrtf(gnorm2[i / nc]));            // the cloud's own gradient norm
-    delta[t] = feat[i * 6 + 3 + c] - ori[t] + alpha * (dfeat[i * 6 + 3 + c] / gn);
-}
-
-__global__ void bim_l2_apply_kernel(float *__restrict__ feat, const float *__restrict__ ori, const float *__restrict__ delta, size_t n,
-                                    size_t nc, float eps, const float *__restrict__ dnorm2)
-{
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const size_t i = t / 3;
-    const int c = (int)(t % 3);
-    const float dn = sqrtf(dnorm2[i / nc]);
-    const float scale = dn > eps ? eps / dn : 1.0f;
-    feat[i * 6 + 3 + c] = fminf(fmaxf(ori[t] + delta[t] * scale, 0.0f), 1.0f);
-}
-
-__global__ void copy_cols_kernel(const float *__restrict__ src, int ld_s, int c0, int nc, size_t rows, float *__restrict__ dst, int ld_d, int d0)
-{
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= rows * nc) return;
-    const size_t r = t / nc;
-    const int c = (int)(t % nc);
-    dst[r * ld_d + d0 + c] = src[r * ld_s + c0 + c];
-}
-
-inline unsigned blocks_for(size_t total) { return (unsigned)((total + 255) / 256); }
-
-struct EncLayers { RLayer mlp1, lfa_mlp1, att1_fc, att1_mlp, lfa_mlp2, att2_fc, att2_mlp, mlp2, shortcut; };
-
-}  // namespace
-
-struct psg_rla_model {
-    uint64_t gen = psg::next_generation();   // never re-used (psg_common.h): what the replayed BIM iteration is keyed on
-    psg_ctx *ctx;
-    RLayer fc0, decoder0, dec[RL], fc1, fc2, fc;
-    EncLayers enc[RL];
-    std::vector<void *> allocs;
-};
-
-struct LevelBuf {
-    int n = 0, n_sub = 0, d = 0, h = 0, d_in = 0;   // n, n_sub: rows of ALL clouds of the workspace (B * per-cloud counts)
-    int nc = 0, nc_sub = 0;                         // per cloud
-    float *xyz = nullptr;                           // [B][nc][3]: the level's points, cloud by cloud
-    int32_t *neigh = nullptr, *up = nullptr;   // [n][16], [n][1] (row numbers of this level / of the next); pool = a cloud's first nc_sub rows
-    // transposes of the two index arrays (the geometry is fixed for a whole attack, so they are built once per cloud): for every
-    // row j of this level the edges e = p * 16 + k with neigh[e] == j, ascending (inv_off [n + 1], inv_ent [n * 16]); for every row
-    // t of the next level the rows n with up[n] == t, ascending (invu_off [n_sub + 1], invu_ent [n]).  The backward pass GATHERS
-    // through them in that fixed order instead of scattering with float atomics: bit-reproducible, and faster.
-    int32_t *inv_off = nullptr, *inv_ent = nullptr, *invu_off = nullptr, *invu_ent = nullptr;
-    // the same for the edges of the SAMPLED points only (the max-pool reads just those): entries i = r * 16 + k, r a sampled row
-    int32_t *invp_off = nullptr, *invp_ent = nullptr;
-    float *relpos, *fxyz1, *fxyz2;             // [n*16][10], [n*16][h] x2
-    float *fpc, *cat1, *a1, *agg1, *fagg1, *cat2, *a2, *agg2, *fagg2, *m2, *sc, *enc, *samp;
-    uint32_t *m_fpc, *m_fagg1, *m_fagg2, *m_enc;
-    uint8_t *arg;
-    float *d_enc, *d_samp;                     // gradients w.r.t. enc [n][2d] and samp [n_sub][2d]
-    float *d_fpc, *d_fagg1;                    // [n][h]
-    // full workspaces only (psg_rla_ws_create_full), the position-branch gradient: sign words of fxyz1 / fxyz2 [16n][ceil(h/32)],
-    // G2 / G1 [16n][h] (gradients of the pre-activations of LFAmlp2 / LFAmlp1), g_rp [16n][10], what every edge hands to its
-    // point i and to its neighbour j ([16n] float4 each), gxyz [n][3]
-    uint32_t *m_fxyz1 = nullptr, *m_fxyz2 = nullptr;
-    float *G1 = nullptr, *G2 = nullptr, *g_rp = nullptr, *gxyz = nullptr;
-    float4 *side_i = nullptr, *side_j = nullptr;
-};
-
-struct psg_rla_ws {
-    uint64_t gen = psg::next_generation();   // never re-used (psg_common.h): what a replayed NU window is keyed on
-    psg_ctx *ctx;
-    int N = 0;                      // rows of all clouds: B * Nc
-    int B = 1, Nc = 0;              // clouds per workspace (independent: every index stays inside its cloud), points per cloud
-    void *arena = nullptr;
-    size_t bytes = 0;
-    float *xyz_all;                 // [B][Nc][3]; a level's points are the first Nc / ratio points of each cloud
-    float *xyz_last;                // [B][nc5][3]: the sub-sampled points of the last level
-    LevelBuf lv[RL];
-    float *f0; uint32_t *m_f0;      // fc0 output [N][8]
-    float *dec0; uint32_t *m_dec0;  // decoder_0 output [n5][1024]
-    float *dec_cat[RL], *dec_out[RL]; uint32_t *m_dec[RL];
-    float *fc1o, *fc2o; uint32_t *m_fc1, *m_fc2;
-    float *logits, *dlogits;
-    float *scratch_a, *scratch_b;   // [max edges * d] gradient scratch (dcat / ds), also decoder d_cat
-    float *d_f0, *d_dec0, *d_dec_out[RL], *d_fc1o, *d_fc2o;
-    char *acc = nullptr; size_t acc_bytes = 0;   // the contiguous block of gradient accumulators
-    float *feat, *dfeat, *ori, *delta, *norms;   // attack state: [N][6], [N][6], [N][3], [N][3], [2][B] (l_2: squared gradient / delta norm per cloud)
-    int32_t *labels;
-    bool cloud_set = false, have_fwd = false;
-    bool fuse16 = true;           // PSG_RLA_NO_FUSE16=1: the unfused chain at level 0 too (A/B runs, tests)
-    bool split = true;            // PSG_RLA_NO_SPLIT=1: levels 1-4 through the gather + per-edge score GEMM chain (A/B runs)
-    bool use_inv = true;          // PSG_RLA_ATOMICS=1: the scatter kernels with float atomics instead of the inverse-list gathers
-    bool full = false;            // psg_rla_ws_create_full: the buffers of the coordinate gradient, level 0 on the unfused chain
-    size_t scratch_bytes = 0;     // of scratch_a and of scratch_b
-    EvLog prof;                   // psg_rla_prof_enable
-    uint64_t xyz_branch_model = 0;   // generation number (not the address: a freed model's address can come back) of the model whose xyz-branch features (fxyz1 / fxyz2) are resident
-    // hipGraph of one BIM iteration (forward, loss gradient, backward, update: ~150 short launches), valid for the
-    // (model, eps, alpha, metric) below; every captured kernel works on workspace buffers, so it is cloud-independent
-    psg::GraphSlot bim;
-    uint64_t bim_model_gen = 0;      // the model's generation number, not its address (psg_common.h)
-    float bim_eps = 0.f, bim_alpha = 0.f;
-    int bim_metric = -1;
-};
-
-namespace {
-
 // tensors[6 * i .. 6 * i + 5] = weight [cout][cin], bias or null, bn gamma, beta, mean, var or null
 // (`ok` is cleared when an upload fails)
 RLayer make_layer(psg_rla_model *m, const float *const *t, int cin, int cout, bool &ok)
@@ -1409,13 +1222,8 @@ extern "C" int psg_rla_prof_read_kernels(psg_rla_ws *ws, int n_tags, double *tot
     return PSG_OK;
 }
 
-namespace {
-struct ProfBind {   // routes rl_gemm's scopes to the workspace of the call in progress
-    EvLog *prev;
-    explicit ProfBind(psg_rla_ws *ws) : prev(tl_prof) { tl_prof = (ws && ws->prof.on) ? &ws->prof : nullptr; }
-    ~ProfBind() { tl_prof = prev; }
-};
-}  // namespace
+psg::ProfBind::ProfBind(psg_rla_ws *ws) : prev(tl_prof) { tl_prof = (ws && ws->prof.on) ? &ws->prof : nullptr; }
+psg::ProfBind::~ProfBind() { tl_prof = prev; }
 
 // ent = the positions 0 .. m-1 of keys[], stably sorted by key (hipcub radix sort: ties keep their ascending position),
 // off[t] = where target t's run begins.  Temporaries in the workspace's two scratch buffers (idle while the pyramid is built).
@@ -1436,9 +1244,7 @@ static int build_inverse(psg_rla_ws *ws, const int32_t *keys, size_t m, int n_ta
     return PSG_OK;
 }
 
-// The index pyramid of the reference's tf_map (main_S3DIS.py:198-207) and the relative position encodings, from the
-// cloud in ws->xyz_all.
-static int build_pyramid(psg_rla_ws *ws, psg_stream stream)
+int psg::build_pyramid(psg_rla_ws *ws, psg_stream stream)
 {
     hipStream_t st = (hipStream_t)stream;
     int rc;
@@ -1902,684 +1708,4 @@ static int rla_backward(psg_rla_model *m, psg_rla_ws *ws, const float *dlogits, 
     if ((rc = conv_bwd(m->fc0, ws->d_f0, 8, dfeatures_out, 6, N, 0, st))) return rc;
     ws->have_fwd = false;   // agg / fagg buffers were reused as gradient scratch
     return PSG_OK;
-}
-
-extern "C" int psg_rla_colper_grad(const float *logits, const int32_t *labels, int n, float *dlogits, float *loss_out, psg_stream stream)
-{
-    PSG_REQUIRE(logits && labels && dlogits && n > 0, "psg_rla_colper_grad: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (loss_out) PSG_CHECK_HIP(hipMemsetAsync(loss_out, 0, 4, st));
-    hipLaunchKernelGGL(colper_grad_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, logits, labels, (const uint8_t *)nullptr, 1.0f, n,
-                       dlogits, loss_out);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-extern "C" int psg_rla_colper_grad_masked(const float *logits, const int32_t *ys, const uint8_t *mask, float sign, int n,
-                                          float *dlogits, float *loss_out, psg_stream stream)
-{
-    PSG_REQUIRE(logits && ys && dlogits && n > 0, "psg_rla_colper_grad_masked: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (loss_out) PSG_CHECK_HIP(hipMemsetAsync(loss_out, 0, 4, st));
-    hipLaunchKernelGGL(colper_grad_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, logits, ys, mask, sign, n, dlogits, loss_out);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// One BIM update of the colour half of feat [n][6] from its gradient dfeat [n][6] (bim.py:84-98): l_inf or l_2 (norms:
-// 2 floats of scratch), then the clip to [0, 1].  The step of psg_rla_bim_attack as an entry of its own, for the attacks
-// whose loop lives on the host because the reference reads an accuracy back every iteration (TBIM's `sr > 0.9` exit).
-extern "C" int psg_rla_bim_step(float *feat, const float *dfeat, const float *ori, int n, float eps, float alpha, int l2_metric,
-                                float *norms, float *delta, psg_stream stream)
-{
-    PSG_REQUIRE(feat && dfeat && ori && n > 0 && (!l2_metric || (norms && delta)), "psg_rla_bim_step: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t N = (size_t)n;
-    if (!l2_metric) {
-        hipLaunchKernelGGL(bim_linf_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, feat, dfeat, ori, N, alpha, eps);
-        PSG_LAUNCH_CHECK();
-        return PSG_OK;
-    }
-    hipLaunchKernelGGL(sq_norm_kernel, dim3(1), dim3(1024), 0, st, dfeat, 6, 3, N, norms);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bim_l2_delta_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, feat, dfeat, ori, N, N, alpha, norms, delta);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sq_norm_kernel, dim3(1), dim3(1024), 0, st, delta, 3, 0, N, norms + 1);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bim_l2_apply_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, feat, ori, delta, N, N, eps, norms + 1);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// ---- NUattack / tar_NUattack (ares/ares/attack/NUattack.py:12-74, tar_NUattack.py:12-84): Adam on d_ws in tanh space.
-//   ws = atanh(2 b x - b) + d_ws (b = 1 - 1e-6), adv = (tanh(ws) + 1) / 2, masked: adv = mask adv + (1 - mask) x;
-//   loss = |adv - x|_2 + c * score;  TF1 Adam: lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), d_ws -= lr_t m / (sqrt(v) + 1e-8).
-namespace {
-constexpr float kNuBound = 1.0f - 1e-6f;
-
-__global__ void nu_color_kernel(const float *__restrict__ xs, const float *__restrict__ dws, const uint8_t *__restrict__ mask,
-                                size_t n, float *__restrict__ feat, float *__restrict__ dist2)
-{
-    float s = 0.0f;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * 3; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = t / 3;
-        const int c = (int)(t % 3);
-        const float x = xs[t];
-        const float w = atanhf(2.0f * kNuBound * x - kNuBound) + dws[t];
-        float adv = 0.5f * (tanhf(w) + 1.0f);
-        if (mask && !mask[i]) adv = x;
-        feat[i * 6 + 3 + c] = adv;
-        const float d = adv - x;
-        s += d * d;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) atomicAdd(dist2, s);
-}
-
-__global__ void nu_adam_kernel(const float *__restrict__ xs, float *__restrict__ dws, float *__restrict__ m, float *__restrict__ v,
-                               const uint8_t *__restrict__ mask, const float *__restrict__ feat, const float *__restrict__ dfeat,
-                               const float *__restrict__ dist2, size_t n, float c, float lr_t, float b1, float b2, float eps)
-{
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const size_t i = t / 3;
-    const int ch = (int)(t % 3);
-    const float x = xs[t];
-    const float w = atanhf(2.0f * kNuBound * x - kNuBound) + dws[t];
-    const float th = tanhf(w);
-    const float adv = feat[i * 6 + 3 + ch];
-    const float dist = sqrtf(dist2[0]);
-    // d loss / d adv = (adv - x) / |adv - x|_2 + c * d score / d adv;  d adv / d d_ws = mask * (1 - tanh^2) / 2
-    float g = (dist > 0.0f ? (adv - x) / dist : 0.0f) + c * dfeat[i * 6 + 3 + ch];
-    g *= (mask && !mask[i]) ? 0.0f : 0.5f * (1.0f - th * th);
-    const float mm = b1 * m[t] + (1.0f - b1) * g;
-    const float vv = b2 * v[t] + (1.0f - b2) * g * g;
-    m[t] = mm;
-    v[t] = vv;
-    dws[t] -= lr_t * mm / (sqrtf(vv) + eps);
-}
-}  // namespace
-
-// adv colours of d_ws into feat [n][6] (columns 3..5) and dist2[0] = |adv - x|_2^2 (cleared here)
-extern "C" int psg_rla_nu_color(const float *xs, const float *dws, const uint8_t *mask, int n, float *feat, float *dist2,
-                                psg_stream stream)
-{
-    PSG_REQUIRE(xs && dws && feat && dist2 && n > 0, "psg_rla_nu_color: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    PSG_CHECK_HIP(hipMemsetAsync(dist2, 0, 4, st));
-    hipLaunchKernelGGL(nu_color_kernel, dim3(256), dim3(256), 0, st, xs, dws, mask, (size_t)n, feat, dist2);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// one Adam step (t = 1, 2, ..) on d_ws from dfeat = d score / d features [n][6] of the forward that psg_rla_nu_color fed
-extern "C" int psg_rla_nu_adam_step(const float *xs, float *dws, float *m, float *v, const uint8_t *mask, const float *feat,
-                                    const float *dfeat, const float *dist2, int n, float c, float lr, int t, psg_stream stream)
-{
-    PSG_REQUIRE(xs && dws && m && v && feat && dfeat && dist2 && n > 0 && t >= 1, "psg_rla_nu_adam_step: bad argument");
-    const double b1 = 0.9, b2 = 0.999;
-    const float lr_t = (float)((double)lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t)));
-    hipLaunchKernelGGL(nu_adam_kernel, dim3(blocks_for((size_t)n * 3)), dim3(256), 0, (hipStream_t)stream, xs, dws, m, v, mask, feat,
-                       dfeat, dist2, (size_t)n, c, lr_t, 0.9f, 0.999f, 1e-8f);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// BIM (ares/ares/attack/bim.py:190-236): `iters` gradient steps on the colour half of the features of one cloud.
-extern "C" int psg_rla_bim_attack(psg_rla_model *m, psg_rla_ws *ws, const float *features, const int32_t *labels, float eps,
-                                  float alpha, int iters, int l2_metric, float *adv_features_out, psg_stream stream)
-{
-    PSG_REQUIRE(m && ws && features && labels && adv_features_out && iters > 0, "psg_rla_bim_attack: bad argument");
-    ProfBind bind(ws);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t N = ws->N;
-    int rc;
-    PSG_CHECK_HIP(hipMemcpyAsync(ws->feat, features, N * 6 * 4, hipMemcpyDeviceToDevice, st));
-    PSG_CHECK_HIP(hipMemcpyAsync(ws->labels, labels, N * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(copy_cols_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, features, 6, 3, 3, N, ws->ori, 3, 0);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(copy_cols_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, features, 6, 0, 3, N, ws->xyz_all, 3, 0);
-    PSG_LAUNCH_CHECK();
-    if ((rc = build_pyramid(ws, stream))) return rc;        // geometry: once per cloud, the attack moves colours only
-    auto iteration = [&]() -> int {
-        int r;
-        if ((r = psg_rla_forward(m, ws, ws->feat, ws->logits, stream))) return r;
-        if ((r = psg_rla_colper_grad(ws->logits, ws->labels, (int)N, ws->dlogits, nullptr, stream))) return r;
-        if ((r = psg_rla_backward(m, ws, ws->dlogits, ws->dfeat, stream))) return r;
-        if (!l2_metric) {
-            hipLaunchKernelGGL(bim_linf_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, ws->feat, ws->dfeat, ws->ori, N, alpha, eps);
-            PSG_LAUNCH_CHECK();
-        } else {
-            // per cloud (bim.py:84-98 normalises every sample of the batch by its own norms): norms [2][B]
-            const size_t Nc = (size_t)ws->Nc;
-            hipLaunchKernelGGL(sq_norm_kernel, dim3(ws->B), dim3(1024), 0, st, ws->dfeat, 6, 3, Nc, ws->norms);
-            PSG_LAUNCH_CHECK();
-            hipLaunchKernelGGL(bim_l2_delta_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, ws->feat, ws->dfeat, ws->ori, N, Nc, alpha,
-                               ws->norms, ws->delta);
-            PSG_LAUNCH_CHECK();
-            hipLaunchKernelGGL(sq_norm_kernel, dim3(ws->B), dim3(1024), 0, st, ws->delta, 3, 0, Nc, ws->norms + ws->B);
-            PSG_LAUNCH_CHECK();
-            hipLaunchKernelGGL(bim_l2_apply_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, ws->feat, ws->ori, ws->delta, N, Nc, eps,
-                               ws->norms + ws->B);
-            PSG_LAUNCH_CHECK();
-        }
-        return PSG_OK;
-    };
-    // The first iteration runs eagerly (it computes the xyz branch and sets kernel attributes outside any capture); the
-    // others enqueue the same launches with the same arguments, so they are captured once into a hipGraph kept in the
-    // workspace and replayed: one graph launch instead of ~150 kernel launches per iteration, which is what lets several
-    // long attacks on different streams actually overlap (the host would otherwise spend its time filling one stream's
-    // queue).  Capture is impossible on the legacy default stream; the loop then stays eager.
-    if ((rc = iteration())) return rc;
-    int it = 1;
-    static const bool use_graph = !((psg::env_int("PSG_RLA_NO_GRAPH", 0) != 0)) && !trace_sync_enabled();   // (the tracer synchronises after every launch)
-    if (use_graph && !ws->prof.on && iters - it >= 2) {
-        const bool same_key = ws->bim_model_gen == m->gen && ws->bim_eps == eps && ws->bim_alpha == alpha && ws->bim_metric == l2_metric;
-        if (!same_key) PSG_CHECK_HIP(ws->bim.forget(st));
-        if (!ws->bim.exec && !ws->bim.capture_failed) {
-            ws->bim.capture(st, iteration);
-            ws->bim_model_gen = m->gen; ws->bim_eps = eps; ws->bim_alpha = alpha; ws->bim_metric = l2_metric;
-        }
-        if (ws->bim.exec) {
-            PSG_CHECK_HIP(ws->bim.replay(st, iters - it));
-            it = iters;
-        } else {
-            ws->bim.note_eager(iters - it);
-        }
-    }
-    for (; it < iters; ++it)
-        if ((rc = iteration())) return rc;
-    PSG_CHECK_HIP(hipMemcpyAsync(adv_features_out, ws->feat, N * 6 * 4, hipMemcpyDeviceToDevice, st));
-    return PSG_OK;
-}
-
-// ---- NUattack / tar_NUattack on G clouds in lockstep (the batch workspace: one launch of every network kernel serves all
-// clouds).  blockIdx.y = cloud; a cloud whose `active` byte is clear is skipped by whole workgroups.  The reductions use no
-// float atomics: PSG_RLA_NU_PARTS workgroups per cloud each own a fixed slice and write one partial, a second kernel adds the
-// partials in index order - the same bits in every run, whatever the other clouds do.
-namespace {
-constexpr int kNuParts = PSG_RLA_NU_PARTS;
-
-__global__ __launch_bounds__(256) void nu_color_clouds_kernel(const float *__restrict__ xs, const float *__restrict__ dws,
-                                                              const uint8_t *__restrict__ mask, const uint8_t *__restrict__ active,
-                                                              size_t n, float *__restrict__ feat, double *__restrict__ partials)
-{
-    __shared__ double s_part[4];
-    const int g = blockIdx.y;
-    if (active && !active[g]) return;
-    const size_t base = (size_t)g * n;
-    double s = 0.0;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * 3; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = t / 3;
-        const int c = (int)(t % 3);
-        const float x = xs[base * 3 + t];
-        const float w = atanhf(2.0f * kNuBound * x - kNuBound) + dws[base * 3 + t];
-        float adv = 0.5f * (tanhf(w) + 1.0f);
-        if (mask && !mask[base + i]) adv = x;
-        feat[(base + i) * 6 + 3 + c] = adv;
-        const double d = (double)adv - (double)x;       // exact; the sum is of the colours as written, like sq_norm_kernel's
-        s += d * d;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[(size_t)g * gridDim.x + blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-}
-
-__global__ void nu_dist2_clouds_kernel(const double *__restrict__ partials, const uint8_t *__restrict__ active, int G, int parts,
-                                       float *__restrict__ dist2)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= G || (active && !active[g])) return;
-    double tot = 0.0;
-    for (int p = 0; p < parts; ++p) tot += partials[(size_t)g * parts + p];
-    dist2[g] = (float)tot;
-}
-
-// nu_adam_kernel's update, expression for expression, with the cloud's own distance
-__global__ void nu_adam_clouds_kernel(const float *__restrict__ xs, float *__restrict__ dws, float *__restrict__ m, float *__restrict__ v,
-                                      const uint8_t *__restrict__ mask, const uint8_t *__restrict__ active,
-                                      const float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ dist2,
-                                      size_t n, float c, float lr_arg, const float *__restrict__ consts, float b1, float b2, float eps)
-{
-    const int g = blockIdx.y;
-    if (active && !active[g]) return;
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const float lr_t = consts ? consts[3] : lr_arg;
-    const size_t i = (size_t)g * n + t / 3;
-    const int ch = (int)(t % 3);
-    t += (size_t)g * n * 3;
-    const float x = xs[t];
-    const float w = atanhf(2.0f * kNuBound * x - kNuBound) + dws[t];
-    const float th = tanhf(w);
-    const float adv = feat[i * 6 + 3 + ch];
-    const float dist = sqrtf(dist2[g]);
-    float gr = (dist > 0.0f ? (adv - x) / dist : 0.0f) + c * dfeat[i * 6 + 3 + ch];
-    gr *= (mask && !mask[i]) ? 0.0f : 0.5f * (1.0f - th * th);
-    const float mm = b1 * m[t] + (1.0f - b1) * gr;
-    const float vv = b2 * v[t] + (1.0f - b2) * gr * gr;
-    m[t] = mm;
-    v[t] = vv;
-    dws[t] -= lr_t * mm / (sqrtf(vv) + eps);
-}
-
-// Latch, first half: pred = first maximum of the 13 logits; every workgroup counts its slice of the cloud into
-// scratch[g][1 + 2 part + {0, 1}] = {#(pred == labels), #(mask & pred == ys)}; scratch[g][0] = was the cloud active when the
-// latch began (the second half clears `active`, so its workgroups must not read it)
-__global__ __launch_bounds__(256) void nu_latch_count_kernel(const float *__restrict__ logits, const int32_t *__restrict__ labels,
-                                                             const int32_t *__restrict__ ys, const uint8_t *__restrict__ mask,
-                                                             const uint8_t *__restrict__ active, int n, int32_t *__restrict__ pred,
-                                                             int32_t *__restrict__ scratch)
-{
-    __shared__ int s_cnt[4][2];
-    const int g = blockIdx.y, parts = gridDim.x;
-    int32_t *sc = scratch + (size_t)g * (2 * parts + 1);
-    const bool live = active[g] != 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) sc[0] = live ? 1 : 0;
-    if (!live) return;
-    const int chunk = (n + parts - 1) / parts;
-    const int lo = min(n, (int)blockIdx.x * chunk), hi = min(n, lo + chunk);
-    int c0 = 0, c1 = 0;
-    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        const size_t r = (size_t)g * n + i;
-        const float *z = logits + r * RNCLS;
-        float best = z[0];
-        int bi = 0;
-        for (int k = 1; k < RNCLS; ++k)
-            if (z[k] > best) { best = z[k]; bi = k; }
-        pred[r] = bi;
-        c0 += bi == labels[r] ? 1 : 0;
-        c1 += (mask && mask[r] && bi == ys[r]) ? 1 : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor(c0, o); c1 += __shfl_xor(c1, o); }
-    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6][0] = c0; s_cnt[threadIdx.x >> 6][1] = c1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        sc[1 + 2 * blockIdx.x] = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0];
-        sc[2 + 2 * blockIdx.x] = s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1] + s_cnt[3][1];
-    }
-}
-
-// Latch, second half: every workgroup of a live cloud adds the cloud's counts, takes the exit decision (integers) and, for a
-// snapshot, copies its slice; workgroup 0 writes the history row, the snapshot's statistics, exit_step and active.
-__global__ __launch_bounds__(256) void nu_latch_commit_kernel(const float *__restrict__ feat, const int32_t *__restrict__ pred,
-                                                              const float *__restrict__ dist2, const int32_t *__restrict__ n_mask,
-                                                              const int32_t *__restrict__ scratch, int n, int mode, int num, int den,
-                                                              int step_arg, int can_exit, int final, const float *__restrict__ consts,
-                                                              float *__restrict__ hist_row, float *__restrict__ out_adv,
-                                                              int32_t *__restrict__ out_pred, float *__restrict__ out_stats,
-                                                              uint8_t *__restrict__ active, int32_t *__restrict__ exit_step)
-{
-    const int g = blockIdx.y, parts = gridDim.x;
-    const int32_t *sc = scratch + (size_t)g * (2 * parts + 1);
-    if (!sc[0]) return;
-    const int step = consts ? __builtin_bit_cast(int, consts[0]) : step_arg;
-    int nc = 0, nh = 0;
-    for (int p = 0; p < parts; ++p) { nc += sc[1 + 2 * p]; nh += sc[2 + 2 * p]; }
-    const bool fire = mode == 0 ? (long long)den * nc < (long long)num * n : (long long)den * nh > (long long)num * n_mask[g];
-    const bool exits = fire && can_exit && step >= 1;
-    if (exits || final) {
-        const int chunk = (n + parts - 1) / parts;
-        const int lo = min(n, (int)blockIdx.x * chunk), hi = min(n, lo + chunk);
-        for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-            const size_t r = (size_t)g * n + i;
-            out_adv[r * 3] = feat[r * 6 + 3];
-            out_adv[r * 3 + 1] = feat[r * 6 + 4];
-            out_adv[r * 3 + 2] = feat[r * 6 + 5];
-            out_pred[r] = pred[r];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const float row[3] = {(float)nc, (float)nh, dist2[g]};
-        for (int k = 0; k < 3; ++k) hist_row[g * 3 + k] = row[k];
-        if (exits || final)
-            for (int k = 0; k < 3; ++k) out_stats[g * 3 + k] = row[k];
-        if (exits) { exit_step[g] = step; active[g] = 0; }
-    }
-}
-}  // namespace
-
-extern "C" int psg_rla_nu_color_clouds(const float *xs, const float *dws, const uint8_t *mask, const uint8_t *active, int G, int n,
-                                       float *feat, float *dist2, double *partials, psg_stream stream)
-{
-    PSG_REQUIRE(xs && dws && feat && dist2 && partials, "psg_rla_nu_color_clouds: null argument");
-    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_nu_color_clouds: G=%d n=%d out of range", G, n);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(nu_color_clouds_kernel, dim3(kNuParts, G), dim3(256), 0, st, xs, dws, mask, active, (size_t)n, feat, partials);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(nu_dist2_clouds_kernel, dim3(ceil_div(G, 64)), dim3(64), 0, st, partials, active, G, kNuParts, dist2);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-extern "C" int psg_rla_nu_adam_clouds(const float *xs, float *dws, float *m, float *v, const uint8_t *mask, const uint8_t *active,
-                                      const float *feat, const float *dfeat, const float *dist2, int G, int n, float c, float lr, int t,
-                                      psg_stream stream)
-{
-    PSG_REQUIRE(xs && dws && m && v && feat && dfeat && dist2 && t >= 1, "psg_rla_nu_adam_clouds: bad argument");
-    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_nu_adam_clouds: G=%d n=%d out of range", G, n);
-    const double b1 = 0.9, b2 = 0.999;
-    const float lr_t = (float)((double)lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t)));
-    hipLaunchKernelGGL(nu_adam_clouds_kernel, dim3(blocks_for((size_t)n * 3), G), dim3(256), 0, (hipStream_t)stream, xs, dws, m, v, mask,
-                       active, feat, dfeat, dist2, (size_t)n, c, lr_t, psg::nu_step_consts(), 0.9f, 0.999f, 1e-8f);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-extern "C" int psg_rla_nu_latch_clouds(const float *logits, const int32_t *labels, const int32_t *ys, const uint8_t *mask,
-                                       const int32_t *n_mask, const float *feat, const float *dist2, int G, int n, int mode, int num,
-                                       int den, int step, int can_exit, int final, float *hist_row, int32_t *pred, float *out_adv,
-                                       int32_t *out_pred, float *out_stats, uint8_t *active, int32_t *exit_step, int32_t *scratch,
-                                       psg_stream stream)
-{
-    PSG_REQUIRE(logits && labels && feat && dist2 && hist_row && pred && out_adv && out_pred && out_stats && active && exit_step && scratch,
-                "psg_rla_nu_latch_clouds: null argument");
-    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_nu_latch_clouds: G=%d n=%d out of range", G, n);
-    PSG_REQUIRE(mode == 0 || mode == 1, "psg_rla_nu_latch_clouds: mode %d out of range", mode);
-    PSG_REQUIRE(!mask || ys, "psg_rla_nu_latch_clouds: a mask needs ys");
-    PSG_REQUIRE(mode == 0 || (mask && n_mask), "psg_rla_nu_latch_clouds: mode 1 needs mask and n_mask");
-    PSG_REQUIRE(num >= 0 && den > 0 && step >= 0, "psg_rla_nu_latch_clouds: num=%d den=%d step=%d out of range", num, den, step);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(nu_latch_count_kernel, dim3(kNuParts, G), dim3(256), 0, st, logits, labels, ys, mask, (const uint8_t *)active, n, pred,
-                       scratch);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(nu_latch_commit_kernel, dim3(kNuParts, G), dim3(256), 0, st, feat, (const int32_t *)pred, dist2, n_mask,
-                       (const int32_t *)scratch, n, mode, num, den, step, can_exit, final, psg::nu_step_consts(), hist_row, out_adv, out_pred,
-                       out_stats, active, exit_step);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// One step sequence of a window, shared by the eager and the captured path; rows: the window's step-constant device rows
-// {evaluation index, -, -, lr_t} or null.  Everything in it is a launch on `stream`: a single chain.
-static int rla_nu_window_steps(const psg_rla_nu_window_args *a, const float *rows, psg_stream stream)
-{
-    const int G = a->G, N = a->N;
-    const int total = a->n_steps + (a->tail_eval ? 1 : 0);
-    int rc = PSG_OK;
-    for (int i = 0; i < total && rc == PSG_OK; ++i) {
-        const int t = a->adam_t0 + i;                // Adam index of the step; the forward before it evaluates index t - 1
-        const bool tail = i == a->n_steps;
-        if ((rc = psg_rla_nu_color_clouds(a->xs, a->dws, a->mask, a->active, G, N, a->feat, a->dist2, a->partials, stream))) break;
-        if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
-        psg::nu_set_step_consts(rows ? rows + 4 * i : nullptr);
-        // (a captured window serves every later one: there the latch's own `step >= 1` rule keeps the start from exiting)
-        rc = psg_rla_nu_latch_clouds(a->logits, a->labels, a->ys, a->mask, a->n_mask, a->feat, a->dist2, G, N, a->mode, a->num, a->den,
-                                     t - 1, (rows || t - 1 >= 1) ? 1 : 0, tail ? 1 : 0, a->hist + (size_t)i * 3 * G, a->pred, a->out_adv,
-                                     a->out_pred, a->out_stats, a->active, a->exit_step, a->scratch, stream);
-        if (rc == PSG_OK && !tail) {
-            if ((rc = psg_rla_colper_grad_masked(a->logits, a->ys, a->mask, 1.0f, G * N, a->dlogits, nullptr, stream)) == PSG_OK &&
-                (rc = psg_rla_backward(a->model, a->ws, a->dlogits, a->dfeat, stream)) == PSG_OK)
-                rc = psg_rla_nu_adam_clouds(a->xs, a->dws, a->m, a->v, a->mask, a->active, a->feat, a->dfeat, a->dist2, G, N, a->cs, a->lr, t,
-                                            stream);
-        }
-        psg::nu_set_step_consts(nullptr);
-    }
-    psg::nu_set_step_consts(nullptr);
-    return rc;
-}
-
-extern "C" int psg_rla_nu_window(const psg_rla_nu_window_args *a, psg_nu_graph *graph, psg_stream stream)
-{
-    PSG_REQUIRE(a && a->model && a->ws && a->xs && a->dws && a->m && a->v && a->labels && a->ys && a->feat && a->logits && a->dlogits &&
-                    a->dfeat && a->dist2 && a->partials && a->pred && a->scratch && a->hist && a->out_adv && a->out_pred && a->out_stats &&
-                    a->active && a->exit_step,
-                "psg_rla_nu_window: null argument");
-    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->Nc, "psg_rla_nu_window: the workspace is for %d clouds of %d points, the window for %d of %d",
-                a->ws->B, a->ws->Nc, a->G, a->N);
-    PSG_REQUIRE(a->n_steps >= 1 && a->n_steps <= PSG_NU_GRAPH_MAX_STEPS, "psg_rla_nu_window: n_steps=%d outside 1..%d", a->n_steps,
-                PSG_NU_GRAPH_MAX_STEPS);
-    PSG_REQUIRE(a->adam_t0 >= 1, "psg_rla_nu_window: adam_t0=%d (the first step is 1)", a->adam_t0);
-    PSG_REQUIRE(a->mode == 0 || a->mode == 1, "psg_rla_nu_window: mode %d out of range", a->mode);
-    PSG_REQUIRE(a->mode == 0 || (a->mask && a->n_mask), "psg_rla_nu_window: mode 1 needs mask and n_mask");
-    PSG_REQUIRE(a->num >= 0 && a->den > 0, "psg_rla_nu_window: threshold %d / %d out of range", a->num, a->den);
-    if (!a->ws->cloud_set) { set_error("psg_rla_nu_window: psg_rla_set_cloud has not been called"); return PSG_ERR_STATE; }
-    ProfBind bind(a->ws);
-    // what a captured window is valid for: the argument block without what the device rows carry
-    psg_rla_nu_window_args key;
-    memset(&key, 0, sizeof(key));
-    key = *a;
-    key.adam_t0 = 0; key.lr = 0.0f;
-    const int total = a->n_steps + (a->tail_eval ? 1 : 0);
-    float lr_rows[PSG_NU_GRAPH_MAX_STEPS + 1];
-    const double b1 = 0.9, b2 = 0.999;
-    for (int i = 0; i < total; ++i) {      // psg_rla_nu_adam_clouds' lr_t (the tail's row has no Adam step)
-        const int t = a->adam_t0 + i;
-        lr_rows[i] = i < a->n_steps ? (float)((double)a->lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t))) : 0.0f;
-    }
-    // no graph while the profiler is on (per-launch events) or before the first forward of (cloud, model), which computes the
-    // xyz branch: a capture would either bake it in or, replayed after a new cloud, skip it
-    const bool plain = a->ws->prof.on || a->ws->xyz_branch_model != a->model->gen;
-    return nu_graph_window(plain ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, total, a->adam_t0 - 1, a->adam_t0 - 1, a->lr,
-                           0.9f, 0.999f, (hipStream_t)stream, [&](const float *rows) { return rla_nu_window_steps(a, rows, stream); }, lr_rows);
-}
-
-// ---- TBIM / tar_NBattack (bim.py:277-505) on G clouds in lockstep.  blockIdx.y = cloud (blockIdx.x for the one-workgroup-per-
-// cloud kernels); a cloud that is not running is skipped by whole workgroups.  The update is psg_rla_bim_step's, expression for
-// expression, with the cloud's own norms; the latch has TBIM.batch_attack's ordering: the exit is decided on the forward BEFORE
-// the iteration's update, the leaving cloud still takes that update, and only then are its colours snapshot and it is retired.
-namespace {
-// sq_norm_kernel for the running clouds only: the same strides, the same double accumulation, the same tree
-__global__ __launch_bounds__(1024) void sq_norm_clouds_kernel(const float *__restrict__ a, int ld, int c0, size_t nc,
-                                                              const uint8_t *__restrict__ running, float *__restrict__ out)
-{
-    __shared__ double s_part[16];
-    if (running && !running[blockIdx.x]) return;
-    const float *p = a + (size_t)blockIdx.x * nc * ld;
-    double s = 0.0;
-    for (size_t t = threadIdx.x; t < nc * 3; t += blockDim.x) {
-        const float v = p[(t / 3) * ld + c0 + (t % 3)];
-        s += (double)v * (double)v;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_part[w];
-        out[blockIdx.x] = (float)tot;
-    }
-}
-
-__global__ void bim_linf_clouds_kernel(float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ ori,
-                                       const uint8_t *__restrict__ running, size_t n, float alpha, float eps)
-{
-    const int cl = blockIdx.y;
-    if (running && !running[cl]) return;
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const size_t i = (size_t)cl * n + t / 3;
-    const int c = (int)(t % 3);
-    t += (size_t)cl * n * 3;
-    const float g = dfeat[i * 6 + 3 + c], x = ori[t];
-    const float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
-    float v = feat[i * 6 + 3 + c] + alpha * sg;
-    v = fminf(fmaxf(v, x - eps), x + eps);
-    feat[i * 6 + 3 + c] = fminf(fmaxf(v, 0.0f), 1.0f);
-}
-
-__global__ void bim_l2_delta_clouds_kernel(const float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ ori,
-                                           const uint8_t *__restrict__ running, size_t n, float alpha,
-                                           const float *__restrict__ gnorm2, float *__restrict__ delta)
-{
-    const int cl = blockIdx.y;
-    if (running && !running[cl]) return;
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const size_t i = (size_t)cl * n + t / 3;
-    const int c = (int)(t % 3);
-    t += (size_t)cl * n * 3;
-    const float gn = fmaxf(1e-12f, sqrtf(gnorm2[cl]));
-    delta[t] = feat[i * 6 + 3 + c] - ori[t] + alpha * (dfeat[i * 6 + 3 + c] / gn);
-}
-
-__global__ void bim_l2_apply_clouds_kernel(float *__restrict__ feat, const float *__restrict__ ori, const float *__restrict__ delta,
-                                           const uint8_t *__restrict__ running, size_t n, float eps, const float *__restrict__ dnorm2)
-{
-    const int cl = blockIdx.y;
-    if (running && !running[cl]) return;
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 3) return;
-    const size_t i = (size_t)cl * n + t / 3;
-    const int c = (int)(t % 3);
-    t += (size_t)cl * n * 3;
-    const float dn = sqrtf(dnorm2[cl]);
-    const float scale = dn > eps ? eps / dn : 1.0f;
-    feat[i * 6 + 3 + c] = fminf(fmaxf(ori[t] + delta[t] * scale, 0.0f), 1.0f);
-}
-
-// TBIM latch, second half (the first is nu_latch_count_kernel): every workgroup of a live cloud adds the cloud's counts and
-// takes the exit decision (integers); a leaving cloud (or, final, every live one) gets its slice of out_pred; workgroup 0 writes
-// the history row, the statistics, exit_step and the leaving byte.  `active` is read by nobody here and written by nobody.
-__global__ __launch_bounds__(256) void tbim_latch_commit_kernel(const int32_t *__restrict__ pred, const int32_t *__restrict__ n_mask,
-                                                                const int32_t *__restrict__ scratch, int n, int num, int den, int it_arg,
-                                                                int final, const float *__restrict__ consts, float *__restrict__ hist_row,
-                                                                int32_t *__restrict__ out_pred, float *__restrict__ out_stats,
-                                                                uint8_t *__restrict__ leaving, int32_t *__restrict__ exit_step)
-{
-    const int g = blockIdx.y, parts = gridDim.x;
-    const int32_t *sc = scratch + (size_t)g * (2 * parts + 1);
-    if (!sc[0]) return;
-    const int it = consts ? __builtin_bit_cast(int, consts[0]) : it_arg;
-    int nc = 0, nh = 0;
-    for (int p = 0; p < parts; ++p) { nc += sc[1 + 2 * p]; nh += sc[2 + 2 * p]; }
-    const bool exits = it >= 1 && (long long)den * nh > (long long)num * n_mask[g];
-    if (exits || final) {
-        const int chunk = (n + parts - 1) / parts;
-        const int lo = min(n, (int)blockIdx.x * chunk), hi = min(n, lo + chunk);
-        for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-            const size_t r = (size_t)g * n + i;
-            out_pred[r] = pred[r];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const float row[3] = {(float)nc, (float)nh, 0.0f};
-        for (int k = 0; k < 3; ++k) hist_row[g * 3 + k] = row[k];
-        if (exits || final)
-            for (int k = 0; k < 3; ++k) out_stats[g * 3 + k] = row[k];
-        if (exits) exit_step[g] = it;
-        leaving[g] = exits ? 1 : 0;
-    }
-}
-
-// one workgroup per cloud: the flags are read before anything is written, the colours copied, then the flags cleared
-__global__ __launch_bounds__(1024) void tbim_retire_kernel(const float *__restrict__ feat, size_t n, int final, float *__restrict__ out_adv,
-                                                           uint8_t *__restrict__ active, uint8_t *__restrict__ leaving)
-{
-    const int g = blockIdx.x;
-    const bool go = active[g] != 0 && (leaving[g] != 0 || final != 0);
-    __syncthreads();
-    if (!go) return;
-    const size_t base = (size_t)g * n;
-    for (size_t t = threadIdx.x; t < n * 3; t += blockDim.x) out_adv[base * 3 + t] = feat[(base + t / 3) * 6 + 3 + (t % 3)];
-    if (threadIdx.x == 0) { active[g] = 0; leaving[g] = 0; }
-}
-}  // namespace
-
-extern "C" int psg_rla_bim_step_clouds(float *feat, const float *dfeat, const float *ori, const uint8_t *running, int G, int n, float eps,
-                                       float alpha, int l2_metric, float *norms, float *delta, psg_stream stream)
-{
-    PSG_REQUIRE(feat && dfeat && ori && (!l2_metric || (norms && delta)), "psg_rla_bim_step_clouds: null argument");
-    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_bim_step_clouds: G=%d n=%d out of range", G, n);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t N = (size_t)n;
-    const dim3 grid(blocks_for(N * 3), G);
-    if (!l2_metric) {
-        hipLaunchKernelGGL(bim_linf_clouds_kernel, grid, dim3(256), 0, st, feat, dfeat, ori, running, N, alpha, eps);
-        PSG_LAUNCH_CHECK();
-        return PSG_OK;
-    }
-    hipLaunchKernelGGL(sq_norm_clouds_kernel, dim3(G), dim3(1024), 0, st, dfeat, 6, 3, N, running, norms);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bim_l2_delta_clouds_kernel, grid, dim3(256), 0, st, (const float *)feat, dfeat, ori, running, N, alpha,
-                       (const float *)norms, delta);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sq_norm_clouds_kernel, dim3(G), dim3(1024), 0, st, (const float *)delta, 3, 0, N, running, norms + G);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bim_l2_apply_clouds_kernel, grid, dim3(256), 0, st, feat, ori, (const float *)delta, running, N, eps,
-                       (const float *)(norms + G));
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-extern "C" int psg_rla_tbim_latch_clouds(const float *logits, const int32_t *labels, const int32_t *hit_ys, const uint8_t *mask,
-                                         const int32_t *n_mask, int G, int n, int num, int den, int it, int final, float *hist_row,
-                                         int32_t *pred, int32_t *out_pred, float *out_stats, const uint8_t *active, uint8_t *leaving,
-                                         int32_t *exit_step, int32_t *scratch, psg_stream stream)
-{
-    PSG_REQUIRE(logits && labels && hit_ys && hist_row && pred && out_pred && out_stats && active && leaving && exit_step && scratch,
-                "psg_rla_tbim_latch_clouds: null argument");
-    PSG_REQUIRE(mask && n_mask, "psg_rla_tbim_latch_clouds: mask and n_mask are required");
-    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_tbim_latch_clouds: G=%d n=%d out of range", G, n);
-    PSG_REQUIRE(num >= 0 && den > 0 && it >= 0, "psg_rla_tbim_latch_clouds: num=%d den=%d it=%d out of range", num, den, it);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(nu_latch_count_kernel, dim3(kNuParts, G), dim3(256), 0, st, logits, labels, hit_ys, mask, active, n, pred, scratch);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tbim_latch_commit_kernel, dim3(kNuParts, G), dim3(256), 0, st, (const int32_t *)pred, n_mask,
-                       (const int32_t *)scratch, n, num, den, it, final, psg::nu_step_consts(), hist_row, out_pred, out_stats, leaving,
-                       exit_step);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-extern "C" int psg_rla_tbim_retire_clouds(const float *feat, int G, int n, int final, float *out_adv, uint8_t *active, uint8_t *leaving,
-                                          psg_stream stream)
-{
-    PSG_REQUIRE(feat && out_adv && active && leaving, "psg_rla_tbim_retire_clouds: null argument");
-    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_tbim_retire_clouds: G=%d n=%d out of range", G, n);
-    hipLaunchKernelGGL(tbim_retire_kernel, dim3(G), dim3(1024), 0, (hipStream_t)stream, feat, (size_t)n, final, out_adv, active, leaving);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
-}
-
-// One step sequence of a TBIM window, shared by the eager and the captured path; rows: the window's step-constant device rows
-// {iteration index, -, -, -} or null.  Everything in it is a launch on `stream`: a single chain.
-static int rla_tbim_window_steps(const psg_rla_tbim_window_args *a, const float *rows, psg_stream stream)
-{
-    const int G = a->G, N = a->N;
-    int rc = PSG_OK;
-    for (int i = 0; i < a->n_steps && rc == PSG_OK; ++i) {
-        const int final = (a->final && i == a->n_steps - 1) ? 1 : 0;
-        if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
-        psg::nu_set_step_consts(rows ? rows + 4 * i : nullptr);
-        rc = psg_rla_tbim_latch_clouds(a->logits, a->labels, a->hit_ys, a->mask, a->n_mask, G, N, a->num, a->den, a->it0 + i, final,
-                                       a->hist + (size_t)i * 3 * G, a->pred, a->out_pred, a->out_stats, a->active, a->leaving, a->exit_step,
-                                       a->scratch, stream);
-        psg::nu_set_step_consts(nullptr);
-        if (rc == PSG_OK && (rc = psg_rla_colper_grad_masked(a->logits, a->loss_ys, a->mask, a->sign, G * N, a->dlogits, nullptr, stream)) == PSG_OK &&
-            (rc = psg_rla_backward(a->model, a->ws, a->dlogits, a->dfeat, stream)) == PSG_OK &&
-            (rc = psg_rla_bim_step_clouds(a->feat, a->dfeat, a->ori, a->active, G, N, a->eps, a->alpha, a->l2_metric, a->norms, a->delta,
-                                          stream)) == PSG_OK)
-            rc = psg_rla_tbim_retire_clouds(a->feat, G, N, final, a->out_adv, a->active, a->leaving, stream);
-    }
-    psg::nu_set_step_consts(nullptr);
-    return rc;
-}
-
-extern "C" int psg_rla_tbim_window(const psg_rla_tbim_window_args *a, psg_nu_graph *graph, psg_stream stream)
-{
-    PSG_REQUIRE(a && a->model && a->ws && a->ori && a->labels && a->hit_ys && a->loss_ys && a->feat && a->logits && a->dlogits && a->dfeat &&
-                    a->pred && a->scratch && a->hist && a->out_adv && a->out_pred && a->out_stats && a->active && a->leaving && a->exit_step,
-                "psg_rla_tbim_window: null argument");
-    PSG_REQUIRE(a->mask && a->n_mask, "psg_rla_tbim_window: mask and n_mask are required");
-    PSG_REQUIRE(!a->l2_metric || (a->norms && a->delta), "psg_rla_tbim_window: the l_2 metric needs norms and delta");
-    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->Nc, "psg_rla_tbim_window: the workspace is for %d clouds of %d points, the window for %d of %d",
-                a->ws->B, a->ws->Nc, a->G, a->N);
-    PSG_REQUIRE(a->n_steps >= 1 && a->n_steps <= PSG_NU_GRAPH_MAX_STEPS, "psg_rla_tbim_window: n_steps=%d outside 1..%d", a->n_steps,
-                PSG_NU_GRAPH_MAX_STEPS);
-    PSG_REQUIRE(a->it0 >= 0, "psg_rla_tbim_window: it0=%d (the first iteration is 0)", a->it0);
-    PSG_REQUIRE(a->num >= 0 && a->den > 0, "psg_rla_tbim_window: threshold %d / %d out of range", a->num, a->den);
-    if (!a->ws->cloud_set) { set_error("psg_rla_tbim_window: psg_rla_set_cloud has not been called"); return PSG_ERR_STATE; }
-    ProfBind bind(a->ws);
-    // what a captured window is valid for: the argument block (padding bytes as the caller holds them) without what the device
-    // rows carry
-    psg_rla_tbim_window_args key;
-    memcpy(&key, a, sizeof(key));
-    key.it0 = 0;
-    // no graph while the profiler is on (per-launch events) or before the first forward of (cloud, model), which computes the
-    // xyz branch: a capture would either bake it in or, replayed after a new cloud, skip it
-    const bool plain = a->ws->prof.on || a->ws->xyz_branch_model != a->model->gen;
-    return nu_graph_window(plain ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, a->n_steps, a->it0, a->it0, 0.0f, 0.9f, 0.999f,
-                           (hipStream_t)stream, [&](const float *rows) { return rla_tbim_window_steps(a, rows, stream); });
 }

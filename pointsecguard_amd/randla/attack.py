@@ -34,6 +34,91 @@ from pointsecguard_amd.randla import network
 _FIELD_ONLY = ("field=%r: the coordinate field runs in BIM / NBattack / TBIM / tar_NBattack.batch_attack with batch_size == 1 "
                "(one cloud per call); %s moves colours only")
 
+CHUNK = 10  # optimiser steps per device-side window (the CHUNK of the other networks' NU attacks)
+
+
+def _features(features, clouds=None, device=True):
+    """features (tensor or numpy) -> float32 device tensor (device=False: a tensor where it is); clouds False: [N, 6] of one
+    cloud, True: [G, N, 6], None: either (the caller checks).  A bad shape is refused before any device work."""
+    f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
+    if clouds is False and (f.dim() != 2 or f.shape[1] != 6):
+        raise ValueError("features must be [N, 6] (xyz, rgb) of one cloud, got %s" % (tuple(f.shape),))
+    if clouds and (f.dim() != 3 or f.shape[2] != 6 or f.shape[0] < 1):
+        raise ValueError("features must be [G, N, 6] (xyz, rgb) of G >= 1 clouds, got %s" % (tuple(f.shape),))
+    return f.float().cuda().contiguous() if device else f
+
+
+def _labels(labels, host=None):
+    """labels (tensor or numpy) -> int32 device tensor, or (host = a numpy dtype) a host array of that type"""
+    if host is not None:
+        return (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(host)
+    y = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
+    return y.to(torch.int32).cuda().contiguous()
+
+
+_SETTINGS = {"magnitude": "eps", "alpha": "alpha", "cs": "cs", "rand_init_magnitude": "rand_init_eps",
+             # the coordinate field's own (eps, alpha); unset, they follow magnitude / alpha
+             "coord_magnitude": "coord_eps", "coord_alpha": "coord_alpha"}
+
+
+def _config(atk, kwargs, *names):
+    """Takes from kwargs the settings in `names` that it gives: iteration as int, logger as it is, the others as floats (the
+    reference passes numbers or 1-element arrays)."""
+    for name in names:
+        if name not in kwargs:
+            continue
+        if name == "iteration":
+            atk.iteration = int(kwargs[name])
+        elif name == "logger":
+            atk.logger = kwargs[name]
+        else:
+            setattr(atk, _SETTINGS[name], float(np.asarray(kwargs[name]).reshape(-1)[0]))
+
+
+def _mean_iou(pred, true):
+    """compute_iou of the reference's attack classes (bim.py:153-165)."""
+    pred, true = np.asarray(pred).ravel(), np.asarray(true).ravel()
+    iou = []
+    for l in np.unique(np.concatenate([pred, true])):
+        inter = np.sum((pred == l) & (true == l))
+        iou.append(inter / np.float32(np.sum(true == l) + np.sum(pred == l) - inter))
+    return float(np.mean(iou))
+
+
+def _targeted_out(logger, pred, pred0, lab, ys_target, mask_h, new_dists):
+    """One cloud's tuple of the targeted attacks (bim.py:508), logged: (target_points, sr, other_acc, original_other_accuracy,
+    new_dists, other_mIoU, original_other_mIoU) from the last prediction, the clean one, the labels, the target labels and the
+    origin-class mask [N]."""
+    n, tp = lab.shape[0], float(mask_h.sum())
+    out = (tp, float(np.sum(pred[mask_h] == ys_target[mask_h]) / tp), float(np.sum(pred[~mask_h] == ys_target[~mask_h]) / (n - tp)),
+           float(np.sum(pred0[~mask_h] == lab[~mask_h]) / (n - tp)), new_dists, _mean_iou(pred[~mask_h], lab[~mask_h]),
+           _mean_iou(pred0[~mask_h], lab[~mask_h]))
+    if logger is not None:
+        logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
+                    "original_other_mIoU={}".format(*out))
+    return out
+
+
+def _untargeted_out(logger, pred, pred0, rpred, lab, new_dists):
+    """One cloud's tuple of NUattack (NUattack.py:233), logged: (acc, original_accuracy, new_dists, mIoU, original_mIoU,
+    rand_acc, rand_mIoU) from the last prediction, the clean one and the one under random noise of the same size."""
+    n = lab.shape[0]
+    out = (float(np.sum(pred == lab) / n), float(np.sum(pred0 == lab) / n), new_dists, _mean_iou(pred, lab), _mean_iou(pred0, lab),
+           float(np.sum(rpred == lab) / n), _mean_iou(rpred, lab))
+    if logger is not None:
+        logger.info("acc={}, original_acc={}, new_dists={}, mIoU={}, original_mIoU={}, rand_acc={}, rand_mIoU={}".format(*out))
+    return out
+
+
+def _origin_points(lab, ori, tester_lines):
+    """mask of the origin class [N] or [G, N]; every cloud needs a point of it"""
+    mask_h = lab == ori
+    empty = np.flatnonzero(mask_h.reshape(-1, mask_h.shape[-1]).sum(1) == 0)
+    if empty.size:
+        where = "this cloud" if lab.ndim == 1 else "cloud(s) %s" % ", ".join(str(g) for g in empty)
+        raise ValueError("no point of the origin class %d in %s (tester_S3DIS.py:%s skips such clouds)" % (ori, where, tester_lines))
+    return mask_h
+
 
 class _FieldState:
     """Device buffers of the coordinate-field loop of one cloud and its full workspace (network.RandLAWorkspace(full=True))."""
@@ -77,43 +162,126 @@ def _field_finish(atk, S, feat):
     S.ws.set_cloud(atk.last_adv_xyz)
 
 
-def _config_coord(atk, kwargs):
-    """coord_magnitude / coord_alpha: the coordinate field's own (eps, alpha); unset, they follow magnitude / alpha"""
-    if "coord_magnitude" in kwargs:
-        atk.coord_eps = float(np.asarray(kwargs["coord_magnitude"]).reshape(-1)[0])
-    if "coord_alpha" in kwargs:
-        atk.coord_alpha = float(np.asarray(kwargs["coord_alpha"]).reshape(-1)[0])
+class _CloudsState:
+    """Device buffers of G clouds of N points attacked in lockstep, their cloud-batch workspace and the graph handle of the
+    full windows (every full window of one call shape has the same argument block).  For TBIM xs are the clean colours, dws the
+    l_2 step's delta, ys the labels of the hinge and hit_ys the labels the hits are counted against."""
+
+    def __init__(self, n, G):
+        self.ws = network.RandLAWorkspace(n, batch=G)
+        dev = self.ws.device
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+        R = G * n
+        self.dws, self.m, self.v = f32(R, 3), f32(R, 3), f32(R, 3)
+        self.xs, self.feat, self.dfeat = f32(R, 3), f32(R, 6), f32(R, 6)
+        self.logits, self.dlogits = f32(R, 13), f32(R, 13)
+        self.labels, self.ys, self.hit_ys, self.pred, self.out_pred = i32(R), i32(R), i32(R), i32(R), i32(R)
+        self.mask = torch.zeros(R, dtype=torch.uint8, device=dev)
+        self.n_mask = i32(G)
+        self.dist2, self.norms, self.out_stats, self.out_adv = f32(G), f32(2, G), f32(G, 3), f32(R, 3)
+        self.partials = torch.zeros(G, _lib.RLA_NU_PARTS, dtype=torch.float64, device=dev)
+        self.scratch = i32(G, 2 * _lib.RLA_NU_PARTS + 1)
+        self.hist = f32(CHUNK + 1, G, 3)
+        self.active, self.leaving = (torch.zeros(G, dtype=torch.uint8, device=dev) for _ in range(2))
+        self.exit = i32(G)
+        # two handles: the full windows, and a full window that is also the last one (it carries the tail evaluation)
+        self.graph, self.graph_tail = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph))
+        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph_tail))
+
+    def __del__(self):
+        try:
+            for g in (self.graph, self.graph_tail):
+                if g:
+                    _lib.load().psg_nu_graph_destroy(g)
+        except Exception:
+            pass
 
 
-class BIM:
+def _bind(win, S, fields):
+    """pointers of the state's tensors into the argument block: `fields` = block field names, `field=attribute` where the
+    state calls the tensor otherwise"""
+    for item in fields.split():
+        field, _, attr = item.partition("=")
+        setattr(win, field, getattr(S, attr or field).data_ptr())
+
+
+def _run_windows(entry, win, S, first, cap, chunk, set_window, hook):
+    """The window loop of the lockstep attacks: steps first .. cap in windows of `chunk` (at most CHUNK), the last one cut at
+    the cap, through the library's `entry`.  set_window(first step, steps, last) sets the window's fields of `win` and returns
+    the number of history rows it writes; after the window's one read-back (those rows and the exit steps)
+    hook(first step, steps, last, S, rows [rows, G, 3]) is called; the loop ends after the window in which the last cloud
+    exits.  Only a full CHUNK window gets a graph handle (cut windows run eagerly): S.graph, or S.graph_tail when it is
+    also the last.  -> (the row count of every window, steps taken per cloud [G]: the exit step, or the cap, counted from
+    `first`)."""
+    chunk = max(1, min(int(chunk), CHUNK))
+    G = S.exit.shape[0]
+    exited, rows_run = np.full(G, -1, np.int64), []
+    t0 = first
+    while t0 <= cap:
+        n_run = min(chunk, cap - t0 + 1)
+        last = t0 + n_run - 1 == cap
+        rows = set_window(t0, n_run, last)
+        graph = None if n_run != CHUNK else (S.graph_tail if last else S.graph)
+        _lib.call(entry, ctypes.byref(win), graph, runtime.stream())
+        back = torch.cat([S.hist[:rows].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
+        exited = back[rows * G * 3:].astype(np.int64)
+        rows_run.append(rows)
+        if hook is not None:
+            hook(t0, n_run, last, S, back[:rows * G * 3].reshape(rows, G, 3))
+        t0 += n_run
+        if (exited >= 0).all():
+            break
+    return rows_run, np.where(exited >= 0, exited, cap) + 1 - first
+
+
+class _Attack:
+    """What the constructors share: the field, the model, the per-shape workspaces."""
+
     step_hook = None        # tests, tools (non-colour fields): called after every iteration with (iteration, features [N, 6])
 
-    def __init__(self, model, batch_size=1, loss="colper", goal="ut", distance_metric="l_inf", session=None,
-                 iteration_callback=None, field="color"):
+    def __init__(self, model, batch_size, field, field_one_cloud=False):
         self.field = check_field(field)
-        if self.field != "color" and batch_size != 1:
+        if field_one_cloud and self.field != "color" and batch_size != 1:
             raise NotImplementedError(_FIELD_ONLY % (field, "batch_size > 1"))
         self.coord_eps = self.coord_alpha = self.last_adv_xyz = self.last_dist_xyz = None
         if not isinstance(model, network.RandLAModel):
             raise TypeError("model must be a pointsecguard_amd.randla.network.RandLAModel")
+        self.model, self.batch_size = model, batch_size
+        self.iteration = None
+        self._ws = {}
+
+    def _field_state(self, n):
+        if ("field", n) not in self._ws:
+            self._ws[("field", n)] = _FieldState(n)
+        return self._ws[("field", n)]
+
+
+class _RandInit:
+    """NBattack.py's `rand_init_magnitude`: accepted and, like there, without effect"""
+
+    rand_init_eps = None
+
+    def config(self, **kwargs):
+        super().config(**kwargs)
+        _config(self, kwargs, "rand_init_magnitude")
+
+
+class BIM(_Attack):
+    def __init__(self, model, batch_size=1, loss="colper", goal="ut", distance_metric="l_inf", session=None,
+                 iteration_callback=None, field="color"):
+        super().__init__(model, batch_size, field, field_one_cloud=True)
         if goal != "ut" or distance_metric not in ("l_inf", "l_2") or iteration_callback is not None:
             raise NotImplementedError("BIM / NBattack: goal='ut', l_inf / l_2 (the targeted attack is TBIM / tar_NBattack)")
         if batch_size < 1:
             raise ValueError("batch_size must be positive")
-        self.model, self.distance_metric, self.batch_size = model, distance_metric, batch_size
+        self.distance_metric = distance_metric
         self.eps = self.alpha = None
-        self.iteration = None
-        self._ws = {}
 
     def config(self, **kwargs):
         """magnitude (max distortion), alpha (step size), iteration (bim.py:118-150)."""
-        if "magnitude" in kwargs:
-            self.eps = float(np.asarray(kwargs["magnitude"]).reshape(-1)[0])
-        if "alpha" in kwargs:
-            self.alpha = float(np.asarray(kwargs["alpha"]).reshape(-1)[0])
-        if "iteration" in kwargs:
-            self.iteration = int(kwargs["iteration"])
-        _config_coord(self, kwargs)
+        _config(self, kwargs, "magnitude", "alpha", "iteration", "coord_magnitude", "coord_alpha")
 
     def batch_attack(self, features, labels):
         """features [N,6] (xyz, rgb) and labels [N] of one cloud - or [batch_size, N, 6] and [batch_size, N] - (device
@@ -121,19 +289,14 @@ class BIM:
         field "coord" / "both" (one cloud): the moved positions are `last_adv_xyz` [N,3], `last_dist_xyz` their l_2 distance."""
         if self.eps is None or self.alpha is None or self.iteration is None:
             raise RuntimeError("call config(magnitude=..., alpha=..., iteration=...) first")
-        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
-        y = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
-        f = f.float().cuda().contiguous()
-        y = y.to(torch.int32).cuda().contiguous()
+        f, y = _features(features), _labels(labels)
         batched = f.dim() == 3
         if batched != (self.batch_size > 1) or (batched and f.shape[0] != self.batch_size):
             raise ValueError("features must be [N,6] for batch_size=1, [batch_size,N,6] otherwise (batch_size=%d, got %s)" %
                              (self.batch_size, tuple(f.shape)))
         n = f.shape[-2]
         if self.field != "color":
-            if ("field", n) not in self._ws:
-                self._ws[("field", n)] = _FieldState(n)
-            S, feat = self._ws[("field", n)], f.clone()
+            S, feat = self._field_state(n), f.clone()
             S.start(feat)
             for it in range(self.iteration + 1):                 # bim.py:204-232, as below
                 _field_iteration(self, S, feat, y, None, 1.0)
@@ -150,50 +313,27 @@ class BIM:
         return rgb.reshape(self.batch_size, n, 3) if batched else rgb
 
 
-def _mean_iou(pred, true):
-    """compute_iou of the reference's attack classes (bim.py:153-165)."""
-    pred, true = np.asarray(pred).ravel(), np.asarray(true).ravel()
-    iou = []
-    for l in np.unique(np.concatenate([pred, true])):
-        inter = np.sum((pred == l) & (true == l))
-        iou.append(inter / np.float32(np.sum(true == l) + np.sum(pred == l) - inter))
-    return float(np.mean(iou))
-
-
-class _StepAttack:
+class _StepAttack(_Attack):
     """Shared plumbing of the host-loop attacks: device buffers of one cloud and the step entry points."""
 
-    step_hook = None        # tests, tools (non-colour fields): called after every iteration with (iteration, features [N, 6])
-
     def __init__(self, model, batch_size=1, field="color"):
-        self.field = check_field(field)
-        self.coord_eps = self.coord_alpha = self.last_adv_xyz = self.last_dist_xyz = None
-        if not isinstance(model, network.RandLAModel):
-            raise TypeError("model must be a pointsecguard_amd.randla.network.RandLAModel")
+        super().__init__(model, batch_size, field)
         if batch_size != 1:
             raise NotImplementedError("one cloud per call (ConfigS3DIS.val_batch_size = 1): the accuracy exits are per cloud")
-        self.model, self.batch_size = model, batch_size
-        self.iteration, self.logger, self.last_adv = None, None, None
-        self._ws = {}
-        self._clouds, self.last_steps = {}, None        # the lockstep NU attacks (batch_attack_clouds)
+        self.logger, self.last_adv = None, None
+        self._clouds, self.last_steps = {}, None        # the lockstep attacks (batch_attack_clouds)
 
     def _setup(self, features, labels, full=False):
-        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
-        y = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
-        f = f.float().cuda().contiguous()
-        if f.dim() != 2 or f.shape[1] != 6:
-            raise ValueError("features must be [N, 6] (xyz, rgb) of one cloud, got %s" % (tuple(f.shape),))
+        f = _features(features, clouds=False)
         n = f.shape[0]
         if full:                                             # the coordinate field: a full workspace and its loop's buffers
-            if ("field", n) not in self._ws:
-                self._ws[("field", n)] = _FieldState(n)
-            ws = self._ws[("field", n)].ws
+            ws = self._field_state(n).ws
         else:
             if n not in self._ws:
                 self._ws[n] = network.RandLAWorkspace(n)
             ws = self._ws[n]
         ws.set_cloud(f[:, 0:3].contiguous())
-        return ws, f.clone(), y.to(torch.int32).cuda().contiguous(), n
+        return ws, f.clone(), _labels(labels), n
 
     @staticmethod
     def _grad(ws, model, feat, ys, mask, sign):
@@ -202,6 +342,21 @@ class _StepAttack:
         _lib.call("psg_rla_colper_grad_masked", runtime.ptr(logits), runtime.ptr(ys), None if mask is None else runtime.ptr(mask),
                   float(sign), logits.shape[0], runtime.ptr(dlogits), None, runtime.stream())
         return logits, ws.backward(model, dlogits)
+
+    def _start_clouds(self, f):
+        """The lockstep state of f [G, N, 6] (built on the shape's first use) with the clouds loaded, every cloud active, and the
+        clean prediction [G, N]."""
+        G, n = int(f.shape[0]), int(f.shape[1])
+        if (n, G) not in self._clouds:
+            self._clouds[(n, G)] = _CloudsState(n, G)
+        S = self._clouds[(n, G)]
+        S.feat.copy_(f.reshape(G * n, 6))
+        S.xs.copy_(S.feat[:, 3:6])                       # the clean colours
+        S.ws.set_cloud(S.feat[:, 0:3].contiguous())
+        pred0 = S.ws.forward(self.model, S.feat).argmax(1).cpu().numpy().reshape(G, n)
+        S.active.fill_(1)
+        S.exit.fill_(-1)
+        return S, pred0
 
 
 class TBIM(_StepAttack):
@@ -219,15 +374,7 @@ class TBIM(_StepAttack):
         self.eps = self.alpha = None
 
     def config(self, **kwargs):
-        if "magnitude" in kwargs:
-            self.eps = float(np.asarray(kwargs["magnitude"]).reshape(-1)[0])
-        if "alpha" in kwargs:
-            self.alpha = float(np.asarray(kwargs["alpha"]).reshape(-1)[0])
-        if "iteration" in kwargs:
-            self.iteration = int(kwargs["iteration"])
-        if "logger" in kwargs:
-            self.logger = kwargs["logger"]
-        _config_coord(self, kwargs)
+        _config(self, kwargs, "magnitude", "alpha", "iteration", "logger", "coord_magnitude", "coord_alpha")
 
     def batch_attack(self, features, labels, target=None, ori=2):
         """-> (target_points, sr, other_acc, original_other_accuracy, new_dists, other_mIoU, original_other_mIoU),
@@ -236,14 +383,12 @@ class TBIM(_StepAttack):
         if self.eps is None or self.alpha is None or self.iteration is None:
             raise RuntimeError("call config(magnitude=..., alpha=..., iteration=...) first")
         ws, feat, y, n = self._setup(features, labels, full=self.field != "color")
-        S = self._ws[("field", n)] if self.field != "color" else None
+        S = self._field_state(n) if self.field != "color" else None
         if S is not None:
             S.start(feat)
         lab = y.cpu().numpy()
-        mask_h = lab == ori
+        mask_h = _origin_points(lab, ori, "311-314")
         target_points = float(mask_h.sum())
-        if target_points == 0:
-            raise ValueError("no point of the origin class %d in this cloud (tester_S3DIS.py:311-314 skips such clouds)" % ori)
         ys_target = np.where(mask_h, target, lab).astype(np.int32)
         targeted = self.goal in ("t", "tm")
         ys = torch.from_numpy(ys_target if targeted else lab.astype(np.int32)).cuda()
@@ -251,10 +396,7 @@ class TBIM(_StepAttack):
         ori_rgb = feat[:, 3:6].contiguous()
         norms = torch.zeros(2, dtype=torch.float32, device=feat.device)
         delta = torch.empty(n, 3, dtype=torch.float32, device=feat.device)
-        pred0 = ws.forward(self.model, feat).argmax(1).cpu().numpy()
-        original_other_accuracy = float(np.sum(pred0[~mask_h] == lab[~mask_h]) / (n - target_points))
-        original_other_miou = _mean_iou(pred0[~mask_h], lab[~mask_h])
-        sr = other_acc = other_miou = 0.0
+        pred = pred0 = ws.forward(self.model, feat).argmax(1).cpu().numpy()
         # bim.py:470-482 runs the update once before the loop; its result is the loop's starting point
         for it in range(self.iteration + 1):
             if S is not None:                                # the coordinate field: gradient and update(s) in one go
@@ -263,8 +405,6 @@ class TBIM(_StepAttack):
                 logits, dfeat = self._grad(ws, self.model, feat, ys, mask, -1.0 if targeted else 1.0)
             pred = logits.argmax(1).cpu().numpy()            # the one read-back of the iteration (the reference's session.run)
             sr = float(np.sum(pred[mask_h] == ys_target[mask_h]) / target_points)
-            other_acc = float(np.sum(pred[~mask_h] == ys_target[~mask_h]) / (n - target_points))
-            other_miou = _mean_iou(pred[~mask_h], lab[~mask_h])
             if S is None:
                 _lib.call("psg_rla_bim_step", runtime.ptr(feat), runtime.ptr(dfeat), runtime.ptr(ori_rgb), n, self.eps, self.alpha,
                           1 if self.distance_metric == "l_2" else 0, runtime.ptr(norms), runtime.ptr(delta), runtime.stream())
@@ -276,11 +416,7 @@ class TBIM(_StepAttack):
             _field_finish(self, S, feat)
         self.last_adv = feat[:, 3:6].contiguous()
         new_dists = float(torch.linalg.vector_norm(self.last_adv - ori_rgb))
-        out = (target_points, sr, other_acc, original_other_accuracy, new_dists, other_miou, original_other_miou)
-        if self.logger is not None:
-            self.logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
-                             "original_other_mIoU={}".format(*out))
-        return out
+        return _targeted_out(self.logger, pred, pred0, lab, ys_target, mask_h, new_dists)
 
     # the lockstep form: the exit `hits / points > 0.90` as an integer ratio, steps per window, the tests' and tools' hook
     EXIT_RATIO = (9, 10)
@@ -301,30 +437,16 @@ class TBIM(_StepAttack):
             raise ValueError("iteration must be positive")
         if target is None:
             raise ValueError("target: the class the points of class `ori` are pushed to")
-        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
-        if f.dim() != 3 or f.shape[2] != 6 or f.shape[0] < 1:
-            raise ValueError("features must be [G, N, 6] (xyz, rgb) of G >= 1 clouds, got %s" % (tuple(f.shape),))
+        f = _features(features, clouds=True, device=False)
         G, n = int(f.shape[0]), int(f.shape[1])
-        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int32)
+        lab = _labels(labels, np.int32)
         if lab.shape != (G, n):
             raise ValueError("labels must be [G, N] = %s, got %s" % ((G, n), lab.shape))
-        mask_h = lab == ori
-        target_points = mask_h.sum(1).astype(np.float64)
-        if (target_points == 0).any():
-            raise ValueError("no point of the origin class %d in cloud(s) %s (tester_S3DIS.py:311-314 skips such clouds)" %
-                             (ori, ", ".join(str(g) for g in np.flatnonzero(target_points == 0))))
+        mask_h = _origin_points(lab, ori, "311-314")
+        f = f.float().cuda().contiguous()
         ys_target = np.where(mask_h, target, lab).astype(np.int32)
         targeted = self.goal in ("t", "tm")
-        f = f.float().cuda().contiguous()
-        key = (n, G)
-        if key not in self._clouds:
-            self._clouds[key] = _TbimCloudsState(n, G)
-        S = self._clouds[key]
-        ws = S.ws
-        S.feat.copy_(f.reshape(G * n, 6))
-        S.xs.copy_(S.feat[:, 3:6])                       # the clean colours
-        ws.set_cloud(S.feat[:, 0:3].contiguous())
-        pred0 = ws.forward(self.model, S.feat).argmax(1).cpu().numpy().reshape(G, n)
+        S, pred0 = self._start_clouds(f)
         S.labels.copy_(torch.from_numpy(lab.reshape(-1)))
         S.hit_ys.copy_(torch.from_numpy(ys_target.reshape(-1)))
         S.ys.copy_(torch.from_numpy((ys_target if targeted else lab).reshape(-1)))       # the labels of the hinge
@@ -332,54 +454,28 @@ class TBIM(_StepAttack):
         S.n_mask.copy_(torch.from_numpy(mask_h.sum(1).astype(np.int32)))
         for t in (S.norms, S.out_stats, S.out_adv, S.out_pred, S.leaving):
             t.zero_()
-        S.active.fill_(1)
-        S.exit.fill_(-1)
         win = _lib.RlaTbimWindowArgs()
-        win.model, win.ws = self.model.handle, ws.handle
+        win.model, win.ws = self.model.handle, S.ws.handle
         win.G, win.N, win.l2_metric = G, n, 1 if self.distance_metric == "l_2" else 0
         win.num, win.den = int(self.EXIT_RATIO[0]), int(self.EXIT_RATIO[1])
         win.eps, win.alpha, win.sign = self.eps, self.alpha, -1.0 if targeted else 1.0
-        for name, t in (("ori", S.xs), ("mask", S.mask), ("n_mask", S.n_mask), ("labels", S.labels), ("hit_ys", S.hit_ys),
-                        ("loss_ys", S.ys), ("feat", S.feat), ("logits", S.logits), ("dlogits", S.dlogits), ("dfeat", S.dfeat),
-                        ("norms", S.norms), ("delta", S.dws), ("pred", S.pred), ("scratch", S.scratch), ("hist", S.hist),
-                        ("out_adv", S.out_adv), ("out_pred", S.out_pred), ("out_stats", S.out_stats), ("active", S.active),
-                        ("leaving", S.leaving), ("exit_step", S.exit)):
-            setattr(win, name, t.data_ptr())
-        chunk = max(1, min(int(self.chunk), CHUNK))
-        exited = np.full(G, -1, np.int64)
-        it0 = 0
-        while it0 <= self.iteration:                     # iterations 0 .. iteration (bim.py:470-482: one update before the loop)
-            n_run = min(chunk, self.iteration - it0 + 1)
-            final = it0 + n_run - 1 == self.iteration     # the cap: its last step snapshots the clouds still running
+        _bind(win, S, "ori=xs mask n_mask labels hit_ys loss_ys=ys feat logits dlogits dfeat norms delta=dws pred scratch hist "
+                      "out_adv out_pred out_stats active leaving exit_step=exit")
+
+        def set_window(it0, n_run, final):               # final, the cap: its last step snapshots the clouds still running
             win.n_steps, win.it0, win.final = n_run, it0, 1 if final else 0
-            graph = None if n_run != CHUNK else (S.graph_tail if final else S.graph)      # cut windows run eagerly
-            _lib.call("psg_rla_tbim_window", ctypes.byref(win), graph, runtime.stream())
-            back = torch.cat([S.hist[:n_run].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
-            exited = back[n_run * G * 3:].astype(np.int64)
-            if self.window_hook is not None:
-                self.window_hook(it0, n_run, final, S, back[:n_run * G * 3].reshape(n_run, G, 3))
-            it0 += n_run
-            if (exited >= 0).all():
-                break
+            return n_run
+
+        # iterations 0 .. iteration (bim.py:470-482: one update before the loop)
+        _, self.last_steps = _run_windows("psg_rla_tbim_window", win, S, 0, self.iteration, self.chunk, set_window, self.window_hook)
         self.last_adv = S.out_adv.reshape(G, n, 3).clone()
-        self.last_steps = np.where(exited >= 0, exited, self.iteration) + 1
         pred = S.out_pred.cpu().numpy().reshape(G, n)
         ori_rgb = S.xs.reshape(G, n, 3)
-        outs = []
-        for g in range(G):
-            mk, tp = mask_h[g], float(target_points[g])
-            new_dists = float(torch.linalg.vector_norm(self.last_adv[g] - ori_rgb[g]))
-            out = (tp, float(np.sum(pred[g][mk] == ys_target[g][mk]) / tp), float(np.sum(pred[g][~mk] == ys_target[g][~mk]) / (n - tp)),
-                   float(np.sum(pred0[g][~mk] == lab[g][~mk]) / (n - tp)), new_dists, _mean_iou(pred[g][~mk], lab[g][~mk]),
-                   _mean_iou(pred0[g][~mk], lab[g][~mk]))
-            if self.logger is not None:
-                self.logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
-                                 "original_other_mIoU={}".format(*out))
-            outs.append(out)
-        return outs
+        return [_targeted_out(self.logger, pred[g], pred0[g], lab[g], ys_target[g], mask_h[g],
+                              float(torch.linalg.vector_norm(self.last_adv[g] - ori_rgb[g]))) for g in range(G)]
 
 
-class NBattack(BIM):
+class NBattack(_RandInit, BIM):
     """NBattack.py:8-48: BIM plus a `rand_init_magnitude` setting.  The reference computes the random start point but never
     assigns it (`setup_xs` still assigns the clean colours, NBattack.py:27-29), so the attack IS BIM; the setting is
     accepted and, like there, has no effect."""
@@ -387,77 +483,10 @@ class NBattack(BIM):
     def __init__(self, model, batch_size=1, loss="colper", goal="ut", distance_metric="l_2", session=None, iteration_callback=None,
                  field="color"):
         super().__init__(model, batch_size, loss, goal, distance_metric, session, iteration_callback, field)
-        self.rand_init_eps = None
-
-    def config(self, **kwargs):
-        super().config(**kwargs)
-        if "rand_init_magnitude" in kwargs:
-            self.rand_init_eps = float(np.asarray(kwargs["rand_init_magnitude"]).reshape(-1)[0])
 
 
-class tar_NBattack(TBIM):
+class tar_NBattack(_RandInit, TBIM):
     """NBattack.py:53-65: TBIM plus the same unused `rand_init_magnitude` setting."""
-
-    def __init__(self, model, batch_size=1, loss="colper", goal="t", distance_metric="l_2", session=None, iteration_callback=None,
-                 field="color"):
-        super().__init__(model, batch_size, loss, goal, distance_metric, session, iteration_callback, field)
-        self.rand_init_eps = None
-
-    def config(self, **kwargs):
-        super().config(**kwargs)
-        if "rand_init_magnitude" in kwargs:
-            self.rand_init_eps = float(np.asarray(kwargs["rand_init_magnitude"]).reshape(-1)[0])
-
-
-CHUNK = 10  # optimiser steps per device-side window (the CHUNK of the other networks' NU attacks)
-
-
-class _CloudsState:
-    """Device buffers of G clouds of N points attacked in lockstep, their cloud-batch workspace and the graph handle of the
-    full windows (every full window of one call shape has the same argument block)."""
-
-    def __init__(self, n, G):
-        self.ws = network.RandLAWorkspace(n, batch=G)
-        dev = self.ws.device
-        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
-        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-        R = G * n
-        self.dws, self.m, self.v = f32(R, 3), f32(R, 3), f32(R, 3)
-        self.xs, self.feat, self.dfeat = f32(R, 3), f32(R, 6), f32(R, 6)
-        self.logits, self.dlogits = f32(R, 13), f32(R, 13)
-        self.labels, self.ys, self.pred, self.out_pred = i32(R), i32(R), i32(R), i32(R)
-        self.mask = torch.zeros(R, dtype=torch.uint8, device=dev)
-        self.n_mask = i32(G)
-        self.dist2, self.out_stats, self.out_adv = f32(G), f32(G, 3), f32(R, 3)
-        self.partials = torch.zeros(G, _lib.RLA_NU_PARTS, dtype=torch.float64, device=dev)
-        self.scratch = i32(G, 2 * _lib.RLA_NU_PARTS + 1)
-        self.hist = f32(CHUNK + 1, G, 3)
-        self.active = torch.zeros(G, dtype=torch.uint8, device=dev)
-        self.exit = i32(G)
-        # two handles: the full windows, and a full window that is also the last one (it carries the tail evaluation)
-        self.graph, self.graph_tail = ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph))
-        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph_tail))
-
-    def __del__(self):
-        try:
-            for g in (self.graph, self.graph_tail):
-                if g:
-                    _lib.load().psg_nu_graph_destroy(g)
-        except Exception:
-            pass
-
-
-class _TbimCloudsState(_CloudsState):
-    """The same buffers for TBIM.batch_attack_clouds (xs: the clean colours, dws: the l_2 step's delta, ys: the labels of the
-    hinge; graph_tail: a full window that is also the last) plus what only TBIM needs."""
-
-    def __init__(self, n, G):
-        super().__init__(n, G)
-        dev = self.ws.device
-        self.hit_ys = torch.zeros(G * n, dtype=torch.int32, device=dev)      # the labels the hits are counted against
-        self.norms = torch.zeros(2, G, dtype=torch.float32, device=dev)
-        self.leaving = torch.zeros(G, dtype=torch.uint8, device=dev)
 
 
 class NUattack(_StepAttack):
@@ -476,12 +505,7 @@ class NUattack(_StepAttack):
         self.lr, self.cs, self.iteration = float(learning_rate), 1.0, 1000
 
     def config(self, **kwargs):
-        if "cs" in kwargs:
-            self.cs = float(np.asarray(kwargs["cs"]).reshape(-1)[0])
-        if "iteration" in kwargs:
-            self.iteration = int(kwargs["iteration"])
-        if "logger" in kwargs:
-            self.logger = kwargs["logger"]
+        _config(self, kwargs, "cs", "iteration", "logger")
 
     def _run(self, features, labels, ys_h, mask_h, stop):
         ws, feat, y, n = self._setup(features, labels)
@@ -511,47 +535,39 @@ class NUattack(_StepAttack):
 
     def batch_attack(self, features, labels):
         """-> (acc, original_accuracy, new_dists, mIoU, original_mIoU, rand_acc, rand_mIoU), NUattack.py:233."""
-        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64)
+        lab = _labels(labels, np.int64)
         st = self._run(features, labels, lab, None, lambda s: s["correct"] / s["n"] < 1 / 13)
-        n, pred = st["n"], st["pred"].cpu().numpy()
-        acc, miou = float(np.sum(pred == lab) / n), _mean_iou(pred, lab)
-        original_accuracy, original_miou = float(np.sum(st["pred0"] == lab) / n), _mean_iou(st["pred0"], lab)
-        # random noise of the same l_2 size (NUattack.py:236-252); numpy's global generator, like the reference
-        noise = np.random.uniform(0, 1, size=(n, 3))
-        noise = noise / np.linalg.norm(noise) * st["dist"]
-        rnd = st["feat"].clone()
-        rnd[:, 3:6] = torch.clamp(st["xs"] + torch.from_numpy(noise.astype(np.float32)).cuda(), 0, 1)
-        rpred = st["ws"].forward(self.model, rnd).argmax(1).cpu().numpy()
-        out = (acc, original_accuracy, st["dist"], miou, original_miou, float(np.sum(rpred == lab) / n), _mean_iou(rpred, lab))
-        if self.logger is not None:
-            self.logger.info("acc={}, original_acc={}, new_dists={}, mIoU={}, original_mIoU={}, rand_acc={}, rand_mIoU={}".format(*out))
-        return out
+        rpred = self._noise_pred(st["ws"], st["feat"], st["xs"], [st["dist"]], st["n"])[0]
+        return _untargeted_out(self.logger, st["pred"].cpu().numpy(), st["pred0"], rpred, lab, st["dist"])
 
+    def _noise_pred(self, ws, feat, xs, dist, n):
+        """Prediction [G, N] under random noise of the same l_2 size (NUattack.py:236-252): numpy's global generator, like the
+        reference, once per cloud in cloud order - a seeded run consumes the stream as G consecutive batch_attack calls do;
+        then one forward for the G noisy clouds."""
+        G = len(dist)
+        noise = np.empty((G, n, 3), np.float32)
+        for g in range(G):
+            z = np.random.uniform(0, 1, size=(n, 3))
+            noise[g] = (z / np.linalg.norm(z) * dist[g]).astype(np.float32)
+        rnd = feat.clone()
+        rnd[:, 3:6] = torch.clamp(xs + torch.from_numpy(noise.reshape(G * n, 3)).cuda(), 0, 1)
+        return ws.forward(self.model, rnd).argmax(1).cpu().numpy().reshape(G, n)
 
     # the accuracy exit as an integer ratio: mode 0 `correct / n < num / den`, mode 1 `hits / points > num / den`
     EXIT_MODE, EXIT_RATIO = 0, (1, 13)
+    chunk = CHUNK           # steps per window (tests shorten it; at most CHUNK)
     window_hook = None      # tests, tools: called after every window's read-back with (first step, steps, tail, state, history rows)
 
     def _run_clouds(self, features, labels, ys_h, mask_h):
         """The lockstep loop: features [G, N, 6], labels / ys_h [G, N] (host), mask_h [G, N] bool or None.  -> the state,
         pred0 [G, N], per cloud the snapshot's pred [G, N], {n_correct, n_hits, dist2} [G, 3] and the exit steps [G]."""
-        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, np.float32))
-        f = f.float().cuda().contiguous()
-        if f.dim() != 3 or f.shape[2] != 6 or f.shape[0] < 1:
-            raise ValueError("features must be [G, N, 6] (xyz, rgb) of G >= 1 clouds, got %s" % (tuple(f.shape),))
+        f = _features(features, clouds=True)
         G, n = int(f.shape[0]), int(f.shape[1])
         if tuple(ys_h.shape) != (G, n):
             raise ValueError("labels must be [G, N] = %s, got %s" % ((G, n), tuple(ys_h.shape)))
         if self.iteration < 1:
             raise ValueError("iteration must be positive")
-        if (n, G) not in self._clouds:
-            self._clouds[(n, G)] = _CloudsState(n, G)
-        S = self._clouds[(n, G)]
-        ws = S.ws
-        S.feat.copy_(f.reshape(G * n, 6))
-        S.xs.copy_(S.feat[:, 3:6])
-        ws.set_cloud(S.feat[:, 0:3].contiguous())
-        pred0 = ws.forward(self.model, S.feat).argmax(1).cpu().numpy().reshape(G, n)
+        S, pred0 = self._start_clouds(f)
         S.labels.copy_(torch.from_numpy(np.ascontiguousarray(labels, np.int32).reshape(-1)))
         S.ys.copy_(torch.from_numpy(np.ascontiguousarray(ys_h, np.int32).reshape(-1)))
         if mask_h is not None:
@@ -559,67 +575,34 @@ class NUattack(_StepAttack):
             S.n_mask.copy_(torch.from_numpy(mask_h.reshape(G, n).sum(1).astype(np.int32)))
         for t in (S.dws, S.m, S.v, S.dist2, S.out_stats, S.out_adv, S.out_pred):
             t.zero_()
-        S.active.fill_(1)
-        S.exit.fill_(-1)
         win = _lib.RlaNuWindowArgs()
-        win.model, win.ws = self.model.handle, ws.handle
+        win.model, win.ws = self.model.handle, S.ws.handle
         win.G, win.N, win.mode = G, n, self.EXIT_MODE
         win.num, win.den = int(self.EXIT_RATIO[0]), int(self.EXIT_RATIO[1])
         win.cs, win.lr = self.cs, self.lr
-        for name, t in (("xs", S.xs), ("dws", S.dws), ("m", S.m), ("v", S.v), ("labels", S.labels), ("ys", S.ys), ("feat", S.feat),
-                        ("logits", S.logits), ("dlogits", S.dlogits), ("dfeat", S.dfeat), ("dist2", S.dist2), ("partials", S.partials),
-                        ("pred", S.pred), ("scratch", S.scratch), ("hist", S.hist), ("out_adv", S.out_adv), ("out_pred", S.out_pred),
-                        ("out_stats", S.out_stats), ("active", S.active), ("exit_step", S.exit)):
-            setattr(win, name, t.data_ptr())
+        _bind(win, S, "xs dws m v labels ys feat logits dlogits dfeat dist2 partials pred scratch hist out_adv out_pred out_stats "
+                      "active exit_step=exit")
         win.mask = S.mask.data_ptr() if mask_h is not None else None
         win.n_mask = S.n_mask.data_ptr() if mask_h is not None else None
-        chunk = max(1, min(int(self.chunk), CHUNK))
-        exited = np.full(G, -1, np.int64)
-        t0 = 1
-        while t0 <= self.iteration:                      # windows [1..W], [W+1..2W], ..; the last one is cut to the cap
-            n_run = min(chunk, self.iteration - t0 + 1)
-            tail = t0 + n_run - 1 == self.iteration       # .. and evaluates its last step, snapshotting the clouds still running
-            win.n_steps, win.adam_t0, win.tail_eval = n_run, t0, 1 if tail else 0
-            graph = None if n_run != CHUNK else (S.graph_tail if tail else S.graph)      # cut windows run eagerly
-            _lib.call("psg_rla_nu_window", ctypes.byref(win), graph, runtime.stream())
-            rows = n_run + (1 if tail else 0)
-            back = torch.cat([S.hist[:rows].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
-            exited = back[rows * G * 3:].astype(np.int64)
-            if self.window_hook is not None:
-                self.window_hook(t0, n_run, tail, S, back[:rows * G * 3].reshape(rows, G, 3))
-            t0 += n_run
-            if (exited >= 0).all():
-                break
-        self.last_adv = S.out_adv.reshape(G, n, 3).clone()
-        self.last_steps = np.where(exited >= 0, exited, self.iteration)
-        return S, pred0, S.out_pred.cpu().numpy().reshape(G, n), S.out_stats.cpu().numpy().astype(np.float64), G, n
 
-    chunk = CHUNK           # steps per window (tests shorten it; at most CHUNK)
+        def set_window(t0, n_run, tail):                 # tail, the cap: it also evaluates its last step, snapshotting the clouds still running
+            win.n_steps, win.adam_t0, win.tail_eval = n_run, t0, 1 if tail else 0
+            return n_run + (1 if tail else 0)
+
+        # windows [1..W], [W+1..2W], ..; the last one is cut to the cap
+        _, self.last_steps = _run_windows("psg_rla_nu_window", win, S, 1, self.iteration, self.chunk, set_window, self.window_hook)
+        self.last_adv = S.out_adv.reshape(G, n, 3).clone()
+        return S, pred0, S.out_pred.cpu().numpy().reshape(G, n), S.out_stats.cpu().numpy().astype(np.float64), G, n
 
     def batch_attack_clouds(self, features, labels):
         """G clouds in lockstep: features [G, N, 6], labels [G, N] -> a list of G tuples, each the reference's
         (acc, original_accuracy, new_dists, mIoU, original_mIoU, rand_acc, rand_mIoU) of that cloud (NUattack.py:233), the
         fields `batch_attack` returns.  Every cloud has its own early exit; one that exits stops moving."""
-        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64)
+        lab = _labels(labels, np.int64)
         S, pred0, pred, stats, G, n = self._run_clouds(features, lab, lab, None)
         dist = np.sqrt(stats[:, 2])
-        # random noise of the same l_2 size (NUattack.py:236-252): numpy's global generator, once per cloud in cloud order - a
-        # seeded run consumes the stream as G consecutive batch_attack calls do; then one forward for the G noisy clouds
-        rnd = S.feat.clone()
-        noise = np.empty((G, n, 3), np.float32)
-        for g in range(G):
-            z = np.random.uniform(0, 1, size=(n, 3))
-            noise[g] = (z / np.linalg.norm(z) * dist[g]).astype(np.float32)
-        rnd[:, 3:6] = torch.clamp(S.xs + torch.from_numpy(noise.reshape(G * n, 3)).cuda(), 0, 1)
-        rpred = S.ws.forward(self.model, rnd).argmax(1).cpu().numpy().reshape(G, n)
-        outs = []
-        for g in range(G):
-            out = (float(np.sum(pred[g] == lab[g]) / n), float(np.sum(pred0[g] == lab[g]) / n), float(dist[g]), _mean_iou(pred[g], lab[g]),
-                   _mean_iou(pred0[g], lab[g]), float(np.sum(rpred[g] == lab[g]) / n), _mean_iou(rpred[g], lab[g]))
-            if self.logger is not None:
-                self.logger.info("acc={}, original_acc={}, new_dists={}, mIoU={}, original_mIoU={}, rand_acc={}, rand_mIoU={}".format(*out))
-            outs.append(out)
-        return outs
+        rpred = self._noise_pred(S.ws, S.feat, S.xs, dist, n)
+        return [_untargeted_out(self.logger, pred[g], pred0[g], rpred[g], lab[g], float(dist[g])) for g in range(G)]
 
 
 class tar_NUattack(NUattack):
@@ -637,11 +620,9 @@ class tar_NUattack(NUattack):
 
     def batch_attack(self, features, labels, target=None, ori=2):
         """-> (target_points, sr, other_acc, original_other_accuracy, new_dists, other_mIoU, original_other_mIoU)."""
-        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64)
-        mask_h = lab == ori
+        lab = _labels(labels, np.int64)
+        mask_h = _origin_points(lab, ori, "253-256")
         target_points = float(mask_h.sum())
-        if target_points == 0:
-            raise ValueError("no point of the origin class %d in this cloud (tester_S3DIS.py:253-256 skips such clouds)" % ori)
         ys_target = np.where(mask_h, target, lab)
         mask_t = torch.from_numpy(mask_h).cuda()
         ys_t = torch.from_numpy(ys_target).cuda()
@@ -650,14 +631,7 @@ class tar_NUattack(NUattack):
             s["sr"] = float((s["pred"][mask_t] == ys_t[mask_t]).sum()) / target_points
             return s["sr"] > 0.95
         st = self._run(features, labels, ys_target, mask_h, stop)
-        n, pred, pred0 = st["n"], st["pred"].cpu().numpy(), st["pred0"]
-        out = (target_points, st["sr"], float(np.sum(pred[~mask_h] == ys_target[~mask_h]) / (n - target_points)),
-               float(np.sum(pred0[~mask_h] == lab[~mask_h]) / (n - target_points)), st["dist"],
-               _mean_iou(pred[~mask_h], lab[~mask_h]), _mean_iou(pred0[~mask_h], lab[~mask_h]))
-        if self.logger is not None:
-            self.logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
-                             "original_other_mIoU={}".format(*out))
-        return out
+        return _targeted_out(self.logger, st["pred"].cpu().numpy(), st["pred0"], lab, ys_target, mask_h, st["dist"])
 
     EXIT_MODE, EXIT_RATIO = 1, (19, 20)
 
@@ -665,24 +639,11 @@ class tar_NUattack(NUattack):
         """G clouds in lockstep -> a list of G tuples (target_points, sr, other_acc, original_other_accuracy, new_dists,
         other_mIoU, original_other_mIoU), the fields `batch_attack` returns.  Raises ValueError, before any device work, when
         a cloud has no point of class `ori`."""
-        lab = (labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64)
+        lab = _labels(labels, np.int64)
         if lab.ndim != 2:
             raise ValueError("labels must be [G, N], got %s" % (lab.shape,))
-        mask_h = lab == ori
-        target_points = mask_h.sum(1).astype(np.float64)
-        if (target_points == 0).any():
-            raise ValueError("no point of the origin class %d in cloud(s) %s (tester_S3DIS.py:253-256 skips such clouds)" %
-                             (ori, ", ".join(str(g) for g in np.flatnonzero(target_points == 0))))
+        mask_h = _origin_points(lab, ori, "253-256")
         ys_target = np.where(mask_h, target, lab)
         S, pred0, pred, stats, G, n = self._run_clouds(features, lab, ys_target, mask_h)
-        outs = []
-        for g in range(G):
-            mk, tp = mask_h[g], target_points[g]
-            out = (float(tp), float(np.sum(pred[g][mk] == ys_target[g][mk]) / tp),
-                   float(np.sum(pred[g][~mk] == ys_target[g][~mk]) / (n - tp)), float(np.sum(pred0[g][~mk] == lab[g][~mk]) / (n - tp)),
-                   float(np.sqrt(stats[g, 2])), _mean_iou(pred[g][~mk], lab[g][~mk]), _mean_iou(pred0[g][~mk], lab[g][~mk]))
-            if self.logger is not None:
-                self.logger.info("points={}, sr={},  other_acc={}, original_other_accuracy={}, new_dists={}, other_mIoU={}, "
-                                 "original_other_mIoU={}".format(*out))
-            outs.append(out)
-        return outs
+        return [_targeted_out(self.logger, pred[g], pred0[g], lab[g], ys_target[g], mask_h[g], float(np.sqrt(stats[g, 2])))
+                for g in range(G)]

@@ -1,4 +1,4 @@
-"""RandLA-Net on the MI355X: thin object layer over the psg_rla_* C ABI (csrc/psg_randla_net.hip).
+"""RandLA-Net on the MI355X: thin object layer over the psg_rla_* C ABI (csrc/psg_randla_net.hip, the BIM loop csrc/psg_randla_attack.hip).
 
 Restates Network.inference of RandLA-Net/RandLANet.py:150-190 (eval mode) and the BIM colour attack of
 ares/ares/attack/bim.py of the reference; one cloud per workspace like the reference's validation batches.  PARITY

@@ -1,6 +1,7 @@
 """Numpy restatements for the lockstep RandLA-Net NU attacks (psg_rla_nu_color_clouds / _adam_clouds / _latch_clouds):
 the evaluation and exit latch the reference runs after every optimiser step (NUattack.py:190-213, tar_NUattack.py:235),
-the integer exit tests next to the host's double-precision ones, and the colour arithmetic in float64.
+the integer exit tests next to the host's double-precision ones, the colour arithmetic in float64, and one Adam step in
+float64 with the counted bound of the float32 kernel (adam64).
 
 `latch` takes switches that turn it into the mutants the host tests must catch; the defaults are the specification."""
 import numpy as np
@@ -65,3 +66,68 @@ def latch(state, hist_row, logits, labels, ys, mask, n_mask, feat, dist2, mode, 
         if exits:
             state["exit_step"][g] = step
             state["active"][g] = 0
+
+
+# ---- one Adam step in float64, with the float32 kernel's first-order error counted operation by operation
+U = 2.0 ** -24
+LIBM_ULPS = 5                    # atanhf, tanhf: the OpenCL full-profile limit the device's math library is built to (5 ulp; 1 ulp <= 2 u |result|)
+B1, B2, ADAM_EPS = np.float32(0.9), np.float32(0.999), np.float32(1e-8)
+
+
+def adam_lr_t(lr, t):
+    """TF1 Adam's step size as the library forms it: in double from the float32 lr, rounded to float32 once"""
+    return np.float32(np.float64(np.float32(lr)) * np.sqrt(1.0 - 0.999 ** t) / (1.0 - 0.9 ** t))
+
+
+def adam64(xs, dws, m, v, adv, dscore, dist2, c, lr, t, mask=None, one_minus=None):
+    """psg_rla_nu_adam_step / _clouds on float32 inputs, every operation in float64: xs, dws, m, v, adv (the colours the
+    forward saw), dscore (d score / d colours) [..., n, 3], dist2 [...] (one per cloud), mask [..., n] or None.
+    -> ((d_ws', m', v'), (their bounds)), the bounds per element and COUNTED: every float32 operation of the kernel adds one
+    rounding, u = 2^-24 times the magnitude of its float64 result, to the error its operands bring (first order; a fused
+    multiply-add only removes a rounding; sqrtf and the division are correctly rounded, atanhf and tanhf LIBM_ULPS ulp).
+    The two gradient terms: gd = (adv - x) / dist carries 3 roundings (difference, root, quotient), gs = c dscore 1, their sum
+    1 more of |gd + gs|; the chain factor (1 - th^2) / 2 carries what th = tanh(atanh(2 b x - b) + d_ws) brings plus 2.
+    one_minus: (1 - beta1, 1 - beta2) as float32; the default is the kernel's (and TF1's), the float32 differences
+    1 - 0.9f and 1 - 0.999f, which are exact - not float32(0.1) and float32(0.001), which oracle/randla_net.py takes."""
+    x, d, m0, v0, a, s = (np.asarray(q, np.float64) for q in (xs, dws, m, v, adv, dscore))
+    b, L = np.float64(NU_BOUND), LIBM_ULPS * 2 * U
+    arg = 2.0 * b * x - b
+    e = U * np.abs(2.0 * b * x) + U * np.abs(arg)
+    at = np.arctanh(arg)
+    e = e / (1.0 - arg * arg) + L * np.abs(at)
+    w = at + d
+    e = e + U * np.abs(w)
+    th = np.tanh(w)
+    e_th = (1.0 - th * th) * e + L * np.abs(th)
+    chain = 0.5 * (1.0 - th * th)
+    e_chain = 0.5 * (2.0 * np.abs(th) * e_th + U * th * th + U * (1.0 - th * th))
+    dist = np.sqrt(np.asarray(dist2, np.float64))[..., None, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        gd = np.where(dist > 0, (a - x) / dist, 0.0)
+    gs = np.float64(np.float32(c)) * s
+    e_sum = 3 * U * np.abs(gd) + U * np.abs(gs) + U * np.abs(gd + gs)
+    g = (gd + gs) * chain
+    e_g = np.abs(gd + gs) * e_chain + chain * e_sum + U * np.abs(g)
+    if mask is not None:
+        on = np.asarray(mask, bool)[..., None]
+        g, e_g = np.where(on, g, 0.0), np.where(on, e_g, 0.0)
+    b1, b2 = np.float64(B1), np.float64(B2)
+    nb1, nb2 = (np.float64(q) for q in (one_minus or (np.float32(1) - B1, np.float32(1) - B2)))
+    m1 = b1 * m0 + nb1 * g
+    e_m = U * np.abs(b1 * m0) + nb1 * e_g + U * np.abs(nb1 * g) + U * np.abs(m1)
+    p = nb2 * g
+    e_p = nb2 * e_g + U * np.abs(p)
+    v1 = b2 * v0 + p * g
+    e_v = U * np.abs(b2 * v0) + np.abs(p) * e_g + np.abs(g) * e_p + U * np.abs(p * g) + U * np.abs(v1)
+    lr_t = np.float64(adam_lr_t(lr, t))
+    q = lr_t * m1
+    e_q = lr_t * e_m + 2 * U * np.abs(q)                       # the product, and lr_t's own last bit (pow against **)
+    r = np.sqrt(v1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        e_r = np.where(r > 0, e_v / (2.0 * r), 0.0) + U * r
+    den = r + np.float64(ADAM_EPS)
+    e_den = e_r + U * den
+    step = q / den
+    e_step = e_q / den + np.abs(step) * e_den / den + U * np.abs(step)
+    w1 = d - step
+    return (w1, m1, v1), (e_step + U * np.abs(w1), e_m, e_v)

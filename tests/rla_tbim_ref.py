@@ -133,3 +133,47 @@ def host_loop(feat0_g, pred_fn_g, dfeat_fn_g, hit_ys_g, mask_g, iteration, eps=0
         if it > 0 and sr > 0.90:
             break
     return pred, feat[0][:, 3:6].copy(), steps
+
+
+U = 2.0 ** -24
+
+
+def bim_step64(feat, dfeat, ori, eps, alpha, norms=None):
+    """bim_step's l_2 formula on float32 inputs, every operation in float64: feat, dfeat [G, n, 6], ori [G, n, 3].
+    -> ((rgb [G, n, 3], norms [2][G], delta [G, n, 3]), (their bounds)).  norms: the squared norms to normalise with in place
+    of the clouds' own (the mutants of the tests).  The bounds are per element and COUNTED: every float32 operation of the
+    kernels adds one rounding, u = 2^-24 times the magnitude of its float64 result, to the error its operands bring (first
+    order; a fused multiply-add only removes a rounding; sqrtf and the division are correctly rounded):
+      |g|^2, |delta|^2   double sums (3 n terms: (3 n + 2) 2^-53, nothing next to u) rounded to float32 ONCE: 1; the second one
+                         sums the float32 deltas as stored, so it brings their errors too: 2 sum |delta| e_delta
+      gn = max(1e-12, sqrt |g|^2)   half the square's error plus 1; none where the floor holds
+      delta = (adv - x) + alpha (g / gn)   the difference 1, the quotient 1 on top of gn's, the product 1, the sum 1
+      scale = eps / sqrt |delta|^2 where clipped   the root as above, the quotient 1; none where scale = 1
+      rgb = clip(x + delta scale, 0, 1)   the product 1, the sum 1; the clip is exact and moves no two values apart."""
+    f, g, x = (np.asarray(q, np.float64) for q in (feat[:, :, 3:6], dfeat[:, :, 3:6], ori))
+    eps, alpha, n3 = np.float64(np.float32(eps)), np.float64(np.float32(alpha)), f.shape[1] * 3
+    dbl = (n3 + 2) * 2.0 ** -53
+    gn2 = (g ** 2).sum((1, 2)) if norms is None else np.asarray(norms[0], np.float64)
+    e_gn2 = (U + dbl) * gn2
+    floor = np.sqrt(gn2) < np.float64(np.float32(1e-12))
+    gn = np.where(floor, np.float64(np.float32(1e-12)), np.sqrt(gn2))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        e_gn = np.where(floor, 0.0, e_gn2 / (2.0 * gn) + U * gn)
+    gn, e_gn = gn[:, None, None], e_gn[:, None, None]
+    a, q = f - x, g / gn
+    e_q = np.abs(q) * e_gn / gn + U * np.abs(q)
+    delta = a + alpha * q
+    e_delta = U * np.abs(a) + alpha * e_q + U * np.abs(alpha * q) + U * np.abs(delta)
+    own_dn2 = (delta ** 2).sum((1, 2))
+    e_dn2 = 2.0 * (np.abs(delta) * e_delta).sum((1, 2)) + (U + dbl) * own_dn2
+    dn2 = own_dn2 if norms is None else np.asarray(norms[1], np.float64)
+    dn = np.sqrt(dn2)
+    clipped = dn > eps
+    with np.errstate(invalid="ignore", divide="ignore"):
+        e_dn = np.where(dn > 0, e_dn2 / (2.0 * dn), 0.0) + U * dn
+        scale = np.where(clipped, eps / dn, 1.0)
+        e_scale = np.where(clipped, scale * e_dn / dn + U * scale, 0.0)
+    scale, e_scale = scale[:, None, None], e_scale[:, None, None]
+    out = x + delta * scale
+    e_out = scale * e_delta + np.abs(delta) * e_scale + U * np.abs(delta * scale) + U * np.abs(out)
+    return (np.clip(out, 0.0, 1.0), np.stack([gn2, own_dn2]), delta), (e_out, np.stack([e_gn2, e_dn2]), e_delta)

@@ -121,34 +121,58 @@ def test_adam_clouds_equals_the_one_cloud_kernel(n, masked):
     """State from the one-cloud kernels (psg_rla_nu_color per cloud), dist2 fed equal to theirs: d_ws, m and v of every cloud
     are bit-equal to psg_rla_nu_adam_step on that cloud alone; inactive clouds are bit-unchanged.  (The step-constant row
     cannot be set through the C ABI: test_windows_equal_hand_driven_steps compares windows that read it with steps that take
-    the scalar.)"""
+    the scalar.)  Both against the float64 step at t = 3, 1, 7, cloud 2 at distance 0.  That bound is per element and counted,
+    one rounding u = 2^-24 of the float64 result per float32 operation (rla_nu_ref.adam64 carries them along): the distance
+    term (adv - x) / dist 3 (difference, root, quotient), c dscore 1, their sum 1, the chain factor 2 + what tanh(atanh(.) + d_ws)
+    brings (the two library functions at 5 ulp), the product 1; m 3 more, v 4, the step 5 + the root's."""
     import torch
     xs, dws0, mask = small_case(n, masked, seed=3)
     rng = np.random.default_rng(n)
     dfeat = rng.standard_normal((G, n, 6)).astype(np.float32)
     m0 = (0.1 * rng.standard_normal((G, n, 3))).astype(np.float32)
     v0 = (0.01 * rng.random((G, n, 3))).astype(np.float32)
-    c, lr, t = 0.5, 0.01, 3
+    c, lr = 0.5, 0.01
     feat, dist2 = torch.zeros(G, n, 6, device="cuda"), torch.zeros(G, device="cuda")
     d_xs, d_dfeat = dev(xs), dev(dfeat)
     d_mask = dev(mask) if masked else None
-    want = []
     for g in range(G):
-        mp = P(d_mask[g]) if masked else None
-        call("psg_rla_nu_color", P(d_xs[g]), D(dws0[g]), mp, n, P(feat[g]), P(dist2[g:g + 1]))
-        w, m, v = dev(dws0[g]), dev(m0[g]), dev(v0[g])
-        call("psg_rla_nu_adam_step", P(d_xs[g]), P(w), P(m), P(v), mp, P(feat[g]), P(d_dfeat[g]), P(dist2[g:g + 1]), n, c, lr, t)
-        want.append((host(w), host(m), host(v)))
-    for active in (None, np.array([1, 0, 1], np.uint8)):
-        w, m, v = dev(dws0), dev(m0), dev(v0)
-        call("psg_rla_nu_adam_clouds", P(d_xs), P(w), P(m), P(v), P(d_mask) if masked else None,
-             None if active is None else D(active), P(feat), P(d_dfeat), P(dist2), G, n, c, lr, t)
+        call("psg_rla_nu_color", P(d_xs[g]), D(dws0[g]), P(d_mask[g]) if masked else None, n, P(feat[g]), P(dist2[g:g + 1]))
+    # cloud 2 stands where the attack starts: the clean colours, distance 0 (the `dist > 0 ?` branch of the gradient)
+    feat[2, :, 3:6] = d_xs[2]
+    dist2[2] = 0.0
+    adv_h, dist2_h = host(feat)[:, :, 3:6], host(dist2)
+    for t in (3, 1, 7):
+        want = []
         for g in range(G):
-            if active is not None and not active[g]:
-                assert same(host(w)[g], dws0[g]) and same(host(m)[g], m0[g]) and same(host(v)[g], v0[g])
-            else:
-                for got, ref, name in zip((w, m, v), want[g], "wmv"):
-                    assert same(host(got)[g], ref), (name, g)
+            mp = P(d_mask[g]) if masked else None
+            w, m, v = dev(dws0[g]), dev(m0[g]), dev(v0[g])
+            call("psg_rla_nu_adam_step", P(d_xs[g]), P(w), P(m), P(v), mp, P(feat[g]), P(d_dfeat[g]), P(dist2[g:g + 1]), n, c, lr, t)
+            want.append((host(w), host(m), host(v)))
+        for active in (None, np.array([1, 0, 1], np.uint8)):
+            w, m, v = dev(dws0), dev(m0), dev(v0)
+            call("psg_rla_nu_adam_clouds", P(d_xs), P(w), P(m), P(v), P(d_mask) if masked else None,
+                 None if active is None else D(active), P(feat), P(d_dfeat), P(dist2), G, n, c, lr, t)
+            for g in range(G):
+                if active is not None and not active[g]:
+                    assert same(host(w)[g], dws0[g]) and same(host(m)[g], m0[g]) and same(host(v)[g], v0[g])
+                else:
+                    for got, ref, name in zip((w, m, v), want[g], "wmv"):
+                        assert same(host(got)[g], ref), (name, g)
+        # both forms are one kernel now, so the yardstick is the float64 step with its counted bound (rla_nu_ref.adam64); the
+        # mutants - the neighbour cloud's distance, the mask ignored - must leave that bound somewhere
+        args = (xs, dws0, m0, v0, adv_h, dfeat[:, :, 3:6], dist2_h, c, lr, t)
+        ref, bound = R.adam64(*args, mask)
+        got = [np.stack([wg[k] for wg in want]).astype(np.float64) for k in range(3)]
+        assert all(np.isfinite(q).all() for q in got)
+        for k, name in enumerate(("d_ws", "m", "v")):
+            err = np.abs(got[k] - ref[k])
+            print("n", n, "t", t, name, "largest error / bound", float((err / bound[k]).max()))
+            assert (err <= bound[k]).all(), (name, t)
+        mutants = {"the neighbour's dist2": R.adam64(*args[:6], np.roll(dist2_h, -1), *args[7:], mask)[0]}
+        if masked:
+            mutants["the mask ignored"] = R.adam64(*args)[0]
+        for name, mut in mutants.items():
+            assert any((np.abs(mut[k] - got[k]) > bound[k]).any() for k in range(3)), (name, t)
 
 
 # ---------------------------------------------------------------------------------------------- 6. latch kernel

@@ -104,6 +104,11 @@ def step_clouds(feat, dfeat, ori, running, n, l2):
 @pytest.mark.parametrize("l2", [0, 1])
 @pytest.mark.parametrize("n", SMALL)
 def test_step_clouds_equals_the_one_cloud_step(n, l2):
+    """psg_rla_bim_step_clouds against psg_rla_bim_step cloud by cloud (bit for bit), and for l_2 both against the float64
+    formula.  That bound is per element and counted, one rounding u = 2^-24 of the float64 result per float32 operation
+    (rla_tbim_ref.bim_step64 carries them along): the norms 1 each (double sums rounded once; |delta|^2 also what the deltas
+    bring), gn 1.5 of its own, delta 4 (difference, quotient, product, sum) + gn's, scale 1.5 + 1 where clipped, the colour 2
+    (product, sum) + delta's + scale's."""
     feat, dfeat, ori = step_case(n)
     want = step_one_cloud(feat, dfeat, ori, n, l2)
     got_f, got_norms, got_delta = step_clouds(feat, dfeat, ori, None, n, l2)
@@ -120,6 +125,17 @@ def test_step_clouds_equals_the_one_cloud_step(n, l2):
         assert gn[1] == 0.0 and gn[0] > 0.0 and dn[0] < EPS and dn[1] < EPS and dn[2] > EPS
         d64 = np.sqrt(((got_f[2][:, 3:6].astype(np.float64) - ori[2]) ** 2).sum())
         assert abs(d64 - EPS) <= 1e-5 * EPS + 3 * n * 2.0 ** -24          # clipped onto the eps sphere (float32 colours)
+        # both entry points launch one kernel set now, so the yardstick is the float64 step with its counted bound
+        # (rla_tbim_ref.bim_step64); the mutant - cloud g normalised by cloud (g + 1) % G's norms - must leave it somewhere
+        ref, bound = R.bim_step64(feat, dfeat, ori, EPS, ALPHA)
+        one = [np.stack([w[k] for w in want]) for k in range(3)]
+        for tag, (f, norms, delta) in (("clouds", (got_f, got_norms, got_delta)), ("one cloud", (one[0], one[1].T, one[2]))):
+            for name, got, k in (("feat", f[:, :, 3:6], 0), ("norms", norms, 1), ("delta", delta, 2)):
+                err = np.abs(got.astype(np.float64) - ref[k])
+                print("n", n, tag, name, "largest error / bound", float((err / np.maximum(bound[k], 1e-300)).max()))
+                assert (err <= bound[k]).all(), (tag, name)
+            mutant = R.bim_step64(feat, dfeat, ori, EPS, ALPHA, norms=np.roll(ref[1], -1, axis=1))[0][0]
+            assert (np.abs(mutant - f[:, :, 3:6]) > bound[0]).any(), tag
     else:
         assert linf_matches_numpy(got_f, feat, dfeat, ori)
     # two runs: the same bits

@@ -133,3 +133,38 @@ def test_classes_have_the_lockstep_methods_and_keep_the_one_cloud_guard():
     assert callable(attack.NUattack.batch_attack_clouds) and callable(attack.tar_NUattack.batch_attack_clouds)
     assert attack.NUattack.EXIT_RATIO == (1, 13) and attack.tar_NUattack.EXIT_RATIO == (19, 20)
     assert attack.CHUNK == 10
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("t", [1, 7])
+def test_adam64_is_pinned_to_the_oracle(t, masked):
+    """The float64 restatement of the Adam step (rla_nu_ref.adam64, the yardstick of the GPU test of the kernel) against
+    oracle/randla_net.nu_adam_step on 50 points: the oracle's mixed float32 / float64 evaluation takes no more roundings than
+    the kernel, so it lies inside the counted bound."""
+    from oracle import randla_net as O
+    rng = np.random.default_rng(50 + t)
+    n, c, lr = 50, 0.5, 0.01
+    xs = rng.random((n, 3), dtype=np.float32)
+    dws = (0.3 * rng.standard_normal((n, 3))).astype(np.float32)
+    m = (0.1 * rng.standard_normal((n, 3))).astype(np.float32)
+    v = (0.01 * rng.random((n, 3))).astype(np.float32)
+    dscore = rng.standard_normal((n, 3)).astype(np.float32)
+    mask = (rng.random(n) < 0.4) if masked else None
+    adv, _ = O.nu_color(xs, dws, mask)
+    dist2 = np.float32(((adv.astype(np.float64) - xs) ** 2).sum())
+    w_o, m_o, v_o, dist = O.nu_adam_step(xs, dws, m, v, t, dscore, c, lr, mask)
+    assert abs(dist - np.sqrt(np.float64(dist2))) <= 2.0 ** -24 * dist
+    oracle_consts = (np.float32(1 - 0.9), np.float32(1 - 0.999))          # (adam64's docstring: the kernel's differ in the last bits)
+    (w_r, m_r, v_r), (e_w, e_m, e_v) = R.adam64(xs, dws, m, v, adv, dscore, dist2, c, lr, t, mask, one_minus=oracle_consts)
+    for name, got, ref, bound in (("d_ws", w_o, w_r, e_w), ("m", m_o, m_r, e_m), ("v", v_o, v_r, e_v)):
+        err = np.abs(got.astype(np.float64) - ref)
+        print(name, "largest error / bound", float((err / bound).max()), "largest bound / |value|", float((bound / np.abs(ref)).max()))
+        assert (err <= bound).all(), name
+    # the bound resolves the last bits of a constant: with the kernel's 1 - 0.999f (1.3e-5 below float32(0.001)) the oracle's v
+    # no longer fits it
+    (_, _, v_k), (_, _, e_vk) = R.adam64(xs, dws, m, v, adv, dscore, dist2, c, lr, t, mask)
+    assert (np.abs(v_o.astype(np.float64) - v_k) > e_vk).any()
+    assert R.adam_lr_t(lr, t) == np.float32(lr * np.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t))
+    if masked:      # a masked-out point: no gradient, the moments only decay
+        off = ~mask
+        assert np.array_equal(m_r[off], np.float64(R.B1) * m[off]) and np.array_equal(v_r[off], np.float64(R.B2) * v[off])
