@@ -1072,6 +1072,48 @@ typedef struct psg_rla_tbim_window_args {
 } psg_rla_tbim_window_args;
 int psg_rla_tbim_window(const psg_rla_tbim_window_args *args, psg_nu_graph *graph, psg_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * RandLA-Net data preparation: grid sub-sampling and the projection of raw points onto the sub-cloud (psg_grid.hip).
+ *
+ * A.  DataProcessing.grid_sub_sampling (RandLA-Net/helper_tool.py:197-216) = cpp_subsampling.compute
+ * (utils/cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp:5-106): one output point per occupied cell of
+ * edge grid_size - the barycentre of the cell's points, their mean feature, their most frequent label per label dimension.  All
+ * arithmetic is fp32 in the reference's order (a cell's sums are sequential additions in INPUT order), so barycentres and
+ * mean features are bit-equal to the reference's.  Ours: the output is in ascending cell-key order (the reference's is its hash
+ * map's iteration order); of equally frequent labels the smallest (signed) wins; a cell index of -1 (the origin can exceed
+ * the minimum corner by a rounding; undefined in the reference) counts as 0.  Results are the same bytes from run to run.
+ *
+ * One handle holds the scratch of clouds of up to max_points points (about 60 bytes per point) and the state between the
+ * calls; it is used from one stream at a time.  Everything is enqueued on `stream`; psg_grid_assign and psg_grid_index
+ * synchronise it.
+ *
+ * psg_grid_assign: points [n][3] device -> the cells, their order and *n_voxels_out = M, the number of occupied cells
+ * (two small read-backs: the corners of the cloud, from which the host derives the grid, and M, which sizes the
+ * caller's outputs); voxel_of_point [n] (device, or NULL) = the output row of every input point.  Refuses, before
+ * anything is written: n < 1, grid_size not a positive finite number, non-finite coordinates, a grid of more than 2^20
+ * cells along an axis.
+ * psg_grid_reduce: the outputs of the last psg_grid_assign, from the same `points`: sub_points [M][3], sub_features [M][d]
+ * from features [n][d] (d = 0: both NULL), sub_labels [M][l] from labels [n][l] int32, any values (l = 0: both NULL).
+ *
+ * B.  proj_idx of utils/data_prepare_s3dis.py (KDTree(sub_xyz).query(xyz, k = 1)): psg_grid_index bins sub_points [m][3]
+ * by their own coordinates into cells of edge grid_size - the SMALLEST cell the table uses: the edge is doubled until the grid has
+ * at most 64 cells per sub-point and 2^20 along an axis, which bounds a query's work; the answer does not depend on it - and
+ * keeps them sorted by cell key in the handle (this replaces the state of psg_grid_assign);
+ * psg_grid_nearest writes, for query [n_query][3], out_idx [n_query] = the index of the nearest sub-point, exactly
+ * psg_knn_points(sub_points, query, k = 1): fp32 distance ((dx*dx) + dy*dy) + dz*dz, ties to the lower index - found through
+ * the cell table, ring by ring, under a stopping bound that is conservative in fp32.  Queries outside the
+ * cloud's box are answered too (the further out, the more of the table they read).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct psg_grid psg_grid;
+int psg_grid_create(psg_ctx *ctx, int max_points, psg_grid **out);
+int psg_grid_destroy(psg_grid *g);
+int psg_grid_assign(psg_grid *g, const float *points, int n, float grid_size, int32_t *voxel_of_point, int *n_voxels_out,
+                    psg_stream stream);
+int psg_grid_reduce(psg_grid *g, const float *points, const float *features, int d, const int32_t *labels, int l,
+                    float *sub_points, float *sub_features, int32_t *sub_labels, psg_stream stream);
+int psg_grid_index(psg_grid *g, const float *sub_points, int m, float grid_size, psg_stream stream);
+int psg_grid_nearest(psg_grid *g, const float *query, int n_query, int32_t *out_idx, psg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,12 @@ SIGNATURES = {
     "psg_vote_add": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]),
     "psg_vote_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
     "psg_l2_dist": (ci, [vp, vp, ctypes.c_size_t, vp, vp, vp]),
+    "psg_grid_create": (ci, [vp, ci, ctypes.POINTER(vp)]),
+    "psg_grid_destroy": (ci, [vp]),
+    "psg_grid_assign": (ci, [vp, vp, ci, cf, vp, ctypes.POINTER(ci), vp]),
+    "psg_grid_reduce": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]),
+    "psg_grid_index": (ci, [vp, vp, ci, cf, vp]),
+    "psg_grid_nearest": (ci, [vp, vp, ci, vp, vp]),
 }
 
 

@@ -6,6 +6,9 @@ the tf.data map function of main_S3DIS.py:189-214 (`tf_map`: for each of the num
 k_n neighbours, the pooling indices of the sub-sampled points and the nearest sub-sampled point of every point).
 Both run `psg_knn_points` (exact brute-force k-NN, hand-written HIP); there is no CPU path.
 
+`DataProcessing.grid_sub_sampling` (helper_tool.py:197-216, the reference's native cpp_subsampling) is the numpy face of
+`randla/grid.py`, which also holds the projection of raw points onto the sub-cloud (`nearest_sub_point`).
+
 Only the indices are produced here; the network (RandLANet.py) is `randla/network.py`, the tester's attacks are
 `randla/attack.py`, and the possibility-based crop sampler of main_S3DIS.py:116-187 is `randla/sampler.py`.
 """
@@ -42,6 +45,43 @@ class DataProcessing:
         s = torch.from_numpy(np.ascontiguousarray(support_pts, np.float32)).cuda()
         q = torch.from_numpy(np.ascontiguousarray(query_pts, np.float32)).cuda()
         return knn_points(s, q, k).cpu().numpy().astype(np.int32)
+
+    @staticmethod
+    def grid_sub_sampling(points, features=None, labels=None, grid_size=0.1, verbose=0):
+        """
+        Grid sub_sampling on the device (method = barycenter for points and features)
+        :param points: (N, 3) matrix of input points
+        :param features: optional (N, d) matrix of features (floating number)
+        :param labels: optional (N,) or (N, l) matrix of integer labels
+        :param grid_size: parameter defining the size of grid voxels
+        :param verbose: accepted for the reference's signature; nothing is printed
+        :return: sub_sampled points, with features and/or labels depending of the input: points alone, (points, features),
+        (points, labels) or (points, features, labels); float32 / int32, labels 2-D (M, l) as the reference's wrapper returns
+        them.  Inputs are coerced like the wrapper's: anything -> float32 / int32 (uint8 colours are accepted).
+
+        Barycentres and mean features are bit-equal to the reference's.  Rows come in ascending cell-key order, label ties
+        go to the smallest label, a cell index of -1 counts as 0 (randla/grid.py).  Shape errors are ValueError, raised
+        before any device work.
+        """
+        p = np.ascontiguousarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise ValueError("Wrong dimensions : points.shape is not (N, 3)")
+        f = lab = None
+        if features is not None:
+            f = np.ascontiguousarray(features, np.float32)
+            if f.ndim != 2 or f.shape[0] != p.shape[0] or f.shape[1] < 1:
+                raise ValueError("Wrong dimensions : features.shape is not (N, d)")
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, np.int32)
+            if lab.ndim not in (1, 2) or lab.shape[0] != p.shape[0] or (lab.ndim == 2 and lab.shape[1] < 1):
+                raise ValueError("Wrong dimensions : classes.shape is not (N,) or (N, d)")
+        if not (float(grid_size) > 0.0 and np.isfinite(float(grid_size))):
+            raise ValueError("grid_size must be a positive finite number (got %r)" % (grid_size,))
+        from pointsecguard_amd.randla.grid import grid_sub_sampling_device
+        sp, sf, sl = grid_sub_sampling_device(torch.from_numpy(p).cuda(), None if f is None else torch.from_numpy(f).cuda(),
+                                              None if lab is None else torch.from_numpy(lab).cuda(), grid_size)
+        out = [t.cpu().numpy() for t in (sp, sf, sl) if t is not None]
+        return out[0] if len(out) == 1 else tuple(out)
 
 
 def tf_map_indices(batch_xyz, num_layers=5, k_n=16, sub_sampling_ratio=(4, 4, 4, 4, 2)):
