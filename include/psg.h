@@ -1072,6 +1072,78 @@ typedef struct psg_rla_tbim_window_args {
 } psg_rla_tbim_window_args;
 int psg_rla_tbim_window(const psg_rla_tbim_window_args *args, psg_nu_graph *graph, psg_stream stream);
 
+/* NUattack / tar_NUattack on the COORDINATE field of G clouds of n points in lockstep.  The optimiser
+ * variable is delta [G][n][3] in metres (no tanh space: coordinates have no box).  Buffers are cloud-major, `active` [G] as
+ * above (NULL: every cloud), an inactive cloud is skipped by whole workgroups; no float atomics anywhere.
+ *
+ * psg_rla_nu_coord_apply_clouds: positions fl(ori_xyz + delta) on the points of mask [G][n] (NULL: all points; the others keep
+ * ori_xyz byte for byte) into columns 0..2 of feat [G][n][6] and into the contiguous xyz [G][n][3] (what the pyramid is
+ * rebuilt from); dist2_xyz[g] = sum (xyz as written - ori_xyz)^2, the difference formed in double, summed in a fixed order by
+ * PSG_RLA_NU_PARTS workgroups per cloud (partials: [G][PSG_RLA_NU_PARTS] doubles of scratch), rounded to float once. */
+int psg_rla_nu_coord_apply_clouds(const float *ori_xyz, const float *delta, const uint8_t *mask, const uint8_t *active, int G, int n,
+                                  float *feat, float *xyz, float *dist2_xyz, double *partials, psg_stream stream);
+/* One TF1-Adam step (t = 1, 2, ..; betas 0.9 / 0.999, eps 1e-8 outside the root; psg_rla_nu_adam_clouds' operation order) on
+ * delta of loss = |xyz - ori_xyz|_2 + c * score:  g = (dist > 0 ? (xyz - ori_xyz) / dist : 0) + c * (dfeat[:, 0:3] + dxyz), the
+ * inner sum one fp32 add as in psg_rla_bim_step_field, g = 0 off the mask; dist = sqrt(dist2_xyz[g]); xyz [G][n][3] the
+ * positions psg_rla_nu_coord_apply_clouds wrote, dfeat [G][n][6] / dxyz [G][n][3] from psg_rla_backward_full.  lr_t is
+ * computed in double on the host, or read from the step-constant device row when one is set (psg_rla_nu_adam_clouds). */
+int psg_rla_nu_coord_adam_clouds(const float *ori_xyz, float *delta, float *m_xyz, float *v_xyz, const uint8_t *mask,
+                                 const uint8_t *active, const float *xyz, const float *dfeat, const float *dxyz, const float *dist2_xyz,
+                                 int G, int n, float c, float lr, int t, psg_stream stream);
+/* psg_rla_nu_latch_clouds (the same count stage, exit rules, integer thresholds, can_exit, "never the unperturbed start") with
+ * a 4-column row: hist_row [G][4] = {n_correct, n_hits, dist2_rgb[g], dist2_xyz[g]} (dist2_rgb NULL: 0, the "coord" field), and
+ * a snapshot that also carries the positions: out_adv_xyz [G][n][3] = columns 0..2 of feat, out_adv [G][n][3] = columns 3..5,
+ * out_pred [G][n], out_stats [G][4] = the row. */
+int psg_rla_nu_field_latch_clouds(const float *logits, const int32_t *labels, const int32_t *ys, const uint8_t *mask,
+                                  const int32_t *n_mask, const float *feat, const float *dist2_rgb, const float *dist2_xyz, int G, int n,
+                                  int mode, int num, int den, int step, int can_exit, int final, float *hist_row, int32_t *pred,
+                                  float *out_adv_xyz, float *out_adv, int32_t *out_pred, float *out_stats, uint8_t *active,
+                                  int32_t *exit_step, int32_t *scratch, psg_stream stream);
+
+/* One window of the lockstep attack on the coordinate field, or on both fields.  For each of n_steps optimiser steps with Adam
+ * index t = adam_t0 + i: psg_rla_nu_coord_apply_clouds (field BOTH: then psg_rla_nu_color_clouds), the index pyramid of all G
+ * clouds rebuilt from `xyz` (what psg_rla_set_cloud(ws, xyz) does, stream-ordered, no read-back), psg_rla_forward, the field
+ * latch of evaluation index t - 1 (history row i; exits from index 1 on), psg_rla_colper_grad_masked against ys (sign +1),
+ * psg_rla_backward_full, psg_rla_nu_coord_adam_clouds with coord_lr (field BOTH: then psg_rla_nu_adam_clouds with lr, the colour
+ * variable keeping its own dist2 and moments).  tail_eval != 0 appends apply, pyramid, forward and a latch with final = 1
+ * (history row n_steps).  Nothing returns to the host inside a window; there is no hipGraph form (the pyramid's sorts and the
+ * per-step xyz branch are not captured).  A frozen cloud's delta, moments and snapshot are not touched; its pyramid is rebuilt
+ * from unchanged positions, to the same bits.  PSG_ERR_ARG, before anything is enqueued: a workspace that is not
+ * psg_rla_ws_create_full's, (G, N) not the workspace's, field not COORD / BOTH, n_steps < 1, mode 1 without mask / n_mask, a
+ * null required pointer (field COORD needs none of xs, dws, m, v, dist2, partials). */
+typedef struct psg_rla_nu_field_window_args {
+    psg_rla_model *model;
+    psg_rla_ws *ws;              /* psg_rla_ws_create_full, G clouds of N points */
+    int n_steps, G, N, mode;
+    int num, den;                /* the exit threshold num / den */
+    int adam_t0, tail_eval;
+    int field;                   /* PSG_NU_FIELD_COORD or PSG_NU_FIELD_BOTH */
+    float cs, lr, coord_lr;
+    const float *xs;             /* [G][N][3] clean colours (BOTH) */
+    float *dws, *m, *v;          /* [G][N][3] the colour variable and its moments (BOTH) */
+    float *delta, *m_xyz, *v_xyz;   /* [G][N][3] the coordinate variable and its moments */
+    const float *ori_xyz;        /* [G][N][3] clean positions */
+    float *xyz;                  /* [G][N][3] the positions of the step, contiguous */
+    float *dxyz;                 /* [G][N][3] */
+    const uint8_t *mask;         /* [G][N], nullable (required in mode 1) */
+    const int32_t *n_mask;       /* [G], mode 1 */
+    const int32_t *labels, *ys;  /* [G][N] */
+    float *feat;                 /* [G][N][6] */
+    float *logits, *dlogits;     /* [G][N][13] */
+    float *dfeat;                /* [G][N][6] */
+    float *dist2, *dist2_xyz;    /* [G] each (dist2: BOTH) */
+    double *partials, *partials_xyz;   /* [G][PSG_RLA_NU_PARTS] each (partials: BOTH) */
+    int32_t *pred;               /* [G][N] */
+    int32_t *scratch;            /* [G][2 * PSG_RLA_NU_PARTS + 1] */
+    float *hist;                 /* [n_steps + (tail_eval != 0)][G][4] */
+    float *out_adv, *out_adv_xyz;   /* [G][N][3] each */
+    int32_t *out_pred;           /* [G][N] */
+    float *out_stats;            /* [G][4] */
+    uint8_t *active;             /* [G] */
+    int32_t *exit_step;          /* [G], -1 before */
+} psg_rla_nu_field_window_args;
+int psg_rla_nu_field_window(const psg_rla_nu_field_window_args *args, psg_stream stream);
+
 /* ------------------------------------------------------------------------------------------
  * RandLA-Net data preparation: grid sub-sampling and the projection of raw points onto the sub-cloud (psg_grid.hip).
  *

@@ -166,6 +166,11 @@ SIGNATURES = {
     "psg_rla_tbim_latch_clouds": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "psg_rla_tbim_retire_clouds": (ci, [vp, ci, ci, ci, vp, vp, vp, vp]),
     "psg_rla_tbim_window": (ci, [vp, vp, vp]),
+    "psg_rla_nu_coord_apply_clouds": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]),
+    "psg_rla_nu_coord_adam_clouds": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, ci, vp]),
+    "psg_rla_nu_field_latch_clouds": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, vp, vp]),
+    "psg_rla_nu_field_window": (ci, [vp, vp]),
     "psg_seg_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
     "psg_vote_add": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]),
     "psg_vote_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
@@ -240,6 +245,16 @@ class RlaTbimWindowArgs(ctypes.Structure):
                 [(n, vp) for n in ("ori", "mask", "n_mask", "labels", "hit_ys", "loss_ys", "feat", "logits", "dlogits", "dfeat", "norms",
                                    "delta", "pred", "scratch", "hist", "out_adv", "out_pred", "out_stats", "active", "leaving",
                                    "exit_step")])
+
+
+class RlaNuFieldWindowArgs(ctypes.Structure):
+    """psg_rla_nu_field_window_args of include/psg.h, field for field (9 ints and 3 floats: no padding)."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("n_steps", "G", "N", "mode", "num", "den", "adam_t0", "tail_eval", "field")] +
+                [(n, cf) for n in ("cs", "lr", "coord_lr")] +
+                [(n, vp) for n in ("xs", "dws", "m", "v", "delta", "m_xyz", "v_xyz", "ori_xyz", "xyz", "dxyz", "mask", "n_mask", "labels",
+                                   "ys", "feat", "logits", "dlogits", "dfeat", "dist2", "dist2_xyz", "partials", "partials_xyz", "pred",
+                                   "scratch", "hist", "out_adv", "out_adv_xyz", "out_pred", "out_stats", "active", "exit_step")])
 
 
 class NuFieldArgs(ctypes.Structure):

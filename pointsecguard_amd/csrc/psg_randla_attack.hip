@@ -1,6 +1,7 @@
 // The colour attacks on RandLA-Net (psg_randla_net.hip): the "colper" loss, the BIM update and loop (ares/ares/attack/
 // bim.py:66-116, :190-236), NUattack / tar_NUattack (NUattack.py:12-74, tar_NUattack.py:12-84) and TBIM / tar_NBattack
-// (bim.py:277-505), for one cloud and for G clouds in lockstep.
+// (bim.py:277-505), for one cloud and for G clouds in lockstep; and the two NU attacks on the point positions (DESIGN.md 5s:
+// psg_rla_nu_coord_apply_clouds / _coord_adam_clouds / _field_latch_clouds, psg_rla_nu_field_window), G clouds in lockstep.
 //
 // Every update kernel exists once, in the G-cloud form: blockIdx.y = cloud (blockIdx.x for the one-workgroup-per-cloud kernels),
 // a cloud whose `running` / `active` byte is clear is skipped by whole workgroups, a null byte array runs every cloud.  The
@@ -404,6 +405,107 @@ __global__ __launch_bounds__(1024) void tbim_retire_kernel(const float *__restri
     if (threadIdx.x == 0) { active[g] = 0; leaving[g] = 0; }
 }
 
+// ---- NUattack / tar_NUattack on the coordinate field: Adam on delta [G][n][3] in metres, no tanh space.
+//   xyz = ori + delta (masked: the other points keep ori), loss = |xyz - ori|_2 + c * score.
+
+// nu_color_clouds_kernel's scheme for the positions: kNuParts workgroups per cloud, each with one partial sum of
+// |xyz - ori|^2 in double; the positions go to feat's columns 0..2 and to the contiguous xyz the pyramid is rebuilt from
+__global__ __launch_bounds__(256) void nu_coord_apply_clouds_kernel(const float *__restrict__ ori, const float *__restrict__ delta,
+                                                                    const uint8_t *__restrict__ mask, const uint8_t *__restrict__ active,
+                                                                    size_t n, float *__restrict__ feat, float *__restrict__ xyz,
+                                                                    double *__restrict__ partials)
+{
+    __shared__ double s_part[4];
+    const int g = blockIdx.y;
+    if (active && !active[g]) return;
+    const size_t base = (size_t)g * n;
+    double s = 0.0;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * 3; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t / 3;
+        const int c = (int)(t % 3);
+        const float x = ori[base * 3 + t];
+        float p = x + delta[base * 3 + t];
+        if (mask && !mask[base + i]) p = x;
+        feat[(base + i) * 6 + c] = p;
+        xyz[base * 3 + t] = p;
+        const double d = (double)p - (double)x;         // exact; the sum is of the positions as written
+        s += d * d;
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[(size_t)g * gridDim.x + blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+}
+
+// nu_adam_clouds_kernel without the tanh chain: d xyz / d delta = mask; the score's gradient is the feature path's plus the
+// position branch's, one fp32 add (psg_rla_bim_step_field)
+__global__ void nu_coord_adam_clouds_kernel(const float *__restrict__ ori, float *__restrict__ delta, float *__restrict__ m,
+                                            float *__restrict__ v, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ active,
+                                            const float *__restrict__ xyz, const float *__restrict__ dfeat, const float *__restrict__ dxyz,
+                                            const float *__restrict__ dist2, size_t n, float c, float lr_arg,
+                                            const float *__restrict__ consts, float b1, float b2, float eps)
+{
+    const int g = blockIdx.y;
+    if (active && !active[g]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * 3) return;
+    const float lr_t = consts ? consts[3] : lr_arg;
+    const size_t i = (size_t)g * n + t / 3;
+    const int ch = (int)(t % 3);
+    t += (size_t)g * n * 3;
+    const float x = ori[t], p = xyz[t];
+    const float dist = sqrtf(dist2[g]);
+    const float ds = dfeat[i * 6 + ch] + dxyz[t];
+    float gr = (dist > 0.0f ? (p - x) / dist : 0.0f) + c * ds;
+    if (mask && !mask[i]) gr = 0.0f;                    // (not a product: whatever the gradient buffers hold there)
+    const float mm = b1 * m[t] + (1.0f - b1) * gr;
+    const float vv = b2 * v[t] + (1.0f - b2) * gr * gr;
+    m[t] = mm;
+    v[t] = vv;
+    delta[t] -= lr_t * mm / (sqrtf(vv) + eps);
+}
+
+// Field latch, second half: nu_latch_commit_kernel with the 4-column row {nc, nh, d2_rgb, d2_xyz} and a snapshot that carries
+// the positions too.  Workgroup 0 writes the row, the statistics, exit_step and active.
+__global__ __launch_bounds__(256) void nu_field_latch_commit_kernel(const float *__restrict__ feat, const int32_t *__restrict__ pred,
+                                                                    const float *__restrict__ dist2_rgb, const float *__restrict__ dist2_xyz,
+                                                                    const int32_t *__restrict__ n_mask, const int32_t *__restrict__ scratch,
+                                                                    int n, int mode, int num, int den, int step_arg, int can_exit, int final,
+                                                                    const float *__restrict__ consts, float *__restrict__ hist_row,
+                                                                    float *__restrict__ out_adv_xyz, float *__restrict__ out_adv,
+                                                                    int32_t *__restrict__ out_pred, float *__restrict__ out_stats,
+                                                                    uint8_t *__restrict__ active, int32_t *__restrict__ exit_step)
+{
+    const int g = blockIdx.y, parts = gridDim.x;
+    const int32_t *sc = scratch + (size_t)g * (2 * parts + 1);
+    if (!sc[0]) return;
+    const int step = consts ? __builtin_bit_cast(int, consts[0]) : step_arg;
+    int nc, nh;
+    latch_counts(sc, parts, nc, nh);
+    const bool fire = mode == 0 ? (long long)den * nc < (long long)num * n : (long long)den * nh > (long long)num * n_mask[g];
+    const bool exits = fire && can_exit && step >= 1;
+    if (exits || final) {
+        int lo, hi;
+        latch_slice(n, parts, lo, hi);
+        for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+            const size_t r = (size_t)g * n + i;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                out_adv_xyz[r * 3 + k] = feat[r * 6 + k];
+                out_adv[r * 3 + k] = feat[r * 6 + 3 + k];
+            }
+            out_pred[r] = pred[r];
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const float row[4] = {(float)nc, (float)nh, dist2_rgb ? dist2_rgb[g] : 0.0f, dist2_xyz[g]};
+        for (int k = 0; k < 4; ++k) hist_row[g * 4 + k] = row[k];
+        if (exits || final)
+            for (int k = 0; k < 4; ++k) out_stats[g * 4 + k] = row[k];
+        if (exits) { exit_step[g] = step; active[g] = 0; }
+    }
+}
+
 }  // namespace
 
 // ---- one cloud
@@ -712,4 +814,118 @@ extern "C" int psg_rla_tbim_window(const psg_rla_tbim_window_args *a, psg_nu_gra
     const bool plain = a->ws->prof.on || a->ws->xyz_branch_model != a->model->gen;
     return nu_graph_window(plain ? nullptr : graph, &key, sizeof(key), a->model->gen, a->ws->gen, a->n_steps, a->it0, a->it0, 0.0f, 0.9f, 0.999f,
                            (hipStream_t)stream, [&](const float *rows) { return rla_tbim_window_steps(a, rows, stream); });
+}
+
+// ---- NUattack / tar_NUattack on the coordinate field, G clouds in lockstep
+
+extern "C" int psg_rla_nu_coord_apply_clouds(const float *ori_xyz, const float *delta, const uint8_t *mask, const uint8_t *active, int G,
+                                             int n, float *feat, float *xyz, float *dist2_xyz, double *partials, psg_stream stream)
+{
+    PSG_REQUIRE(ori_xyz && delta && feat && xyz && dist2_xyz && partials, "psg_rla_nu_coord_apply_clouds: null argument");
+    if (int rc = check_clouds("psg_rla_nu_coord_apply_clouds", G, n)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nu_coord_apply_clouds_kernel, dim3(kNuParts, G), dim3(256), 0, st, ori_xyz, delta, mask, active, (size_t)n, feat, xyz,
+                       partials);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nu_dist2_clouds_kernel, dim3(ceil_div(G, 64)), dim3(64), 0, st, (const double *)partials, active, G, kNuParts,
+                       dist2_xyz);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_rla_nu_coord_adam_clouds(const float *ori_xyz, float *delta, float *m_xyz, float *v_xyz, const uint8_t *mask,
+                                            const uint8_t *active, const float *xyz, const float *dfeat, const float *dxyz,
+                                            const float *dist2_xyz, int G, int n, float c, float lr, int t, psg_stream stream)
+{
+    PSG_REQUIRE(ori_xyz && delta && m_xyz && v_xyz && xyz && dfeat && dxyz && dist2_xyz && t >= 1, "psg_rla_nu_coord_adam_clouds: bad argument");
+    if (int rc = check_clouds("psg_rla_nu_coord_adam_clouds", G, n)) return rc;
+    hipLaunchKernelGGL(nu_coord_adam_clouds_kernel, dim3(blocks_for((size_t)n * 3), G), dim3(256), 0, (hipStream_t)stream, ori_xyz, delta,
+                       m_xyz, v_xyz, mask, active, xyz, dfeat, dxyz, dist2_xyz, (size_t)n, c, adam_lr_t(lr, t), psg::nu_step_consts(), 0.9f,
+                       0.999f, 1e-8f);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_rla_nu_field_latch_clouds(const float *logits, const int32_t *labels, const int32_t *ys, const uint8_t *mask,
+                                             const int32_t *n_mask, const float *feat, const float *dist2_rgb, const float *dist2_xyz, int G,
+                                             int n, int mode, int num, int den, int step, int can_exit, int final, float *hist_row,
+                                             int32_t *pred, float *out_adv_xyz, float *out_adv, int32_t *out_pred, float *out_stats,
+                                             uint8_t *active, int32_t *exit_step, int32_t *scratch, psg_stream stream)
+{
+    PSG_REQUIRE(logits && labels && feat && dist2_xyz && hist_row && pred && out_adv_xyz && out_adv && out_pred && out_stats && active &&
+                    exit_step && scratch,
+                "psg_rla_nu_field_latch_clouds: null argument");
+    if (int rc = check_clouds("psg_rla_nu_field_latch_clouds", G, n)) return rc;
+    PSG_REQUIRE(mode == 0 || mode == 1, "psg_rla_nu_field_latch_clouds: mode %d out of range", mode);
+    PSG_REQUIRE(!mask || ys, "psg_rla_nu_field_latch_clouds: a mask needs ys");
+    PSG_REQUIRE(mode == 0 || (mask && n_mask), "psg_rla_nu_field_latch_clouds: mode 1 needs mask and n_mask");
+    PSG_REQUIRE(num >= 0 && den > 0 && step >= 0, "psg_rla_nu_field_latch_clouds: num=%d den=%d step=%d out of range", num, den, step);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nu_latch_count_kernel, dim3(kNuParts, G), dim3(256), 0, st, logits, labels, ys, mask, (const uint8_t *)active, n, pred,
+                       scratch);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nu_field_latch_commit_kernel, dim3(kNuParts, G), dim3(256), 0, st, feat, (const int32_t *)pred, dist2_rgb, dist2_xyz,
+                       n_mask, (const int32_t *)scratch, n, mode, num, den, step, can_exit, final, psg::nu_step_consts(), hist_row, out_adv_xyz,
+                       out_adv, out_pred, out_stats, active, exit_step);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+// the positions of the step into the workspace and the pyramid of all clouds on them: psg_rla_set_cloud's two steps, from the
+// window's own device buffer; stream-ordered, nothing is read back
+static int rla_field_pyramid(psg_rla_ws *ws, const float *xyz, psg_stream stream)
+{
+    PSG_CHECK_HIP(hipMemcpyAsync(ws->xyz_all, xyz, (size_t)ws->N * 3 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return build_pyramid(ws, stream);
+}
+
+extern "C" int psg_rla_nu_field_window(const psg_rla_nu_field_window_args *a, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws, "psg_rla_nu_field_window: null argument");
+    PSG_REQUIRE(a->field == PSG_NU_FIELD_COORD || a->field == PSG_NU_FIELD_BOTH, "psg_rla_nu_field_window: field %d is neither coord nor both",
+                a->field);
+    const bool both = a->field == PSG_NU_FIELD_BOTH;
+    PSG_REQUIRE(a->delta && a->m_xyz && a->v_xyz && a->ori_xyz && a->xyz && a->dxyz && a->labels && a->ys && a->feat && a->logits &&
+                    a->dlogits && a->dfeat && a->dist2_xyz && a->partials_xyz && a->pred && a->scratch && a->hist && a->out_adv &&
+                    a->out_adv_xyz && a->out_pred && a->out_stats && a->active && a->exit_step,
+                "psg_rla_nu_field_window: null argument");
+    PSG_REQUIRE(!both || (a->xs && a->dws && a->m && a->v && a->dist2 && a->partials),
+                "psg_rla_nu_field_window: field both needs the colour variable (xs, dws, m, v, dist2, partials)");
+    PSG_REQUIRE(a->ws->full, "psg_rla_nu_field_window: the workspace was not made by psg_rla_ws_create_full");
+    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->Nc,
+                "psg_rla_nu_field_window: the workspace is for %d clouds of %d points, the window for %d of %d", a->ws->B, a->ws->Nc, a->G, a->N);
+    if (int rc = check_clouds("psg_rla_nu_field_window", a->G, a->N)) return rc;
+    PSG_REQUIRE(a->n_steps >= 1, "psg_rla_nu_field_window: n_steps=%d (at least 1)", a->n_steps);
+    PSG_REQUIRE(a->adam_t0 >= 1, "psg_rla_nu_field_window: adam_t0=%d (the first step is 1)", a->adam_t0);
+    PSG_REQUIRE(a->mode == 0 || a->mode == 1, "psg_rla_nu_field_window: mode %d out of range", a->mode);
+    PSG_REQUIRE(a->mode == 0 || (a->mask && a->n_mask), "psg_rla_nu_field_window: mode 1 needs mask and n_mask");
+    PSG_REQUIRE(a->num >= 0 && a->den > 0, "psg_rla_nu_field_window: threshold %d / %d out of range", a->num, a->den);
+    ProfBind bind(a->ws);
+    const int G = a->G, N = a->N;
+    const int total = a->n_steps + (a->tail_eval ? 1 : 0);
+    const float *d2_rgb = both ? a->dist2 : nullptr;
+    int rc = PSG_OK;
+    for (int i = 0; i < total && rc == PSG_OK; ++i) {
+        const int t = a->adam_t0 + i;                // Adam index of the step; the forward before it evaluates index t - 1
+        const bool tail = i == a->n_steps;
+        if ((rc = psg_rla_nu_coord_apply_clouds(a->ori_xyz, a->delta, a->mask, a->active, G, N, a->feat, a->xyz, a->dist2_xyz,
+                                                a->partials_xyz, stream)))
+            break;
+        if (both && (rc = psg_rla_nu_color_clouds(a->xs, a->dws, a->mask, a->active, G, N, a->feat, a->dist2, a->partials, stream))) break;
+        if ((rc = rla_field_pyramid(a->ws, a->xyz, stream))) break;
+        if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
+        rc = psg_rla_nu_field_latch_clouds(a->logits, a->labels, a->ys, a->mask, a->n_mask, a->feat, d2_rgb, a->dist2_xyz, G, N, a->mode,
+                                           a->num, a->den, t - 1, t - 1 >= 1 ? 1 : 0, tail ? 1 : 0, a->hist + (size_t)i * 4 * G, a->pred,
+                                           a->out_adv_xyz, a->out_adv, a->out_pred, a->out_stats, a->active, a->exit_step, a->scratch, stream);
+        if (rc != PSG_OK || tail) continue;
+        if ((rc = psg_rla_colper_grad_masked(a->logits, a->ys, a->mask, 1.0f, G * N, a->dlogits, nullptr, stream))) break;
+        if ((rc = psg_rla_backward_full(a->model, a->ws, a->dlogits, a->dfeat, a->dxyz, stream))) break;
+        if ((rc = psg_rla_nu_coord_adam_clouds(a->ori_xyz, a->delta, a->m_xyz, a->v_xyz, a->mask, a->active, a->xyz, a->dfeat, a->dxyz,
+                                               a->dist2_xyz, G, N, a->cs, a->coord_lr, t, stream)))
+            break;
+        if (both)
+            rc = psg_rla_nu_adam_clouds(a->xs, a->dws, a->m, a->v, a->mask, a->active, a->feat, a->dfeat, a->dist2, G, N, a->cs, a->lr, t,
+                                        stream);
+    }
+    return rc;
 }

@@ -21,6 +21,7 @@ per window; the accuracy exits are taken per cloud on the device, in integers.  
 forward on [positions | rgb], the hinge gradient, `psg_rla_backward_full` (feature path + relative-position branch) and the
 field step `psg_rla_bim_step_field` - under "both" followed by the unchanged colour step, each field normalised and clipped
 on its own with its own (magnitude, alpha); coordinates have no box.  `field="color"` is the code above, byte for byte.
+NUattack / tar_NUattack refuse the other fields here; their coordinate-field forms are the subclasses of `randla/nu_field.py`.
 """
 import ctypes
 
@@ -32,7 +33,8 @@ from pointsecguard_amd.attacks.torchattacks.attacks._common import check_field
 from pointsecguard_amd.randla import network
 
 _FIELD_ONLY = ("field=%r: the coordinate field runs in BIM / NBattack / TBIM / tar_NBattack.batch_attack with batch_size == 1 "
-               "(one cloud per call); %s moves colours only")
+               "(one cloud per call); %s moves colours only (the NU attacks on this field: randla.nu_field.NUattackField / "
+               "tar_NUattackField)")
 
 CHUNK = 10  # optimiser steps per device-side window (the CHUNK of the other networks' NU attacks)
 

@@ -9,7 +9,12 @@ all of them (workspaces, first eager windows, graph capture) every run times (a)
 (at least 3), on a side stream, synchronised around each timed region.  Prints min / median / max clouds per second, ms per
 optimiser step and cloud, and the hipGraph bookkeeping of each lockstep shape as one JSON line.
 
-    python tools/rla_nu_time.py [--runs 3] [--clouds 8] [--steps 20] [--points 40960] [--out profiles/r18_rla_nu.json]
+--field coord | both times the coordinate-field attack instead (randla/nu_field.py, psg_rla_nu_field_window: the pyramid of
+every cloud rebuilt in every step, the full backward, no hipGraph): there is no host loop for that field, so leg (a) is left out
+and the colour lockstep legs stay as the baseline the field legs alternate with; the JSON line then also carries `field` and the
+bytes of each full workspace.  With the default, --field color, nothing changes.
+
+    python tools/rla_nu_time.py [--runs 3] [--clouds 8] [--steps 20] [--points 40960] [--field color] [--out profiles/r18_rla_nu.json]
 """
 import argparse
 import json
@@ -23,7 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from pointsecguard_amd import _lib  # noqa: E402
-from pointsecguard_amd.randla import attack, network  # noqa: E402
+from pointsecguard_amd.randla import attack, network, nu_field  # noqa: E402
 from pointsecguard_amd.synthetic import randla_params  # noqa: E402
 
 
@@ -34,6 +39,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--points", type=int, default=40960)
     ap.add_argument("--sizes", default="1,4,8")
+    ap.add_argument("--field", default="color", choices=("color", "coord", "both"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     runs, clouds, n = max(3, a.runs), a.clouds, a.points
@@ -51,6 +57,12 @@ def main():
         lock[G] = attack.NUattack(model, 1, "ut", "l_2")
         lock[G].config(cs=1.0, iteration=a.steps)
         lock[G].EXIT_RATIO = (0, 1)                      # den * n_correct < 0 never holds
+    moved = {}
+    if a.field != "color":
+        for G in sizes:
+            moved[G] = nu_field.NUattackField(model, 1, "ut", "l_2", field=a.field)
+            moved[G].config(cs=1.0, iteration=a.steps)
+            moved[G].EXIT_RATIO = (0, 1)
     steps_run = {}
     with torch.cuda.stream(side):
         feats = torch.from_numpy(feats_h).cuda()
@@ -77,7 +89,19 @@ def main():
             leg.__name__ = "batch_attack_clouds_G%d" % G
             return leg
 
+        def field_leg(G):
+            def leg():
+                done = 0
+                for i in range(0, clouds, G):
+                    moved[G].batch_attack_clouds(feats[i:i + G], labels[i:i + G])
+                    done += int(moved[G].last_steps.sum())
+                steps_run[leg.__name__] = done
+            leg.__name__ = "field_%s_G%d" % (a.field, G)
+            return leg
+
         legs = [per_cloud] + [lockstep(G) for G in sizes]
+        if a.field != "color":
+            legs = [f for G in sizes for f in (lockstep(G), field_leg(G))]
         times = {f.__name__: [] for f in legs}
         np.random.seed(0)
         for f in legs:                                   # warm-up: workspaces, eager first windows, the capture
@@ -100,6 +124,9 @@ def main():
     for G in sizes:
         S = lock[G]._clouds[(n, G)]
         res["graphs"]["G%d" % G] = dict(full=_lib.capture_stats(S.graph), full_with_tail=_lib.capture_stats(S.graph_tail))
+    if a.field != "color":
+        res["field"] = a.field
+        res["full_workspace_bytes"] = {"G%d" % G: int(moved[G]._field_clouds[(n, G)].ws.nbytes) for G in sizes}
     res["capture_stats_process"] = _lib.capture_stats()
     res["largest_spread_of_a_figure"] = max(max(v["clouds_per_s_max"] / v["clouds_per_s_min"] for v in res["figures"].values()) - 1.0, 0.0)
     line = json.dumps(res)
