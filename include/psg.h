@@ -1144,6 +1144,76 @@ typedef struct psg_rla_nu_field_window_args {
 } psg_rla_nu_field_window_args;
 int psg_rla_nu_field_window(const psg_rla_nu_field_window_args *args, psg_stream stream);
 
+/* BIM / NBattack and TBIM / tar_NBattack on the COORDINATE field of G clouds of n points in lockstep.
+ *
+ * psg_rla_bim_step_field_clouds: psg_rla_bim_step_field's update of every running cloud (running [G] bytes, NULL: all) of
+ * feat [G][n][6] with that cloud's own norms: norms [2][G] = {|g|^2, |delta|^2} of cloud g, delta [G][n][3] (both l_2 only),
+ * g = dfeat[:, 0:3] + dxyz as one fp32 add, no box.  The same kernels serve psg_rla_bim_step_field (G = 1) and keep its
+ * summation order (one workgroup per cloud, double accumulation, the fixed tree), so a cloud's positions are bit-equal to
+ * psg_rla_bim_step_field on that cloud alone.  xyz_out [G][n][3] (nullable): the new positions, contiguous - the bytes of
+ * feat's columns 0..2 - for the pyramid rebuild.  No byte of feat, delta, norms or xyz_out of a cloud that is not running is
+ * written, whatever its gradients hold. */
+int psg_rla_bim_step_field_clouds(float *feat, const float *dfeat, const float *dxyz, const float *ori_xyz, const uint8_t *running,
+                                  int G, int n, float eps, float alpha, int l2_metric, float *norms, float *delta, float *xyz_out,
+                                  psg_stream stream);
+/* psg_rla_tbim_retire_clouds with both halves of feat snapshot: every active cloud that is leaving (or, final != 0, every
+ * active cloud) gets out_adv_xyz [G][n][3] = columns 0..2 and out_adv [G][n][3] = columns 3..5 of feat [G][n][6], then
+ * active[g] = 0 and leaving[g] = 0. */
+int psg_rla_tbim_retire_field_clouds(const float *feat, int G, int n, int final, float *out_adv, float *out_adv_xyz, uint8_t *active,
+                                     uint8_t *leaving, psg_stream stream);
+
+/* One window of the lockstep BIM family on the coordinate field, or on both fields.  For each of n_steps iterations
+ * it = it0 + i: the index pyramid of all G clouds rebuilt from `xyz` (what psg_rla_set_cloud(ws, xyz) does, stream-ordered, no
+ * read-back; the caller puts the starting positions there), psg_rla_forward on feat, in mode 1 psg_rla_tbim_latch_clouds
+ * (history row i [G][3]; final on the window's last step when `final` is set), psg_rla_colper_grad_masked against loss_ys with
+ * mask and `sign` (mode 0: against labels, no mask, sign +1), psg_rla_backward_full, psg_rla_bim_step_field_clouds with
+ * (coord_eps, coord_alpha) on the active clouds, writing `xyz`; field BOTH: then psg_rla_bim_step_clouds with (eps, alpha) on
+ * the colours; psg_rla_tbim_retire_field_clouds.  `delta` is the scratch of both steps, one after the other.
+ *   mode 1 (TBIM): psg_rla_tbim_window's semantics - the update of the exiting iteration is still applied to the leaving cloud,
+ *     its snapshot is the prediction BEFORE that update and the positions and colours AFTER it, the cap is snapshot the same
+ *     way under `final`, there is no tail forward.
+ *   mode 0 (BIM, goal 'ut'): no latch, no exit; every active cloud takes every step; `final` on the window's last step snapshots
+ *     all of them (out_adv, out_adv_xyz) and clears `active`.  hist, mask, n_mask, hit_ys, loss_ys, leaving and exit_step may be
+ *     NULL; sign, num and den are not used (den > 0 is still required).
+ * A retired cloud's positions, colours and snapshot are not touched; its pyramid is rebuilt from unchanged positions, to the
+ * same bits.  Eager: there is no hipGraph form (the pyramid's sorts are not captured).  PSG_ERR_ARG, before anything is
+ * enqueued: a workspace that is not psg_rla_ws_create_full's, (G, N) not the workspace's, field not COORD / BOTH, mode not 0 / 1,
+ * n_steps < 1, it0 < 0, den <= 0, mode 1 without mask / n_mask / hit_ys / loss_ys / hist / leaving / exit_step, l_2 without
+ * norms_xyz / delta (BOTH: norms), BOTH without ori, any other null pointer (COORD needs neither ori nor norms). */
+typedef struct psg_rla_bim_field_window_args {
+    psg_rla_model *model;
+    psg_rla_ws *ws;              /* psg_rla_ws_create_full, G clouds of N points */
+    int n_steps, G, N, it0;
+    int num, den;                /* the exit threshold num / den (mode 1) */
+    int final, l2_metric;
+    int mode, field;             /* 0 BIM / 1 TBIM; PSG_NU_FIELD_COORD or PSG_NU_FIELD_BOTH */
+    float eps, alpha, sign;      /* the colours' (BOTH); sign: -1 for goal 't' / 'tm', +1 for goal 'ut' (mode 1) */
+    float coord_eps, coord_alpha;   /* the positions' (4 bytes of padding follow) */
+    const float *ori;            /* [G][N][3] clean colours (BOTH) */
+    const uint8_t *mask;         /* [G][N] (mode 1) */
+    const int32_t *n_mask;       /* [G] (mode 1) */
+    const int32_t *labels, *hit_ys, *loss_ys;   /* [G][N] (hit_ys, loss_ys: mode 1) */
+    float *feat;                 /* [G][N][6] */
+    float *logits, *dlogits;     /* [G][N][13] */
+    float *dfeat;                /* [G][N][6] */
+    float *norms;                /* [2][G] (l_2, BOTH) */
+    float *delta;                /* [G][N][3] (l_2) */
+    int32_t *pred;               /* [G][N] */
+    int32_t *scratch;            /* [G][2 * PSG_RLA_NU_PARTS + 1] */
+    float *hist;                 /* [n_steps][G][3] (mode 1) */
+    float *out_adv;              /* [G][N][3] */
+    int32_t *out_pred;           /* [G][N] */
+    float *out_stats;            /* [G][3] */
+    uint8_t *active, *leaving;   /* [G] (leaving: mode 1) */
+    int32_t *exit_step;          /* [G], -1 before (mode 1) */
+    const float *ori_xyz;        /* [G][N][3] clean positions */
+    float *xyz;                  /* [G][N][3] the positions of the iteration, contiguous */
+    float *dxyz;                 /* [G][N][3] */
+    float *norms_xyz;            /* [2][G] (l_2) */
+    float *out_adv_xyz;          /* [G][N][3] */
+} psg_rla_bim_field_window_args;
+int psg_rla_bim_field_window(const psg_rla_bim_field_window_args *args, psg_stream stream);
+
 /* ------------------------------------------------------------------------------------------
  * RandLA-Net data preparation: grid sub-sampling and the projection of raw points onto the sub-cloud (psg_grid.hip).
  *

@@ -171,6 +171,9 @@ SIGNATURES = {
     "psg_rla_nu_field_latch_clouds": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp,
                                            vp, vp, vp]),
     "psg_rla_nu_field_window": (ci, [vp, vp]),
+    "psg_rla_bim_step_field_clouds": (ci, [vp, vp, vp, vp, vp, ci, ci, cf, cf, ci, vp, vp, vp, vp]),
+    "psg_rla_tbim_retire_field_clouds": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "psg_rla_bim_field_window": (ci, [vp, vp]),
     "psg_seg_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
     "psg_vote_add": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]),
     "psg_vote_stats": (ci, [vp, vp, ci, ci, vp, vp, vp]),
@@ -255,6 +258,16 @@ class RlaNuFieldWindowArgs(ctypes.Structure):
                 [(n, vp) for n in ("xs", "dws", "m", "v", "delta", "m_xyz", "v_xyz", "ori_xyz", "xyz", "dxyz", "mask", "n_mask", "labels",
                                    "ys", "feat", "logits", "dlogits", "dfeat", "dist2", "dist2_xyz", "partials", "partials_xyz", "pred",
                                    "scratch", "hist", "out_adv", "out_adv_xyz", "out_pred", "out_stats", "active", "exit_step")])
+
+
+class RlaBimFieldWindowArgs(ctypes.Structure):
+    """psg_rla_bim_field_window_args of include/psg.h, field for field (10 ints and 5 floats: 4 bytes of padding follow)."""
+    _fields_ = ([("model", vp), ("ws", vp)] +
+                [(n, ci) for n in ("n_steps", "G", "N", "it0", "num", "den", "final", "l2_metric", "mode", "field")] +
+                [(n, cf) for n in ("eps", "alpha", "sign", "coord_eps", "coord_alpha")] +
+                [(n, vp) for n in ("ori", "mask", "n_mask", "labels", "hit_ys", "loss_ys", "feat", "logits", "dlogits", "dfeat", "norms",
+                                   "delta", "pred", "scratch", "hist", "out_adv", "out_pred", "out_stats", "active", "leaving",
+                                   "exit_step", "ori_xyz", "xyz", "dxyz", "norms_xyz", "out_adv_xyz")])
 
 
 class NuFieldArgs(ctypes.Structure):

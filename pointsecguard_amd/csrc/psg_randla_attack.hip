@@ -1,7 +1,9 @@
 // The colour attacks on RandLA-Net (psg_randla_net.hip): the "colper" loss, the BIM update and loop (ares/ares/attack/
 // bim.py:66-116, :190-236), NUattack / tar_NUattack (NUattack.py:12-74, tar_NUattack.py:12-84) and TBIM / tar_NBattack
 // (bim.py:277-505), for one cloud and for G clouds in lockstep; and the two NU attacks on the point positions (DESIGN.md 5s:
-// psg_rla_nu_coord_apply_clouds / _coord_adam_clouds / _field_latch_clouds, psg_rla_nu_field_window), G clouds in lockstep.
+// psg_rla_nu_coord_apply_clouds / _coord_adam_clouds / _field_latch_clouds, psg_rla_nu_field_window), G clouds in lockstep, and
+// the BIM family's lockstep window on the same field (psg_rla_tbim_retire_field_clouds, psg_rla_bim_field_window;
+// its field step, psg_rla_bim_step_field_clouds, is compiled without contraction in psg_randla_coord.hip).
 //
 // Every update kernel exists once, in the G-cloud form: blockIdx.y = cloud (blockIdx.x for the one-workgroup-per-cloud kernels),
 // a cloud whose `running` / `active` byte is clear is skipped by whole workgroups, a null byte array runs every cloud.  The
@@ -403,6 +405,28 @@ __global__ __launch_bounds__(1024) void tbim_retire_kernel(const float *__restri
     const size_t base = (size_t)g * n;
     for (size_t t = threadIdx.x; t < n * 3; t += blockDim.x) out_adv[base * 3 + t] = feat[(base + t / 3) * 6 + 3 + (t % 3)];
     if (threadIdx.x == 0) { active[g] = 0; leaving[g] = 0; }
+}
+
+// tbim_retire_kernel with both halves of feat snapshot (the coordinate-field TBIM / BIM): columns 0..2 to
+// out_adv_xyz, 3..5 to out_adv.  leaving null (the untargeted window, which has no latch): only `final` retires.
+__global__ __launch_bounds__(1024) void tbim_retire_field_kernel(const float *__restrict__ feat, size_t n, int final,
+                                                                 float *__restrict__ out_adv, float *__restrict__ out_adv_xyz,
+                                                                 uint8_t *__restrict__ active, uint8_t *__restrict__ leaving)
+{
+    const int g = blockIdx.x;
+    const bool go = active[g] != 0 && ((leaving && leaving[g] != 0) || final != 0);
+    __syncthreads();
+    if (!go) return;
+    const size_t base = (size_t)g * n;
+    for (size_t t = threadIdx.x; t < n * 3; t += blockDim.x) {
+        const float *row = feat + (base + t / 3) * 6 + (t % 3);
+        out_adv_xyz[base * 3 + t] = row[0];
+        out_adv[base * 3 + t] = row[3];
+    }
+    if (threadIdx.x == 0) {
+        active[g] = 0;
+        if (leaving) leaving[g] = 0;
+    }
 }
 
 // ---- NUattack / tar_NUattack on the coordinate field: Adam on delta [G][n][3] in metres, no tanh space.
@@ -926,6 +950,75 @@ extern "C" int psg_rla_nu_field_window(const psg_rla_nu_field_window_args *a, ps
         if (both)
             rc = psg_rla_nu_adam_clouds(a->xs, a->dws, a->m, a->v, a->mask, a->active, a->feat, a->dfeat, a->dist2, G, N, a->cs, a->lr, t,
                                         stream);
+    }
+    return rc;
+}
+
+// ---- BIM / TBIM on the coordinate field, G clouds in lockstep
+
+extern "C" int psg_rla_tbim_retire_field_clouds(const float *feat, int G, int n, int final, float *out_adv, float *out_adv_xyz,
+                                                uint8_t *active, uint8_t *leaving, psg_stream stream)
+{
+    PSG_REQUIRE(feat && out_adv && out_adv_xyz && active && leaving, "psg_rla_tbim_retire_field_clouds: null argument");
+    if (int rc = check_clouds("psg_rla_tbim_retire_field_clouds", G, n)) return rc;
+    hipLaunchKernelGGL(tbim_retire_field_kernel, dim3(G), dim3(1024), 0, (hipStream_t)stream, feat, (size_t)n, final, out_adv, out_adv_xyz,
+                       active, leaving);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_rla_bim_field_window(const psg_rla_bim_field_window_args *a, psg_stream stream)
+{
+    PSG_REQUIRE(a && a->model && a->ws, "psg_rla_bim_field_window: null argument");
+    PSG_REQUIRE(a->mode == 0 || a->mode == 1, "psg_rla_bim_field_window: mode %d out of range", a->mode);
+    PSG_REQUIRE(a->field == PSG_NU_FIELD_COORD || a->field == PSG_NU_FIELD_BOTH, "psg_rla_bim_field_window: field %d is neither coord nor both",
+                a->field);
+    const bool both = a->field == PSG_NU_FIELD_BOTH, tbim = a->mode == 1;
+    PSG_REQUIRE(a->ori_xyz && a->xyz && a->dxyz && a->out_adv_xyz && a->labels && a->feat && a->logits && a->dlogits && a->dfeat && a->pred &&
+                    a->scratch && a->out_adv && a->out_pred && a->out_stats && a->active,
+                "psg_rla_bim_field_window: null argument");
+    PSG_REQUIRE(!tbim || (a->mask && a->n_mask && a->hit_ys && a->loss_ys && a->hist && a->leaving && a->exit_step),
+                "psg_rla_bim_field_window: mode 1 needs mask, n_mask, hit_ys, loss_ys, hist, leaving and exit_step");
+    PSG_REQUIRE(!a->l2_metric || (a->norms_xyz && a->delta && (!both || a->norms)),
+                "psg_rla_bim_field_window: the l_2 metric needs norms_xyz and delta (field both: norms too)");
+    PSG_REQUIRE(!both || a->ori, "psg_rla_bim_field_window: field both needs ori (the clean colours)");
+    PSG_REQUIRE(a->ws->full, "psg_rla_bim_field_window: the workspace was not made by psg_rla_ws_create_full");
+    PSG_REQUIRE(a->G == a->ws->B && a->N == a->ws->Nc,
+                "psg_rla_bim_field_window: the workspace is for %d clouds of %d points, the window for %d of %d", a->ws->B, a->ws->Nc, a->G, a->N);
+    if (int rc = check_clouds("psg_rla_bim_field_window", a->G, a->N)) return rc;
+    PSG_REQUIRE(a->n_steps >= 1, "psg_rla_bim_field_window: n_steps=%d (at least 1)", a->n_steps);
+    PSG_REQUIRE(a->it0 >= 0, "psg_rla_bim_field_window: it0=%d (the first iteration is 0)", a->it0);
+    PSG_REQUIRE(a->num >= 0 && a->den > 0, "psg_rla_bim_field_window: threshold %d / %d out of range", a->num, a->den);
+    ProfBind bind(a->ws);
+    hipStream_t st = (hipStream_t)stream;
+    const int G = a->G, N = a->N;
+    int rc = PSG_OK;
+    for (int i = 0; i < a->n_steps && rc == PSG_OK; ++i) {
+        const int final = (a->final && i == a->n_steps - 1) ? 1 : 0;
+        if ((rc = rla_field_pyramid(a->ws, a->xyz, stream))) break;
+        if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
+        if (tbim) {
+            if ((rc = psg_rla_tbim_latch_clouds(a->logits, a->labels, a->hit_ys, a->mask, a->n_mask, G, N, a->num, a->den, a->it0 + i, final,
+                                                a->hist + (size_t)i * 3 * G, a->pred, a->out_pred, a->out_stats, a->active, a->leaving,
+                                                a->exit_step, a->scratch, stream)))
+                break;
+            rc = psg_rla_colper_grad_masked(a->logits, a->loss_ys, a->mask, a->sign, G * N, a->dlogits, nullptr, stream);
+        } else {
+            rc = psg_rla_colper_grad_masked(a->logits, a->labels, nullptr, 1.0f, G * N, a->dlogits, nullptr, stream);
+        }
+        if (rc) break;
+        if ((rc = psg_rla_backward_full(a->model, a->ws, a->dlogits, a->dfeat, a->dxyz, stream))) break;
+        if ((rc = psg_rla_bim_step_field_clouds(a->feat, a->dfeat, a->dxyz, a->ori_xyz, a->active, G, N, a->coord_eps, a->coord_alpha,
+                                                a->l2_metric, a->norms_xyz, a->delta, a->xyz, stream)))
+            break;
+        if (both && (rc = psg_rla_bim_step_clouds(a->feat, a->dfeat, a->ori, a->active, G, N, a->eps, a->alpha, a->l2_metric, a->norms,
+                                                  a->delta, stream)))
+            break;
+        if (tbim || final) {        // (the untargeted loop has no latch and no exit: only the cap retires, every cloud)
+            hipLaunchKernelGGL(tbim_retire_field_kernel, dim3(G), dim3(1024), 0, st, (const float *)a->feat, (size_t)N, final, a->out_adv,
+                               a->out_adv_xyz, a->active, a->leaving);
+            PSG_LAUNCH_CHECK();
+        }
     }
     return rc;
 }

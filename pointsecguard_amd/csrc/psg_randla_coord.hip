@@ -58,20 +58,27 @@ __global__ void point_sum_kernel(const float4 *__restrict__ side_i, const float4
     gxyz[p * 3] = ax; gxyz[p * 3 + 1] = ay; gxyz[p * 3 + 2] = az;
 }
 
-// ---- BIM step on the coordinate columns 0:3 of feat [n][6] (bim.py:84-96), g = dfeat[:, 0:3] + dxyz as one fp32 add; no clip
-// to a box.  The l_2 norms in psg_rla_bim_step's order: one workgroup, every thread its strided elements in double, a fixed tree.
+// ---- BIM step on the coordinate columns 0:3 of feat [G][n][6] (bim.py:84-96), g = dfeat[:, 0:3] + dxyz as one fp32 add; no clip
+// to a box.  One copy of the kernels for 1 and G clouds, as bim_step's in psg_randla_attack.hip: blockIdx.y = cloud (blockIdx.x
+// for the norm kernel), a cloud whose `running` byte is clear is skipped by whole workgroups, a null byte array runs every
+// cloud.  The l_2 norms in psg_rla_bim_step's order: one workgroup per cloud, every thread its strided elements in double, a
+// fixed tree.  The apply kernels also write the new position into the contiguous xyz_out [G][n][3] when it is given.
 __device__ __forceinline__ float field_grad(const float *__restrict__ dfeat, const float *__restrict__ dxyz, size_t t)
 {
     return dfeat[(t / 3) * 6 + (t % 3)] + dxyz[t];
 }
 
+// dfeat / dxyz (delta null) or delta: the arrays of all clouds; out[cloud]
 __global__ __launch_bounds__(1024) void field_sq_norm_kernel(const float *__restrict__ dfeat, const float *__restrict__ dxyz,
-                                                              const float *__restrict__ delta, size_t n, float *__restrict__ out)
+                                                              const float *__restrict__ delta, const uint8_t *__restrict__ running,
+                                                              size_t n, float *__restrict__ out)
 {
     __shared__ double s_part[16];
+    if (running && !running[blockIdx.x]) return;
+    const size_t base = (size_t)blockIdx.x * n * 3;
     double s = 0.0;
     for (size_t t = threadIdx.x; t < n * 3; t += blockDim.x) {
-        const float v = delta ? delta[t] : field_grad(dfeat, dxyz, t);
+        const float v = delta ? delta[base + t] : field_grad(dfeat, dxyz, base + t);
         s += (double)v * (double)v;
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -80,40 +87,80 @@ __global__ __launch_bounds__(1024) void field_sq_norm_kernel(const float *__rest
     if (threadIdx.x == 0) {
         double tot = 0.0;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_part[w];
-        out[0] = (float)tot;
+        out[blockIdx.x] = (float)tot;
     }
 }
 
 __global__ void field_linf_kernel(float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ dxyz,
-                                  const float *__restrict__ ori, size_t n, float alpha, float eps)
+                                  const float *__restrict__ ori, const uint8_t *__restrict__ running, size_t n, float alpha, float eps,
+                                  float *__restrict__ xyz_out)
 {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int cl = blockIdx.y;
+    if (running && !running[cl]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * 3) return;
+    t += (size_t)cl * n * 3;
     const size_t at = (t / 3) * 6 + (t % 3);
     const float g = field_grad(dfeat, dxyz, t), x = ori[t];
     const float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
     const float v = feat[at] + alpha * sg;
-    feat[at] = fminf(fmaxf(v, x - eps), x + eps);
+    const float p = fminf(fmaxf(v, x - eps), x + eps);
+    feat[at] = p;
+    if (xyz_out) xyz_out[t] = p;
 }
 
 __global__ void field_l2_delta_kernel(const float *__restrict__ feat, const float *__restrict__ dfeat, const float *__restrict__ dxyz,
-                                      const float *__restrict__ ori, size_t n, float alpha, const float *__restrict__ gnorm2,
-                                      float *__restrict__ delta)
+                                      const float *__restrict__ ori, const uint8_t *__restrict__ running, size_t n, float alpha,
+                                      const float *__restrict__ gnorm2, float *__restrict__ delta)
 {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int cl = blockIdx.y;
+    if (running && !running[cl]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * 3) return;
-    const float gn = fmaxf(1e-12f, sqrtf(gnorm2[0]));
+    t += (size_t)cl * n * 3;
+    const float gn = fmaxf(1e-12f, sqrtf(gnorm2[cl]));            // the cloud's own gradient norm
     delta[t] = feat[(t / 3) * 6 + (t % 3)] - ori[t] + alpha * (field_grad(dfeat, dxyz, t) / gn);
 }
 
-__global__ void field_l2_apply_kernel(float *__restrict__ feat, const float *__restrict__ ori, const float *__restrict__ delta, size_t n,
-                                      float eps, const float *__restrict__ dnorm2)
+__global__ void field_l2_apply_kernel(float *__restrict__ feat, const float *__restrict__ ori, const float *__restrict__ delta,
+                                      const uint8_t *__restrict__ running, size_t n, float eps, const float *__restrict__ dnorm2,
+                                      float *__restrict__ xyz_out)
 {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int cl = blockIdx.y;
+    if (running && !running[cl]) return;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * 3) return;
-    const float dn = sqrtf(dnorm2[0]);
+    t += (size_t)cl * n * 3;
+    const float dn = sqrtf(dnorm2[cl]);
     const float scale = dn > eps ? eps / dn : 1.0f;
-    feat[(t / 3) * 6 + (t % 3)] = ori[t] + delta[t] * scale;
+    const float p = ori[t] + delta[t] * scale;
+    feat[(t / 3) * 6 + (t % 3)] = p;
+    if (xyz_out) xyz_out[t] = p;
+}
+
+// One field step of the running clouds: one launch for l_inf, four for l_2 (norms [2][G] and delta [G][n][3] are its scratch).
+// The one copy behind psg_rla_bim_step_field (G = 1) and psg_rla_bim_step_field_clouds.
+int field_step(float *feat, const float *dfeat, const float *dxyz, const float *ori, const uint8_t *running, int G, int n, float eps,
+               float alpha, int l2, float *norms, float *delta, float *xyz_out, hipStream_t st)
+{
+    const size_t N = (size_t)n;
+    const dim3 grid(blocks_for(N * 3), G);
+    if (!l2) {
+        hipLaunchKernelGGL(field_linf_kernel, grid, dim3(256), 0, st, feat, dfeat, dxyz, ori, running, N, alpha, eps, xyz_out);
+        PSG_LAUNCH_CHECK();
+        return PSG_OK;
+    }
+    hipLaunchKernelGGL(field_sq_norm_kernel, dim3(G), dim3(1024), 0, st, dfeat, dxyz, (const float *)nullptr, running, N, norms);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(field_l2_delta_kernel, grid, dim3(256), 0, st, (const float *)feat, dfeat, dxyz, ori, running, N, alpha,
+                       (const float *)norms, delta);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(field_sq_norm_kernel, dim3(G), dim3(1024), 0, st, dfeat, dxyz, (const float *)delta, running, N, norms + G);
+    PSG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(field_l2_apply_kernel, grid, dim3(256), 0, st, feat, ori, (const float *)delta, running, N, eps,
+                       (const float *)(norms + G), xyz_out);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
 }
 
 }  // namespace
@@ -137,20 +184,16 @@ extern "C" int psg_rla_bim_step_field(float *feat, const float *dfeat, const flo
                                       float alpha, int l2_metric, float *norms, float *delta, psg_stream stream)
 {
     PSG_REQUIRE(feat && dfeat && dxyz && ori_xyz && n > 0 && (!l2_metric || (norms && delta)), "psg_rla_bim_step_field: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t N = (size_t)n;
-    if (!l2_metric) {
-        hipLaunchKernelGGL(field_linf_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, feat, dfeat, dxyz, ori_xyz, N, alpha, eps);
-        PSG_LAUNCH_CHECK();
-        return PSG_OK;
-    }
-    hipLaunchKernelGGL(field_sq_norm_kernel, dim3(1), dim3(1024), 0, st, dfeat, dxyz, (const float *)nullptr, N, norms);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(field_l2_delta_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, feat, dfeat, dxyz, ori_xyz, N, alpha, norms, delta);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(field_sq_norm_kernel, dim3(1), dim3(1024), 0, st, dfeat, dxyz, (const float *)delta, N, norms + 1);
-    PSG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(field_l2_apply_kernel, dim3(blocks_for(N * 3)), dim3(256), 0, st, feat, ori_xyz, delta, N, eps, norms + 1);
-    PSG_LAUNCH_CHECK();
-    return PSG_OK;
+    return field_step(feat, dfeat, dxyz, ori_xyz, nullptr, 1, n, eps, alpha, l2_metric, norms, delta, nullptr, (hipStream_t)stream);
+}
+
+// psg_rla_bim_step_field's update of every running cloud with that cloud's own norms (the limits: psg_randla_attack.hip's
+// check_clouds - G is a grid dimension, G * n rows are indexed by 32-bit ints on the host side)
+extern "C" int psg_rla_bim_step_field_clouds(float *feat, const float *dfeat, const float *dxyz, const float *ori_xyz, const uint8_t *running,
+                                             int G, int n, float eps, float alpha, int l2_metric, float *norms, float *delta, float *xyz_out,
+                                             psg_stream stream)
+{
+    PSG_REQUIRE(feat && dfeat && dxyz && ori_xyz && (!l2_metric || (norms && delta)), "psg_rla_bim_step_field_clouds: null argument");
+    PSG_REQUIRE(G > 0 && G <= 65535 && n > 0 && (size_t)G * n <= (size_t)1 << 20, "psg_rla_bim_step_field_clouds: G=%d n=%d out of range", G, n);
+    return field_step(feat, dfeat, dxyz, ori_xyz, running, G, n, eps, alpha, l2_metric, norms, delta, xyz_out, (hipStream_t)stream);
 }

@@ -22,6 +22,7 @@ forward on [positions | rgb], the hinge gradient, `psg_rla_backward_full` (featu
 field step `psg_rla_bim_step_field` - under "both" followed by the unchanged colour step, each field normalised and clipped
 on its own with its own (magnitude, alpha); coordinates have no box.  `field="color"` is the code above, byte for byte.
 NUattack / tar_NUattack refuse the other fields here; their coordinate-field forms are the subclasses of `randla/nu_field.py`.
+The lockstep form of these fields for BIM / NBattack / TBIM / tar_NBattack is the subclasses of `randla/nb_field.py`.
 """
 import ctypes
 
@@ -34,7 +35,7 @@ from pointsecguard_amd.randla import network
 
 _FIELD_ONLY = ("field=%r: the coordinate field runs in BIM / NBattack / TBIM / tar_NBattack.batch_attack with batch_size == 1 "
                "(one cloud per call); %s moves colours only (the NU attacks on this field: randla.nu_field.NUattackField / "
-               "tar_NUattackField)")
+               "tar_NUattackField; G clouds in lockstep: randla.nb_field.BIMField / NBattackField / TBIMField / tar_NBattackField)")
 
 CHUNK = 10  # optimiser steps per device-side window (the CHUNK of the other networks' NU attacks)
 
