@@ -24,10 +24,12 @@ using psg::sumsq3;
 typedef float v2f __attribute__((ext_vector_type(2)));   // operand of the packed-fp32 pipe (v_pk_*_f32)
 
 // ---- wave-level max with DPP (no LDS round trips) --------------------------------------------
+// `old` is 0, the identity of an unsigned max: a lane the row mask leaves out gets 0 and keeps its own v, exactly as with
+// old = v, and the compiler folds the whole stage into ONE v_max_u32_dpp (with old = v it is v_mov, s_nop, v_mov_dpp, v_max).
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ unsigned dpp_max_u32(unsigned v)
 {
-    unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xF, false);
+    unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
     return o > v ? o : v;
 }
 // max over each row of 16 lanes, result in every lane of the row
@@ -47,69 +49,114 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v)
     v = dpp_max_u32<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
+// max of N keys as a tree of three-input maxima (v_max3_u32), depth ceil(log3 N)
+template <int N>
+__device__ __forceinline__ unsigned max_of(const unsigned (&k)[N])
+{
+    constexpr int G = (N + 2) / 3;
+    unsigned t[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        unsigned a = k[3 * g];
+        if (3 * g + 1 < N) a = max(a, k[3 * g + 1]);
+        if (3 * g + 2 < N) a = max(a, k[3 * g + 2]);
+        t[g] = a;
+    }
+    if constexpr (G == 1) return t[0];
+    else return max_of<G>(t);
+}
 
 // ---------------------------------------------------------------------------------------------
 // FPS: one workgroup per problem; thread t owns the PPT consecutive points PPT*t .. PPT*t+PPT-1
-// (so a lower lane / lower wave always means a lower point index).  xyz stays in LDS for the centroid
-// broadcast and in registers for the distance update.  Per step:
-//   distance update + in-thread argmax  ->  wave max by DPP  ->  ballot picks the lowest lane holding
-//   it  ->  one LDS slot per wave, ONE barrier (slots double-buffered)  ->  16-lane DPP max over the
-//   wave partials, ballot picks the lowest wave.
-// Distances are non-negative floats, compared as their bit patterns (exact same order); ties resolve to
-// the lowest index like torch.max on CPU.
+// (so a lower lane / lower wave always means a lower point index).  The points stay in registers for the
+// distance update; the centroid of a step is broadcast from the cloud in LDS (LDSC) or, in the form that
+// keeps LDS free for more resident problems, read from the cloud in global memory by scalar loads at
+// the wave-uniform index.  Per step:
+//   distance update  ->  per-lane max of the keys  ->  wave max by DPP  ->  ballot picks the lowest lane
+//   holding it, one compare per key against the wave max gives the lanes holding it at point j, and the
+//   lowest j whose mask has the winning lane's bit is picked on the scalar side  ->  one LDS slot per
+//   wave, ONE barrier (slots double-buffered)  ->  16-lane DPP max over the wave partials, ballot picks
+//   the lowest wave.
+// Distances are non-negative floats, kept and compared as their bit patterns (exact same order): the
+// update `d < dist ? d : dist` is an unsigned min on the bits - d is +0 or above, NaN or +inf, never
+// -0, and the bits of a NaN (either sign) or of +inf lie above those of every distance the array can
+// hold (<= 1e10f), so they keep the old distance as `<` does.  A padding point (index >= N) starts at
+// 0, stays at 0 under min, and a key of 0 never beats a real point: at equal keys the lower index
+// wins, and index 0 is real.  Ties resolve to the lowest index like torch.max on CPU.  When every key is 0
+// (all points taken, or S above the number of distinct positions) every lane of every wave ties at 0,
+// the lowest lane's lowest point is picked in wave 0, and the result is index 0.
 // ---------------------------------------------------------------------------------------------
-template <int NT, int PPT>
+template <int NT, int PPT, bool LDSC>
 __global__ __launch_bounds__(NT) void fps_kernel(const float *__restrict__ xyz, int n_clouds, int N, int S,
                                                  const int32_t *__restrict__ start, int32_t *__restrict__ out)
 {
     constexpr int NW = NT / 64;
     extern __shared__ float smem[];
-    float *s_xyz = smem;                                 // [NT*PPT*3] (padded cloud)
-    uint2 *s_part = (uint2 *)(smem + NT * PPT * 3);      // [2][NW] (value bits, index)
+    float *s_xyz = smem;                                           // LDSC: [NT*PPT*3] (padded cloud)
+    uint2 *s_part = (uint2 *)(smem + (LDSC ? NT * PPT * 3 : 0));   // [2][NW] (value bits, index)
 
     const int p = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float *src = xyz + (size_t)(p % n_clouds) * N * 3;
-    for (int i = tid; i < NT * PPT * 3; i += NT) s_xyz[i] = i < N * 3 ? src[i] : 0.0f;
-    __syncthreads();
+    if (LDSC) {
+        for (int i = tid; i < NT * PPT * 3; i += NT) s_xyz[i] = i < N * 3 ? src[i] : 0.0f;
+        __syncthreads();
+    }
 
     // points in registers as pairs: the distance update runs on the packed-fp32 pipe (two points per instruction,
-    // every lane result bit-identical to the scalar sub / mul / add sequence of sumsq3)
+    // every lane result bit-identical to the scalar sub / mul / add sequence of sumsq3); PPT = 1 has one point in
+    // both halves of its pair and a single key
     constexpr int PP = (PPT + 1) / 2;
-    v2f px[PP], py[PP], pz[PP], dist[PP];
+    v2f px[PP], py[PP], pz[PP];
+    unsigned dist[PPT];
 #pragma unroll
     for (int q = 0; q < PP; ++q) {
         const int i = tid * PPT + 2 * q, i1 = (2 * q + 1 < PPT) ? i + 1 : i;
-        px[q] = v2f{s_xyz[3 * i], s_xyz[3 * i1]};
-        py[q] = v2f{s_xyz[3 * i + 1], s_xyz[3 * i1 + 1]};
-        pz[q] = v2f{s_xyz[3 * i + 2], s_xyz[3 * i1 + 2]};
-        dist[q] = v2f{1e10f, 1e10f};
+        if (LDSC) {
+            px[q] = v2f{s_xyz[3 * i], s_xyz[3 * i1]};
+            py[q] = v2f{s_xyz[3 * i + 1], s_xyz[3 * i1 + 1]};
+            pz[q] = v2f{s_xyz[3 * i + 2], s_xyz[3 * i1 + 2]};
+        } else {
+            // a thread's PPT points are 12 * PPT consecutive bytes of the cloud; padding points are zeros, as in the LDS image
+            const bool in0 = i < N, in1 = i1 < N;
+            px[q] = v2f{in0 ? src[3 * i] : 0.0f, in1 ? src[3 * i1] : 0.0f};
+            py[q] = v2f{in0 ? src[3 * i + 1] : 0.0f, in1 ? src[3 * i1 + 1] : 0.0f};
+            pz[q] = v2f{in0 ? src[3 * i + 2] : 0.0f, in1 ? src[3 * i1 + 2] : 0.0f};
+        }
     }
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) dist[j] = (tid * PPT + j) < N ? __float_as_uint(1e10f) : 0u;
+
     int far = start[p];
     int32_t *o = out + (size_t)p * S;
     for (int s = 0; s < S; ++s) {
         if (tid == 0) o[s] = far;
-        const float cx = s_xyz[3 * far], cy = s_xyz[3 * far + 1], cz = s_xyz[3 * far + 2];
+        float cx, cy, cz;
+        if (LDSC) {
+            cx = s_xyz[3 * far], cy = s_xyz[3 * far + 1], cz = s_xyz[3 * far + 2];
+        } else {
+            const float *c = src + 3 * (size_t)far;   // far is wave-uniform and < N: three scalar loads, served by L2
+            cx = c[0], cy = c[1], cz = c[2];
+        }
         const v2f cx2 = {cx, cx}, cy2 = {cy, cy}, cz2 = {cz, cz};
-        unsigned best = 0u;
-        int bq = 0;
 #pragma unroll
         for (int q = 0; q < PP; ++q) {
             const v2f dx = px[q] - cx2, dy = py[q] - cy2, dz = pz[q] - cz2;
             const v2f d = ((dx * dx) + (dy * dy)) + (dz * dz);
-            dist[q] = v2f{d[0] < dist[q][0] ? d[0] : dist[q][0], d[1] < dist[q][1] ? d[1] : dist[q][1]};
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (2 * q + u >= PPT) break;
-                // points past N never win: their key is 0 and the real maximum is >= 0 at a lower index
-                unsigned key = (tid * PPT + 2 * q + u) < N ? __float_as_uint(dist[q][u]) : 0u;
-                if (key > best) { best = key; bq = 2 * q + u; }
-            }
+            dist[2 * q] = min(dist[2 * q], __float_as_uint(d[0]));
+            if (2 * q + 1 < PPT) dist[2 * q + 1] = min(dist[2 * q + 1], __float_as_uint(d[1]));
         }
+        const unsigned best = max_of<PPT>(dist);
         const unsigned wmax = wave_max_u32(best);
         const unsigned long long hit = __ballot(best == wmax);
         const int src_lane = __builtin_ctzll(hit);
-        int widx = __builtin_amdgcn_readlane(tid * PPT + bq, src_lane);
+        // the winning lane holds wmax at one point at least: the lowest such point, from the lane masks of the keys
+        int bq = PPT - 1;
+#pragma unroll
+        for (int j = PPT - 2; j >= 0; --j)
+            if ((__ballot(dist[j] == wmax) >> src_lane) & 1ull) bq = j;
+        int widx = (wave * 64 + src_lane) * PPT + bq;
         if (NW > 1) {
             uint2 *slot = s_part + (s & 1) * NW;
             if (lane == 0) slot[wave] = make_uint2(wmax, (unsigned)widx);
@@ -119,7 +166,7 @@ __global__ __launch_bounds__(NT) void fps_kernel(const float *__restrict__ xyz, 
             const unsigned long long hw = __ballot(part.x == gmax) & ((1ull << NW) - 1ull);
             widx = __builtin_amdgcn_readlane((int)part.y, __builtin_ctzll(hw));
         }
-        far = widx;
+        far = __builtin_amdgcn_readfirstlane(widx);
     }
 }
 
@@ -487,13 +534,13 @@ __global__ void square_distance_kernel(const float *__restrict__ src, const floa
     }
 }
 
-template <int NT, int PPT>
+template <int NT, int PPT, bool LDSC = true>
 int launch_fps(const float *xyz, int n_clouds, int P, int N, int S, const int32_t *start, int32_t *out,
                hipStream_t st)
 {
-    size_t lds = (size_t)NT * PPT * 3 * 4 + 2 * (NT / 64) * 8;
-    if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)fps_kernel<NT, PPT>));
-    hipLaunchKernelGGL((fps_kernel<NT, PPT>), dim3(P), dim3(NT), lds, st, xyz, n_clouds, N, S, start, out);
+    size_t lds = (LDSC ? (size_t)NT * PPT * 3 * 4 : 0) + 2 * (NT / 64) * 8;
+    if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)fps_kernel<NT, PPT, LDSC>));
+    hipLaunchKernelGGL((fps_kernel<NT, PPT, LDSC>), dim3(P), dim3(NT), lds, st, xyz, n_clouds, N, S, start, out);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
 }
@@ -510,13 +557,27 @@ extern "C" int psg_fps(psg_ctx *ctx, const float *xyz, int n_clouds, int P, int 
     if (N <= 64) return launch_fps<64, 1>(xyz, n_clouds, P, N, S, start, out_idx, st);
     if (N <= 256) return launch_fps<64, 4>(xyz, n_clouds, P, N, S, start, out_idx, st);
     if (N <= 1024) return launch_fps<256, 4>(xyz, n_clouds, P, N, S, start, out_idx, st);
-    // many problems (a whole attack plan: iterations x rooms): 256 threads x 16 points keeps three problems per CU resident and
-    // needs a 4-wave instead of a 16-wave reduction per step; few problems: the latency of a step is what counts, and 512 threads
-    // x 8 points has it (tools/fps_cfg_probe.py on MI355X, microseconds per 4096 -> 1024 call, 1024 x 4 / 512 x 8 / 256 x 16:
-    // 1 - 128 problems 690 / 672 / 735, 320 problems 1167 / 1010 / 978, 640: 1733 / 1420 / 1324, 2560: 5254 / 4071 / 3798)
-    static const int cfg = psg::env_int("PSG_FPS_CFG", 0);   // measurement switch: 1 = 1024 x 4, 2 = 512 x 8, 3 = 256 x 16
+    // few problems (up to one per CU): the latency of a step is what counts, and 512 threads x 8 points has it.  More (a whole
+    // attack plan: iterations x rooms): throughput counts; 256 threads x 16 points needs a 4-wave instead of an 8- or 16-wave
+    // reduction per step, and without the 48 KiB cloud in LDS (the centroid of a step comes from global memory by scalar loads;
+    // the level-0 cloud of a room is shared by all its forwards and sits in L2) seven problems instead of three are resident per
+    // CU.  tools/fps_cfg_probe.py on MI355X, microseconds per 4096 -> 1024 call,
+    //                 1024 x 4   512 x 8   256 x 16   256 x 16, no LDS cloud   512 x 8, no LDS cloud
+    //    1 problem       548        547       580             638                     575
+    //  128               573        557       579             627                     589
+    //  256               597        578       596             649                     608
+    //  320               875        814       769             754                     821
+    //  640              1307       1086      1051            1048                    1116
+    // 1280              2077       1913      1690            1570                    1754
+    // 2560              3869       3185      3054            2756                    3148
+    // (with the step loop of before - compare + select per point, in-lane index tracking - the first three columns were
+    // 693 / 680 / 737 at 1 problem, 1193 / 1023 / 989 at 320 and 5353 / 4126 / 3804 at 2560)
+    // measurement switch: 1 = 1024 x 4, 2 = 512 x 8, 3 = 256 x 16, 4 = 256 x 16 and 5 = 512 x 8 without the cloud in LDS
+    static const int cfg = psg::env_int("PSG_FPS_CFG", 0);
     if (N <= 4096 && cfg == 1) return launch_fps<1024, 4>(xyz, n_clouds, P, N, S, start, out_idx, st);
-    if (N <= 4096 && (cfg == 3 || (cfg == 0 && P >= 256))) return launch_fps<256, 16>(xyz, n_clouds, P, N, S, start, out_idx, st);
+    if (N <= 4096 && cfg == 3) return launch_fps<256, 16>(xyz, n_clouds, P, N, S, start, out_idx, st);
+    if (N <= 4096 && cfg == 5) return launch_fps<512, 8, false>(xyz, n_clouds, P, N, S, start, out_idx, st);
+    if (N <= 4096 && (cfg == 4 || (cfg == 0 && P > 256))) return launch_fps<256, 16, false>(xyz, n_clouds, P, N, S, start, out_idx, st);
     if (N <= 4096) return launch_fps<512, 8>(xyz, n_clouds, P, N, S, start, out_idx, st);
     return launch_fps<1024, 8>(xyz, n_clouds, P, N, S, start, out_idx, st);
 }

@@ -25,10 +25,9 @@ def find_trace(path):
 
 def short(name):
     """kernel name without its argument list and the `void psg::` prefix"""
-    name = name.split("(")[0].strip()
-    for p in ("void ", "psg::", "(anonymous namespace)::"):
+    for p in ("void ", "psg::", "(anonymous namespace)::"):      # (before the cut: the namespace's own parenthesis)
         name = name.replace(p, "")
-    return name
+    return name.split("(")[0].strip()
 
 
 def main():
