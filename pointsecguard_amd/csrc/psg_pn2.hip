@@ -171,9 +171,10 @@ bool arch_pack(const ArchDesc &A)
 // L followed by level digits (L0, L02) = exactly those levels; a level named that way that does not fit the packed kernel's
 // configuration is an error at its launch, not a fall-back (bit 8: levels named explicitly).
 // Every level has a packed backward kernel; the default set holds the levels whose launch is faster packed in the headline
-// rooms, measured per level: levels 0 and 1.  Levels 2 and 3 are slower packed (too few
-// workgroups are left to hide the sparse stream's latency) and run packed only where named (L2, L3).
-constexpr int kPackBwdBuilt = (1 << 0) | (1 << 1);
+// rooms, measured per level (rounds 19 and 27): levels 0, 1 and 2 - level 2 since its max-pool transpose
+// runs in channel order (sa_bwd_packed_chan: 82 against 100 us).  Level 3 is slower packed (too few workgroups are left to
+// hide the sparse stream's latency) and runs packed only where named (L3).
+constexpr int kPackBwdBuilt = (1 << 0) | (1 << 1) | (1 << 2);
 int pack_bwd_levels()
 {
     static const int levels = [] {
@@ -188,6 +189,17 @@ int pack_bwd_levels()
         return atoi(v) != 0 ? kPackBwdBuilt : 0;
     }();
     return levels;
+}
+
+// The max-pool transpose of a packed sparse level: channel order over all of a workgroup's groups (sa_bwd_packed_chan), or with
+// PSG_PN2_POOLT_ORDER=row the batches of row-ordered item lists (sa_bwd_packed_sparse).  The same bytes; read once per process.
+bool poolt_order_channel()
+{
+    static const bool chan = [] {
+        const char *v = psg::env_str("PSG_PN2_POOLT_ORDER");
+        return !(v && strcmp(v, "row") == 0);
+    }();
+    return chan;
 }
 
 const ArchDesc &arch_of(int id)
@@ -614,6 +626,10 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
             return PSG_ERR_STATE;
         }
     }
+    // Channel-ordered transpose of the packed sparse levels whose pooled gradient is plain rows, levels 1 and 2
+    // (sa_bwd_packed_chan: its group starts lie inside the batches' staging); PSG_PN2_POOLT_ORDER=row keeps the batches of
+    // sa_pool_t_sparse there (A/B runs, tests/test_gpu_sa_poolt_order.py), which level 3 always runs.
+    const bool chan = packed && (spv == 1 || spv == 2) && a.dout && !a.nninv_off && poolt_order_channel();
     const int staged = spv ? a.sp_off + 2 * NT + NW * 32 + P + 1 + (packed ? SA_PACK_GCAP + 1 : 0) : a.pos_off + P + (packed ? P : 0);
     const int blocks = main_blocks + ceil_div(staged, blk_floats);
     if (std::max(std::max(a.l3t.mb, a.l2t.mb), a.split ? 0 : a.l1t.mb) * (P / 32) > d.maxt_b * NW) {
@@ -624,6 +640,12 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     const int tag = TAG_SA_BWD + lvl;
     if (packed) {
         const SaBwdPackedArgs pa{a, ws->pk_desc[lvl] + prob * grid.x};
+        if (chan) {
+            switch (spv) {
+            case 1: return launch_lds(ws, tag, PSG_SITE "#chan#sa2#bwd#packed", (sa_bwd_packed_kernel<64, 4, 1, 1 + SA_PACK_CHAN>), grid, 4 * 64, blocks, Lds<64>::BLK, pa, st);   // SSG sa2
+            case 2: return launch_lds(ws, tag, PSG_SITE "#chan#sa3#bwd#packed", (sa_bwd_packed_kernel<32, 4, 1, 2 + SA_PACK_CHAN>), grid, 4 * 64, blocks, Lds<32>::BLK, pa, st);   // SSG sa3
+            }
+        }
         switch (spv) {
         case 1: return launch_lds(ws, tag, PSG_SITE "#sa2#bwd#packed", (sa_bwd_packed_kernel<64, 4, 1, 1>), grid, 4 * 64, blocks, Lds<64>::BLK, pa, st);   // SSG sa2
         case 2: return launch_lds(ws, tag, PSG_SITE "#sa3#bwd#packed", (sa_bwd_packed_kernel<32, 4, 1, 2>), grid, 4 * 64, blocks, Lds<32>::BLK, pa, st);   // SSG sa3

@@ -377,6 +377,7 @@ __global__ __launch_bounds__(NW * 64) void sa_fwd_kernel(SaFwdArgs a)
 // in front of the gather): x = first group | groups << 16 (0 groups: surplus), y / z / w = cnt - 1 of its groups, five bits
 // each, six to a word.  cnt and seg stay in the plan for read-back (psg_pn2_plan_ptr).
 constexpr int SA_PACK_GCAP = 16;
+constexpr int SA_PACK_CHAN = 8;    // sa_bwd_packed_kernel's last template argument: SPV + this = the channel-ordered transpose
 
 __device__ __forceinline__ int sa_pack_cnt(const int4 &d, int i)
 {
@@ -814,7 +815,8 @@ __device__ __forceinline__ void sa_mask_tile(float *__restrict__ buf0, int mb, i
 // where k is below the group's count gst[g + 1] - gst[g] (a row at or past the count holds no item: the forward's arg-max is
 // below the count); steps 1 - 4 only - the mask pass belongs to the caller, once, after its last batch.
 // Timing diagnosis (diagnostic builds only): PSG_DIAG bit 128 = no stream (step 4), 1024 = no list build and no stream (steps
-// 1 - 4), 2048 = no mask pass (step 5; sa_bwd_body then skips l2t as well).
+// 1 - 4), 2048 = no mask pass (step 5; sa_bwd_body then skips l2t as well), 8192 = every item reads weight row 0 (the same
+// loads and FMAs on 256 * SPV bytes of W3 instead of all of it: what the stream costs beyond its bytes).
 template <int P, int NW, int MAXT, int SPV, bool PACKED = false>
 __device__ __forceinline__ void sa_pool_t_sparse(const SaBwdArgs &a, float *__restrict__ buf0, float *__restrict__ dsrc, int key,
                                                  size_t wg, const int *__restrict__ gst = nullptr, float dval = 0.0f)
@@ -927,7 +929,7 @@ __device__ __forceinline__ void sa_pool_t_sparse(const SaBwdArgs &a, float *__re
                 for (int u = 0; u < U; ++u) {
                     xs[u] = __builtin_amdgcn_readlane(mine.x, q + u);
                     ds[u] = __int_as_float(__builtin_amdgcn_readlane(mine.y, q + u));
-                    if (q + u < n) w[u] = *(const VT *)(wr + (size_t)(xs[u] & 0xFFFF) * C2);
+                    if (q + u < n) w[u] = *(const VT *)(wr + (size_t)(PSG_DIAGBIT(a, 8192) ? 0 : xs[u] & 0xFFFF) * C2);
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -1309,9 +1311,161 @@ __device__ __forceinline__ void sa_bwd_packed_sparse(const SaBwdArgs &a, float *
     __syncthreads();
 }
 
-template <int P, int NW, int MAXT, int SPV>
+// The same transpose in CHANNEL order (round 27; PSG_PN2_POOLT_ORDER=row keeps the batches above).  A packed workgroup holds at
+// most P live rows, so one accumulator per (live row, column) fits in registers and the pass can walk the channels once for
+// all of the workgroup's groups: no item list (ballots, scan, scatter), no batches, no barrier per batch, and W3 is read once
+// per wave, in address order, instead of once per group as a gather.
+//   * the waves are dealt as (64-column slice of C2) x (range of groups): wave = range slot * SPV + slice.  The ranges are cut
+//     from the workgroup's groups in order, a new one after per = ceil(ng / NR) groups (NR = NW / SPV range slots) or where the
+//     next group would take the range past 32 rows; range i goes to slot i % NR.  Every group lies in exactly one range, a
+//     range holds at most 32 rows = the 32 accumulators of a lane (acc[r] = packed row row0 + r, column slice * 64 + lane),
+//     and a slot that is dealt more than one range (many small groups behind two large ones) runs them one after another;
+//   * a wave walks its range CH = 8 channels at a time: the 8 weight rows W3[c][slice] of the NEXT chunk are loaded while this
+//     one is summed (16 at a time cost 102 - 104 VGPRs, a wave per SIMD fewer than the batches run at); lane (q, u) holds the
+//     item of the q-th group of a set of 8 of the range at channel 8 * chunk + u, as {accumulator index or -1, pooled
+//     gradient}, read straight from the arg-max bytes and the pooled-gradient rows, also one chunk ahead; the items are
+//     broadcast with v_readlane at constant lanes and acc[index] is updated at the wave-uniform index; an item without a row (arg-max 255, or a sample at or past the group's count) is
+//     skipped by a uniform branch;
+//   * per (row, column) this is sa_pool_t_sparse's chain: fmaf from 0 over the row's items in ascending channel order - a row
+//     belongs to one group, a group to one range, and within a range the order is (chunk, set, group, channel): for one
+//     group, ascending channels.  Rows without items store the zeros they started from.  The bytes do not change;
+//   * every live row is stored exactly once (the ranges partition the groups, a range stores rows [row0, row0 + rows)); the
+//     tail of the last 32-row block is zero-filled as before; one barrier, then the mask pass.
+// Levels 1 and 2 (C2 = 64 / 128, the pooled gradient as plain rows).  Level 3 keeps the batches: its channel-ordered kernel (the
+// nninv sums staged once per workgroup, four column slices) took 129 us per launch against 99 us unpacked and 122 us in batches
+//  - every slice pays the per-item chain again and the level has too few workgroups to hide it.
+// LDS: gstart [SA_PACK_GCAP + 1] at sp_off (inside the staging the batches use).
+template <int P, int NW, int SPV>
+__device__ __forceinline__ void sa_bwd_packed_chan(const SaBwdArgs &a, float *__restrict__ buf0, float *__restrict__ dsrc,
+                                                   const int4 &desc, int b, size_t wg, int nrows)
+{
+    using L = Lds<P>;
+    constexpr int PB = P / 32, NT = NW * 64, C2 = 64 * SPV, GCAP = SA_PACK_GCAP, NR = NW / SPV, CH = 8, GQ = 64 / CH;
+    static_assert(NW % SPV == 0 && NR >= 1, "whole range slots");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ng = desc.x >> 16, sA = desc.x & 0xFFFF;
+    const int nblk = (nrows + 31) >> 5;
+    int *gstart = (int *)(dsrc + a.sp_off);                     // [GCAP + 1] first packed row of each group; nrows from ng on
+    {
+        int st = 0;
+        for (int i = 0; i < ng; ++i) {                          // (uniform)
+            if (tid == i) gstart[i] = st;
+            st += sa_pack_cnt(desc, i);
+        }
+        if (tid >= ng && tid <= GCAP) gstart[tid] = nrows;
+    }
+    // the tail of the last block: zeroed once (no range writes it)
+    for (int t = tid; t < (nblk * 32 - nrows) * (C2 / 4); t += NT) {
+        const int r = nrows + t / (C2 / 4), q = t % (C2 / 4);
+        *(float4 *)(buf0 + L::off(4 * q, r)) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    // layer 2's ReLU mask word of this wave's tile (mb, pb) of dZ2, at the packed key the forward stored it at
+    const int mb = wave / nblk, pb = wave - mb * nblk;
+    const bool mtile = wave < (C2 / 32) * nblk;
+    unsigned msk = 0xFFFFu;
+    if (mtile && a.l3t.mask) msk = a.l3t.mask[((wg * (C2 / 32) + mb) * PB + pb) * 64 + lane];
+    __syncthreads();
+    if (!PSG_DIAGBIT(a, 128 | 1024)) {
+        const int slice = wave % SPV, slot = wave / SPV;
+        // W3 through a buffer descriptor: one vector offset (the lane's column), the row as the scalar offset
+        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)a.w3r, 0, a.C3 * C2 * 4, 0x00020000);
+        const unsigned coff = (slice * 64 + lane) * 4u;
+        const uint8_t *arow = a.arg + ((size_t)b * a.S + sA) * a.C3;
+        const float *drow = a.dout + ((size_t)b * a.S + sA) * a.ld + a.c_off;   // (plain rows: run_sa_bwd checks)
+        const int per = (ng + NR - 1) / NR, nch = a.C3 / CH;
+        const int lq = lane / CH, lu = lane % CH;
+        int ga = 0, row0 = 0, rows = 0, rid = 0;
+        for (int i = 0; i <= ng; ++i) {                         // (uniform; the counts from the table: gstart[ng] = nrows)
+            const int cnt = i < ng ? __builtin_amdgcn_readfirstlane(gstart[i + 1] - gstart[i]) : 0;
+            if (i > ga && (i == ng || i - ga == per || rows + cnt > 32)) {   // groups [ga, i) are range rid, rows [row0, row0 + rows)
+                if (rid % NR == slot) {
+                    const int gb = i, nset = (gb - ga + GQ - 1) / GQ;
+                    float acc[32];
+#pragma unroll
+                    for (int r = 0; r < 32; ++r) acc[r] = 0.0f;
+                    // lane (lq, lu) holds the item of group ga + GQ * j + lq (set j) at channel k * CH + lu: its arg-max byte and
+                    // gradient are loaded a chunk ahead and turned into {accumulator index or -1, gradient} where they are used
+                    auto raw = [&](int k, int j, int &v, float &dv) {
+                        const int g = ga + GQ * j + lq, c = k * CH + lu;
+                        v = 255;
+                        dv = 0.0f;
+                        if (g < gb) {
+                            v = arow[(size_t)g * a.C3 + c];
+                            dv = drow[(size_t)g * a.ld + c];
+                        }
+                    };
+                    auto base = [&](int j, int &st, int &cn) {   // the group's first accumulator and its count (0: no such group)
+                        const int g = ga + GQ * j + lq;
+                        st = 0;
+                        cn = 0;
+                        if (g < gb) {
+                            const int s0 = gstart[g];
+                            cn = gstart[g + 1] - s0;
+                            st = s0 - row0;
+                        }
+                    };
+                    int st0, cn0, vn;
+                    float wn[CH], dvn;
+                    base(0, st0, cn0);
+#pragma unroll
+                    for (int u = 0; u < CH; ++u) wn[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, coff, u * C2 * 4, 0));
+                    raw(0, 0, vn, dvn);
+                    for (int k = 0; k < nch; ++k) {
+                        float w[CH], dv = dvn;
+                        int v = vn, st = st0, cn = cn0;
+#pragma unroll
+                        for (int u = 0; u < CH; ++u) w[u] = wn[u];
+                        if (k + 1 < nch) {
+                            const int r1 = PSG_DIAGBIT(a, 8192) ? 0 : (k + 1) * CH;
+#pragma unroll
+                            for (int u = 0; u < CH; ++u) wn[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, coff, (r1 + u) * C2 * 4, 0));
+                            raw(k + 1, 0, vn, dvn);
+                        }
+                        for (int j = 0; j < nset; ++j) {
+                            if (j > 0) {
+                                raw(k, j, v, dv);
+                                base(j, st, cn);
+                            }
+                            const int dl = v < cn ? st + v : -1;   // (255 = no gradient: below no count)
+#pragma unroll
+                            for (int q = 0; q < GQ; ++q) {
+                                if (ga + GQ * j + q < gb) {
+#pragma unroll
+                                    for (int u = 0; u < CH; ++u) {
+                                        const int xs = __builtin_amdgcn_readlane(dl, q * CH + u);
+                                        if (xs >= 0) {
+                                            const float ds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), q * CH + u));
+                                            acc[xs] = fmaf(ds, w[u], acc[xs]);
+                                        }
+                                    }
+                                }
+                            }
+                        }
+                    }
+                    float *o = buf0 + L::off(slice * 64 + lane, row0);
+#pragma unroll
+                    for (int r = 0; r < 32; ++r)
+                        if (r < rows) o[r * 8] = acc[r];
+                }
+                ++rid;
+                row0 += rows;
+                rows = 0;
+                ga = i;
+            }
+            rows += cnt;
+        }
+    }   // (PSG_DIAG bits 128, 1024)
+    __syncthreads();
+    if (mtile) sa_mask_tile<P>(buf0, mb, pb, lane & 31, lane >> 5, msk);
+    __syncthreads();
+}
+
+// SPVO = SPV, plus SA_PACK_CHAN where the sparse max-pool transpose runs in channel order (sa_bwd_packed_chan: levels 1 and 2)
+template <int P, int NW, int MAXT, int SPVO>
 __global__ __launch_bounds__(NW * 64) void sa_bwd_packed_kernel(SaBwdPackedArgs pa)
 {
+    constexpr int SPV = SPVO & (SA_PACK_CHAN - 1);
+    constexpr bool CHAN = SPVO >= SA_PACK_CHAN;
     const SaBwdArgs &a = pa.a;
     using L = Lds<P>;
     static_assert(MAXT == 1 && (SPV > 0 ? P <= 64 : P == 32 * NW), "one tile per wave in every layer");
@@ -1343,7 +1497,8 @@ __global__ __launch_bounds__(NW * 64) void sa_bwd_packed_kernel(SaBwdPackedArgs 
     if constexpr (SPV > 0) {
         // the sparse levels: dZ2 of the packed rows by batches of the sparse stream, masked (ends behind a barrier)
         if (tid < P) s_pos[tid] = tid < nrows ? a.gpos_out[(size_t)b * a.S * KS + (size_t)(sA + rg_g) * KS + tid - rg_st] : -1;
-        sa_bwd_packed_sparse<P, NW, SPV>(a, buf0, dsrc, desc, b, wg, nrows);
+        if constexpr (CHAN) sa_bwd_packed_chan<P, NW, SPV>(a, buf0, dsrc, desc, b, wg, nrows);
+        else sa_bwd_packed_sparse<P, NW, SPV>(a, buf0, dsrc, desc, b, wg, nrows);
     } else {
         int *s_row = s_pos + P;                                     // [P] local group << 5 | sample of a packed row, -1 = tail
         if (tid < P) {
