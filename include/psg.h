@@ -1256,6 +1256,41 @@ int psg_grid_reduce(psg_grid *g, const float *points, const float *features, int
 int psg_grid_index(psg_grid *g, const float *sub_points, int m, float grid_size, psg_stream stream);
 int psg_grid_nearest(psg_grid *g, const float *query, int n_query, int32_t *out_idx, psg_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Whole-scene NB attack: one colour per scene point across all the overlapping blocks that hold
+ * it.  A "slot" is a block row e = b * block_points + i of the scene's block arrays [rows][.]; point_idx [rows] int32
+ * names the scene point of every slot.  rows must lie in 1 .. INT_MAX / 9 (slot numbers address [rows][9] floats):
+ * anything else is refused with a message.  Nothing here uses float atomics; every output element has one writer.
+ *
+ * psg_scene_occ_build: the occurrence lists of every scene point, built once per scene: occ_off [n_scene + 1] (offsets,
+ * occ_off[n_scene] = number of valid slots), occ_ent [rows] (the slots of point p at occ_off[p] .. occ_off[p + 1],
+ * ASCENDING) - exactly np.argsort(point_idx, kind = "stable") with the offsets of np.bincount; the result does not
+ * depend on scheduling.  scratch: int32 [n_scene + rows].  A slot whose index lies outside [0, n_scene) ORs 1 into
+ * *bad_flag (int32, device: the psg_vote_add convention), joins no list and is neither read nor written through; the
+ * unused tail of occ_ent then holds -1.
+ * psg_scene_colour_to_blocks: x [rows][9], channels 3:6 of every slot <- scene_rgb [n_scene][3] of its point; the other
+ * six floats of a row keep their bytes.  Bad index: flag, row untouched.
+ * psg_scene_rows_mask: dlogp [rows][n_cls]: the rows of slots whose scene point is not under scene_mask [n_scene] (uint8)
+ * are set to +0.0, the others are not touched (an index out of range counts as not masked).
+ * psg_scene_pgd_step: for every scene point p (scene_mask nullable: under the mask only) with at least one slot:
+ *   g = ((0 + dx0[e_0][3:6]) + dx0[e_1][3:6]) + ...   over the slots of p in list order, fp32, no contraction
+ *   and then psg_pgd_step's arithmetic with scene_ori [n_scene][3] as the clean colours:
+ *   stepped = c + dir*alpha*sign(g) (sign(0) = sign(NaN) = 0);  eta = clamp(stepped - ori, -eps, eps);
+ *   c = last ? stepped : clamp(ori + eta, 0, 1)
+ * scene_rgb [n_scene][3] in place.  A point without a slot does not move.  Every list is bounded by rows (offsets
+ * clamped, entries outside [0, rows) skipped).  gsum_out (nullable) [n_scene][3]: the summed gradient (+0 for points
+ * outside the mask or without a slot).
+ * ------------------------------------------------------------------------------------------ */
+int psg_scene_occ_build(const int32_t *point_idx, int rows, int n_scene, int32_t *occ_off, int32_t *occ_ent,
+                        int32_t *scratch, int32_t *bad_flag, psg_stream stream);
+int psg_scene_colour_to_blocks(const float *scene_rgb, const int32_t *point_idx, int rows, int n_scene, float *x,
+                               int32_t *bad_flag, psg_stream stream);
+int psg_scene_rows_mask(float *dlogp, const int32_t *point_idx, const uint8_t *scene_mask, int rows, int n_cls,
+                        int n_scene, psg_stream stream);
+int psg_scene_pgd_step(float *scene_rgb, const float *scene_ori, const uint8_t *scene_mask, const int32_t *occ_off,
+                       const int32_t *occ_ent, const float *dx0, int rows, int n_scene, float alpha, float eps, float dir,
+                       int last, float *gsum_out, psg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,10 @@ SIGNATURES = {
     "psg_grid_reduce": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]),
     "psg_grid_index": (ci, [vp, vp, ci, cf, vp]),
     "psg_grid_nearest": (ci, [vp, vp, ci, vp, vp]),
+    "psg_scene_occ_build": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
+    "psg_scene_colour_to_blocks": (ci, [vp, vp, ci, ci, vp, vp, vp]),
+    "psg_scene_rows_mask": (ci, [vp, vp, vp, ci, ci, ci, vp]),
+    "psg_scene_pgd_step": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, ci, vp, vp]),
 }
 
 

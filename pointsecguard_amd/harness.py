@@ -333,6 +333,121 @@ def _scene_batch(classifier, attack, make_attack, targeted, lane, dev, n_pt, sba
     return []
 
 
+def evaluate_whole_scene_consistent(classifier, dataset, make_scene_attack, batch_size=8, log_path=None, rank=0, world=1,
+                                    log=print, targeted=None, on_scene=None):
+    """evaluate_whole_scene with ONE adversarial scene per room: the attack moves one colour per
+    physical scene point - attacks.scene.SceneNBAttack - instead of one per block slot, so the adversarial blocks that are
+    voted on are slices of a point cloud that exists (and can be saved and re-sliced).
+
+    make_scene_attack(classifier) -> a SceneNBAttack (for the targeted protocol one built with the same origin / target);
+    its batch_size is set to this call's.  Per scene of the rank's shard, in this order - which is also the order in which the
+    generators are consumed: np.random by the slicing, torch's CPU generator by the FPS starts of every forward -
+      1. one slicing (dataset[si]; num_votes is 1, as in the reference's attack scripts);
+      2. the clean forwards of all batches, in batch order;
+      3. the scene attack (iteration outer, batch inner);
+      4. the adversarial forwards of all batches, in batch order.
+    Steps 3 and 4 draw, in that order, from a fork of the CPU generator (torch.random.fork_rng) taken after step 2: when the
+    scene is done the generator stands where its clean forwards left it.  The clean forwards of EVERY scene therefore draw
+    exactly what evaluate_whole_scene(classifier, dataset, None) draws under the same seeds - the clean counters of the two are
+    the same numbers -, and a seeded run is reproducible; the price is that a scene's attack and the next scene's clean
+    forwards start from the same generator state.
+    Votes, counters, the per-batch TSV rows (same header and row format; L2_dis per batch of adversarial against clean
+    blocks) and the totals are those of evaluate_whole_scene.  targeted = dict(origin=o, target=t): the ten-column rows,
+    written for the batches that hold a point of `origin`; a scene without such a point is evaluated clean and logs no rows.
+    on_scene(name, adv_rgb01): called once per scene with the adversarial colours as a float32 numpy array [n_scene, 3] in
+    [0, 1] (the clean ones for a scene that was not attacked) - the reference's .xyzrgb dump.  One stream, no replicas."""
+    from .attacks.scene import check_scene_model
+    check_scene_model(classifier)
+    dev = next(classifier.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.PsgError("the classifier must be on the MI355X device (got %s); there is no CPU path" % dev)
+    attack = make_scene_attack(classifier)
+    attack.batch_size = int(batch_size)
+    if targeted is not None and (attack.origin != targeted["origin"] or attack.target != targeted["target"]):
+        raise ValueError("the scene attack's origin / target differ from the targeted protocol's")
+    n_pt = dataset.block_points
+    total = torch.zeros(2, 3, NUM_CLASSES, dtype=torch.int64, device=dev)
+    scene_rows = []
+    fh = None
+    if log_path is not None:
+        path = log_path if world == 1 else "%s.rank%d" % (log_path, rank)
+        fh = open(path, "w")
+        fh.write(LOG_HEADER if targeted is None else TARGETED_LOG_HEADER)
+    try:
+        for si in shard_scenes(list(range(len(dataset))), rank, world):
+            labels_np = dataset.semantic_labels_list[si]
+            n_scene = labels_np.shape[0]
+            scene_labels = torch.from_numpy(labels_np.astype(np.int32)).to(dev)
+            pool = torch.zeros(n_scene, NUM_CLASSES, dtype=torch.int32, device=dev)
+            adv_pool = torch.zeros_like(pool)
+            vote_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            scene_data, scene_label, scene_smpw, scene_point_index = dataset[si]
+            num_blocks = scene_data.shape[0]
+            x_all = upload(torch.from_numpy(scene_data.astype(np.float32)), dev, pin=True)            # [nb, bp, 9] point-major
+            gt_all = upload(torch.from_numpy(scene_label.astype(np.int32)), dev, pin=True)
+            idx_all = upload(torch.from_numpy(scene_point_index.astype(np.int32)), dev, pin=True)
+            smpw_all = upload(torch.from_numpy(scene_smpw.astype(np.float32)), dev, pin=True)
+            batches = [(lo, min(lo + batch_size, num_blocks)) for lo in range(0, num_blocks, batch_size)]
+            attacked = targeted is None or bool((labels_np == targeted["origin"]).any())
+            clean_stats = []
+            for lo, hi in batches:
+                torch_data = x_all[lo:hi].transpose(2, 1).contiguous()
+                seg_pred, _ = classifier(torch_data)
+                seg_pred = seg_pred.detach().contiguous()
+                add_vote(pool, idx_all[lo:hi], seg_pred, smpw_all[lo:hi], bad=vote_bad)
+                if not attacked:
+                    add_vote(adv_pool, idx_all[lo:hi], seg_pred, smpw_all[lo:hi], bad=vote_bad)
+                clean_stats.append(runtime.seg_stats(seg_pred, gt_all[lo:hi])[0])
+            check_votes(vote_bad)
+            pending, adv_rgb = [], None
+            rgb_np = dataset.scene_points_list[si][:, 3:6]
+            if attacked:
+                # steps 3 and 4 draw from a FORK of the CPU generator: afterwards it stands where the clean forwards left it
+                with torch.random.fork_rng(devices=[]):
+                    adv_rgb, pending = _scene_attack_and_votes(classifier, attack, targeted, batches, n_pt, x_all, idx_all, gt_all,
+                                                               smpw_all, scene_label, rgb_np, scene_labels, adv_pool, vote_bad,
+                                                               clean_stats)
+                check_votes(vote_bad)
+            if on_scene is not None:
+                on_scene(dataset.file_list[si][:-4],
+                         adv_rgb.cpu().numpy() if attacked else (rgb_np / 255.0).astype(np.float32))
+            _write_rows(pending, targeted, fh)
+            c_scene = vote_stats(pool, scene_labels)
+            c_scene_adv = vote_stats(adv_pool, scene_labels)
+            total[0] += c_scene
+            total[1] += c_scene_adv
+            name = dataset.file_list[si][:-4]
+            scene_rows.append((name, _miou(c_scene), _miou(c_scene_adv)))
+            log('Mean IoU of %s: %.4f' % (name, scene_rows[-1][1]))
+            log('Mean IoU of %s: %.4f' % (name, scene_rows[-1][2]))
+    finally:
+        if fh is not None:
+            fh.close()
+    return _finish(total, scene_rows, rank, log)
+
+
+def _scene_attack_and_votes(classifier, attack, targeted, batches, n_pt, x_all, idx_all, gt_all, smpw_all, scene_label, rgb_np,
+                            scene_labels, adv_pool, vote_bad, clean_stats):
+    """Steps 3 and 4 of evaluate_whole_scene_consistent for one scene: the scene attack, then the adversarial forwards, votes,
+    counters and L2 of every batch in batch order; returns (adversarial colours [n_scene, 3], the scene's pending log rows)."""
+    adv_rgb, adv_blocks = attack(x_all, idx_all, gt_all, rgb_np, scene_labels)
+    pending = []
+    for sbatch, (lo, hi) in enumerate(batches):
+        adv_data = adv_blocks[lo:hi].transpose(2, 1).contiguous()
+        adv_seg_pred, _ = classifier(adv_data)
+        adv_seg_pred = adv_seg_pred.detach().contiguous()
+        add_vote(adv_pool, idx_all[lo:hi], adv_seg_pred, smpw_all[lo:hi], bad=vote_bad)
+        c_adv, _ = runtime.seg_stats(adv_seg_pred, gt_all[lo:hi])
+        dis = l2_distance(adv_data, x_all[lo:hi].transpose(2, 1).contiguous())
+        count, hits = 0, None
+        if targeted is not None:
+            count = int((scene_label[lo:hi] == targeted["origin"]).sum())
+            hits = ((adv_seg_pred.argmax(dim=2) == targeted["target"]) & (gt_all[lo:hi] == targeted["origin"])).sum()
+        if targeted is None or count:
+            pending.append((sbatch, (hi - lo) * n_pt, count, dis, clean_stats[sbatch], c_adv, hits))
+    return adv_rgb, pending
+
+
 def _write_rows(pending, targeted, fh):
     """The scene's TSV rows in the order the batches were issued (NB_nontarget_test_semseg.py:213-215): ONE read-back for all."""
     if not pending:

@@ -474,6 +474,66 @@ def seg_stats(logp, labels, n_cls=NUM_CLASSES, counters=None):
     return counters, pred.view(labels.shape)
 
 
+# ---- whole-scene NB attack (psg_scene.hip) ------------------------------------
+def scene_occ_build(point_idx, n_scene, bad):
+    """Occurrence lists of every scene point over the block slots: point_idx int32 [rows] (any shape) ->
+    (occ_off int32 [n_scene + 1], occ_ent int32 [rows]), the slots of a point ascending; bad: int32 [1] device flag."""
+    require_cuda(point_idx, "point_idx", torch.int32)
+    require_cuda(bad, "bad", torch.int32)
+    rows = point_idx.numel()
+    occ_off = torch.empty(n_scene + 1, dtype=torch.int32, device=point_idx.device)
+    occ_ent = torch.empty(rows, dtype=torch.int32, device=point_idx.device)
+    scratch = torch.empty(n_scene + rows, dtype=torch.int32, device=point_idx.device)
+    _lib.call("psg_scene_occ_build", ptr(point_idx), rows, int(n_scene), ptr(occ_off), ptr(occ_ent), ptr(scratch), ptr(bad),
+              stream())
+    return occ_off, occ_ent
+
+
+def scene_colour_to_blocks(scene_rgb, point_idx, x, bad):
+    """x [.., 9] channels 3:6 of every slot <- scene_rgb [n_scene, 3] of its point, in place."""
+    require_cuda(scene_rgb, "scene_rgb", torch.float32)
+    require_cuda(point_idx, "point_idx", torch.int32)
+    require_cuda(x, "x", torch.float32)
+    require_cuda(bad, "bad", torch.int32)
+    rows = point_idx.numel()
+    assert x.numel() == rows * 9 and scene_rgb.dim() == 2 and scene_rgb.shape[1] == 3
+    _lib.call("psg_scene_colour_to_blocks", ptr(scene_rgb), ptr(point_idx), rows, scene_rgb.shape[0], ptr(x), ptr(bad), stream())
+    return x
+
+
+def scene_rows_mask(dlogp, point_idx, scene_mask):
+    """dlogp [.., n_cls]: rows of slots whose scene point is not under scene_mask (uint8 [n_scene]) <- +0.0, in place."""
+    require_cuda(dlogp, "dlogp", torch.float32)
+    require_cuda(point_idx, "point_idx", torch.int32)
+    require_cuda(scene_mask, "scene_mask", torch.uint8)
+    rows = point_idx.numel()
+    assert dlogp.numel() == rows * dlogp.shape[-1]
+    _lib.call("psg_scene_rows_mask", ptr(dlogp), ptr(point_idx), ptr(scene_mask), rows, dlogp.shape[-1], scene_mask.numel(),
+              stream())
+    return dlogp
+
+
+def scene_pgd_step(scene_rgb, scene_ori, scene_mask, occ_off, occ_ent, dx0, alpha, eps, direction, last, gsum_out=None):
+    """One step on the scene's colours [n_scene, 3] (in place) from the block gradients dx0 [rows, 9] summed over every
+    point's slots in ascending slot order (psg_scene_pgd_step)."""
+    require_cuda(scene_rgb, "scene_rgb", torch.float32)
+    require_cuda(scene_ori, "scene_ori", torch.float32)
+    require_cuda(occ_off, "occ_off", torch.int32)
+    require_cuda(occ_ent, "occ_ent", torch.int32)
+    require_cuda(dx0, "dx0", torch.float32)
+    if scene_mask is not None:
+        require_cuda(scene_mask, "scene_mask", torch.uint8)
+        assert scene_mask.numel() == scene_rgb.shape[0]
+    if gsum_out is not None:
+        require_cuda(gsum_out, "gsum_out", torch.float32)
+        assert gsum_out.shape == scene_rgb.shape
+    rows, n_scene = occ_ent.numel(), scene_rgb.shape[0]
+    assert dx0.numel() == rows * 9 and occ_off.numel() == n_scene + 1 and scene_ori.shape == scene_rgb.shape == (n_scene, 3)
+    _lib.call("psg_scene_pgd_step", ptr(scene_rgb), ptr(scene_ori), ptr(scene_mask), ptr(occ_off), ptr(occ_ent), ptr(dx0), rows,
+              n_scene, float(alpha), float(eps), float(direction), 1 if last else 0, ptr(gsum_out), stream())
+    return scene_rgb
+
+
 # ---- ResGCN (dense DeepGCN) ------------------------------------------------------------------------
 def gcn_tensor_list(sd, n_blocks):
     """state_dict (reference key names, ResGCN/sem_seg_dense/architecture.py) -> the flat fp32 tensor list of
