@@ -519,6 +519,318 @@ __global__ __launch_bounds__(NN_THREADS) void three_nn_kernel(const float *__res
     w[o] = __fdiv_rn(r0, norm); w[o + 1] = __fdiv_rn(r1, norm); w[o + 2] = __fdiv_rn(r2, norm);
 }
 
+// ---------------------------------------------------------------------------------------------
+// 3-NN through a uniform grid over the COARSE cloud (round 29), for the level-0 shape (4096 fine points against 1024
+// coarse ones: the scan above tests every pair, 10.7 G of them per plan of 2560 problems, and is vector-issue-bound).  The
+// three nearest of the ~evenly spread FPS samples lie a few centimetres away: a few dozen candidates instead of S.
+// Per workgroup: the coarse cloud is staged with |p|^2, its bounding box reduced, the points binned by an LDS counting
+// sort as in ball_query_grid_kernel (the sorted copy holds {x, y, z, |p|^2} so that a run of cells is a contiguous read);
+// there is no radius here, so the cell edge is free: cbrt(NNG_PPC x box volume / S), i.e. about NNG_PPC points per cell
+// of a volume-filling cloud (a flat axis counts as 1/64 of the longest), grown by 1.25 x until the box fits NNG_CELLS.
+// One LANE per fine point then looks outward from its own cell - the 3 x 3 x 3 block first, then the shell around it, and so
+// on - keeping its best three as keys (d, j):
+//   * d is three_nn_kernel's arithmetic, operation for operation (sqdist: fma chain, (-2 dot + |fine|^2) + |coarse|^2);
+//   * the order is d ascending, then j ascending - what the scan's strict `<` over ascending j produces; the grid meets
+//     candidates in cell order, so the tie rule is explicit; the slots start as (inf, 0) and a candidate whose d is +inf or NaN
+//     never enters, as in the scan;
+//   * after a block / shell: L = distance from the query to the nearest face of what is not yet visited (faces beyond the
+//     border cells do not count: there is nothing behind them), less NNG_SLACK x max|coordinate| for the rounding of the
+//     cell index and of the face position.  An unvisited point is at least L away, and its COMPUTED d is at least
+//     L^2 - err, err = 1e-5 max|coordinate|^2 (the expansion's rounding is below 2.4e-7 (|f| + |c|)^2 <= 3e-6
+//     max|coordinate|^2, query included: the ball grid's bound and its factor).  The walk stops only when L^2 - err is
+//     STRICTLY above the third-best d: a candidate that would tie the third best with a lower j is never skipped.  A
+//     walk that reaches every cell is the scan;
+//   * a query that is non-finite or further outside the coarse box than the grid is long, and every query of a problem
+//     whose coarse cloud holds a non-finite coordinate (no grid is built), takes all S candidates in ascending j through
+//     the scan's own compare chain.
+// Schedule.  Lanes that walk by themselves pay for each other: per candidate the wave runs the run-advance and the insert of
+// its slowest lane, ~100 instructions against the scan's 8, and the first version of this kernel (one lane, one walk, queries
+// in file order) was SLOWER than the scan (3.42 against 2.07 ms per 2560 problems).  So the workgroup also sorts its queries by
+// cell of the same grid (a second counting sort, inside the launch, from the buffers passed in: nothing is kept across
+// calls), a wave takes 64 queries that are neighbours in that order, and the first step is taken TOGETHER: every cell of the
+// box around the wave's blocks - a superset of each lane's own block, which is as good for the stop rule - with wave-uniform
+// run bounds and candidates (LDS broadcasts, scalar loop control, four candidates per step, the index read only when d can
+// enter): ~146 candidates per query instead of 37, at a tenth of the cost each.  A lane whose stop rule fails after that step
+// (0.1 % of the lanes of a room) starts over and walks by itself, block and shells, as described above.
+// Same idx and w as three_nn_kernel, byte for byte (tests/test_gpu_three_nn_grid.py; the walk, the schedule and the stop rule
+// restated in numpy: tests/three_nn_grid_ref.py, tests/test_three_nn_grid_host.py).
+// ---------------------------------------------------------------------------------------------
+constexpr int NNG_THREADS = 512;         // 8 waves: three workgroups per CU at 7 waves per SIMD and 51 KiB of LDS each
+constexpr int NNG_CELLS = 2 * NNG_THREADS;   // cells per coarse cloud at most (the scan of the cell counts takes two per thread)
+constexpr int NNG_MAX_S = 1024;        // LDS: 34 B per coarse point, 8 KiB of cell tables, 2 B per query: 50 KiB at level 0
+constexpr float NNG_PPC = 2.0f;        // coarse points per cell the edge aims at (tools/three_nn_probe.py; DESIGN round 29)
+constexpr float NNG_ERR = 1e-5f;       // x max|coordinate|^2: rounding of the expansion
+constexpr float NNG_SLACK = 4e-6f;     // x max|coordinate|: rounding of cell index and face position
+
+__device__ __forceinline__ int nn_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float nn_uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ bool nn_before(float d, int j, float bd, int bj) { return d < bd || (d == bd && j < bj); }
+
+__global__ __launch_bounds__(NNG_THREADS) void three_nn_grid_kernel(const float *__restrict__ xyz1, int n_clouds1,
+                                                                    const float *__restrict__ xyz2, int N, int S, int qpb,
+                                                                    int32_t *__restrict__ idx, float *__restrict__ w)
+{
+    // file order [S] | cell order [S] | cell starts [CELLS + 1] | cursors [CELLS + 1] | j in cell order [S] u16 | queries in cell order [qpb] u16
+    extern __shared__ float4 s_pt[];
+    float4 *s_sp = s_pt + S;
+    int *s_start = (int *)(s_sp + S);
+    int *s_cur = s_start + NNG_CELLS + 1;
+    unsigned short *s_sj = (unsigned short *)(s_cur + NNG_CELLS + 1);
+    unsigned short *s_qs = s_sj + S;
+    __shared__ float s_red[NNG_THREADS / 64][6];
+    __shared__ float s_box[8];          // min x, y, z, 1 / cell edge; max x, y, z, cell edge
+    __shared__ int s_dim[4];            // nx, ny, nz, cells
+    __shared__ int s_wsum[NNG_THREADS / 64];
+    __shared__ int s_bad;               // the coarse cloud holds a non-finite coordinate
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.y;
+    const float *c2 = xyz2 + (size_t)p * S * 3;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    float mn0 = INFINITY, mn1 = INFINITY, mn2 = INFINITY, mx0 = -INFINITY, mx1 = -INFINITY, mx2 = -INFINITY;
+    bool bad = false;
+    for (int i = tid; i < S; i += NNG_THREADS) {
+        const float x = c2[3 * i], y = c2[3 * i + 1], z = c2[3 * i + 2];
+        s_pt[i] = make_float4(x, y, z, sumsq3(x, y, z));
+        mn0 = fminf(mn0, x); mn1 = fminf(mn1, y); mn2 = fminf(mn2, z);
+        mx0 = fmaxf(mx0, x); mx1 = fmaxf(mx1, y); mx2 = fmaxf(mx2, z);
+        bad = bad || !(fmaxf(fmaxf(fabsf(x), fabsf(y)), fabsf(z)) < 1e18f) || x != x || y != y || z != z;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mn0 = fminf(mn0, __shfl_xor(mn0, o)); mn1 = fminf(mn1, __shfl_xor(mn1, o)); mn2 = fminf(mn2, __shfl_xor(mn2, o));
+        mx0 = fmaxf(mx0, __shfl_xor(mx0, o)); mx1 = fmaxf(mx1, __shfl_xor(mx1, o)); mx2 = fmaxf(mx2, __shfl_xor(mx2, o));
+    }
+    if (lane == 0) { s_red[wave][0] = mn0; s_red[wave][1] = mn1; s_red[wave][2] = mn2; s_red[wave][3] = mx0; s_red[wave][4] = mx1; s_red[wave][5] = mx2; }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    const bool scan_all = nn_uni(s_bad) != 0;   // (uniform over the workgroup)
+    float bx = 0.f, by = 0.f, bz = 0.f, inv = 1.f, hx = 0.f, hy = 0.f, hz = 0.f, edge = 1.f;
+    int nx = 1, ny = 1, nz = 1;
+    if (!scan_all) {
+        if (tid == 0) {
+            float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (int wv = 0; wv < NNG_THREADS / 64; ++wv) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], s_red[wv][a]); hi[a] = fmaxf(hi[a], s_red[wv][3 + a]); }
+            }
+            const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+            const float emax = fmaxf(ex, fmaxf(ey, ez));
+            float e = 1.0f;
+            int dx = 1, dy = 1, dz = 1;
+            if (emax > 0.0f) {                                         // (all points identical: one cell)
+                const float fl = emax * (1.0f / 64.0f);
+                e = cbrtf(fmaxf(ex, fl) * fmaxf(ey, fl) * fmaxf(ez, fl) * (NNG_PPC / (float)S));
+                for (;;) {
+                    dx = (int)(ex / e) + 1; dy = (int)(ey / e) + 1; dz = (int)(ez / e) + 1;
+                    if ((long long)dx * dy * dz <= NNG_CELLS) break;
+                    e *= 1.25f;
+                }
+            }
+            s_box[0] = lo[0]; s_box[1] = lo[1]; s_box[2] = lo[2]; s_box[3] = 1.0f / e;
+            s_box[4] = hi[0]; s_box[5] = hi[1]; s_box[6] = hi[2]; s_box[7] = e;
+            s_dim[0] = dx; s_dim[1] = dy; s_dim[2] = dz; s_dim[3] = dx * dy * dz;
+        }
+        __syncthreads();
+        // (workgroup-uniform: kept in scalar registers)
+        bx = nn_uni(s_box[0]); by = nn_uni(s_box[1]); bz = nn_uni(s_box[2]); inv = nn_uni(s_box[3]);
+        hx = nn_uni(s_box[4]); hy = nn_uni(s_box[5]); hz = nn_uni(s_box[6]); edge = nn_uni(s_box[7]);
+        nx = nn_uni(s_dim[0]); ny = nn_uni(s_dim[1]); nz = nn_uni(s_dim[2]);
+    }
+    const int ncell = nx * ny * nz;
+    // the cell of a coordinate: clamped in float (a NaN becomes 0), then truncated - monotone in v
+    auto cell1 = [&](float v, float b, int n) { return (int)fminf(fmaxf((v - b) * inv, 0.0f), (float)(n - 1)); };
+    // inclusive scan of a[1 .. ncell] in place over the workgroup (counts -> a[c] = start of cell c, a[0] = 0): two cells per thread
+    auto scan_counts = [&](int *a) {
+        const int c0 = 1 + 2 * tid;
+        const int v0 = c0 <= ncell ? a[c0] : 0, v1 = c0 + 1 <= ncell ? a[c0 + 1] : 0;
+        const int inc = (int)bq_wave_incl_scan((unsigned)(v0 + v1));
+        if (lane == 63) s_wsum[wave] = inc;
+        __syncthreads();
+        int base = inc;
+        for (int wv = 0; wv < wave; ++wv) base += s_wsum[wv];
+        if (c0 <= ncell) a[c0] = base - v1;
+        if (c0 + 1 <= ncell) a[c0 + 1] = base;
+        __syncthreads();
+    };
+    const float *f1 = xyz1 + (size_t)(p % n_clouds1) * N * 3;
+    const int q_begin = blockIdx.x * qpb, nq = min(N, q_begin + qpb) - q_begin;
+    auto cell_of = [&](float x, float y, float z) { return (cell1(z, bz, nz) * ny + cell1(y, by, ny)) * nx + cell1(x, bx, nx); };
+    if (!scan_all) {
+        for (int c = tid; c <= ncell; c += NNG_THREADS) s_start[c] = 0;
+        __syncthreads();
+        for (int i = tid; i < S; i += NNG_THREADS) {
+            const float4 q = s_pt[i];
+            atomicAdd(&s_start[cell_of(q.x, q.y, q.z) + 1], 1);
+        }
+        __syncthreads();
+        scan_counts(s_start);
+        for (int c = tid; c <= ncell; c += NNG_THREADS) s_cur[c] = c < ncell ? s_start[c] : 0;
+        __syncthreads();
+        for (int i = tid; i < S; i += NNG_THREADS) {
+            const float4 q = s_pt[i];
+            const int pos = atomicAdd(&s_cur[cell_of(q.x, q.y, q.z)], 1);
+            s_sp[pos] = q;
+            s_sj[pos] = (unsigned short)i;
+        }
+        __syncthreads();
+        // the workgroup's queries in cell order of the same grid (a query outside the box goes to the border cell, a NaN to 0)
+        for (int c = tid; c <= ncell; c += NNG_THREADS) s_cur[c] = 0;
+        __syncthreads();
+        for (int t = tid; t < nq; t += NNG_THREADS) {
+            const float *fp = f1 + (size_t)(q_begin + t) * 3;
+            atomicAdd(&s_cur[cell_of(fp[0], fp[1], fp[2]) + 1], 1);
+        }
+        __syncthreads();
+        scan_counts(s_cur);
+        for (int t = tid; t < nq; t += NNG_THREADS) {
+            const float *fp = f1 + (size_t)(q_begin + t) * 3;
+            s_qs[atomicAdd(&s_cur[cell_of(fp[0], fp[1], fp[2])], 1)] = (unsigned short)t;
+        }
+    }
+    __syncthreads();
+    const float span = (float)max(nx, max(ny, nz)) * edge;
+    const float box_abs = fmaxf(fmaxf(fmaxf(fabsf(bx), fabsf(by)), fabsf(bz)), fmaxf(fmaxf(fabsf(hx), fabsf(hy)), fabsf(hz)));
+    // a wave serves 64 queries that are neighbours in cell order
+    for (int g = wave; g * 64 < nq; g += NNG_THREADS / 64) {
+        const int t = g * 64 + lane;
+        const bool live = t < nq;
+        const int i = q_begin + (live ? (scan_all ? t : (int)s_qs[t]) : 0);
+        const float *fp = f1 + (size_t)i * 3;
+        const float fx = fp[0], fy = fp[1], fz = fp[2];
+        const float fsq = sumsq3(fx, fy, fz);
+        float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
+        int i0 = 0, i1 = 0, i2 = 0;
+        auto take = [&](float d, int j) {       // (d, j) into the best three, which stay ordered by d, then j
+            if (nn_before(d, j, d2, i2)) {      // (selects, not nested branches: before slot 0 implies before slot 1)
+                const bool b1 = nn_before(d, j, d1, i1), b0 = nn_before(d, j, d0, i0);
+                d2 = b1 ? d1 : d; i2 = b1 ? i1 : j;
+                d1 = b0 ? d0 : (b1 ? d : d1); i1 = b0 ? i0 : (b1 ? j : i1);
+                d0 = b0 ? d : d0; i0 = b0 ? j : i0;
+            }
+        };
+        auto cand = [&](int pos) {
+            const float4 q = s_sp[pos];
+            take(sqdist(fx, fy, fz, fsq, q.x, q.y, q.z, q.w), (int)s_sj[pos]);
+        };
+        // (written so that a NaN coordinate makes it true)
+        const bool far = scan_all || !(fx >= bx - span && fx <= hx + span && fy >= by - span && fy <= hy + span &&
+                                       fz >= bz - span && fz <= hz + span);
+        const bool walks = live && !far;
+        const int cx = cell1(fx, bx, nx), cy = cell1(fy, by, ny), cz = cell1(fz, bz, nz);
+        const float maxabs = fmaxf(box_abs, fmaxf(fmaxf(fabsf(fx), fabsf(fy)), fabsf(fz)));
+        const float err = NNG_ERR * (maxabs * maxabs), slack = NNG_SLACK * maxabs;
+        // after the cells [c - k, c + k]^3: may the walk stop?
+        auto done = [&](int k) {
+            float L = INFINITY;                 // nearest face of what is not visited
+            if (cx - k > 0) L = fminf(L, fx - (bx + (float)(cx - k) * edge));
+            if (cx + k < nx - 1) L = fminf(L, (bx + (float)(cx + k + 1) * edge) - fx);
+            if (cy - k > 0) L = fminf(L, fy - (by + (float)(cy - k) * edge));
+            if (cy + k < ny - 1) L = fminf(L, (by + (float)(cy + k + 1) * edge) - fy);
+            if (cz - k > 0) L = fminf(L, fz - (bz + (float)(cz - k) * edge));
+            if (cz + k < nz - 1) L = fminf(L, (bz + (float)(cz + k + 1) * edge) - fz);
+            if (L == INFINITY) return true;     // every cell visited
+            const float Ls = L - slack;
+            return Ls > 0.0f && Ls * Ls - err > d2;
+        };
+        bool alone = false;                     // this lane's walk goes on beyond what the wave visited together
+        if (__any(walks)) {
+            // together: every cell of the box around the wave's 3 x 3 x 3 blocks, a superset of each lane's own block; the run
+            // bounds and the candidates are wave-uniform (LDS broadcasts), a candidate costs what it costs in the scan
+            int x0 = walks ? cx : nx, x1 = walks ? cx : -1, y0 = walks ? cy : ny, y1 = walks ? cy : -1, z0 = walks ? cz : nz, z1 = walks ? cz : -1;
+            for (int o = 32; o > 0; o >>= 1) {
+                x0 = min(x0, __shfl_xor(x0, o)); y0 = min(y0, __shfl_xor(y0, o)); z0 = min(z0, __shfl_xor(z0, o));
+                x1 = max(x1, __shfl_xor(x1, o)); y1 = max(y1, __shfl_xor(y1, o)); z1 = max(z1, __shfl_xor(z1, o));
+            }
+            x0 = max(__builtin_amdgcn_readfirstlane(x0) - 1, 0); x1 = min(__builtin_amdgcn_readfirstlane(x1) + 1, nx - 1);
+            y0 = max(__builtin_amdgcn_readfirstlane(y0) - 1, 0); y1 = min(__builtin_amdgcn_readfirstlane(y1) + 1, ny - 1);
+            z0 = max(__builtin_amdgcn_readfirstlane(z0) - 1, 0); z1 = min(__builtin_amdgcn_readfirstlane(z1) + 1, nz - 1);
+            // rows that follow each other in the sorted list (the box spans all of x, or all of x and y) are one run; four
+            // candidates per step, and the index of a candidate is read only when its d can enter the best three
+            const bool all_x = x0 == 0 && x1 == nx - 1;
+            const int ys = all_x ? y1 - y0 + 1 : 1;
+            const int zs = all_x && ys == ny ? z1 - z0 + 1 : 1;
+            if (walks) {
+                for (int z = z0; z <= z1; z += zs)
+                    for (int y = y0; y <= y1; y += ys) {
+                        const int end = nn_uni(s_start[((z + zs - 1) * ny + (y + ys - 1)) * nx + x1 + 1]);
+                        for (int pos = nn_uni(s_start[(z * ny + y) * nx + x0]); pos < end; pos += 4) {
+                            float d[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const float4 q = s_sp[min(pos + u, S - 1)];
+                                d[u] = sqdist(fx, fy, fz, fsq, q.x, q.y, q.z, q.w);
+                            }
+#pragma unroll
+                            for (int u = 0; u < 4; ++u)
+                                if (pos + u < end && d[u] <= d2) take(d[u], (int)s_sj[pos + u]);
+                        }
+                    }
+            }
+            alone = walks && !done(1);
+        }
+        if (alone) {
+            // rare (the third best lies beyond this lane's own block): the lane starts over and walks by itself, its own block
+            // as one loop over the candidates of its 9 runs, then shell by shell
+            d0 = d1 = d2 = INFINITY; i0 = i1 = i2 = 0;
+            {
+                const int x0 = max(cx - 1, 0), xn = min(cx + 1, nx - 1) - x0 + 1;
+                int r = 0, pos = 0, end = 0;
+                for (;;) {
+                    while (pos >= end && r < 9) {
+                        const int rz = (r * 11) >> 5;                  // r / 3 for r < 9
+                        const int z = cz + rz - 1, y = cy + (r - 3 * rz) - 1;
+                        if (z >= 0 && z < nz && y >= 0 && y < ny) {
+                            const int lin = (z * ny + y) * nx + x0;
+                            pos = s_start[lin]; end = s_start[lin + xn];
+                        }
+                        ++r;
+                    }
+                    if (pos >= end) break;
+                    cand(pos++);
+                }
+            }
+            for (int k = 1; !done(k); ++k) {
+                // shell k + 1: full x runs in its top / bottom / front / back rows, the two end cells in the others
+                const int kk = k + 1;
+                for (int z = max(cz - kk, 0); z <= min(cz + kk, nz - 1); ++z)
+                    for (int y = max(cy - kk, 0); y <= min(cy + kk, ny - 1); ++y) {
+                        const int row = (z * ny + y) * nx;
+                        const bool rim = z - cz == kk || cz - z == kk || y - cy == kk || cy - y == kk;
+                        if (rim) {
+                            const int end = s_start[row + min(cx + kk, nx - 1) + 1];
+                            for (int pos = s_start[row + max(cx - kk, 0)]; pos < end; ++pos) cand(pos);
+                        } else {
+                            if (cx - kk >= 0) { const int end = s_start[row + cx - kk + 1]; for (int pos = s_start[row + cx - kk]; pos < end; ++pos) cand(pos); }
+                            if (cx + kk < nx) { const int end = s_start[row + cx + kk + 1]; for (int pos = s_start[row + cx + kk]; pos < end; ++pos) cand(pos); }
+                        }
+                    }
+            }
+        }
+        if (live && far) {
+            for (int j = 0; j < S; ++j) {       // the scan: ascending j, strict `<`
+                const float4 q = s_pt[j];
+                const float d = sqdist(fx, fy, fz, fsq, q.x, q.y, q.z, q.w);
+                if (d < d2) {
+                    if (d < d1) {
+                        d2 = d1; i2 = i1;
+                        if (d < d0) { d1 = d0; i1 = i0; d0 = d; i0 = j; }
+                        else { d1 = d; i1 = j; }
+                    } else { d2 = d; i2 = j; }
+                }
+            }
+        }
+        if (live) {
+            float r0 = __fdiv_rn(1.0f, __fadd_rn(d0, 1e-8f));
+            float r1 = __fdiv_rn(1.0f, __fadd_rn(d1, 1e-8f));
+            float r2 = __fdiv_rn(1.0f, __fadd_rn(d2, 1e-8f));
+            float norm = __fadd_rn(__fadd_rn(r0, r1), r2);
+            size_t o = ((size_t)p * N + i) * 3;
+            idx[o] = i0; idx[o + 1] = i1; idx[o + 2] = i2;
+            w[o] = __fdiv_rn(r0, norm); w[o + 1] = __fdiv_rn(r1, norm); w[o + 2] = __fdiv_rn(r2, norm);
+        }
+    }
+}
+
 // square_distance(src, dst) materialised (public helper of pointnet_util; not on the attack path)
 __global__ void square_distance_kernel(const float *__restrict__ src, const float *__restrict__ dst, int N, int M,
                                        float *__restrict__ out)
@@ -638,6 +950,29 @@ extern "C" int psg_three_nn(psg_ctx *ctx, const float *xyz1, int n_clouds1, cons
     PSG_REQUIRE(ctx && xyz1 && xyz2 && out_idx && out_w, "psg_three_nn: null argument");
     PSG_REQUIRE(P > 0 && n_clouds1 > 0 && N > 0 && S >= 3, "psg_three_nn: bad sizes (need S >= 3)");
     PSG_REQUIRE(S <= 8192, "psg_three_nn: S=%d exceeds the LDS-resident limit 8192", S);
+    // PSG_THREE_NN=scan forces the scan, =grid the grid kernel wherever its LDS layout fits (A/B runs, tests); unset: the grid
+    // kernel at the level-0 shape of a plan.  tools/three_nn_probe.py on MI355X, ms per launch, scan / grid:
+    //                  2560 problems    320 problems    8 problems
+    //   4096 x 1024    2.07 / 1.08      0.32 / 0.26     0.078 / 0.098
+    //   1024 x  256    0.22 / 0.25      0.039 / 0.080   0.027 / 0.058
+    //    256 x   64    0.024 / 0.107    0.010 / 0.042   0.009 / 0.036
+    // (the build and the sort of the queries cost a workgroup ~30 us before its first candidate: not repaid below level 0, and
+    // not with eight problems; between 8 and 320 problems nothing was measured, so the scan stays there)
+    static const int mode = []() {
+        const char *v = psg::env_str("PSG_THREE_NN");
+        return !v ? 0 : std::string(v) == "scan" ? 1 : std::string(v) == "grid" ? 2 : 0;
+    }();
+    if (S <= NNG_MAX_S && (mode == 2 || (mode == 0 && N >= 2048 && S >= 512 && P >= 320))) {
+        // a workgroup serves all queries of a problem (one grid build per problem) once there are problems enough to fill the
+        // device, else 1024 of them
+        const int qpb = (size_t)P * psg::ceil_div(N, 1024) > 2048 ? 4096 : 1024;
+        const size_t glds = (size_t)S * (2 * sizeof(float4) + 2) + (size_t)(2 * NNG_CELLS + 2) * 4 + (size_t)qpb * 2;
+        if (glds + 1024 > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)three_nn_grid_kernel));
+        hipLaunchKernelGGL(three_nn_grid_kernel, dim3(psg::ceil_div(N, qpb), P), dim3(NNG_THREADS), glds, (hipStream_t)stream,
+                           xyz1, n_clouds1, xyz2, N, S, qpb, out_idx, out_w);
+        PSG_LAUNCH_CHECK();
+        return PSG_OK;
+    }
     size_t lds = (size_t)2 * ((S + 1) / 2) * sizeof(float4);
     if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)three_nn_kernel));
     hipLaunchKernelGGL(three_nn_kernel, dim3(psg::ceil_div(N, NN_THREADS), P), dim3(NN_THREADS), lds,
