@@ -1291,6 +1291,23 @@ int psg_scene_pgd_step(float *scene_rgb, const float *scene_ori, const uint8_t *
                        const int32_t *occ_ent, const float *dx0, int rows, int n_scene, float alpha, float eps, float dir,
                        int last, float *gsum_out, psg_stream stream);
 
+/* The coordinate field of the whole-scene attack: ONE displacement delta [n_scene][3] (metres) per
+ * scene point.  Same slot / rows conventions and refusals as above; no float atomics, one writer per output element.
+ *
+ * psg_scene_delta_to_blocks: x [rows][9], channels 0:3 of every slot <- fl32(x_clean[e][0:3] + delta[point_idx[e]]): one
+ * fp32 add onto the CLEAN block coordinates x_clean [rows][9] (channels 0:3 are read); the other six floats of a row of x
+ * keep their bytes.  Bad index: flag, row neither read nor written.
+ * psg_scene_field_step: for every scene point p (scene_mask nullable: under the mask only) with at least one slot:
+ *   g = ((0 + dx0[e_0][0:3]) + dx0[e_1][0:3]) + ...   over the slots of p in list order, fp32, no contraction
+ *   stepped = delta + fl(dir*alpha)*sign(g) (sign(0) = sign(NaN) = 0);  delta = last ? stepped : clamp(stepped, -eps, +eps)
+ * delta [n_scene][3] in place; there is no box.  A point without a slot does not move.  Lists are bounded as in
+ * psg_scene_pgd_step; gsum_out (nullable) [n_scene][3] as there. */
+int psg_scene_delta_to_blocks(const float *delta, const int32_t *point_idx, const float *x_clean, int rows, int n_scene,
+                              float *x, int32_t *bad_flag, psg_stream stream);
+int psg_scene_field_step(float *delta, const uint8_t *scene_mask, const int32_t *occ_off, const int32_t *occ_ent,
+                         const float *dx0, int rows, int n_scene, float alpha, float eps, float dir, int last,
+                         float *gsum_out, psg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,8 @@ SIGNATURES = {
     "psg_scene_colour_to_blocks": (ci, [vp, vp, ci, ci, vp, vp, vp]),
     "psg_scene_rows_mask": (ci, [vp, vp, vp, ci, ci, ci, vp]),
     "psg_scene_pgd_step": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, ci, vp, vp]),
+    "psg_scene_delta_to_blocks": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
+    "psg_scene_field_step": (ci, [vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, ci, vp, vp]),
 }
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd.attacks.torchattacks.attacks._common import check_field
 from pointsecguard_amd.models import pointnet2_sem_seg, pointnet2_sem_seg_msg
 from pointsecguard_amd.models.pointnet2_sem_seg import draw_fps_starts, upload
 
@@ -56,10 +57,33 @@ class SceneNBAttack:
     bit-identical to torchattacks.NB_attack on a scene whose blocks do not overlap.
 
     trace: optional callback, called after every iteration with (t, starts of every batch [list of int32 device tensors],
-    dx0 [nb, bp, 9], c before the step, c after it, dlogp [nb, bp, 13]) - device tensors; dx0 is the attack's own buffer."""
+    dx0 [nb, bp, 9], c before the step, c after it, dlogp [nb, bp, 13]) - device tensors; dx0 is the attack's own buffer.
 
-    def __init__(self, model, eps, alpha, iters, batch_size=8, target=None, origin=None, project_last=True, trace=None):
+    field (an extension of the reference API, like NB_attack's): "color" (default) is the attack above,
+    launch for launch.  "coord" moves channels 0:3, "both" the two fields together; PointNet++ SSG only (the exact coordinate
+    gradient psg_pn2_backward_full).  The variable is ONE displacement delta [n_scene][3] (float32, metres, starting at zero)
+    per scene point, |delta| <= coord_eps and no box; coord_eps / coord_alpha fall back to eps / alpha.  Every slot holds
+    x[e][0:3] = fl32(x_clean[e][0:3] + delta[point_idx[e]]) - one fp32 add onto the slot's clean, block-centred coordinates -,
+    so all copies of a point carry the same displacement to within half an ulp of each slot's coordinate; channels 6:9 stay
+    as given (the per-block coordinate field's convention).  Block membership is the ORIGINAL slicing's: a point that moves
+    across a block's border stays in the blocks that held it, the moved scene is not re-sliced.  Per iteration every batch
+    runs psg_scene_delta_to_blocks (both: + psg_scene_colour_to_blocks), the FPS starts, psg_pn2_plan_build (geometry moves),
+    psg_pn2_forward_lean, psg_ce_logp_grad, (targeted) psg_scene_rows_mask and psg_pn2_backward_full; then
+    psg_scene_field_step sums channels 0:3 of the block gradients over each point's slots in ascending slot order and takes
+    delta = clamp(delta + dir * coord_alpha * sign(g), -coord_eps, coord_eps) (un-clamped on the last iteration under
+    project_last=False); "both" also runs psg_scene_pgd_step on channels 3:6 of the same gradients.  __call__ still returns
+    (adv_rgb01, adv_blocks) - adv_rgb01 is the clean c0 under "coord" -; the final delta is left in self.last_delta (device
+    tensor [n_scene, 3]; None after a colour run).
+    trace_field: the field path's callback (`trace` is the colour path's and is not called here), called after every iteration
+    with a dict: t, starts, dx0 [nb, bp, 9], delta_before, delta_after, c_before, c_after (None under "coord"), dlogp."""
+
+    def __init__(self, model, eps, alpha, iters, batch_size=8, target=None, origin=None, project_last=True, trace=None,
+                 field="color", coord_eps=None, coord_alpha=None, trace_field=None):
         self.model = check_scene_model(model)
+        self.field = check_field(field)
+        if self.field != "color" and not isinstance(model, pointnet2_sem_seg.get_model):
+            raise NotImplementedError("field=%r is implemented for the PointNet++ SSG network (pointnet2_sem_seg): the exact "
+                                      "coordinate gradient psg_pn2_backward_full refuses MSG" % self.field)
         if (target is None) != (origin is None):
             raise ValueError("the targeted scene attack needs both `target` and `origin`")
         if target is not None and not 0 <= int(target) < NUM_CLASSES:
@@ -67,7 +91,11 @@ class SceneNBAttack:
         if int(iters) < 1 or int(batch_size) < 1:
             raise ValueError("iters and batch_size must be positive")
         self.eps, self.alpha, self.iters, self.batch_size = float(eps), float(alpha), int(iters), int(batch_size)
+        self.coord_eps = self.eps if coord_eps is None else float(coord_eps)
+        self.coord_alpha = self.alpha if coord_alpha is None else float(coord_alpha)
         self.target, self.origin, self.project_last, self.trace = target, origin, bool(project_last), trace
+        self.trace_field = trace_field
+        self.last_delta = None
 
     def __call__(self, blocks, point_idx, block_labels, scene_rgb, scene_labels):
         net = self.model
@@ -101,6 +129,9 @@ class SceneNBAttack:
         if int(bad.item()):        # (the one read-back, before the loop: once per scene)
             raise IndexError("SceneNBAttack: a point index is outside [0, %d)" % n_scene)
 
+        if self.field != "color":
+            return self._run_field(net, dev, x, idx, gt, c0, mask, occ_off, occ_ent, bad)
+        self.last_delta = None
         x = x.clone()              # the caller's blocks stay clean
         c = c0.clone()
         dx0_all = torch.zeros(nb, bp, 9, dtype=torch.float32, device=dev)     # backward_colour writes channels 3:6 only
@@ -140,4 +171,60 @@ class SceneNBAttack:
             if trace is not None:
                 trace(t, starts_t, dx0_all, c_before, c.clone(), dlogp_all)
         runtime.scene_colour_to_blocks(c, idx, x, bad)
+        return c, x
+
+    def _run_field(self, net, dev, x_clean, idx, gt, c0, mask, occ_off, occ_ent, bad):
+        """field = "coord" | "both": the loop of the class docstring on delta [n_scene][3] (and on c under "both")."""
+        nb, bp = x_clean.shape[0], x_clean.shape[1]
+        both = self.field == "both"
+        targeted = self.target is not None
+        x = x_clean.clone()        # the caller's blocks stay clean: every iteration adds delta onto THEM
+        delta = torch.zeros(c0.shape[0], 3, dtype=torch.float32, device=dev)
+        c = c0.clone() if both else c0
+        dx0_all = torch.empty(nb, bp, 9, dtype=torch.float32, device=dev)     # backward_full writes all nine channels
+        model = net._packed()
+        batches = [(lo, min(lo + self.batch_size, nb)) for lo in range(0, nb, self.batch_size)]
+        sizes = sorted({hi - lo for lo, hi in batches})
+        ws = {b: net._workspace(b, bp, 1) for b in sizes}
+        net._generation += 1       # the workspace activations no longer belong to an earlier autograd forward
+        logp = {b: torch.empty(b, bp, NUM_CLASSES, dtype=torch.float32, device=dev) for b in sizes}
+        trace = self.trace_field
+        if trace is not None:
+            dlogp_all = torch.zeros(nb, bp, NUM_CLASSES, dtype=torch.float32, device=dev)
+        else:
+            dlogp = {b: torch.empty(b, bp, NUM_CLASSES, dtype=torch.float32, device=dev) for b in sizes}
+        direction = -1.0 if targeted else 1.0
+        st = runtime.stream
+        for t in range(self.iters):
+            starts_t = []
+            for lo, hi in batches:
+                b = hi - lo
+                xb, ib, w = x[lo:hi], idx[lo:hi], ws[b]
+                runtime.scene_delta_to_blocks(delta, ib, x_clean[lo:hi], xb, bad)
+                if both:
+                    runtime.scene_colour_to_blocks(c, ib, xb, bad)
+                starts = upload(draw_fps_starts(b, bp, 1, pinned=True), dev, pin=True)
+                dl = dlogp_all[lo:hi] if trace is not None else dlogp[b]
+                _lib.call("psg_pn2_plan_build", w.handle, runtime.ptr(xb), runtime.ptr(starts), 1, st())
+                _lib.call("psg_pn2_forward_lean", model.handle, w.handle, 0, runtime.ptr(xb), runtime.ptr(logp[b]), st())
+                _lib.call("psg_ce_logp_grad", runtime.ptr(logp[b]), None if targeted else runtime.ptr(gt[lo:hi]),
+                          int(self.target) if targeted else 0, b * bp, b * bp, NUM_CLASSES, 1.0 / bp, runtime.ptr(dl), None, st())
+                if targeted:
+                    runtime.scene_rows_mask(dl, ib, mask)
+                _lib.call("psg_pn2_backward_full", model.handle, w.handle, 0, runtime.ptr(dl), runtime.ptr(dx0_all[lo:hi]), st())
+                if trace is not None:
+                    starts_t.append(starts)
+            last = t == self.iters - 1 and not self.project_last
+            if trace is not None:
+                before = dict(delta_before=delta.clone(), c_before=c.clone() if both else None)
+            runtime.scene_field_step(delta, mask, occ_off, occ_ent, dx0_all, self.coord_alpha, self.coord_eps, direction, last)
+            if both:
+                runtime.scene_pgd_step(c, c0, mask, occ_off, occ_ent, dx0_all, self.alpha, self.eps, direction, last)
+            if trace is not None:
+                trace(dict(t=t, starts=starts_t, dx0=dx0_all, delta_after=delta.clone(), c_after=c.clone() if both else None,
+                           dlogp=dlogp_all, **before))
+        runtime.scene_delta_to_blocks(delta, idx, x_clean, x, bad)
+        if both:
+            runtime.scene_colour_to_blocks(c, idx, x, bad)
+        self.last_delta = delta
         return c, x

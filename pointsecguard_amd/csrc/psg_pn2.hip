@@ -1910,7 +1910,9 @@ static int geometry_grad(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *dx0, 
         hipLaunchKernelGGL(gx_level_kernel, dim3(std::min(2048, ceil_div(B * n, GG_NT))), dim3(GG_NT), 0, st, a, B);
         PSG_LAUNCH_CHECK();
         if (L <= 3) {
-            hipLaunchKernelGGL(gx_fps_down_kernel, dim3(std::min(2048, ceil_div(B * kS[L], GG_NT))), dim3(GG_NT), 0, st,
+            static_assert(GX_FPS_MAX_S >= 1024, "gx_fps_down_kernel holds a room's FPS table (kS[L] entries) in LDS");
+            PSG_REQUIRE(kS[L] <= GX_FPS_MAX_S, "psg_pn2_backward_full: level %d has more coarse points than gx_fps_down_kernel holds", L);
+            hipLaunchKernelGGL(gx_fps_down_kernel, dim3(B), dim3(GG_NT), 0, st,
                                (const float *)ws->gxyz[L + 1], (const int32_t *)(ws->fps[L] + prob * kS[L]), B, kS[L], n, a.out, a.out_ld);
             PSG_LAUNCH_CHECK();
         }

@@ -199,18 +199,36 @@ __global__ __launch_bounds__(GG_NT) void gx_level_kernel(GxArgs a, int B)
 }
 
 // new_xyz = xyz[fps_idx] (pointnet_util.py:126): the coarser level's complete coordinate gradient is added to the rows of
-// the points FPS chose.  FPS picks distinct points, so every fine row has at most one writer.
+// the points FPS chose.  FPS picks distinct points while the cloud has unpicked positions left; a cloud with fewer distinct
+// positions than S (a block padded by sampling with replacement, at a level with S = N) makes it pick one index again and
+// again, and the gather's transpose then SUMS those coarse rows.  One workgroup per room, the room's table in LDS: the
+// first coarse point s that names a fine row p owns it and adds g[s], then g[s''] of every later s'' that names p, in
+// ascending s'' - one writer per row and a fixed order, whatever the table; an injective table gives the single add.
+constexpr int GX_FPS_MAX_S = 1024;
 __global__ __launch_bounds__(GG_NT) void gx_fps_down_kernel(const float *__restrict__ g_coarse, const int32_t *__restrict__ fps,
                                                             int B, int S, int n_fine, float *__restrict__ out, int out_ld)
 {
-    const size_t total = (size_t)B * S;
-    for (size_t t = (size_t)blockIdx.x * GG_NT + threadIdx.x; t < total; t += (size_t)gridDim.x * GG_NT) {
-        const int b = (int)(t / S);
-        const int p = fps[t];
+    __shared__ int32_t s_fps[GX_FPS_MAX_S];
+    const int b = blockIdx.x;
+    if (b >= B || S > GX_FPS_MAX_S) return;
+    for (int s = threadIdx.x; s < S; s += GG_NT) s_fps[s] = fps[(size_t)b * S + s];
+    __syncthreads();
+    for (int s = threadIdx.x; s < S; s += GG_NT) {
+        const int p = s_fps[s];
         if (p < 0 || p >= n_fine) continue;
+        bool owner = true;
+        for (int j = 0; j < s; ++j)
+            if (s_fps[j] == p) { owner = false; break; }
+        if (!owner) continue;
         float *o = out + ((size_t)b * n_fine + p) * out_ld;
-        const float *g = g_coarse + t * 3;
-        o[0] += g[0]; o[1] += g[1]; o[2] += g[2];
+        const float *g = g_coarse + ((size_t)b * S + s) * 3;
+        float ox = o[0] + g[0], oy = o[1] + g[1], oz = o[2] + g[2];
+        for (int j = s + 1; j < S; ++j) {
+            if (s_fps[j] != p) continue;
+            const float *gj = g_coarse + ((size_t)b * S + j) * 3;
+            ox += gj[0]; oy += gj[1]; oz += gj[2];
+        }
+        o[0] = ox; o[1] = oy; o[2] = oz;
     }
 }
 

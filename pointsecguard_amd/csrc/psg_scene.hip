@@ -4,6 +4,10 @@
 //   psg_scene_rows_mask         zero the dlogp rows of slots whose scene point is not under the scene mask
 //   psg_scene_pgd_step          gradient summed over a point's occurrences in ascending slot order, then psg_pgd_step's
 //                               arithmetic (psg_attack.hip: pgd_step_kernel) on the scene's colours
+// and the coordinate field of the same attack: ONE displacement delta [n_scene][3] per scene point
+//   psg_scene_delta_to_blocks   channels 0:3 of every block row <- fl32(clean coordinate of the row + delta of its point)
+//   psg_scene_field_step        the same ordered sum over channels 0:3 of the block gradients, a sign step on delta and the
+//                               clamp to [-eps, +eps] (no box: coordinates have none)
 // Compiled with -ffp-contract=off: the summation order and the step's evaluation order decide bits.  No float atomics
 // anywhere; every output element has one writer.  The only atomics are integer ones (histogram, list cursors, the bad-index
 // flag), whose results do not depend on the order they land in; the order INSIDE a list, which an atomic cursor would leave
@@ -145,6 +149,53 @@ __global__ void scene_pgd_step_kernel(float *__restrict__ scene_rgb, const float
     scene_rgb[t] = last ? stepped : proj;
 }
 
+// x[row][ch] = fl32(x_clean[row][ch] + delta[point_idx[row]][ch]) for ch in 0:3 - one fp32 add onto the CLEAN coordinate of
+// the slot (never onto the previously moved one); the other six floats of a row are not touched
+__global__ void delta_to_blocks_kernel(const float *__restrict__ delta, const int32_t *__restrict__ point_idx,
+                                       const float *__restrict__ x_clean, size_t total, int n_scene, float *__restrict__ x,
+                                       int32_t *__restrict__ bad)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // over rows * 3
+    if (t >= total) return;
+    const size_t row = t / 3;
+    const int ch = (int)(t % 3);
+    const int p = point_idx[row];
+    if (p < 0 || p >= n_scene) { atomicOr(bad, 1); return; }
+    x[row * 9 + ch] = __fadd_rn(x_clean[row * 9 + ch], delta[(size_t)p * 3 + ch]);
+}
+
+// one thread per (scene point, coordinate): scene_pgd_step_kernel's list walk over channels 0:3, then
+// stepped = delta + step * sign(g); delta = last ? stepped : clamp(stepped, -eps, +eps)
+__global__ void scene_field_step_kernel(float *__restrict__ delta, const uint8_t *__restrict__ scene_mask,
+                                        const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ_ent,
+                                        const float *__restrict__ dx0, int rows, size_t total, float step, float eps, int last,
+                                        float *__restrict__ gsum_out)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // over n_scene * 3
+    if (t >= total) return;
+    const size_t p = t / 3;
+    const int ch = (int)(t % 3);
+    const bool on = !scene_mask || scene_mask[p];
+    int lo = occ_off[p], hi = occ_off[p + 1];
+    lo = max(lo, 0);
+    hi = min(hi, rows);
+    float g = 0.0f;
+    bool any = false;
+    if (on) {
+        for (int i = lo; i < hi; ++i) {
+            const int e = occ_ent[i];
+            if (e < 0 || e >= rows) continue;
+            g = __fadd_rn(g, dx0[(size_t)e * 9 + ch]);
+            any = true;
+        }
+    }
+    if (gsum_out) gsum_out[t] = g;
+    if (!any) return;                                  // no occurrence (or not under the mask): the point does not move
+    const float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
+    const float stepped = __fadd_rn(delta[t], __fmul_rn(step, sg));
+    delta[t] = last ? stepped : fminf(fmaxf(stepped, -eps), eps);
+}
+
 // the rows of [rows][9] are addressed through int32 slot numbers (the lists hold them): rows * 9 floats must stay below 2^31
 inline bool rows_ok(int rows) { return rows > 0 && rows <= INT_MAX / 9; }
 
@@ -209,6 +260,31 @@ extern "C" int psg_scene_pgd_step(float *scene_rgb, const float *scene_ori, cons
     const size_t total = (size_t)n_scene * 3;
     hipLaunchKernelGGL(scene_pgd_step_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, scene_rgb, scene_ori,
                        scene_mask, occ_off, occ_ent, dx0, rows, total, dir * alpha, eps, last, gsum_out);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_scene_delta_to_blocks(const float *delta, const int32_t *point_idx, const float *x_clean, int rows, int n_scene,
+                                         float *x, int32_t *bad_flag, psg_stream stream)
+{
+    PSG_REQUIRE(delta && point_idx && x_clean && x && bad_flag && n_scene > 0, "psg_scene_delta_to_blocks: bad argument");
+    PSG_REQUIRE(rows_ok(rows), "psg_scene_delta_to_blocks: rows=%d outside 1 .. INT_MAX / 9", rows);
+    const size_t total = (size_t)rows * 3;
+    hipLaunchKernelGGL(delta_to_blocks_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, delta, point_idx, x_clean,
+                       total, n_scene, x, bad_flag);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_scene_field_step(float *delta, const uint8_t *scene_mask, const int32_t *occ_off, const int32_t *occ_ent,
+                                    const float *dx0, int rows, int n_scene, float alpha, float eps, float dir, int last,
+                                    float *gsum_out, psg_stream stream)
+{
+    PSG_REQUIRE(delta && occ_off && occ_ent && dx0 && n_scene > 0, "psg_scene_field_step: bad argument");
+    PSG_REQUIRE(rows_ok(rows), "psg_scene_field_step: rows=%d outside 1 .. INT_MAX / 9 (slot numbers address [rows][9] floats)", rows);
+    const size_t total = (size_t)n_scene * 3;
+    hipLaunchKernelGGL(scene_field_step_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, delta, scene_mask,
+                       occ_off, occ_ent, dx0, rows, total, dir * alpha, eps, last, gsum_out);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
 }

@@ -334,7 +334,7 @@ def _scene_batch(classifier, attack, make_attack, targeted, lane, dev, n_pt, sba
 
 
 def evaluate_whole_scene_consistent(classifier, dataset, make_scene_attack, batch_size=8, log_path=None, rank=0, world=1,
-                                    log=print, targeted=None, on_scene=None):
+                                    log=print, targeted=None, on_scene=None, on_scene_field=None):
     """evaluate_whole_scene with ONE adversarial scene per room: the attack moves one colour per
     physical scene point - attacks.scene.SceneNBAttack - instead of one per block slot, so the adversarial blocks that are
     voted on are slices of a point cloud that exists (and can be saved and re-sliced).
@@ -355,7 +355,10 @@ def evaluate_whole_scene_consistent(classifier, dataset, make_scene_attack, batc
     blocks) and the totals are those of evaluate_whole_scene.  targeted = dict(origin=o, target=t): the ten-column rows,
     written for the batches that hold a point of `origin`; a scene without such a point is evaluated clean and logs no rows.
     on_scene(name, adv_rgb01): called once per scene with the adversarial colours as a float32 numpy array [n_scene, 3] in
-    [0, 1] (the clean ones for a scene that was not attacked) - the reference's .xyzrgb dump.  One stream, no replicas."""
+    [0, 1] (the clean ones for a scene that was not attacked) - the reference's .xyzrgb dump.  One stream, no replicas.
+    on_scene_field(name, adv_rgb01, adv_xyz): the same call with the moved geometry beside the colours, for a scene attack
+    built with field="coord" | "both" (DESIGN.md section 5v): adv_xyz = the scene's xyz (float64, metres, [n_scene, 3]) + the
+    attack's displacement delta; the clean arrays for a scene that was not attacked or an attack that moves colours only."""
     from .attacks.scene import check_scene_model
     check_scene_model(classifier)
     dev = next(classifier.parameters()).device
@@ -411,6 +414,13 @@ def evaluate_whole_scene_consistent(classifier, dataset, make_scene_attack, batc
             if on_scene is not None:
                 on_scene(dataset.file_list[si][:-4],
                          adv_rgb.cpu().numpy() if attacked else (rgb_np / 255.0).astype(np.float32))
+            if on_scene_field is not None:
+                xyz = np.array(dataset.scene_points_list[si][:, 0:3], dtype=np.float64)
+                delta = getattr(attack, "last_delta", None) if attacked else None
+                if delta is not None:
+                    xyz += delta.cpu().numpy().astype(np.float64)
+                on_scene_field(dataset.file_list[si][:-4],
+                               adv_rgb.cpu().numpy() if attacked else (rgb_np / 255.0).astype(np.float32), xyz)
             _write_rows(pending, targeted, fh)
             c_scene = vote_stats(pool, scene_labels)
             c_scene_adv = vote_stats(adv_pool, scene_labels)

@@ -534,6 +534,41 @@ def scene_pgd_step(scene_rgb, scene_ori, scene_mask, occ_off, occ_ent, dx0, alph
     return scene_rgb
 
 
+def scene_delta_to_blocks(delta, point_idx, x_clean, x, bad):
+    """x [.., 9] channels 0:3 of every slot <- fl32(x_clean [.., 9] channels 0:3 + delta [n_scene, 3] of its point), in
+    place on x; x_clean holds the clean blocks (psg_scene_delta_to_blocks)."""
+    require_cuda(delta, "delta", torch.float32)
+    require_cuda(point_idx, "point_idx", torch.int32)
+    require_cuda(x_clean, "x_clean", torch.float32)
+    require_cuda(x, "x", torch.float32)
+    require_cuda(bad, "bad", torch.int32)
+    rows = point_idx.numel()
+    assert x.numel() == rows * 9 and x_clean.numel() == rows * 9 and delta.dim() == 2 and delta.shape[1] == 3
+    _lib.call("psg_scene_delta_to_blocks", ptr(delta), ptr(point_idx), ptr(x_clean), rows, delta.shape[0], ptr(x), ptr(bad),
+              stream())
+    return x
+
+
+def scene_field_step(delta, scene_mask, occ_off, occ_ent, dx0, alpha, eps, direction, last, gsum_out=None):
+    """One step on the scene's displacements [n_scene, 3] (in place) from channels 0:3 of the block gradients dx0 [rows, 9]
+    summed over every point's slots in ascending slot order; clamp to [-eps, eps], no box (psg_scene_field_step)."""
+    require_cuda(delta, "delta", torch.float32)
+    require_cuda(occ_off, "occ_off", torch.int32)
+    require_cuda(occ_ent, "occ_ent", torch.int32)
+    require_cuda(dx0, "dx0", torch.float32)
+    if scene_mask is not None:
+        require_cuda(scene_mask, "scene_mask", torch.uint8)
+        assert scene_mask.numel() == delta.shape[0]
+    if gsum_out is not None:
+        require_cuda(gsum_out, "gsum_out", torch.float32)
+        assert gsum_out.shape == delta.shape
+    rows, n_scene = occ_ent.numel(), delta.shape[0]
+    assert dx0.numel() == rows * 9 and occ_off.numel() == n_scene + 1 and delta.shape == (n_scene, 3)
+    _lib.call("psg_scene_field_step", ptr(delta), ptr(scene_mask), ptr(occ_off), ptr(occ_ent), ptr(dx0), rows, n_scene,
+              float(alpha), float(eps), float(direction), 1 if last else 0, ptr(gsum_out), stream())
+    return delta
+
+
 # ---- ResGCN (dense DeepGCN) ------------------------------------------------------------------------
 def gcn_tensor_list(sd, n_blocks):
     """state_dict (reference key names, ResGCN/sem_seg_dense/architecture.py) -> the flat fp32 tensor list of

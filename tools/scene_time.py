@@ -12,9 +12,14 @@ three pay the same one).  Median, min and max in blocks/s (blocks of the room / 
 The per-block loop is the yardstick; the consistent loop rebuilds the geometry plan for every (iteration, batch) and coalesces
 nothing, so it is expected to be slower.
 
+--field coord | both adds the coordinate field to the same rounds: after `consistent` (colours, as above)
+come `consistent_field` (SceneNBAttack(field=...), one displacement per scene point) and the per-block loop with
+NB_attack(field=...) at streams = 1 and at its default streams; coord_eps / coord_alpha follow eps / alpha.  The ratios are then
+consistent_field over each of the three.
+
 --kernel-trace DIR_OR_CSV folds in, from a `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python
-tools/scene_time.py --only consistent --runs 1` run made BEFORE, the share of the device time of that run spent in the kernels
-of csrc/psg_scene.hip (timings taken under the profiler are not figures for the calls); --trace-only prints that and stops.
+tools/scene_time.py --only consistent --runs 1` (with --field: `--only consistent_field`) run made BEFORE, the share of the device time of that run spent in the kernels
+of csrc/psg_scene.hip, and in the two coordinate-field kernels among them (timings taken under the profiler are not figures for the calls); --trace-only prints that and stops.
 """
 import argparse
 import json
@@ -29,8 +34,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 OURS = ("occ_count_kernel", "occ_scan_kernel", "occ_fill_kernel", "occ_rank_kernel", "colour_to_blocks_kernel",
-        "rows_mask_kernel", "scene_pgd_step_kernel")
+        "rows_mask_kernel", "scene_pgd_step_kernel", "delta_to_blocks_kernel", "scene_field_step_kernel")
+FIELD_KERNELS = ("delta_to_blocks_kernel", "scene_field_step_kernel")
 VARIANTS = ("consistent", "per_block_streams1", "per_block_default")
+FIELD_VARIANTS = ("consistent", "consistent_field", "per_block_field_streams1", "per_block_field_default")
 
 
 def synthetic_room(n, size_x, size_y, seed=28):
@@ -57,7 +64,9 @@ def scene_kernel_share(path):
                 d = per.setdefault(name, dict(calls=0, total_us=0.0))
                 d["calls"] += 1
                 d["total_us"] += us
-    return dict(scene_kernels_us=ours, all_kernels_us=total, share=ours / total if total else None, kernels=per)
+    field = sum(per[k]["total_us"] for k in FIELD_KERNELS if k in per)
+    return dict(scene_kernels_us=ours, field_kernels_us=field, all_kernels_us=total, share=ours / total if total else None,
+                field_share=field / total if total else None, kernels=per)
 
 
 def main():
@@ -68,7 +77,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=8)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--only", choices=VARIANTS, default=None)
+    ap.add_argument("--field", choices=("color", "coord", "both"), default="color")
+    ap.add_argument("--only", choices=sorted(set(VARIANTS + FIELD_VARIANTS)), default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-trace", default=None)
     ap.add_argument("--trace-only", action="store_true")
@@ -100,6 +110,14 @@ def main():
         if variant == "consistent":
             harness.evaluate_whole_scene_consistent(net, ds, lambda m: SceneNBAttack(m, eps, alpha, a.iters),
                                                     batch_size=a.batch_size, log=quiet)
+        elif variant == "consistent_field":
+            harness.evaluate_whole_scene_consistent(net, ds, lambda m: SceneNBAttack(m, eps, alpha, a.iters, field=a.field),
+                                                    batch_size=a.batch_size, log=quiet)
+        elif variant.startswith("per_block_field"):
+            kw = {"streams": 1} if variant == "per_block_field_streams1" else {}
+            harness.evaluate_whole_scene(net, ds, lambda m: torchattacks.NB_attack(m, eps=eps, alpha=alpha, iters=a.iters,
+                                                                                     field=a.field),
+                                         batch_size=a.batch_size, log=quiet, **kw)
         else:
             kw = {"streams": 1} if variant == "per_block_streams1" else {}
             harness.evaluate_whole_scene(net, ds, lambda m: torchattacks.NB_attack(m, eps=eps, alpha=alpha, iters=a.iters),
@@ -107,7 +125,10 @@ def main():
         torch.cuda.synchronize()
         return n_blocks / (time.perf_counter() - t0)
 
-    variants = [a.only] if a.only else list(VARIANTS)
+    all_variants = VARIANTS if a.field == "color" else FIELD_VARIANTS
+    if a.only and a.only not in all_variants:
+        ap.error("--only %s does not exist under --field %s" % (a.only, a.field))
+    variants = [a.only] if a.only else list(all_variants)
     for v in variants:                          # warm-up: workspaces, packed weights, replicas' first launches
         call(v)
     rate = {v: [] for v in variants}
@@ -116,10 +137,12 @@ def main():
             rate[v].append(call(v))
     med = {v: statistics.median(r) for v, r in rate.items()}
     out = dict(tool="scene_time", device=torch.cuda.get_device_name(0), n_points=a.points, size=list(a.size), block_points=a.block_points,
-               n_blocks=n_blocks, batch_size=a.batch_size, eps=eps, alpha=alpha, iters=a.iters, runs=a.runs,
+               n_blocks=n_blocks, batch_size=a.batch_size, eps=eps, alpha=alpha, iters=a.iters, runs=a.runs, field=a.field,
                occurrences=dict(mean=float(counts.mean()), max=int(counts.max()), multi_share=float((counts > 1).mean())),
                blocks_per_s={v: dict(median=med[v], min=min(r), max=max(r), spread=(max(r) - min(r)) / med[v]) for v, r in rate.items()})
-    if not a.only:
+    if not a.only and a.field != "color":
+        out["consistent_field_over"] = {v: med["consistent_field"] / med[v] for v in variants if v != "consistent_field"}
+    elif not a.only:
         out["consistent_over_per_block"] = dict(streams1=med["consistent"] / med["per_block_streams1"],
                                                 default=med["consistent"] / med["per_block_default"])
     if a.kernel_trace:
