@@ -1308,6 +1308,40 @@ int psg_scene_field_step(float *delta, const uint8_t *scene_mask, const int32_t 
                          const float *dx0, int rows, int n_scene, float alpha, float eps, float dir, int last,
                          float *gsum_out, psg_stream stream);
 
+/* Whole-scene NU attack: Adam in tanh space on ONE colour per scene point.  w / m / v / c / c0 are
+ * [n_scene][3] fp32; slots, lists (psg_scene_occ_build) and the rows guard as above; no float atomics, one writer per
+ * output element.  `active` is one int32 word on the device (1 while the attack runs): while it is 0 psg_scene_nu_colour,
+ * psg_scene_nu_step and psg_scene_nu_latch leave every byte alone.  A point MOVES when it is under scene_mask (nullable =
+ * all points) and has at least one slot; every other point keeps the bytes of its w / m / v / c.
+ *
+ * psg_scene_nu_init: w = 0.5 * log((1 + x) / (1 - x)), x = 2 c0 - 1, for every point (psg_nu_inverse_tanh's formula).
+ * psg_scene_nu_colour: c = 0.5 * (tanh(w) + 1) on the moving points (psg_nu_tanh_color's formula).
+ * psg_scene_nu_step: for every moving point and channel, in psg_nu_adam_step's expression order, fp32, no contraction:
+ *   Gf = ((0 + dx0[e_0][3:6]) + dx0[e_1][3:6]) + ...    over the slots of the point in list order (dx0 [rows][9])
+ *   Gs = the same ordered sum over sgrad [rows][3]       (the per-slot Smooth gradients)
+ *   g  = Gf + (cw * 2) * (c - c0);  g = g + cw * Gs;  th = tanh(w);  g = (g * 0.5) * (1 - th * th)
+ *   then torch.optim.Adam's single-tensor update on w / m / v (step >= 1; lr / (1 - beta1^step) and sqrt(1 - beta2^step)
+ *   computed in double on the host, as psg_nu_adam_step does).  The L2 term counts once per POINT, not once per slot.
+ *   gsum_f_out / gsum_s_out (nullable) [n_scene][3]: Gf and Gs (+0 for points that do not move).
+ * psg_scene_nu_latch: the exit test in integers over all slots.  Non-targeted (scene_mask == NULL): n_hits = slots with
+ *   pred == labels, n_counted = rows; fires when n_hits * den < num * n_counted.  Targeted (scene_mask given; labels may be
+ *   NULL): n_counted = slots whose point is under the mask (an index out of range counts as unmasked), n_hits = those with
+ *   pred == target; fires when n_hits * den > num * n_counted.  64-bit products, no float arithmetic.  Two launches: the
+ *   counts (integer atomics into counters [2], int32, which must be zero on entry and are left zero), then ONE workgroup
+ *   whose first thread decides.  While active: hist_row [2] (int64) <- n_hits, n_counted; a firing step copies c into snap
+ *   [n_scene][3], stores `step` in exit_step [1] and clears active.  num >= 0, den > 0. */
+int psg_scene_nu_init(const float *c0, int n_scene, float *w_out, psg_stream stream);
+int psg_scene_nu_colour(const float *w, const uint8_t *scene_mask, const int32_t *occ_off, int n_scene,
+                        const int32_t *active, float *c, psg_stream stream);
+int psg_scene_nu_step(float *w, float *m, float *v, const float *c, const float *c0, const uint8_t *scene_mask,
+                      const int32_t *occ_off, const int32_t *occ_ent, const float *dx0, const float *sgrad, int rows,
+                      int n_scene, float cw, float lr, float beta1, float beta2, float eps, int step,
+                      const int32_t *active, float *gsum_f_out, float *gsum_s_out, psg_stream stream);
+int psg_scene_nu_latch(const int32_t *pred, const int32_t *labels, int target, const int32_t *point_idx,
+                       const uint8_t *scene_mask, int rows, int n_scene, int num, int den, int step, const float *c,
+                       float *snap, int32_t *counters, long long *hist_row, int32_t *exit_step, int32_t *active,
+                       psg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

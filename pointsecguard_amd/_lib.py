@@ -190,6 +190,10 @@ SIGNATURES = {
     "psg_scene_pgd_step": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, ci, vp, vp]),
     "psg_scene_delta_to_blocks": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "psg_scene_field_step": (ci, [vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, ci, vp, vp]),
+    "psg_scene_nu_init": (ci, [vp, ci, vp, vp]),
+    "psg_scene_nu_colour": (ci, [vp, vp, vp, ci, vp, vp, vp]),
+    "psg_scene_nu_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, cf, cf, ci, vp, vp, vp, vp]),
+    "psg_scene_nu_latch": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 

@@ -6,7 +6,12 @@ with a different colour in every block that holds it.  Here the variable is the 
 iteration writes c into all block slots, runs the network's forward / CE gradient / colour backward batch by batch, sums the
 block gradients over each point's slots in ascending slot order (fp32, no atomics) and takes one sign step on c.  The
 result is a point cloud: one colour per point, bounded by eps once.
+
+SceneNUAttack is the norm-unbounded counterpart: Adam in tanh space on the same one-colour-per-point
+variable, with the f-loss and Smooth gradients of the blocks summed the same way and the L2 term counted once per point.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -228,3 +233,178 @@ class SceneNBAttack:
             runtime.scene_colour_to_blocks(c, idx, x, bad)
         self.last_delta = delta
         return c, x
+
+
+BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-8          # torch.optim.Adam's defaults, as nu.py passes them
+
+
+def _ratio(name, r):
+    num, den = int(r[0]), int(r[1])
+    if den < 1 or num < 0:
+        raise ValueError("%s = (num, den) needs num >= 0 and den > 0, got %r" % (name, (r,)))
+    return num, den
+
+
+class SceneNUAttack:
+    """The norm-unbounded attack (Adam in tanh space, the reference's NU column) on the colours of a whole scene: ONE
+    colour per physical scene point.  Same models, same call and same batch_size / target / origin
+    attributes as SceneNBAttack, so it drops into harness.evaluate_whole_scene_consistent.
+
+    The variable is w [n_scene][3] = inverse_tanh_space(c0), c0 = float32(rgb / 255.0); the colours are c = 1/2 (tanh w + 1).
+    Minimised:  cost = sum_blocks f_b + c * sum_blocks Smooth_b + c * sum_points |c_p - c0_p|^2
+    f_b: the reference's f-loss over the block's slots (psg_nu_f_loss_grad_rooms, kappa) - non-targeted y = block labels,
+    tsign = +1; targeted (target and origin both given) y = target, tsign = -1 and the dlogp rows of slots whose point is
+    not of class `origin` zeroed (psg_scene_rows_mask).  This is the plain targeted f-loss, deliberately NOT tar_NU_attack's
+    quirks (`_targeted` left at +1, mask and Smooth of batch row 0).  Smooth_b: per block, the `neighbour` (default 10,
+    targeted 5) smallest distances from every adversarial colour of the block to the clean colours of the same block
+    (psg_smooth_knn_rooms, N <= 8192).  The L2 term counts once per scene point.  Points that move: non-targeted every point
+    with a slot, targeted those of class `origin` with a slot (none: ValueError); the others keep the bytes of c0.
+
+    Step s (outer), batch k (inner, slicer order): psg_scene_nu_colour, psg_scene_colour_to_blocks; per batch the FPS
+    starts (draw_fps_starts(B_k, bp, 1), CPU generator), psg_pn2_plan_build, psg_pn2_forward_lean,
+    psg_nu_f_loss_grad_rooms, (targeted) psg_scene_rows_mask, psg_pn2_backward_colour, psg_smooth_knn_rooms; then
+    psg_scene_nu_latch and - not after the last step - psg_scene_nu_step (Adam step s + 1, betas 0.9 / 0.999, eps 1e-8).
+    No restart rule, no learning-rate halving, no graph capture.
+
+    Exit, in integers: non-targeted n_hits = slots with pred == label, fires at the first step with n_hits * den < num *
+    rows, (num, den) = exit_below; targeted n_hits = masked slots with pred == target, fires with n_hits * den > num *
+    masked slots, (num, den) = exit_above.  exit_below = (0, 1) never fires.  The firing step snapshots the colours its
+    forward saw and clears the device's `active` word; later launches leave every byte alone.  The host reads that word every
+    `check_every` steps (every step under `trace`) and nothing else inside the loop; results do not depend on check_every.
+
+    Returns (adv_rgb01 [n_scene, 3], adv_blocks [nb, bp, 9]): the colours of the exit step's forward, or of step
+    steps - 1's, in every slot; channels 0:3 and 6:9 and the caller's blocks stay clean.  Afterwards last_exit_step (-1 at
+    the cap), last_history (int64 numpy [steps_run][2]: n_hits, n_counted) and last_w (device tensor).
+    trace(dict), after every step: s, starts, dx0 [nb, bp, 9], sgrad [nb, bp, 3], pred [nb, bp], w_before, w_after, m_after,
+    v_after, c (the colours of the step's forward), gsum_f, gsum_s (None where no Adam step ran: after the last step or the
+    exit), active (0 / 1 after the step's latch) - device tensors; dx0 / sgrad / pred are the attack's own buffers."""
+
+    def __init__(self, model, c=1e-4, kappa=0, steps=1000, lr=0.01, batch_size=8, neighbour=None, target=None, origin=None,
+                 exit_below=(1, 13), exit_above=(9, 10), check_every=10, trace=None):
+        self.model = check_scene_model(model)
+        if (target is None) != (origin is None):
+            raise ValueError("the targeted scene attack needs both `target` and `origin`")
+        if target is not None and not 0 <= int(target) < NUM_CLASSES:
+            raise ValueError("target class %r out of range" % (target,))
+        if int(steps) < 1 or int(batch_size) < 1 or int(check_every) < 1:
+            raise ValueError("steps, batch_size and check_every must be positive")
+        self.exit_below, self.exit_above = _ratio("exit_below", exit_below), _ratio("exit_above", exit_above)
+        if neighbour is None:
+            neighbour = 5 if target is not None else 10          # the reference's: nontarget.py / target.py
+        if not 1 <= int(neighbour) <= 16:
+            raise ValueError("neighbour = %r outside 1 .. 16 (psg_smooth_knn_rooms)" % (neighbour,))
+        self.c, self.kappa, self.steps, self.lr = float(c), float(kappa), int(steps), float(lr)
+        self.batch_size, self.neighbour, self.check_every = int(batch_size), int(neighbour), int(check_every)
+        self.target, self.origin, self.trace = target, origin, trace
+        self.last_exit_step, self.last_history, self.last_w = None, None, None
+
+    def __call__(self, blocks, point_idx, block_labels, scene_rgb, scene_labels):
+        net = self.model
+        params = next(net.parameters())
+        if not params.is_cuda:
+            raise _lib.PsgError("the model must be on the MI355X device (got %s); there is no CPU path" % params.device)
+        dev = params.device
+        x_clean = _device_array(blocks, torch.float32, np.float32, "blocks", dev)
+        idx = _device_array(point_idx, torch.int32, np.int32, "point_idx", dev)
+        gt = _device_array(block_labels, torch.int32, np.int32, "block_labels", dev)
+        if x_clean.dim() != 3 or x_clean.shape[2] != 9 or idx.shape != x_clean.shape[:2] or gt.shape != x_clean.shape[:2]:
+            raise ValueError("expected blocks [nb, bp, 9] with point_idx / block_labels [nb, bp], got %s, %s, %s" % (
+                tuple(x_clean.shape), tuple(idx.shape), tuple(gt.shape)))
+        if not isinstance(scene_rgb, np.ndarray) or scene_rgb.ndim != 2 or scene_rgb.shape[1] != 3:
+            raise ValueError("scene_rgb must be a numpy array [n_scene, 3] of colours 0..255")
+        nb, bp = x_clean.shape[0], x_clean.shape[1]
+        n_scene = scene_rgb.shape[0]
+        c0 = upload(torch.from_numpy(np.ascontiguousarray((scene_rgb / 255.0).astype(np.float32))), dev, pin=True)
+        targeted = self.target is not None
+        mask = None
+        if targeted:
+            if isinstance(scene_labels, torch.Tensor):
+                mask = (runtime.require_cuda(scene_labels, "scene_labels") == int(self.origin)).to(torch.uint8).contiguous()
+            else:
+                mask = upload(torch.from_numpy((np.asarray(scene_labels) == self.origin).astype(np.uint8)), dev, pin=True)
+            if mask.numel() != n_scene:
+                raise ValueError("scene_labels must hold %d labels" % n_scene)
+
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        occ_off, occ_ent = runtime.scene_occ_build(idx, n_scene, bad)
+        if int(bad.item()):        # (read-backs before the loop, once per scene)
+            raise IndexError("SceneNUAttack: a point index is outside [0, %d)" % n_scene)
+        if targeted and not bool(mask[idx.reshape(-1).long()].any().item()):
+            raise ValueError("SceneNUAttack: no slot of this scene holds a point of the origin class %r" % (self.origin,))
+
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)        # noqa: E731
+        x = x_clean.clone()        # the caller's blocks stay clean, and are the Smooth term's reference colours
+        c = c0.clone()
+        w = runtime.scene_nu_init(c0)
+        m, v, snap = f32(n_scene, 3), f32(n_scene, 3), f32(n_scene, 3)
+        active = torch.ones(1, dtype=torch.int32, device=dev)
+        exit_step = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        counters = i32(2)
+        hist = torch.zeros(self.steps, 2, dtype=torch.int64, device=dev)
+        dx0_all = f32(nb, bp, 9)   # backward_colour writes channels 3:6 only
+        sgrad_all = f32(nb, bp, 3)
+        pred_all = i32(nb, bp)
+        nn_state = i32(nb, bp, self.neighbour)
+        model = net._packed()
+        batches = [(lo, min(lo + self.batch_size, nb)) for lo in range(0, nb, self.batch_size)]
+        sizes = sorted({hi - lo for lo, hi in batches})
+        ws = {b: net._workspace(b, bp, 1) for b in sizes}
+        net._generation += 1       # the workspace activations no longer belong to an earlier autograd forward
+        logp = {b: f32(b, bp, NUM_CLASSES) for b in sizes}
+        dlogp = {b: f32(b, bp, NUM_CLASSES) for b in sizes}
+        f_sum = {b: f32(b) for b in sizes}             # psg_nu_f_loss_grad_rooms adds the rooms' f sums here: not read
+        trace = self.trace
+        gsum_f = gsum_s = None
+        if trace is not None:
+            gsum_f, gsum_s = f32(n_scene, 3), f32(n_scene, 3)
+        tsign = -1.0 if targeted else 1.0
+        num, den = self.exit_above if targeted else self.exit_below
+        off3 = lambda t: ctypes.c_void_p(t.data_ptr() + 3 * 4)                          # noqa: E731  (channel 3 of row 0)
+        st = runtime.stream
+        for s in range(self.steps):
+            runtime.scene_nu_colour(w, mask, occ_off, active, c)
+            runtime.scene_colour_to_blocks(c, idx, x, bad)
+            starts_s = []
+            for lo, hi in batches:
+                b = hi - lo
+                xb, wsb = x[lo:hi], ws[b]
+                starts = upload(draw_fps_starts(b, bp, 1, pinned=True), dev, pin=True)
+                _lib.call("psg_pn2_plan_build", wsb.handle, runtime.ptr(xb), runtime.ptr(starts), 1, st())
+                _lib.call("psg_pn2_forward_lean", model.handle, wsb.handle, 0, runtime.ptr(xb), runtime.ptr(logp[b]), st())
+                _lib.call("psg_nu_f_loss_grad_rooms", runtime.ptr(logp[b]), None if targeted else runtime.ptr(gt[lo:hi]),
+                          int(self.target) if targeted else 0, b, bp, NUM_CLASSES, self.kappa, tsign, runtime.ptr(dlogp[b]),
+                          runtime.ptr(f_sum[b]), runtime.ptr(pred_all[lo:hi]), st())
+                if targeted:
+                    runtime.scene_rows_mask(dlogp[b], idx[lo:hi], mask)
+                _lib.call("psg_pn2_backward_colour", model.handle, wsb.handle, 0, runtime.ptr(dlogp[b]),
+                          runtime.ptr(dx0_all[lo:hi]), st())
+                _lib.call("psg_smooth_knn_rooms", off3(xb), 9, bp * 9, off3(x_clean[lo:hi]), 9, bp * 9, b, bp, self.neighbour,
+                          None, runtime.ptr(sgrad_all[lo:hi]), runtime.ptr(nn_state[lo:hi]), 1 if s > 0 else 0, st())
+                if trace is not None:
+                    starts_s.append(starts)
+            runtime.scene_nu_latch(pred_all, None if targeted else gt, int(self.target) if targeted else 0, idx, mask, num, den, s,
+                                   c, snap, counters, hist[s], exit_step, active)
+            stepping = s < self.steps - 1
+            if trace is not None:
+                w_before = w.clone()
+                running = bool(active.item())
+            if stepping:
+                runtime.scene_nu_step(w, m, v, c, c0, mask, occ_off, occ_ent, dx0_all, sgrad_all, self.c, self.lr, BETA1, BETA2,
+                                      ADAM_EPS, s + 1, active, gsum_f, gsum_s)
+            if trace is not None:
+                stepped = stepping and running
+                trace(dict(s=s, starts=starts_s, dx0=dx0_all, sgrad=sgrad_all, pred=pred_all, w_before=w_before, w_after=w.clone(),
+                           m_after=m.clone(), v_after=v.clone(), c=c.clone(), gsum_f=gsum_f.clone() if stepped else None,
+                           gsum_s=gsum_s.clone() if stepped else None, active=int(running)))
+                if not running:
+                    break
+            elif (s + 1) % self.check_every == 0 and not int(active.item()):
+                break
+        exited = int(exit_step.item())
+        self.last_exit_step = exited
+        self.last_history = hist[:exited + 1 if exited >= 0 else self.steps].cpu().numpy()
+        self.last_w = w
+        adv = snap if exited >= 0 else c
+        runtime.scene_colour_to_blocks(adv, idx, x, bad)
+        return adv, x

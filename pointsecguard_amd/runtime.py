@@ -569,6 +569,87 @@ def scene_field_step(delta, scene_mask, occ_off, occ_ent, dx0, alpha, eps, direc
     return delta
 
 
+# ---- whole-scene NU attack (psg_scene_nu.hip) ---------------------------------
+def _scene_nu_common(scene_mask, active, n_scene):
+    require_cuda(active, "active", torch.int32)
+    assert active.numel() == 1
+    if scene_mask is not None:
+        require_cuda(scene_mask, "scene_mask", torch.uint8)
+        assert scene_mask.numel() == n_scene
+
+
+def scene_nu_init(c0, w_out=None):
+    """w [n_scene, 3] = inverse_tanh_space(c0 [n_scene, 3]) (psg_scene_nu_init)."""
+    require_cuda(c0, "c0", torch.float32)
+    assert c0.dim() == 2 and c0.shape[1] == 3
+    if w_out is None:
+        w_out = torch.empty_like(c0)
+    require_cuda(w_out, "w_out", torch.float32)
+    assert w_out.shape == c0.shape
+    _lib.call("psg_scene_nu_init", ptr(c0), c0.shape[0], ptr(w_out), stream())
+    return w_out
+
+
+def scene_nu_colour(w, scene_mask, occ_off, active, c):
+    """c [n_scene, 3] <- 0.5 (tanh(w) + 1) on the moving points while active [1] (int32) is set, in place
+    (psg_scene_nu_colour)."""
+    require_cuda(w, "w", torch.float32)
+    require_cuda(occ_off, "occ_off", torch.int32)
+    require_cuda(c, "c", torch.float32)
+    n_scene = w.shape[0]
+    _scene_nu_common(scene_mask, active, n_scene)
+    assert w.shape == c.shape == (n_scene, 3) and occ_off.numel() == n_scene + 1
+    _lib.call("psg_scene_nu_colour", ptr(w), ptr(scene_mask), ptr(occ_off), n_scene, ptr(active), ptr(c), stream())
+    return c
+
+
+def scene_nu_step(w, m, v, c, c0, scene_mask, occ_off, occ_ent, dx0, sgrad, cw, lr, beta1, beta2, eps, step, active,
+                  gsum_f_out=None, gsum_s_out=None):
+    """One Adam step (step >= 1) on w / m / v [n_scene, 3] in place from the block gradients dx0 [rows, 9] (channels 3:6)
+    and the per-slot Smooth gradients sgrad [rows, 3], both summed over every point's slots in ascending slot order; the L2
+    term once per point (psg_scene_nu_step)."""
+    n_scene, rows = w.shape[0], occ_ent.numel()
+    for t, name in ((w, "w"), (m, "m"), (v, "v"), (c, "c"), (c0, "c0"), (dx0, "dx0"), (sgrad, "sgrad")):
+        require_cuda(t, name, torch.float32)
+    require_cuda(occ_off, "occ_off", torch.int32)
+    require_cuda(occ_ent, "occ_ent", torch.int32)
+    _scene_nu_common(scene_mask, active, n_scene)
+    for t, name in ((gsum_f_out, "gsum_f_out"), (gsum_s_out, "gsum_s_out")):
+        if t is not None:
+            require_cuda(t, name, torch.float32)
+            assert t.shape == w.shape
+    assert w.shape == m.shape == v.shape == c.shape == c0.shape == (n_scene, 3) and occ_off.numel() == n_scene + 1
+    assert dx0.numel() == rows * 9 and sgrad.numel() == rows * 3
+    _lib.call("psg_scene_nu_step", ptr(w), ptr(m), ptr(v), ptr(c), ptr(c0), ptr(scene_mask), ptr(occ_off), ptr(occ_ent), ptr(dx0),
+              ptr(sgrad), rows, n_scene, float(cw), float(lr), float(beta1), float(beta2), float(eps), int(step), ptr(active),
+              ptr(gsum_f_out), ptr(gsum_s_out), stream())
+    return w
+
+
+def scene_nu_latch(pred, labels, target, point_idx, scene_mask, num, den, step, c, snap, counters, hist_row, exit_step, active):
+    """The integer exit test of the whole-scene NU attack over all slots (psg_scene_nu_latch): pred / labels / point_idx int32
+    [rows]; scene_mask None = non-targeted (hits: pred == labels, fires when hits * den < num * rows), uint8 [n_scene] =
+    targeted (hits: masked slots with pred == target, fires when hits * den > num * masked slots).  counters int32 [2] (zero
+    on entry, left zero), hist_row int64 [2], exit_step int32 [1], snap [n_scene, 3] <- c at the firing step."""
+    require_cuda(pred, "pred", torch.int32)
+    rows, n_scene = pred.numel(), c.shape[0]
+    if labels is not None:
+        require_cuda(labels, "labels", torch.int32)
+        assert labels.numel() == rows
+    if point_idx is not None:
+        require_cuda(point_idx, "point_idx", torch.int32)
+        assert point_idx.numel() == rows
+    require_cuda(c, "c", torch.float32)
+    require_cuda(snap, "snap", torch.float32)
+    require_cuda(counters, "counters", torch.int32)
+    require_cuda(hist_row, "hist_row", torch.int64)
+    require_cuda(exit_step, "exit_step", torch.int32)
+    _scene_nu_common(scene_mask, active, n_scene)
+    assert c.shape == snap.shape == (n_scene, 3) and counters.numel() == 2 and hist_row.numel() == 2 and exit_step.numel() == 1
+    _lib.call("psg_scene_nu_latch", ptr(pred), ptr(labels), int(target), ptr(point_idx), ptr(scene_mask), rows, n_scene, int(num),
+              int(den), int(step), ptr(c), ptr(snap), ptr(counters), ptr(hist_row), ptr(exit_step), ptr(active), stream())
+
+
 # ---- ResGCN (dense DeepGCN) ------------------------------------------------------------------------
 def gcn_tensor_list(sd, n_blocks):
     """state_dict (reference key names, ResGCN/sem_seg_dense/architecture.py) -> the flat fp32 tensor list of
