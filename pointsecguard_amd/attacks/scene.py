@@ -10,6 +10,7 @@ result is a point cloud: one colour per point, bounded by eps once.
 SceneNUAttack is the norm-unbounded counterpart: Adam in tanh space on the same one-colour-per-point
 variable, with the f-loss and Smooth gradients of the blocks summed the same way and the L2 term counted once per point.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -36,6 +37,79 @@ def _device_array(a, dtype, np_dtype, name, device):
     if isinstance(a, np.ndarray):
         return upload(torch.from_numpy(np.ascontiguousarray(a.astype(np_dtype))), device, pin=True)
     return runtime.require_cuda(a, name, dtype)
+
+
+def _check_target(target, origin):
+    if (target is None) != (origin is None):
+        raise ValueError("the targeted scene attack needs both `target` and `origin`")
+    if target is not None and not 0 <= int(target) < NUM_CLASSES:
+        raise ValueError("target class %r out of range" % (target,))
+
+
+_Scene = collections.namedtuple("_Scene", "dev x_clean idx gt c0 mask occ_off occ_ent bad nb bp n_scene")
+
+
+def _open_scene(who, net, blocks, point_idx, block_labels, scene_rgb, scene_labels, origin):
+    """One scene as both attacks take it (the class docstrings), checked and on the device: the clean blocks, c0 =
+    float32(rgb / 255.0), mask = (scene_labels == origin) as uint8 (None without an origin) and the occurrence lists of every
+    scene point.  `who` names the calling class in the index error."""
+    params = next(net.parameters())
+    if not params.is_cuda:
+        raise _lib.PsgError("the model must be on the MI355X device (got %s); there is no CPU path" % params.device)
+    dev = params.device
+    x = _device_array(blocks, torch.float32, np.float32, "blocks", dev)
+    idx = _device_array(point_idx, torch.int32, np.int32, "point_idx", dev)
+    gt = _device_array(block_labels, torch.int32, np.int32, "block_labels", dev)
+    if x.dim() != 3 or x.shape[2] != 9 or idx.shape != x.shape[:2] or gt.shape != x.shape[:2]:
+        raise ValueError("expected blocks [nb, bp, 9] with point_idx / block_labels [nb, bp], got %s, %s, %s" % (
+            tuple(x.shape), tuple(idx.shape), tuple(gt.shape)))
+    if not isinstance(scene_rgb, np.ndarray) or scene_rgb.ndim != 2 or scene_rgb.shape[1] != 3:
+        raise ValueError("scene_rgb must be a numpy array [n_scene, 3] of colours 0..255")
+    n_scene = scene_rgb.shape[0]
+    c0 = upload(torch.from_numpy(np.ascontiguousarray((scene_rgb / 255.0).astype(np.float32))), dev, pin=True)
+    mask = None
+    if origin is not None:
+        if isinstance(scene_labels, torch.Tensor):
+            mask = (runtime.require_cuda(scene_labels, "scene_labels") == int(origin)).to(torch.uint8).contiguous()
+        else:
+            mask = upload(torch.from_numpy((np.asarray(scene_labels) == origin).astype(np.uint8)), dev, pin=True)
+        if mask.numel() != n_scene:
+            raise ValueError("scene_labels must hold %d labels" % n_scene)
+
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    occ_off, occ_ent = runtime.scene_occ_build(idx, n_scene, bad)
+    if int(bad.item()):        # (the one read-back of the prologue, before the loop: once per scene)
+        raise IndexError("%s: a point index is outside [0, %d)" % (who, n_scene))
+    return _Scene(dev, x, idx, gt, c0, mask, occ_off, occ_ent, bad, x.shape[0], x.shape[1], n_scene)
+
+
+class _Batches:
+    """The scene's blocks in batches of `batch_size` consecutive blocks, slicer order (the last one may be smaller): `spans`
+    [(lo, hi)], one workspace and one logp buffer per batch size, and the front and the back of a batch's pass."""
+
+    def __init__(self, net, scene, batch_size):
+        self.dev, self.bp = scene.dev, scene.bp
+        self.model = net._packed()
+        self.spans = [(lo, min(lo + batch_size, scene.nb)) for lo in range(0, scene.nb, batch_size)]
+        self.sizes = sorted({hi - lo for lo, hi in self.spans})
+        self.ws = {b: net._workspace(b, scene.bp, 1) for b in self.sizes}
+        net._generation += 1       # the workspace activations no longer belong to an earlier autograd forward
+        self.logp = self.per_size(torch.empty, scene.bp, NUM_CLASSES)
+
+    def per_size(self, make, *tail):
+        """{B: float32 device tensor [B, *tail]} for every batch size; make = torch.empty | torch.zeros."""
+        return {b: make(b, *tail, dtype=torch.float32, device=self.dev) for b in self.sizes}
+
+    def forward(self, xb):
+        """FPS starts from the CPU generator (one draw per batch), plan, lean forward -> (starts, logp [B, bp, 13])."""
+        b = xb.shape[0]
+        starts = upload(draw_fps_starts(b, self.bp, 1, pinned=True), self.dev, pin=True)
+        self.ws[b].plan_build(xb, starts, 1)
+        return starts, self.ws[b].forward(self.model, 0, xb, self.logp[b], lean=True)
+
+    def backward(self, dlogp, dx0, full=False):
+        """dx0 [B, bp, 9] <- channels 3:6 (psg_pn2_backward_colour), or all nine under full (psg_pn2_backward_full)."""
+        self.ws[dlogp.shape[0]].backward(self.model, 0, dlogp, dx0, colour_only=not full, full=full)
 
 
 class SceneNBAttack:
@@ -89,10 +163,7 @@ class SceneNBAttack:
         if self.field != "color" and not isinstance(model, pointnet2_sem_seg.get_model):
             raise NotImplementedError("field=%r is implemented for the PointNet++ SSG network (pointnet2_sem_seg): the exact "
                                       "coordinate gradient psg_pn2_backward_full refuses MSG" % self.field)
-        if (target is None) != (origin is None):
-            raise ValueError("the targeted scene attack needs both `target` and `origin`")
-        if target is not None and not 0 <= int(target) < NUM_CLASSES:
-            raise ValueError("target class %r out of range" % (target,))
+        _check_target(target, origin)
         if int(iters) < 1 or int(batch_size) < 1:
             raise ValueError("iters and batch_size must be positive")
         self.eps, self.alpha, self.iters, self.batch_size = float(eps), float(alpha), int(iters), int(batch_size)
@@ -104,132 +175,56 @@ class SceneNBAttack:
 
     def __call__(self, blocks, point_idx, block_labels, scene_rgb, scene_labels):
         net = self.model
-        params = next(net.parameters())
-        if not params.is_cuda:
-            raise _lib.PsgError("the model must be on the MI355X device (got %s); there is no CPU path" % params.device)
-        dev = params.device
-        x = _device_array(blocks, torch.float32, np.float32, "blocks", dev)
-        idx = _device_array(point_idx, torch.int32, np.int32, "point_idx", dev)
-        gt = _device_array(block_labels, torch.int32, np.int32, "block_labels", dev)
-        if x.dim() != 3 or x.shape[2] != 9 or idx.shape != x.shape[:2] or gt.shape != x.shape[:2]:
-            raise ValueError("expected blocks [nb, bp, 9] with point_idx / block_labels [nb, bp], got %s, %s, %s" % (
-                tuple(x.shape), tuple(idx.shape), tuple(gt.shape)))
-        if not isinstance(scene_rgb, np.ndarray) or scene_rgb.ndim != 2 or scene_rgb.shape[1] != 3:
-            raise ValueError("scene_rgb must be a numpy array [n_scene, 3] of colours 0..255")
-        nb, bp = x.shape[0], x.shape[1]
-        n_scene = scene_rgb.shape[0]
-        c0 = upload(torch.from_numpy(np.ascontiguousarray((scene_rgb / 255.0).astype(np.float32))), dev, pin=True)
+        sc = _open_scene("SceneNBAttack", net, blocks, point_idx, block_labels, scene_rgb, scene_labels, self.origin)
+        dev, x_clean, idx, gt, c0, mask, occ_off, occ_ent, bad, nb, bp, n_scene = sc
+        colour, coord = self.field != "coord", self.field != "color"
         targeted = self.target is not None
-        mask = None
-        if targeted:
-            if isinstance(scene_labels, torch.Tensor):
-                mask = (runtime.require_cuda(scene_labels, "scene_labels") == int(self.origin)).to(torch.uint8).contiguous()
-            else:
-                mask = upload(torch.from_numpy((np.asarray(scene_labels) == self.origin).astype(np.uint8)), dev, pin=True)
-            if mask.numel() != n_scene:
-                raise ValueError("scene_labels must hold %d labels" % n_scene)
-
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        occ_off, occ_ent = runtime.scene_occ_build(idx, n_scene, bad)
-        if int(bad.item()):        # (the one read-back, before the loop: once per scene)
-            raise IndexError("SceneNBAttack: a point index is outside [0, %d)" % n_scene)
-
-        if self.field != "color":
-            return self._run_field(net, dev, x, idx, gt, c0, mask, occ_off, occ_ent, bad)
-        self.last_delta = None
-        x = x.clone()              # the caller's blocks stay clean
-        c = c0.clone()
-        dx0_all = torch.zeros(nb, bp, 9, dtype=torch.float32, device=dev)     # backward_colour writes channels 3:6 only
-        model = net._packed()
-        batches = [(lo, min(lo + self.batch_size, nb)) for lo in range(0, nb, self.batch_size)]
-        sizes = sorted({hi - lo for lo, hi in batches})
-        ws = {b: net._workspace(b, bp, 1) for b in sizes}
-        net._generation += 1       # the workspace activations no longer belong to an earlier autograd forward
-        logp = {b: torch.empty(b, bp, NUM_CLASSES, dtype=torch.float32, device=dev) for b in sizes}
-        trace = self.trace
+        x = x_clean.clone()     # the caller's blocks stay clean: every iteration adds delta onto THEM
+        c = c0.clone() if colour else c0
+        delta = torch.zeros(n_scene, 3, dtype=torch.float32, device=dev) if coord else None
+        # backward_full writes all nine channels, backward_colour channels 3:6 only
+        dx0_all = (torch.empty if coord else torch.zeros)(nb, bp, 9, dtype=torch.float32, device=dev)
+        bt = _Batches(net, sc, self.batch_size)
+        trace = self.trace_field if coord else self.trace
         if trace is not None:      # the tests read every batch's dlogp: kept scene-wide only then
             dlogp_all = torch.zeros(nb, bp, NUM_CLASSES, dtype=torch.float32, device=dev)
         else:
-            dlogp = {b: torch.empty(b, bp, NUM_CLASSES, dtype=torch.float32, device=dev) for b in sizes}
+            dlogp = bt.per_size(torch.empty, bp, NUM_CLASSES)
         direction = -1.0 if targeted else 1.0
-        st = runtime.stream
         for t in range(self.iters):
             starts_t = []
-            for lo, hi in batches:
+            for lo, hi in bt.spans:
                 b = hi - lo
-                xb, ib, w = x[lo:hi], idx[lo:hi], ws[b]
-                runtime.scene_colour_to_blocks(c, ib, xb, bad)
-                starts = upload(draw_fps_starts(b, bp, 1, pinned=True), dev, pin=True)
-                dl = dlogp_all[lo:hi] if trace is not None else dlogp[b]
-                _lib.call("psg_pn2_plan_build", w.handle, runtime.ptr(xb), runtime.ptr(starts), 1, st())
-                _lib.call("psg_pn2_forward_lean", model.handle, w.handle, 0, runtime.ptr(xb), runtime.ptr(logp[b]), st())
-                _lib.call("psg_ce_logp_grad", runtime.ptr(logp[b]), None if targeted else runtime.ptr(gt[lo:hi]),
-                          int(self.target) if targeted else 0, b * bp, b * bp, NUM_CLASSES, 1.0 / bp, runtime.ptr(dl), None, st())
-                if targeted:
-                    runtime.scene_rows_mask(dl, ib, mask)
-                _lib.call("psg_pn2_backward_colour", model.handle, w.handle, 0, runtime.ptr(dl), runtime.ptr(dx0_all[lo:hi]), st())
-                if trace is not None:
-                    starts_t.append(starts)
-            last = t == self.iters - 1 and not self.project_last
-            c_before = c.clone() if trace is not None else None
-            runtime.scene_pgd_step(c, c0, mask, occ_off, occ_ent, dx0_all, self.alpha, self.eps, direction, last)
-            if trace is not None:
-                trace(t, starts_t, dx0_all, c_before, c.clone(), dlogp_all)
-        runtime.scene_colour_to_blocks(c, idx, x, bad)
-        return c, x
-
-    def _run_field(self, net, dev, x_clean, idx, gt, c0, mask, occ_off, occ_ent, bad):
-        """field = "coord" | "both": the loop of the class docstring on delta [n_scene][3] (and on c under "both")."""
-        nb, bp = x_clean.shape[0], x_clean.shape[1]
-        both = self.field == "both"
-        targeted = self.target is not None
-        x = x_clean.clone()        # the caller's blocks stay clean: every iteration adds delta onto THEM
-        delta = torch.zeros(c0.shape[0], 3, dtype=torch.float32, device=dev)
-        c = c0.clone() if both else c0
-        dx0_all = torch.empty(nb, bp, 9, dtype=torch.float32, device=dev)     # backward_full writes all nine channels
-        model = net._packed()
-        batches = [(lo, min(lo + self.batch_size, nb)) for lo in range(0, nb, self.batch_size)]
-        sizes = sorted({hi - lo for lo, hi in batches})
-        ws = {b: net._workspace(b, bp, 1) for b in sizes}
-        net._generation += 1       # the workspace activations no longer belong to an earlier autograd forward
-        logp = {b: torch.empty(b, bp, NUM_CLASSES, dtype=torch.float32, device=dev) for b in sizes}
-        trace = self.trace_field
-        if trace is not None:
-            dlogp_all = torch.zeros(nb, bp, NUM_CLASSES, dtype=torch.float32, device=dev)
-        else:
-            dlogp = {b: torch.empty(b, bp, NUM_CLASSES, dtype=torch.float32, device=dev) for b in sizes}
-        direction = -1.0 if targeted else 1.0
-        st = runtime.stream
-        for t in range(self.iters):
-            starts_t = []
-            for lo, hi in batches:
-                b = hi - lo
-                xb, ib, w = x[lo:hi], idx[lo:hi], ws[b]
-                runtime.scene_delta_to_blocks(delta, ib, x_clean[lo:hi], xb, bad)
-                if both:
+                xb, ib = x[lo:hi], idx[lo:hi]
+                if coord:
+                    runtime.scene_delta_to_blocks(delta, ib, x_clean[lo:hi], xb, bad)
+                if colour:
                     runtime.scene_colour_to_blocks(c, ib, xb, bad)
-                starts = upload(draw_fps_starts(b, bp, 1, pinned=True), dev, pin=True)
+                starts, logp = bt.forward(xb)
                 dl = dlogp_all[lo:hi] if trace is not None else dlogp[b]
-                _lib.call("psg_pn2_plan_build", w.handle, runtime.ptr(xb), runtime.ptr(starts), 1, st())
-                _lib.call("psg_pn2_forward_lean", model.handle, w.handle, 0, runtime.ptr(xb), runtime.ptr(logp[b]), st())
-                _lib.call("psg_ce_logp_grad", runtime.ptr(logp[b]), None if targeted else runtime.ptr(gt[lo:hi]),
-                          int(self.target) if targeted else 0, b * bp, b * bp, NUM_CLASSES, 1.0 / bp, runtime.ptr(dl), None, st())
+                _lib.call("psg_ce_logp_grad", runtime.ptr(logp), None if targeted else runtime.ptr(gt[lo:hi]),
+                          int(self.target) if targeted else 0, b * bp, b * bp, NUM_CLASSES, 1.0 / bp, runtime.ptr(dl), None,
+                          runtime.stream())
                 if targeted:
                     runtime.scene_rows_mask(dl, ib, mask)
-                _lib.call("psg_pn2_backward_full", model.handle, w.handle, 0, runtime.ptr(dl), runtime.ptr(dx0_all[lo:hi]), st())
+                bt.backward(dl, dx0_all[lo:hi], full=coord)
                 if trace is not None:
                     starts_t.append(starts)
             last = t == self.iters - 1 and not self.project_last
             if trace is not None:
-                before = dict(delta_before=delta.clone(), c_before=c.clone() if both else None)
-            runtime.scene_field_step(delta, mask, occ_off, occ_ent, dx0_all, self.coord_alpha, self.coord_eps, direction, last)
-            if both:
+                delta_before, c_before = delta.clone() if coord else None, c.clone() if colour else None
+            if coord:
+                runtime.scene_field_step(delta, mask, occ_off, occ_ent, dx0_all, self.coord_alpha, self.coord_eps, direction, last)
+            if colour:
                 runtime.scene_pgd_step(c, c0, mask, occ_off, occ_ent, dx0_all, self.alpha, self.eps, direction, last)
-            if trace is not None:
-                trace(dict(t=t, starts=starts_t, dx0=dx0_all, delta_after=delta.clone(), c_after=c.clone() if both else None,
-                           dlogp=dlogp_all, **before))
-        runtime.scene_delta_to_blocks(delta, idx, x_clean, x, bad)
-        if both:
+            if trace is not None and coord:
+                trace(dict(t=t, starts=starts_t, dx0=dx0_all, delta_before=delta_before, delta_after=delta.clone(),
+                           c_before=c_before, c_after=c.clone() if colour else None, dlogp=dlogp_all))
+            elif trace is not None:
+                trace(t, starts_t, dx0_all, c_before, c.clone(), dlogp_all)
+        if coord:
+            runtime.scene_delta_to_blocks(delta, idx, x_clean, x, bad)
+        if colour:
             runtime.scene_colour_to_blocks(c, idx, x, bad)
         self.last_delta = delta
         return c, x
@@ -282,10 +277,7 @@ class SceneNUAttack:
     def __init__(self, model, c=1e-4, kappa=0, steps=1000, lr=0.01, batch_size=8, neighbour=None, target=None, origin=None,
                  exit_below=(1, 13), exit_above=(9, 10), check_every=10, trace=None):
         self.model = check_scene_model(model)
-        if (target is None) != (origin is None):
-            raise ValueError("the targeted scene attack needs both `target` and `origin`")
-        if target is not None and not 0 <= int(target) < NUM_CLASSES:
-            raise ValueError("target class %r out of range" % (target,))
+        _check_target(target, origin)
         if int(steps) < 1 or int(batch_size) < 1 or int(check_every) < 1:
             raise ValueError("steps, batch_size and check_every must be positive")
         self.exit_below, self.exit_above = _ratio("exit_below", exit_below), _ratio("exit_above", exit_above)
@@ -300,36 +292,10 @@ class SceneNUAttack:
 
     def __call__(self, blocks, point_idx, block_labels, scene_rgb, scene_labels):
         net = self.model
-        params = next(net.parameters())
-        if not params.is_cuda:
-            raise _lib.PsgError("the model must be on the MI355X device (got %s); there is no CPU path" % params.device)
-        dev = params.device
-        x_clean = _device_array(blocks, torch.float32, np.float32, "blocks", dev)
-        idx = _device_array(point_idx, torch.int32, np.int32, "point_idx", dev)
-        gt = _device_array(block_labels, torch.int32, np.int32, "block_labels", dev)
-        if x_clean.dim() != 3 or x_clean.shape[2] != 9 or idx.shape != x_clean.shape[:2] or gt.shape != x_clean.shape[:2]:
-            raise ValueError("expected blocks [nb, bp, 9] with point_idx / block_labels [nb, bp], got %s, %s, %s" % (
-                tuple(x_clean.shape), tuple(idx.shape), tuple(gt.shape)))
-        if not isinstance(scene_rgb, np.ndarray) or scene_rgb.ndim != 2 or scene_rgb.shape[1] != 3:
-            raise ValueError("scene_rgb must be a numpy array [n_scene, 3] of colours 0..255")
-        nb, bp = x_clean.shape[0], x_clean.shape[1]
-        n_scene = scene_rgb.shape[0]
-        c0 = upload(torch.from_numpy(np.ascontiguousarray((scene_rgb / 255.0).astype(np.float32))), dev, pin=True)
+        sc = _open_scene("SceneNUAttack", net, blocks, point_idx, block_labels, scene_rgb, scene_labels, self.origin)
+        dev, x_clean, idx, gt, c0, mask, occ_off, occ_ent, bad, nb, bp, n_scene = sc
         targeted = self.target is not None
-        mask = None
-        if targeted:
-            if isinstance(scene_labels, torch.Tensor):
-                mask = (runtime.require_cuda(scene_labels, "scene_labels") == int(self.origin)).to(torch.uint8).contiguous()
-            else:
-                mask = upload(torch.from_numpy((np.asarray(scene_labels) == self.origin).astype(np.uint8)), dev, pin=True)
-            if mask.numel() != n_scene:
-                raise ValueError("scene_labels must hold %d labels" % n_scene)
-
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        occ_off, occ_ent = runtime.scene_occ_build(idx, n_scene, bad)
-        if int(bad.item()):        # (read-backs before the loop, once per scene)
-            raise IndexError("SceneNUAttack: a point index is outside [0, %d)" % n_scene)
-        if targeted and not bool(mask[idx.reshape(-1).long()].any().item()):
+        if targeted and not bool(mask[idx.reshape(-1).long()].any().item()):       # (a read-back, once per scene)
             raise ValueError("SceneNUAttack: no slot of this scene holds a point of the origin class %r" % (self.origin,))
 
         f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)      # noqa: E731
@@ -346,14 +312,9 @@ class SceneNUAttack:
         sgrad_all = f32(nb, bp, 3)
         pred_all = i32(nb, bp)
         nn_state = i32(nb, bp, self.neighbour)
-        model = net._packed()
-        batches = [(lo, min(lo + self.batch_size, nb)) for lo in range(0, nb, self.batch_size)]
-        sizes = sorted({hi - lo for lo, hi in batches})
-        ws = {b: net._workspace(b, bp, 1) for b in sizes}
-        net._generation += 1       # the workspace activations no longer belong to an earlier autograd forward
-        logp = {b: f32(b, bp, NUM_CLASSES) for b in sizes}
-        dlogp = {b: f32(b, bp, NUM_CLASSES) for b in sizes}
-        f_sum = {b: f32(b) for b in sizes}             # psg_nu_f_loss_grad_rooms adds the rooms' f sums here: not read
+        bt = _Batches(net, sc, self.batch_size)
+        dlogp = bt.per_size(torch.zeros, bp, NUM_CLASSES)
+        f_sum = bt.per_size(torch.zeros)               # psg_nu_f_loss_grad_rooms adds the rooms' f sums here: not read
         trace = self.trace
         gsum_f = gsum_s = None
         if trace is not None:
@@ -366,19 +327,16 @@ class SceneNUAttack:
             runtime.scene_nu_colour(w, mask, occ_off, active, c)
             runtime.scene_colour_to_blocks(c, idx, x, bad)
             starts_s = []
-            for lo, hi in batches:
+            for lo, hi in bt.spans:
                 b = hi - lo
-                xb, wsb = x[lo:hi], ws[b]
-                starts = upload(draw_fps_starts(b, bp, 1, pinned=True), dev, pin=True)
-                _lib.call("psg_pn2_plan_build", wsb.handle, runtime.ptr(xb), runtime.ptr(starts), 1, st())
-                _lib.call("psg_pn2_forward_lean", model.handle, wsb.handle, 0, runtime.ptr(xb), runtime.ptr(logp[b]), st())
-                _lib.call("psg_nu_f_loss_grad_rooms", runtime.ptr(logp[b]), None if targeted else runtime.ptr(gt[lo:hi]),
+                xb = x[lo:hi]
+                starts, logp = bt.forward(xb)
+                _lib.call("psg_nu_f_loss_grad_rooms", runtime.ptr(logp), None if targeted else runtime.ptr(gt[lo:hi]),
                           int(self.target) if targeted else 0, b, bp, NUM_CLASSES, self.kappa, tsign, runtime.ptr(dlogp[b]),
                           runtime.ptr(f_sum[b]), runtime.ptr(pred_all[lo:hi]), st())
                 if targeted:
                     runtime.scene_rows_mask(dlogp[b], idx[lo:hi], mask)
-                _lib.call("psg_pn2_backward_colour", model.handle, wsb.handle, 0, runtime.ptr(dlogp[b]),
-                          runtime.ptr(dx0_all[lo:hi]), st())
+                bt.backward(dlogp[b], dx0_all[lo:hi])
                 _lib.call("psg_smooth_knn_rooms", off3(xb), 9, bp * 9, off3(x_clean[lo:hi]), 9, bp * 9, b, bp, self.neighbour,
                           None, runtime.ptr(sgrad_all[lo:hi]), runtime.ptr(nn_state[lo:hi]), 1 if s > 0 else 0, st())
                 if trace is not None:

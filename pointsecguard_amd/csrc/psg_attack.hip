@@ -8,6 +8,7 @@
 //   PointNet/NB_nontarget_test_semseg.py:188-211                  acc / per-class I, U, seen
 #include <string.h>
 
+#include "psg_adam.cuh"
 #include "psg_common.h"
 
 namespace {
@@ -661,12 +662,7 @@ __global__ void nu_adam_step_kernel(float *__restrict__ w, float *__restrict__ m
         if (smooth_grad && pt < (size_t)N) g += c_smooth * smooth_grad[t];
         const float th = tanhf(w[t]);
         g = g * 0.5f * (1.0f - th * th);
-        const float mm = __fadd_rn(m[t], __fmul_rn(__fsub_rn(g, m[t]), 1.0f - beta1));
-        const float vv = __fadd_rn(__fmul_rn(v[t], beta2), __fmul_rn(1.0f - beta2, __fmul_rn(g, g)));
-        m[t] = mm;
-        v[t] = vv;
-        const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2_sqrt), eps);
-        w[t] = __fadd_rn(w[t], __fmul_rn(-step_size, __fdiv_rn(mm, denom)));
+        w[t] = psg::adam_update(w[t], m[t], v[t], g, beta1, beta2, eps, step_size, bc2_sqrt);
     }
     for (int o = 32; o >= 1; o >>= 1) l2 += __shfl_xor(l2, o);
     if (!l2_sum) return;
@@ -958,12 +954,10 @@ extern "C" int psg_nu_adam_step(float *w, float *m, float *v, const uint8_t *mas
                                 psg_stream stream)
 {
     PSG_REQUIRE(w && m && v && dx0 && x0 && ori && B > 0 && N > 0 && step >= 1, "psg_nu_adam_step: bad argument");
-    // torch.optim.Adam (single tensor): step_size = lr / (1 - beta1^t), denom = sqrt(v)/sqrt(1 - beta2^t) + eps
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    const psg::AdamConsts k = psg::adam_consts(lr, beta1, beta2, step);
     size_t rows = (size_t)B * N;
     hipLaunchKernelGGL(nu_adam_step_kernel, dim3(grid_for(rows * 3)), dim3(256), 0, (hipStream_t)stream, w, m, v, mask,
-                       dx0, x0, ori, smooth_grad, c_smooth, c_l2, beta1, beta2, eps, step_size, bc2_sqrt, N, rows, l2_sum,
+                       dx0, x0, ori, smooth_grad, c_smooth, c_l2, beta1, beta2, eps, k.step_size, k.bc2_sqrt, N, rows, l2_sum,
                        (const uint8_t *)nullptr, g_nu_dconsts);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
@@ -976,11 +970,10 @@ extern "C" int psg_nu_adam_step_rooms(float *w, float *m, float *v, const uint8_
                                       float *l2_sum_rooms, psg_stream stream)
 {
     PSG_REQUIRE(w && m && v && dx0 && x0 && ori && B > 1 && B <= 65535 && N > 0 && step >= 1, "psg_nu_adam_step_rooms: bad argument (B >= 2)");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    const psg::AdamConsts k = psg::adam_consts(lr, beta1, beta2, step);
     // (12 workgroups per room, four elements per thread at 4096 points: 12 atomics per room sum)
     hipLaunchKernelGGL(nu_adam_step_kernel, dim3(std::min(grid_for((size_t)N * 3), 12), B), dim3(256), 0, (hipStream_t)stream, w, m, v, mask_rooms,
-                       dx0, x0, ori, smooth_grad_rooms, c_smooth, c_l2, beta1, beta2, eps, step_size, bc2_sqrt, N, (size_t)N, l2_sum_rooms,
+                       dx0, x0, ori, smooth_grad_rooms, c_smooth, c_l2, beta1, beta2, eps, k.step_size, k.bc2_sqrt, N, (size_t)N, l2_sum_rooms,
                        room_active, g_nu_dconsts);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
@@ -1176,13 +1169,12 @@ int psg::nu_graph_window(psg_nu_graph *graph, const void *key, size_t key_bytes,
     // (PSG_NU_NO_GRAPH=1: eager windows, for counter passes - per-dispatch counter rows need per-dispatch launches)
     static const bool no_graph = psg::env_int("PSG_NU_NO_GRAPH", 0) != 0;
     if (!graph || no_graph || n_steps > PSG_NU_GRAPH_MAX_STEPS || psg::trace_sync_enabled()) return steps(nullptr);
-    // the step-dependent constants of this window (torch.optim.Adam: step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t))
+    // the step-dependent constants of this window
     for (int i = 0; i < n_steps; ++i) {
-        const int t = adam_t0 + i + 1;
-        const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+        const psg::AdamConsts k = psg::adam_consts(lr, beta1, beta2, adam_t0 + i + 1);
         graph->host[4 * i] = __builtin_bit_cast(float, step0 + i);
-        graph->host[4 * i + 1] = (float)((double)lr / bc1);
-        graph->host[4 * i + 2] = (float)sqrt(bc2);
+        graph->host[4 * i + 1] = k.step_size;
+        graph->host[4 * i + 2] = k.bc2_sqrt;
         graph->host[4 * i + 3] = slot3 ? slot3[i] : 0.0f;     // (psg_rla_nu_window: TF1 Adam's lr_t)
     }
     PSG_CHECK_HIP(hipMemcpyAsync(graph->dconsts, graph->host, (size_t)n_steps * 16, hipMemcpyHostToDevice, st));

@@ -174,13 +174,7 @@ __global__ __launch_bounds__(256) void nu_coord_adam_kernel(float *__restrict__ 
         l2 += d * d;
         float g = dx0[(y * N + pt) * 9 + t % 3] + coord_c * 2.0f * d;
         if (sgrad) g += coord_c * sgrad[o3 + t];
-        const float m0 = m[o3 + t], v0 = v[o3 + t];
-        const float mm = __fadd_rn(m0, __fmul_rn(__fsub_rn(g, m0), 1.0f - beta1));
-        const float vv = __fadd_rn(__fmul_rn(v0, beta2), __fmul_rn(1.0f - beta2, __fmul_rn(g, g)));
-        m[o3 + t] = mm;
-        v[o3 + t] = vv;
-        const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2_sqrt), eps);
-        delta[o3 + t] = __fadd_rn(d, __fmul_rn(-step_size, __fdiv_rn(mm, denom)));
+        delta[o3 + t] = psg::adam_update(d, m[o3 + t], v[o3 + t], g, beta1, beta2, eps, step_size, bc2_sqrt);
     }
     for (int o = 32; o >= 1; o >>= 1) l2 += __shfl_xor(l2, o);
     if (!l2_sum) return;
@@ -243,11 +237,9 @@ extern "C" int psg_nu_coord_adam_step_rooms(float *delta, float *m, float *v, co
                                             int step, int B, int N, const uint8_t *room_active, float *l2_sum_rooms, psg_stream stream)
 {
     PSG_REQUIRE(delta && m && v && dx0 && B > 0 && B <= 65535 && N > 0 && step >= 1, "psg_nu_coord_adam_step_rooms: bad argument");
-    // torch.optim.Adam (single tensor): step_size = lr / (1 - beta1^t), denom = sqrt(v) / sqrt(1 - beta2^t) + eps
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)coord_lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    const psg::AdamConsts k = psg::adam_consts(coord_lr, beta1, beta2, step);
     hipLaunchKernelGGL(nu_coord_adam_kernel, dim3(std::min(grid_for((size_t)N * 3), 12), B), dim3(256), 0, (hipStream_t)stream, delta, m, v,
-                       mask_rooms, dx0, sgrad_xyz, coord_c, beta1, beta2, eps, step_size, bc2_sqrt, N, room_active, l2_sum_rooms);
+                       mask_rooms, dx0, sgrad_xyz, coord_c, beta1, beta2, eps, k.step_size, k.bc2_sqrt, N, room_active, l2_sum_rooms);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
 }
@@ -419,13 +411,7 @@ __global__ __launch_bounds__(256) void nu_coord_adam_w_kernel(float *__restrict_
         l2 += d * d;
         float g = dx0[(y * N + pt) * 9 + t % 3] + c_l2 * 2.0f * d;
         if (sgrad) g += c_smooth * sgrad[o3 + t];
-        const float m0 = m[o3 + t], v0 = v[o3 + t];
-        const float mm = __fadd_rn(m0, __fmul_rn(__fsub_rn(g, m0), 1.0f - beta1));
-        const float vv = __fadd_rn(__fmul_rn(v0, beta2), __fmul_rn(1.0f - beta2, __fmul_rn(g, g)));
-        m[o3 + t] = mm;
-        v[o3 + t] = vv;
-        const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2_sqrt), eps);
-        delta[o3 + t] = __fadd_rn(d, __fmul_rn(-step_size, __fdiv_rn(mm, denom)));
+        delta[o3 + t] = psg::adam_update(d, m[o3 + t], v[o3 + t], g, beta1, beta2, eps, step_size, bc2_sqrt);
     }
     for (int o = 32; o >= 1; o >>= 1) l2 += __shfl_xor(l2, o);
     if (!l2_sum) return;
@@ -487,10 +473,9 @@ extern "C" int psg_nu_coord_adam_step_rooms_w(float *delta, float *m, float *v, 
                                               psg_stream stream)
 {
     PSG_REQUIRE(delta && m && v && dx0 && B > 0 && B <= 65535 && N > 0 && step >= 1, "psg_nu_coord_adam_step_rooms_w: bad argument");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)coord_lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    const psg::AdamConsts k = psg::adam_consts(coord_lr, beta1, beta2, step);
     hipLaunchKernelGGL(nu_coord_adam_w_kernel, dim3(std::min(grid_for((size_t)N * 3), 12), B), dim3(256), 0, (hipStream_t)stream, delta, m, v,
-                       mask_rooms, dx0, sgrad_xyz, c_smooth, c_l2, beta1, beta2, eps, step_size, bc2_sqrt, N, room_active, l2_sum_rooms,
+                       mask_rooms, dx0, sgrad_xyz, c_smooth, c_l2, beta1, beta2, eps, k.step_size, k.bc2_sqrt, N, room_active, l2_sum_rooms,
                        g_nu_dconsts);
     PSG_LAUNCH_CHECK();
     return PSG_OK;

@@ -11,18 +11,18 @@
 // Compiled with -ffp-contract=off: the summation order and the step's evaluation order decide bits.  No float atomics
 // anywhere; every output element has one writer.  The only atomics are integer ones (histogram, list cursors, the bad-index
 // flag), whose results do not depend on the order they land in; the order INSIDE a list, which an atomic cursor would leave
-// to scheduling, is fixed afterwards by ranking every entry among its list.
+// to scheduling, is fixed afterwards by ranking every entry among its list.  The readers of the lists - the two step kernels
+// here, scene_nu_step_kernel in psg_scene_nu.hip - all go through for_each_slot (psg_scene_lists.cuh).
 #include <climits>
 
 #include "psg_common.h"
+#include "psg_scene_lists.cuh"
 
 using namespace psg;
 
 namespace {
 
 constexpr int SCAN_THREADS = 1024;
-
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
 // cnt[p] += 1 for every row with a valid index (cnt zeroed by the caller); an index outside [0, n_scene) raises the flag
 __global__ void occ_count_kernel(const int32_t *__restrict__ point_idx, int rows, int n_scene, int32_t *__restrict__ cnt,
@@ -125,20 +125,10 @@ __global__ void scene_pgd_step_kernel(float *__restrict__ scene_rgb, const float
     if (t >= total) return;
     const size_t p = t / 3;
     const int ch = (int)(t % 3);
-    const bool on = !scene_mask || scene_mask[p];
-    int lo = occ_off[p], hi = occ_off[p + 1];
-    lo = max(lo, 0);
-    hi = min(hi, rows);
     float g = 0.0f;
     bool any = false;
-    if (on) {
-        for (int i = lo; i < hi; ++i) {
-            const int e = occ_ent[i];
-            if (e < 0 || e >= rows) continue;
-            g = __fadd_rn(g, dx0[(size_t)e * 9 + 3 + ch]);
-            any = true;
-        }
-    }
+    if (!scene_mask || scene_mask[p])
+        any = for_each_slot(occ_off, occ_ent, p, rows, [&](int e) { g = __fadd_rn(g, dx0[(size_t)e * 9 + 3 + ch]); });
     if (gsum_out) gsum_out[t] = g;
     if (!any) return;                                  // no occurrence (or not under the mask): the point does not move
     const float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
@@ -164,7 +154,7 @@ __global__ void delta_to_blocks_kernel(const float *__restrict__ delta, const in
     x[row * 9 + ch] = __fadd_rn(x_clean[row * 9 + ch], delta[(size_t)p * 3 + ch]);
 }
 
-// one thread per (scene point, coordinate): scene_pgd_step_kernel's list walk over channels 0:3, then
+// one thread per (scene point, coordinate): scene_pgd_step_kernel's ordered sum over channels 0:3, then
 // stepped = delta + step * sign(g); delta = last ? stepped : clamp(stepped, -eps, +eps)
 __global__ void scene_field_step_kernel(float *__restrict__ delta, const uint8_t *__restrict__ scene_mask,
                                         const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ_ent,
@@ -175,29 +165,16 @@ __global__ void scene_field_step_kernel(float *__restrict__ delta, const uint8_t
     if (t >= total) return;
     const size_t p = t / 3;
     const int ch = (int)(t % 3);
-    const bool on = !scene_mask || scene_mask[p];
-    int lo = occ_off[p], hi = occ_off[p + 1];
-    lo = max(lo, 0);
-    hi = min(hi, rows);
     float g = 0.0f;
     bool any = false;
-    if (on) {
-        for (int i = lo; i < hi; ++i) {
-            const int e = occ_ent[i];
-            if (e < 0 || e >= rows) continue;
-            g = __fadd_rn(g, dx0[(size_t)e * 9 + ch]);
-            any = true;
-        }
-    }
+    if (!scene_mask || scene_mask[p])
+        any = for_each_slot(occ_off, occ_ent, p, rows, [&](int e) { g = __fadd_rn(g, dx0[(size_t)e * 9 + ch]); });
     if (gsum_out) gsum_out[t] = g;
     if (!any) return;                                  // no occurrence (or not under the mask): the point does not move
     const float sg = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
     const float stepped = __fadd_rn(delta[t], __fmul_rn(step, sg));
     delta[t] = last ? stepped : fminf(fmaxf(stepped, -eps), eps);
 }
-
-// the rows of [rows][9] are addressed through int32 slot numbers (the lists hold them): rows * 9 floats must stay below 2^31
-inline bool rows_ok(int rows) { return rows > 0 && rows <= INT_MAX / 9; }
 
 }  // namespace
 

@@ -1,6 +1,7 @@
 // Whole-scene NU attack: Adam in tanh space on ONE colour per scene point across all the overlapping
-// blocks that hold it.  The lists are psg_scene_occ_build's (psg_scene.hip); the arithmetic is psg_attack.hip's NU kernels
-// (nu_inverse_tanh_kernel, nu_tanh_color_kernel, nu_adam_step_kernel), operation for operation.
+// blocks that hold it.  The lists are psg_scene_occ_build's (psg_scene.hip), read through for_each_slot
+// (psg_scene_lists.cuh); the arithmetic is psg_attack.hip's NU kernels (nu_inverse_tanh_kernel, nu_tanh_color_kernel,
+// nu_adam_step_kernel), operation for operation, the Adam update being the one both call (psg_adam.cuh).
 //   psg_scene_nu_init    w = inverse_tanh_space(c0) for every scene point
 //   psg_scene_nu_colour  c = 1/2 (tanh w + 1) on the moving points while the attack is active
 //   psg_scene_nu_step    f-loss and Smooth gradients summed over a point's slots in ascending slot order, the L2 term once
@@ -11,10 +12,10 @@
 // output element has one writer.  The only atomics are the integer ones of the latch's two counters.  `active` is one int32
 // word on the device: while it is 0 the colour, step and latch launches leave every byte alone.
 #include <algorithm>
-#include <climits>
-#include <cmath>
 
+#include "psg_adam.cuh"
 #include "psg_common.h"
+#include "psg_scene_lists.cuh"
 
 using namespace psg;
 
@@ -22,11 +23,6 @@ namespace {
 
 constexpr int LATCH_THREADS = 1024;
 constexpr unsigned COUNT_BLOCKS = 1024;
-
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
-
-// the slot numbers of the lists address [rows][9] floats: psg_scene.hip's guard
-inline bool rows_ok(int rows) { return rows > 0 && rows <= INT_MAX / 9; }
 
 // w = atanh(2 c0 - 1) written the reference's way, 0.5 * log((1 + x) / (1 - x)): nu_inverse_tanh_kernel on [n_scene][3]
 __global__ void scene_nu_init_kernel(const float *__restrict__ c0, float *__restrict__ w, size_t total)
@@ -51,8 +47,9 @@ __global__ void scene_nu_colour_kernel(const float *__restrict__ w, const uint8_
     c[t] = __fmul_rn(0.5f, __fadd_rn(tanhf(w[t]), 1.0f));
 }
 
-// one thread per (scene point, colour channel): scene_pgd_step_kernel's list walk over dx0[e][3 + ch] and over sgrad[e][ch],
-// then nu_adam_step_kernel's gradient assembly and Adam update with the L2 term of the POINT (once, not once per slot)
+// one thread per (scene point, colour channel): the ordered sums over dx0[e][3 + ch] and over sgrad[e][ch] in one walk of the
+// point's slots, then nu_adam_step_kernel's gradient assembly and Adam update with the L2 term of the POINT (once, not once
+// per slot)
 __global__ void scene_nu_step_kernel(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v, const float *__restrict__ c,
                                      const float *__restrict__ c0, const uint8_t *__restrict__ scene_mask,
                                      const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ_ent,
@@ -65,21 +62,13 @@ __global__ void scene_nu_step_kernel(float *__restrict__ w, float *__restrict__ 
     if (t >= total) return;
     const size_t p = t / 3;
     const int ch = (int)(t % 3);
-    const bool on = !scene_mask || scene_mask[p];
-    int lo = occ_off[p], hi = occ_off[p + 1];
-    lo = max(lo, 0);
-    hi = min(hi, rows);
     float gf = 0.0f, gs = 0.0f;
     bool any = false;
-    if (on) {
-        for (int i = lo; i < hi; ++i) {
-            const int e = occ_ent[i];
-            if (e < 0 || e >= rows) continue;
+    if (!scene_mask || scene_mask[p])
+        any = for_each_slot(occ_off, occ_ent, p, rows, [&](int e) {
             gf = __fadd_rn(gf, dx0[(size_t)e * 9 + 3 + ch]);
             gs = __fadd_rn(gs, sgrad[(size_t)e * 3 + ch]);
-            any = true;
-        }
-    }
+        });
     if (gsum_f_out) gsum_f_out[t] = gf;
     if (gsum_s_out) gsum_s_out[t] = gs;
     if (!any) return;                                  // no occurrence (or not under the mask): the point does not move
@@ -88,12 +77,7 @@ __global__ void scene_nu_step_kernel(float *__restrict__ w, float *__restrict__ 
     g = __fadd_rn(g, __fmul_rn(cw, gs));
     const float th = tanhf(w[t]);
     g = __fmul_rn(__fmul_rn(g, 0.5f), __fsub_rn(1.0f, __fmul_rn(th, th)));
-    const float mm = __fadd_rn(m[t], __fmul_rn(__fsub_rn(g, m[t]), 1.0f - beta1));
-    const float vv = __fadd_rn(__fmul_rn(v[t], beta2), __fmul_rn(1.0f - beta2, __fmul_rn(g, g)));
-    m[t] = mm;
-    v[t] = vv;
-    const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2_sqrt), eps);
-    w[t] = __fadd_rn(w[t], __fmul_rn(-step_size, __fdiv_rn(mm, denom)));
+    w[t] = adam_update(w[t], m[t], v[t], g, beta1, beta2, eps, step_size, bc2_sqrt);
 }
 
 // counters[0] += slots that hit, counters[1] += slots that count (both zero on entry).  Non-targeted (scene_mask == NULL):
@@ -199,12 +183,10 @@ extern "C" int psg_scene_nu_step(float *w, float *m, float *v, const float *c, c
     PSG_REQUIRE(w && m && v && c && c0 && occ_off && occ_ent && dx0 && sgrad && active && n_scene > 0 && step >= 1,
                 "psg_scene_nu_step: bad argument");
     PSG_REQUIRE(rows_ok(rows), "psg_scene_nu_step: rows=%d outside 1 .. INT_MAX / 9 (slot numbers address [rows][9] floats)", rows);
-    // torch.optim.Adam (single tensor), as psg_nu_adam_step computes it: step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t)
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    const AdamConsts k = adam_consts(lr, beta1, beta2, step);
     const size_t total = (size_t)n_scene * 3;
     hipLaunchKernelGGL(scene_nu_step_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, w, m, v, c, c0, scene_mask,
-                       occ_off, occ_ent, dx0, sgrad, rows, total, cw, beta1, beta2, eps, step_size, bc2_sqrt, active, gsum_f_out,
+                       occ_off, occ_ent, dx0, sgrad, rows, total, cw, beta1, beta2, eps, k.step_size, k.bc2_sqrt, active, gsum_f_out,
                        gsum_s_out);
     PSG_LAUNCH_CHECK();
     return PSG_OK;

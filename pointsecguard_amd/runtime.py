@@ -513,22 +513,29 @@ def scene_rows_mask(dlogp, point_idx, scene_mask):
     return dlogp
 
 
-def scene_pgd_step(scene_rgb, scene_ori, scene_mask, occ_off, occ_ent, dx0, alpha, eps, direction, last, gsum_out=None):
-    """One step on the scene's colours [n_scene, 3] (in place) from the block gradients dx0 [rows, 9] summed over every
-    point's slots in ascending slot order (psg_scene_pgd_step)."""
-    require_cuda(scene_rgb, "scene_rgb", torch.float32)
-    require_cuda(scene_ori, "scene_ori", torch.float32)
+def _scene_step_common(var, name, scene_mask, occ_off, occ_ent, dx0, gsum_out):
+    """The checks of the two step wrappers below: `var` [n_scene, 3] is the array the step moves.  Returns (rows, n_scene)."""
+    require_cuda(var, name, torch.float32)
     require_cuda(occ_off, "occ_off", torch.int32)
     require_cuda(occ_ent, "occ_ent", torch.int32)
     require_cuda(dx0, "dx0", torch.float32)
     if scene_mask is not None:
         require_cuda(scene_mask, "scene_mask", torch.uint8)
-        assert scene_mask.numel() == scene_rgb.shape[0]
+        assert scene_mask.numel() == var.shape[0]
     if gsum_out is not None:
         require_cuda(gsum_out, "gsum_out", torch.float32)
-        assert gsum_out.shape == scene_rgb.shape
-    rows, n_scene = occ_ent.numel(), scene_rgb.shape[0]
-    assert dx0.numel() == rows * 9 and occ_off.numel() == n_scene + 1 and scene_ori.shape == scene_rgb.shape == (n_scene, 3)
+        assert gsum_out.shape == var.shape
+    rows, n_scene = occ_ent.numel(), var.shape[0]
+    assert dx0.numel() == rows * 9 and occ_off.numel() == n_scene + 1 and var.shape == (n_scene, 3)
+    return rows, n_scene
+
+
+def scene_pgd_step(scene_rgb, scene_ori, scene_mask, occ_off, occ_ent, dx0, alpha, eps, direction, last, gsum_out=None):
+    """One step on the scene's colours [n_scene, 3] (in place) from the block gradients dx0 [rows, 9] summed over every
+    point's slots in ascending slot order (psg_scene_pgd_step)."""
+    rows, n_scene = _scene_step_common(scene_rgb, "scene_rgb", scene_mask, occ_off, occ_ent, dx0, gsum_out)
+    require_cuda(scene_ori, "scene_ori", torch.float32)
+    assert scene_ori.shape == scene_rgb.shape
     _lib.call("psg_scene_pgd_step", ptr(scene_rgb), ptr(scene_ori), ptr(scene_mask), ptr(occ_off), ptr(occ_ent), ptr(dx0), rows,
               n_scene, float(alpha), float(eps), float(direction), 1 if last else 0, ptr(gsum_out), stream())
     return scene_rgb
@@ -552,18 +559,7 @@ def scene_delta_to_blocks(delta, point_idx, x_clean, x, bad):
 def scene_field_step(delta, scene_mask, occ_off, occ_ent, dx0, alpha, eps, direction, last, gsum_out=None):
     """One step on the scene's displacements [n_scene, 3] (in place) from channels 0:3 of the block gradients dx0 [rows, 9]
     summed over every point's slots in ascending slot order; clamp to [-eps, eps], no box (psg_scene_field_step)."""
-    require_cuda(delta, "delta", torch.float32)
-    require_cuda(occ_off, "occ_off", torch.int32)
-    require_cuda(occ_ent, "occ_ent", torch.int32)
-    require_cuda(dx0, "dx0", torch.float32)
-    if scene_mask is not None:
-        require_cuda(scene_mask, "scene_mask", torch.uint8)
-        assert scene_mask.numel() == delta.shape[0]
-    if gsum_out is not None:
-        require_cuda(gsum_out, "gsum_out", torch.float32)
-        assert gsum_out.shape == delta.shape
-    rows, n_scene = occ_ent.numel(), delta.shape[0]
-    assert dx0.numel() == rows * 9 and occ_off.numel() == n_scene + 1 and delta.shape == (n_scene, 3)
+    rows, n_scene = _scene_step_common(delta, "delta", scene_mask, occ_off, occ_ent, dx0, gsum_out)
     _lib.call("psg_scene_field_step", ptr(delta), ptr(scene_mask), ptr(occ_off), ptr(occ_ent), ptr(dx0), rows, n_scene,
               float(alpha), float(eps), float(direction), 1 if last else 0, ptr(gsum_out), stream())
     return delta
