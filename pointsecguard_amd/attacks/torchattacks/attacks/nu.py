@@ -26,13 +26,13 @@ import numpy as np
 import torch
 
 from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd.attacks.nu_windows import CHUNK, RoomsState, _bind, room_masks, to_restart, window_end, window_loop
 from pointsecguard_amd.models.pointnet2_sem_seg import draw_fps_starts, upload
 
 from . import pointnet as pointnet_net
 from ._common import labels_to_device, mask_to_device, psg_model
 
 BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
-CHUNK = 10  # control-flow window: restarts can only happen after steps that are multiples of 10
 # Geometry plan horizon (round 6).  A plan may run up to PLAN_AHEAD forwards ahead of the control-flow windows (`plan_ahead`
 # forwards at once; what a restart or an early exit leaves unused of it is re-drawn / given back to the generator: the FPS
 # draws come from the CPU generator in forward order, pointnet_util.py:75, the restart noise of target.py:131 from the
@@ -46,51 +46,21 @@ PLAN_AHEAD = 50          # capacity: forwards a geometry plan may hold (graph ha
 plan_ahead = CHUNK       # forwards actually planned at once (a multiple of CHUNK, <= PLAN_AHEAD): module-level knob
 
 
-class _NuState:
-    """Device buffers of one attack shape (G attacks of `rows` batch rows, N points), kept with the model instance between
-    calls: the addresses stay the same, so a 10-step window captured as a hipGraph by one call is replayed by the next
-    (one model instance serves one host thread / stream at a time, like its network workspace)."""
+class _NuState(RoomsState):
+    """RoomsState of G attacks of `rows` batch rows with the colour loops' scratch, and one graph handle per window position
+    inside a geometry plan (a captured window holds its plan slots)."""
 
     def __init__(self, dev, G, rows, N, neighbour):
+        super().__init__(dev, G, rows, N, neighbour, n_scal=3, n_graphs=PLAN_AHEAD // CHUNK)     # scal rows: f, smooth, l2
         B = G * rows
-        f32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
         self.key = (G, rows, N, int(neighbour))
-        self.x0, self.x0_orig, self.ori = f32(B, N, 9), f32(B, N, 9), f32(B, N, 3)
-        self.w, self.m, self.v = f32(B, N, 3), f32(B, N, 3), f32(B, N, 3)
-        self.logp, self.dlogp, self.dx0 = f32(B, N, 13), f32(B, N, 13), f32(B, N, 9)
-        self.sgrad = f32(G, N, 3)
-        self.pred = torch.empty(B, N, device=dev, dtype=torch.int32)
-        self.labels = torch.empty(B, N, device=dev, dtype=torch.int32)
-        self.mask = torch.empty(G, N, device=dev, dtype=torch.uint8)
-        self.scal = f32(3, G)                                        # rows: f, smooth, l2
-        self.nn_state = torch.empty(G, N, int(neighbour), device=dev, dtype=torch.int32)   # Smooth term: last step's neighbours
-        self.hist = f32(CHUNK, 5, G)                                 # one window of history rows: n_correct, n_hits, f, smooth, l2
-        self.active = torch.empty(G, device=dev, dtype=torch.uint8)
-        self.exit = torch.empty(G, device=dev, dtype=torch.int32)
-        self.n_mask = torch.empty(G, device=dev, dtype=torch.int32)
-        self.restart_l2 = f32(G)                                     # psg_nu_restart_rooms: sum((x - x_orig)^2), channels 0:3 and 6:9
-        self.out = f32(B, 9, N)
-        # one graph handle per window position inside a geometry plan (a captured window holds its plan slots)
-        self.graphs = [ctypes.c_void_p() for _ in range(PLAN_AHEAD // CHUNK)]
-        for g in self.graphs:
-            _lib.call("psg_nu_graph_create", ctypes.byref(g))
-        self.graph = self.graphs[0]
-
-    def __del__(self):
-        try:
-            for g in self.graphs:
-                if g:
-                    _lib.load().psg_nu_graph_destroy(g)
-        except Exception:
-            pass
+        self.x0_orig = self._f32(B, N, 9)
+        self.logp, self.dlogp = self._f32(B, N, 13), self._f32(B, N, 13)
+        self.restart_l2 = self._f32(G)                               # psg_nu_restart_rooms: sum((x - x_orig)^2), channels 0:3 and 6:9
 
 
 def _state(net, dev, G, rows, N, neighbour):
-    cache = net.__dict__.setdefault("_psg_nu_states", {})
-    key = (str(dev), G, rows, N, int(neighbour))
-    if key not in cache:
-        cache[key] = _NuState(dev, G, rows, N, neighbour)
-    return cache[key]
+    return _NuState.of(net, "_psg_nu_states", (str(dev), G, rows, N, int(neighbour)), dev, G, rows, N, neighbour)
 
 
 def _pointnet_restart(S, x0, again, n_mask, G, rows, N, dev, extra_l2):
@@ -111,23 +81,24 @@ def _pointnet_restart(S, x0, again, n_mask, G, rows, N, dev, extra_l2):
     extra_l2[again] = S.restart_l2.cpu().numpy().astype(np.float64)[again]               # one read-back for all of them
 
 
-def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, trace, starts_fn, G, rows, record=None):
+def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, trace, starts_fn, G, rows, record=None, restore_lr=False):
     """G attacks of `rows` batch rows each, advanced together: (1, B) = the reference's call on a batch of B rows (its batch
     semantics: Smooth term and mask of batch row 0, counts over all rows), (R, 1) = R one-room calls in lockstep.
-    masks: bool numpy [G, N] or None.  Returns (out [G*rows, 9, N], exited [G] = step of the exit test or -1, steps done).
+    masks: [G, N] or None.  Returns (out [G*rows, 9, N], steps_run [G]: the optimiser steps the reference's loop ran).
 
-    The same loop serves the vanilla PointNet (pointnet.is_pointnet): its windows are psg_pointnet_nu_window calls, it has no
-    geometry plan (no FPS starts, nothing drawn from or given back to the CPU generator) and its restart is one
-    psg_nu_restart_rooms launch; window boundaries, read-backs, halving and the restart test are the code below for both.
+    The window loop is nu_windows.window_loop; this function supplies what is this network's.  The vanilla PointNet
+    (pointnet.is_pointnet) goes the same way: its windows are psg_pointnet_nu_window calls, it has no geometry plan (no FPS
+    starts, nothing drawn from or given back to the CPU generator) and its restart is one psg_nu_restart_rooms launch.
     `record(step, row [5, G], extra_l2 [G], was_active [G])` (tests) receives every step's history row without changing the
     windows (`trace` reads back after every step, so it cannot observe them), and `record(step, None, extra_l2, restarting [G])`
     when attacks restart after `step`."""
+    B, _, N = images.shape
+    assert B == G * rows
+    masks, n_mask = room_masks(masks, G, N, targeted_variant, "target.py:104")
     pointnet = pointnet_net.is_pointnet(atk.model)
     net = psg_model(atk.model)
     dev = atk.device
     images = images.detach().to(dev).float().contiguous()
-    B, C, N = images.shape
-    assert B == G * rows
     st = runtime.stream
     S = _state(net, dev, G, rows, N, neighbour)
     model = net._packed()
@@ -139,18 +110,10 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
     use_target = targeted_variant and target is not None
     mode = 0 if not targeted_variant else (2 if use_target else 1)
     S.labels.copy_(labels_to_device(labels, dev))
+    mask_b = None
     if masks is not None:
         S.mask.copy_(torch.from_numpy(masks.astype(np.uint8)))
-        n_mask = masks.sum(axis=1).astype(np.float64)
         mask_b = S.mask.bool()
-        if targeted_variant and (n_mask == 0).any():
-            # the reference divides the hits by the mask count (target.py:104-105): an empty mask raises there too
-            raise ZeroDivisionError("tar_NU_attack: attacks %s have an empty mask (target.py:104: division by the mask count)"
-                                    % np.nonzero(n_mask == 0)[0].tolist())
-    else:
-        if targeted_variant:
-            raise ValueError("the targeted variant needs a mask")
-        n_mask, mask_b = np.zeros(G), None
     S.n_mask.copy_(torch.from_numpy(n_mask.astype(np.int32)))
     x0, w, m, v = S.x0, S.w, S.m, S.v
     _lib.call("psg_to_point_major", runtime.ptr(images), B, 9, N, runtime.ptr(x0), st())
@@ -161,26 +124,22 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
     S.active.fill_(1); S.exit.fill_(-1)
     extra_l2 = np.zeros(G)  # (adv - images)^2 over the non-colour channels: non-zero only after a restart clamped them
     prev_cost = np.full((atk.steps, G), 1e10)
-    lr, adam_t = float(atk.lr), 0
-    tsign = float(atk._targeted)
-    planned_until, rng_at = (atk.steps, None) if pointnet else (0, None)           # (PointNet: nothing to plan)
-    plan_base = 0
-    exited = np.full(G, -1, np.int64)                                # step at which an attack's exit test fired (-1: running)
+    cost = None
     win_args, win_entry = (_lib.PointnetNuWindowArgs, "psg_pointnet_nu_window") if pointnet else (_lib.NuWindowArgs, "psg_pn2_nu_window")
     win = win_args(
         model=model.handle.value, ws=ws.handle.value, G=G, rows=rows, N=N, mode=mode, use_target=int(use_target),
-        target=int(target) if use_target else 0, neighbour=int(neighbour), kappa=float(atk.kappa), tsign=tsign, c_smooth=float(atk.c),
-        c_l2=float(atk.c), beta1=BETA1, beta2=BETA2, eps=ADAM_EPS, w=w.data_ptr(), m=m.data_ptr(), v=v.data_ptr(),
-        mask=S.mask.data_ptr() if masks is not None else None, n_mask=S.n_mask.data_ptr(), x0=x0.data_ptr(), ori=S.ori.data_ptr(),
-        labels=S.labels.data_ptr(), logp=S.logp.data_ptr(), dlogp=S.dlogp.data_ptr(), dx0=S.dx0.data_ptr(), sgrad=S.sgrad.data_ptr(),
-        pred=S.pred.data_ptr(), scal=S.scal.data_ptr(), nn_state=S.nn_state.data_ptr(), hist=S.hist.data_ptr(), out=S.out.data_ptr(),
-        active=S.active.data_ptr(), exit_step=S.exit.data_ptr())
+        target=int(target) if use_target else 0, neighbour=int(neighbour), kappa=float(atk.kappa), tsign=float(atk._targeted),
+        c_smooth=float(atk.c), c_l2=float(atk.c), beta1=BETA1, beta2=BETA2, eps=ADAM_EPS)
+    _bind(win, S, "w m v n_mask x0 ori labels logp dlogp dx0 sgrad pred scal nn_state hist out active exit_step=exit")
+    win.mask = S.mask.data_ptr() if masks is not None else None
     if pointnet:
         win.fused_head = 1 if pointnet_net.fused_head else 0
         win.logp = None                                  # (scratch of the three-kernel head's log-probs: nobody reads a copy)
+    planned_until, plan_base, rng_at = 0, 0, None
 
-    step = 0
-    while step < atk.steps:
+    def plan(step):
+        """the geometry plan that covers `step`, built when there is none -> its end"""
+        nonlocal planned_until, plan_base, rng_at
         if step >= planned_until:
             # Geometry windows end after steps 10, 20, 30, ..: a restart (which draws from the RNG and may move xyz) can
             # only follow a step that is a multiple of 10 greater than 10, so the FPS draws of a window come out of the
@@ -200,82 +159,69 @@ def _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr
                     torch.set_rng_state(rng_at[step])                # the unused draws of the plan this one replaces
                 parts, rng_at, s_ = [], {}, step
                 while s_ < step + n_plan:
-                    e_ = min(1 if s_ == 0 else ((s_ - 1) // CHUNK + 1) * CHUNK + 1, step + n_plan)
+                    e_ = min(window_end(s_, CHUNK), step + n_plan)
                     parts.append(draw_fps_starts(B, N, e_ - s_))
                     rng_at[e_] = torch.get_rng_state()
                     s_ = e_
                 starts = upload(torch.cat(parts), dev)
             ws.plan_build(x0, starts, n_plan)
             plan_base, planned_until = step, step + n_plan
-        # ---- the steps up to the end of the control-flow window (= up to the next point where the reference's host work needs
-        # values) in ONE call: colours, forward, f-loss, backward, Smooth term, Adam step, statistics + exit latch per step;
-        # full windows of the same shape are replayed as a hipGraph (psg_pn2_nu_window)
-        window_end = 1 if step == 0 else ((step - 1) // CHUNK + 1) * CHUNK + 1          # [0], [1..10], [11..20], ..
-        n_run = 1 if trace is not None else min(planned_until, window_end) - step
+        return planned_until
+
+    def enqueue(step, n_run, adam_t):
+        # the steps of the window in ONE call: colours, forward, f-loss, backward, Smooth term, Adam step, statistics + exit
+        # latch per step; full windows of the same shape are replayed as a hipGraph (psg_pn2_nu_window)
         win.step0, win.n_steps = step, n_run
-        win.adam_t0, win.lr, win.warm_first = adam_t, lr, 1 if step > 0 else 0
+        win.adam_t0, win.lr, win.warm_first = adam_t, float(atk.lr), 1 if step > 0 else 0
         if pointnet:
             graph = S.graphs[0] if n_run == CHUNK else None              # (no plan slots in the key: one handle serves every window)
         else:
             win.slot0 = step - plan_base
             graph = S.graphs[((step - plan_base) // CHUNK) % len(S.graphs)] if n_run == CHUNK and (step - plan_base) % CHUNK == 0 else None
         _lib.call(win_entry, ctypes.byref(win), graph, st())
-        adam_t += n_run
-        last = step + n_run - 1
-        # ---- the reference's control flow, per attack, where the reference's host work needs the values (ONE read-back)
-        got = torch.cat([S.hist[:n_run].reshape(-1), S.exit.float()]).cpu().numpy().astype(np.float64)
-        hrows, exited = got[:-G].reshape(n_run, 5, G), got[-G:].astype(np.int64)
-        for s_i in range(step, last + 1):
-            was_active = (exited < 0) | (exited >= s_i)                  # attacks whose loop was still running at step s_i
-            f_loss, sm_loss = hrows[s_i - step, 2], hrows[s_i - step, 3]
-            l2_loss = hrows[s_i - step, 4] + extra_l2
-            cost = f_loss + float(atk.c) * sm_loss + float(atk.c) * l2_loss
-            prev_cost[s_i] = np.where(was_active, cost, prev_cost[s_i])
-            if trace is not None:
-                trace(s_i, cost, f_loss, sm_loss, l2_loss, was_active, S)
-            if record is not None:
-                record(s_i, hrows[s_i - step].copy(), extra_l2.copy(), was_active.copy())
-        step = last + 1
-        active = exited < 0                              # after this step's exits (nontarget.py:95-96, target.py:116-121)
-        if not active.any():
-            break
-        if not targeted_variant:
-            continue
-        if last > 0 and last % 50 == 0:                  # target.py:123-125: halve lr, NEW optimiser (moments reset)
-            atk.lr = atk.lr / 2
-            lr, adam_t = float(atk.lr), 0
-            m.zero_()
-            v.zero_()
-        if last > 10 and last % 10 == 0:                 # target.py:127-132, attack by attack
-            again = np.nonzero(active & (cost >= prev_cost[last - 10]))[0]
-            if record is not None and len(again):
-                record(last, None, extra_l2.copy(), np.isin(np.arange(G), again))        # a restart event: who restarts after `last`
-            if pointnet:
-                if len(again):
-                    _pointnet_restart(S, x0, again, n_mask, G, rows, N, dev, extra_l2)
-            else:
-                for g in again:                              # the noise draws stay per attack, in order
-                    k = int(n_mask[g])
-                    noise = torch.empty(rows, 3, k, device=dev, dtype=torch.float32).uniform_(0, 1)
-                    col = x0[g * rows:(g + 1) * rows, :, 3:6].transpose(1, 2)        # view [rows, 3, N]
-                    col[:, :, mask_b[g]] = col[:, :, mask_b[g]] + noise
-                if len(again):
-                    ridx = torch.from_numpy(np.concatenate([np.arange(g * rows, (g + 1) * rows) for g in again])).to(dev)
-                    clamped = x0[ridx].clamp_(min=0, max=1)                   # ALL channels, like the reference
-                    x0[ridx] = clamped
-                    d = clamped - S.x0_orig[ridx]
-                    sums = ((d[:, :, 0:3] ** 2).sum(dim=(1, 2)) + (d[:, :, 6:9] ** 2).sum(dim=(1, 2))).reshape(len(again), rows)
-                    extra_l2[again] = sums.sum(dim=1).cpu().numpy().astype(np.float64)   # one read-back for all of them
-                    planned_until = step                     # xyz may have moved: rebuild the plan before the next forward
+
+    def on_step(s_i, row, was_active, exited):
+        nonlocal cost
+        f_loss, sm_loss, l2_loss = row[2], row[3], row[4] + extra_l2
+        cost = f_loss + float(atk.c) * sm_loss + float(atk.c) * l2_loss
+        prev_cost[s_i] = np.where(was_active, cost, prev_cost[s_i])
+        if trace is not None:
+            trace(s_i, cost, f_loss, sm_loss, l2_loss, was_active, S)
+        if record is not None:
+            record(s_i, row.copy(), extra_l2.copy(), was_active.copy())
+
+    def between(last, step, active):                     # target.py:127-132, attack by attack
+        nonlocal planned_until
+        again = to_restart(last, active, cost, prev_cost)
+        if not len(again):
+            return
+        if record is not None:
+            record(last, None, extra_l2.copy(), np.isin(np.arange(G), again))        # a restart event: who restarts after `last`
+        if pointnet:
+            _pointnet_restart(S, x0, again, n_mask, G, rows, N, dev, extra_l2)
+            return
+        for g in again:                                  # the noise draws stay per attack, in order
+            k = int(n_mask[g])
+            noise = torch.empty(rows, 3, k, device=dev, dtype=torch.float32).uniform_(0, 1)
+            col = x0[g * rows:(g + 1) * rows, :, 3:6].transpose(1, 2)        # view [rows, 3, N]
+            col[:, :, mask_b[g]] = col[:, :, mask_b[g]] + noise
+        ridx = torch.from_numpy(np.concatenate([np.arange(g * rows, (g + 1) * rows) for g in again])).to(dev)
+        clamped = x0[ridx].clamp_(min=0, max=1)                   # ALL channels, like the reference
+        x0[ridx] = clamped
+        d = clamped - S.x0_orig[ridx]
+        sums = ((d[:, :, 0:3] ** 2).sum(dim=(1, 2)) + (d[:, :, 6:9] ** 2).sum(dim=(1, 2))).reshape(len(again), rows)
+        extra_l2[again] = sums.sum(dim=1).cpu().numpy().astype(np.float64)   # one read-back for all of them
+        planned_until = step                             # xyz may have moved: rebuild the plan before the next forward
+
+    out, steps_run, step = window_loop(atk, S, rows, enqueue, targeted_variant=targeted_variant, on_step=on_step, between=between,
+                                       limit=None if pointnet else plan, one_step=trace is not None, moments=(m, v),
+                                       restore_lr=restore_lr)
     if rng_at is not None and planned_until > step:
         # draws of forwards that never ran go back to the generator - all but those of the window the attack stopped in
         # (rounds 3-5 drew window by window: the generator is left where it was left then)
         e_ = step if step in rng_at else min(k for k in rng_at if k >= step)
         torch.set_rng_state(rng_at[e_])
-    out = S.out.clone()                                  # (the caller owns what it gets; the state buffer is reused)
-    for g in np.nonzero(exited < 0)[0]:                  # attacks that ran to the cap: the current image
-        _lib.call("psg_to_channel_major", runtime.ptr(x0[g * rows:(g + 1) * rows]), rows, 9, N, runtime.ptr(out[g * rows:(g + 1) * rows]), st())
-    return out, exited, step
+    return out, steps_run
 
 
 def nu_attack(atk, images, labels, mask, target, neighbour, targeted_variant=False, trace=None, starts_fn=None, return_steps=False,
@@ -293,8 +239,9 @@ def nu_attack(atk, images, labels, mask, target, neighbour, targeted_variant=Fal
         def tr(step, cost, f, sm, l2, was_active, S):
             trace(step=step, cost=float(cost[0]), f=float(f[0]), smooth=float(sm[0]), l2=float(l2[0]), w=S.w, m=S.m, v=S.v, dx0=S.dx0,
                   x0=S.x0, pred=S.pred)
-    out, exited, steps_done = _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr, starts_fn, 1, B, record=record)
-    return (out, int(exited[0]) + 1 if exited[0] >= 0 else steps_done) if return_steps else out
+    # (the reference leaves the halved lr on the attack object, target.py:123-125: a batch call does too)
+    out, steps_run = _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr, starts_fn, 1, B, record=record)
+    return (out, int(steps_run[0])) if return_steps else out
 
 
 def nu_attack_rooms(atk, images, labels, masks, target, neighbour, targeted_variant=False, trace=None, starts_fn=None, record=None):
@@ -325,24 +272,12 @@ def nu_attack_rooms(atk, images, labels, masks, target, neighbour, targeted_vari
     R, _, N = images.shape
     if R < 2:
         raise ValueError("nu_attack_rooms advances several rooms in lockstep; call nu_attack for one room")
-    lr_at_call = atk.lr
-    mk = None
-    if masks is not None:
-        mk = masks.detach().to(torch.bool).cpu().numpy() if isinstance(masks, torch.Tensor) else np.asarray(masks).astype(bool)
-        if mk.shape != (R, N):
-            raise ValueError("masks must be boolean [%d, %d], got shape %s" % (R, N, mk.shape))
-    elif targeted_variant:
-        raise ValueError("the targeted variant needs one mask per room")
     tr = None
     if trace is not None:
         def tr(step, cost, f, sm, l2, was_active, S):
             trace(step=step, cost=cost, f=f, smooth=sm, l2=l2, w=S.w, m=S.m, v=S.v, dx0=S.dx0, x0=S.x0, pred=S.pred,
                   active=was_active.copy())
-    try:
-        out, exited, steps_done = _nu_core(atk, images, labels, mk, target, neighbour, targeted_variant, tr, starts_fn, R, 1, record=record)
-    finally:
-        atk.lr = lr_at_call
-    return out, np.where(exited >= 0, exited + 1, steps_done).astype(np.int64)
+    return _nu_core(atk, images, labels, masks, target, neighbour, targeted_variant, tr, starts_fn, R, 1, record=record, restore_lr=True)
 
 
 def ctypes_off(t, n_floats):

@@ -30,43 +30,29 @@ import numpy as np
 import torch
 
 from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd.attacks.nu_windows import RoomsState, _bind, room_masks, window_loop
 from pointsecguard_amd.models.pointnet2_sem_seg import draw_fps_starts, upload
 
 from ._common import check_field, labels_to_device, psg_model
-from .nu import ADAM_EPS, BETA1, BETA2, CHUNK
+from .nu import ADAM_EPS, BETA1, BETA2
 from .pointnet import is_pointnet
 
 FIELD_CODES = {"coord": 1, "both": 2}          # PSG_NU_FIELD_COORD / PSG_NU_FIELD_BOTH of include/psg.h
 
 
-class _FieldState:
-    """Device buffers of one attack shape (G rooms of N points), kept with the model instance between calls."""
+class _FieldState(RoomsState):
+    """RoomsState of G rooms with the coordinate variable; no graph handle: the plan is rebuilt by every step."""
 
     def __init__(self, dev, G, N, neighbour):
-        f32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)       # noqa: E731
-        self.x0, self.ori, self.ori_xyz = f32(G, N, 9), f32(G, N, 3), f32(G, N, 3)
-        self.w, self.m, self.v = f32(G, N, 3), f32(G, N, 3), f32(G, N, 3)
+        super().__init__(dev, G, 1, N, neighbour, n_scal=5, n_graphs=0)     # scal rows: f, Smooth_rgb, L2_rgb, Smooth_xyz, L2_xyz
+        f32 = self._f32
+        self.ori_xyz, self.sgrad_xyz = f32(G, N, 3), f32(G, N, 3)
         self.delta, self.m_xyz, self.v_xyz = f32(G, N, 3), f32(G, N, 3), f32(G, N, 3)
-        self.logp, self.dlogp, self.dx0 = f32(G, N, 13), f32(G, N, 13), f32(G, N, 9)
-        self.sgrad, self.sgrad_xyz = f32(G, N, 3), f32(G, N, 3)
-        self.pred = torch.empty(G, N, device=dev, dtype=torch.int32)
-        self.labels = torch.empty(G, N, device=dev, dtype=torch.int32)
-        self.mask = torch.empty(G, N, device=dev, dtype=torch.uint8)
-        self.scal = f32(5, G)                                        # rows: f, Smooth_rgb, L2_rgb, Smooth_xyz, L2_xyz
-        self.nn_state = torch.empty(G, N, int(neighbour), device=dev, dtype=torch.int32)
-        self.hist = f32(CHUNK, 7, G)                                 # one window of history rows
-        self.active = torch.empty(G, device=dev, dtype=torch.uint8)
-        self.exit = torch.empty(G, device=dev, dtype=torch.int32)
-        self.n_mask = torch.empty(G, device=dev, dtype=torch.int32)
-        self.out = f32(G, 9, N)
+        self.logp, self.dlogp = f32(G, N, 13), f32(G, N, 13)
 
 
 def _state(net, dev, G, N, neighbour):
-    cache = net.__dict__.setdefault("_psg_nu_field_states", {})
-    key = (str(dev), G, N, int(neighbour))
-    if key not in cache:
-        cache[key] = _FieldState(dev, G, N, neighbour)
-    return cache[key]
+    return _FieldState.of(net, "_psg_nu_field_states", (str(dev), G, N, int(neighbour)), dev, G, N, neighbour)
 
 
 def check_network(model, field):
@@ -92,21 +78,8 @@ def nu_field_attack_rooms(atk, images, labels, masks, target, neighbour, targete
         raise ValueError("images must be [rooms, 9, points], got %s" % (tuple(images.shape),))
     if N % 64:
         raise ValueError("the lockstep f-loss sums need a point count that is a multiple of 64, got %d" % N)
-    mk = None
-    if masks is not None:
-        mk = masks.detach().to(torch.bool).cpu().numpy() if isinstance(masks, torch.Tensor) else np.asarray(masks).astype(bool)
-        if mk.shape != (G, N):
-            raise ValueError("masks must be boolean [%d, %d], got shape %s" % (G, N, mk.shape))
-        if targeted_variant and (mk.sum(axis=1) == 0).any():
-            raise ZeroDivisionError("tar_NU_attack: rooms %s have an empty mask (target.py:104: division by the mask count)"
-                                    % np.nonzero(mk.sum(axis=1) == 0)[0].tolist())
-    elif targeted_variant:
-        raise ValueError("the targeted variant needs one mask per room")
-    lr_at_call, coord_lr_at_call = atk.lr, atk.coord_lr
-    try:
-        return _field_core(atk, net, images, labels, mk, target, neighbour, targeted_variant, trace, starts_fn, record, field)
-    finally:
-        atk.lr, atk.coord_lr = lr_at_call, coord_lr_at_call
+    mk, n_mask = room_masks(masks, G, N, targeted_variant, "target.py:104")
+    return _field_core(atk, net, images, labels, mk, n_mask, target, neighbour, targeted_variant, trace, starts_fn, record, field)
 
 
 def nu_field_attack(atk, images, labels, mask, target, neighbour, targeted_variant=False, trace=None, starts_fn=None):
@@ -115,13 +88,11 @@ def nu_field_attack(atk, images, labels, mask, target, neighbour, targeted_varia
     if images.shape[0] != 1:
         raise ValueError("field=%r attacks one room per call (the reference's batch semantics are a colour-path property and are "
                          "not extended); use forward_rooms for %d rooms in lockstep" % (atk.field, images.shape[0]))
-    masks = None
-    if mask is not None:
-        masks = (mask.detach().to(torch.bool).cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask).astype(bool))[None]
+    masks = None if mask is None else (mask if isinstance(mask, torch.Tensor) else np.asarray(mask))[None]
     return nu_field_attack_rooms(atk, images, labels, masks, target, neighbour, targeted_variant, trace, starts_fn)[0]
 
 
-def _field_core(atk, net, images, labels, masks, target, neighbour, targeted_variant, trace, starts_fn, record, field):
+def _field_core(atk, net, images, labels, masks, n_mask, target, neighbour, targeted_variant, trace, starts_fn, record, field):
     dev = atk.device
     images = images.detach().to(dev).float().contiguous()
     G, _, N = images.shape
@@ -134,10 +105,8 @@ def _field_core(atk, net, images, labels, masks, target, neighbour, targeted_var
     use_target = targeted_variant and target is not None
     mode = 0 if not targeted_variant else (2 if use_target else 1)
     S.labels.copy_(labels_to_device(labels, dev).reshape(G, N))
-    n_mask = np.zeros(G)
     if masks is not None:
         S.mask.copy_(torch.from_numpy(masks.astype(np.uint8)))
-        n_mask = masks.sum(axis=1).astype(np.float64)
     S.n_mask.copy_(torch.from_numpy(n_mask.astype(np.int32)))
     _lib.call("psg_to_point_major", runtime.ptr(images), G, 9, N, runtime.ptr(S.x0), st())
     S.ori_xyz.copy_(S.x0[:, :, 0:3])
@@ -149,60 +118,37 @@ def _field_core(atk, net, images, labels, masks, target, neighbour, targeted_var
     S.active.fill_(1)
     S.exit.fill_(-1)
     c, coord_c = float(atk.c), float(atk.c if atk.coord_c is None else atk.coord_c)
-    lr = float(atk.lr)
-    coord_lr = lr if atk.coord_lr is None else float(atk.coord_lr)
     a = _lib.NuFieldArgs(
         model=model.handle.value, ws=ws.handle.value, G=G, N=N, mode=mode, use_target=int(use_target),
         target=int(target) if use_target else 0, neighbour=int(neighbour), field=FIELD_CODES[field], kappa=float(atk.kappa),
-        tsign=float(atk._targeted), c=c, coord_c=coord_c, beta1=BETA1, beta2=BETA2, eps=ADAM_EPS,
-        w=S.w.data_ptr(), m=S.m.data_ptr(), v=S.v.data_ptr(), delta=S.delta.data_ptr(), m_xyz=S.m_xyz.data_ptr(),
-        v_xyz=S.v_xyz.data_ptr(), ori_xyz=S.ori_xyz.data_ptr(), mask=S.mask.data_ptr() if masks is not None else None,
-        n_mask=S.n_mask.data_ptr(), x0=S.x0.data_ptr(), ori=S.ori.data_ptr(), labels=S.labels.data_ptr(), logp=S.logp.data_ptr(),
-        dlogp=S.dlogp.data_ptr(), dx0=S.dx0.data_ptr(), sgrad=S.sgrad.data_ptr(), sgrad_xyz=S.sgrad_xyz.data_ptr(),
-        pred=S.pred.data_ptr(), scal=S.scal.data_ptr(), nn_state=S.nn_state.data_ptr(), out=S.out.data_ptr(),
-        active=S.active.data_ptr(), exit_step=S.exit.data_ptr())
-    every_step = trace is not None or record is not None
-    exited = np.full(G, -1, np.int64)
-    step, adam_t = 0, 0
-    while step < atk.steps:
-        window_end = 1 if step == 0 else ((step - 1) // CHUNK + 1) * CHUNK + 1          # [0], [1..10], [11..20], ..
-        n_run = 1 if every_step else min(window_end, atk.steps) - step
+        tsign=float(atk._targeted), c=c, coord_c=coord_c, beta1=BETA1, beta2=BETA2, eps=ADAM_EPS)
+    _bind(a, S, "w m v delta m_xyz v_xyz ori_xyz n_mask x0 ori labels logp dlogp dx0 sgrad sgrad_xyz pred scal nn_state out active "
+                "exit_step=exit")
+    a.mask = S.mask.data_ptr() if masks is not None else None
+
+    def enqueue(step, n_run, adam_t):
+        # the FPS draws of a window are made together; then one psg_pn2_nu_field_step call per step (the plan follows the points)
         if starts_fn is not None:
             starts = upload(torch.cat([torch.as_tensor(starts_fn(step + i, 1), dtype=torch.int32).reshape(1, 4, G) for i in range(n_run)]), dev)
         else:
             starts = upload(draw_fps_starts(G, N, n_run), dev)
+        a.lr = float(atk.lr)
+        a.coord_lr = a.lr if atk.coord_lr is None else float(atk.coord_lr)
         for i in range(n_run):
             a.step, a.adam_t, a.warm = step + i, adam_t + i + 1, 1 if step + i > 0 else 0
-            a.lr, a.coord_lr = lr, coord_lr
             a.starts = starts.data_ptr() + 4 * 4 * G * i
             a.hist = S.hist.data_ptr() + 4 * 7 * G * i
             _lib.call("psg_pn2_nu_field_step", ctypes.byref(a), st())
-        adam_t += n_run
-        last = step + n_run - 1
-        got = torch.cat([S.hist[:n_run].reshape(-1), S.exit.float()]).cpu().numpy().astype(np.float64)     # ONE read-back
-        hrows, exited = got[:-G].reshape(n_run, 7, G), got[-G:].astype(np.int64)
-        if every_step:
-            was_active = (exited < 0) | (exited >= last)
-            row = hrows[0]
-            if trace is not None:
-                cost = row[2] + c * (row[3] + row[4]) + coord_c * (row[5] + row[6])
-                trace(step=last, cost=cost, f=row[2], smooth=row[3], l2=row[4], smooth_xyz=row[5], l2_xyz=row[6],
-                      active=was_active.copy(), S=S)
-            if record is not None:
-                record(last, row.copy(), was_active.copy())
-        step = last + 1
-        if not (exited < 0).any():
-            break
-        if targeted_variant and last > 0 and last % 50 == 0:       # target.py:123-125: halve, NEW optimiser (moments reset)
-            atk.lr = atk.lr / 2
-            if atk.coord_lr is not None:
-                atk.coord_lr = atk.coord_lr / 2
-            lr = float(atk.lr)
-            coord_lr = lr if atk.coord_lr is None else float(atk.coord_lr)
-            adam_t = 0
-            for t in (S.m, S.v, S.m_xyz, S.v_xyz):
-                t.zero_()
-    out = S.out.clone()                                  # (the caller owns what it gets; the state buffer is reused)
-    for g in np.nonzero(exited < 0)[0]:                  # rooms that ran to the cap: the current image
-        _lib.call("psg_to_channel_major", runtime.ptr(S.x0[g:g + 1]), 1, 9, N, runtime.ptr(out[g:g + 1]), st())
-    return out, np.where(exited >= 0, exited + 1, step).astype(np.int64)
+
+    def on_step(s_i, row, was_active, exited):
+        if trace is not None:
+            cost = row[2] + c * (row[3] + row[4]) + coord_c * (row[5] + row[6])
+            trace(step=s_i, cost=cost, f=row[2], smooth=row[3], l2=row[4], smooth_xyz=row[5], l2_xyz=row[6],
+                  active=was_active.copy(), S=S)
+        if record is not None:
+            record(s_i, row.copy(), was_active.copy())
+
+    every_step = trace is not None or record is not None             # (here `record` shortens the windows too)
+    out, steps_run, _ = window_loop(atk, S, 1, enqueue, targeted_variant=targeted_variant, on_step=on_step if every_step else None,
+                                    one_step=every_step, lr_names=("lr", "coord_lr"), moments=(S.m, S.v, S.m_xyz, S.v_xyz))
+    return out, steps_run

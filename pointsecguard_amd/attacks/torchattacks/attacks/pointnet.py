@@ -8,7 +8,8 @@ NB_attack / tar_NB_attack: one fused, stream-ordered libpsg call (psg_pointnet_n
 CE-on-log-probs gradient, input-gradient backward, sign step + L-inf projection).  This network draws no random
 numbers, so unlike the PointNet++ path there are no FPS starts.
 
-NU_attack / tar_NU_attack: the window loop of nu.py (`_nu_core`, shared with PointNet++): steps [0], [1..10], [11..20], ..
+NU_attack / tar_NU_attack: the window loop of attacks/nu_windows.py with nu.py's callables (`_nu_core`, shared with
+PointNet++: no geometry plan here, the restart is one psg_nu_restart_rooms launch): steps [0], [1..10], [11..20], ..
 are one psg_pointnet_nu_window call each, replayed as a hipGraph from the third full window on, with one read-back per
 window; `forward` is one attack on the batch (G = 1, rows = B), `forward_rooms` R one-room attacks in lockstep.  The
 reference's control flow (PointNet/attacks/torchattacks/attacks/nontarget.py:52-105, target.py:62-133) sits between the

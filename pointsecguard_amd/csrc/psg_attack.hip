@@ -1103,17 +1103,10 @@ static int nu_window_steps(const psg_nu_window_args *a, const float *dconsts_row
         if ((rc = psg_smooth_knn_rooms(a->x0 + 3, 9, (size_t)N * 9, a->ori, 3, (size_t)N * 3, G, N, a->neighbour, a->scal + G, a->sgrad,
                                        a->nn_state, (i > 0 || a->warm_first) ? 1 : 0, stream)))
             break;
-        g_nu_dconsts = dconsts_rows ? dconsts_rows + 4 * i : nullptr;
-        rc = rooms ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr,
-                                            a->beta1, a->beta2, a->eps, adam_t, B, N, a->active, a->scal + 2 * G, stream)
-                   : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr, a->beta1,
-                                      a->beta2, a->eps, adam_t, B, N, a->scal + 2, stream);
-        if (rc == PSG_OK)
-            rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, a->rows, N,
-                                   a->mode, a->scal, a->hist + (size_t)i * 5 * G, a->x0, a->out, a->active, a->exit_step, step, stream);
-        g_nu_dconsts = nullptr;
+        psg::NuStepConsts consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
+        rc = psg::nu_colour_adam(a, a->c_smooth, a->c_l2, a->rows, adam_t, stream);
+        if (rc == PSG_OK) rc = psg::nu_latch(a, a->rows, a->hist + (size_t)i * 5 * G, step, stream);
     }
-    g_nu_dconsts = nullptr;
     return rc;
 }
 

@@ -127,6 +127,33 @@ int nu_graph_window(psg_nu_graph *graph, const void *key, size_t key_bytes, uint
 // read their step constants from this device row.
 void nu_set_step_consts(const float *row);
 const float *nu_step_consts();
+// The step walkers set a step's row through this scope: the row holds from here to the end of the enclosing block and is
+// cleared on every way out of it.
+struct NuStepConsts {
+    explicit NuStepConsts(const float *row) { nu_set_step_consts(row); }
+    ~NuStepConsts() { nu_set_step_consts(nullptr); }
+    NuStepConsts(const NuStepConsts &) = delete;
+    NuStepConsts &operator=(const NuStepConsts &) = delete;
+};
+// The tail every NU step walker ends in, over its own argument block `a` (the blocks share these field names).
+// Adam step on the colour variable of G attacks of `rows` batch rows: the lockstep form for two attacks and more; one attack
+// is the batch form - the same arithmetic (its L2 sum at scal + 2 * G = scal + 2), and what it runs past an exit is discarded
+// with the latch's snapshot either way.
+template <typename Args> int nu_colour_adam(const Args *a, float c_smooth, float c_l2, int rows, int adam_t, psg_stream stream)
+{
+    const int G = a->G, B = G * rows;
+    return G > 1 ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, c_smooth, c_l2, a->lr, a->beta1,
+                                          a->beta2, a->eps, adam_t, B, a->N, a->active, a->scal + 2 * G, stream)
+                 : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, c_smooth, c_l2, a->lr, a->beta1, a->beta2,
+                                    a->eps, adam_t, B, a->N, a->scal + 2 * G, stream);
+}
+// statistics, history row `hist_step` and exit latch of step `step`
+template <typename Args> int nu_latch(const Args *a, int rows, float *hist_step, int step, psg_stream stream)
+{
+    return psg_nu_step_latch(a->pred, a->labels, a->use_target ? a->target : 0, a->mode ? a->mask : nullptr,
+                             a->mode ? a->n_mask : nullptr, a->G, rows, a->N, a->mode, a->scal, hist_step, a->x0, a->out, a->active,
+                             a->exit_step, step, stream);
+}
 // scal rows 3, 4 (Smooth_xyz, L2_xyz of the coordinate-field NU steps) into rows 5, 6 of hist_step [7][G], zeroed (psg_attack.hip)
 int nu_field_hist_tail(float *scal, float *hist_step, int G, hipStream_t st);
 

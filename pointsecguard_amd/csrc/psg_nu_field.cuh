@@ -279,20 +279,12 @@ extern "C" int psg_pn2_nu_field_step(const psg_nu_field_args *a, psg_stream stre
     if ((rc = psg_smooth_knn_xyz_rooms(a->x0, 9, (size_t)N * 9, a->ori_xyz, 3, (size_t)N * 3, G, N, a->neighbour, a->scal + 3 * G, a->sgrad_xyz,
                                        a->active, nullptr, stream)))
         return rc;
-    if (both) {
-        // (psg_nu_adam_step_rooms serves two rooms and more; one room is the batch-of-one call of the same kernel)
-        rc = G > 1 ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c, a->c, a->lr, a->beta1, a->beta2,
-                                            a->eps, a->adam_t, G, N, a->active, a->scal + 2 * G, stream)
-                   : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c, a->c, a->lr, a->beta1, a->beta2, a->eps,
-                                      a->adam_t, 1, N, a->scal + 2, stream);
-        if (rc) return rc;
-    }
+    // (no step-constants row: this step is never captured, its kernels take the constants from their arguments)
+    if (both && (rc = psg::nu_colour_adam(a, a->c, a->c, 1, a->adam_t, stream))) return rc;
     if ((rc = psg_nu_coord_adam_step_rooms(a->delta, a->m_xyz, a->v_xyz, a->mask, a->dx0, a->sgrad_xyz, a->coord_c, a->coord_lr, a->beta1,
                                            a->beta2, a->eps, a->adam_t, G, N, a->active, a->scal + 4 * G, stream)))
         return rc;
-    if ((rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, 1, N, a->mode,
-                                a->scal, a->hist, a->x0, a->out, a->active, a->exit_step, a->step, stream)))
-        return rc;
+    if ((rc = psg::nu_latch(a, 1, a->hist, a->step, stream))) return rc;
     hipLaunchKernelGGL(nu_field_hist_tail_kernel, dim3(psg::ceil_div(2 * G, 256)), dim3(256), 0, (hipStream_t)stream, a->scal, a->hist, G);
     PSG_LAUNCH_CHECK();
     return PSG_OK;

@@ -700,7 +700,7 @@ static int rla_nu_window_steps(const psg_rla_nu_window_args *a, const float *row
         const bool tail = i == a->n_steps;
         if ((rc = psg_rla_nu_color_clouds(a->xs, a->dws, a->mask, a->active, G, N, a->feat, a->dist2, a->partials, stream))) break;
         if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
-        psg::nu_set_step_consts(rows ? rows + 4 * i : nullptr);
+        psg::NuStepConsts consts(rows ? rows + 4 * i : nullptr);
         // (a captured window serves every later one: there the latch's own `step >= 1` rule keeps the start from exiting)
         rc = psg_rla_nu_latch_clouds(a->logits, a->labels, a->ys, a->mask, a->n_mask, a->feat, a->dist2, G, N, a->mode, a->num, a->den,
                                      t - 1, (rows || t - 1 >= 1) ? 1 : 0, tail ? 1 : 0, a->hist + (size_t)i * 3 * G, a->pred, a->out_adv,
@@ -711,9 +711,7 @@ static int rla_nu_window_steps(const psg_rla_nu_window_args *a, const float *row
                 rc = psg_rla_nu_adam_clouds(a->xs, a->dws, a->m, a->v, a->mask, a->active, a->feat, a->dfeat, a->dist2, G, N, a->cs, a->lr, t,
                                             stream);
         }
-        psg::nu_set_step_consts(nullptr);
     }
-    psg::nu_set_step_consts(nullptr);
     return rc;
 }
 
@@ -798,18 +796,18 @@ static int rla_tbim_window_steps(const psg_rla_tbim_window_args *a, const float 
     for (int i = 0; i < a->n_steps && rc == PSG_OK; ++i) {
         const int final = (a->final && i == a->n_steps - 1) ? 1 : 0;
         if ((rc = psg_rla_forward(a->model, a->ws, a->feat, a->logits, stream))) break;
-        psg::nu_set_step_consts(rows ? rows + 4 * i : nullptr);
-        rc = psg_rla_tbim_latch_clouds(a->logits, a->labels, a->hit_ys, a->mask, a->n_mask, G, N, a->num, a->den, a->it0 + i, final,
-                                       a->hist + (size_t)i * 3 * G, a->pred, a->out_pred, a->out_stats, a->active, a->leaving, a->exit_step,
-                                       a->scratch, stream);
-        psg::nu_set_step_consts(nullptr);
+        {
+            psg::NuStepConsts consts(rows ? rows + 4 * i : nullptr);
+            rc = psg_rla_tbim_latch_clouds(a->logits, a->labels, a->hit_ys, a->mask, a->n_mask, G, N, a->num, a->den, a->it0 + i, final,
+                                           a->hist + (size_t)i * 3 * G, a->pred, a->out_pred, a->out_stats, a->active, a->leaving,
+                                           a->exit_step, a->scratch, stream);
+        }
         if (rc == PSG_OK && (rc = psg_rla_colper_grad_masked(a->logits, a->loss_ys, a->mask, a->sign, G * N, a->dlogits, nullptr, stream)) == PSG_OK &&
             (rc = psg_rla_backward(a->model, a->ws, a->dlogits, a->dfeat, stream)) == PSG_OK &&
             (rc = psg_rla_bim_step_clouds(a->feat, a->dfeat, a->ori, a->active, G, N, a->eps, a->alpha, a->l2_metric, a->norms, a->delta,
                                           stream)) == PSG_OK)
             rc = psg_rla_tbim_retire_clouds(a->feat, G, N, final, a->out_adv, a->active, a->leaving, stream);
     }
-    psg::nu_set_step_consts(nullptr);
     return rc;
 }
 

@@ -1678,6 +1678,38 @@ extern "C" int psg_gcn_backward(psg_gcn_model *m, psg_gcn_ws *ws, const float *d
 }
 
 // ====================================================================================== NB attack
+// The `iters` iterations of an NB attack (psg_gcn_nb_attack, psg_gcn_nb_attack_field).  The first iteration runs eagerly (it
+// also sets kernel attributes outside any capture).  The interior iterations 1 .. iters-2 enqueue exactly the same ~300 short
+// launches with the same arguments: where the caller allows (`may_capture`) and at least two of them are left, they are
+// captured once into `slot` (kept in the workspace with its key: `same_key()` compares it, `store_key()` records it) and
+// replayed, which removes most of the per-launch cost that bounds a single-room ResGCN iteration; a capture that fails - it
+// is not possible on the legacy default stream - leaves them eager, counted.  The last iteration differs (it returns the
+// un-projected step) and is eager again.
+template <typename Iteration, typename SameKey, typename StoreKey>
+static int nb_iterations(psg::GraphSlot &slot, hipStream_t st, int iters, bool may_capture, Iteration &&iteration, SameKey &&same_key,
+                         StoreKey &&store_key)
+{
+    int rc;
+    if ((rc = iteration(iters == 1))) return rc;
+    int it = 1;
+    if (may_capture && iters - 1 - it >= 2) {
+        if (!same_key()) PSG_CHECK_HIP(slot.forget(st));
+        if (!slot.exec && !slot.capture_failed) {
+            slot.capture(st, [&] { return iteration(false); });
+            store_key();
+        }
+        if (slot.exec) {
+            PSG_CHECK_HIP(slot.replay(st, iters - 1 - it));
+            it = iters - 1;
+        } else {
+            slot.note_eager(iters - 1 - it);
+        }
+    }
+    for (; it < iters; ++it)
+        if ((rc = iteration(it == iters - 1))) return rc;
+    return PSG_OK;
+}
+
 // colper.NB_attack (ResGCN/sem_seg_dense/attacks/torchattacks/attacks/colper.py:17-39): CrossEntropyLoss()
 // (mean over all B*N points) on the logits, sign ascent on the colour channels, L-inf projection; the
 // returned colours are the un-projected last step (the projection is not written back after the loop).
@@ -1694,43 +1726,25 @@ extern "C" int psg_gcn_nb_attack(psg_gcn_model *m, psg_gcn_ws *ws, const float *
     hipLaunchKernelGGL(extract_color3_kernel, dim3(ceil_div((int)(R * 3), 256)), dim3(256), 0, st, ws->x0, ws->ori, R);
     PSG_LAUNCH_CHECK();
     PSG_CHECK_HIP(hipMemcpyAsync(ws->nb_labels, labels, R * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    // the attack moves colours only: the head's kNN graph on xyz (architecture.py:59) is the same in every iteration, so the
+    // first forward builds it and the later ones keep it
+    struct Unfreeze { psg_gcn_ws *w; ~Unfreeze() { w->head_graph_frozen = false; } } unfreeze{ws};
+    ws->head_graph_frozen = false;
     auto iteration = [&](bool last) -> int {
         int r;
         if ((r = psg_gcn_forward(m, ws, ws->x0, ws->logits, st))) return r;
+        ws->head_graph_frozen = true;
         if ((r = psg_ce_logp_grad(ws->logits, ws->nb_labels, 0, (int)R, (int)R, NCLS, 1.0f / (float)R, ws->dlogits, nullptr, st)))
             return r;
         if ((r = psg_gcn_backward(m, ws, ws->dlogits, ws->dx0, st))) return r;
         return psg_pgd_step(ws->x0, ws->dx0, ws->ori, nullptr, B, N, alpha, eps, 1.0f, last ? 1 : 0, st);
     };
-    int it = 0;
-    // The first iteration runs eagerly (it also sets kernel attributes outside any capture).  The interior
-    // iterations 1 .. iters-2 enqueue exactly the same ~300 short launches with the same arguments: they are captured
-    // once into a hipGraph (kept in the workspace) and replayed, which removes most of the per-launch cost that
-    // bounds a single-room ResGCN iteration.  Capture is not possible on the legacy default stream; the loop then
-    // simply stays eager.  The last iteration differs (it returns the un-projected step) and is eager again.
-    ws->head_graph_frozen = false;
-    if ((rc = iteration(iters == 1))) return rc;
-    it = 1;
-    // the attack moves colours only: the head's kNN graph on xyz (architecture.py:59) is the same in every iteration
-    struct Unfreeze { psg_gcn_ws *w; ~Unfreeze() { w->head_graph_frozen = false; } } unfreeze{ws};
-    ws->head_graph_frozen = true;
     static const bool use_graph = !((psg::env_int("PSG_GCN_NO_GRAPH", 0) != 0)) && !trace_sync_enabled();   // (the tracer synchronises after every launch)
-    if (use_graph && !ws->prof.on && iters - 1 - it >= 2) {
-        const bool same_key = ws->nb_model_gen == m->gen && ws->nb_eps == eps && ws->nb_alpha == alpha && ws->nb_fixed == ws->fixed_graphs;
-        if (!same_key) PSG_CHECK_HIP(ws->nb.forget(st));
-        if (!ws->nb.exec && !ws->nb.capture_failed) {
-            ws->nb.capture(st, [&] { return iteration(false); });
-            ws->nb_model_gen = m->gen; ws->nb_eps = eps; ws->nb_alpha = alpha; ws->nb_fixed = ws->fixed_graphs;
-        }
-        if (ws->nb.exec) {
-            PSG_CHECK_HIP(ws->nb.replay(st, iters - 1 - it));
-            it = iters - 1;
-        } else {
-            ws->nb.note_eager(iters - 1 - it);
-        }
-    }
-    for (; it < iters; ++it)
-        if ((rc = iteration(it == iters - 1))) return rc;
+    if ((rc = nb_iterations(
+             ws->nb, st, iters, use_graph && !ws->prof.on, iteration,
+             [&] { return ws->nb_model_gen == m->gen && ws->nb_eps == eps && ws->nb_alpha == alpha && ws->nb_fixed == ws->fixed_graphs; },
+             [&] { ws->nb_model_gen = m->gen; ws->nb_eps = eps; ws->nb_alpha = alpha; ws->nb_fixed = ws->fixed_graphs; })))
+        return rc;
     return psg_to_channel_major(ws->x0, B, 9, N, adv_out, st);
 }
 
@@ -1757,19 +1771,10 @@ static int gcn_nu_window_steps(const psg_gcn_nu_window_args *a, const float *dco
         if ((rc = psg_smooth_knn_sym_rooms(a->x0 + 3, 9, (size_t)N * 9, G, N, a->neighbour, a->scal + G, a->sgrad, a->active,
                                            a->nn_state, stream)))
             break;
-        nu_set_step_consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
-        // (psg_nu_adam_step_rooms is the lockstep form for two rooms and more; one room is the batch form at B = 1: the same
-        // arithmetic, and its speculative steps past the exit are discarded with the latch's snapshot either way)
-        rc = G > 1 ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr,
-                                            a->beta1, a->beta2, a->eps, adam_t, G, N, a->active, a->scal + 2 * G, stream)
-                   : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr, a->beta1,
-                                      a->beta2, a->eps, adam_t, 1, N, a->scal + 2, stream);
-        if (rc == PSG_OK)
-            rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, 1, N,
-                                   a->mode, a->scal, a->hist + (size_t)i * 5 * G, a->x0, a->out, a->active, a->exit_step, step, stream);
-        nu_set_step_consts(nullptr);
+        psg::NuStepConsts consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
+        rc = psg::nu_colour_adam(a, a->c_smooth, a->c_l2, 1, adam_t, stream);
+        if (rc == PSG_OK) rc = psg::nu_latch(a, 1, a->hist + (size_t)i * 5 * G, step, stream);
     }
-    nu_set_step_consts(nullptr);
     return rc;
 }
 
@@ -1842,31 +1847,20 @@ extern "C" int psg_gcn_nb_attack_field(psg_gcn_model *m, psg_gcn_ws *ws, const f
             return r;
         return both ? psg_pgd_step_field(ws->x0, ws->dx0, ws->ori, nullptr, B, N, 3, alpha, eps, 1.0f, last ? 1 : 0, st) : PSG_OK;
     };
-    // first and last iteration eager, the interior ones captured once (into ws->nbf) and replayed, as in psg_gcn_nb_attack;
-    // the captured sequence is a single chain on `st`.  On the legacy default stream (no capture there), under the
-    // launch tracer and while the workspace is profiling, the loop stays eager.
-    int it = 0;
-    if ((rc = iteration(iters == 1))) return rc;
-    it = 1;
+    // the interior iterations are captured into ws->nbf (a single chain on `st`).  On the legacy default stream (no capture
+    // there), under the launch tracer and while the workspace is profiling, the loop stays eager.
     static const bool use_graph = !((psg::env_int("PSG_GCN_NO_GRAPH", 0) != 0)) && !trace_sync_enabled();
-    if (use_graph && st && !ws->prof.on && iters - 1 - it >= 2) {
-        const bool same_key = ws->nbf_model_gen == m->gen && ws->nbf_field == field && ws->nbf_eps == eps && ws->nbf_alpha == alpha &&
-                              ws->nbf_ceps == coord_eps && ws->nbf_calpha == coord_alpha && ws->nbf_fixed == ws->fixed_graphs;
-        if (!same_key) PSG_CHECK_HIP(ws->nbf.forget(st));
-        if (!ws->nbf.exec && !ws->nbf.capture_failed) {
-            ws->nbf.capture(st, [&] { return iteration(false); });
-            ws->nbf_model_gen = m->gen; ws->nbf_field = field; ws->nbf_eps = eps; ws->nbf_alpha = alpha;
-            ws->nbf_ceps = coord_eps; ws->nbf_calpha = coord_alpha; ws->nbf_fixed = ws->fixed_graphs;
-        }
-        if (ws->nbf.exec) {
-            PSG_CHECK_HIP(ws->nbf.replay(st, iters - 1 - it));
-            it = iters - 1;
-        } else {
-            ws->nbf.note_eager(iters - 1 - it);
-        }
-    }
-    for (; it < iters; ++it)
-        if ((rc = iteration(it == iters - 1))) return rc;
+    if ((rc = nb_iterations(
+             ws->nbf, st, iters, use_graph && st && !ws->prof.on, iteration,
+             [&] {
+                 return ws->nbf_model_gen == m->gen && ws->nbf_field == field && ws->nbf_eps == eps && ws->nbf_alpha == alpha &&
+                        ws->nbf_ceps == coord_eps && ws->nbf_calpha == coord_alpha && ws->nbf_fixed == ws->fixed_graphs;
+             },
+             [&] {
+                 ws->nbf_model_gen = m->gen; ws->nbf_field = field; ws->nbf_eps = eps; ws->nbf_alpha = alpha;
+                 ws->nbf_ceps = coord_eps; ws->nbf_calpha = coord_alpha; ws->nbf_fixed = ws->fixed_graphs;
+             })))
+        return rc;
     return psg_to_channel_major(ws->x0, B, 9, N, adv_out, st);
 }
 
@@ -1897,22 +1891,16 @@ static int gcn_nu_field_window_steps(const psg_gcn_nu_field_window_args *a, cons
         if ((rc = psg_smooth_knn_xyz_sym_rooms(a->x0, 9, (size_t)N * 9, G, N, a->neighbour, a->scal + 3 * G, a->sgrad_xyz, a->active,
                                                a->nn_xyz, stream)))
             break;
-        nu_set_step_consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
-        if (both)
-            rc = G > 1 ? psg_nu_adam_step_rooms(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr,
-                                                a->beta1, a->beta2, a->eps, adam_t, G, N, a->active, a->scal + 2 * G, stream)
-                       : psg_nu_adam_step(a->w, a->m, a->v, a->mask, a->dx0, a->x0, a->ori, a->sgrad, a->c_smooth, a->c_l2, a->lr, a->beta1,
-                                          a->beta2, a->eps, adam_t, 1, N, a->scal + 2, stream);
-        if (rc == PSG_OK)
-            rc = psg_nu_coord_adam_step_rooms_w(a->delta, a->mx, a->vx, a->mask, a->dx0, a->sgrad_xyz, a->c_smooth_xyz, a->c_l2_xyz,
-                                                a->coord_lr, a->beta1, a->beta2, a->eps, adam_t, G, N, a->active, a->scal + 4 * G, stream);
-        if (rc == PSG_OK)
-            rc = psg_nu_step_latch(a->pred, a->labels, f_target, a->mode ? a->mask : nullptr, a->mode ? a->n_mask : nullptr, G, 1, N,
-                                   a->mode, a->scal, hist, a->x0, a->out, a->active, a->exit_step, step, stream);
-        nu_set_step_consts(nullptr);
+        {
+            psg::NuStepConsts consts(dconsts_rows ? dconsts_rows + 4 * i : nullptr);
+            if (both) rc = psg::nu_colour_adam(a, a->c_smooth, a->c_l2, 1, adam_t, stream);
+            if (rc == PSG_OK)
+                rc = psg_nu_coord_adam_step_rooms_w(a->delta, a->mx, a->vx, a->mask, a->dx0, a->sgrad_xyz, a->c_smooth_xyz, a->c_l2_xyz,
+                                                    a->coord_lr, a->beta1, a->beta2, a->eps, adam_t, G, N, a->active, a->scal + 4 * G, stream);
+            if (rc == PSG_OK) rc = psg::nu_latch(a, 1, hist, step, stream);
+        }
         if (rc == PSG_OK) rc = psg::nu_field_hist_tail(a->scal, hist, G, (hipStream_t)stream);
     }
-    nu_set_step_consts(nullptr);
     return rc;
 }
 

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd.attacks.nu_windows import _bind, destroy_graphs, new_graphs  # noqa: F401  (_bind: the field modules' too)
 from pointsecguard_amd.attacks.torchattacks.attacks._common import check_field
 from pointsecguard_amd.randla import network
 
@@ -189,50 +190,40 @@ class _CloudsState:
         self.active, self.leaving = (torch.zeros(G, dtype=torch.uint8, device=dev) for _ in range(2))
         self.exit = i32(G)
         # two handles: the full windows, and a full window that is also the last one (it carries the tail evaluation)
-        self.graph, self.graph_tail = ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph))
-        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph_tail))
+        self.graph, self.graph_tail = new_graphs(2)
 
     def __del__(self):
-        try:
-            for g in (self.graph, self.graph_tail):
-                if g:
-                    _lib.load().psg_nu_graph_destroy(g)
-        except Exception:
-            pass
+        destroy_graphs((getattr(self, "graph", None), getattr(self, "graph_tail", None)))
 
 
-def _bind(win, S, fields):
-    """pointers of the state's tensors into the argument block: `fields` = block field names, `field=attribute` where the
-    state calls the tensor otherwise"""
-    for item in fields.split():
-        field, _, attr = item.partition("=")
-        setattr(win, field, getattr(S, attr or field).data_ptr())
-
-
-def _run_windows(entry, win, S, first, cap, chunk, set_window, hook):
+def _run_windows(entry, win, S, first, cap, chunk, set_window, hook, read_back=True):
     """The window loop of the lockstep attacks: steps first .. cap in windows of `chunk` (at most CHUNK), the last one cut at
     the cap, through the library's `entry`.  set_window(first step, steps, last) sets the window's fields of `win` and returns
     the number of history rows it writes; after the window's one read-back (those rows and the exit steps)
-    hook(first step, steps, last, S, rows [rows, G, 3]) is called; the loop ends after the window in which the last cloud
-    exits.  Only a full CHUNK window gets a graph handle (cut windows run eagerly): S.graph, or S.graph_tail when it is
-    also the last.  -> (the row count of every window, steps taken per cloud [G]: the exit step, or the cap, counted from
+    hook(first step, steps, last, S, rows [rows, G, columns of S.hist]) is called; the loop ends after the window in which
+    the last cloud exits.  read_back=False (the untargeted field BIM: every cloud takes every step): nothing returns to the
+    host, no hook.  A state with graph handles passes one to the entry point, for a full CHUNK window only (cut windows run
+    eagerly): S.graph, or S.graph_tail when it is also the last; the field windows' states have none and their entry points
+    take none.  -> (the row count of every window, steps taken per cloud [G]: the exit step, or the cap, counted from
     `first`)."""
     chunk = max(1, min(int(chunk), CHUNK))
-    G = S.exit.shape[0]
+    G, cols = S.exit.shape[0], S.hist.shape[2]
     exited, rows_run = np.full(G, -1, np.int64), []
     t0 = first
     while t0 <= cap:
         n_run = min(chunk, cap - t0 + 1)
         last = t0 + n_run - 1 == cap
         rows = set_window(t0, n_run, last)
-        graph = None if n_run != CHUNK else (S.graph_tail if last else S.graph)
-        _lib.call(entry, ctypes.byref(win), graph, runtime.stream())
-        back = torch.cat([S.hist[:rows].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
-        exited = back[rows * G * 3:].astype(np.int64)
+        if hasattr(S, "graph"):
+            _lib.call(entry, ctypes.byref(win), None if n_run != CHUNK else (S.graph_tail if last else S.graph), runtime.stream())
+        else:
+            _lib.call(entry, ctypes.byref(win), runtime.stream())
         rows_run.append(rows)
-        if hook is not None:
-            hook(t0, n_run, last, S, back[:rows * G * 3].reshape(rows, G, 3))
+        if read_back:
+            back = torch.cat([S.hist[:rows].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
+            exited = back[rows * G * cols:].astype(np.int64)
+            if hook is not None:
+                hook(t0, n_run, last, S, back[:rows * G * cols].reshape(rows, G, cols))
         t0 += n_run
         if (exited >= 0).all():
             break

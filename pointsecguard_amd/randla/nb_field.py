@@ -13,12 +13,10 @@ After a run: `last_adv_xyz` [G, N, 3] the moved positions, `last_dist_xyz` [G] t
 colours (targeted pair; the untargeted one returns them), `last_steps` [G] the gradient steps taken (targeted pair).  The tuples'
 `new_dists` stays the colour distance (0.0 under "coord"), as for `batch_attack`.  The state's workspace is left on
 `last_adv_xyz`, so a forward on the adversarial features evaluates the attack."""
-import ctypes
-
 import numpy as np
 import torch
 
-from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd import _lib
 from pointsecguard_amd.randla import attack, network
 
 CHUNK = attack.CHUNK
@@ -47,31 +45,6 @@ class _FieldCloudsState:
         self.out_adv, self.out_adv_xyz, self.out_stats = f32(R, 3), f32(R, 3), f32(G, 3)
         self.active, self.leaving = (torch.zeros(G, dtype=torch.uint8, device=dev) for _ in range(2))
         self.exit = i32(G)
-
-
-def _run_windows(win, S, cap, chunk, read_back, hook):
-    """attack._run_windows for the field window (no graph handle): iterations 0 .. cap in windows of `chunk` (at most CHUNK), the
-    last one cut at the cap and `final`.  read_back (the targeted pair): one read-back per window, the history rows and the exit
-    steps, then hook(first iteration, iterations, final, S, rows [iterations, G, 3]); the loop ends after the window in which the
-    last cloud left.  Without it nothing returns to the host.  -> gradient steps per cloud [G]."""
-    chunk = max(1, min(int(chunk), CHUNK))
-    G = S.exit.shape[0]
-    exited = np.full(G, -1, np.int64)
-    it0 = 0
-    while it0 <= cap:
-        n_run = min(chunk, cap - it0 + 1)
-        final = it0 + n_run - 1 == cap
-        win.n_steps, win.it0, win.final = n_run, it0, 1 if final else 0
-        _lib.call("psg_rla_bim_field_window", ctypes.byref(win), runtime.stream())
-        if read_back:
-            back = torch.cat([S.hist[:n_run].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
-            exited = back[n_run * G * 3:].astype(np.int64)
-            if hook is not None:
-                hook(it0, n_run, final, S, back[:n_run * G * 3].reshape(n_run, G, 3))
-        it0 += n_run
-        if read_back and (exited >= 0).all():
-            break
-    return np.where(exited >= 0, exited, cap) + 1
 
 
 class _NbField:
@@ -133,7 +106,14 @@ class _NbField:
             attack._bind(win, S, "ori=xs norms")
         if mode:
             attack._bind(win, S, "mask n_mask hit_ys loss_ys=ys hist leaving exit_step=exit")
-        steps = _run_windows(win, S, self.iteration, self.chunk, bool(mode), self.window_hook)
+
+        def set_window(it0, n_run, final):               # final, the cap: its last step snapshots the clouds still running
+            win.n_steps, win.it0, win.final = n_run, it0, 1 if final else 0
+            return n_run
+
+        # iterations 0 .. iteration; the targeted pair (mode 1) reads back once per window, the untargeted pair nothing
+        _, steps = attack._run_windows("psg_rla_bim_field_window", win, S, 0, self.iteration, self.chunk, set_window, self.window_hook,
+                                       read_back=bool(mode))
         if mode:
             self.last_steps = steps
         self.last_adv = S.out_adv.reshape(G, n, 3).clone()

@@ -13,12 +13,10 @@ on the device in integers.  `batch_attack` is that loop at G = 1.  No hipGraph: 
 After a run: `last_adv_xyz` [G, N, 3] the moved positions, `last_dist_xyz` [G] their l_2 distances, `last_adv` [G, N, 3] the
 colours, `last_steps` [G] the steps taken (`batch_attack`: the two position / colour tensors without the cloud axis).  The
 tuples' `new_dists` stays the colour distance (0.0 under "coord"), as for the BIM family."""
-import ctypes
-
 import numpy as np
 import torch
 
-from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd import _lib
 from pointsecguard_amd.attacks.torchattacks.attacks._common import check_field
 from pointsecguard_amd.randla import attack, network
 
@@ -50,28 +48,6 @@ class _FieldCloudsState:
         self.hist = f32(CHUNK + 1, G, 4)
         self.active = torch.zeros(G, dtype=torch.uint8, device=dev)
         self.exit = i32(G)
-
-
-def _run_windows(win, S, first, cap, chunk, set_window, hook):
-    """attack._run_windows for the field window: 4-column history rows, no graph handle.  One read-back per window."""
-    chunk = max(1, min(int(chunk), CHUNK))
-    G = S.exit.shape[0]
-    exited, rows_run = np.full(G, -1, np.int64), []
-    t0 = first
-    while t0 <= cap:
-        n_run = min(chunk, cap - t0 + 1)
-        last = t0 + n_run - 1 == cap
-        rows = set_window(t0, n_run, last)
-        _lib.call("psg_rla_nu_field_window", ctypes.byref(win), runtime.stream())
-        back = torch.cat([S.hist[:rows].reshape(-1), S.exit.float()]).cpu().numpy()     # the window's one read-back
-        exited = back[rows * G * 4:].astype(np.int64)
-        rows_run.append(rows)
-        if hook is not None:
-            hook(t0, n_run, last, S, back[:rows * G * 4].reshape(rows, G, 4))
-        t0 += n_run
-        if (exited >= 0).all():
-            break
-    return rows_run, np.where(exited >= 0, exited, cap) + 1 - first
 
 
 class _NuField:
@@ -128,7 +104,9 @@ class _NuField:
             win.n_steps, win.adam_t0, win.tail_eval = n_run, t0, 1 if tail else 0
             return n_run + (1 if tail else 0)
 
-        _, self.last_steps = _run_windows(win, S, 1, self.iteration, self.chunk, set_window, self.window_hook)
+        # (4-column history rows; the state has no graph handle and the entry point takes none)
+        _, self.last_steps = attack._run_windows("psg_rla_nu_field_window", win, S, 1, self.iteration, self.chunk, set_window,
+                                                 self.window_hook)
         self.last_adv = S.out_adv.reshape(G, n, 3).clone()
         self.last_adv_xyz = S.out_adv_xyz.reshape(G, n, 3).clone()
         stats = S.out_stats.cpu().numpy().astype(np.float64)

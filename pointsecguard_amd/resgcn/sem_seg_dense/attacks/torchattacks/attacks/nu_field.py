@@ -22,12 +22,11 @@ NO RESTART and no restart draws: tcolper.py:128-131 clamps all nine channels to 
 the room); the restart of colper.py:92-95 writes a dead variable.  The CPU generator advances by one stochastic-graph draw
 set per forward that the reference's loop would have run; the device generator is not touched.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from pointsecguard_amd import _lib, runtime
+from pointsecguard_amd.attacks.nu_windows import RoomsState, _bind, room_masks, window_loop
 from pointsecguard_amd.attacks.torchattacks.attacks._common import check_field
 from pointsecguard_amd.attacks.torchattacks.attacks.nu import ADAM_EPS, BETA1, BETA2
 
@@ -35,58 +34,35 @@ from .colper import FIELD_CODES, _gcn
 from .nu import CHUNK
 
 
-class _GcnFieldState:
-    """Device buffers of one lockstep shape (G rooms of N points, `neighbour` Smooth neighbours), kept with the model instance
-    between calls: the addresses stay the same, so a window captured by one call is replayed by the next."""
+class _GcnFieldState(RoomsState):
+    """RoomsState of G rooms with the coordinate variable and this network's scratch; one graph handle: every full window has
+    the same shape."""
 
     def __init__(self, dev, G, N, neighbour):
-        f32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)       # noqa: E731
-        i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)         # noqa: E731
-        self.x0, self.ori, self.ori_xyz = f32(G, N, 9), f32(G, N, 3), f32(G, N, 3)
-        self.w, self.m, self.v = f32(G, N, 3), f32(G, N, 3), f32(G, N, 3)
+        super().__init__(dev, G, 1, N, neighbour, n_scal=5, n_graphs=1)      # scal rows: f, Smooth, L2, Smooth_xyz, L2_xyz
+        f32 = self._f32
+        self.ori_xyz, self.sgrad_xyz = f32(G, N, 3), f32(G, N, 3)
         self.delta, self.mx, self.vx = f32(G, N, 3), f32(G, N, 3), f32(G, N, 3)
-        self.logits, self.dlogits, self.dx0 = f32(G, N, 13), f32(G, N, 13), f32(G, N, 9)
-        self.sgrad, self.sgrad_xyz = f32(G, N, 3), f32(G, N, 3)
-        self.pred, self.labels = i32(G, N), i32(G, N)
-        self.mask = torch.empty(G, N, device=dev, dtype=torch.uint8)
-        self.scal = f32(5, G)                                        # rows: f, Smooth, L2, Smooth_xyz, L2_xyz
-        self.nn_state, self.nn_xyz = i32(G, N, int(neighbour)), i32(G, N, int(neighbour))
-        self.hist = f32(CHUNK, 7, G)                                 # one window of history rows
-        self.active = torch.empty(G, device=dev, dtype=torch.uint8)
-        self.exit, self.n_mask = i32(G), i32(G)
-        self.out = f32(G, 9, N)
-        self.graph = ctypes.c_void_p()                               # one handle: every full window has the same shape
-        _lib.call("psg_nu_graph_create", ctypes.byref(self.graph))
-
-    def __del__(self):
-        try:
-            if self.graph:
-                _lib.load().psg_nu_graph_destroy(self.graph)
-        except Exception:
-            pass
+        self.logits, self.dlogits = f32(G, N, 13), f32(G, N, 13)
+        self.nn_xyz = self._i32(G, N, int(neighbour))
 
 
 def _state(net, dev, G, N, neighbour, field):
-    cache = net.__dict__.setdefault("_psg_gcn_nu_field_states", {})
-    key = (str(dev), G, N, int(neighbour), field)
-    if key not in cache:
-        cache[key] = _GcnFieldState(dev, G, N, neighbour)
-    return cache[key]
+    return _GcnFieldState.of(net, "_psg_gcn_nu_field_states", (str(dev), G, N, int(neighbour), field), dev, G, N, neighbour)
 
 
 def window_args(S, model, ws, G, N, field, mode, use_target, target, neighbour, kappa, tsign, c_f, c_l2, c_l2_xyz, masked):
     """The argument block of psg_gcn_nu_field_window over the buffers of a _GcnFieldState (step0 / n_steps / adam_t0 / lr /
     coord_lr are set per window)."""
-    return _lib.GcnNuFieldWindowArgs(
+    win = _lib.GcnNuFieldWindowArgs(
         model=model.handle.value, ws=ws.handle.value, G=G, N=N, mode=mode, use_target=int(use_target),
         target=int(target) if use_target else 0, neighbour=int(neighbour), field=FIELD_CODES[field], kappa=float(kappa),
         tsign=float(tsign), c_f=c_f, c_smooth=1e-4, c_l2=c_l2, c_smooth_xyz=1e-4, c_l2_xyz=c_l2_xyz, beta1=BETA1, beta2=BETA2,
-        eps=ADAM_EPS, w=S.w.data_ptr(), m=S.m.data_ptr(), v=S.v.data_ptr(), delta=S.delta.data_ptr(), mx=S.mx.data_ptr(),
-        vx=S.vx.data_ptr(), ori_xyz=S.ori_xyz.data_ptr(), mask=S.mask.data_ptr() if masked else None, n_mask=S.n_mask.data_ptr(),
-        x0=S.x0.data_ptr(), ori=S.ori.data_ptr(), labels=S.labels.data_ptr(), logits=S.logits.data_ptr(),
-        dlogits=S.dlogits.data_ptr(), dx0=S.dx0.data_ptr(), sgrad=S.sgrad.data_ptr(), sgrad_xyz=S.sgrad_xyz.data_ptr(),
-        pred=S.pred.data_ptr(), scal=S.scal.data_ptr(), nn_state=S.nn_state.data_ptr(), nn_xyz=S.nn_xyz.data_ptr(),
-        hist=S.hist.data_ptr(), out=S.out.data_ptr(), active=S.active.data_ptr(), exit_step=S.exit.data_ptr())
+        eps=ADAM_EPS)
+    _bind(win, S, "w m v delta mx vx ori_xyz n_mask x0 ori labels logits dlogits dx0 sgrad sgrad_xyz pred scal nn_state nn_xyz hist "
+                  "out active exit_step=exit")
+    win.mask = S.mask.data_ptr() if masked else None
+    return win
 
 
 def init_state(S, images, labels, masks, both):
@@ -125,21 +101,8 @@ def gcn_nu_field_attack_rooms(atk, images, labels, masks=None, target=None, neig
     if images.dim() != 4 or images.shape[1] != 9 or images.shape[3] != 1:
         raise ValueError("expected images [R, 9, N, 1], got %s" % (tuple(images.shape),))
     G, _, N, _ = images.shape
-    mk = None
-    if masks is not None:
-        mk = masks.detach().to(torch.bool).cpu().numpy() if isinstance(masks, torch.Tensor) else np.asarray(masks).astype(bool)
-        if mk.shape != (G, N):
-            raise ValueError("masks must be boolean [%d, %d], got shape %s" % (G, N, mk.shape))
-        if targeted_variant and (mk.sum(axis=1) == 0).any():
-            raise ZeroDivisionError("tar_NU_attack: rooms %s have an empty mask (tcolper.py:109: division by the mask count)"
-                                    % np.nonzero(mk.sum(axis=1) == 0)[0].tolist())
-    elif targeted_variant:
-        raise ValueError("the targeted variant needs one mask per room")
-    lr_at_call, coord_lr_at_call = atk.lr, atk.coord_lr
-    try:
-        return _field_core(atk, net, images, labels, mk, target, neighbour, targeted_variant, trace, record, field)
-    finally:
-        atk.lr, atk.coord_lr = lr_at_call, coord_lr_at_call
+    mk, _ = room_masks(masks, G, N, targeted_variant, "tcolper.py:109")
+    return _field_core(atk, net, images, labels, mk, target, neighbour, targeted_variant, trace, record, field)
 
 
 def gcn_nu_field_attack(atk, images, labels, mask=None, target=None, neighbour=10, targeted_variant=False):
@@ -148,10 +111,7 @@ def gcn_nu_field_attack(atk, images, labels, mask=None, target=None, neighbour=1
     if images.shape[0] != 1:
         raise ValueError("field=%r attacks one room per call (the reference's batch semantics are a colour-path property and are "
                          "not extended); use forward_rooms for %d rooms in lockstep" % (atk.field, images.shape[0]))
-    masks = None
-    if mask is not None:
-        masks = (mask.detach().to(torch.bool).cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask).astype(bool))
-        masks = masks.reshape(1, -1)
+    masks = None if mask is None else (mask if isinstance(mask, torch.Tensor) else np.asarray(mask)).reshape(1, -1)
     return gcn_nu_field_attack_rooms(atk, images, labels, masks, target, neighbour, targeted_variant)[0]
 
 
@@ -172,51 +132,28 @@ def _field_core(atk, net, images, labels, mk, target, neighbour, targeted_varian
     init_state(S, images, labels, mk, both)
     win = window_args(S, model, ws, G, N, field, mode, use_target, target, neighbour, atk.kappa, atk._targeted, c_f, c_l2, c_l2_xyz,
                       mk is not None)
-    lr = float(atk.lr)
-    coord_lr = lr if atk.coord_lr is None else float(atk.coord_lr)
-    every_step = trace is not None
-    exited = np.full(G, -1, np.int64)
     rng_after = {}              # CPU generator after the forward of step s: what speculative steps drew is given back
-    step, adam_t = 0, 0
-    while step < atk.steps:
-        window_end = 1 if step == 0 else ((step - 1) // CHUNK + 1) * CHUNK + 1          # [0], [1..10], [11..20], ..
-        n_run = 1 if every_step else min(atk.steps, window_end) - step
+
+    def enqueue(step, n_run, adam_t):
         for s_i in range(step, step + n_run):            # one stochastic-graph draw set per forward (torch_edge.py:21)
             net.consume_rng(1)
             rng_after[s_i] = torch.get_rng_state()
-        win.step0, win.n_steps, win.adam_t0, win.lr, win.coord_lr = step, n_run, adam_t, lr, coord_lr
+        lr = float(atk.lr)
+        win.step0, win.n_steps, win.adam_t0 = step, n_run, adam_t
+        win.lr, win.coord_lr = lr, lr if atk.coord_lr is None else float(atk.coord_lr)
         ws.nu_field_window(win, S.graph if n_run == CHUNK else None)
-        adam_t += n_run
-        last = step + n_run - 1
-        got = torch.cat([S.hist[:n_run].reshape(-1), S.exit.float()]).cpu().numpy().astype(np.float64)     # ONE read-back
-        hrows, exited = got[:-G].reshape(n_run, 7, G), got[-G:].astype(np.int64)
-        for s_i in range(step, last + 1):
-            if trace is None and record is None:
-                break
-            row = hrows[s_i - step]
-            was_active = (exited < 0) | (exited >= s_i)
-            if trace is not None:
-                cost = c_f * row[2] + 1e-4 * row[5] + c_l2_xyz * row[6] + (1e-4 * row[3] + c_l2 * row[4] if both else 0.0)
-                trace(step=s_i, cost=cost, f=row[2], smooth=row[3], l2=row[4], smooth_xyz=row[5], l2_xyz=row[6],
-                      active=was_active.copy(), S=S)
-            if record is not None:
-                record(s_i, row.copy(), was_active.copy())
-        step = last + 1
-        if not (exited < 0).any():
-            break
-        if targeted_variant and last > 0 and last % 50 == 0:       # tcolper.py:125-127: halve, NEW optimiser (moments reset)
-            atk.lr = atk.lr / 2
-            if atk.coord_lr is not None:
-                atk.coord_lr = atk.coord_lr / 2
-            lr = float(atk.lr)
-            coord_lr = lr if atk.coord_lr is None else float(atk.coord_lr)
-            adam_t = 0
-            for t in (S.m, S.v, S.mx, S.vx):
-                t.zero_()
-    steps_run = np.where(exited >= 0, exited + 1, step).astype(np.int64)
+
+    def on_step(s_i, row, was_active, exited):
+        if trace is not None:
+            cost = c_f * row[2] + 1e-4 * row[5] + c_l2_xyz * row[6] + (1e-4 * row[3] + c_l2 * row[4] if both else 0.0)
+            trace(step=s_i, cost=cost, f=row[2], smooth=row[3], l2=row[4], smooth_xyz=row[5], l2_xyz=row[6],
+                  active=was_active.copy(), S=S)
+        if record is not None:
+            record(s_i, row.copy(), was_active.copy())
+
+    out, steps_run, step = window_loop(atk, S, 1, enqueue, targeted_variant=targeted_variant,
+                                       on_step=on_step if trace is not None or record is not None else None,
+                                       one_step=trace is not None, lr_names=("lr", "coord_lr"), moments=(S.m, S.v, S.mx, S.vx))
     if step:
         torch.set_rng_state(rng_after[int(steps_run.max()) - 1])        # as for the longest-running room
-    out = S.out.clone()                                  # (the caller owns what it gets; the state buffer is reused)
-    for g in np.nonzero(exited < 0)[0]:                  # rooms that ran to the cap: the current image
-        _lib.call("psg_to_channel_major", runtime.ptr(S.x0[g:g + 1]), 1, 9, N, runtime.ptr(out[g:g + 1]), runtime.stream())
     return out.unsqueeze(-1), steps_run
