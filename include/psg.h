@@ -119,8 +119,9 @@ size_t psg_pn2_ws_bytes(const psg_pn2_ws *ws);
  * bracketed by two events.  prof_read (blocking: waits for the events) sums the elapsed ms and counts per
  * kernel tag: 0-3 sa1-4 fwd, 4-7 fp1-4 fwd (4 = fp1+head), 8-11 fp1-4 bwd, 12-15 sa1-4 bwd, 16 fps,
  * 17 ball query, 18 three_nn, 19 gather, 20 ce grad, 21 pgd step, 22 input-gradient gather, 23 / 24 per-point first
- * layers fwd / bwd, 25-27 psg_pn2_backward_full only: g_rel rows, 3-NN weight gradients, per-level coordinate sums.
- * n_tags >= 28. */
+ * layers fwd / bwd, 25-27 psg_pn2_backward_full only: g_rel rows, 3-NN weight gradients, per-level coordinate sums,
+ * 28 packed-SA plan, 29 the NB loop's fp1+head forward, CE gradient and backward in one launch (then 4, 8 and 20 of that
+ * loop are empty).  n_tags >= 30. */
 int psg_pn2_prof_enable(psg_pn2_ws *ws, int on);
 int psg_pn2_prof_read(psg_pn2_ws *ws, int n_tags, double *total_ms, int *counts);
 
@@ -194,6 +195,18 @@ int psg_pn2_backward_colour(psg_pn2_model *model, psg_pn2_ws *ws, int forward, c
 int psg_pn2_backward_colour_pgd(psg_pn2_model *model, psg_pn2_ws *ws, int forward, const float *dlogp, float *x,
                                 const float *ori, const uint8_t *mask, float alpha, float eps, float dir, int last,
                                 psg_stream stream);
+
+/* One iteration of psg_pn2_nb_attack's loop on plan slot `forward`, exactly as the attack runs it (its loop body is this call):
+ * lean forward of x [batch][n_point][9], loss gradient (non-targeted: labels [batch][n_point], CE_sum / n_point; targeted:
+ * labels ignored, class `target`, CE_mean of room 0), colour backward with the step applied to x in place (ori, mask, alpha,
+ * eps, last as in psg_pn2_backward_colour_pgd).  By default fp1 + head forward, the loss gradient and fp1 + head backward are
+ * ONE launch (same bits as the three launches, which PSG_PN2_FP1_LOOP=0 keeps); that launch writes neither log-probs nor masks
+ * to memory, so afterwards NO forward is resident for psg_pn2_backward* - run psg_pn2_forward first. */
+int psg_pn2_nb_step(psg_pn2_model *model, psg_pn2_ws *ws, int forward, float *x, const float *ori, const int32_t *labels,
+                    const uint8_t *mask, float alpha, float eps, int targeted, int target, int last, psg_stream stream);
+/* fp1's first-layer gradient rows [batch][n_point][128] as the last backward or step left them (what fp2's backward gathers;
+ * with PSG_PN2_FPSPLIT=0 the rows are fp1's interpolated-input gradient instead).  Read-only device pointer, for tests. */
+const float *psg_pn2_fp1_grad_ptr(const psg_pn2_ws *ws);
 
 /* Per-layer activations of the last forward, for parity tests: which 0..3 = l1..l4 points (sa1..sa4
  * outputs), 4..6 = fp4, fp3, fp2 outputs.  Returns a device pointer [batch][points][channels]. */

@@ -66,6 +66,8 @@ SIGNATURES = {
     "psg_pn2_forward_lean": (ci, [vp, vp, ci, vp, vp, vp]),
     "psg_pn2_backward_colour": (ci, [vp, vp, ci, vp, vp, vp]),
     "psg_pn2_backward_colour_pgd": (ci, [vp, vp, ci, vp, vp, vp, vp, cf, cf, cf, ci, vp]),
+    "psg_pn2_nb_step": (ci, [vp, vp, ci, vp, vp, vp, vp, cf, cf, ci, ci, ci, vp]),
+    "psg_pn2_fp1_grad_ptr": (vp, [vp]),
     "psg_pn2_activation_ptr": (vp, [vp, ci]),
     "psg_pn2_activation_channels": (ci, [vp, ci]),
     "psg_to_point_major": (ci, [vp, ci, ci, ci, vp, vp]),

@@ -26,7 +26,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"PSG_PN2_FPSPLIT", 'p'},        {"PSG_FPS_CFG", 'p'},         {"PSG_PN2_L1T_COLOUR", 'p'},
     {"PSG_PN2_PGD_FUSE", 'p'},       {"PSG_PN2_POOLT_SPARSE", 'p'}, {"PSG_PN2_PW_SIZED", 'p'},
     {"PSG_PN2_BALL_TABLE", 'p'},     {"PSG_PN2_PACK", 'p'},          {"PSG_PN2_PACK_BWD", 'p'},
-    {"PSG_PN2_POOLT_ORDER", 'p'},    {"PSG_THREE_NN", 'p'},
+    {"PSG_PN2_POOLT_ORDER", 'p'},    {"PSG_THREE_NN", 'p'},         {"PSG_PN2_FP1_LOOP", 'p'},
 #ifdef PSG_DIAG_BUILD
     {"PSG_DIAG", 'r'},
 #endif

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "psg_adam.cuh"
+#include "psg_ce_row.cuh"
 #include "psg_common.h"
 
 namespace {
@@ -31,7 +32,7 @@ __global__ void to_channel_major_kernel(const float *__restrict__ src, float *__
     }
 }
 
-constexpr int MAXC = 32;
+constexpr int MAXC = psg::CE_ROW_MAXC;
 
 // 256 rows per workgroup staged through LDS: the rows of a block are one contiguous piece of logp / dlogp, so global
 // accesses are whole cache lines (a thread per row reading its n_cls floats directly strides the lanes 52 bytes apart);
@@ -48,24 +49,11 @@ __global__ __launch_bounds__(256) void ce_logp_grad_kernel(const float *__restri
     const int r = r0 + (int)threadIdx.x;
     float g[MAXC];
     if ((int)threadIdx.x < nr) {
-        if (r >= rows_active) {
-            for (int c = 0; c < n_cls; ++c) g[c] = 0.0f;
-        } else {
-            const float *lp = s_z + threadIdx.x * n_cls;        // (n_cls = 13: an odd stride, conflict-free)
-            float z[MAXC];
-            float m = -INFINITY;
-            for (int c = 0; c < n_cls; ++c) { z[c] = lp[c]; m = fmaxf(m, z[c]); }
-            float s = 0.0f;
-            for (int c = 0; c < n_cls; ++c) s += expf(z[c] - m);
-            const float lse = logf(s);
-            const int y = labels ? labels[r] : target;
-            for (int c = 0; c < n_cls; ++c) {
-                float lp2 = (z[c] - m) - lse;  // second log_softmax (CrossEntropyLoss applied to log-probs)
-                float p = expf(lp2);
-                g[c] = (p - (c == y ? 1.0f : 0.0f)) * scale;
-                if (cost && c == y) atomicAdd(cost, -lp2 * scale);
-            }
-        }
+        // (the row arithmetic: psg_ce_row.cuh, shared with the fused fp1 + head launch of the PointNet++ NB loop)
+        const bool active = r < rows_active;
+        const int y = !active ? -1 : labels ? labels[r] : target;
+        const float term = psg::ce_row_grad(s_z + threadIdx.x * n_cls, n_cls, y, scale, active, g);   // (n_cls = 13: an odd stride, conflict-free)
+        if (cost && active && y >= 0 && y < n_cls) atomicAdd(cost, term);
     }
     __syncthreads();
     if ((int)threadIdx.x < nr) {

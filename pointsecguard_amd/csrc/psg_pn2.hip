@@ -386,7 +386,8 @@ BwdLayer bwd_layer(const PackedLayer &p, const uint16_t *mask)
 // kernel tags of the per-launch profile (psg_pn2_prof_read)
 enum { TAG_SA_FWD = 0, TAG_FP_FWD = 4, TAG_FP_BWD = 8, TAG_SA_BWD = 12, TAG_FPS = 16, TAG_BALL = 17, TAG_NN = 18,
        TAG_GATHER = 19, TAG_CE = 20, TAG_PGD = 21, TAG_ZERO = 22, TAG_PW_FWD = 23, TAG_PW_BWD = 24,
-       TAG_GEOM_GREL = 25, TAG_GEOM_WGRAD = 26, TAG_GEOM_GX = 27, TAG_PACK_PLAN = 28, TAG_COUNT = 29 };   // 25-27: psg_pn2_backward_full only
+       TAG_GEOM_GREL = 25, TAG_GEOM_WGRAD = 26, TAG_GEOM_GX = 27, TAG_PACK_PLAN = 28, TAG_FP1_LOOP = 29,
+       TAG_COUNT = 30 };   // 25-27: psg_pn2_backward_full only; 29: the NB loop's fp1 + head forward, CE and backward in one launch
 
 // Every launch with a dynamic LDS buffer of `blocks8` blocks of `blk` floats goes through here: size check, the shared LDS
 // opt-in above 48 KiB, the profile scope and the launch check.  `site` is the CALLER's launch site (PSG_SITE, psg_common.h).
@@ -1057,6 +1058,62 @@ int run_fp_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, con
     if constexpr (FpCfg<LVL>::P2 != FpCfg<LVL>::P)
         if (ws->Nl[LVL] % FpCfg<LVL>::P2 == 0) return run_fp_bwd_p<LVL, FpCfg<LVL>::P2>(m, ws, fwd, logp, dlogp, st);
     return run_fp_bwd_p<LVL, FpCfg<LVL>::P>(m, ws, fwd, logp, dlogp, st);
+}
+
+// The NB loop's fp1 + head forward, CE gradient and fp1 + head backward as ONE launch (fp1_loop_kernel, psg_pn2_kernels.cuh)
+// where forward and backward share the 64-point tiling: the split fp1 of both architectures (three 128-wide layers without
+// skip columns, conv1, the 13-class conv2).  Anything else - PSG_PN2_FPSPLIT=0, the wave-private chain (PSG_FP1_WAVE=1), a
+// point count that is no multiple of 64, a diagnostic build, PSG_PN2_FP1_LOOP=0 (A/B runs, tests/test_gpu_fp1_loop.py) - keeps
+// the three launches.  The results are the same bits either way.
+bool fp1_loop_applies(const psg_pn2_model *m, const psg_pn2_ws *ws)
+{
+    static const bool on = psg::env_int("PSG_PN2_FP1_LOOP", 1) != 0;
+#ifdef PSG_DIAG_BUILD
+    constexpr bool diag_build = true;     // (the fused kernel has no section-skipping switches)
+#else
+    constexpr bool diag_build = false;
+#endif
+    if (!on || diag_build || FpCfg<0>::P2 != 64 || FpCfg<0>::NW != 4 || fp1_wave() || !m->fsplit[0] || ws->Nl[0] % 64) return false;
+    const ArchDesc &A = *m->arch;
+    const int first = A.fp_first[0], head = A.head;
+    if (A.fp_count[0] != 3 || NCLS != 13 || m->fa[0].k8f() != 0 || m->fa[0].cout != 128 || m->fb[0].cout != 128) return false;
+    for (const PackedLayer *p : {&m->L[first + 1], &m->L[first + 2], &m->L[head]})
+        if (p->k8f() != 16 || p->mbf() != 4 || p->k8b() != 16 || p->mbb() != 4) return false;
+    const PackedLayer &c2 = m->L[head + 1];
+    return c2.k8f() == 16 && c2.mbf() == 1 && c2.k8b() == 2 && c2.mbb() == 4;
+}
+
+int run_fp1_loop(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const int32_t *labels, int target, int rows_active, float scale,
+                 hipStream_t st)
+{
+    constexpr int P = 64, NW = 4;
+    const ArchDesc &A = *m->arch;
+    const int B = ws->B, N = ws->Nl[0], first = A.fp_first[0], head = A.head;
+    const size_t prob = (size_t)fwd * B;
+    Fp1LoopArgs a{};
+    a.fwd.nn_idx = ws->nn_idx[0] + prob * N * 3;
+    a.fwd.nn_w = ws->nn_w[0] + prob * N * 3;
+    a.fwd.tsrc = ws->tfp[0]; a.fwd.ldt = m->fa[0].cout;
+    a.fwd.N = N; a.fwd.S = ws->Nl[1];
+    a.fwd.layer[0] = fwd_layer(m->fa[0], true, nullptr);      // (k8 = 0: no skip columns)
+    a.fwd.layer[0].bias = m->L[first].bias;
+    a.f[0] = fwd_layer(m->L[first + 1], true, nullptr);
+    a.f[1] = fwd_layer(m->L[first + 2], true, nullptr);
+    a.f[2] = fwd_layer(m->L[head], true, nullptr);
+    a.head = fwd_layer(m->L[head + 1], false, nullptr);
+    a.t[0] = bwd_layer(m->L[head + 1], nullptr);
+    a.t[1] = bwd_layer(m->L[head], nullptr);
+    a.t[2] = bwd_layer(m->L[first + 2], nullptr);
+    a.t[3] = bwd_layer(m->L[first + 1], nullptr);
+    a.labels = labels; a.target = target; a.rows_active = rows_active; a.scale = scale;
+    a.dint_out = ws->dint[0];
+    a.N = N;
+#if PSG_MLP_PAIRS
+    return launch_lds(ws, TAG_FP1_LOOP, PSG_SITE, (fp1_loop_kernel<P, NW, NCLS>), dim3(N / P, B), NW * 64, 16 + PSG_LDS_SPARE, Lds<P>::BLK, a, st);
+#else   // (the single-tile engine runs fp1 at 32 points: fp1_loop_applies is false, and no paired loop is built)
+    set_error("run_fp1_loop: built without the paired k-loop");
+    return PSG_ERR_STATE;
+#endif
 }
 
 __global__ void extract_xyz_kernel(const float *__restrict__ x0, float *__restrict__ xyz, size_t rows)
@@ -1758,13 +1815,10 @@ extern "C" int psg_pn2_activation_channels(const psg_pn2_ws *ws, int which)
 }
 
 // ================================================================================ forward / backward
-extern "C" int psg_pn2_forward(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *x0, float *logp_out,
-                               float *l4_out, psg_stream stream)
+// Everything of a forward in front of fp1 + head: the four SA levels and fp4 .. fp2 (whose last launch also writes the T rows
+// fp1's split first layer gathers)
+static int forward_to_fp2(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *x0, hipStream_t st)
 {
-    PSG_REQUIRE(m && ws && x0 && logp_out, "psg_pn2_forward: null argument");
-    PSG_REQUIRE(m->arch == ws->arch, "psg_pn2_forward: model and workspace were created for different architectures");
-    PSG_REQUIRE(fwd >= 0 && fwd < ws->planned, "psg_pn2_forward: plan slot %d not built (planned %d)", fwd, ws->planned);
-    hipStream_t st = (hipStream_t)stream;
     int rc;
     ws->x0_fwd = x0;
     for (int l = 0; l < 4; ++l) {
@@ -1775,7 +1829,18 @@ extern "C" int psg_pn2_forward(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const 
     }
     if ((rc = run_fp_fwd<3>(m, ws, fwd, nullptr, st))) return rc;
     if ((rc = run_fp_fwd<2>(m, ws, fwd, nullptr, st))) return rc;
-    if ((rc = run_fp_fwd<1>(m, ws, fwd, nullptr, st))) return rc;
+    return run_fp_fwd<1>(m, ws, fwd, nullptr, st);
+}
+
+extern "C" int psg_pn2_forward(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *x0, float *logp_out,
+                               float *l4_out, psg_stream stream)
+{
+    PSG_REQUIRE(m && ws && x0 && logp_out, "psg_pn2_forward: null argument");
+    PSG_REQUIRE(m->arch == ws->arch, "psg_pn2_forward: model and workspace were created for different architectures");
+    PSG_REQUIRE(fwd >= 0 && fwd < ws->planned, "psg_pn2_forward: plan slot %d not built (planned %d)", fwd, ws->planned);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = forward_to_fp2(m, ws, fwd, x0, st))) return rc;
     if ((rc = run_fp_fwd<0>(m, ws, fwd, ws->logp, st))) return rc;
     if (logp_out != ws->logp)
         PSG_CHECK_HIP(hipMemcpyAsync(logp_out, ws->logp, (size_t)ws->B * ws->N * NCLS * 4, hipMemcpyDeviceToDevice, st));
@@ -1786,12 +1851,14 @@ extern "C" int psg_pn2_forward(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const 
 }
 
 static int backward_impl(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, const float *dlogp,
-                         float *dx0, int c_lo, int c_hi, hipStream_t st, const PgdFuse *pgd = nullptr, bool rel0 = false)
+                         float *dx0, int c_lo, int c_hi, hipStream_t st, const PgdFuse *pgd = nullptr, bool rel0 = false,
+                         bool fp1_done = false)
 {
     const ArchDesc &A = *m->arch;
     int rc;
     // no gradient buffer is accumulated into: every row has exactly one writer, consumers gather (fixed order)
-    if ((rc = run_fp_bwd<0>(m, ws, fwd, logp, dlogp, st))) return rc;
+    // (fp1_done: the fused launch of the NB step has already written fp1's dZ1 rows; logp / dlogp are not read then)
+    if (!fp1_done && (rc = run_fp_bwd<0>(m, ws, fwd, logp, dlogp, st))) return rc;
     if ((rc = run_fp_bwd<1>(m, ws, fwd, nullptr, nullptr, st))) return rc;
     if ((rc = run_fp_bwd<2>(m, ws, fwd, nullptr, nullptr, st))) return rc;
     if ((rc = run_fp_bwd<3>(m, ws, fwd, nullptr, nullptr, st))) return rc;
@@ -1990,6 +2057,63 @@ extern "C" int psg_pn2_backward_colour_pgd(psg_pn2_model *m, psg_pn2_ws *ws, int
 }
 
 // ====================================================================================== NB attack
+// One PGD iteration of the NB / tar_NB loop on plan slot `fwd` (nontarget.py:29-39, target.py:31-43): lean forward, loss
+// gradient, colour backward with the step applied to x.  Written once: psg_pn2_nb_attack's loop body is this call and nothing
+// else, and psg_pn2_nb_step exports it for the teacher-forced tests.
+//   non-targeted: CE_sum over all rooms / N (nontarget.py:34); targeted: CE_mean of room 0 (target.py:36-39)
+// Where fp1 + head runs as one launch there and back (fp1_loop_applies), the forward stops in front of fp1, the fused launch
+// takes the loss gradient with it, and the backward starts behind fp1; ws->logp, ws->dlogp and the four masks of fp1 + head are
+// not written then, so no forward is resident for the general backward entry points afterwards.
+static int nb_step(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *x, const float *ori, const int32_t *labels, const uint8_t *mask,
+                   float alpha, float eps, int targeted, int target, bool last, hipStream_t st)
+{
+    const int B = ws->B, N = ws->N, rows = B * N;
+    const int rows_active = targeted ? N : rows;
+    const float scale = 1.0f / (float)N, dir = targeted ? -1.0f : 1.0f;
+    const bool fused = fp1_loop_applies(m, ws);
+    int r;
+    if (fused) {
+        PSG_REQUIRE(fwd >= 0 && fwd < ws->planned, "psg_pn2_nb_step: plan slot %d not built (planned %d)", fwd, ws->planned);
+        ws->lean = true;
+        r = forward_to_fp2(m, ws, fwd, x, st);
+        ws->lean = false;
+        ws->fwd_slot = -1;
+        if (r) return r;
+        if ((r = run_fp1_loop(m, ws, fwd, labels, target, rows_active, scale, st))) return r;
+    } else {
+        if ((r = psg::pn2_forward_lean(m, ws, fwd, x, ws->logp, st))) return r;
+        EvScope prof(&ws->prof, TAG_CE, 0.0, st);
+        if ((r = psg_ce_logp_grad(ws->logp, labels, target, rows, rows_active, NCLS, scale, ws->dlogp, nullptr, st))) return r;
+    }
+    // (the PGD step rides on the gradient's last gather: dx0_gather_pgd_kernel; PSG_PN2_PGD_FUSE=0: two launches)
+    static const bool pgd_fuse = psg::env_int("PSG_PN2_PGD_FUSE", 1) != 0;
+    if (pgd_fuse) {
+        const PgdFuse pf{x, ori, mask, dir * alpha, eps, last ? 1 : 0};
+        return backward_impl(m, ws, fwd, ws->logp, ws->dlogp, ws->dx0, 3, 6, st, &pf, false, fused);
+    }
+    if ((r = backward_impl(m, ws, fwd, ws->logp, ws->dlogp, ws->dx0, 3, 6, st, nullptr, false, fused))) return r;
+    EvScope prof(&ws->prof, TAG_PGD, 0.0, st);
+    return psg_pgd_step(x, ws->dx0, ori, mask, B, N, alpha, eps, dir, last, st);
+}
+
+extern "C" int psg_pn2_nb_step(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *x, const float *ori, const int32_t *labels,
+                               const uint8_t *mask, float alpha, float eps, int targeted, int target, int last, psg_stream stream)
+{
+    PSG_REQUIRE(m && ws && x && ori, "psg_pn2_nb_step: null argument");
+    PSG_REQUIRE(m->arch == ws->arch, "psg_pn2_nb_step: model and workspace were created for different architectures");
+    PSG_REQUIRE(targeted || labels, "psg_pn2_nb_step: labels required for the non-targeted step");
+    PSG_REQUIRE(!targeted || (target >= 0 && target < NCLS), "psg_pn2_nb_step: target class %d out of range", target);
+    PSG_REQUIRE(fwd >= 0 && fwd < ws->planned, "psg_pn2_nb_step: plan slot %d not built (planned %d)", fwd, ws->planned);
+    return nb_step(m, ws, fwd, x, ori, targeted ? nullptr : labels, mask, alpha, eps, targeted, target, last != 0, (hipStream_t)stream);
+}
+
+// The dZ1 rows of fp1 [batch][n_point][128] as the last backward (or fused step) left them: what fp2's backward gathers.
+// Read-only, for the tests.
+extern "C" const float *psg_pn2_fp1_grad_ptr(const psg_pn2_ws *ws)
+{
+    return ws ? ws->dint[0] : nullptr;
+}
+
 extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *images, const int32_t *labels,
                                  const int32_t *starts, const uint8_t *mask, float eps, float alpha, int iters,
                                  int targeted, int target, float *adv_out, psg_stream stream)
@@ -2015,28 +2139,8 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
                            ws->ori, (size_t)B * N);
         PSG_LAUNCH_CHECK();
         if ((r = psg_pn2_plan_build(ws, ws->x0, ws->nb_starts, iters, st))) return r;
-        const int rows = B * N;
-        for (int it = 0; it < iters; ++it) {
-            if ((r = psg::pn2_forward_lean(m, ws, it, ws->x0, ws->logp, st))) return r;
-            // non-targeted: CE_sum over all rooms / N (nontarget.py:34); targeted: CE_mean of room 0 (target.py:36-39)
-            {
-                EvScope prof(&ws->prof, TAG_CE, 0.0, st);
-                if ((r = psg_ce_logp_grad(ws->logp, labels_ws, target, rows, targeted ? N : rows, NCLS, 1.0f / (float)N, ws->dlogp,
-                                          nullptr, st)))
-                    return r;
-            }
-            // (the PGD step rides on the gradient's last gather: dx0_gather_pgd_kernel; PSG_PN2_PGD_FUSE=0: two launches)
-            static const bool pgd_fuse = psg::env_int("PSG_PN2_PGD_FUSE", 1) != 0;
-            if (pgd_fuse) {
-                const PgdFuse pf{ws->x0, ws->ori, mask_ws, (targeted ? -1.0f : 1.0f) * alpha, eps, it == iters - 1 ? 1 : 0};
-                if ((r = backward_impl(m, ws, it, ws->logp, ws->dlogp, ws->dx0, 3, 6, st, &pf))) return r;
-            } else {
-                if ((r = backward_impl(m, ws, it, ws->logp, ws->dlogp, ws->dx0, 3, 6, st))) return r;
-                EvScope prof(&ws->prof, TAG_PGD, 0.0, st);
-                if ((r = psg_pgd_step(ws->x0, ws->dx0, ws->ori, mask_ws, B, N, alpha, eps, targeted ? -1.0f : 1.0f, it == iters - 1, st)))
-                    return r;
-            }
-        }
+        for (int it = 0; it < iters; ++it)
+            if ((r = nb_step(m, ws, it, ws->x0, ws->ori, labels_ws, mask_ws, alpha, eps, targeted, target, it == iters - 1, st))) return r;
         return PSG_OK;
     };
     // Round 5, measured and left OFF (PSG_PN2_GRAPH=1 turns it on): the body is ~33 launches per iteration + the plan (1 300
@@ -2063,7 +2167,8 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
             PSG_CHECK_HIP(hipStreamWaitEvent(gs, ws->nb_ev[0], 0));
             if (ws->nb.exec || ws->nb.capture(gs, [&] { return body(gs); })) {
                 PSG_CHECK_HIP(ws->nb.replay(gs));
-                ws->planned = iters; ws->fwd_slot = iters - 1; ws->x0_fwd = ws->x0;      // (the host-side state the eager body leaves)
+                // (the host-side state the eager body leaves)
+                ws->planned = iters; ws->fwd_slot = fp1_loop_applies(m, ws) ? -1 : iters - 1; ws->x0_fwd = ws->x0;
                 // .. and the caller's stream goes on after the attack
                 PSG_CHECK_HIP(hipEventRecord(ws->nb_ev[1], gs));
                 PSG_CHECK_HIP(hipStreamWaitEvent(st, ws->nb_ev[1], 0));

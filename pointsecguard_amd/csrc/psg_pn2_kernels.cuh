@@ -10,6 +10,7 @@
 //   head         PointNet/models/pointnet2_sem_seg.py:36-38 (conv1+bn1+ReLU, conv2, log_softmax)
 //   backward     what autograd derives for d/d(input features); geometry is constant w.r.t. colour.
 #pragma once
+#include "psg_ce_row.cuh"
 #include "psg_mlp.cuh"
 
 // Timing-diagnosis switches (tools/diag_*.sh: skip a kernel section to see what it costs; the results are then wrong).
@@ -2119,6 +2120,210 @@ __global__ __launch_bounds__(NW * 64) void fp_bwd_kernel(FpBwdArgs a)
         const unsigned o = __umul24((unsigned)j, (unsigned)a.C1);
         for (int q = ql; q < (a.C1 >> 2); q += 32) *(float4 *)(d1 + (o + 4u * q)) = *(const float4 *)(in + L::off(4 * q, j));
     }
+}
+
+// ------------------------------------------------------------------------------------------ fp1 + head, there and back
+// The NB loop's fp1 + head forward, CE gradient and fp1 + head backward in ONE launch (psg_pn2_nb_step): fp_fwd_kernel<64, 4>
+// and fp_bwd_kernel<64, 4, 2> share their tiling - 64 points per workgroup, four waves, the one in-place LDS buffer, xcd_tile's
+// order - and the backward needs nothing of the forward but the ReLU bits and the 13 log-probs of its own points.  A workgroup
+// runs its tile from the gather of the T rows to the store of its dZ1 rows; what the three launches exchanged through HBM
+// (logp, dlogp, the masks of four layers) stays in LDS and registers:
+//   * a wave owns the tile pair (mb = first, pb = 0 / 1) of every 128-wide layer, forward and transposed (layer_fwd's and
+//     layer_bwd's pair dealing: the same `first`); the 2 x 16 ReLU bits of a layer are one register per lane, kept from the
+//     layer's forward epilogue to the transposed layer whose output they gate;
+//   * the split first layer deals single tiles (fp_layer1_split), so the bits of a wave's pair have another owner there: the
+//     wave reads them back from the layer's output in LDS (positive exactly where the bit was set);
+//   * log-probs and their gradient are staged in LDS blocks 4 .. 7, which the head leaves free (fp_bwd_kernel's prologue).
+// Every tile runs the k-loops, the epilogue and the row arithmetic of the separate kernels, expression for expression: the
+// results are the same bits (tests/test_gpu_fp1_loop.py).  NC = the class count, a constant here so that the CE row's arrays
+// are registers.
+struct Fp1LoopArgs {
+    FpFwdArgs fwd;          // what fp_layer1_split reads of the forward's arguments: nn_idx, nn_w, tsrc, ldt, N, S and layer[0]
+                            // (the split first layer: its bias, k8 = 0, no mask pointer)
+    FwdLayer f[3];          // fp1 layers 2 and 3, conv1 (ReLU; no mask pointer: the bits stay in registers)
+    FwdLayer head;          // conv2
+    BwdLayer t[4];          // conv2^T, conv1^T, fp1 layer 3^T, layer 2^T (no mask pointer)
+    const int32_t *labels;  // [B][N], or null: `target` for every row
+    int target, rows_active;
+    float scale;
+    float *dint_out;        // [B][N][128]: the dZ1 rows, where fp_bwd_kernel writes them for fp2's gather
+    int N;
+};
+
+__device__ __forceinline__ void add_bias16(f32x16 &c, const float4 &bq0, const float4 &bq1, const float4 &bq2, const float4 &bq3)
+{
+    c[0] += bq0.x; c[1] += bq0.y; c[2] += bq0.z; c[3] += bq0.w;
+    c[4] += bq1.x; c[5] += bq1.y; c[6] += bq1.z; c[7] += bq1.w;
+    c[8] += bq2.x; c[9] += bq2.y; c[10] += bq2.z; c[11] += bq2.w;
+    c[12] += bq3.x; c[13] += bq3.y; c[14] += bq3.z; c[15] += bq3.w;
+}
+
+// the ReLU bits of the wave's pair (first, 0 / 1) read back from the layer's output in LDS: an element is positive exactly where
+// relu_bits set its bit (it stored x where 0 < x and 0 elsewhere)
+template <int P>
+__device__ __forceinline__ unsigned fp1_loop_pair_bits(const float *__restrict__ buf, int first, int lane)
+{
+    const int j = lane & 31, h = lane >> 5;
+    const float *o = buf + (size_t)(first * 4) * Lds<P>::BLK + j * 8 + 4 * h;
+    unsigned m = 0;
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 v = *(const float4 *)(o + (size_t)g * Lds<P>::BLK + pb * 32 * 8);
+            m |= (v.x > 0.0f ? 1u : 0u) << (16 * pb + 4 * g);
+            m |= (v.y > 0.0f ? 1u : 0u) << (16 * pb + 4 * g + 1);
+            m |= (v.z > 0.0f ? 1u : 0u) << (16 * pb + 4 * g + 2);
+            m |= (v.w > 0.0f ? 1u : 0u) << (16 * pb + 4 * g + 3);
+        }
+    }
+    return m;
+}
+
+// the wave's pair (first, 0 / 1) of a 128-wide forward layer, in place: layer_fwd's pair path with the bits returned
+// (low half: point block 0, high half: point block 1).  The caller places the barrier behind it, as behind layer_fwd.
+template <int P>
+__device__ __forceinline__ unsigned fp1_loop_pair_fwd(const FwdLayer &Lr, float *__restrict__ buf, int first, int lane)
+{
+    constexpr int BLK = Lds<P>::BLK;
+    const int j = lane & 31, h = lane >> 5;
+    const float4 *bp = (const float4 *)(Lr.bias + first * 32 + 4 * h);
+    const float4 bq0 = bp[0], bq1 = bp[2], bq2 = bp[4], bq3 = bp[6];
+    f32x16 c0, c1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; }
+    tile_mac_x2<BLK, false>(Lr.w + (size_t)first * Lr.k8 * 64 + lane, Lr.k8, buf + j * 8 + 4 * h, c0, c1);
+    add_bias16(c0, bq0, bq1, bq2, bq3);
+    const unsigned m0 = relu_bits(c0);
+    add_bias16(c1, bq0, bq1, bq2, bq3);
+    const unsigned m1 = relu_bits(c1);
+    __syncthreads();
+    store_tile<P>(buf, first, j, h, c0);
+    store_tile<P>(buf, first, 32 + j, h, c1);
+    return m0 | (m1 << 16);
+}
+
+// the same pair of a transposed layer, gated by the bits `m` of the forward layer whose input gradient this is
+template <int P>
+__device__ __forceinline__ void fp1_loop_pair_bwd(const BwdLayer &Lt, float *__restrict__ buf, int first, int lane, unsigned m)
+{
+    constexpr int BLK = Lds<P>::BLK;
+    const int j = lane & 31, h = lane >> 5;
+    f32x16 c0, c1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; }
+    tile_mac_x2<BLK, false>(Lt.w + (size_t)first * Lt.k8 * 64 + lane, Lt.k8, buf + j * 8 + 4 * h, c0, c1);
+    apply_bits(c0, m);
+    apply_bits(c1, m >> 16);
+    __syncthreads();
+    store_tile<P>(buf, first, j, h, c0);
+    store_tile<P>(buf, first, 32 + j, h, c1);
+}
+
+template <int P, int NW, int NC>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void fp1_loop_kernel(Fp1LoopArgs a)
+{
+    static_assert(P == 64 && NW == 4 && NC <= 16, "one pair of tiles per wave and 128-wide layer; the classes in two LDS blocks");
+    using L = Lds<P>;
+    constexpr int NT = NW * 64;
+    extern __shared__ float lds[];
+    float *buf0 = lds;   // the one activation buffer (layers run in place), 16 blocks
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    int bx, b;
+    xcd_tile(bx, b);
+    const int n0 = bx * P;
+    const size_t wg = (size_t)b * gridDim.x + bx;
+    const int first = (wave + (int)(wg & (NW - 1))) & (NW - 1);
+
+    // ---- forward: split first layer (fp_layer1_split itself: the compiler contracts its weighted sums element by element as
+    // it sees fit, and only the same function gives the same bits), layers 2 and 3, conv1
+    fp_layer1_split<P, NW>(a.fwd, b, n0, buf0, wg);
+    __syncthreads();
+    const unsigned m_l1 = fp1_loop_pair_bits<P>(buf0, first, lane);
+    const unsigned m_l2 = fp1_loop_pair_fwd<P>(a.f[0], buf0, first, lane);
+    __syncthreads();
+    const unsigned m_l3 = fp1_loop_pair_fwd<P>(a.f[1], buf0, first, lane);
+    __syncthreads();
+    const unsigned m_c1 = fp1_loop_pair_fwd<P>(a.f[2], buf0, first, lane);
+    __syncthreads();
+    // conv2: one output block, two single tiles (layer_fwd's single-tile path: task = first < 2 is point block `first`)
+    {
+        f32x16 c;
+        if (first < P / 32) {
+            const float4 *bp = (const float4 *)(a.head.bias + 4 * h);
+            const float4 bq0 = bp[0], bq1 = bp[2], bq2 = bp[4], bq3 = bp[6];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c[r] = 0.0f;
+            c = tile_mac<L::BLK, false>(a.head.w + lane, a.head.k8, buf0 + (first * 32 + j) * 8 + 4 * h, c);
+            add_bias16(c, bq0, bq1, bq2, bq3);
+        }
+        __syncthreads();
+        if (first < P / 32) store_tile<P>(buf0, 0, first * 32 + j, h, c);
+    }
+    __syncthreads();
+
+    // ---- log_softmax (fp_fwd_kernel's: 8 lanes per point, classes q and q + 8 per lane) into LDS blocks 4 .. 5
+    float *s_lp = buf0 + (size_t)4 * L::BLK, *s_dl = buf0 + (size_t)6 * L::BLK;
+    for (int t = tid; t < P * 8; t += NT) {
+        const int pj = t >> 3, q = t & 7;
+        const bool has0 = q < NC;
+        const float z0 = has0 ? buf0[L::off(q, pj)] : -INFINITY;
+        const bool has1 = q + 8 < NC;
+        const float z1 = has1 ? buf0[L::off(q + 8, pj)] : -INFINITY;
+        float m = fmaxf(z0, z1);
+        m = fmaxf(m, __shfl_xor(m, 1));
+        m = fmaxf(m, __shfl_xor(m, 2));
+        m = fmaxf(m, __shfl_xor(m, 4));
+        float s = (has0 ? expf(z0 - m) : 0.0f) + (has1 ? expf(z1 - m) : 0.0f);
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        s += __shfl_xor(s, 4);
+        const float lse = logf(s);
+        float *o = s_lp + pj * NC;
+        if (has0) o[q] = (z0 - m) - lse;
+        if (has1) o[q + 8] = (z1 - m) - lse;
+    }
+    __syncthreads();
+    // ---- CE row (psg_ce_row.cuh: ce_logp_grad_kernel's arithmetic), one thread per point = the first wave
+    if (tid < P) {
+        const int r = b * a.N + n0 + tid;
+        const bool active = r < a.rows_active;
+        const int y = !active ? -1 : a.labels ? a.labels[r] : a.target;
+        ce_row_grad(s_lp + tid * NC, NC, y, a.scale, active, s_dl + tid * NC);
+    }
+    __syncthreads();
+    // ---- log_softmax backward (fp_bwd_kernel's prologue): dz = dlogp - exp(logp) * sum(dlogp), four lanes per point
+    for (int t = tid; t < P * 4; t += NT) {
+        const int pj = t >> 2, q = t & 3;
+        const float *lp = s_lp + pj * NC, *dl = s_dl + pj * NC;
+        float s = 0.0f;
+        if (q == 0)
+            for (int c = 0; c < NC; ++c) s += dl[c];
+        s = __shfl(s, (tid & 63) & ~3);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = q + 4 * i;
+            buf0[L::off(c, pj)] = c < NC ? dl[c] - expf(lp[c]) * s : 0.0f;
+        }
+    }
+    __syncthreads();
+
+    // ---- backward: conv2^T, conv1^T, layer 3^T, layer 2^T, each gated by the bits of the layer below it
+    fp1_loop_pair_bwd<P>(a.t[0], buf0, first, lane, m_c1);
+    __syncthreads();
+    fp1_loop_pair_bwd<P>(a.t[1], buf0, first, lane, m_l3);
+    __syncthreads();
+    fp1_loop_pair_bwd<P>(a.t[2], buf0, first, lane, m_l2);
+    __syncthreads();
+    fp1_loop_pair_bwd<P>(a.t[3], buf0, first, lane, m_l1);
+    __syncthreads();
+    // dZ1 rows, 16 bytes per thread, 32 lanes per row (fp_bwd_kernel's output rows of the split module)
+    constexpr int RG = NT / 32, CD = 128;
+    const int ql = tid & 31, rg = tid >> 5;
+    float *d2 = a.dint_out + ((size_t)b * a.N + n0) * CD;
+    for (int pj = rg; pj < P; pj += RG)
+        *(float4 *)(d2 + (pj * CD + 4 * ql)) = *(const float4 *)(buf0 + L::off(4 * ql, pj));
 }
 
 // ------------------------------------------------------------------------------------------ per-point side of the SA split

@@ -254,6 +254,27 @@ class PN2Workspace(_Handle):
                   float(alpha), float(eps), -1.0 if descent else 1.0, 1 if last else 0, stream())
         return x0
 
+    def nb_step(self, model, slot, x0, ori, labels, alpha, eps, mask=None, target=None, last=False):
+        """One iteration of nb_attack's loop on plan slot `slot`, exactly as the attack runs it (psg_pn2_nb_step): x0
+        [B][N][9] is updated in place.  Afterwards no forward is resident for backward(): call forward() first."""
+        require_cuda(x0, "x0", torch.float32)
+        require_cuda(ori, "ori", torch.float32)
+        if labels is not None:
+            require_cuda(labels, "labels", torch.int32)
+        if mask is not None:
+            require_cuda(mask, "mask", torch.uint8)
+        assert x0.shape == (self.batch, self.n_point, 9) and ori.shape == (self.batch, self.n_point, 3) and x0.is_contiguous() and ori.is_contiguous()
+        _lib.call("psg_pn2_nb_step", model.handle, self.handle, slot, ptr(x0), ptr(ori), ptr(labels), ptr(mask), float(alpha),
+                  float(eps), 0 if target is None else 1, 0 if target is None else int(target), 1 if last else 0, stream())
+        return x0
+
+    def fp1_grad(self):
+        """fp1's first-layer gradient rows [B][N][128] as the last backward or step left them (parity tests)."""
+        src = _lib.load().psg_pn2_fp1_grad_ptr(self.handle)
+        out = torch.empty(self.batch, self.n_point, 128, dtype=torch.float32, device=self.device)
+        _hip_memcpy_d2d(out.data_ptr(), src, out.numel() * 4)
+        return out
+
     def nb_attack(self, model, images, labels, starts, eps, alpha, iters, mask=None, target=None, out=None):
         require_cuda(images, "images", torch.float32)
         require_cuda(starts, "starts", torch.int32)
@@ -271,7 +292,7 @@ class PN2Workspace(_Handle):
     PROF_TAGS = ("sa1_fwd", "sa2_fwd", "sa3_fwd", "sa4_fwd", "fp1_head_fwd", "fp2_fwd", "fp3_fwd", "fp4_fwd",
                  "fp1_head_bwd", "fp2_bwd", "fp3_bwd", "fp4_bwd", "sa1_bwd", "sa2_bwd", "sa3_bwd", "sa4_bwd",
                  "fps", "ball_query", "three_nn", "gather", "ce_grad", "pgd_step", "dx0_gather", "pw_fwd", "pw_bwd",
-                 "geom_grel", "geom_wgrad", "geom_gx", "sa_pack_plan")
+                 "geom_grel", "geom_wgrad", "geom_gx", "sa_pack_plan", "fp1_head_loop")
 
     def prof_enable(self, on=True):
         _lib.call("psg_pn2_prof_enable", self.handle, 1 if on else 0)
