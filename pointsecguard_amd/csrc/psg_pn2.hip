@@ -13,200 +13,43 @@
 //   sa3 (64, .2/.4, 259->128,196,256 | 128,196,256)             sa4 (16, .4/.8, 515->256,256,512 | 256,384,512)
 //   fp4 1536->256,256   fp3 512->256,256   fp2 352->256,128    fp1 128->128,128,128, same head
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "psg_common.h"
+#include "psg_pn2_paths.h"
 #include "psg_pn2_kernels.cuh"
 #include "psg_chain.cuh"
 #include "psg_pn2_geomgrad.cuh"
 
 using namespace psg;
+using namespace psg_pn2;
 
 namespace {
 
-constexpr int MAXL = PSG_PN2_MSG_NUM_LAYERS;   // the larger of the two layer counts
-constexpr int NCLS = PSG_PN2_NUM_CLASSES;
-const int kS[4] = {1024, 256, 64, 16};
-
-// Section-skipping timing switches of the module kernels: compiled in by `make EXTRA=-DPSG_DIAG_BUILD` only
-// (tools/diag_*.sh); the default library has no way to skip work (psg_pn2_kernels.cuh: PSG_DIAGBIT == 0).
-static inline int diag_build_bits()
+const Pn2Switches &sw()     // the process-wide switches, read once (psg_pn2_paths.h: Pn2Switches documents each)
 {
-#ifdef PSG_DIAG_BUILD
-    static const int bits = psg::env_int("PSG_DIAG", 0);
-    return bits;
-#else
-    return 0;
-#endif
+    static const Pn2Switches s = read_switches(psg::env_int, psg::env_str);
+    return s;
 }
+static inline int diag_build_bits() { return sw().diag; }
 
-// One ball-query scale of an SA level: its three conv layers, the column of its pooled output inside the level's
-// rows, and the kernel configuration (points / waves per workgroup, tiles a wave may hold across a layer's barrier).
-struct ScaleDesc {
-    int K;          // nsample: 32, or 16 (two groups per 32-point MFMA tile)
-    float r2;       // float32(radius**2) with radius**2 evaluated in double, as Python does (pointnet_util.py:102)
-    int l0;         // index of the first of its 3 layers
-    int c_off;      // first column of its C3 channels in the level's output rows
-    int P, NW, maxt_f, maxt_b;
-};
-
-struct ArchDesc {
-    int id;                 // PSG_PN2_ARCH_*
-    int ns;                 // scales per SA level
-    ScaleDesc sc[4][2];
-    int C[5];               // feature channels of level 0..4
-    int n_layers;
-    int cin[MAXL], cout[MAXL];
-    int fp_first[4], fp_count[4];   // FP module LVL (0 = fp1 .. 3 = fp4): first layer index, layer count
-    int fp_maxt_b[4];
-    int head;               // conv1; conv2 = head + 1
-    bool sa_perm;           // reference concat order is [rel_xyz, feats] (SSG) rather than [feats, rel_xyz] (MSG)
-    bool fp4_big;           // fp4's concatenated input exceeds LDS: streamed first / last layer
-    int c3(int lvl, int s) const { return cout[sc[lvl][s].l0 + 2]; }
-};
-
-ArchDesc make_ssg()
+// What SA level lvl, scale sc of an architecture runs in this process (psg_pn2_paths.h: sa_path), computed once.  The model,
+// the workspace layout, the plan and both launch functions read THIS: forward and backward cannot disagree.
+const SaPath &sa_path_of(const ArchDesc &A, int lvl, int sc)
 {
-    ArchDesc a{};
-    a.id = PSG_PN2_ARCH_SSG; a.ns = 1; a.n_layers = PSG_PN2_NUM_LAYERS; a.sa_perm = true; a.fp4_big = false;
-    const int cin[PSG_PN2_NUM_LAYERS] = {12, 32, 32, 67, 64, 64, 131, 128, 128, 259, 256, 256, 768, 256, 384, 256, 320, 256,
-                                         128, 128, 128, 128, 128};
-    const int cout[PSG_PN2_NUM_LAYERS] = {32, 32, 64, 64, 64, 128, 128, 128, 256, 256, 256, 512, 256, 256, 256, 256, 256, 128,
-                                          128, 128, 128, 128, 13};
-    for (int i = 0; i < a.n_layers; ++i) { a.cin[i] = cin[i]; a.cout[i] = cout[i]; }
-    const int C[5] = {9, 64, 128, 256, 512};
-    for (int i = 0; i < 5; ++i) a.C[i] = C[i];
-    const double r[4] = {0.1, 0.2, 0.4, 0.8};
-    // points / waves per workgroup of each module (forward and backward share P); backward tiles per wave:
-    // ceil(widest layer's tiles / waves) (sa2 67->96: 6 tiles on 4 waves; sa3 131->160: 5 on 4; sa4 259->288: 9 on 8)
-    const int P[4] = {128, 64, 32, 32}, NW[4] = {4, 4, 4, 8}, mb[4] = {1, 2, 2, 2};
-    for (int l = 0; l < 4; ++l) a.sc[l][0] = ScaleDesc{32, (float)(r[l] * r[l]), 3 * l, 0, P[l], NW[l], 1, mb[l]};
-    // layer indices: fp4 12,13  fp3 14,15  fp2 16,17  fp1 18,19,20 (+ head 21,22 fused into fp1)
-    const int ff[4] = {18, 16, 14, 12}, fc[4] = {3, 2, 2, 2}, fm[4] = {1, 2, 2, 3};   // fp2 320: 10 tiles on 8 waves; fp3 384: 12; fp4 768: 24
-    for (int l = 0; l < 4; ++l) { a.fp_first[l] = ff[l]; a.fp_count[l] = fc[l]; a.fp_maxt_b[l] = fm[l]; }
-    a.head = 21;
-    return a;
-}
-
-ArchDesc make_msg()
-{
-    ArchDesc a{};
-    a.id = PSG_PN2_ARCH_MSG; a.ns = 2; a.n_layers = PSG_PN2_MSG_NUM_LAYERS; a.sa_perm = false; a.fp4_big = true;
-    const int mlp[4][2][3] = {{{16, 16, 32}, {32, 32, 64}}, {{64, 64, 128}, {64, 96, 128}},
-                              {{128, 196, 256}, {128, 196, 256}}, {{256, 256, 512}, {256, 384, 512}}};
-    const double r[4][2] = {{0.05, 0.1}, {0.1, 0.2}, {0.2, 0.4}, {0.4, 0.8}};
-    // kernel configurations: every layer of a module must fit maxt tiles per wave (tiles = ceil(width / 32) * P / 32)
-    const int P[4][2] = {{128, 128}, {64, 64}, {32, 32}, {32, 32}}, NW[4][2] = {{4, 4}, {4, 8}, {8, 8}, {8, 8}};
-    const int mf[4][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 2}};     // sa4 scale 1: 384 -> 12 tiles on 8 waves
-    const int mbk[4][2] = {{1, 1}, {2, 1}, {2, 2}, {3, 3}};    // first layers transposed: 99 -> 8 tiles, 259 -> 9, 515 -> 17
-    a.C[0] = 9;
-    int li = 0;
-    for (int l = 0; l < 4; ++l) {
-        int coff = 0;
-        for (int s = 0; s < 2; ++s) {
-            a.sc[l][s] = ScaleDesc{s == 0 ? 16 : 32, (float)(r[l][s] * r[l][s]), li, coff, P[l][s], NW[l][s], mf[l][s], mbk[l][s]};
-            int last = a.C[l] + 3;
-            for (int j = 0; j < 3; ++j) { a.cin[li] = last; a.cout[li] = mlp[l][s][j]; last = mlp[l][s][j]; ++li; }
-            coff += mlp[l][s][2];
-        }
-        a.C[l + 1] = coff;
-    }
-    // fp4, fp3, fp2, fp1 (state_dict order), then the head
-    const int fin[4] = {a.C[3] + a.C[4], a.C[2] + 256, a.C[1] + 256, 128};
-    const int fw[4][3] = {{256, 256, 0}, {256, 256, 0}, {256, 128, 0}, {128, 128, 128}};
-    const int fm[4] = {1, 2, 2, 1};   // by LVL: fp1 1; fp2 352 -> 11 tiles on 8 waves; fp3 512 -> 16; fp4 streamed
-    for (int q = 0; q < 4; ++q) {
-        const int lvl = 3 - q, n = q == 3 ? 3 : 2;
-        a.fp_first[lvl] = li; a.fp_count[lvl] = n; a.fp_maxt_b[lvl] = fm[lvl];
-        int last = fin[q];
-        for (int j = 0; j < n; ++j) { a.cin[li] = last; a.cout[li] = fw[q][j]; last = fw[q][j]; ++li; }
-    }
-    a.head = li;
-    a.cin[li] = 128; a.cout[li] = 128; ++li;
-    a.cin[li] = 128; a.cout[li] = NCLS; ++li;
-    return a;
-}
-
-// The first layer of SA level `lvl` split into a per-point feature product and a per-row xyz chunk (psg_pn2_kernels.cuh,
-// sa_fwd_kernel SPLIT).  SSG levels 1 - 3: 8 x fewer points than grouped rows and 64 / 128 / 256 feature channels.  Level 0 stays
-// whole: its 9 feature channels are 2 of the module's 14 k8-chunk passes, the rows of T (32 floats) would be a larger gather
-// than the 12 floats it replaces, and its backward writes compact 16-byte colour rows (DESIGN.md section 6 has the numbers).
-// PSG_PN2_SPLIT=0 keeps the whole first layers everywhere (A/B runs, tests/test_gpu_alt_paths.py).
-bool arch_split(const ArchDesc &A, int lvl)
-{
-    static const bool on = psg::env_int("PSG_PN2_SPLIT", 1) != 0;
-    return on && lvl >= 1;      // SSG and MSG alike (MSG: both scales of a level; its level-0 scales stay whole like SSG's)
-}
-// PSG_PN2_SPLIT=2 (measurement): the FORWARD of level 0 split as well - T0 = W1f . x0 + b1 per point of the
-// room (9 -> 32 on the vector pipe), gathered into the accumulators like the other levels; its backward stays whole.
-bool arch_split_fwd(const ArchDesc &A, int lvl)
-{
-    static const bool l0 = psg::env_int("PSG_PN2_SPLIT", 1) == 2;
-    return arch_split(A, lvl) || (l0 && A.id == PSG_PN2_ARCH_SSG && lvl == 0);
-}
-
-// The first layer of FP module `lvl` (0 = fp1 .. 2 = fp3) split across the 3-NN interpolation (psg_pn2_kernels.cuh,
-// fp_layer1_split): its interpolated-part columns run per COARSE point inside the coarser module's kernels, forward and
-// backward.  fp4 stays whole (its coarse side is the 16 points of level 4: nothing to fuse into).  PSG_PN2_FPSPLIT=0 keeps the
-// whole first layers (A/B runs, tests/test_gpu_alt_paths.py); the wave-private fp1 kernels (PSG_FP1_WAVE=1) know no split.
-bool arch_fp_split(const ArchDesc &A, int lvl)
-{
-    static const bool on = psg::env_int("PSG_PN2_FPSPLIT", 1) != 0, wave1 = psg::env_int("PSG_FP1_WAVE", 0) != 0;
-    return on && lvl <= 2 && !(lvl == 0 && wave1);
-}
-
-// SSG: the SA forward kernels run a group's valid rows only (psg_pn2_kernels.cuh, sa_fwd_packed_kernel).  PSG_PN2_PACK=0 keeps the
-// unpacked kernels everywhere (A/B runs, tests/test_gpu_sa_pack.py); MSG (16-sample scales) always runs them.
-bool arch_pack(const ArchDesc &A)
-{
-    static const bool on = psg::env_int("PSG_PN2_PACK", 1) != 0;
-    return on && A.id == PSG_PN2_ARCH_SSG;
-}
-
-// The SA backward of a packed level runs the same packed rows (psg_pn2_kernels.cuh, sa_bwd_packed_kernel), and the level's
-// forward then keys its ReLU masks by packed workgroup.  PSG_PN2_PACK_BWD, read once per process, names the levels: unset or
-// 1 = the default set kPackBwdBuilt, 0 = none (the unpacked backward kernels and the unpacked-keyed masks, as before round 17),
-// L followed by level digits (L0, L02) = exactly those levels; a level named that way that does not fit the packed kernel's
-// configuration is an error at its launch, not a fall-back (bit 8: levels named explicitly).
-// Every level has a packed backward kernel; the default set holds the levels whose launch is faster packed in the headline
-// rooms, measured per level (rounds 19 and 27): levels 0, 1 and 2 - level 2 since its max-pool transpose
-// runs in channel order (sa_bwd_packed_chan: 82 against 100 us).  Level 3 is slower packed (too few workgroups are left to
-// hide the sparse stream's latency) and runs packed only where named (L3).
-constexpr int kPackBwdBuilt = (1 << 0) | (1 << 1) | (1 << 2);
-int pack_bwd_levels()
-{
-    static const int levels = [] {
-        const char *v = psg::env_str("PSG_PN2_PACK_BWD");
-        if (!v || !*v) return kPackBwdBuilt;
-        if (*v == 'L' || *v == 'l') {
-            int mask = 1 << 8;
-            for (const char *c = v + 1; *c; ++c)
-                if (*c >= '0' && *c <= '3') mask |= 1 << (*c - '0');
-            return mask;
-        }
-        return atoi(v) != 0 ? kPackBwdBuilt : 0;
+    static const std::vector<SaPath> t = [] {
+        std::vector<SaPath> t(16);       // [arch][level][scale]
+        for (int i = 0; i < 16; ++i)
+            if ((i & 1) < arch_of(i >> 3).ns) t[i] = sa_path(arch_of(i >> 3), sw(), (i >> 1) & 3, i & 1);
+        return t;
     }();
-    return levels;
+    return t[(A.id == PSG_PN2_ARCH_MSG ? 8 : 0) + lvl * 2 + sc];
 }
-
-// The max-pool transpose of a packed sparse level: channel order over all of a workgroup's groups (sa_bwd_packed_chan), or with
-// PSG_PN2_POOLT_ORDER=row the batches of row-ordered item lists (sa_bwd_packed_sparse).  The same bytes; read once per process.
-bool poolt_order_channel()
-{
-    static const bool chan = [] {
-        const char *v = psg::env_str("PSG_PN2_POOLT_ORDER");
-        return !(v && strcmp(v, "row") == 0);
-    }();
-    return chan;
-}
-
-const ArchDesc &arch_of(int id)
-{
-    static const ArchDesc ssg = make_ssg(), msg = make_msg();
-    return id == PSG_PN2_ARCH_MSG ? msg : ssg;
-}
+inline bool arch_split(const ArchDesc &A, int lvl) { return sa_path_of(A, lvl, 0).split_bwd; }       // (both scales of a level alike)
+inline bool arch_split_fwd(const ArchDesc &A, int lvl) { return sa_path_of(A, lvl, 0).split_fwd; }
+inline bool arch_fp_split(const ArchDesc &, int lvl) { return fp_split(sw(), lvl); }
+inline bool arch_pack(const ArchDesc &A) { return sa_path_of(A, 0, 0).packed; }
 
 struct PackedLayer {
     float4 *wf = nullptr;  // forward packing  [mb(cout)][k8(cin)][64]
@@ -262,7 +105,7 @@ struct psg_pn2_ws {
     int32_t *pk_cnt[4];   // packed SA forward (arch_pack): [F*B][S_l] valid rows of each group
     int32_t *pk_seg[4];   // [F*B][S_l / G_l + 2] workgroup segmentation (psg_pn2_kernels.cuh: sa_pack_plan_kernel)
     int4 *pk_desc[4];     // [F*B][S_l / G_l] what the packed kernel's workgroups read: one descriptor each
-    int32_t *ball0[2];    // per level-0 scale: [B][N][K] the room's ball query with every point as centroid, or null (ball_table_mode)
+    int32_t *ball0[2];    // per level-0 scale: [B][N][K] the room's ball query with every point as centroid, or null (ball_table_route)
     int32_t *nn_idx[4];   // [F*B][N_l][3]
     float *nn_w[4];
     int32_t *inv_off[4];  // inverse 3-NN lists (CSR by coarse point): [F*B][S_l + 1]
@@ -390,16 +233,19 @@ enum { TAG_SA_FWD = 0, TAG_FP_FWD = 4, TAG_FP_BWD = 8, TAG_SA_BWD = 12, TAG_FPS 
        TAG_COUNT = 30 };   // 25-27: psg_pn2_backward_full only; 29: the NB loop's fp1 + head forward, CE and backward in one launch
 
 // Every launch with a dynamic LDS buffer of `blocks8` blocks of `blk` floats goes through here: size check, the shared LDS
-// opt-in above 48 KiB, the profile scope and the launch check.  `site` is the CALLER's launch site (PSG_SITE, psg_common.h).
+// opt-in above 48 KiB, the profile scope and the launch check.  `site` is the CALLER's launch site (PSG_SITE, psg_common.h);
+// a launch line that serves several kernels passes the "#variant" chosen at run time, appended when the tracer is on.
 template <typename KernelT, typename ArgsT>
 int launch_lds(psg_pn2_ws *ws, int tag, const char *site, KernelT kern, dim3 grid, int threads, int blocks8, int blk,
-               const ArgsT &args, hipStream_t st)
+               const ArgsT &args, hipStream_t st, const char *variant = nullptr)
 {
     size_t lds = (size_t)blocks8 * blk * sizeof(float);
     if (lds > 160 * 1024) { set_error("LDS request %zu exceeds 160 KiB", lds); return PSG_ERR_ARG; }
     if (lds > 48 * 1024) PSG_CHECK_HIP(psg::allow_big_lds((const void *)kern));
     EvScope prof(&ws->prof, tag, 0.0, st);
     hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, args);
+    char full[192];
+    if (variant && psg::trace_sync_enabled()) site = (snprintf(full, sizeof full, "%s%s", site, variant), full);
     PSG_LAUNCH_CHECK_AT(site);
     return PSG_OK;
 }
@@ -411,40 +257,21 @@ inline int gsa_stride(const ArchDesc &A, int lvl)
     return lvl == 0 ? 12 : A.C[lvl];
 }
 
-#define PSG_CFG_KEY(P, NW, KS, MT) ((P) * 10000 + (NW) * 1000 + (KS) * 10 + (MT))
-
-// Max-pool transpose as a sparse weight-row stream (psg_pn2_kernels.cuh: sa_pool_t_sparse) where the level's shapes fit it:
-// SSG levels 1 - 3 (sa1: C2 = 32 is half a wave's lanes; MSG: KS = 16 and C2 = 96 / 196 / 384).  PSG_PN2_POOLT_SPARSE=0 keeps
-// the dense transposed layer on the matrix pipe.  Returns SPV = C2 / 64, or 0 for the dense layer.
-int sa_sparse_spv(const ScaleDesc &d, const PackedLayer *L, bool w1c)
+// Calls f(Row{}) for row `row` of the kernel table: a compare chain over the type list (psg_pn2_paths.h: SaRows)
+template <class F, class... R> int sa_visit(SaRowList<R...>, int row, F &&f)
 {
-    static const bool poolt_sparse = psg::env_int("PSG_PN2_POOLT_SPARSE", 1) != 0;
-    const int C3 = L[2].cout, C2 = L[2].cin, NT = d.NW * 64;
-    return poolt_sparse && L[2].wr && d.K == 32 && d.P <= 64 && (d.P / d.K) * C3 <= NT && C3 % 64 == 0 && !w1c &&
-           (C2 == 64 || C2 == 128 || C2 == 256) ? C2 / 64 : 0;
+    int rc = PSG_ERR_STATE, i = 0;
+    (void)((i++ == row ? (rc = f(R{}), true) : false) || ...);
+    return rc;
 }
 
-// Does the backward of SA level lvl run packed?  The ONE place that decides it: run_sa_fwd keys the level's ReLU masks by it and
-// run_sa_bwd picks the kernel by it.  Needs the plan's descriptors (SSG under PSG_PN2_PACK) and the level named by
-// PSG_PN2_PACK_BWD; by default also the configuration the kernel is built for - SSG as shipped: level 0 whole, level 1 split, so
-// that the pooled-output gradient of level 0 arrives as plain rows - and any other (PSG_PN2_SPLIT) keeps the unpacked backward.
-// Levels 1 - 3 qualify in the shipped configuration only: forward and backward split (the forward then takes the packed path,
-// run_sa_fwd; the rows stored are dZ1), the max-pool transpose as the sparse stream (sa_sparse_spv), and the pooled gradient
-// as plain rows (levels 1 and 2: the level above split) or level 3's nninv gather.
-bool sa_pack_bwd_level(const psg_pn2_model *m, const psg_pn2_ws *ws, int lvl)
-{
-    const int levels = pack_bwd_levels();
-    if (!ws->pk_cnt[lvl] || !((levels >> lvl) & 1)) return false;
-    if (levels >> 8) return true;                                  // named explicitly: run_sa_fwd / run_sa_bwd fail where it does not fit
-    if (lvl == 0) return !m->split_fwd[0] && !m->split[0] && m->split[1];
-    return m->split_fwd[lvl] && m->split[lvl] && (lvl == 3 || m->split[lvl + 1]) &&
-           sa_sparse_spv(m->arch->sc[lvl][0], &m->L[m->arch->sc[lvl][0].l0], false) > 0;
-}
-
+// An SA module's two launches: the kernel FAMILY from the level's path (sa_path_of), the template arguments from the scale's row;
+// `if constexpr` on the row's flags keeps the instantiations to what the table names.  Site: the launch line + sa_site's variant.
 int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const float *x0, hipStream_t st)
 {
     const ArchDesc &A = *m->arch;
     const ScaleDesc &d = A.sc[lvl][sc];
+    const SaPath &path = sa_path_of(A, lvl, sc);
     const int B = ws->B, S = kS[lvl], Np = ws->Nl[lvl], D = A.C[lvl], KS = d.K, P = d.P, NW = d.NW;
     const PackedLayer *L = &m->L[d.l0];
     const size_t prob = (size_t)fwd * B;
@@ -459,7 +286,7 @@ int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const
     a.ld_out = A.C[lvl + 1];
     a.c_out = d.c_off;
     a.arg = ws->arg[lvl][sc];
-    const bool split = m->split_fwd[lvl];
+    const bool split = path.split_fwd;
     a.l1 = fwd_layer(split ? m->sx[lvl][sc] : L[0], true, ws->mask[d.l0]);
     a.l2 = fwd_layer(L[1], true, ws->mask[d.l0 + 1]);
     a.w3 = L[2].wf; a.b3 = L[2].bias; a.k8_3 = L[2].k8f(); a.nb3 = L[2].mbf();
@@ -474,86 +301,42 @@ int run_sa_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, const
     }
     const dim3 grid(S / (P / KS), B);
     const int tag = TAG_SA_FWD + lvl;
-    a.pk_desc = nullptr; a.pk_tab_off = 0;
-    // packed rows (SSG as shipped: level 0 whole, levels 1 - 3 split); any other first-layer form keeps the unpacked kernels
+    const SaKernel fam = sa_fwd_family(path);
+    if (fam == SaKernel::error) { set_error("run_sa_fwd level %d: %s", lvl, path.fwd_error); return PSG_ERR_STATE; }
+    // packed rows: the [P][C3] pool rows over the activation buffer, the row maps behind the buffer
     const int blk = P * 8 + PSG_LDS_PAD;                           // Lds<P>::BLK
-    // (LDS: the [P][C3] pool rows over the activation buffer; the row maps behind the buffer, the group starts in pool row P - 1)
-    const bool pkm = sa_pack_bwd_level(m, ws, lvl);                  // masks keyed by packed workgroup: the backward runs packed
-    if (ws->pk_cnt[lvl] && KS == 32 && d.maxt_f == 1 && split == (lvl >= 1) && a.nb3 * (P / 32) == 2 * NW &&
-        blocks * blk + 2 * P <= (P - 1) * a.C3 && (P * a.C3) % blk == 0) {
-        a.pk_desc = ws->pk_desc[lvl] + prob * grid.x;
-        a.pk_tab_off = blocks * blk;
-        const int pblocks = P * a.C3 / blk;
-        if (pkm) {
-            switch (PSG_CFG_KEY(P, NW, KS, split ? 1 : 0)) {
-            case PSG_CFG_KEY(128, 4, 32, 0): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<128, 4, false, true>), grid, 4 * 64, pblocks, blk, a, st);
-            case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<64, 4, true, true>), grid, 4 * 64, pblocks, blk, a, st);
-            case PSG_CFG_KEY(32, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 4, true, true>), grid, 4 * 64, pblocks, blk, a, st);
-            case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 8, true, true>), grid, 8 * 64, pblocks, blk, a, st);
-            }
-            set_error("run_sa_fwd level %d: PSG_PN2_PACK_BWD names a level without a packed-key forward kernel (P=%d NW=%d)", lvl, P, NW);
-            return PSG_ERR_STATE;
+    a.pk_desc = path.packed_fwd ? ws->pk_desc[lvl] + prob * grid.x : nullptr;
+    a.pk_tab_off = path.packed_fwd ? blocks * blk : 0;
+    const int lds_blocks = path.packed_fwd ? P * a.C3 / blk : blocks;
+    const SaSite site = sa_site(SaRows::cfg[d.row], fam, lvl, false, psg::trace_sync_enabled());
+    return sa_visit(SaRows{}, d.row, [&](auto row) -> int {
+        using R = decltype(row);
+        auto go = [&](auto kern) { return launch_lds(ws, tag, PSG_SITE, kern, grid, R::NW * 64, lds_blocks, Lds<R::P>::BLK, a, st, site.text); };
+        if constexpr ((R::V & (V_PACK0 | V_PACK)) != 0) {
+            if (fam == SaKernel::fwd_packed_keys) return go(sa_fwd_packed_kernel<R::P, R::NW, (R::V & V_PACK) != 0, true>);
+            if (fam == SaKernel::fwd_packed) return go(sa_fwd_packed_kernel<R::P, R::NW, (R::V & V_PACK) != 0>);
         }
-        switch (PSG_CFG_KEY(P, NW, KS, split ? 1 : 0)) {
-        case PSG_CFG_KEY(128, 4, 32, 0): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<128, 4, false>), grid, 4 * 64, pblocks, blk, a, st);
-        case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<64, 4, true>), grid, 4 * 64, pblocks, blk, a, st);
-        case PSG_CFG_KEY(32, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 4, true>), grid, 4 * 64, pblocks, blk, a, st);
-        case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE "#packed", (sa_fwd_packed_kernel<32, 8, true>), grid, 8 * 64, pblocks, blk, a, st);
-        }
-        a.pk_desc = nullptr; a.pk_tab_off = 0;
-    }
-    if (pkm) {
-        set_error("run_sa_fwd level %d: the packed backward (PSG_PN2_PACK_BWD) needs the packed forward, which this configuration does not run", lvl);
+        if constexpr ((R::V & V_SPLIT) != 0)
+            if (fam == SaKernel::fwd_split) return go(sa_fwd_kernel<R::P, R::NW, R::K, R::MF, true>);
+        if (fam == SaKernel::fwd_whole) return go(sa_fwd_kernel<R::P, R::NW, R::K, R::MF>);
+        set_error("run_sa_fwd: no split kernel for P=%d NW=%d K=%d MAXT=%d", R::P, R::NW, R::K, R::MF);
         return PSG_ERR_STATE;
-    }
-#define PSG_SA_FWD_CASE(P_, NW_, KS_, MT_) \
-    case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
-        return launch_lds(ws, tag, PSG_SITE, sa_fwd_kernel<P_, NW_, KS_, MT_>, grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
-    if (split) {
-        switch (PSG_CFG_KEY(P, NW, KS, d.maxt_f)) {
-        case PSG_CFG_KEY(128, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<128, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<128>::BLK, a, st);
-        case PSG_CFG_KEY(64, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<64, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);
-        case PSG_CFG_KEY(32, 4, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 4, 32, 1, true>), grid, 4 * 64, blocks, Lds<32>::BLK, a, st);
-        case PSG_CFG_KEY(32, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 8, 32, 1, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);
-        case PSG_CFG_KEY(64, 4, 16, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<64, 4, 16, 1, true>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);   // MSG sa2 scale 0
-        case PSG_CFG_KEY(64, 8, 32, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<64, 8, 32, 1, true>), grid, 8 * 64, blocks, Lds<64>::BLK, a, st);   // MSG sa2 scale 1
-        case PSG_CFG_KEY(32, 8, 16, 1): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 8, 16, 1, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // MSG sa3 / sa4 scale 0
-        case PSG_CFG_KEY(32, 8, 32, 2): return launch_lds(ws, tag, PSG_SITE, (sa_fwd_kernel<32, 8, 32, 2, true>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // MSG sa4 scale 1
-        }
-        set_error("run_sa_fwd: no split kernel for P=%d NW=%d K=%d MAXT=%d", P, NW, KS, d.maxt_f);
-        return PSG_ERR_STATE;
-    }
-    switch (PSG_CFG_KEY(P, NW, KS, d.maxt_f)) {
-        PSG_SA_FWD_CASE(128, 4, 32, 1);   // SSG sa1, MSG sa1 scale 1
-        PSG_SA_FWD_CASE(64, 4, 32, 1);    // SSG sa2
-        PSG_SA_FWD_CASE(32, 4, 32, 1);    // SSG sa3
-        PSG_SA_FWD_CASE(32, 8, 32, 1);    // SSG sa4, MSG sa3 scale 1
-        PSG_SA_FWD_CASE(128, 4, 16, 1);   // MSG sa1 scale 0
-        PSG_SA_FWD_CASE(64, 4, 16, 1);    // MSG sa2 scale 0
-        PSG_SA_FWD_CASE(64, 8, 32, 1);    // MSG sa2 scale 1
-        PSG_SA_FWD_CASE(32, 8, 16, 1);    // MSG sa3 / sa4 scale 0
-        PSG_SA_FWD_CASE(32, 8, 32, 2);    // MSG sa4 scale 1
-    }
-#undef PSG_SA_FWD_CASE
-    set_error("run_sa_fwd: no kernel for P=%d NW=%d K=%d MAXT=%d", P, NW, KS, d.maxt_f);
-    return PSG_ERR_STATE;
+    });
 }
 
 int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c_lo, int c_hi, hipStream_t st)
 {
     const ArchDesc &A = *m->arch;
     const ScaleDesc &d = A.sc[lvl][sc];
+    const SaPath &path = sa_path_of(A, lvl, sc);
     const int B = ws->B, S = kS[lvl], Np = ws->Nl[lvl], D = A.C[lvl], KS = d.K, P = d.P, NW = d.NW;
     const PackedLayer *L = &m->L[d.l0];
     const size_t prob = (size_t)fwd * B;
-    SaBwdArgs a;
+    SaBwdArgs a{};            // (no nninv gather, no inverse group lists unless set below)
     a.diag = diag_build_bits();
     a.ld = A.C[lvl + 1];
     a.c_off = d.c_off;
     a.dout = ws->dact[lvl];   // skip-link gradient rows written by fp_bwd level lvl + 1
-    a.nninv_off = nullptr; a.nninv_ent = nullptr; a.dint = nullptr; a.n_fine = 0;
-    a.ginv_off = nullptr; a.gsa = nullptr; a.g_rows = 0;
-    a.ginv_off2 = nullptr; a.gsa2 = nullptr; a.g_rows2 = 0;
     if (lvl < 3 && m->split[lvl + 1]) {
         a.dout = ws->dsum[lvl];   // skip-link rows + the transposed grouping of level lvl + 1, summed per point by pw_bwd_kernel
     } else if (lvl < 3) {   // plus the transposed grouping of SA level lvl + 1, gathered through its inverse lists
@@ -571,10 +354,11 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
         set_error("run_sa_bwd level %d scale %d: %d max-pool tasks exceed 4 per thread", lvl, sc, P * (C3 / 8));
         return PSG_ERR_STATE;
     }
+    const bool colour = lvl == 0 && c_hi - c_lo == 3;   // colour-only: compact float4 rows
     a.gsa_out = ws->gsa[lvl][sc];
     a.gpos_out = ws->ginv_pos[lvl][sc] + prob * S * KS;
-    a.cg_out = (lvl == 0 && c_hi - c_lo == 3) ? 4 : gsa_stride(A, lvl);   // colour-only: compact float4 rows
-    a.split = m->split[lvl] ? 1 : 0;
+    a.cg_out = colour ? 4 : gsa_stride(A, lvl);
+    a.split = path.split_bwd ? 1 : 0;
     if (a.split) { c_lo = 0; c_hi = L[0].cout; }   // the rows stored are dZ1 [C1]
     if (lvl == 3) {   // l4_points feed only fp4: its gradient is gathered from fp4's interpolated-part rows
         a.dout = nullptr;
@@ -590,15 +374,13 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     a.l1t = bwd_layer(L[0], nullptr);
     a.D = D; a.Np = Np; a.S = S; a.C3 = C3;
     a.c_lo = c_lo; a.c_hi = c_hi;
-    // colour-only request at level 0: three of the first layer's columns on the vector pipe (psg_pn2_kernels.cuh: sa_l1t_colour;
-    // PSG_PN2_L1T_COLOUR=0 keeps the transposed layer on the matrix pipe)
-    static const bool l1t_colour = psg::env_int("PSG_PN2_L1T_COLOUR", 1) != 0;
-    a.w1c = nullptr; a.C1 = L[0].cout; a.w1c_off = 0;
-    if (l1t_colour && a.cg_out == 4 && !a.split && P == 32 * NW && (a.C1 == 16 || a.C1 == 32)) a.w1c = m->w1feat[sc];
-    // max-pool transpose as a sparse weight-row stream (sa_sparse_spv).  The sparse pass needs no dZ3 tile: the buffer is sized
+    // colour-only request at level 0: three of the first layer's columns on the vector pipe (psg_pn2_kernels.cuh: sa_l1t_colour)
+    a.w1c = sa_w1c(path, colour) ? m->w1feat[sc] : nullptr;
+    a.C1 = L[0].cout;
+    // max-pool transpose as a sparse weight-row stream (SaPath::spv).  The sparse pass needs no dZ3 tile: the buffer is sized
     // without l3t's K.
     const int C2 = L[2].cin, NT = NW * 64;
-    const int spv = sa_sparse_spv(d, L, a.w1c != nullptr);
+    const int spv = sa_spv(path, colour);
     const int l3_blocks = spv ? a.l3t.mb * 4 : layer_blocks(a.l3t.k8, a.l3t.mb);
     const int main_blocks = std::max(std::max(l3_blocks, layer_blocks(a.l2t.k8, a.l2t.mb)),
                                      a.split ? 0 : layer_blocks(a.l1t.k8, a.l1t.mb)) + PSG_LDS_SPARE;
@@ -609,28 +391,11 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     // sparse: item list [NT] int2, count / offset table [NW][32], row starts [P + 1]
     a.sp_off = round_up(a.pos_off + P, 4);
     a.w3r = spv ? L[2].wr : nullptr;
-    // packed backward: the same packed rows as the level's forward, masks at the packed key (sa_pack_bwd_level).  Its row map
-    // [P] lies behind the output slots; the pooled-output gradient must be plain rows (the split level above sums them per point)
-    // Levels 1 - 3 (sparse): split, G * C3 == NT (a batch of the packed kernel is one unpacked workgroup's pass), one tile per
-    // wave in l2t and the mask pass, the pooled gradient as plain rows or (level 3) the nninv gather alone; the first packed row
-    // of each group [SA_PACK_GCAP + 1] lies behind the sparse pass's row starts.
-    const bool packed = sa_pack_bwd_level(m, ws, lvl);
-    if (packed) {
-        const bool dense0 = !spv && !a.split && a.dout && !a.nninv_off && !a.ginv_off && !((a.ld | a.c_off) & 3) && !(C3 & 7) &&
-                            PSG_CFG_KEY(P, NW, KS, d.maxt_b) == PSG_CFG_KEY(128, 4, 32, 1);
-        const bool sparse = spv && a.split && m->split_fwd[lvl] && !a.ginv_off && (a.dout != nullptr) != (a.nninv_off != nullptr) &&
-                            (P / KS) * C3 == NT && std::max(a.l3t.mb, a.l2t.mb) * (P / 32) <= NW &&
-                            (PSG_CFG_KEY(P, NW, KS, spv) == PSG_CFG_KEY(64, 4, 32, 1) || PSG_CFG_KEY(P, NW, KS, spv) == PSG_CFG_KEY(32, 4, 32, 2) ||
-                             PSG_CFG_KEY(P, NW, KS, spv) == PSG_CFG_KEY(32, 8, 32, 4));
-        if (!dense0 && !sparse) {
-            set_error("run_sa_bwd level %d: PSG_PN2_PACK_BWD names a level without a packed backward kernel in this configuration", lvl);
-            return PSG_ERR_STATE;
-        }
-    }
-    // Channel-ordered transpose of the packed sparse levels whose pooled gradient is plain rows, levels 1 and 2
-    // (sa_bwd_packed_chan: its group starts lie inside the batches' staging); PSG_PN2_POOLT_ORDER=row keeps the batches of
-    // sa_pool_t_sparse there (A/B runs, tests/test_gpu_sa_poolt_order.py), which level 3 always runs.
-    const bool chan = packed && (spv == 1 || spv == 2) && a.dout && !a.nninv_off && poolt_order_channel();
+    const SaKernel fam = sa_bwd_family(path, colour);
+    if (fam == SaKernel::error) { set_error("run_sa_bwd level %d: %s", lvl, path.bwd_error); return PSG_ERR_STATE; }
+    // packed backward: the same packed rows as the level's forward, masks at the packed key.  Its row map [P] lies behind the
+    // output slots; levels 1 - 3: the first packed row of each group [SA_PACK_GCAP + 1] lies behind the sparse pass's row starts.
+    const bool packed = path.packed_bwd != SaPath::none;
     const int staged = spv ? a.sp_off + 2 * NT + NW * 32 + P + 1 + (packed ? SA_PACK_GCAP + 1 : 0) : a.pos_off + P + (packed ? P : 0);
     const int blocks = main_blocks + ceil_div(staged, blk_floats);
     if (std::max(std::max(a.l3t.mb, a.l2t.mb), a.split ? 0 : a.l1t.mb) * (P / 32) > d.maxt_b * NW) {
@@ -639,50 +404,21 @@ int run_sa_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, int c
     }
     const dim3 grid(S / (P / KS), B);
     const int tag = TAG_SA_BWD + lvl;
-    if (packed) {
-        const SaBwdPackedArgs pa{a, ws->pk_desc[lvl] + prob * grid.x};
-        if (chan) {
-            switch (spv) {
-            case 1: return launch_lds(ws, tag, PSG_SITE "#chan#sa2#bwd#packed", (sa_bwd_packed_kernel<64, 4, 1, 1 + SA_PACK_CHAN>), grid, 4 * 64, blocks, Lds<64>::BLK, pa, st);   // SSG sa2
-            case 2: return launch_lds(ws, tag, PSG_SITE "#chan#sa3#bwd#packed", (sa_bwd_packed_kernel<32, 4, 1, 2 + SA_PACK_CHAN>), grid, 4 * 64, blocks, Lds<32>::BLK, pa, st);   // SSG sa3
-            }
-        }
-        switch (spv) {
-        case 1: return launch_lds(ws, tag, PSG_SITE "#sa2#bwd#packed", (sa_bwd_packed_kernel<64, 4, 1, 1>), grid, 4 * 64, blocks, Lds<64>::BLK, pa, st);   // SSG sa2
-        case 2: return launch_lds(ws, tag, PSG_SITE "#sa3#bwd#packed", (sa_bwd_packed_kernel<32, 4, 1, 2>), grid, 4 * 64, blocks, Lds<32>::BLK, pa, st);   // SSG sa3
-        case 4: return launch_lds(ws, tag, PSG_SITE "#sa4#bwd#packed", (sa_bwd_packed_kernel<32, 8, 1, 4>), grid, 8 * 64, blocks, Lds<32>::BLK, pa, st);   // SSG sa4
-        }
-        if (a.w1c) return launch_lds(ws, tag, PSG_SITE "#colour#bwd#packed", (sa_bwd_packed_kernel<128, 4, 1, 0>), grid, 4 * 64, blocks, Lds<128>::BLK, pa, st);
-        return launch_lds(ws, tag, PSG_SITE "#bwd#packed", (sa_bwd_packed_kernel<128, 4, 1, 0>), grid, 4 * 64, blocks, Lds<128>::BLK, pa, st);
-    }
-#define PSG_SA_BWD_CASE(P_, NW_, KS_, MT_) \
-    case PSG_CFG_KEY(P_, NW_, KS_, MT_): \
-        if (a.w1c) return launch_lds(ws, tag, PSG_SITE "#colour", (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st); \
-        return launch_lds(ws, tag, PSG_SITE, (sa_bwd_kernel<P_, NW_, MT_, KS_>), grid, NW_ * 64, blocks, Lds<P_>::BLK, a, st)
-    if (spv) {
-        switch (PSG_CFG_KEY(P, NW, KS, d.maxt_b) * 8 + spv) {
-        case PSG_CFG_KEY(64, 4, 32, 2) * 8 + 1: return launch_lds(ws, tag, PSG_SITE, (sa_bwd_sparse_kernel<64, 4, 2, 1>), grid, 4 * 64, blocks, Lds<64>::BLK, a, st);   // SSG sa2
-        case PSG_CFG_KEY(32, 4, 32, 2) * 8 + 2: return launch_lds(ws, tag, PSG_SITE, (sa_bwd_sparse_kernel<32, 4, 2, 2>), grid, 4 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa3
-        case PSG_CFG_KEY(32, 8, 32, 2) * 8 + 4: return launch_lds(ws, tag, PSG_SITE, (sa_bwd_sparse_kernel<32, 8, 2, 4>), grid, 8 * 64, blocks, Lds<32>::BLK, a, st);   // SSG sa4
-        }
-        set_error("run_sa_bwd: no sparse kernel for P=%d NW=%d MAXT=%d C2=%d", P, NW, d.maxt_b, C2);
+    const SaBwdPackedArgs pa{a, packed ? ws->pk_desc[lvl] + prob * grid.x : nullptr};
+    const SaSite site = sa_site(SaRows::cfg[d.row], fam, lvl, a.w1c != nullptr, psg::trace_sync_enabled());
+    return sa_visit(SaRows{}, d.row, [&](auto row) -> int {
+        using R = decltype(row);
+        auto go = [&](auto kern, const auto &args) { return launch_lds(ws, tag, PSG_SITE, kern, grid, R::NW * 64, blocks, Lds<R::P>::BLK, args, st, site.text); };
+        if constexpr ((R::V & V_CHAN) != 0)
+            if (fam == SaKernel::bwd_packed_chan) return go(sa_bwd_packed_kernel<R::P, R::NW, 1, R::SPV + SA_PACK_CHAN>, pa);
+        if constexpr ((R::V & (V_PACK0 | V_PACK)) != 0)
+            if (fam == SaKernel::bwd_packed_dense0 || fam == SaKernel::bwd_packed_sparse) return go(sa_bwd_packed_kernel<R::P, R::NW, 1, R::SPV>, pa);
+        if constexpr (R::SPV != 0)
+            if (fam == SaKernel::bwd_sparse && spv == R::SPV) return go(sa_bwd_sparse_kernel<R::P, R::NW, R::MB, R::SPV>, a);
+        if (fam == SaKernel::bwd_dense) return go(sa_bwd_kernel<R::P, R::NW, R::MB, R::K>, a);
+        set_error("run_sa_bwd: no sparse kernel for P=%d NW=%d MAXT=%d C2=%d", R::P, R::NW, R::MB, C2);
         return PSG_ERR_STATE;
-    }
-    switch (PSG_CFG_KEY(P, NW, KS, d.maxt_b)) {
-        PSG_SA_BWD_CASE(128, 4, 32, 1);   // SSG sa1, MSG sa1 scale 1
-        PSG_SA_BWD_CASE(64, 4, 32, 2);    // SSG sa2
-        PSG_SA_BWD_CASE(32, 4, 32, 2);    // SSG sa3
-        PSG_SA_BWD_CASE(32, 8, 32, 2);    // SSG sa4, MSG sa3 scale 1
-        PSG_SA_BWD_CASE(128, 4, 16, 1);   // MSG sa1 scale 0
-        PSG_SA_BWD_CASE(64, 4, 16, 2);    // MSG sa2 scale 0
-        PSG_SA_BWD_CASE(64, 8, 32, 1);    // MSG sa2 scale 1
-        PSG_SA_BWD_CASE(32, 8, 16, 2);    // MSG sa3 scale 0
-        PSG_SA_BWD_CASE(32, 8, 16, 3);    // MSG sa4 scale 0
-        PSG_SA_BWD_CASE(32, 8, 32, 3);    // MSG sa4 scale 1
-    }
-#undef PSG_SA_BWD_CASE
-    set_error("run_sa_bwd: no kernel for P=%d NW=%d K=%d MAXT=%d", P, NW, KS, d.maxt_b);
-    return PSG_ERR_STATE;
+    });
 }
 
 // FP module `LVL` (0 = fp1 ... 3 = fp4) upsamples level LVL+1 -> level LVL.
@@ -696,15 +432,6 @@ inline int fp_in2_slot(int lvl) { return lvl == 3 ? 3 : fp_out_slot(lvl + 1); }
 // P: it decides the ReLU mask layout; both take it from the level's point count.
 template <int LVL> struct FpCfg { static constexpr int P = 32, P2 = 32, NW = 8; };
 template <> struct FpCfg<0> { static constexpr int P = 32, P2 = PSG_MLP_PAIRS ? 64 : 32, NW = 4; };
-
-// PSG_FP1_WAVE=1 selects the wave-private fp1 + head kernels (psg_chain.cuh) instead of the workgroup-cooperative
-// ones.  Measured on MI355X at a 32-room device batch: forward 193 vs 193 us, backward 211 vs 189 us, so the
-// cooperative kernels stay the default (DESIGN.md section 4 has the analysis).
-inline bool fp1_wave()
-{
-    static const bool v = psg::env_int("PSG_FP1_WAVE", 0) != 0;
-    return v;
-}
 
 // level 0 forward split (PSG_PN2_SPLIT=2): T0[n][c] = b1[c] + sum_k W1f[c][k] x0[n][k], one thread per (point, 4 channels)
 __global__ void pw9_fwd_kernel(const float *__restrict__ x0, const float *__restrict__ w, const float *__restrict__ bias, size_t rows,
@@ -728,33 +455,17 @@ __global__ void pw9_fwd_kernel(const float *__restrict__ x0, const float *__rest
     *(float4 *)(out + n * 32 + c0) = make_float4(r[0], r[1], r[2], r[3]);
 }
 
-// PSG_PN2_PW_SIZED=0 keeps the per-point launches of the split SA levels as they were: the forward product on the borrowed
-// fp_fwd_kernel<32, 8> (a skip part only), its gradient on pw_bwd_kernel<32, 8> whatever the layer's width (A/B runs,
-// tests/test_gpu_pw_sized.py).  Default: workgroups with as many waves as the layer has output tiles (run_pw_fwd, run_pw_bwd).
-// Either way every tile runs the same k-loop over the whole K: the two paths are bit-identical.
-inline bool pw_sized()
-{
-    static const bool v = psg::env_int("PSG_PN2_PW_SIZED", 1) != 0;
-    return v;
-}
-
 // Level-0 ball query of a plan (psg_pn2_plan_build).  A plan of n_forward forwards queries n_forward x 1024 centroids per room,
 // every one of them a point of the room; the table route queries each of the room's N points once and copies rows
 // (group_from_table_kernel).  It is taken when the plan asks for at least BALL_TABLE_C x N centroids per room: the colour
 // attacks' plans (40 forwards: 40 960 against 4 096; the NU plans: 10 or 11 forwards), not a one-forward evaluation plan, and
 // not the coordinate attacks, which rebuild a one-forward plan whenever xyz moves (the table would be built for 1024 rows).
-// PSG_PN2_BALL_TABLE=0: always the direct query (A/B runs, tests/test_gpu_ball_table.py); =2: the table for every plan (the
-// measurement of the threshold).  Integer results: the two routes are equal or one is wrong.
+// Pn2Switches::ball_table = 0 / 2 forces the direct query / the table.
 constexpr int BALL_TABLE_C = 2;
 static_assert(1 * 1024 < BALL_TABLE_C * 1024, "a one-forward plan stays on the direct route at every n_point a workspace accepts");
-inline int ball_table_mode()
-{
-    static const int v = psg::env_int("PSG_PN2_BALL_TABLE", 1);
-    return v;
-}
 inline bool ball_table_route(int n_forward, int N)
 {
-    const int mode = ball_table_mode();
+    const int mode = sw().ball_table;
     if (mode == 0 || mode == 2) return mode == 2;
     return (long long)n_forward * kS[0] >= (long long)BALL_TABLE_C * N;
 }
@@ -775,7 +486,7 @@ int run_pw_fwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
         PSG_LAUNCH_CHECK();
         return PSG_OK;
     }
-    if (pw_sized()) {
+    if (sw().pw_sized) {
         PwFwdArgs p;
         p.in = ws->act[lvl - 1]; p.out = ws->tfeat[lvl][sc];
         p.l = fwd_layer(F, false, nullptr);
@@ -829,7 +540,7 @@ int run_pw_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int lvl, int sc, int fwd, hipSt
         set_error("run_pw_bwd level %d: unsupported shape", lvl);
         return PSG_ERR_STATE;
     }
-    if (pw_sized() && a.wt.mb <= 4) {    // (D <= 128: one float4 piece of a skip-link row per thread)
+    if (sw().pw_sized && a.wt.mb <= 4) {    // (D <= 128: one float4 piece of a skip-link row per thread)
         const int blocks = layer_blocks(a.wt.k8, a.wt.mb) + PSG_LDS_SPARE;
         return launch_lds(ws, TAG_PW_BWD, PSG_SITE "#nw4", (pw_bwd_kernel<P, 4, 1, 1>), dim3(N / P, B), 4 * 64, blocks, Lds<P>::BLK, a, st);
     }
@@ -847,7 +558,7 @@ int run_fp_fwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStre
     const int B = ws->B, N = ws->Nl[LVL], S = ws->Nl[LVL + 1];
     const size_t prob = (size_t)fwd * B;
     const int first = A.fp_first[LVL], head = A.head;
-    if (LVL == 0 && fp1_wave()) {
+    if (LVL == 0 && sw().fp1_wave) {
         // fp1 + classifier head as a wave-private chain (psg_chain.cuh): one wave per 32 points, no barriers
         Fp1FwdArgs w;
         w.feat2 = ws->act[fp_in2_slot(0)];
@@ -931,10 +642,10 @@ int run_fp_fwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *logp, hipStre
     blocks += PSG_LDS_SPARE;
     if constexpr (LVL == 3) if (big) {
         if (a.C1 % 4 || a.C2 % 4 || (a.C1 % 512) || !a.feat1) { set_error("run_fp_fwd: streamed fp4 wants C1 a multiple of 512"); return PSG_ERR_STATE; }
-        return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, true>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
+        return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, true>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st, "#big");
     }
-    if (a.tsrc) return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
-    return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st);
+    return launch_lds(ws, TAG_FP_FWD + LVL, PSG_SITE, (fp_fwd_kernel<P, NW, false>), dim3(N / P, B), NW * 64, blocks, Lds<P>::BLK, a, st,
+                      a.tsrc ? "#tsrc" : "#whole");
 }
 
 template <int LVL, int P>
@@ -945,7 +656,7 @@ int run_fp_bwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, c
     const int B = ws->B, N = ws->Nl[LVL], S = ws->Nl[LVL + 1];
     const size_t prob = (size_t)fwd * B;
     const int first = A.fp_first[LVL], cnt = A.fp_count[LVL], head = A.head;
-    if (LVL == 0 && fp1_wave()) {
+    if (LVL == 0 && sw().fp1_wave) {
         Fp1BwdArgs w;
         w.logp = logp; w.dlogp = dlogp;
         for (int i = 0; i < 4; ++i) w.mask[i] = (const unsigned long long *)ws->mask[i < 3 ? first + i : head];
@@ -1027,18 +738,20 @@ int run_fp_bwd_p(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, c
     }
     blocks += PSG_LDS_SPARE;
     const dim3 grid(N / P, B);
-    if constexpr (LVL == 3) if (big) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 1, true>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
-    // (fp1 + head: 128-wide layers on 4 waves, one tile per wave at 32 points, one pair at 64; the 8-wave modules have
-    // ragged layers)
+    auto go = [&](auto kern, const char *variant) {
+        return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, kern, grid, NW * 64, blocks, Lds<P>::BLK, a, st, variant);
+    };
+    if constexpr (LVL == 3) if (big) return go(fp_bwd_kernel<P, NW, 1, true>, "#big");
+    // (fp1 + head: 128-wide layers on 4 waves, one tile per wave at 32 points, two tiles = one pair at 64; the 8-wave modules
+    // have ragged layers)
     if constexpr (P == 64) {
-        // (fp1 + head at 64 points: two tiles = one pair per wave)
-        if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+        if (maxt == 2) return go(fp_bwd_kernel<P, NW, 2, false>, "#p64#t2");
     } else {
-        if (maxt == 1) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 1, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
-    }
-    if constexpr (LVL > 0 && P == 32) {
-        if (maxt == 2) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 2, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
-        if (maxt == 3) return launch_lds(ws, TAG_FP_BWD + LVL, PSG_SITE, (fp_bwd_kernel<P, NW, 3, false>), grid, NW * 64, blocks, Lds<P>::BLK, a, st);
+        if (maxt == 1) return go(fp_bwd_kernel<P, NW, 1, false>, "#t1");
+        if constexpr (LVL > 0) {
+            if (maxt == 2) return go(fp_bwd_kernel<P, NW, 2, false>, "#t2");
+            if (maxt == 3) return go(fp_bwd_kernel<P, NW, 3, false>, "#t3");
+        }
     }
     set_error("run_fp_bwd<%d>: no kernel for MAXT=%d", LVL, maxt);
     return PSG_ERR_STATE;
@@ -1067,13 +780,13 @@ int run_fp_bwd(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, const float *logp, con
 // the three launches.  The results are the same bits either way.
 bool fp1_loop_applies(const psg_pn2_model *m, const psg_pn2_ws *ws)
 {
-    static const bool on = psg::env_int("PSG_PN2_FP1_LOOP", 1) != 0;
+    const bool on = sw().fp1_loop;
 #ifdef PSG_DIAG_BUILD
     constexpr bool diag_build = true;     // (the fused kernel has no section-skipping switches)
 #else
     constexpr bool diag_build = false;
 #endif
-    if (!on || diag_build || FpCfg<0>::P2 != 64 || FpCfg<0>::NW != 4 || fp1_wave() || !m->fsplit[0] || ws->Nl[0] % 64) return false;
+    if (!on || diag_build || FpCfg<0>::P2 != 64 || FpCfg<0>::NW != 4 || sw().fp1_wave || !m->fsplit[0] || ws->Nl[0] % 64) return false;
     const ArchDesc &A = *m->arch;
     const int first = A.fp_first[0], head = A.head;
     if (A.fp_count[0] != 3 || NCLS != 13 || m->fa[0].k8f() != 0 || m->fa[0].cout != 128 || m->fb[0].cout != 128) return false;
@@ -1471,160 +1184,111 @@ extern "C" int psg_pn2_model_create_arch(psg_ctx *ctx, int arch, const float *co
     auto *m = new psg_pn2_model();
     m->ctx = ctx;
     m->arch = &A;
-    const int NLr = A.n_layers, fp1 = A.fp_first[0];
-    std::vector<std::vector<float>> wf(NLr), wb(NLr), bs(NLr), wf4(NLr), wb4(NLr);
-    std::vector<bool> sa_first(NLr, false), sa_rows(NLr, false);
-    for (int l = 0; l < 4; ++l)
-        for (int s = 0; s < A.ns; ++s) {
-            sa_first[A.sc[l][s].l0] = A.sa_perm;
-            sa_rows[A.sc[l][s].l0 + 2] = A.id == PSG_PN2_ARCH_SSG && l >= 1;   // (run_sa_bwd: the levels that may run sparse)
-        }
-    size_t total = 0;
-    for (int i = 0; i < NLr; ++i) {
-        if (!weights[i] || !biases[i]) { delete m; set_error("psg_pn2_model_create: layer %d is null", i); return PSG_ERR_ARG; }
-        const int cin = A.cin[i], cout = A.cout[i];
-        std::vector<int> perm;
-        if (sa_first[i]) perm = sa_input_perm(cin);
-        wf[i] = pack_fwd(weights[i], cin, cout, sa_first[i] ? &perm : nullptr);
-        wb[i] = pack_bwd(weights[i], cin, cout, sa_first[i] ? &perm : nullptr);
-        bs[i].assign((size_t)ceil_div(cout, 32) * 32, 0.0f);
-        std::copy(biases[i], biases[i] + cout, bs[i].begin());
-        if ((i >= fp1 && i < fp1 + 3) || i >= A.head) {   // fp1 + head run as wave-private chains: k8-major packings of the 128-wide sides
-            if (cout == 128) wf4[i] = k8_major_padded(wf[i], 4, ceil_div(cin, 8), ceil_div(cin, 8));
-            wb4[i] = k8_major_padded(wb[i], 4, ceil_div(cout, 8), round_up(ceil_div(cout, 8), 4));
-        }
-        total += ((wf[i].size() + wb[i].size() + bs[i].size() + wf4[i].size() + wb4[i].size()) * 4 + 6 * 256);
-        if (sa_rows[i]) total += (size_t)cout * cin * 4;
-    }
-    // split first layers (arch_split): reference column order of the layer is [rel_xyz(3), feats(D)] (SSG: sa_perm)
-    std::vector<float> sxf[8], sff[8], sfb[8], sfbias[8], w0raw;
-    for (int ls = 0; ls < 8; ++ls) {
-        const int l = ls >> 1, s = ls & 1;
-        m->split[l] = arch_split(A, l);
-        m->split_fwd[l] = arch_split_fwd(A, l);
-        if (!m->split_fwd[l] || s >= A.ns) continue;
-        const int li = A.sc[l][s].l0, cin = A.cin[li], cout = A.cout[li], D = cin - 3;
-        const int xo = A.sa_perm ? 0 : D, fo = A.sa_perm ? 3 : 0;
-        std::vector<float> wx((size_t)cout * 3), wfe((size_t)cout * D);
-        for (int o = 0; o < cout; ++o) {
-            for (int c = 0; c < 3; ++c) wx[(size_t)o * 3 + c] = weights[li][(size_t)o * cin + xo + c];
-            for (int c = 0; c < D; ++c) wfe[(size_t)o * D + c] = weights[li][(size_t)o * cin + fo + c];
-        }
-        sxf[ls] = pack_fwd(wx.data(), 3, cout, nullptr);
-        sff[ls] = pack_fwd(wfe.data(), D, cout, nullptr);
-        sfb[ls] = pack_bwd(wfe.data(), D, cout, nullptr);
-        sfbias[ls] = bs[li];
-        if (l == 0) w0raw = wfe;
-        total += (sxf[ls].size() + sff[ls].size() + sfb[ls].size() + sfbias[ls].size() + (l == 0 ? wfe.size() : 0)) * 4 + 5 * 256;
-    }
-    // split FP first layers (arch_fp_split): reference column order is [points1 (skip, C1), interpolated (C2)]
-    std::vector<float> faf[3], fab[3], fbf[3], fbb[3], fzero[3];
-    for (int l = 0; l < 3; ++l) {
-        m->fsplit[l] = arch_fp_split(A, l);
-        if (!m->fsplit[l]) continue;
-        const int li = A.fp_first[l], cin = A.cin[li], cout = A.cout[li], C1 = l == 0 ? 0 : A.C[l], C2 = cin - C1;
-        std::vector<float> wa((size_t)cout * std::max(C1, 1)), wbm((size_t)cout * C2);
-        for (int o = 0; o < cout; ++o) {
-            for (int c = 0; c < C1; ++c) wa[(size_t)o * C1 + c] = weights[li][(size_t)o * cin + c];
-            for (int c = 0; c < C2; ++c) wbm[(size_t)o * C2 + c] = weights[li][(size_t)o * cin + C1 + c];
-        }
-        if (C1) { faf[l] = pack_fwd(wa.data(), C1, cout, nullptr); fab[l] = pack_bwd(wa.data(), C1, cout, nullptr); }
-        fbf[l] = pack_fwd(wbm.data(), C2, cout, nullptr);
-        fbb[l] = pack_bwd(wbm.data(), C2, cout, nullptr);
-        fzero[l].assign((size_t)ceil_div(cout, 32) * 32, 0.0f);
-        total += (faf[l].size() + fab[l].size() + fbf[l].size() + fbb[l].size() + fzero[l].size()) * 4 + 6 * 256;
-    }
-    std::vector<float> w1f_host[2];
-    for (int sc = 0; sc < A.ns; ++sc) {
-        const int li = A.sc[0][sc].l0, cin = A.cin[li], cout = A.cout[li], D = cin - 3, fo = A.sa_perm ? 3 : 0;
-        w1f_host[sc].resize((size_t)cout * D);
-        for (int o = 0; o < cout; ++o)
-            for (int f = 0; f < D; ++f) w1f_host[sc][(size_t)o * D + f] = weights[li][(size_t)o * cin + fo + f];
-        total += w1f_host[sc].size() * 4 + 256;
-    }
-    std::vector<float> w1x_host[4];
-    for (int l = 1; l < 4; ++l) {   // SSG column order of a first layer: [rel_xyz(3), feats(D)]
+    auto fail = [&](int rc) { psg_pn2_model_destroy(m); return rc; };     // (frees the arena, if any, and the handle)
+    for (int i = 0; i < A.n_layers; ++i)
+        if (!weights[i] || !biases[i]) { set_error("psg_pn2_model_create: layer %d is null", i); return fail(PSG_ERR_ARG); }
+    // Every weight block is listed ONCE, in arena order: its host copy and where its device pointer goes.  The layout below
+    // takes them in this order (256-byte aligned), the arena is their exact sum, and one loop uploads them.
+    struct Block { const void *src; size_t bytes; std::function<void(void *)> set; void *dst; };
+    std::vector<Block> blocks;
+    std::vector<std::vector<float>> host;     // owns the packed copies (a moved vector keeps its data pointer)
+    auto add = [&](std::vector<float> v, std::function<void(void *)> set) {
+        blocks.push_back({v.data(), v.size() * 4, std::move(set), nullptr});
+        host.push_back(std::move(v));
+    };
+    auto padded_bias = [&](int i) {
+        std::vector<float> b(biases[i], biases[i] + A.cout[i]);
+        b.resize((size_t)ceil_div(A.cout[i], 32) * 32, 0.0f);
+        return b;
+    };
+    for (int l = 0; l < 4; ++l) { m->split[l] = arch_split(A, l); m->split_fwd[l] = arch_split_fwd(A, l); }
+    for (int l = 0; l < 3; ++l) m->fsplit[l] = arch_fp_split(A, l);
+    auto cols = [&](int li, int c0, int n) {     // columns [c0, c0 + n) of layer li's rows, as [cout][n]
+        std::vector<float> w((size_t)A.cout[li] * std::max(n, 1));
+        for (int o = 0; o < A.cout[li]; ++o)
+            for (int c = 0; c < n; ++c) w[(size_t)o * n + c] = weights[li][(size_t)o * A.cin[li] + c0 + c];
+        return w;
+    };
+    for (int l = 1; l < 4; ++l) {   // SSG column order of a first layer: [rel_xyz(3), feats(D)]; the xyz columns as [3][C1]
         if (A.id != PSG_PN2_ARCH_SSG || !m->split[l]) continue;
         const int li = A.sc[l][0].l0, cin = A.cin[li], cout = A.cout[li];
-        w1x_host[l].resize((size_t)3 * cout);
+        std::vector<float> w1x((size_t)3 * cout);
         for (int o = 0; o < cout; ++o)
-            for (int c = 0; c < 3; ++c) w1x_host[l][(size_t)c * cout + o] = weights[li][(size_t)o * cin + c];
-        total += w1x_host[l].size() * 4 + 256;
-    }
-    PSG_CHECK_HIP(hipMalloc(&m->arena, total));
-    Bump bp;
-    bp.base = (char *)m->arena;
-    for (int l = 1; l < 4; ++l) {
-        if (w1x_host[l].empty()) continue;
-        m->w1x[l] = bp.take<float>(w1x_host[l].size());
-        PSG_CHECK_HIP(psg::copy_sync(m->w1x[l], w1x_host[l].data(), w1x_host[l].size() * 4, hipMemcpyHostToDevice));
+            for (int c = 0; c < 3; ++c) w1x[(size_t)c * cout + o] = weights[li][(size_t)o * cin + c];
+        add(std::move(w1x), [m, l](void *p) { m->w1x[l] = (float *)p; });
     }
     for (int sc = 0; sc < A.ns; ++sc) {
-        m->w1feat[sc] = bp.take<float>(w1f_host[sc].size());
-        PSG_CHECK_HIP(psg::copy_sync(m->w1feat[sc], w1f_host[sc].data(), w1f_host[sc].size() * 4, hipMemcpyHostToDevice));
+        const int li = A.sc[0][sc].l0;
+        add(cols(li, A.sa_perm ? 3 : 0, A.cin[li] - 3), [m, sc](void *p) { m->w1feat[sc] = (float *)p; });
     }
+    // split FP first layers (arch_fp_split): reference column order is [points1 (skip, C1), interpolated (C2)]
     for (int l = 0; l < 3; ++l) {
         if (!m->fsplit[l]) continue;
-        const int li = A.fp_first[l], C1 = l == 0 ? 0 : A.C[l];
-        PackedLayer &Fa = m->fa[l], &Fb = m->fb[l];
-        Fa.cin = C1; Fa.cout = A.cout[li];
-        Fb.cin = A.cin[li] - C1; Fb.cout = A.cout[li];
+        const int li = A.fp_first[l], cout = A.cout[li], C1 = l == 0 ? 0 : A.C[l], C2 = A.cin[li] - C1;
+        const std::vector<float> wa = cols(li, 0, C1), wbm = cols(li, C1, C2);
+        PackedLayer *Fa = &m->fa[l], *Fb = &m->fb[l];
+        Fa->cin = C1; Fa->cout = cout;
+        Fb->cin = C2; Fb->cout = cout;
         if (C1) {
-            Fa.wf = bp.take<float4>(faf[l].size() / 4);
-            Fa.wb = bp.take<float4>(fab[l].size() / 4);
-            PSG_CHECK_HIP(psg::copy_sync(Fa.wf, faf[l].data(), faf[l].size() * 4, hipMemcpyHostToDevice));
-            PSG_CHECK_HIP(psg::copy_sync(Fa.wb, fab[l].data(), fab[l].size() * 4, hipMemcpyHostToDevice));
+            add(pack_fwd(wa.data(), C1, cout, nullptr), [Fa](void *p) { Fa->wf = (float4 *)p; });
+            add(pack_bwd(wa.data(), C1, cout, nullptr), [Fa](void *p) { Fa->wb = (float4 *)p; });
         }
-        Fb.wf = bp.take<float4>(fbf[l].size() / 4);
-        Fb.wb = bp.take<float4>(fbb[l].size() / 4);
-        Fb.bias = bp.take<float>(fzero[l].size());
-        PSG_CHECK_HIP(psg::copy_sync(Fb.wf, fbf[l].data(), fbf[l].size() * 4, hipMemcpyHostToDevice));
-        PSG_CHECK_HIP(psg::copy_sync(Fb.wb, fbb[l].data(), fbb[l].size() * 4, hipMemcpyHostToDevice));
-        PSG_CHECK_HIP(psg::copy_sync(Fb.bias, fzero[l].data(), fzero[l].size() * 4, hipMemcpyHostToDevice));
+        add(pack_fwd(wbm.data(), C2, cout, nullptr), [Fb](void *p) { Fb->wf = (float4 *)p; });
+        add(pack_bwd(wbm.data(), C2, cout, nullptr), [Fb](void *p) { Fb->wb = (float4 *)p; });
+        add(std::vector<float>((size_t)ceil_div(cout, 32) * 32, 0.0f), [Fb](void *p) { Fb->bias = (float *)p; });
     }
+    // split first layers (arch_split): reference column order of the layer is [rel_xyz(3), feats(D)] (SSG: sa_perm)
     for (int ls = 0; ls < 8; ++ls) {
         const int l = ls >> 1, s = ls & 1;
         if (!m->split_fwd[l] || s >= A.ns) continue;
-        const int li = A.sc[l][s].l0;
-        PackedLayer &X = m->sx[l][s], &F = m->sf[l][s];
-        X.cin = 3; X.cout = A.cout[li];
-        F.cin = A.cin[li] - 3; F.cout = A.cout[li];
-        X.wf = bp.take<float4>(sxf[ls].size() / 4);
-        F.wf = bp.take<float4>(sff[ls].size() / 4);
-        F.wb = bp.take<float4>(sfb[ls].size() / 4);
-        F.bias = bp.take<float>(sfbias[ls].size());
-        X.bias = F.bias;     // (unused: the bias arrives through T)
-        PSG_CHECK_HIP(psg::copy_sync(X.wf, sxf[ls].data(), sxf[ls].size() * 4, hipMemcpyHostToDevice));
-        PSG_CHECK_HIP(psg::copy_sync(F.wf, sff[ls].data(), sff[ls].size() * 4, hipMemcpyHostToDevice));
-        PSG_CHECK_HIP(psg::copy_sync(F.wb, sfb[ls].data(), sfb[ls].size() * 4, hipMemcpyHostToDevice));
-        PSG_CHECK_HIP(psg::copy_sync(F.bias, sfbias[ls].data(), sfbias[ls].size() * 4, hipMemcpyHostToDevice));
-        if (l == 0) {
-            m->w0f = bp.take<float>(w0raw.size());
-            m->b0f = F.bias;
-            PSG_CHECK_HIP(psg::copy_sync(m->w0f, w0raw.data(), w0raw.size() * 4, hipMemcpyHostToDevice));
-        }
+        const int li = A.sc[l][s].l0, cout = A.cout[li], D = A.cin[li] - 3;
+        std::vector<float> wx = cols(li, A.sa_perm ? 0 : D, 3), wfe = cols(li, A.sa_perm ? 3 : 0, D);
+        PackedLayer *X = &m->sx[l][s], *F = &m->sf[l][s];
+        X->cin = 3; X->cout = cout;
+        F->cin = D; F->cout = cout;
+        add(pack_fwd(wx.data(), 3, cout, nullptr), [X](void *p) { X->wf = (float4 *)p; });
+        add(pack_fwd(wfe.data(), D, cout, nullptr), [F](void *p) { F->wf = (float4 *)p; });
+        add(pack_bwd(wfe.data(), D, cout, nullptr), [F](void *p) { F->wb = (float4 *)p; });
+        add(padded_bias(li), [m, X, F, l](void *p) {
+            X->bias = F->bias = (float *)p;     // (X's is unused: the bias arrives through T)
+            if (l == 0) m->b0f = F->bias;
+        });
+        if (l == 0) add(std::move(wfe), [m](void *p) { m->w0f = (float *)p; });
     }
-    for (int i = 0; i < NLr; ++i) {
-        PackedLayer &L = m->L[i];
-        L.cin = A.cin[i]; L.cout = A.cout[i];
-        L.wf = bp.take<float4>(wf[i].size() / 4);
-        L.wb = bp.take<float4>(wb[i].size() / 4);
-        L.bias = bp.take<float>(bs[i].size());
-        PSG_CHECK_HIP(psg::copy_sync(L.wf, wf[i].data(), wf[i].size() * 4, hipMemcpyHostToDevice));
-        PSG_CHECK_HIP(psg::copy_sync(L.wb, wb[i].data(), wb[i].size() * 4, hipMemcpyHostToDevice));
-        PSG_CHECK_HIP(psg::copy_sync(L.bias, bs[i].data(), bs[i].size() * 4, hipMemcpyHostToDevice));
-        if (!wf4[i].empty()) {
-            L.wf4 = bp.take<float4>(wf4[i].size() / 4);
-            PSG_CHECK_HIP(psg::copy_sync(L.wf4, wf4[i].data(), wf4[i].size() * 4, hipMemcpyHostToDevice));
+    const int fp1 = A.fp_first[0];
+    for (int i = 0; i < A.n_layers; ++i) {
+        const int cin = A.cin[i], cout = A.cout[i];
+        bool sa_first = false, sa_rows = false;
+        for (int l = 0; l < 4; ++l)
+            for (int s = 0; s < A.ns; ++s) {
+                if (A.sc[l][s].l0 == i) sa_first = A.sa_perm;
+                if (A.sc[l][s].l0 + 2 == i) sa_rows = A.id == PSG_PN2_ARCH_SSG && l >= 1;   // (SaPath::spv: the levels that may run sparse)
+            }
+        std::vector<int> perm;
+        if (sa_first) perm = sa_input_perm(cin);
+        std::vector<float> wf = pack_fwd(weights[i], cin, cout, sa_first ? &perm : nullptr);
+        std::vector<float> wb = pack_bwd(weights[i], cin, cout, sa_first ? &perm : nullptr), wf4, wb4;
+        if ((i >= fp1 && i < fp1 + 3) || i >= A.head) {   // fp1 + head run as wave-private chains: k8-major packings of the 128-wide sides
+            if (cout == 128) wf4 = k8_major_padded(wf, 4, ceil_div(cin, 8), ceil_div(cin, 8));
+            wb4 = k8_major_padded(wb, 4, ceil_div(cout, 8), round_up(ceil_div(cout, 8), 4));
         }
-        if (!wb4[i].empty()) {
-            L.wb4 = bp.take<float4>(wb4[i].size() / 4);
-            PSG_CHECK_HIP(psg::copy_sync(L.wb4, wb4[i].data(), wb4[i].size() * 4, hipMemcpyHostToDevice));
-        }
-        if (sa_rows[i]) {
-            L.wr = bp.take<float>((size_t)L.cout * L.cin);
-            PSG_CHECK_HIP(psg::copy_sync(L.wr, weights[i], (size_t)L.cout * L.cin * 4, hipMemcpyHostToDevice));
-        }
+        PackedLayer *L = &m->L[i];
+        L->cin = cin; L->cout = cout;
+        add(std::move(wf), [L](void *p) { L->wf = (float4 *)p; });
+        add(std::move(wb), [L](void *p) { L->wb = (float4 *)p; });
+        add(padded_bias(i), [L](void *p) { L->bias = (float *)p; });
+        if (!wf4.empty()) add(std::move(wf4), [L](void *p) { L->wf4 = (float4 *)p; });
+        if (!wb4.empty()) add(std::move(wb4), [L](void *p) { L->wb4 = (float4 *)p; });
+        if (sa_rows) blocks.push_back({weights[i], (size_t)cout * cin * 4, [L](void *p) { L->wr = (float *)p; }, nullptr});
+    }
+    size_t bytes = 0;
+    if (int rc = carve_arena(&m->arena, &bytes, "psg_pn2_model_create", [&](Bump &bp) {
+            for (Block &b : blocks) b.set(b.dst = bp.take<char>(b.bytes));
+        }))
+        return fail(rc);
+    for (const Block &b : blocks) {
+        const hipError_t e = psg::copy_sync(b.dst, b.src, b.bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { set_error("psg_pn2_model_create: upload failed: %s", hipGetErrorString(e)); return fail(PSG_ERR_HIP); }
     }
     *out = m;
     return PSG_OK;
@@ -2086,8 +1750,7 @@ static int nb_step(psg_pn2_model *m, psg_pn2_ws *ws, int fwd, float *x, const fl
         if ((r = psg_ce_logp_grad(ws->logp, labels, target, rows, rows_active, NCLS, scale, ws->dlogp, nullptr, st))) return r;
     }
     // (the PGD step rides on the gradient's last gather: dx0_gather_pgd_kernel; PSG_PN2_PGD_FUSE=0: two launches)
-    static const bool pgd_fuse = psg::env_int("PSG_PN2_PGD_FUSE", 1) != 0;
-    if (pgd_fuse) {
+    if (sw().pgd_fuse) {
         const PgdFuse pf{x, ori, mask, dir * alpha, eps, last ? 1 : 0};
         return backward_impl(m, ws, fwd, ws->logp, ws->dlogp, ws->dx0, 3, 6, st, &pf, false, fused);
     }
@@ -2143,16 +1806,11 @@ extern "C" int psg_pn2_nb_attack(psg_pn2_model *m, psg_pn2_ws *ws, const float *
             if ((r = nb_step(m, ws, it, ws->x0, ws->ori, labels_ws, mask_ws, alpha, eps, targeted, target, it == iters - 1, st))) return r;
         return PSG_OK;
     };
-    // Round 5, measured and left OFF (PSG_PN2_GRAPH=1 turns it on): the body is ~33 launches per iteration + the plan (1 300
-    // for the 40-iteration attack), and a harness that calls the attack batch after batch (NB_nontarget_test_semseg.py:169-171)
-    // repeats exactly these launches with exactly these arguments, so the second call with a key can capture them into a
-    // hipGraph kept in the workspace and later calls replay it (same bits: tests/test_gpu_api.py).  On this runtime the replay is
-    // SLOWER than the eager launches it replaces: one 8-room attack at a time 324 -> 307 rooms/s, four in flight 541 -> 386,
-    // the whole-scene harness with three streams 1 141 -> 660 blocks/s (gpurun_out/r5m_*) - a linear
-    // 1 300-node graph is dispatched with a dependency between every pair of nodes and the three graphs in flight no longer
-    // interleave, while the eager launches were never launch-bound here (a launch is 20 - 50 us of GPU work against ~5 us
-    // of host time; the graphs of the ResGCN / RandLA-Net / NU loops replace one-room launches of 5 - 15 us: +23 .. +60 %).
-    static const bool use_graph = psg::env_int("PSG_PN2_GRAPH", 0) != 0 && !psg::trace_sync_enabled();
+    // Pn2Switches::graph (off): a harness that calls the attack batch after batch (NB_nontarget_test_semseg.py:169-171) repeats
+    // exactly these ~1 300 launches with exactly these arguments, so the second call with a key captures them into a hipGraph
+    // kept in the workspace and later calls replay it (same bits: tests/test_gpu_api.py).  On this runtime the replay is SLOWER:
+    // one 8-room attack at a time 324 -> 307 rooms/s, four in flight 541 -> 386.
+    const bool use_graph = sw().graph && !psg::trace_sync_enabled();
     if (use_graph && B <= 16 && !ws->prof.on) {
         const psg_pn2_ws::NbKey key{m->gen, eps, alpha, iters, targeted ? 1 : 0, targeted ? target : 0, mask ? 1 : 0, targeted ? 0 : 1, 0};
         const bool same = ws->nb_have_key && memcmp(&key, &ws->nb_key, sizeof(key)) == 0;

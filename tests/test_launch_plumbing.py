@@ -31,6 +31,31 @@ def test_duplicated_plumbing_stays_gone(name):
     assert [f for f, src in csrc_sources().items() if name in src] == []
 
 
+PN2_SWITCHES = ["PSG_PN2_SPLIT", "PSG_PN2_FPSPLIT", "PSG_FP1_WAVE", "PSG_PN2_PACK", "PSG_PN2_PACK_BWD", "PSG_PN2_POOLT_ORDER",
+                "PSG_PN2_POOLT_SPARSE", "PSG_PN2_L1T_COLOUR", "PSG_PN2_PW_SIZED", "PSG_PN2_BALL_TABLE", "PSG_PN2_FP1_LOOP",
+                "PSG_PN2_PGD_FUSE", "PSG_PN2_GRAPH", "PSG_DIAG"]
+
+
+@pytest.mark.parametrize("name", PN2_SWITCHES)
+def test_every_pn2_switch_is_read_in_one_place(name):
+    """One env_int / env_str call per PointNet++ switch in csrc/: the switch set of psg_pn2_paths.h (Pn2Switches), which
+    psg_pn2.hip fills once per process; nothing reads the environment on its own."""
+    import re
+    reads = [(f, m.group(0)) for f, src in csrc_sources().items() for m in re.finditer(r'env_(?:int|str)\(\s*"%s"' % re.escape(name), src)]
+    assert len(reads) == 1 and reads[0][0] == "psg_pn2_paths.h", reads
+    assert csrc_sources()["psg_pn2.hip"].count("read_switches(") == 1
+    assert not any("getenv(" in src for f, src in csrc_sources().items() if f.startswith("psg_pn2"))
+
+
+@pytest.mark.parametrize("kernel", ["sa_fwd_kernel<", "sa_fwd_packed_kernel<", "sa_bwd_kernel<", "sa_bwd_sparse_kernel<", "sa_bwd_packed_kernel<"])
+def test_sa_kernels_are_named_by_the_table_visitor_alone(kernel):
+    """psg_pn2.hip names each SA kernel with template arguments at most twice (run_sa_fwd / run_sa_bwd, from the row of the
+    kernel table in psg_pn2_paths.h); the per-configuration switch tables and their key macro stay gone."""
+    src = csrc_sources()["psg_pn2.hip"]
+    assert 1 <= src.count(kernel) <= 2, src.count(kernel)
+    assert "PSG_CFG_KEY" not in src
+
+
 # ---- the folds as they were before runtime._as_f64 / runtime._fold_conv_bn (this project's own earlier code, verbatim)
 def old_fold_state_dict(sd, eps=1e-5, msg=False):
     def arr(k):
