@@ -1355,6 +1355,22 @@ int psg_scene_nu_latch(const int32_t *pred, const int32_t *labels, int target, c
                        float *snap, int32_t *counters, long long *hist_row, int32_t *exit_step, int32_t *active,
                        psg_stream stream);
 
+/* The coordinate field of the whole-scene NU attack: Adam on ONE displacement delta [n_scene][3]
+ * (metres, no tanh space: coordinates have no box) per scene point; delta / m / v [n_scene][3] fp32 in place.  Lists, the
+ * rows guard, the moving points and the `active` word as for psg_scene_nu_step; the slots are written by
+ * psg_scene_delta_to_blocks.  For every moving point and channel ch = 0..2, in psg_nu_coord_adam_step_rooms' expression
+ * order, fp32, no contraction:
+ *   Gx = ((0 + dx0[e_0][ch]) + dx0[e_1][ch]) + ...       over the slots of the point in list order (dx0 [rows][9])
+ *   Gs = the same ordered sum over sgrad_xyz [rows][3]    (the per-slot Smooth_xyz gradients, psg_smooth_knn_xyz_rooms)
+ *   g  = Gx + (coord_c * 2) * delta;  g = g + coord_c * Gs
+ *   then torch.optim.Adam's single-tensor update on delta / m / v (step >= 1; the step constants in double on the host).
+ * The L2 term counts once per POINT.  gsum_x_out / gsum_s_out (nullable) [n_scene][3]: Gx and Gs (+0 for points that do
+ * not move).  No float atomics, one writer per output element; while active[0] == 0 every byte is left alone. */
+int psg_scene_nu_field_step(float *delta, float *m, float *v, const uint8_t *scene_mask, const int32_t *occ_off,
+                            const int32_t *occ_ent, const float *dx0, const float *sgrad_xyz, int rows, int n_scene,
+                            float coord_c, float coord_lr, float beta1, float beta2, float eps, int step,
+                            const int32_t *active, float *gsum_x_out, float *gsum_s_out, psg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,7 @@ SIGNATURES = {
     "psg_scene_nu_colour": (ci, [vp, vp, vp, ci, vp, vp, vp]),
     "psg_scene_nu_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, cf, cf, ci, vp, vp, vp, vp]),
     "psg_scene_nu_latch": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "psg_scene_nu_field_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, cf, cf, ci, vp, vp, vp, vp]),
 }
 
 

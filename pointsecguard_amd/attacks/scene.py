@@ -272,11 +272,33 @@ class SceneNUAttack:
     the cap), last_history (int64 numpy [steps_run][2]: n_hits, n_counted) and last_w (device tensor).
     trace(dict), after every step: s, starts, dx0 [nb, bp, 9], sgrad [nb, bp, 3], pred [nb, bp], w_before, w_after, m_after,
     v_after, c (the colours of the step's forward), gsum_f, gsum_s (None where no Adam step ran: after the last step or the
-    exit), active (0 / 1 after the step's latch) - device tensors; dx0 / sgrad / pred are the attack's own buffers."""
+    exit), active (0 / 1 after the step's latch) - device tensors; dx0 / sgrad / pred are the attack's own buffers.
+
+    field (an extension of the reference API, like SceneNBAttack's): "color" (default) is the attack
+    above, launch for launch.  "coord" moves channels 0:3, "both" the two fields together; PointNet++ SSG only
+    (psg_pn2_backward_full).  The coordinate variable is ONE displacement delta [n_scene][3] (float32, metres, zero at the
+    start) per scene point, optimised by Adam directly - no tanh space, coordinates have no box -, moments mx = vx = 0; every
+    slot holds x[e][0:3] = fl32(x_clean[e][0:3] + delta[point_idx[e]]) (psg_scene_delta_to_blocks, always onto the clean
+    blocks), channels 6:9 stay as given and block membership is the original slicing's, as in SceneNBAttack.  Minimised:
+      sum_blocks f_b + coord_c * sum_blocks SmoothXyz_b + coord_c * sum_points |delta_p|^2     ("both": + the two colour terms)
+    SmoothXyz_b: the Smooth term on channels 0:3 of the block's moved slots against its CLEAN slots (psg_smooth_knn_xyz_rooms,
+    direct differences); coord_c / coord_lr fall back to c / lr.  Per batch: psg_scene_delta_to_blocks (both: +
+    psg_scene_colour_to_blocks), the FPS starts, psg_pn2_plan_build (geometry moves), psg_pn2_forward_lean,
+    psg_nu_f_loss_grad_rooms, (targeted) psg_scene_rows_mask, psg_pn2_backward_full, psg_smooth_knn_xyz_rooms (both: +
+    psg_smooth_knn_rooms); then psg_scene_nu_latch (its snapshot is of the colours: c0 under "coord") and - not after the last
+    step - psg_scene_nu_field_step (both: + psg_scene_nu_step on channels 3:6 of the same gradients).  The exit leaves delta as
+    the firing step's forward saw it.  __call__ still returns (adv_rgb01, adv_blocks) - adv_rgb01 is the clean c0 under
+    "coord" -; afterwards last_delta (device tensor [n_scene, 3]; None after a colour run), last_mx, last_vx.  The trace dict
+    then also carries delta_before, delta_after, mx_after, vx_after, sgrad_xyz [nb, bp, 3], gsum_x, gsum_sx (None where no
+    Adam step ran); under "coord" the colour state's entries (w_*, m_after, v_after, sgrad, gsum_f, gsum_s) are None."""
 
     def __init__(self, model, c=1e-4, kappa=0, steps=1000, lr=0.01, batch_size=8, neighbour=None, target=None, origin=None,
-                 exit_below=(1, 13), exit_above=(9, 10), check_every=10, trace=None):
+                 exit_below=(1, 13), exit_above=(9, 10), check_every=10, trace=None, field="color", coord_c=None, coord_lr=None):
         self.model = check_scene_model(model)
+        self.field = check_field(field)
+        if self.field != "color" and not isinstance(model, pointnet2_sem_seg.get_model):
+            raise NotImplementedError("field=%r is implemented for the PointNet++ SSG network (pointnet2_sem_seg): the exact "
+                                      "coordinate gradient psg_pn2_backward_full refuses MSG" % self.field)
         _check_target(target, origin)
         if int(steps) < 1 or int(batch_size) < 1 or int(check_every) < 1:
             raise ValueError("steps, batch_size and check_every must be positive")
@@ -286,75 +308,112 @@ class SceneNUAttack:
         if not 1 <= int(neighbour) <= 16:
             raise ValueError("neighbour = %r outside 1 .. 16 (psg_smooth_knn_rooms)" % (neighbour,))
         self.c, self.kappa, self.steps, self.lr = float(c), float(kappa), int(steps), float(lr)
+        self.coord_c = self.c if coord_c is None else float(coord_c)
+        self.coord_lr = self.lr if coord_lr is None else float(coord_lr)
+        given = self.field != "color"          # the colour attack never reads them: only what the caller passed is checked
+        if (given or coord_lr is not None) and not self.coord_lr > 0:
+            raise ValueError("coord_lr = %r must be positive" % (self.coord_lr,))
+        if (given or coord_c is not None) and not self.coord_c >= 0:
+            raise ValueError("coord_c = %r must not be negative" % (self.coord_c,))
         self.batch_size, self.neighbour, self.check_every = int(batch_size), int(neighbour), int(check_every)
         self.target, self.origin, self.trace = target, origin, trace
         self.last_exit_step, self.last_history, self.last_w = None, None, None
+        self.last_delta, self.last_mx, self.last_vx = None, None, None
 
     def __call__(self, blocks, point_idx, block_labels, scene_rgb, scene_labels):
         net = self.model
         sc = _open_scene("SceneNUAttack", net, blocks, point_idx, block_labels, scene_rgb, scene_labels, self.origin)
         dev, x_clean, idx, gt, c0, mask, occ_off, occ_ent, bad, nb, bp, n_scene = sc
+        colour, coord = self.field != "coord", self.field != "color"
         targeted = self.target is not None
         if targeted and not bool(mask[idx.reshape(-1).long()].any().item()):       # (a read-back, once per scene)
             raise ValueError("SceneNUAttack: no slot of this scene holds a point of the origin class %r" % (self.origin,))
 
         f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)      # noqa: E731
         i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)        # noqa: E731
-        x = x_clean.clone()        # the caller's blocks stay clean, and are the Smooth term's reference colours
-        c = c0.clone()
-        w = runtime.scene_nu_init(c0)
-        m, v, snap = f32(n_scene, 3), f32(n_scene, 3), f32(n_scene, 3)
+        x = x_clean.clone()        # the caller's blocks stay clean, and are the Smooth terms' reference slots
+        c = c0.clone() if colour else c0
+        w = m = v = sgrad_all = nn_state = None
+        if colour:
+            w = runtime.scene_nu_init(c0)
+            m, v = f32(n_scene, 3), f32(n_scene, 3)
+            sgrad_all = f32(nb, bp, 3)
+            nn_state = i32(nb, bp, self.neighbour)
+        delta = mx = vx = sgrad_xyz = None
+        if coord:
+            delta, mx, vx = f32(n_scene, 3), f32(n_scene, 3), f32(n_scene, 3)
+            sgrad_xyz = f32(nb, bp, 3)
+        snap = f32(n_scene, 3)
         active = torch.ones(1, dtype=torch.int32, device=dev)
         exit_step = torch.full((1,), -1, dtype=torch.int32, device=dev)
         counters = i32(2)
         hist = torch.zeros(self.steps, 2, dtype=torch.int64, device=dev)
-        dx0_all = f32(nb, bp, 9)   # backward_colour writes channels 3:6 only
-        sgrad_all = f32(nb, bp, 3)
+        dx0_all = f32(nb, bp, 9)   # backward_colour writes channels 3:6 only, backward_full all nine
         pred_all = i32(nb, bp)
-        nn_state = i32(nb, bp, self.neighbour)
         bt = _Batches(net, sc, self.batch_size)
         dlogp = bt.per_size(torch.zeros, bp, NUM_CLASSES)
         f_sum = bt.per_size(torch.zeros)               # psg_nu_f_loss_grad_rooms adds the rooms' f sums here: not read
         trace = self.trace
-        gsum_f = gsum_s = None
-        if trace is not None:
+        gsum_f = gsum_s = gsum_x = gsum_sx = None
+        if trace is not None and colour:
             gsum_f, gsum_s = f32(n_scene, 3), f32(n_scene, 3)
+        if trace is not None and coord:
+            gsum_x, gsum_sx = f32(n_scene, 3), f32(n_scene, 3)
         tsign = -1.0 if targeted else 1.0
         num, den = self.exit_above if targeted else self.exit_below
         off3 = lambda t: ctypes.c_void_p(t.data_ptr() + 3 * 4)                          # noqa: E731  (channel 3 of row 0)
         st = runtime.stream
         for s in range(self.steps):
-            runtime.scene_nu_colour(w, mask, occ_off, active, c)
-            runtime.scene_colour_to_blocks(c, idx, x, bad)
+            if colour:
+                runtime.scene_nu_colour(w, mask, occ_off, active, c)
+            if not coord:
+                runtime.scene_colour_to_blocks(c, idx, x, bad)
             starts_s = []
             for lo, hi in bt.spans:
                 b = hi - lo
                 xb = x[lo:hi]
+                if coord:
+                    runtime.scene_delta_to_blocks(delta, idx[lo:hi], x_clean[lo:hi], xb, bad)
+                    if colour:
+                        runtime.scene_colour_to_blocks(c, idx[lo:hi], xb, bad)
                 starts, logp = bt.forward(xb)
                 _lib.call("psg_nu_f_loss_grad_rooms", runtime.ptr(logp), None if targeted else runtime.ptr(gt[lo:hi]),
                           int(self.target) if targeted else 0, b, bp, NUM_CLASSES, self.kappa, tsign, runtime.ptr(dlogp[b]),
                           runtime.ptr(f_sum[b]), runtime.ptr(pred_all[lo:hi]), st())
                 if targeted:
                     runtime.scene_rows_mask(dlogp[b], idx[lo:hi], mask)
-                bt.backward(dlogp[b], dx0_all[lo:hi])
-                _lib.call("psg_smooth_knn_rooms", off3(xb), 9, bp * 9, off3(x_clean[lo:hi]), 9, bp * 9, b, bp, self.neighbour,
-                          None, runtime.ptr(sgrad_all[lo:hi]), runtime.ptr(nn_state[lo:hi]), 1 if s > 0 else 0, st())
+                bt.backward(dlogp[b], dx0_all[lo:hi], full=coord)
+                if coord:
+                    _lib.call("psg_smooth_knn_xyz_rooms", runtime.ptr(xb), 9, bp * 9, runtime.ptr(x_clean[lo:hi]), 9, bp * 9, b, bp,
+                              self.neighbour, None, runtime.ptr(sgrad_xyz[lo:hi]), None, None, st())
+                if colour:
+                    _lib.call("psg_smooth_knn_rooms", off3(xb), 9, bp * 9, off3(x_clean[lo:hi]), 9, bp * 9, b, bp, self.neighbour,
+                              None, runtime.ptr(sgrad_all[lo:hi]), runtime.ptr(nn_state[lo:hi]), 1 if s > 0 else 0, st())
                 if trace is not None:
                     starts_s.append(starts)
             runtime.scene_nu_latch(pred_all, None if targeted else gt, int(self.target) if targeted else 0, idx, mask, num, den, s,
                                    c, snap, counters, hist[s], exit_step, active)
             stepping = s < self.steps - 1
             if trace is not None:
-                w_before = w.clone()
+                w_before = w.clone() if colour else None
+                delta_before = delta.clone() if coord else None
                 running = bool(active.item())
-            if stepping:
+            if stepping and coord:
+                runtime.scene_nu_field_step(delta, mx, vx, mask, occ_off, occ_ent, dx0_all, sgrad_xyz, self.coord_c, self.coord_lr,
+                                            BETA1, BETA2, ADAM_EPS, s + 1, active, gsum_x, gsum_sx)
+            if stepping and colour:
                 runtime.scene_nu_step(w, m, v, c, c0, mask, occ_off, occ_ent, dx0_all, sgrad_all, self.c, self.lr, BETA1, BETA2,
                                       ADAM_EPS, s + 1, active, gsum_f, gsum_s)
             if trace is not None:
                 stepped = stepping and running
-                trace(dict(s=s, starts=starts_s, dx0=dx0_all, sgrad=sgrad_all, pred=pred_all, w_before=w_before, w_after=w.clone(),
-                           m_after=m.clone(), v_after=v.clone(), c=c.clone(), gsum_f=gsum_f.clone() if stepped else None,
-                           gsum_s=gsum_s.clone() if stepped else None, active=int(running)))
+                kept = lambda t, on=True: t.clone() if on and t is not None else None      # noqa: E731
+                row = dict(s=s, starts=starts_s, dx0=dx0_all, sgrad=sgrad_all, pred=pred_all, w_before=w_before, w_after=kept(w),
+                           m_after=kept(m), v_after=kept(v), c=c.clone(), gsum_f=kept(gsum_f, stepped), gsum_s=kept(gsum_s, stepped),
+                           active=int(running))
+                if coord:
+                    row.update(delta_before=delta_before, delta_after=delta.clone(), mx_after=mx.clone(), vx_after=vx.clone(),
+                               sgrad_xyz=sgrad_xyz, gsum_x=kept(gsum_x, stepped), gsum_sx=kept(gsum_sx, stepped))
+                trace(row)
                 if not running:
                     break
             elif (s + 1) % self.check_every == 0 and not int(active.item()):
@@ -363,6 +422,11 @@ class SceneNUAttack:
         self.last_exit_step = exited
         self.last_history = hist[:exited + 1 if exited >= 0 else self.steps].cpu().numpy()
         self.last_w = w
-        adv = snap if exited >= 0 else c
-        runtime.scene_colour_to_blocks(adv, idx, x, bad)
+        self.last_delta, self.last_mx, self.last_vx = delta, mx, vx
+        adv = snap if exited >= 0 and colour else c
+        if coord:
+            runtime.scene_delta_to_blocks(delta, idx, x_clean, x, bad)
+        if colour:
+            runtime.scene_colour_to_blocks(adv, idx, x, bad)
         return adv, x
+

@@ -6,6 +6,8 @@
 //   psg_scene_nu_colour  c = 1/2 (tanh w + 1) on the moving points while the attack is active
 //   psg_scene_nu_step    f-loss and Smooth gradients summed over a point's slots in ascending slot order, the L2 term once
 //                        per point, the chain through tanh_space, torch's single-tensor Adam on w / m / v
+//   psg_scene_nu_field_step  the coordinate field (section 5z): the same two ordered sums over channels 0:3 and the per-slot
+//                        Smooth_xyz gradients, nu_coord_adam_kernel's assembly, Adam on the displacement delta / m / v
 //   psg_scene_nu_latch   integer exit test over all slots: two counters, the decision by one thread in a launch of its own,
 //                        the snapshot of the colours the step's forward saw
 // Compiled with -ffp-contract=off: the summation order and the step's evaluation order decide bits.  No float atomics; every
@@ -78,6 +80,37 @@ __global__ void scene_nu_step_kernel(float *__restrict__ w, float *__restrict__ 
     const float th = tanhf(w[t]);
     g = __fmul_rn(__fmul_rn(g, 0.5f), __fsub_rn(1.0f, __fmul_rn(th, th)));
     w[t] = adam_update(w[t], m[t], v[t], g, beta1, beta2, eps, step_size, bc2_sqrt);
+}
+
+// the coordinate field, one thread per (scene point, coordinate): the ordered sums over dx0[e][ch] and
+// over sgrad_xyz[e][ch] in one walk of the point's slots, then nu_coord_adam_kernel's gradient assembly (psg_nu_field.cuh) and
+// the Adam update on the displacement itself - no tanh space, coordinates have no box - with the L2 term of the POINT
+__global__ void scene_nu_field_step_kernel(float *__restrict__ delta, float *__restrict__ m, float *__restrict__ v,
+                                           const uint8_t *__restrict__ scene_mask, const int32_t *__restrict__ occ_off,
+                                           const int32_t *__restrict__ occ_ent, const float *__restrict__ dx0,
+                                           const float *__restrict__ sgrad_xyz, int rows, size_t total, float coord_c, float beta1,
+                                           float beta2, float eps, float step_size, float bc2_sqrt, const int32_t *__restrict__ active,
+                                           float *__restrict__ gsum_x_out, float *__restrict__ gsum_s_out)
+{
+    if (!active[0]) return;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // over n_scene * 3
+    if (t >= total) return;
+    const size_t p = t / 3;
+    const int ch = (int)(t % 3);
+    float gx = 0.0f, gs = 0.0f;
+    bool any = false;
+    if (!scene_mask || scene_mask[p])
+        any = for_each_slot(occ_off, occ_ent, p, rows, [&](int e) {
+            gx = __fadd_rn(gx, dx0[(size_t)e * 9 + ch]);
+            gs = __fadd_rn(gs, sgrad_xyz[(size_t)e * 3 + ch]);
+        });
+    if (gsum_x_out) gsum_x_out[t] = gx;
+    if (gsum_s_out) gsum_s_out[t] = gs;
+    if (!any) return;                                  // no occurrence (or not under the mask): the point does not move
+    const float d = delta[t];
+    float g = __fadd_rn(gx, __fmul_rn(__fmul_rn(coord_c, 2.0f), d));
+    g = __fadd_rn(g, __fmul_rn(coord_c, gs));
+    delta[t] = adam_update(d, m[t], v[t], g, beta1, beta2, eps, step_size, bc2_sqrt);
 }
 
 // counters[0] += slots that hit, counters[1] += slots that count (both zero on entry).  Non-targeted (scene_mask == NULL):
@@ -188,6 +221,23 @@ extern "C" int psg_scene_nu_step(float *w, float *m, float *v, const float *c, c
     hipLaunchKernelGGL(scene_nu_step_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, w, m, v, c, c0, scene_mask,
                        occ_off, occ_ent, dx0, sgrad, rows, total, cw, beta1, beta2, eps, k.step_size, k.bc2_sqrt, active, gsum_f_out,
                        gsum_s_out);
+    PSG_LAUNCH_CHECK();
+    return PSG_OK;
+}
+
+extern "C" int psg_scene_nu_field_step(float *delta, float *m, float *v, const uint8_t *scene_mask, const int32_t *occ_off,
+                                       const int32_t *occ_ent, const float *dx0, const float *sgrad_xyz, int rows, int n_scene,
+                                       float coord_c, float coord_lr, float beta1, float beta2, float eps, int step,
+                                       const int32_t *active, float *gsum_x_out, float *gsum_s_out, psg_stream stream)
+{
+    PSG_REQUIRE(delta && m && v && occ_off && occ_ent && dx0 && sgrad_xyz && active && n_scene > 0 && step >= 1,
+                "psg_scene_nu_field_step: bad argument");
+    PSG_REQUIRE(rows_ok(rows), "psg_scene_nu_field_step: rows=%d outside 1 .. INT_MAX / 9 (slot numbers address [rows][9] floats)", rows);
+    const AdamConsts k = adam_consts(coord_lr, beta1, beta2, step);
+    const size_t total = (size_t)n_scene * 3;
+    hipLaunchKernelGGL(scene_nu_field_step_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, delta, m, v, scene_mask,
+                       occ_off, occ_ent, dx0, sgrad_xyz, rows, total, coord_c, beta1, beta2, eps, k.step_size, k.bc2_sqrt, active,
+                       gsum_x_out, gsum_s_out);
     PSG_LAUNCH_CHECK();
     return PSG_OK;
 }

@@ -643,6 +643,29 @@ def scene_nu_step(w, m, v, c, c0, scene_mask, occ_off, occ_ent, dx0, sgrad, cw, 
     return w
 
 
+def scene_nu_field_step(delta, m, v, scene_mask, occ_off, occ_ent, dx0, sgrad_xyz, coord_c, coord_lr, beta1, beta2, eps, step,
+                        active, gsum_x_out=None, gsum_s_out=None):
+    """One Adam step (step >= 1) on the displacements delta / m / v [n_scene, 3] in place from channels 0:3 of the block
+    gradients dx0 [rows, 9] and the per-slot Smooth_xyz gradients sgrad_xyz [rows, 3], both summed over every point's slots in
+    ascending slot order; the L2 term once per point, no tanh space (psg_scene_nu_field_step)."""
+    n_scene, rows = delta.shape[0], occ_ent.numel()
+    for t, name in ((delta, "delta"), (m, "m"), (v, "v"), (dx0, "dx0"), (sgrad_xyz, "sgrad_xyz")):
+        require_cuda(t, name, torch.float32)
+    require_cuda(occ_off, "occ_off", torch.int32)
+    require_cuda(occ_ent, "occ_ent", torch.int32)
+    _scene_nu_common(scene_mask, active, n_scene)
+    for t, name in ((gsum_x_out, "gsum_x_out"), (gsum_s_out, "gsum_s_out")):
+        if t is not None:
+            require_cuda(t, name, torch.float32)
+            assert t.shape == delta.shape
+    assert delta.shape == m.shape == v.shape == (n_scene, 3) and occ_off.numel() == n_scene + 1
+    assert dx0.numel() == rows * 9 and sgrad_xyz.numel() == rows * 3
+    _lib.call("psg_scene_nu_field_step", ptr(delta), ptr(m), ptr(v), ptr(scene_mask), ptr(occ_off), ptr(occ_ent), ptr(dx0),
+              ptr(sgrad_xyz), rows, n_scene, float(coord_c), float(coord_lr), float(beta1), float(beta2), float(eps), int(step),
+              ptr(active), ptr(gsum_x_out), ptr(gsum_s_out), stream())
+    return delta
+
+
 def scene_nu_latch(pred, labels, target, point_idx, scene_mask, num, den, step, c, snap, counters, hist_row, exit_step, active):
     """The integer exit test of the whole-scene NU attack over all slots (psg_scene_nu_latch): pred / labels / point_idx int32
     [rows]; scene_mask None = non-targeted (hits: pred == labels, fires when hits * den < num * rows), uint8 [n_scene] =

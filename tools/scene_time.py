@@ -31,6 +31,12 @@ from torch.manual_seed to a device synchronise.  No speed bar: the scene attack 
 one stream and replays nothing, the per-block path plans ten steps at once and replays captured windows.  With --attack nu
 --kernel-trace / --trace-only report the share of the kernels of csrc/psg_scene_nu.hip (and of the psg_scene.hip kernels the
 attack launches) in a `--only scene_nu --runs 1` profiler run.
+
+--attack nu --field coord | both alternates three variants in the same way: `scene_nu_field` -
+SceneNUAttack(field=...), Adam on one displacement per scene point -, `scene_nu` - the colour field of the same loop - and
+`per_block_nu_field` - NU_attack(field=...).forward_rooms over the same blocks in groups of batch_size.  The ratios are
+scene_nu_field over each of the other two; the kernel-trace share (a `--only scene_nu_field --runs 1` profiler run) lists
+scene_nu_field_step_kernel on its own.  No speed bar.
 """
 import argparse
 import json
@@ -81,8 +87,9 @@ def scene_kernel_share(path):
 
 
 NU_KERNELS = ("scene_nu_init_kernel", "scene_nu_colour_kernel", "scene_nu_step_kernel", "scene_nu_count_kernel",
-              "scene_nu_decide_kernel")
+              "scene_nu_decide_kernel", "scene_nu_field_step_kernel")
 NU_VARIANTS = ("scene_nu", "per_block_nu")
+NU_FIELD_VARIANTS = ("scene_nu_field", "scene_nu", "per_block_nu_field")
 
 
 def nu_kernel_share(path):
@@ -101,8 +108,9 @@ def nu_kernel_share(path):
                 d["total_us"] += us
     nu = sum(d["total_us"] for k, d in per.items() if k in NU_KERNELS)
     scene = sum(d["total_us"] for k, d in per.items() if k in OURS)
+    step = per.get("scene_nu_field_step_kernel", {}).get("total_us", 0.0)
     return dict(nu_kernels_us=nu, scene_kernels_us=scene, all_kernels_us=total, nu_share=nu / total if total else None,
-                scene_share=scene / total if total else None, kernels=per)
+                scene_share=scene / total if total else None, field_step_share=step / total if total else None, kernels=per)
 
 
 def main_nu(a, ap):
@@ -116,8 +124,9 @@ def main_nu(a, ap):
     from pointsecguard_amd.attacks.scene import SceneNUAttack
     from pointsecguard_amd.models.pointnet2_sem_seg import get_model, upload
     assert torch.cuda.is_available(), "scene_time.py measures on the MI355X; there is nothing to time without it"
-    if a.only and a.only not in NU_VARIANTS:
-        ap.error("--only %s does not exist under --attack nu" % a.only)
+    all_variants = NU_VARIANTS if a.field == "color" else NU_FIELD_VARIANTS
+    if a.only and a.only not in all_variants:
+        ap.error("--only %s does not exist under --attack nu --field %s" % (a.only, a.field))
     room = synthetic_room(a.points, a.size[0], a.size[1])
     ds = harness.ScannetDatasetWholeScene(None, block_points=a.block_points, scenes={"Area_5_room.npy": room})
     np.random.seed(3)
@@ -140,17 +149,19 @@ def main_nu(a, ap):
         torch.manual_seed(3)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if variant == "scene_nu":
-            atk = SceneNUAttack(net, steps=a.iters, batch_size=a.batch_size, exit_below=(0, 1))
+        if variant in ("scene_nu", "scene_nu_field"):
+            atk = SceneNUAttack(net, steps=a.iters, batch_size=a.batch_size, exit_below=(0, 1),
+                                field=a.field if variant == "scene_nu_field" else "color")
             atk(x, idx, gt, rgb, scene_labels)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             ran[variant] = [a.iters if atk.last_exit_step < 0 else atk.last_exit_step + 1]
         else:
-            atk = torchattacks.NU_attack(net, steps=a.iters)
+            field = a.field if variant == "per_block_nu_field" else "color"
+            atk = torchattacks.NU_attack(net, steps=a.iters, field=field)
             steps_run = []
             for lo, hi in groups:
-                if hi - lo > 1:
+                if hi - lo > 1 or field != "color":       # (the field form attacks one room per call: rooms form throughout)
                     steps_run += [int(s) for s in atk.forward_rooms(images[lo:hi], gt[lo:hi])[1]]
                 else:
                     atk(images[lo:hi], gt[lo:hi])
@@ -159,7 +170,7 @@ def main_nu(a, ap):
             ran[variant] = steps_run
         return n_blocks / dt
 
-    variants = [a.only] if a.only else list(NU_VARIANTS)
+    variants = [a.only] if a.only else list(all_variants)
     for v in variants:                          # warm-up: workspaces, packed weights, captured windows
         call(v)
     rate = {v: [] for v in variants}
@@ -169,10 +180,12 @@ def main_nu(a, ap):
     med = {v: statistics.median(r) for v, r in rate.items()}
     out = dict(tool="scene_time", attack="nu", device=torch.cuda.get_device_name(0), n_points=a.points, size=list(a.size),
                block_points=a.block_points, n_blocks=n_blocks, batch_size=a.batch_size, steps=a.iters, exit_below=[0, 1], runs=a.runs,
-               occurrences=dict(mean=float(counts.mean()), max=int(counts.max()), multi_share=float((counts > 1).mean())),
+               field=a.field, occurrences=dict(mean=float(counts.mean()), max=int(counts.max()), multi_share=float((counts > 1).mean())),
                blocks_per_s={v: dict(median=med[v], min=min(r), max=max(r), spread=(max(r) - min(r)) / med[v]) for v, r in rate.items()},
                steps_run={v: dict(min=min(r), max=max(r)) for v, r in ran.items() if r})
-    if not a.only:
+    if not a.only and a.field != "color":
+        out["scene_nu_field_over"] = {v: med["scene_nu_field"] / med[v] for v in variants if v != "scene_nu_field"}
+    elif not a.only:
         out["scene_nu_over_per_block_nu"] = med["scene_nu"] / med["per_block_nu"]
     if a.kernel_trace:
         out["kernel_trace"] = nu_kernel_share(a.kernel_trace)
@@ -193,7 +206,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--field", choices=("color", "coord", "both"), default="color")
-    ap.add_argument("--only", choices=sorted(set(VARIANTS + FIELD_VARIANTS + NU_VARIANTS)), default=None)
+    ap.add_argument("--only", choices=sorted(set(VARIANTS + FIELD_VARIANTS + NU_VARIANTS + NU_FIELD_VARIANTS)), default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-trace", default=None)
     ap.add_argument("--trace-only", action="store_true")
