@@ -358,6 +358,27 @@ int psg_pointnet_backward(psg_pointnet_model *model, psg_pointnet_ws *ws, const 
 int psg_pointnet_nb_attack(psg_pointnet_model *model, psg_pointnet_ws *ws, const float *images, const int32_t *labels,
                            const uint8_t *mask, float eps, float alpha, int iters, int targeted, int target, float *adv_out,
                            psg_stream stream);
+/* Read-only tap into the workspace (tests): the device pointer of a named buffer with its row and column counts; NULL
+ * with the error string set for a null workspace or an unknown `what`.  Launches nothing, allocates nothing, does not
+ * synchronise.  float32 unless noted; B rooms of N points, R = B N rows, T = R / PSG_POINTNET_POINT_TILE tiles.
+ *   forward state, valid from a forward call until the next forward call:
+ *     per point:  0 a1 [R][64]  1 a2 [R][128]  2 h [R][64]  3 k1 [R][64]  4 k2 [R][128]  5 e2 [R][128]  6 z1 [R][512]
+ *       7 z2 [R][256]  8 z3 [R][128]  9 logits [R][13]  10 logp [R][13]  11 x0in [R][9] (the forward's input)
+ *     ReLU bits, uint32 words, cols = words per row, bit c%32 of word c/32 = (activation > 0):
+ *       20 mh [R][2]  21 m1 [R][16]  22 m2 [R][8]  23 m3 [R][4]  24 mf1 [B][16]  25 mf2 [B][8]  26 mfk1 [B][16]  27 mfk2 [B][8]
+ *     pools, columns [STN3d 1024 | STNkd 1024 | encoder 1024]:  30 pool [B][3072]  31 pidx [B][3072] (int32, room-local)
+ *       32 part_val [T][1024]  33 part_idx [T][1024] (int32): the per-tile partial maxima; all three pooled layers write
+ *       them in turn, so after a forward they hold the ENCODER pool's tiles only
+ *     per room:  40 f1 [B][512]  41 f2 [B][256]  42 trans [B][9]  43 fk1 [B][512]  44 fk2 [B][256]  45 tf [B][4096]
+ *       46 t1 [64][3B]  47 w1f [64B][8] (room b = rows 64b .. 64b+63)  48 c2f [128][64B]  49 h1pf [512][64B]  50 gb [B][512]
+ *   gradient state, valid from a backward call until the next backward call:
+ *     60 dz4 [R][13]  61 dz3 [R][128]  62 dz2 [R][256]  63 dz1 [R][512]  64 s1 [B][512]  65 dg [B][1024]  66 dpf [R][64]
+ *     67 ht [64B][N]  68 dpft [64B][N] (the per-room transposes of h and dpf)  69 dtf [B][4096]  70 dfk2 [B][256]
+ *     71 dfk1 [B][512]  72 dgk [B][1024]  73 dh [R][64]  74 dxu [R][8]  75 dtrans [B][9]  76 df2 [B][256]  77 df1 [B][512]
+ *     78 dgs [B][1024]
+ * The attack loops (psg_pointnet_nb_attack, psg_pointnet_nu_window) run forwards and backwards of their own in the same
+ * workspace: after one of them the buffers hold its last iteration. */
+const void *psg_pointnet_debug_ptr(const psg_pointnet_ws *ws, int what, int *rows_out, int *cols_out);
 
 /* ---- NU (Adam in tanh space) attack arithmetic: nontarget.py:52-135, target.py:62-175 -------------
  * w / m / v are [B][N][3] fp32 (the attack variable and its Adam moments); colours live in channels 3:6

@@ -83,6 +83,7 @@ SIGNATURES = {
     "psg_pointnet_forward": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "psg_pointnet_backward": (ci, [vp, vp, vp, vp, vp, vp]),
     "psg_pointnet_nb_attack": (ci, [vp, vp, vp, vp, vp, cf, cf, ci, ci, ci, vp, vp]),
+    "psg_pointnet_debug_ptr": (vp, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "psg_nu_inverse_tanh": (ci, [vp, ci, ci, vp, vp]),
     "psg_nu_tanh_color": (ci, [vp, vp, ci, ci, vp, vp]),
     "psg_nu_f_loss_grad": (ci, [vp, vp, ci, ci, ci, cf, cf, vp, vp, vp, vp]),

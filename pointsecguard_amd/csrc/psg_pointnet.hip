@@ -820,6 +820,77 @@ extern "C" int psg_pointnet_forward(psg_pointnet_model *m, psg_pointnet_ws *ws, 
     return PSG_OK;
 }
 
+// Read-only tap into the workspace (include/psg.h lists the codes and the two validity windows): a pointer, a row count
+// and a column count; no launch, no allocation, no synchronisation.
+extern "C" const void *psg_pointnet_debug_ptr(const psg_pointnet_ws *ws, int what, int *rows_out, int *cols_out)
+{
+    if (!ws) { set_error("psg_pointnet_debug_ptr: null workspace"); return nullptr; }
+    const int B = ws->B, R = ws->B * ws->N, T = R / PT;
+    const void *p = nullptr;
+    int r = 0, c = 0;
+    auto put = [&](const void *ptr, int rows, int cols) { p = ptr; r = rows; c = cols; };
+    switch (what) {
+    case 0: put(ws->a1, R, 64); break;
+    case 1: put(ws->a2, R, 128); break;
+    case 2: put(ws->h, R, 64); break;
+    case 3: put(ws->k1, R, 64); break;
+    case 4: put(ws->k2, R, 128); break;
+    case 5: put(ws->e2, R, 128); break;
+    case 6: put(ws->z1, R, 512); break;
+    case 7: put(ws->z2, R, 256); break;
+    case 8: put(ws->z3, R, 128); break;
+    case 9: put(ws->logits, R, NCLS); break;
+    case 10: put(ws->logp, R, NCLS); break;
+    case 11: put(ws->x0in, R, 9); break;
+    case 20: put(ws->mh, R, 2); break;                                // mask words: cols = 32-bit words per row
+    case 21: put(ws->m1, R, 16); break;
+    case 22: put(ws->m2, R, 8); break;
+    case 23: put(ws->m3, R, 4); break;
+    case 24: put(ws->mf1, B, 16); break;
+    case 25: put(ws->mf2, B, 8); break;
+    case 26: put(ws->mfk1, B, 16); break;
+    case 27: put(ws->mfk2, B, 8); break;
+    case 30: put(ws->pool, B, 3 * GF); break;
+    case 31: put(ws->pidx, B, 3 * GF); break;                         // int32
+    case 32: put(ws->part_val, T, GF); break;
+    case 33: put(ws->part_idx, T, GF); break;                         // int32
+    case 40: put(ws->f1, B, 512); break;
+    case 41: put(ws->f2, B, 256); break;
+    case 42: put(ws->trans, B, 9); break;
+    case 43: put(ws->fk1, B, 512); break;
+    case 44: put(ws->fk2, B, 256); break;
+    case 45: put(ws->tf, B, 4096); break;
+    case 46: put(ws->t1, 64, 3 * B); break;
+    case 47: put(ws->w1f, B * 64, 8); break;
+    case 48: put(ws->c2f, 128, 64 * B); break;
+    case 49: put(ws->h1pf, 512, 64 * B); break;
+    case 50: put(ws->gb, B, 512); break;
+    case 60: put(ws->dz4, R, NCLS); break;
+    case 61: put(ws->dz3, R, 128); break;
+    case 62: put(ws->dz2, R, 256); break;
+    case 63: put(ws->dz1, R, 512); break;
+    case 64: put(ws->s1, B, 512); break;
+    case 65: put(ws->dg, B, GF); break;
+    case 66: put(ws->dpf, R, 64); break;
+    case 67: put(ws->ht, B * 64, ws->N); break;
+    case 68: put(ws->dpft, B * 64, ws->N); break;
+    case 69: put(ws->dtf, B, 4096); break;
+    case 70: put(ws->dfk2, B, 256); break;
+    case 71: put(ws->dfk1, B, 512); break;
+    case 72: put(ws->dgk, B, GF); break;
+    case 73: put(ws->dh, R, 64); break;
+    case 74: put(ws->dxu, R, 8); break;
+    case 75: put(ws->dtrans, B, 9); break;
+    case 76: put(ws->df2, B, 256); break;
+    case 77: put(ws->df1, B, 512); break;
+    case 78: put(ws->dgs, B, GF); break;
+    default: set_error("psg_pointnet_debug_ptr: unknown buffer code what=%d", what); return nullptr;
+    }
+    if (rows_out) *rows_out = r;
+    if (cols_out) *cols_out = c;
+    return p;
+}
+
 extern "C" int psg_pointnet_backward(psg_pointnet_model *m, psg_pointnet_ws *ws, const float *dlogp, const float *dtrans_feat,
                                      float *dx0_out, psg_stream stream)
 {

@@ -417,6 +417,28 @@ class PointNetWorkspace(_Handle):
         _lib.call("psg_pointnet_backward", model.handle, self.handle, ptr(dlogp), ptr(dtrans_feat), ptr(dx0), stream())
         return dx0
 
+    # psg_pointnet_debug_ptr codes (include/psg.h)
+    DEBUG = {"a1": 0, "a2": 1, "h": 2, "k1": 3, "k2": 4, "e2": 5, "z1": 6, "z2": 7, "z3": 8, "logits": 9, "logp": 10, "x0in": 11,
+             "mh": 20, "m1": 21, "m2": 22, "m3": 23, "mf1": 24, "mf2": 25, "mfk1": 26, "mfk2": 27,
+             "pool": 30, "pidx": 31, "part_val": 32, "part_idx": 33,
+             "f1": 40, "f2": 41, "trans": 42, "fk1": 43, "fk2": 44, "tf": 45, "t1": 46, "w1f": 47, "c2f": 48, "h1pf": 49, "gb": 50,
+             "dz4": 60, "dz3": 61, "dz2": 62, "dz1": 63, "s1": 64, "dg": 65, "dpf": 66, "ht": 67, "dpft": 68, "dtf": 69, "dfk2": 70,
+             "dfk1": 71, "dgk": 72, "dh": 73, "dxu": 74, "dtrans": 75, "df2": 76, "df1": 77, "dgs": 78}
+
+    def debug(self, what):
+        """A workspace buffer by name (tests): a [rows, cols] copy taken on the current stream, float32 except the ReLU bit
+        words m* and the arg-max sets pidx / part_idx (int32).  Forward buffers are valid from a forward until the next
+        forward, the d* ones, s1, ht from a backward until the next backward."""
+        code = self.DEBUG[what]
+        rows, cols = ctypes.c_int(), ctypes.c_int()
+        src = _lib.load().psg_pointnet_debug_ptr(self.handle, code, ctypes.byref(rows), ctypes.byref(cols))
+        if not src:
+            raise _lib.PsgError("psg_pointnet_debug_ptr(%s): %s" % (what, _lib.load().psg_last_error().decode()))
+        dtype = torch.int32 if (20 <= code < 30 or code in (31, 33)) else torch.float32
+        out = torch.empty(rows.value, cols.value, dtype=dtype, device=self.device)
+        _hip_memcpy_d2d(out.data_ptr(), src, out.numel() * 4)
+        return out
+
     def nb_attack(self, model, images, labels, eps, alpha, iters, mask=None, target=None, out=None):
         require_cuda(images, "images", torch.float32)
         if labels is not None:

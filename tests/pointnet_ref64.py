@@ -31,42 +31,78 @@ def _fc(sd, name, x):
     return F.linear(x, _t(sd, name + ".weight"), _t(sd, name + ".bias"))
 
 
-def _stn(sd, p, x, k):
-    x = F.relu(_bn(sd, p + ".bn1", _conv(sd, p + ".conv1", x)))
-    x = F.relu(_bn(sd, p + ".bn2", _conv(sd, p + ".conv2", x)))
-    x = F.relu(_bn(sd, p + ".bn3", _conv(sd, p + ".conv3", x)))
-    g, arg = torch.max(x, 2)
-    x = F.relu(_bn(sd, p + ".bn4", _fc(sd, p + ".fc1", g)))
-    x = F.relu(_bn(sd, p + ".bn5", _fc(sd, p + ".fc2", x)))
+def _relu(x, dec, key):
+    """ReLU, or - with prescribed decisions - the product with the given 0 / 1 gate of x's shape"""
+    return F.relu(x) if dec is None else x * dec[key]
+
+
+def _stn(sd, p, x, k, dec=None):
+    x = _relu(_bn(sd, p + ".bn1", _conv(sd, p + ".conv1", x)), dec, p + ".1")
+    x = _relu(_bn(sd, p + ".bn2", _conv(sd, p + ".conv2", x)), dec, p + ".2")
+    x = _bn(sd, p + ".bn3", _conv(sd, p + ".conv3", x))
+    if dec is None:
+        g, arg = torch.max(F.relu(x), 2)
+    else:                                   # the pooled layer's ReLU acts on the pooled value: gate [B,1024]
+        arg = dec[p + ".arg"]
+        g = torch.gather(x, 2, arg[:, :, None])[:, :, 0] * dec[p + ".pool"]
+    x = _relu(_bn(sd, p + ".bn4", _fc(sd, p + ".fc1", g)), dec, p + ".4")
+    x = _relu(_bn(sd, p + ".bn5", _fc(sd, p + ".fc2", x)), dec, p + ".5")
     x = _fc(sd, p + ".fc3", x) + torch.eye(k, dtype=torch.float64).reshape(1, k * k)
     return x.view(-1, k, k), g, arg
 
 
-def forward(sd, x, extras=False):
+def forward(sd, x, extras=False, decide=None):
     """x [B,9,N] float64 -> (log_probs [B,N,13], trans_feat [B,64,64]); extras=True adds a dict with trans, the three
-    pooled vectors 'g_stn', 'g_fstn', 'g_feat' [B,1024] and their arg-max sets 'arg_*' [B,1024]."""
+    pooled vectors 'g_stn', 'g_fstn', 'g_feat' [B,1024] and their arg-max sets 'arg_*' [B,1024].
+    decide: the network's discrete decisions PRESCRIBED instead of taken (device_decisions builds them from a workspace
+    snapshot): float64 0 / 1 gates in the layout of the tensor they multiply - 'feat.stn.1', '.2' [B,C,N], '.4', '.5' [B,C]
+    and '.pool' [B,1024] (likewise 'feat.fstn.*'), 'h', 'e2', 'z1', 'z2', 'z3' [B,C,N] - and the int64 arg-max sets
+    'feat.stn.arg', 'feat.fstn.arg', 'arg' [B,1024].  The result is then a smooth function of x around the decisions."""
     B, _, N = x.shape
     x = x[:, :6, :]
-    trans, g_stn, arg_stn = _stn(sd, "feat.stn", x, 3)
+    dec = decide
+    trans, g_stn, arg_stn = _stn(sd, "feat.stn", x, 3, dec)
     xt = x.transpose(2, 1)
     xyz, feat = xt.split(3, dim=2)
     xt = torch.cat([torch.bmm(xyz, trans), feat], dim=2).transpose(2, 1)
-    h = F.relu(_bn(sd, "feat.bn1", _conv(sd, "feat.conv1", xt)))
-    trans_feat, g_fstn, arg_fstn = _stn(sd, "feat.fstn", h, 64)
+    h = _relu(_bn(sd, "feat.bn1", _conv(sd, "feat.conv1", xt)), dec, "h")
+    trans_feat, g_fstn, arg_fstn = _stn(sd, "feat.fstn", h, 64, dec)
     pf = torch.bmm(h.transpose(2, 1), trans_feat).transpose(2, 1)
-    e = F.relu(_bn(sd, "feat.bn2", _conv(sd, "feat.conv2", pf)))
+    e = _relu(_bn(sd, "feat.bn2", _conv(sd, "feat.conv2", pf)), dec, "e2")
     e = _bn(sd, "feat.bn3", _conv(sd, "feat.conv3", e))
-    g, arg = torch.max(e, 2)
+    if dec is None:
+        g, arg = torch.max(e, 2)
+    else:
+        arg = dec["arg"]
+        g = torch.gather(e, 2, arg[:, :, None])[:, :, 0]
     z = torch.cat([g[:, :, None].expand(B, 1024, N), pf], 1)
-    z = F.relu(_bn(sd, "bn1", _conv(sd, "conv1", z)))
-    z = F.relu(_bn(sd, "bn2", _conv(sd, "conv2", z)))
-    z = F.relu(_bn(sd, "bn3", _conv(sd, "conv3", z)))
+    z = _relu(_bn(sd, "bn1", _conv(sd, "conv1", z)), dec, "z1")
+    z = _relu(_bn(sd, "bn2", _conv(sd, "conv2", z)), dec, "z2")
+    z = _relu(_bn(sd, "bn3", _conv(sd, "conv3", z)), dec, "z3")
     z = _conv(sd, "conv4", z).transpose(2, 1).contiguous()
     logp = F.log_softmax(z.view(-1, 13), dim=-1).view(B, N, 13)
     if not extras:
         return logp, trans_feat
     return logp, trans_feat, dict(trans=trans, g_stn=g_stn, g_fstn=g_fstn, g_feat=g, arg_stn=arg_stn, arg_fstn=arg_fstn,
                                   arg_feat=arg, h=h)
+
+
+def device_decisions(snap, B, N):
+    """`decide` of forward() from a workspace snapshot (tap names; bit words unpacked to [rows, M] bool)"""
+    def pts(a):                                                  # [B*N, C] -> [B, C, N]
+        return torch.from_numpy(np.asarray(a).reshape(B, N, -1).transpose(0, 2, 1).astype(np.float64))
+
+    def room(a):
+        return torch.from_numpy(np.asarray(a).astype(np.float64))
+    pool, pidx = np.asarray(snap["pool"]), np.asarray(snap["pidx"]).astype(np.int64)
+    dec = {"h": pts(snap["mh"]), "e2": pts(np.asarray(snap["e2"]) > 0), "z1": pts(snap["m1"]), "z2": pts(snap["m2"]), "z3": pts(snap["m3"]),
+           "arg": torch.from_numpy(pidx[:, 2048:])}
+    for p, k, a1, a2, m1, m2 in (("feat.stn", 0, "a1", "a2", "mf1", "mf2"), ("feat.fstn", 1, "k1", "k2", "mfk1", "mfk2")):
+        dec[p + ".1"], dec[p + ".2"] = pts(np.asarray(snap[a1]) > 0), pts(np.asarray(snap[a2]) > 0)
+        dec[p + ".4"], dec[p + ".5"] = room(snap[m1]), room(snap[m2])
+        dec[p + ".pool"] = room(pool[:, k * 1024:(k + 1) * 1024] > 0)
+        dec[p + ".arg"] = torch.from_numpy(pidx[:, k * 1024:(k + 1) * 1024])
+    return dec
 
 
 def regulariser(trans):

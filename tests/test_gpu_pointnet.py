@@ -116,6 +116,7 @@ def test_regulariser_gradient_reaches_input(net, sd, rooms):
     (tf64 * tf64).sum().backward()
     got, want = x.grad.cpu().numpy()[:, :6], ref64_x.grad.numpy()[:, :6]
     assert _sign_agree(got, want) >= 0.999
+    assert np.abs(got - want).max() <= 1e-3 * np.abs(want).max()
 
 
 def test_repeat_and_batch_are_bit_identical(sd):
