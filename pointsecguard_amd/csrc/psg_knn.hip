@@ -1,7 +1,7 @@
 // Fused feature-space kNN kernels of the ResGCN path (C = 64) in their own translation unit: compiled with the MFMA
 // accumulators in VGPRs (every accumulator is read by vector compares right after the matrix instructions: the AGPR form
 // costs one v_accvgpr_read per value) and with -ffp-contract=off (the exact distances follow the reference's fp32
-// evaluation order, SURVEY 8a').  psg_resgcn.hip calls the launchers below (psg_knn.h).
+// evaluation order, SURVEY 8a').  psg_resgcn.hip calls the launchers below (psg_knn.h); which one a block takes is knn_path there, on the inputs psg_gcn_plan.h supplies.
 #include "psg_knn.h"
 #include "psg_common.h"
 

@@ -1,7 +1,7 @@
 // Per-operator entry points behind the stand-alone forwards of the reference's public modules:
 //   PointNetSetAbstraction(.Msg).forward   PointNet/models/pointnet_util.py:181-207, 229-267
 //   PointNetFeaturePropagation.forward     PointNet/models/pointnet_util.py:281-320
-// (the ResGCN ones - EdgeConv2d, pairwise_distance - live in psg_resgcn.hip next to the kernels they launch).
+// (the ResGCN ones - EdgeConv2d, pairwise_distance - live in psg_resgcn.hip, the unit that includes their kernels, psg_resgcn_kernels.cuh).
 // Inside get_model these modules run as ONE fused kernel each (psg_pn2.hip); called on their own they are composed from
 // the operators here, every one a thin launch on the caller's tensors: grouping (gather + centre + concat), the shared
 // 1x1-conv stack on the fp32-MFMA row GEMM of psg_gemm.cuh (BatchNorm folded by the caller, ReLU bits kept for the

@@ -1,4 +1,4 @@
-// Wave-level helpers shared by the kNN translation units (psg_resgcn.hip, psg_knn.hip): DPP reductions over the 64 lanes,
+// Wave-level helpers shared by the kNN translation units (psg_resgcn.hip through psg_resgcn_kernels.cuh, psg_knn.hip): DPP reductions over the 64 lanes,
 // the order-preserving float <-> unsigned key map and the in-register bitonic sort of composite keys.
 #pragma once
 #include <hip/hip_runtime.h>

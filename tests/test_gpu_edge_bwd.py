@@ -1,4 +1,4 @@
-"""The EdgeConv max-pass backward without atomics (edge_max_bwd_gather_kernel, psg_resgcn.hip): the transpose of
+"""The EdgeConv max-pass backward without atomics (edge_max_bwd_gather_kernel, psg_resgcn_kernels.cuh): the transpose of
 `batched_index_select` + `max` (ResGCN/gcn_lib/dense/torch_nn.py:82-98, torch_vertex.py:31-35) as a gather through the
 inverse graph.  Checked through the C ABI (psg_edgeconv_bwd leaves [dP | dQ] in its scratch argument) against a numpy
 restatement that sums every destination's in-edges in the kernel's documented order (equal slices of the workgroup's flat
