@@ -1392,6 +1392,47 @@ int psg_scene_nu_field_step(float *delta, float *m, float *v, const uint8_t *sce
                             float coord_c, float coord_lr, float beta1, float beta2, float eps, int step,
                             const int32_t *active, float *gsum_x_out, float *gsum_s_out, psg_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The whole-scene block slicer on the device (psg_slice.hip): the per-cell work of
+ * ScannetDatasetWholeScene.__getitem__ (PointNet/data_utils/S3DISDataLoader.py:124-175).  The random draws stay on the
+ * host (harness.slice_plan: they depend on the cells' member counts only).  No handle: the caller owns every buffer.
+ * Everything is enqueued on `stream`; nothing here synchronises.  No atomics; every output element has one writer; two
+ * runs give the same bytes.
+ *
+ * Scene: n <= 2^30 points; x of point p at xy[p * stride], y at xy[p * stride + 1] (float64; stride in doubles, >= 2).
+ * windows [n_cells][4] float64 = {s_x - pad, e_x + pad, s_y - pad, e_y + pad} in the slicer's cell order (iy outer, ix
+ * inner), computed by the host; point p is a member of cell c when x >= w[0] && x <= w[1] && y >= w[2] && y <= w[3] (IEEE
+ * double compares; a NaN is in no cell).  1 <= n_cells <= PSG_SLICE_MAX_CELLS (the windows sit in LDS), anything else is
+ * PSG_ERR_ARG.  tile_off: int32 scratch of tile_items >= n_cells * ceil(n / PSG_SLICE_TILE) + 1 items (a product beyond
+ * 2^30 is refused), written by psg_slice_count and read by psg_slice_members.
+ *
+ * psg_slice_count: counts [n_cells] = the members of every cell; cell_off [n_cells + 1] = their exclusive prefix sums
+ * modulo 2^32 (the caller sums counts in 64 bits and goes no further when the total exceeds INT_MAX).
+ * psg_slice_members: inside [inside_len], inside_len = the total: the members of cell c in ASCENDING point index
+ * (np.where's order) at cell_off[c] .. cell_off[c + 1].  Same xy / windows as the count; a position outside inside_len
+ * is not written.
+ * psg_slice_gather: one output slot e = b * bp + i of nb blocks of bp points (nb * bp <= INT_MAX / 9): cell =
+ * block_cell[b], p = inside[cell_off[cell] + src_pos[e]];
+ *   data [nb][bp][9] float32 = x - centres[cell][0], y - centres[cell][1], z, r / 255.0, g / 255.0, b / 255.0, x / cmax_x,
+ *     y / cmax_y, z / cmax_z: each ONE float64 operation (a true division) rounded once to float32;
+ *   label [nb][bp] = labels[p];  smpw = labelweights[label] (float32 table of PSG_SLICE_CLASSES entries; +0 for a label
+ *   outside it);  index = p.
+ * xyz [n] rows of xyz_stride doubles, rgb [n] rows of rgb_stride doubles (both >= 3), centres [n_cells][2] float64.  A slot
+ * whose cell, position or point is out of range reads nothing through it: data 0, label 0, smpw 0, index -1.
+ * ------------------------------------------------------------------------------------------ */
+#define PSG_SLICE_MAX_CELLS 1024
+#define PSG_SLICE_TILE 256
+#define PSG_SLICE_CLASSES 13
+int psg_slice_count(const double *xy, int stride, int n, const double *windows, int n_cells, int32_t *tile_off,
+                    long long tile_items, int32_t *counts, int32_t *cell_off, psg_stream stream);
+int psg_slice_members(const double *xy, int stride, int n, const double *windows, int n_cells, const int32_t *tile_off,
+                      long long tile_items, int32_t *inside, int inside_len, psg_stream stream);
+int psg_slice_gather(const double *xyz, int xyz_stride, const double *rgb, int rgb_stride, const int32_t *labels, int n,
+                     const int32_t *inside, int inside_len, const int32_t *cell_off, const int32_t *block_cell,
+                     const double *centres, int n_cells, const int32_t *src_pos, int nb, int bp, double cmax_x, double cmax_y,
+                     double cmax_z, const float *labelweights, float *data, int32_t *label, float *smpw, int32_t *index,
+                     psg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

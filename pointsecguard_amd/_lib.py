@@ -198,8 +198,14 @@ SIGNATURES = {
     "psg_scene_nu_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, cf, cf, ci, vp, vp, vp, vp]),
     "psg_scene_nu_latch": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
     "psg_scene_nu_field_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, cf, cf, ci, vp, vp, vp, vp]),
+    "psg_slice_count": (ci, [vp, ci, ci, vp, ci, vp, ctypes.c_longlong, vp, vp, vp]),
+    "psg_slice_members": (ci, [vp, ci, ci, vp, ci, vp, ctypes.c_longlong, vp, ci, vp]),
+    "psg_slice_gather": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, vp, vp, vp, vp, vp, vp]),
 }
 
+SLICE_MAX_CELLS = 1024   # PSG_SLICE_MAX_CELLS of include/psg.h
+SLICE_TILE = 256         # PSG_SLICE_TILE
 
 
 class NuWindowArgs(ctypes.Structure):

@@ -1,7 +1,8 @@
 """Whole-scene evaluation harness on the device.
 
 Mirrors, relative to /root/reference/PointNet:
-  data_utils/S3DISDataLoader.py:81-178      ScannetDatasetWholeScene  (host-side block slicing: numpy, like the reference)
+  data_utils/S3DISDataLoader.py:81-178      ScannetDatasetWholeScene  (host-side block slicing: numpy, like the reference;
+                                            device_item / slicer="device": the same blocks cut on the device)
   NB_nontarget_test_semseg.py:55-62         add_vote                  (device: psg_vote_add)
   NB_nontarget_test_semseg.py:126-291       the per-scene loop: clean / adversarial predictions of every block batch,
                                             vote pools, per-batch TSV log rows, per-scene and total IoU / accuracy
@@ -27,6 +28,66 @@ LOG_HEADER = "index\tL2_dis\tadv_acc\tacc\tadv_miou\tmiou\n"            # :110
 LOG_ROW = "%d\t%.3f\t%.5f\t%.5f\t%.5f\t\t%.5f\n"                         # :213-215
 TARGETED_LOG_HEADER = "ori\tindex\tL2_dis\tcount\t target acc\tadv_acc\tacc\tadv_miou\tmiou\n"      # NB_target_test_semseg.py:93
 TARGETED_LOG_ROW = "%d\t%d\t%.3f\t%d\t%.5f\t%.5f\t%.5f\t%.5f\t\t%.5f\n"                          # :226-229
+
+
+SLICERS = ("host", "device")
+
+
+def check_slicer(slicer):
+    if slicer not in SLICERS:
+        raise ValueError("slicer must be one of %s, got %r" % (SLICERS, slicer))
+    return slicer
+
+
+def slice_plan(counts, block_points):
+    """The random part of ScannetDatasetWholeScene.__getitem__ from the cells' member counts alone.
+
+    counts: the number of points in every grid cell, in the slicer's cell order (iy outer, ix inner), empty cells included.
+    Per non-empty cell, in that order, numpy's GLOBAL generator is consumed exactly as the slicer consumes it - the padding
+    draw np.random.choice(cnt, extra, replace=extra > cnt) (also when extra == 0), then one permutation of the padded
+    length - because both draws depend on the cell's count only, not on which points its members are; an empty cell draws
+    nothing.  Returns (src_pos, first_block, nb): src_pos int32 [nb * block_points] = for every output slot its position in
+    its cell's member list (np.where's ascending order), first_block int32 [n_cells] = the first block of every cell (a
+    cell of cnt members fills ceil(cnt / block_points) blocks; an empty cell none), nb = the number of blocks.  A scene
+    without a non-empty cell raises ValueError (the host slicer raises too, on its empty vstack)."""
+    counts = np.asarray(counts).astype(np.int64).reshape(-1)
+    bp = int(block_points)
+    if bp < 1 or (counts < 0).any():
+        raise ValueError("slice_plan: block_points=%d and the counts must not be negative" % bp)
+    blocks = -(-counts // bp)
+    first_block = np.concatenate(([0], np.cumsum(blocks)[:-1])) if counts.size else np.zeros(0, np.int64)
+    nb = int(blocks.sum())
+    if nb == 0:
+        raise ValueError("slice_plan: no grid cell holds a point (need at least one array to concatenate)")
+    src_pos = np.empty(nb * bp, dtype=np.int32)
+    for c in np.flatnonzero(counts):
+        cnt, total = int(counts[c]), int(blocks[c]) * bp
+        extra = total - cnt
+        fill = np.random.choice(cnt, extra, replace=extra > cnt)
+        perm = np.random.permutation(total)
+        lo = int(first_block[c]) * bp
+        src_pos[lo:lo + total] = np.concatenate((np.arange(cnt), fill))[perm]
+    return src_pos, first_block.astype(np.int32), nb
+
+
+def slice_cells(cmin, cmax, block_size, stride, padding):
+    """The grid of ScannetDatasetWholeScene.__getitem__ from a scene's corners, with that method's own float64 expressions:
+    (windows float64 [n_cells, 4] = {s_x - pad, e_x + pad, s_y - pad, e_y + pad}, centres float64 [n_cells, 2] = {s_x + bs /
+    2.0, s_y + bs / 2.0}, grid_x, grid_y), cells in the slicer's order (iy outer, ix inner)."""
+    bs, st, pad = block_size, stride, padding
+    grid_x = int(np.ceil(float(cmax[0] - cmin[0] - bs) / st) + 1)
+    grid_y = int(np.ceil(float(cmax[1] - cmin[1] - bs) / st) + 1)
+    windows, centres = [], []
+    for iy in range(grid_y):
+        for ix in range(grid_x):
+            e_x = min(cmin[0] + ix * st + bs, cmax[0])
+            s_x = e_x - bs
+            e_y = min(cmin[1] + iy * st + bs, cmax[1])
+            s_y = e_y - bs
+            windows.append((s_x - pad, e_x + pad, s_y - pad, e_y + pad))
+            centres.append((s_x + bs / 2.0, s_y + bs / 2.0))
+    return (np.array(windows, dtype=np.float64).reshape(-1, 4), np.array(centres, dtype=np.float64).reshape(-1, 2),
+            grid_x, grid_y)
 
 
 class ScannetDatasetWholeScene:
@@ -101,6 +162,104 @@ class ScannetDatasetWholeScene:
         sample_weight = np.hstack(weight_parts).astype(np.float64).reshape((-1, bp))
         index_room = np.hstack(index_parts).reshape((-1, bp))
         return data_room, label_room, sample_weight, index_room
+
+    def _device_scene(self, index, dev):
+        """The scene's float64 [n, 6] array, its int32 labels and the float32 class weights on `dev`: uploaded once and kept
+        until another scene (or device) is asked for."""
+        cache = getattr(self, "_dev_cache", None)
+        if cache is not None and cache[0] == (index, dev):
+            return cache[1:]
+        self._dev_cache = None
+        points = self.scene_points_list[index]
+        if points.dtype != np.float64:
+            raise ValueError('device_item: the scene is %s, the device slicer computes in float64 only (the host path computes '
+                             'in the array\'s own dtype); use slicer="host"' % points.dtype)
+        lab = self.semantic_labels_list[index].astype(np.int32)
+        if lab.size and (int(lab.min()) < 0 or int(lab.max()) >= NUM_CLASSES):
+            raise IndexError("device_item: a label of the scene lies outside [0, %d)" % NUM_CLASSES)
+        scene = torch.from_numpy(np.ascontiguousarray(points[:, :6])).to(dev)
+        labels = torch.from_numpy(lab).to(dev)
+        weights = torch.from_numpy(np.asarray(self.labelweights, dtype=np.float32)).to(dev)
+        self._dev_cache = ((index, dev), scene, labels, weights)
+        return scene, labels, weights
+
+    def device_item(self, index, device=None, xyz=None):
+        """__getitem__(index) cut on the device: device tensors (data float32 [nb, bp, 9], label int32
+        [nb, bp], smpw float32 [nb, bp], index int32 [nb, bp]), bit for bit __getitem__'s four arrays after the casts the
+        harness applies to them (float32, int32, float32, int32) under the same np.random state, and np.random stands
+        afterwards where __getitem__ leaves it: the device counts and lists every cell's members, ONE read-back brings the
+        counts, slice_plan draws from them what the reference draws, the device gathers.  Everything else is enqueued on the
+        current stream.
+
+        xyz: float64 [n, 3] (numpy or a device tensor) in place of the scene's coordinates - a moved scene, such as
+        evaluate_whole_scene_consistent's adv_xyz: corners, grid and windows are those __getitem__ would use on a scene with
+        these coordinates (a device tensor costs one more small read-back, for its corners).
+
+        Refusals: a scene that is not float64 (ValueError; slicer="host" computes in the array's own dtype); a grid of more
+        than 1024 cells (ValueError; their windows sit in LDS); a label outside [0, 13): IndexError - HERE THE TWO PATHS
+        DIFFER: the host path indexes the class weights with the label, so it wraps a negative one."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.PsgError("device_item slices on the MI355X device (got %s); __getitem__ is the host path" % dev)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        scene, labels, weights = self._device_scene(index, dev)
+        n = scene.shape[0]
+        with torch.cuda.device(dev):
+            if xyz is None:
+                points = self.scene_points_list[index]
+                coords, stride = scene, 6
+                cmin, cmax = np.amin(points, axis=0)[:3], np.amax(points, axis=0)[:3]
+            else:
+                on_host = not isinstance(xyz, torch.Tensor)
+                if on_host:
+                    xyz = torch.from_numpy(np.ascontiguousarray(xyz))
+                if xyz.dtype != torch.float64 or tuple(xyz.shape) != (n, 3):
+                    raise ValueError("device_item: xyz must be float64 [%d, 3] (got %s %s)" % (n, xyz.dtype, tuple(xyz.shape)))
+                coords, stride = xyz.to(dev).contiguous(), 3
+                if on_host:
+                    cmin, cmax = np.amin(xyz.numpy(), axis=0), np.amax(xyz.numpy(), axis=0)
+                else:                                   # one small read-back for the corners (min / max are exact anywhere)
+                    cmin, cmax = torch.stack([coords.amin(dim=0), coords.amax(dim=0)]).cpu().numpy()
+            bp = self.block_points
+            windows, centres, grid_x, grid_y = slice_cells(cmin, cmax, self.block_size, self.stride, self.padding)
+            n_cells = windows.shape[0]
+            if n_cells > _lib.SLICE_MAX_CELLS:
+                raise ValueError('device_item: the grid has %d x %d = %d cells, the device slicer holds %d (their windows sit in '
+                                 'LDS); use slicer="host"' % (grid_x, grid_y, n_cells, _lib.SLICE_MAX_CELLS))
+            if n_cells < 1:
+                raise ValueError("device_item: the scene's grid has no cell (need at least one array to concatenate)")
+            st = runtime.stream()
+            tile_items = n_cells * ((n + _lib.SLICE_TILE - 1) // _lib.SLICE_TILE) + 1
+            win_dev = torch.from_numpy(windows).to(dev)
+            tile_off = torch.empty(tile_items, dtype=torch.int32, device=dev)
+            counts_dev = torch.empty(n_cells, dtype=torch.int32, device=dev)
+            cell_off = torch.empty(n_cells + 1, dtype=torch.int32, device=dev)
+            _lib.call("psg_slice_count", runtime.ptr(coords), stride, n, runtime.ptr(win_dev), n_cells, runtime.ptr(tile_off),
+                      tile_items, runtime.ptr(counts_dev), runtime.ptr(cell_off), st)
+            counts = counts_dev.cpu().numpy()                      # the one read-back: the host cannot draw the plan without it
+            blocks = -(-counts.astype(np.int64) // bp)
+            total = int(counts.astype(np.int64).sum())
+            if total > 0x7FFFFFFF or int(blocks.sum()) * bp > 0x7FFFFFFF // 9:
+                raise ValueError('device_item: %d cell members in %d blocks exceed the device slicer\'s 32-bit offsets; use '
+                                 'slicer="host"' % (total, int(blocks.sum())))
+            src_pos, _, nb = slice_plan(counts, bp)
+            block_cell = np.repeat(np.arange(n_cells, dtype=np.int32), blocks)
+            inside = torch.empty(total, dtype=torch.int32, device=dev)
+            _lib.call("psg_slice_members", runtime.ptr(coords), stride, n, runtime.ptr(win_dev), n_cells, runtime.ptr(tile_off),
+                      tile_items, runtime.ptr(inside), total, st)
+            src_dev = upload(torch.from_numpy(src_pos), dev, pin=True)
+            cell_dev = upload(torch.from_numpy(block_cell), dev, pin=True)
+            cen_dev = upload(torch.from_numpy(centres), dev, pin=True)
+            data = torch.empty(nb, bp, 9, dtype=torch.float32, device=dev)
+            label = torch.empty(nb, bp, dtype=torch.int32, device=dev)
+            smpw = torch.empty(nb, bp, dtype=torch.float32, device=dev)
+            idx = torch.empty(nb, bp, dtype=torch.int32, device=dev)
+            _lib.call("psg_slice_gather", runtime.ptr(coords), stride, runtime.ptr(scene[:, 3:]), 6, runtime.ptr(labels), n,
+                      runtime.ptr(inside), total, runtime.ptr(cell_off), runtime.ptr(cell_dev), runtime.ptr(cen_dev), n_cells,
+                      runtime.ptr(src_dev), nb, bp, float(cmax[0]), float(cmax[1]), float(cmax[2]), runtime.ptr(weights),
+                      runtime.ptr(data), runtime.ptr(label), runtime.ptr(smpw), runtime.ptr(idx), st)
+        return data, label, smpw, idx
 
 
 def _cuda(t, name, dtype):
@@ -183,7 +342,7 @@ def _replica(classifier):
 
 
 def evaluate_whole_scene(classifier, dataset, make_attack, batch_size=8, num_votes=1, log_path=None, rank=0, world=1,
-                         log=print, targeted=None, streams=3):
+                         log=print, targeted=None, streams=3, slicer="host"):
     """The reference's evaluation loop (NB_nontarget_test_semseg.py:126-291) with the per-point work on the GPU.
 
     classifier: an eval-mode `get_model` on the GPU; make_attack(classifier) -> a torchattacks attack object (e.g.
@@ -208,7 +367,14 @@ def evaluate_whole_scene(classifier, dataset, make_attack, batch_size=8, num_vot
     numpy's generator: the slicing calls still happen one after the other in the reference's order (scene by scene, vote by
     vote), so `np.random` is consumed exactly as before; a caller's dataset class is sliced in line.  While the helper
     thread runs, `make_attack` / the attack must not draw from numpy's GLOBAL generator (the attacks of this package use torch's
-    generators only); replicas that cannot be built (another constructor signature) fall back to one stream with a log line."""
+    generators only); replicas that cannot be built (another constructor signature) fall back to one stream with a log line.
+
+    slicer="device" (DESIGN.md section 5zb): `dataset.device_item(si, dev)` in the place and order of `dataset[si]` - the same
+    blocks bit for bit and the same np.random draws, so the generator order above holds and the results are those of
+    slicer="host"; no helper thread (nothing is left to hide), the batches take slices of the device tensors instead of
+    uploading numpy slices, and the targeted protocol's masks and counts come from one read-back of the scene's block labels
+    per slicing.  A dataset class without device_item is a TypeError."""
+    _check_device_slicer(slicer, dataset)
     dev = next(classifier.parameters()).device
     n_streams = max(1, int(streams))
     nets = [classifier]
@@ -230,7 +396,7 @@ def evaluate_whole_scene(classifier, dataset, make_attack, batch_size=8, num_vot
     my_scenes = shard_scenes(list(range(len(dataset))), rank, world)
     fetch_order = [si for si in my_scenes for _ in range(num_votes)]
     fetcher = None
-    if type(dataset) is ScannetDatasetWholeScene and len(fetch_order) > 1:
+    if slicer == "host" and type(dataset) is ScannetDatasetWholeScene and len(fetch_order) > 1:
         from concurrent.futures import ThreadPoolExecutor
         fetcher = ThreadPoolExecutor(max_workers=1)
     n_fetched = [0]
@@ -239,11 +405,13 @@ def evaluate_whole_scene(classifier, dataset, make_attack, batch_size=8, num_vot
     def next_scene_data(si):
         k = n_fetched[0]
         n_fetched[0] += 1
+        if slicer == "device":
+            return _device_scene_data(dataset, si, dev, lanes, targeted is not None)
         if fetcher is None:
-            return dataset[si]
+            return dataset[si] + (None,)
         data = nxt[0].result()
         nxt[0] = fetcher.submit(dataset.__getitem__, fetch_order[k + 1]) if k + 1 < len(fetch_order) else None
-        return data
+        return data + (None,)
 
     try:
       for si in my_scenes:
@@ -259,14 +427,15 @@ def evaluate_whole_scene(classifier, dataset, make_attack, batch_size=8, num_vot
                   ln.wait_stream(torch.cuda.current_stream(dev))
           n_issued = 0
           for _ in range(num_votes):
-              scene_data, scene_label, scene_smpw, scene_point_index = next_scene_data(si)
+              scene_data, scene_label, scene_smpw, scene_point_index, label_host = next_scene_data(si)
               num_blocks = scene_data.shape[0]
               for sbatch in range((num_blocks + batch_size - 1) // batch_size):
                   lo, hi = sbatch * batch_size, min((sbatch + 1) * batch_size, num_blocks)
                   slot = n_issued % n_streams
                   n_issued += 1
                   pending.extend(_scene_batch(nets[slot], attacks[slot], make_attack, targeted, lanes[slot], dev, n_pt, sbatch, lo, hi,
-                                              scene_data, scene_label, scene_smpw, scene_point_index, pool, adv_pool, vote_bad))
+                                              scene_data, scene_label, scene_smpw, scene_point_index, pool, adv_pool, vote_bad,
+                                              label_host))
           for ln in lanes:
               if ln is not None:
                   torch.cuda.current_stream(dev).wait_stream(ln)
@@ -289,18 +458,48 @@ def evaluate_whole_scene(classifier, dataset, make_attack, batch_size=8, num_vot
     return _finish(total, scene_rows, rank, log)
 
 
+def _check_device_slicer(slicer, dataset):
+    if check_slicer(slicer) == "device" and not hasattr(dataset, "device_item"):
+        raise TypeError('slicer="device" needs a dataset with device_item (ScannetDatasetWholeScene); %s has none'
+                        % type(dataset).__name__)
+
+
+def _device_scene_data(dataset, si, dev, lanes, want_host_labels):
+    """One device slicing for evaluate_whole_scene: the four device tensors and - for the targeted protocol - the block labels
+    on the host (one read-back per slicing).  The tensors are produced on the caller's stream and consumed on the lanes: the
+    caller's stream first waits for the lanes (the previous slicing's tensors are released here and their memory may be
+    handed out again at once), the lanes then wait for the slicing."""
+    cur = torch.cuda.current_stream(dev)
+    for ln in lanes:
+        if ln is not None:
+            cur.wait_stream(ln)
+    data, label, smpw, index = dataset.device_item(si, dev)
+    label_host = label.cpu().numpy() if want_host_labels else None
+    for ln in lanes:
+        if ln is not None:
+            ln.wait_stream(cur)
+    return data, label, smpw, index, label_host
+
+
 def _scene_batch(classifier, attack, make_attack, targeted, lane, dev, n_pt, sbatch, lo, hi, scene_data, scene_label, scene_smpw,
-                 scene_point_index, pool, adv_pool, vote_bad):
+                 scene_point_index, pool, adv_pool, vote_bad, label_host=None):
     """One batch of a scene on `lane` (a HIP stream, or None = the caller's): clean forward, attack, adversarial forward,
-    votes, counters, L2 - everything stays on the device; returns the batch's pending log row (or nothing)."""
+    votes, counters, L2 - everything stays on the device; returns the batch's pending log row (or nothing).  The scene's four
+    arrays are the host slicer's numpy arrays, or the device slicer's tensors (label_host: their labels on the host, for the
+    targeted protocol)."""
     import contextlib
     with (torch.cuda.stream(lane) if lane is not None else contextlib.nullcontext()):
-        # (numpy does the float64 -> float32 conversion: a torch CPU op of this size wakes the whole OpenMP pool)
-        torch_data = upload(torch.from_numpy(scene_data[lo:hi].astype(np.float32)), dev, pin=True).transpose(2, 1).contiguous()
-        gt_np = scene_label[lo:hi]
-        gt = upload(torch.from_numpy(gt_np.astype(np.int32)), dev, pin=True)
-        idx = upload(torch.from_numpy(scene_point_index[lo:hi].astype(np.int32)), dev, pin=True)
-        smpw = upload(torch.from_numpy(scene_smpw[lo:hi].astype(np.float32)), dev, pin=True)
+        if isinstance(scene_data, torch.Tensor):
+            torch_data = scene_data[lo:hi].transpose(2, 1).contiguous()
+            gt, idx, smpw = scene_label[lo:hi], scene_point_index[lo:hi], scene_smpw[lo:hi]
+            gt_np = label_host[lo:hi] if label_host is not None else gt
+        else:
+            # (numpy does the float64 -> float32 conversion: a torch CPU op of this size wakes the whole OpenMP pool)
+            torch_data = upload(torch.from_numpy(scene_data[lo:hi].astype(np.float32)), dev, pin=True).transpose(2, 1).contiguous()
+            gt_np = scene_label[lo:hi]
+            gt = upload(torch.from_numpy(gt_np.astype(np.int32)), dev, pin=True)
+            idx = upload(torch.from_numpy(scene_point_index[lo:hi].astype(np.int32)), dev, pin=True)
+            smpw = upload(torch.from_numpy(scene_smpw[lo:hi].astype(np.float32)), dev, pin=True)
         seg_pred, _ = classifier(torch_data)
         seg_pred = seg_pred.detach().contiguous()
         count, mask_np = 0, None
@@ -334,7 +533,7 @@ def _scene_batch(classifier, attack, make_attack, targeted, lane, dev, n_pt, sba
 
 
 def evaluate_whole_scene_consistent(classifier, dataset, make_scene_attack, batch_size=8, log_path=None, rank=0, world=1,
-                                    log=print, targeted=None, on_scene=None, on_scene_field=None):
+                                    log=print, targeted=None, on_scene=None, on_scene_field=None, slicer="host"):
     """evaluate_whole_scene with ONE adversarial scene per room: the attack moves one colour per
     physical scene point - attacks.scene.SceneNBAttack - instead of one per block slot, so the adversarial blocks that are
     voted on are slices of a point cloud that exists (and can be saved and re-sliced).
@@ -358,8 +557,11 @@ def evaluate_whole_scene_consistent(classifier, dataset, make_scene_attack, batc
     [0, 1] (the clean ones for a scene that was not attacked) - the reference's .xyzrgb dump.  One stream, no replicas.
     on_scene_field(name, adv_rgb01, adv_xyz): the same call with the moved geometry beside the colours, for a scene attack
     built with field="coord" | "both" (DESIGN.md section 5v): adv_xyz = the scene's xyz (float64, metres, [n_scene, 3]) + the
-    attack's displacement delta; the clean arrays for a scene that was not attacked or an attack that moves colours only."""
+    attack's displacement delta; the clean arrays for a scene that was not attacked or an attack that moves colours only.
+    slicer="device" (DESIGN.md section 5zb): step 1 is dataset.device_item(si, dev) - the same blocks and the same np.random
+    draws, on the device; the results are those of slicer="host".  A dataset class without device_item is a TypeError."""
     from .attacks.scene import check_scene_model
+    _check_device_slicer(slicer, dataset)
     check_scene_model(classifier)
     dev = next(classifier.parameters()).device
     if dev.type != "cuda":
@@ -384,12 +586,16 @@ def evaluate_whole_scene_consistent(classifier, dataset, make_scene_attack, batc
             pool = torch.zeros(n_scene, NUM_CLASSES, dtype=torch.int32, device=dev)
             adv_pool = torch.zeros_like(pool)
             vote_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-            scene_data, scene_label, scene_smpw, scene_point_index = dataset[si]
-            num_blocks = scene_data.shape[0]
-            x_all = upload(torch.from_numpy(scene_data.astype(np.float32)), dev, pin=True)            # [nb, bp, 9] point-major
-            gt_all = upload(torch.from_numpy(scene_label.astype(np.int32)), dev, pin=True)
-            idx_all = upload(torch.from_numpy(scene_point_index.astype(np.int32)), dev, pin=True)
-            smpw_all = upload(torch.from_numpy(scene_smpw.astype(np.float32)), dev, pin=True)
+            if slicer == "device":
+                x_all, gt_all, smpw_all, idx_all = dataset.device_item(si, dev)
+                scene_label = gt_all.cpu().numpy() if targeted is not None else None      # (the targeted rows' counts)
+            else:
+                scene_data, scene_label, scene_smpw, scene_point_index = dataset[si]
+                x_all = upload(torch.from_numpy(scene_data.astype(np.float32)), dev, pin=True)            # [nb, bp, 9] point-major
+                gt_all = upload(torch.from_numpy(scene_label.astype(np.int32)), dev, pin=True)
+                idx_all = upload(torch.from_numpy(scene_point_index.astype(np.int32)), dev, pin=True)
+                smpw_all = upload(torch.from_numpy(scene_smpw.astype(np.float32)), dev, pin=True)
+            num_blocks = x_all.shape[0]
             batches = [(lo, min(lo + batch_size, num_blocks)) for lo in range(0, num_blocks, batch_size)]
             attacked = targeted is None or bool((labels_np == targeted["origin"]).any())
             clean_stats = []

@@ -37,6 +37,16 @@ SceneNUAttack(field=...), Adam on one displacement per scene point -, `scene_nu`
 `per_block_nu_field` - NU_attack(field=...).forward_rooms over the same blocks in groups of batch_size.  The ratios are
 scene_nu_field over each of the other two; the kernel-trace share (a `--only scene_nu_field --runs 1` profiler run) lists
 scene_nu_field_step_kernel on its own.  No speed bar.
+
+--slicer host | device picks the block slicer of every evaluation call above: the numpy loop of
+ScannetDatasetWholeScene.__getitem__ (default) or device_item; --slicer both (--attack nb) runs every variant with either,
+`variant@host` and `variant@device` alternated in the same rounds, and reports device over host per variant and whether the
+two ranges overlap.  --slicing-only times the slicing alone instead: one slicing of
+the room per variant - `host` = ds[0] plus the float32 / int32 casts and the uploads the loops make of it, `device` =
+ds.device_item(0) -, alternated in one process after a warm-up of each, np.random.seed(3) before every call, each call from the
+seed to a device synchronise; median / min / max in ms, whether the two ranges overlap, and the device slicing's shares: the
+host plan (harness.slice_plan on the room's counts, timed alone), the read-back of the counts (from the launch of the count
+pass to the counts on the host) and the three passes' kernels (HIP events, in a run of their own).
 """
 import argparse
 import json
@@ -196,6 +206,127 @@ def main_nu(a, ap):
             fh.write(line + "\n")
 
 
+def main_slicing(a):
+    """--slicing-only: one slicing of the room per variant, host against device (see the module docstring)"""
+    import torch
+    from pointsecguard_amd import harness
+    from pointsecguard_amd.models.pointnet2_sem_seg import upload
+    assert torch.cuda.is_available(), "scene_time.py measures on the MI355X; there is nothing to time without it"
+    dev = torch.device("cuda")
+    room = synthetic_room(a.points, a.size[0], a.size[1])
+    ds = harness.ScannetDatasetWholeScene(None, block_points=a.block_points, scenes={"Area_5_room.npy": room})
+    shape = {}
+
+    def call(variant):
+        np.random.seed(3)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if variant == "device":
+            out = ds.device_item(0)
+        else:                                       # what evaluate_whole_scene_consistent does with the host slicer's arrays
+            data, label, smpw, index = ds[0]
+            out = (upload(torch.from_numpy(data.astype(np.float32)), dev, pin=True),
+                   upload(torch.from_numpy(label.astype(np.int32)), dev, pin=True),
+                   upload(torch.from_numpy(smpw.astype(np.float32)), dev, pin=True),
+                   upload(torch.from_numpy(index.astype(np.int32)), dev, pin=True))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        shape[variant] = tuple(out[0].shape)
+        return dt * 1e3
+
+    variants = ("host", "device")
+    for v in variants:
+        call(v)
+    ms = {v: [] for v in variants}
+    for _ in range(a.runs):
+        for v in variants:
+            ms[v].append(call(v))
+    assert shape["host"] == shape["device"]
+    stat = {v: dict(median=statistics.median(r), min=min(r), max=max(r)) for v, r in ms.items()}
+    overlap = not (stat["device"]["max"] < stat["host"]["min"] or stat["host"]["max"] < stat["device"]["min"])
+    out = dict(tool="scene_time", leg="slicing_only", device=torch.cuda.get_device_name(0), n_points=a.points, size=list(a.size),
+               block_points=a.block_points, n_blocks=shape["device"][0], runs=a.runs, ms=stat, ranges_overlap=overlap,
+               host_over_device=stat["host"]["median"] / stat["device"]["median"], device_shares=slicing_shares(ds, a.runs))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def slicing_shares(ds, runs):
+    """where a device slicing's time goes, each part timed in a run of its own: the host plan, the count pass up to the counts on
+    the host, and the kernels of the three passes by HIP events (medians, ms)"""
+    import torch
+    from pointsecguard_amd import _lib, harness, runtime
+    dev = torch.device("cuda")
+    scene, labels, weights = ds._device_scene(0, dev)
+    points = ds.scene_points_list[0]
+    n, bp = scene.shape[0], ds.block_points
+    cmin, cmax = np.amin(points, axis=0)[:3], np.amax(points, axis=0)[:3]
+    windows, centres, _, _ = harness.slice_cells(cmin, cmax, ds.block_size, ds.stride, ds.padding)
+    n_cells = windows.shape[0]
+    items = n_cells * (-(-n // _lib.SLICE_TILE)) + 1
+    win = torch.from_numpy(windows).to(dev)
+    cen = torch.from_numpy(centres).to(dev)
+    tile_off = torch.empty(items, dtype=torch.int32, device=dev)
+    counts_dev = torch.empty(n_cells, dtype=torch.int32, device=dev)
+    cell_off = torch.empty(n_cells + 1, dtype=torch.int32, device=dev)
+    rgb = runtime.ptr(scene[:, 3:])
+
+    def count():
+        _lib.call("psg_slice_count", runtime.ptr(scene), 6, n, runtime.ptr(win), n_cells, runtime.ptr(tile_off), items,
+                  runtime.ptr(counts_dev), runtime.ptr(cell_off), runtime.stream())
+
+    count()
+    counts = counts_dev.cpu().numpy()
+    total = int(counts.sum())
+    np.random.seed(3)
+    src_pos, _, nb = harness.slice_plan(counts, bp)
+    inside = torch.empty(total, dtype=torch.int32, device=dev)
+    src = torch.from_numpy(src_pos).to(dev)
+    block_cell = torch.from_numpy(np.repeat(np.arange(n_cells, dtype=np.int32), -(-counts.astype(np.int64) // bp))).to(dev)
+    data = torch.empty(nb, bp, 9, dtype=torch.float32, device=dev)
+    label = torch.empty(nb, bp, dtype=torch.int32, device=dev)
+    smpw = torch.empty(nb, bp, dtype=torch.float32, device=dev)
+    index = torch.empty(nb, bp, dtype=torch.int32, device=dev)
+
+    def members():
+        _lib.call("psg_slice_members", runtime.ptr(scene), 6, n, runtime.ptr(win), n_cells, runtime.ptr(tile_off), items,
+                  runtime.ptr(inside), total, runtime.stream())
+
+    def gather():
+        _lib.call("psg_slice_gather", runtime.ptr(scene), 6, rgb, 6, runtime.ptr(labels), n, runtime.ptr(inside), total,
+                  runtime.ptr(cell_off), runtime.ptr(block_cell), runtime.ptr(cen), n_cells, runtime.ptr(src), nb, bp, float(cmax[0]),
+                  float(cmax[1]), float(cmax[2]), runtime.ptr(weights), runtime.ptr(data), runtime.ptr(label), runtime.ptr(smpw),
+                  runtime.ptr(index), runtime.stream())
+
+    def events(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    plan_ms, readback_ms, kern = [], [], dict(count=[], members=[], gather=[])
+    for _ in range(max(runs, 3)):
+        np.random.seed(3)
+        t0 = time.perf_counter()
+        harness.slice_plan(counts, bp)
+        plan_ms.append((time.perf_counter() - t0) * 1e3)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        count()
+        counts_dev.cpu()
+        readback_ms.append((time.perf_counter() - t0) * 1e3)
+        for name, fn in (("count", count), ("members", members), ("gather", gather)):
+            kern[name].append(events(fn))
+    med = statistics.median
+    return dict(n_cells=n_cells, members=total, host_plan_ms=med(plan_ms), count_and_readback_ms=med(readback_ms),
+                kernels_ms={k: med(v) for k, v in kern.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--attack", choices=("nb", "nu"), default="nb")
@@ -210,8 +341,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-trace", default=None)
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--slicer", choices=("host", "device", "both"), default="host")
+    ap.add_argument("--slicing-only", action="store_true")
     a = ap.parse_args()
+    if a.slicing_only:
+        return main_slicing(a)
     if a.attack == "nu":
+        if a.slicer != "host":
+            ap.error("--attack nu slices the room once, outside the timed calls: --slicer does not apply")
         return main_nu(a, ap)
     if a.trace_only:
         print(json.dumps(dict(kernel_trace=scene_kernel_share(a.kernel_trace))))
@@ -233,25 +370,27 @@ def main():
     quiet = lambda *_: None
 
     def call(variant):
+        variant, _, slicer = variant.partition("@")
+        slicer = slicer or a.slicer
         np.random.seed(3)
         torch.manual_seed(3)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if variant == "consistent":
             harness.evaluate_whole_scene_consistent(net, ds, lambda m: SceneNBAttack(m, eps, alpha, a.iters),
-                                                    batch_size=a.batch_size, log=quiet)
+                                                    batch_size=a.batch_size, log=quiet, slicer=slicer)
         elif variant == "consistent_field":
             harness.evaluate_whole_scene_consistent(net, ds, lambda m: SceneNBAttack(m, eps, alpha, a.iters, field=a.field),
-                                                    batch_size=a.batch_size, log=quiet)
+                                                    batch_size=a.batch_size, log=quiet, slicer=slicer)
         elif variant.startswith("per_block_field"):
             kw = {"streams": 1} if variant == "per_block_field_streams1" else {}
             harness.evaluate_whole_scene(net, ds, lambda m: torchattacks.NB_attack(m, eps=eps, alpha=alpha, iters=a.iters,
                                                                                      field=a.field),
-                                         batch_size=a.batch_size, log=quiet, **kw)
+                                         batch_size=a.batch_size, log=quiet, slicer=slicer, **kw)
         else:
             kw = {"streams": 1} if variant == "per_block_streams1" else {}
             harness.evaluate_whole_scene(net, ds, lambda m: torchattacks.NB_attack(m, eps=eps, alpha=alpha, iters=a.iters),
-                                         batch_size=a.batch_size, log=quiet, **kw)
+                                         batch_size=a.batch_size, log=quiet, slicer=slicer, **kw)
         torch.cuda.synchronize()
         return n_blocks / (time.perf_counter() - t0)
 
@@ -259,6 +398,8 @@ def main():
     if a.only and a.only not in all_variants:
         ap.error("--only %s does not exist under --field %s" % (a.only, a.field))
     variants = [a.only] if a.only else list(all_variants)
+    if a.slicer == "both":
+        variants = ["%s@%s" % (v, sl) for v in variants for sl in ("host", "device")]
     for v in variants:                          # warm-up: workspaces, packed weights, replicas' first launches
         call(v)
     rate = {v: [] for v in variants}
@@ -268,9 +409,15 @@ def main():
     med = {v: statistics.median(r) for v, r in rate.items()}
     out = dict(tool="scene_time", device=torch.cuda.get_device_name(0), n_points=a.points, size=list(a.size), block_points=a.block_points,
                n_blocks=n_blocks, batch_size=a.batch_size, eps=eps, alpha=alpha, iters=a.iters, runs=a.runs, field=a.field,
+               slicer=a.slicer,
                occurrences=dict(mean=float(counts.mean()), max=int(counts.max()), multi_share=float((counts > 1).mean())),
                blocks_per_s={v: dict(median=med[v], min=min(r), max=max(r), spread=(max(r) - min(r)) / med[v]) for v, r in rate.items()})
-    if not a.only and a.field != "color":
+    if a.slicer == "both":
+        out["device_over_host"] = {
+            v[:-5]: dict(ratio=med[v[:-5] + "@device"] / med[v],
+                         ranges_overlap=not (max(rate[v]) < min(rate[v[:-5] + "@device"]) or max(rate[v[:-5] + "@device"]) < min(rate[v])))
+            for v in variants if v.endswith("@host")}
+    elif not a.only and a.field != "color":
         out["consistent_field_over"] = {v: med["consistent_field"] / med[v] for v in variants if v != "consistent_field"}
     elif not a.only:
         out["consistent_over_per_block"] = dict(streams1=med["consistent"] / med["per_block_streams1"],
