@@ -757,6 +757,36 @@ int psg_gcn_set_graphs(psg_gcn_ws *ws, const int32_t *nbr, psg_stream stream);
 const int32_t *psg_gcn_edge_ptr(const psg_gcn_ws *ws, int block);
 const float *psg_gcn_feats_ptr(const psg_gcn_ws *ws);
 
+/* Read-only tap into the workspace (tests): the device pointer of a named buffer with its row and column counts.  NULL
+ * with the error string set - and the counts left untouched - for a null workspace, an unknown `what`, a `block` outside
+ * [0, n_blocks), a conv = mr code on an edge workspace, or a kept code while psg_gcn_debug_keep is off.  Launches nothing,
+ * allocates nothing, does not synchronise.  float32 unless noted; B rooms of N points, R = B N rows, F = 64 n_blocks, C_e
+ * the input width of block e (9, 64, or dense: 64 e); `block` selects e where [e] is written and is ignored elsewhere.
+ *   forward state, valid from a forward call until the next forward call:
+ *      0 xyz [R][3]   1 feats [R][F]   2 nbr[e] [R][16] (int32, room-local)   3 arg[e] [R][64] (uint8: winning slot, bit 0x80 =
+ *      the winner's pre-activation was positive; conv = edge)   4 arg_mr[e] [R][C_e] (uint8, conv = mr)
+ *      5 mask_mr[e] [R][2] (uint32 ReLU bits, conv = mr)   6 sq [R][1] and 7 xp [R][64] (the norms and the MFMA-operand copy of
+ *      the LAST 64-wide kNN source whose producer or prep launch wrote them)   8 fused [R][1024]   9 mask_f [R][32] (uint32)
+ *      10 fmax [B][1024]   11 farg [B][1024] (int32, room-local)   12 gb1 [B][512]   13 h1 [R][512]   14 mask1 [R][16] (uint32)
+ *      15 h2 [R][256]   16 mask2 [R][8] (uint32)   17 logits [R][13]
+ *      ReLU bit words: cols = words per row, bit c%32 of word c/32 = (pre-activation > 0)
+ *   gradient state, valid from a backward call until the next backward call:
+ *      30 g2 [R][256]   31 g1 [R][512]   32 g1part [B ceil(N/64)][512]   33 g1sum [B][512]   34 gfvec [B][1024]
+ *      35 dfeats [R][F] (res / edge: prediction head + fusion transpose; other configurations: as the last block left it)
+ *      36 gcur [R][64] (res / edge: G_0; conv = mr: block 0's gated gradient)
+ *   kept copies (psg_gcn_debug_keep on), made on the launch stream as the loops run:
+ *      50 [P | Q] of block e [R][128] (conv = mr: the gathered cat [R][2 C_e])   51 dfeats as the prediction head left it [R][F]
+ *      52 dfeats after the fusion transpose [R][F]   53 [dP | dQ] of block e [R][128] (mr: dcat [R][2 C_e])
+ *      54 the gated output gradient of block e [R][64] (conv = mr)   55 the state after block e's backward: gcur [R][64]
+ *      (res / edge) or the whole dfeats [R][F]   56 dx0 [R][9] as block 0 wrote it */
+const void *psg_gcn_debug_ptr(const psg_gcn_ws *ws, int what, int block, int *rows_out, int *cols_out);
+/* on != 0: the workspace gets a second arena (allocated at the first call, freed by on = 0 and by psg_gcn_ws_destroy) and
+ * psg_gcn_forward / psg_gcn_backward add device-to-device copies of the per-block buffers they overwrite (codes 50-56
+ * above); no kernel and no result changes.  Off (the default), both issue exactly the launches they issue without this
+ * entry point.  While on, psg_gcn_nb_attack, psg_gcn_nb_attack_field, psg_gcn_nu_window and psg_gcn_nu_field_window
+ * return PSG_ERR_STATE: they replay captured forwards, which would not make the copies. */
+int psg_gcn_debug_keep(psg_gcn_ws *ws, int on);
+
 /* A WINDOW of consecutive optimiser steps of the ResGCN NU_attack / tar_NU_attack (colper.py:62-95, tcolper.py:85-132) for
  * G one-room attacks in lockstep (rooms form only: the workspace is for G rooms of N points), enqueued by ONE call.  Per
  * step: psg_nu_tanh_color_rooms, psg_gcn_forward, psg_gcn_f_loss_grad_rooms (scale c_f), psg_gcn_backward,

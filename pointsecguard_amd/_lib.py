@@ -128,6 +128,8 @@ SIGNATURES = {
     "psg_gcn_set_graphs": (ci, [vp, vp, vp]),
     "psg_gcn_edge_ptr": (vp, [vp, ci]),
     "psg_gcn_feats_ptr": (vp, [vp]),
+    "psg_gcn_debug_ptr": (vp, [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "psg_gcn_debug_keep": (ci, [vp, ci]),
     "psg_gcn_nu_window": (ci, [vp, vp, vp]),
     "psg_gcn_nb_attack_field": (ci, [vp, vp, vp, vp, ci, cf, cf, cf, cf, ci, vp, vp]),
     "psg_gcn_nu_field_window": (ci, [vp, vp, vp]),

@@ -87,9 +87,19 @@ struct psg_gcn_ws {
     // the colour loop's graph and the field loop's, a holder each: one survives a call of the other
     NbGraph nb, nbf;
     psg::EvLog prof;           // psg_gcn_prof_enable
+    // psg_gcn_debug_keep: a second arena of per-block copies of what the loops overwrite (null = off, the one pointer the host
+    // path tests per block).  Strides per block: pq_w floats per row for k_pq / k_dpq, fdim for k_state.
+    void *keep = nullptr;
+    float *k_pq, *k_dpq;       // [n_blocks][B*N][pq_w]: every block's [P | Q] (mr: cat) and [dP | dQ] (mr: dcat)
+    float *k_gz;               // [n_blocks][B*N][64]: conv = mr, every block's mr_dz output
+    float *k_state;            // [n_blocks] slots of B*N*fdim floats: after block e, gcur packed [B*N][64] (res / edge) or dfeats [B*N][fdim]
+    float *k_dfh, *k_dff;      // [B*N][fdim]: dfeats as the prediction head left it, and after the fusion transpose
+    float *k_dx0;              // [B*N][9]
 };
 
 const psg_gcn::GcnSwitches &gcn_switches();   // read at the first call
 inline bool gcn_same_cfg(const psg_gcn_model *m, const psg_gcn_ws *ws) { return m->cfg == ws->cfg; }
 // The NB prologue's copies out of ws->x0 (point-major rows of 9): colours -> ws->ori and, `xyz`, coordinates -> ws->ori_xyz
 int gcn_extract_clean(psg_gcn_ws *ws, bool xyz, hipStream_t st);
+// the attack entry points capture and replay forwards: refused while psg_gcn_debug_keep is on (PSG_ERR_STATE), PSG_OK otherwise
+int gcn_keep_refuses(const psg_gcn_ws *ws, const char *who);

@@ -308,6 +308,7 @@ extern "C" int psg_gcn_ws_destroy(psg_gcn_ws *ws)
     ws->nb.slot.destroy();
     ws->nbf.slot.destroy();
     if (ws->arena) (void)hipFree(ws->arena);
+    if (ws->keep) (void)hipFree(ws->keep);
     ws->prof.destroy();
     delete ws;
     return PSG_OK;
@@ -532,6 +533,11 @@ extern "C" int psg_gcn_forward(psg_gcn_model *m, psg_gcn_ws *ws, const float *x0
             if (resid) { a.accumulate = 2; a.addend = resid; a.ld_add = F; }
             if ((rc = launch_gemm<2, 2, EPI_RELU_AFFINE, false>(a, st))) return rc;
         }
+        if (ws->keep) {   // psg_gcn_debug_keep: this block's [P | Q] (mr: the gathered cat) before the next block overwrites it
+            const size_t w = mr ? 2 * (size_t)P.C : 2 * GC;
+            PSG_CHECK_HIP(hipMemcpyAsync(ws->k_pq + (size_t)e * R * ws->pq_w, mr ? ws->pq : ((e & 1) ? ws->pq2 : ws->pq), R * w * 4,
+                                         hipMemcpyDeviceToDevice, st));
+        }
     }
     EvScope prof_head(&ws->prof, GT_HEAD, 2.0 * R * ((double)F * 1024 + (double)F * 512 + 512.0 * 256 + 256.0 * NCLS), st);
     // fusion: Conv(F -> 1024) + ReLU + BN, global max over the room
@@ -609,8 +615,106 @@ static int backward_alt(psg_gcn_model *m, psg_gcn_ws *ws, float *dx0_out, hipStr
                                ws->arg_mr + P.arg_off * R, tgt, ld_t, N, tot);
             PSG_LAUNCH_CHECK();
         }
+        if (ws->keep) {   // psg_gcn_debug_keep: [dP | dQ] (mr: gz and dcat), then the whole dfeats, then dx0 after block 0
+            if (mr) PSG_CHECK_HIP(hipMemcpyAsync(ws->k_gz + (size_t)e * R * GC, ws->gcur, R * GC * 4, hipMemcpyDeviceToDevice, st));
+            PSG_CHECK_HIP(hipMemcpyAsync(ws->k_dpq + (size_t)e * R * ws->pq_w, ws->dpq, R * (mr ? 2 * (size_t)P.C : 2 * GC) * 4,
+                                         hipMemcpyDeviceToDevice, st));
+            PSG_CHECK_HIP(hipMemcpyAsync(ws->k_state + (size_t)e * R * F, ws->dfeats, R * F * 4, hipMemcpyDeviceToDevice, st));
+            if (e == 0) PSG_CHECK_HIP(hipMemcpyAsync(ws->k_dx0, dx0_out, R * 9 * 4, hipMemcpyDeviceToDevice, st));
+        }
     }
     return PSG_OK;
+}
+
+// ---- the test taps: psg_gcn_debug_ptr (read-only: pointer, rows, columns of a named buffer; the codes are listed in
+// include/psg.h) and psg_gcn_debug_keep (per-block copies of what the loops overwrite, in an arena of their own)
+extern "C" const void *psg_gcn_debug_ptr(const psg_gcn_ws *ws, int what, int block, int *rows_out, int *cols_out)
+{
+    if (!ws) { set_error("psg_gcn_debug_ptr: null workspace"); return nullptr; }
+    if (block < 0 || block >= ws->cfg.n_blocks) {
+        set_error("psg_gcn_debug_ptr: block %d out of range [0, %d)", block, ws->cfg.n_blocks);
+        return nullptr;
+    }
+    const int B = ws->B, R = ws->B * ws->N, F = ws->fdim, e = block;
+    const bool mr = ws->cfg.conv == PSG_GCN_CONV_MR, alt = mr || ws->cfg.block != PSG_GCN_BLOCK_RES;
+    const GcnBlock P = gcn_block(ws->cfg, e);
+    const int wpq = mr ? 2 * P.C : 2 * GC;
+    const void *p = nullptr;
+    int r = 0, c = 0;
+    bool known = true, need_mr = false, need_keep = false;
+    auto put = [&](const void *ptr, int rows, int cols) { p = ptr; r = rows; c = cols; };
+    switch (what) {
+    case 0: put(ws->xyz, R, 3); break;
+    case 1: put(ws->feats, R, F); break;
+    case 2: put(ws->nbr + (size_t)e * R * KNB, R, KNB); break;
+    case 3: put(ws->arg + (size_t)e * R * GC, R, GC); break;
+    case 4: need_mr = true; if (mr) put(ws->arg_mr + P.arg_off * R, R, P.C); break;
+    case 5: need_mr = true; if (mr) put(ws->mask_mr + (size_t)e * R * 2, R, 2); break;
+    case 6: put(ws->sq, R, 1); break;
+    case 7: put(ws->xp, R, GC); break;
+    case 8: put(ws->fused, R, 1024); break;
+    case 9: put(ws->mask_f, R, 32); break;
+    case 10: put(ws->fmax, B, 1024); break;
+    case 11: put(ws->farg, B, 1024); break;
+    case 12: put(ws->gb1, B, 512); break;
+    case 13: put(ws->h1, R, 512); break;
+    case 14: put(ws->mask1, R, 16); break;
+    case 15: put(ws->h2, R, 256); break;
+    case 16: put(ws->mask2, R, 8); break;
+    case 17: put(ws->logits, R, NCLS); break;
+    case 30: put(ws->g2, R, 256); break;
+    case 31: put(ws->g1, R, 512); break;
+    case 32: put(ws->g1part, B * ceil_div(ws->N, 64), 512); break;
+    case 33: put(ws->g1sum, B, 512); break;
+    case 34: put(ws->gfvec, B, 1024); break;
+    case 35: put(ws->dfeats, R, F); break;
+    case 36: put(ws->gcur, R, GC); break;
+    case 50: need_keep = true; if (ws->keep) put(ws->k_pq + (size_t)e * R * ws->pq_w, R, wpq); break;
+    case 51: need_keep = true; if (ws->keep) put(ws->k_dfh, R, F); break;
+    case 52: need_keep = true; if (ws->keep) put(ws->k_dff, R, F); break;
+    case 53: need_keep = true; if (ws->keep) put(ws->k_dpq + (size_t)e * R * ws->pq_w, R, wpq); break;
+    case 54: need_keep = need_mr = true; if (ws->keep && mr) put(ws->k_gz + (size_t)e * R * GC, R, GC); break;
+    case 55: need_keep = true; if (ws->keep) put(ws->k_state + (size_t)e * R * F, R, alt ? F : GC); break;
+    case 56: need_keep = true; if (ws->keep) put(ws->k_dx0, R, 9); break;
+    default: known = false;
+    }
+    if (!known) { set_error("psg_gcn_debug_ptr: unknown buffer code what=%d", what); return nullptr; }
+    if (!p) {
+        set_error("psg_gcn_debug_ptr: buffer code %d needs %s", what, need_keep && !ws->keep ? "psg_gcn_debug_keep on" : "conv = mr");
+        return nullptr;
+    }
+    (void)need_mr;
+    if (rows_out) *rows_out = r;
+    if (cols_out) *cols_out = c;
+    return p;
+}
+
+extern "C" int psg_gcn_debug_keep(psg_gcn_ws *ws, int on)
+{
+    PSG_REQUIRE(ws, "psg_gcn_debug_keep: null workspace");
+    if (!on) {
+        if (ws->keep) PSG_CHECK_HIP(hipFree(ws->keep));
+        ws->keep = nullptr;
+        return PSG_OK;
+    }
+    if (ws->keep) return PSG_OK;
+    PSG_CHECK_HIP(hipSetDevice(ws->ctx->device));
+    const size_t R = (size_t)ws->B * ws->N, nb = ws->cfg.n_blocks, F = ws->fdim;
+    size_t bytes = 0;
+    const int rc = carve_arena(&ws->keep, &bytes, "psg_gcn_debug_keep", [&](Bump &bp) {
+        ws->k_pq = bp.take<float>(nb * R * ws->pq_w); ws->k_dpq = bp.take<float>(nb * R * ws->pq_w);
+        ws->k_gz = bp.take<float>(nb * R * GC); ws->k_state = bp.take<float>(nb * R * F);
+        ws->k_dfh = bp.take<float>(R * F); ws->k_dff = bp.take<float>(R * F); ws->k_dx0 = bp.take<float>(R * 9);
+    });
+    if (rc) ws->keep = nullptr;
+    return rc;
+}
+
+int gcn_keep_refuses(const psg_gcn_ws *ws, const char *who)
+{
+    if (!ws->keep) return PSG_OK;
+    set_error("%s: psg_gcn_debug_keep is on for this workspace (a replayed graph would not make the per-block copies)", who);
+    return PSG_ERR_STATE;
 }
 
 extern "C" int psg_gcn_backward(psg_gcn_model *m, psg_gcn_ws *ws, const float *dlogits, float *dx0_out,
@@ -640,6 +744,7 @@ extern "C" int psg_gcn_backward(psg_gcn_model *m, psg_gcn_ws *ws, const float *d
         GemmArgs a = gemm_args(ws->g1, 512, m->wp1b_st, 512, ws->dfeats, F, (int)R, 512, F);
         if ((rc = launch_gemm<2, 2, EPI_LINEAR, false>(a, st))) return rc;
     }
+    if (ws->keep) PSG_CHECK_HIP(hipMemcpyAsync(ws->k_dfh, ws->dfeats, R * F * 4, hipMemcpyDeviceToDevice, st));   // psg_gcn_debug_keep
     // fusion half: gradient of the broadcast vector = (s1 * W1a)^T . (column sum of g1), then back through the
     // global max (one point per channel), ReLU/BN of the fusion block and its 1x1 conv: 1024 scaled row adds
     {
@@ -655,6 +760,7 @@ extern "C" int psg_gcn_backward(psg_gcn_model *m, psg_gcn_ws *ws, const float *d
     hipLaunchKernelGGL(fusion_bwd_kernel, dim3(1024, B, ceil_div(F, 256)), dim3(256), 0, st, ws->gfvec, ws->farg, ws->mask_f, m->sf, m->wf, F,
                        1024, N, ws->dfeats);
     PSG_LAUNCH_CHECK();
+    if (ws->keep) PSG_CHECK_HIP(hipMemcpyAsync(ws->k_dff, ws->dfeats, R * F * 4, hipMemcpyDeviceToDevice, st));
     if (m->cfg.block != PSG_GCN_BLOCK_RES || m->cfg.conv != PSG_GCN_CONV_EDGE) return backward_alt(m, ws, dx0_out, st);
     // backbone in reverse: G_e = d/d x_e
     PSG_CHECK_HIP(hipMemcpy2DAsync(ws->gcur, GC * 4, ws->dfeats + (size_t)(m->cfg.n_blocks - 1) * GC, (size_t)F * 4, GC * 4, R,
@@ -673,6 +779,11 @@ extern "C" int psg_gcn_backward(psg_gcn_model *m, psg_gcn_ws *ws, const float *d
         GemmArgs a = gemm_args(dpq, 2 * GC, L.wcat_t, 2 * GC, e > 0 ? ws->gcur : dx0_out, e > 0 ? GC : P.ld, (int)R, 2 * GC, P.C);
         if (e > 0) { a.accumulate = 1; a.addend = ws->dfeats + P.tgt_off; a.ld_add = F; }
         if ((rc = launch_gemm<4, 1, EPI_LINEAR, false>(a, st))) return rc;
+        if (ws->keep) {   // psg_gcn_debug_keep: this block's [dP | dQ], then gcur (G_{e-1}; unchanged by the head), then dx0
+            PSG_CHECK_HIP(hipMemcpyAsync(ws->k_dpq + (size_t)e * R * ws->pq_w, dpq, R * 2 * GC * 4, hipMemcpyDeviceToDevice, st));
+            PSG_CHECK_HIP(hipMemcpyAsync(ws->k_state + (size_t)e * R * F, ws->gcur, R * GC * 4, hipMemcpyDeviceToDevice, st));
+            if (e == 0) PSG_CHECK_HIP(hipMemcpyAsync(ws->k_dx0, dx0_out, R * 9 * 4, hipMemcpyDeviceToDevice, st));
+        }
     }
     return PSG_OK;
 }

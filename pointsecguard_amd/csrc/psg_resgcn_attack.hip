@@ -79,6 +79,7 @@ extern "C" int psg_gcn_nb_attack(psg_gcn_model *m, psg_gcn_ws *ws, const float *
 {
     PSG_REQUIRE(m && ws && images && labels && adv_out, "psg_gcn_nb_attack: null argument");
     PSG_REQUIRE(iters > 0, "psg_gcn_nb_attack: iters must be positive");
+    if (int rc = gcn_keep_refuses(ws, "psg_gcn_nb_attack")) return rc;
     return gcn_nb_loop(m, ws, images, labels, kGcnFieldColour, eps, alpha, 0.f, 0.f, iters, adv_out, (hipStream_t)stream);
 }
 
@@ -92,6 +93,7 @@ extern "C" int psg_gcn_nb_attack_field(psg_gcn_model *m, psg_gcn_ws *ws, const f
                 "psg_gcn_nb_attack_field: field %d is neither coord (%d) nor both (%d); colours alone are psg_gcn_nb_attack", field,
                 PSG_NU_FIELD_COORD, PSG_NU_FIELD_BOTH);
     PSG_REQUIRE(gcn_same_cfg(m, ws), "psg_gcn_nb_attack_field: model / workspace configuration mismatch");
+    if (int rc = gcn_keep_refuses(ws, "psg_gcn_nb_attack_field")) return rc;
     return gcn_nb_loop(m, ws, images, labels, field, eps, alpha, coord_eps, coord_alpha, iters, adv_out, (hipStream_t)stream);
 }
 
@@ -159,7 +161,7 @@ template <typename Args> static int gcn_nu_check(const Args *a, const char *who)
     PSG_REQUIRE(!a->use_target || (a->target >= 0 && a->target < NCLS), "%s: target class %d out of range", who, a->target);
     PSG_REQUIRE(a->neighbour > 0 && a->neighbour <= 16 && a->N <= 8192, "%s: neighbour=%d (1..16) / N=%d (<= 8192) out of range", who,
                 a->neighbour, a->N);
-    return PSG_OK;
+    return gcn_keep_refuses(a->ws, who);
 }
 
 // Runs or replays the window.  What a captured window is valid for: the argument block without what the device rows carry

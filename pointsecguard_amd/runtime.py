@@ -852,3 +852,27 @@ class GCNWorkspace(_Handle):
         out = torch.empty(self.batch, self.n_point, 64 * self.n_blocks, dtype=torch.float32, device=self.device)
         _hip_memcpy_d2d(out.data_ptr(), src, out.numel() * 4)
         return out
+
+    # psg_gcn_debug_ptr codes (include/psg.h); 50 and above are the kept copies of debug_keep(True)
+    DEBUG = {"xyz": 0, "feats": 1, "nbr": 2, "arg": 3, "arg_mr": 4, "mask_mr": 5, "sq": 6, "xp": 7, "fused": 8, "mask_f": 9,
+             "fmax": 10, "farg": 11, "gb1": 12, "h1": 13, "mask1": 14, "h2": 15, "mask2": 16, "logits": 17,
+             "g2": 30, "g1": 31, "g1part": 32, "g1sum": 33, "gfvec": 34, "dfeats": 35, "gcur": 36,
+             "k_pq": 50, "k_dfeats_head": 51, "k_dfeats_fusion": 52, "k_dpq": 53, "k_gz": 54, "k_state": 55, "k_dx0": 56}
+    _DEBUG_DTYPE = {2: torch.int32, 3: torch.uint8, 4: torch.uint8, 5: torch.int32, 9: torch.int32, 11: torch.int32,
+                    14: torch.int32, 16: torch.int32}
+
+    def debug(self, what, block=0):
+        """A workspace buffer by name (tests): a [rows, cols] copy taken on the current stream; float32 except the arg bytes
+        (uint8), the ReLU bit words and the index tables (int32).  Validity windows and layouts: include/psg.h."""
+        code = self.DEBUG[what]
+        rows, cols = ctypes.c_int(), ctypes.c_int()
+        src = _lib.load().psg_gcn_debug_ptr(self.handle, code, int(block), ctypes.byref(rows), ctypes.byref(cols))
+        if not src:
+            raise _lib.PsgError("psg_gcn_debug_ptr(%s, %d): %s" % (what, block, _lib.load().psg_last_error().decode()))
+        out = torch.empty(rows.value, cols.value, dtype=self._DEBUG_DTYPE.get(code, torch.float32), device=self.device)
+        _hip_memcpy_d2d(out.data_ptr(), src, out.numel() * out.element_size())
+        return out
+
+    def debug_keep(self, on=True):
+        """psg_gcn_debug_keep: per-block copies of the buffers the forward / backward loops overwrite (the k_* names of debug)."""
+        _lib.call("psg_gcn_debug_keep", self.handle, 1 if on else 0)

@@ -16,6 +16,9 @@
   PSG_PN2_PGD_FUSE=0  PointNet++ attack loop: the PGD step as a launch of its own behind the gradient's last gather (rounds 1-4)
   PSG_GCN_EDGE_BWD=atomic  ResGCN: the EdgeConv max-pass backward scatters with float atomics (rounds 1-3) instead of the
                      inverse-graph gather
+  PSG_GEMM_SMALL_BELOW=0  every GEMM on its wide workgroup tiles (<2,2>, <4,1>) instead of 64 x 64 tiles for small grids: the
+                     tile shape must not change the k order, so where the launch sites coincide with the default's the results
+                     must be bit-equal (the stage tests print a hash of logits and, for conv = edge, dx0)
 
 The switches are read once per process, so each case runs the relevant parity tests in ONE child interpreter with the
 switch set and the launch tracer on (PSG_TRACE_SYNC=1 prints the site of every launch - the source line where the launch is
@@ -39,6 +42,7 @@ def child(test_file, keyword, extra_env):
     env.pop("PSG_RLA_ATOMICS", None)
     env.pop("PSG_GCN_PQ_FUSION", None)
     env.pop("PSG_GCN_EDGE_BWD", None)
+    env.pop("PSG_GEMM_SMALL_BELOW", None)
     env.pop("PSG_PN2_SPLIT", None)
     env.pop("PSG_RLA_NO_DIRECT", None)
     env.pop("PSG_RLA_NO_FUSE16", None)
@@ -55,6 +59,9 @@ def child(test_file, keyword, extra_env):
     return out, sites
 
 
+_BASE = {}
+
+
 @pytest.mark.parametrize("test_file,keyword,switch", [
     ("test_gpu_parity.py", "forward_vs_reference or backward_vs_reference or forward_backward_vs_oracle_batch", "PSG_FP1_WAVE"),
     ("test_randla_net.py", "forward_backward_vs_oracle or bim_attack_vs_oracle", "PSG_RLA_ATOMICS"),
@@ -66,6 +73,10 @@ def child(test_file, keyword, extra_env):
     ("test_randla_stages.py", "(forward_stages or backward_stages) and n8704", "PSG_RLA_NO_DIRECT"),
     ("test_gpu_resgcn28.py", "not knn_on_reference_features", "PSG_GCN_PQ_FUSION"),
     ("test_gpu_resgcn.py", "forward_backward or nb_attack", "PSG_GCN_EDGE_BWD=atomic"),
+    # the ResGCN stage-by-stage float64 checks at ragged, multi-room shapes (288 and 400 rows, all six configurations)
+    ("test_gpu_gcn_stages.py", "every_stage and (b3n96 or b2n200)", "PSG_GCN_PQ_FUSION"),
+    ("test_gpu_gcn_stages.py", "every_stage and (b3n96 or b2n200)", "PSG_GCN_EDGE_BWD=atomic"),
+    ("test_gpu_gcn_stages.py", "every_stage and (b3n96 or b2n200)", "PSG_GEMM_SMALL_BELOW=0"),
     ("test_gpu_parity.py", "forward_vs_reference or backward_vs_reference or forward_backward_vs_oracle_batch or nb_attack_steps_vs_reference",
      "PSG_PN2_SPLIT=0"),
     ("test_gpu_parity.py", "forward_vs_reference or backward_vs_reference or forward_backward_vs_oracle_batch or nb_attack_steps_vs_reference",
@@ -80,12 +91,20 @@ def child(test_file, keyword, extra_env):
      "PSG_PN2_PGD_FUSE=0"),
 ])
 def test_switch_selects_other_kernels_with_the_same_parity(test_file, keyword, switch):
-    base, base_sites = child(test_file, keyword, {})
+    if (test_file, keyword) not in _BASE:                       # the default child of a (file, keyword) runs once
+        _BASE[test_file, keyword] = child(test_file, keyword, {})
+    base, base_sites = _BASE[test_file, keyword]
     assert base.returncode == 0, base.stdout[-3000:]
     name, _, value = switch.partition("=")
     alt, alt_sites = child(test_file, keyword, {name: value or "1"})
     assert alt.returncode == 0, alt.stdout[-3000:]
     assert " passed" in alt.stdout and "skipped" not in alt.stdout.splitlines()[-1]
+    if name == "PSG_GEMM_SMALL_BELOW" and base_sites and alt_sites == base_sites:
+        # the same launch sites with other tile shapes: the k order is the same, so the results are bit-equal
+        hashes = [re.findall(r"hash (\S+ \S+ [0-9a-f]{16})", o.stdout) for o in (base, alt)]
+        print("\n".join(hashes[1]))
+        assert len(hashes[0]) >= 12 and hashes[0] == hashes[1], (hashes[0], hashes[1])
+        return
     assert base_sites and alt_sites and alt_sites != base_sites, (switch, sorted(alt_sites ^ base_sites))
 
 
